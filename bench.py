@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the Rater hot path on MI355X (contract: see the task statement).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 N = 1: runs in-process.  N > 1: the driver launches this file under
 `python -m torch.distributed.run --nproc-per-node N ...`; every rank owns one GPU
@@ -14,7 +14,9 @@ forward + backward + gradient all-reduce + clip/Adam, bf16 MFMA operands with f3
 accumulation and f32 master weights, dropout on.  Inputs (the 10M-character
 synthetic corpus) are resident in HBM before the timed region.
 
-Rank 0 prints ONE JSON line.  Besides the contract keys it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and reports them (`value`, `ms_per_step`);
+--dump-outputs DIR then writes what the last timed step computed (dump_outputs below).  With --full the line also
+carries the blocks below (each null in a plain run; --no-* skip some of them)
   roofline      the dominant kernel (the persistent backward scan of one layer) against the
                 dense bf16 MFMA peak: algorithmic FLOPs per launch / mean launch time,
                 timed with HIP events on the engine's stream in an extra traced step.
@@ -50,6 +52,7 @@ DEPTH, WIDTH, LENGTH, VOC, N_CTX = 2, 512, 256, 256, 1
 CORPUS = 10_000_000
 MFMA_BF16_PEAK_TFLOPS = 2500.0     # dense bf16, MI355X_MICROARCH.md
 HBM_PEAK_GBS = 8000.0
+DUMP_BYTES = 60 << 20              # --dump-outputs: array bytes, under 64 MB with the .npy headers
 
 
 def flops_fwd_per_char(depth=DEPTH, width=WIDTH, voc=VOC, n_ctx=N_CTX):
@@ -281,6 +284,25 @@ def incremental_leg(lm, device, depth, width, n_ctx, N, S, seed=3):
             "mfma_frac": N * flops_fwd_per_char(depth, width, VOC, n_ctx) / (gpu_us * 1e-6) / 1e12 / MFMA_BF16_PEAK_TFLOPS}
 
 
+def dump_outputs(out_dir, weights, states, loss):
+    """Writes what a caller of the timed training step holds after its last step as out_dir/<name>.npy: the f32 master
+    weights in Keras shapes (E, Ctx0, K0, U0, b0, ...), `states` [B][2L][W] f32 (the streams' carried h and c) and `loss`
+    f64 (CE, accuracy, regulariser as read back after the timed steps).  When the states would take the files past
+    DUMP_BYTES, the rows of a fixed seeded sample of the streams (in stream order) stand for them.
+    The inputs of a run depend on its arguments only.  The split-K weight-gradient GEMMs add in f32 atomics, so two runs
+    agree to that rounding after one step and drift further apart with every step after it: compare short runs."""
+    arrays = {k: np.asarray(v, dtype=np.float32) for k, v in weights.items()}
+    arrays["loss"] = np.asarray(loss, dtype=np.float64)
+    states = np.asarray(states, dtype=np.float32)
+    room = (DUMP_BYTES - sum(a.nbytes for a in arrays.values())) // states[0].nbytes
+    if room < len(states):
+        states = states[np.sort(np.random.default_rng(0).choice(len(states), room, replace=False))]
+    arrays["states"] = states
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -288,6 +310,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--streams", type=int, default=int(os.environ.get("KL_BENCH_STREAMS", "3072")),
                     help="stateful streams per GPU (B)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the roofline, CPU baselines, incremental step, rating window, "
+                         "other shapes and end-to-end blocks")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
     ap.add_argument("--no-end-to-end", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-incremental", action="store_true")
@@ -363,11 +389,13 @@ def main():
     ce, acc, reg = lm.read_loss()
     chars = args.steps * B * T * world
     value = chars / elapsed
+    if args.dump_outputs and rank == 0:           # (before the --full legs: they step and re-prepare the model)
+        dump_outputs(args.dump_outputs, lm.get_weights(), lm.get_states(), (ce, acc, reg))
 
     # ---- roofline leg: one traced step, HIP events around the cell-step launches
     import ctypes as C
     roofline = None
-    if rank == 0:
+    if rank == 0 and args.full:
         hipabi.check(lm.lib.kl_trace_enable(lm.handle, 1))
         # (five traced steps, every layer's scan launch bracketed: 10 launches per direction at depth 2 -- the figure below is
         # their AVERAGE, comparable with rocprofv3's per-kernel average over the same command)
@@ -416,7 +444,7 @@ def main():
     # ---- incremental rescoring: cfg3 (1024 hypotheses x 512 chars) and the reference's batch cap (128 hypotheses),
     # split precision; every rank runs it on its own GPU (independent hypothesis sets, no collective), values summed
     incremental = None
-    if not args.no_incremental:
+    if args.full and not args.no_incremental:
         lm.prepare(hipabi.KL_PREC_SPLIT)
         legs = {}
         for N, S in ((1024, 512), (128, 512), (32, 512)):
@@ -447,7 +475,7 @@ def main():
     # ---- the step as a beam search sees it (rating.py:809-826): one call per character, the GPU idle in between, wall time
     # from the call to the probabilities in host memory; and Rater.rate_best itself on a synthetic 600-edge page lattice
     beam = None
-    if not args.no_incremental and rank == 0 and world == 1:
+    if args.full and not args.no_incremental and rank == 0 and world == 1:
         try:
             import importlib.util
             def _tool(name):
@@ -468,7 +496,7 @@ def main():
     # ---- rating windows (rate / rate2 / test): the stateful windowed forward in split precision with probabilities out,
     # at the reference's batching (1 stream x 256 chars, rating.py:490) and at 64 streams; rank 0 reports its own GPU
     rating = None
-    if not args.no_incremental:
+    if args.full and not args.no_incremental:
         lm.prepare(hipabi.KL_PREC_SPLIT)
         rating = {}
         for Br in (1, 64):
@@ -498,7 +526,7 @@ def main():
     # ---- the other shapes SURVEY.md 8(d) asks for, one GPU each (N = 1 runs only: no collective in them)
     small_batch = None
     cfg5 = None
-    if rank == 0 and world == 1 and not args.no_extra_shapes:
+    if args.full and rank == 0 and world == 1 and not args.no_extra_shapes:
         lm._ws = None                      # (the 3072-stream workspace goes back to the allocator first)
         lm._ws_key = None
         torch.cuda.empty_cache()
@@ -549,7 +577,7 @@ def main():
     # its README example width 64): training at 1024 streams and at the reference's batching
     ref_models = None
     other_streams = None
-    if rank == 0 and world == 1 and not args.no_extra_shapes:
+    if args.full and rank == 0 and world == 1 and not args.no_extra_shapes:
         ref_models = {}
         for Wm in (128, 64):
             try:
@@ -585,7 +613,7 @@ def main():
     # ---- end to end: Rater.train over synthetic files (rank 0, one GPU): what the Python above the ABI costs
     end_to_end = None
     # (N = 1 only: Rater.train would see the process group and start collectives the other ranks are not in)
-    if rank == 0 and world == 1 and not args.no_end_to_end:
+    if args.full and rank == 0 and world == 1 and not args.no_end_to_end:
         try:
             end_to_end = end_to_end_leg(B)
         except Exception as err:      # informative only
@@ -593,7 +621,7 @@ def main():
 
     cpu = None
     cpu_torch = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:      # (reported at N = 1 only)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:      # (reported at N = 1 only)
         cpu = cpu_baseline()
         try:
             cpu_torch = cpu_baseline_torch()

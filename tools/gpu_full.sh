@@ -9,7 +9,7 @@ rc=$?
 grep -v amdgpu.ids $OUT/full_tests.log | tail -12
 if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then echo "tests timed out: stopping"; exit $rc; fi
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -v amdgpu.ids
-timeout -k 10 700 python bench.py > $OUT/full_bench.json 2> $OUT/full_bench.err
+timeout -k 10 700 python bench.py --full > $OUT/full_bench.json 2> $OUT/full_bench.err
 rc2=$?
 python - <<'PY'
 import json

@@ -28,7 +28,7 @@ def load(d, counter):
 fetch = load(sys.argv[1], 'FETCH_SIZE')
 write = load(sys.argv[2], 'WRITE_SIZE')
 out = {"command": "rocprofv3 --pmc {FETCH_SIZE|WRITE_SIZE} --kernel-trace --output-format csv -- python3 bench.py "
-                  "--steps 3 --warmup 1 --no-cpu-baseline --no-incremental (two separate passes)",
+                  "--full --steps 3 --warmup 1 --no-cpu-baseline --no-incremental (two separate passes)",
        "unit_note": "FETCH_SIZE / WRITE_SIZE are KiB per dispatch; on gfx950 FETCH_SIZE counts 64 B per 128-B request for "
                     "wide coalesced reads (MI355X_MICROARCH.md, HBM) -> doubled in hbm_bytes_per_launch",
        "config": sys.argv[4] if len(sys.argv) > 4 else "", "kernels": {}}
