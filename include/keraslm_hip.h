@@ -12,6 +12,7 @@
  *                                                            (layout: kl_param_layout) + kl_prepare
  *   model.predict_generator (windows), :516                  kl_forward_window (tgt = NULL)
  *   model.evaluate_generator, :490                           kl_forward_window (tgt != NULL)
+ *   Rater.rate, :493-529, for many texts at once             kl_rate_window (one text per stream, target-only delivery)
  *   model.predict_on_batch, stateful (1,1) step, :566        kl_forward_window with T = 1
  *   model.predict_on_batch, incremental + states, :631       kl_step_batch
  *   model.fit_generator -> train_on_batch, :292-298          kl_train_window + kl_adam_step
@@ -119,6 +120,22 @@ int kl_set_loss_rows(kl_handle* h, int rows);
 
 int kl_forward_window(kl_handle* h, int B, int T, const int32_t* idx, const int32_t* ctx, const int32_t* tgt,
                       float* states, float* probs, float* loss_acc, void* ws, size_t ws_bytes, void* stream);
+
+/* Rating windows with target-only delivery (rating.py:493-529 `rate`, for many texts at once: one text per stream).
+ * The recurrence and the logits are those of kl_forward_window on an inference-size workspace
+ * (kl_window_workspace_bytes(.., training = 0)) in the handle's current precision, stateful window mode
+ * (KL_ERR_STATE after kl_set_window_mode(h, 1)); states is advanced in the same way.  What is delivered differs:
+ *   tprob  (device [B][T], or NULL)  tprob[b][t] = softmax(logits[b][t])[tgt[b][t]] where tgt >= 0 (0 is a valid target:
+ *          the unmapped character), 0.0f where tgt < 0 (padded tail, dummy stream);
+ *   bits   (device f64 [B], or NULL) bits[b] += sum over the positions t of stream b with tgt >= 0 of
+ *          -log2(max(tprob[b][t], 1e-99)) (the clamp of rating.py:531-576), summed in f64 in a fixed order: two calls
+ *          on the same inputs add bit-identical amounts;
+ *   status (device f32[4], or NULL)  status[3] += 1 if a scan hand-off timed out (as loss_acc[3] of kl_forward_window).
+ * No [B][T][V] array is written for the caller: 4 bytes leave the output layer per position instead of 4 V.  tgt may be
+ * NULL only if tprob and bits both are (the states advance, nothing else).  ws_bytes >= kl_rate_workspace_bytes(h, B, T). */
+size_t kl_rate_workspace_bytes(const kl_handle* h, int B, int T);
+int kl_rate_window(kl_handle* h, int B, int T, const int32_t* idx, const int32_t* ctx, const int32_t* tgt,
+                   float* states, float* tprob, double* bits, float* status, void* ws, size_t ws_bytes, void* stream);
 
 /* One training batch, forward + backward (rating.py:292-298 -> train_on_batch):
  * writes the gradient of (mean CE + embedding regularisers, rating.py:187-246)

@@ -1183,6 +1183,20 @@ size_t kl_window_workspace_bytes(const kl_handle* h, int B, int T, int training)
   return carve_window(h, nullptr, B, T, training, nullptr);
 }
 
+// recurrence + output layer of an inference window (the non-training workspace layout): advances states, leaves the
+// logits time-major in w.logits.  Shared by kl_forward_window and kl_rate_window, which differ in what they make of them.
+static int window_logits(kl_handle* h, int B, int T, const int32_t* idx, const int32_t* ctx, float* states, WindowWs& w,
+                         hipStream_t s) {
+  const int W = h->cfg.width, V = h->cfg.voc_size, L = h->cfg.depth;
+  KL_TRY(kl_zero_async(w.scan_status, (4 + 256) * sizeof(unsigned), s));
+  KL_TRY(forward_impl(h, B, T, idx, ctx, states, nullptr, 0, w, s));
+  KlOperand op;
+  memset(&op, 0, sizeof(op));
+  op.A = (float*)w.H[L - 1] + (size_t)B * W; op.lda = W; op.a_is_f32 = 1;
+  op.WT_hi = h->d.E_hi; op.WT_lo = h->precision == 3 ? h->d.E_lo : nullptr; op.ldw = W; op.K = W;
+  return kl_launch_thin_gemm(&op, B * T, V, w.logits, V, nullptr, h->precision, s);
+}
+
 static int forward_window_body(kl_handle* h, int B, int T, const int32_t* idx, const int32_t* ctx, const int32_t* tgt,
                       float* states, float* probs, float* loss_acc, void* ws, size_t ws_bytes, void* stream) {
   if (!h || !idx || !states || !ws || B < 1 || T < 1) return KL_ERR_ARG;
@@ -1214,13 +1228,7 @@ static int forward_window_body(kl_handle* h, int B, int T, const int32_t* idx, c
     return hip_ok(hipGetLastError());
   }
   if (ws_bytes < carve_window(h, ws, B, T, 0, &w)) return KL_ERR_WORKSPACE;
-  KL_TRY(kl_zero_async(w.scan_status, (4 + 256) * sizeof(unsigned), s));
-  KL_TRY(forward_impl(h, B, T, idx, ctx, states, nullptr, 0, w, s));
-  KlOperand op;
-  memset(&op, 0, sizeof(op));
-  op.A = (float*)w.H[L - 1] + (size_t)B * W; op.lda = W; op.a_is_f32 = 1;
-  op.WT_hi = h->d.E_hi; op.WT_lo = h->precision == 3 ? h->d.E_lo : nullptr; op.ldw = W; op.K = W;
-  KL_TRY(kl_launch_thin_gemm(&op, B * T, V, w.logits, V, nullptr, h->precision, s));
+  KL_TRY(window_logits(h, B, T, idx, ctx, states, w, s));
   KL_TRY(kl_launch_softmax_ce(w.logits, V, B * T, V, tgt, B, T, 1.0f / (h->last_only ? (float)B : (float)B * T), nullptr, 0,
                               tgt ? loss_acc : nullptr, w.rowstat, 1, s, h->last_only));
   if (probs) {
@@ -2121,6 +2129,45 @@ extern "C" int kl_forward_window(kl_handle* h, int B, int T, const int32_t* idx,
   }));
   if (probs)
     KL_TRY(hip_ok(hipMemcpyAsync(probs, w.s_probs, BT * h->cfg.voc_size * sizeof(float), hipMemcpyDeviceToDevice, s)));
+  return 0;
+}
+
+// ---- rating windows with target-only delivery (rating.py:493-529 `rate`, many texts at once) ----------------
+// The window of kl_forward_window in the inference layout, but what leaves it is one float per position -- the
+// probability of the character that follows -- and/or one f64 sum per stream; the [B][T][V] softmax is never formed.
+// The workspace is the inference window's: its probability staging slot holds the [B][T] picks instead.
+extern "C" size_t kl_rate_workspace_bytes(const kl_handle* h, int B, int T) {
+  if (!h || B < 1 || T < 1) return 0;
+  return carve_window(h, nullptr, B, T, 0, nullptr);
+}
+
+extern "C" int kl_rate_window(kl_handle* h, int B, int T, const int32_t* idx, const int32_t* ctx, const int32_t* tgt,
+                              float* states, float* tprob, double* bits, float* status, void* ws, size_t ws_bytes,
+                              void* stream) {
+  if (!h || !idx || !states || !ws || B < 1 || T < 1) return KL_ERR_ARG;
+  if (h->cfg.n_ctx > 0 && !ctx) return KL_ERR_ARG;
+  if ((tprob || bits) && !tgt) return KL_ERR_ARG;
+  if (!h->precision || h->last_only) return KL_ERR_STATE;      // (one target per window is the stateless graph's: kl_forward_window)
+  hipStream_t s = (hipStream_t)stream;
+  WindowWs w;
+  if (ws_bytes < carve_window(h, ws, B, T, 0, &w)) return KL_ERR_WORKSPACE;
+  const size_t BT = (size_t)B * T;
+  const bool pick = tprob || bits;
+  KL_TRY(hip_ok(hipMemcpyAsync(w.s_idx, idx, BT * sizeof(int), hipMemcpyDeviceToDevice, s)));
+  if (h->cfg.n_ctx > 0)
+    KL_TRY(hip_ok(hipMemcpyAsync(w.s_ctx, ctx, BT * h->cfg.n_ctx * sizeof(int), hipMemcpyDeviceToDevice, s)));
+  if (pick) KL_TRY(hip_ok(hipMemcpyAsync(w.s_tgt, tgt, BT * sizeof(int), hipMemcpyDeviceToDevice, s)));
+  // (baked into the captured launches: states, status, bits and the workspace -- all in the key; tprob is staged)
+  kl_handle::GraphKey key{2, B, T, (tprob ? 1 : 0) | (bits ? 2 : 0), h->precision, states, status, ws, bits, 0};
+  KL_TRY(run_graphed(h, key, s, [&]() {
+    const int V = h->cfg.voc_size;
+    KL_TRY(window_logits(h, B, T, w.s_idx, w.s_ctx, states, w, s));
+    if (pick) KL_TRY(kl_launch_rate_pick(w.logits, V, B * T, V, w.s_tgt, B, T, w.s_probs, s));
+    if (bits) KL_TRY(kl_launch_rate_bits(w.s_probs, w.s_tgt, B, T, bits, s));
+    if (status) hipLaunchKernelGGL(scan_status_kernel, dim3(1), dim3(64), 0, s, w.scan_status, status);
+    return hip_ok(hipGetLastError());
+  }));
+  if (tprob) KL_TRY(hip_ok(hipMemcpyAsync(tprob, w.s_probs, BT * sizeof(float), hipMemcpyDeviceToDevice, s)));
   return 0;
 }
 

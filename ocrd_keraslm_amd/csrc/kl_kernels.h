@@ -321,6 +321,13 @@ int kl_launch_ctx_grads(const float* Ctx, const float* K0rows, long ldk, int R, 
                         float* gK, long ldg, float* gCtx, hipStream_t stream);
 int kl_launch_rows_tm_to_bm(const float* in, long ld_in, float* out, int B, int T, int V, hipStream_t stream);
 
+// ---- rate_pick.hip ------------------------------------------------------
+// tprob[b][t] = softmax(logits[t*B + b])[tgt[b][t]] (0 where tgt < 0); the logits (time-major rows) are left as they are
+int kl_launch_rate_pick(const float* logits, long ld, int rows, int V, const int* tgt, int B, int T, float* tprob,
+                        hipStream_t stream);
+// bits[b] += sum_t -log2(max(tprob[b][t], 1e-99)) over the positions with tgt >= 0, f64, fixed order
+int kl_launch_rate_bits(const float* tprob, const int* tgt, int B, int T, double* bits, hipStream_t stream);
+
 // ---- step_small.hip -----------------------------------------------------
 // one LSTM cell step of a layer for n hypotheses with pool slots (KL_SMALL_STEP_N <= n < KL_BIG_STEP_N), see inc_cell_kernel
 #define KL_SMALL_STEP_N 16

@@ -84,7 +84,11 @@ class HipLM:
         self.loss_acc = torch.zeros(4, dtype=torch.float32, device=self.device)
         self._ws = None
         self._ws_key = None
-        self.states = None          # [B][2L][W] implicit state of the stateful streams
+        self.rate_bits = None       # [B] f64: bits per stream accumulated by rate_window
+        self._rate_status = None
+        self._rate_ws = None
+        self._rate_ws_key = None
+        self.states = None         # [B][2L][W] implicit state of the stateful streams
         self.pool = None            # [slots][2L][W] explicit states of hypotheses
         self.max_streams_per_launch = 0      # 0: what the kernels address (train_window splits larger batches into groups)
         self._part_grads = None
@@ -362,6 +366,72 @@ class HipLM:
                 self.loss_acc[3] = 0.0        # one timed-out window must not fail every later call
                 raise hipabi.KlError("persistent scan hand-off timed out (kl_forward_window)")
         return probs
+
+    # ------------------------------------------------------------------ rating windows, target-only delivery
+    def rate_window(self, idx, ctx, tgt, want_probs=True):
+        """One window of B independent stateful streams as `forward_window` runs it, delivering per position only the
+        probability of the target: idx [B,T], ctx [B,T,n_ctx], tgt [B,T] (< 0: no target, probability 0).
+        Returns a DEVICE tensor [B,T] f32 (None without want_probs) and adds -log2(max(p, 1e-99)) over each stream's
+        valid positions to the f64 accumulator `rate_bits` [B] (rate_bits_read).  Nothing is synchronised here: a timed-out
+        scan hand-off surfaces as KlError in rate_bits_read / rate_status_check."""
+        torch = self.torch
+        if self.precision == 0:
+            raise hipabi.KlError("weights not prepared")
+        with self._launch():
+            idx_d = self._dev_i32(idx)
+            B, T = idx_d.shape
+            ctx_d = self._dev_i32(ctx) if self.n_ctx else None
+            tgt_d = self._dev_i32(tgt)
+            if self.states is None or self.states.shape[0] != B:
+                self.reset_states(B)
+            if self.rate_bits is None or self.rate_bits.shape[0] != B:
+                self.rate_bits = torch.zeros(B, dtype=torch.float64, device=self.device)
+            if self._rate_status is None:
+                self._rate_status = torch.zeros(4, dtype=torch.float32, device=self.device)
+            tprob = torch.empty((B, T), dtype=torch.float32, device=self.device) if want_probs else None
+            parts = self._rating_groups(B)
+            ws = self._rate_workspace(max(b1 - b0 for b0, b1 in parts), T)
+            for b0, b1 in parts:       # (streams are independent: more than one launch sequence takes run as groups)
+                hipabi.check(self.lib.kl_rate_window(
+                    self.handle, b1 - b0, T, _ptr(idx_d[b0:b1]), _ptr(ctx_d[b0:b1] if ctx_d is not None else None),
+                    _ptr(tgt_d[b0:b1]), _ptr(self.states[b0:b1]), _ptr(tprob[b0:b1] if tprob is not None else None),
+                    _ptr(self.rate_bits[b0:b1]), _ptr(self._rate_status), _ptr(ws), ws.numel(), self._stream()),
+                    "kl_rate_window")
+        return tprob
+
+    def _rate_workspace(self, B, T):
+        key = (B, T)
+        if self._rate_ws_key != key:
+            n = self.lib.kl_rate_workspace_bytes(self.handle, B, T)
+            self._rate_ws = None
+            self._rate_ws = self.torch.empty(n, dtype=self.torch.uint8, device=self.device)
+            self._rate_ws_key = key
+        return self._rate_ws
+
+    def rate_status_check(self):
+        """raise if a scan hand-off timed out in a rate_window call since the last check (synchronises)"""
+        if self._rate_status is not None and float(self._rate_status[3].item()) != 0.0:
+            self._rate_status.zero_()        # one timed-out window must not fail every later call
+            raise hipabi.KlError("persistent scan hand-off timed out (kl_rate_window)")
+
+    def rate_bits_take(self, rows):
+        """the accumulated bits of these streams as a DEVICE tensor (f64), the streams' accumulators zeroed; no synchronisation"""
+        torch = self.torch
+        with self._launch():
+            r = torch.as_tensor(np.asarray(rows, dtype=np.int64), device=self.device)
+            out = self.rate_bits[r]
+            self.rate_bits[r] = 0
+        return out
+
+    def rate_bits_read(self, reset=True):
+        """bits [B] (numpy f64) accumulated per stream by rate_window since the last reset"""
+        self.rate_status_check()
+        if self.rate_bits is None:
+            return np.zeros(0, dtype=np.float64)
+        v = self.rate_bits.detach().cpu().numpy().copy()
+        if reset:
+            self.rate_bits.zero_()
+        return v
 
     def draw_dropout_masks(self, B):
         """Inverted-dropout keep masks [L][B][W], time-constant per window (rating.py:146-152)."""

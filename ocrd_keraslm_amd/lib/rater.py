@@ -12,6 +12,9 @@ Differences that are deliberate:
     in lockstep per GPU.  1 reproduces the reference's batch_size=1 stateful
     training (rating.py:90-92); larger values are the data-parallel capability
     north_star asks for (each stream has its own carried state and reset points).
+  * `rate_batch` (new): `rate` for many independent texts at once, up to `streams`
+    of them sharing each window call (ratebatch.py); every text is rated from a
+    zero state, as `reset_states(1); rate(text)` would.
   * beam searches keep hypothesis states in a device-resident pool; `Node.state`
     is then a `StateRef`.  `predict()` called directly still takes and returns
     the reference's list-of-arrays states (rating.py:622-639).
@@ -32,7 +35,7 @@ from random import shuffle
 
 import numpy as np
 
-from . import lattice_beam, modelio, streams, windows
+from . import lattice_beam, modelio, ratebatch, streams, windows
 from .node import Node
 
 PREC_BF16 = 1
@@ -753,6 +756,82 @@ class Rater(object):
             if len(probs) >= size:
                 break
         return probs
+
+    def rate_batch(self, texts, contexts=None, streams=64, want_probs=True):
+        '''Rate many INDEPENDENT texts at once: `probs[i]` (float32 array, one entry per character of the normalised
+        text) is what `self.model.reset_states(1); self.rate(texts[i], contexts[i])` returns, `bits[i]` (float64) is
+        -sum(log2(max(p, 1e-99))) over `probs[i][1:]`; both in input order.  contexts: None, one context list for all
+        texts, or one per text.  Up to `streams` texts share a window call, one per row (ratebatch.py); the HIP engine
+        delivers one float per character (`rate_window`), or -- want_probs=False, which returns (None, bits) -- one
+        double per text.  Unlike `rate`, a batch call neither continues the implicit state of earlier `rate` calls
+        nor leaves one behind: afterwards the state is a freshly reset single row.'''
+        assert self.status > 1
+        assert self.incremental is False
+        texts = list(texts)
+        n = len(texts)
+        if contexts is None or len(contexts) == 0:
+            contexts = [self.underspecify_contexts()] * n
+        elif isinstance(contexts[0], (int, np.integer)):
+            contexts = [list(contexts)] * n
+        else:
+            assert len(contexts) == n, "one context list per text"
+            contexts = [list(c) if (c is not None and len(c)) else self.underspecify_contexts() for c in contexts]
+        self._ensure_precision()
+        lm = self.model
+        bits = np.zeros(n, dtype=np.float64)
+        if not self.stateful:
+            # (the stateless rater's windows are batches of 128 already: the loop itself)
+            probs = []
+            for text, context in zip(texts, contexts):
+                probs.append(np.asarray(self.rate(text, context), dtype=np.float32))
+            bits[:] = [ratebatch.bits_of(p) for p in probs]
+            lm.reset_states(1)
+            return (probs if want_probs else None), bits
+        texts = [windows.normalize(t) for t in texts]
+        ids = [windows.encode(t, self.mapping[0], self._unmapped_input) for t in texts]
+        plan = ratebatch.plan(ids, [windows.clamp_context(c) for c in contexts], self.length, streams)
+        if plan is None:       # (nothing but empty texts and single characters)
+            lm.reset_states(1)
+            return ([np.ones(len(t), dtype=np.float32) for t in texts] if want_probs else None), bits
+        lm.reset_states(plan.B)
+        if hasattr(lm, 'rate_window'):
+            picked = self._run_rate_plan(plan, bits, want_probs)
+        else:
+            # an engine without target-only delivery (the tests' CPU double): the whole softmax and a pick on the host
+            steps = []
+            for s in range(plan.n_calls):
+                x, z, y = plan.call(s)
+                if s and plan.starting(s):
+                    lm.reset_states(rows=plan.reset_rows(s))
+                full = _np(lm.forward_window(x, z, want_probs=True))
+                p = np.take_along_axis(full, np.maximum(y, 0)[:, :, None], axis=2)[:, :, 0]
+                steps.append(np.where(y >= 0, p, 0.0).astype(np.float32))
+            picked = np.stack(steps)
+            bits[:] = [ratebatch.bits_of(plan.text_probs(i, picked)) for i in range(n)]
+        lm.reset_states(1)
+        if not want_probs:
+            return None, bits
+        return [plan.text_probs(i, picked) for i in range(n)], bits
+
+    def _run_rate_plan(self, plan, bits, want_probs):
+        '''the window calls of a ratebatch.Plan on the HIP engine: fills bits (per text) from the device's f64 sums
+        and returns the picked probabilities [n_calls][B][T] (None without want_probs).  One transfer of each at the end.'''
+        lm = self.model
+        lm.rate_bits_read(reset=True)
+        steps, taken = [], []
+        for s in range(plan.n_calls):
+            x, z, y = plan.call(s)
+            if s and plan.starting(s):
+                lm.reset_states(rows=plan.reset_rows(s))
+            p = lm.rate_window(x, z, y, want_probs=want_probs)
+            if want_probs:
+                steps.append(p)
+            ending = plan.ending(s)
+            if ending:       # (a row's sum belongs to the text that ends here: take it, the next text starts from zero)
+                taken.append((ending, lm.rate_bits_take([int(plan.row[i]) for i in ending])))
+        bits[np.concatenate([e for e, _ in taken])] = _np(lm.torch.cat([t for _, t in taken]))
+        lm.rate_status_check()
+        return _np(lm.torch.stack(steps)) if want_probs else None
 
     def rate2(self, text, context=None):
         '''Rate a string one by one (rating.py:531-576): resets the state, feeds one

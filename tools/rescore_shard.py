@@ -3,11 +3,14 @@
 each other through the carried state / traceback, rate.py:150-186, 263-265), so they are dealt round-robin to one
 process per GPU and NOTHING is exchanged between the processes ("no collectives").
 
-  python tools/rescore_shard.py --model model.h5 --gpus 8 [--mode rate|generate] [--out DIR] FILE_OR_DIR ...
+  python tools/rescore_shard.py --model model.h5 --gpus 8 [--mode rate|generate] [--batch N] [--out DIR] FILE_OR_DIR ...
 
 mode rate      per document: Rater.rate over the whole text (context = ceil(year / 10) from `author_title_year.txt`
                names, rating.py:993-999), state reset between documents; writes <out>/<name>.json with the mean
                log2-probability per character and the perplexity
+               --batch N (default 0: one document after the other): a worker rates its documents N at a time as the
+               rows of shared windows (Rater.rate_batch, one document per row, the next one moves up when a row is
+               done) and fetches one number per document from the GPU; same files, same figures
 mode generate  per document: its first line is the prompt; Rater.generate continues it by 64 characters, 3 variants
 
 The parent only starts the workers (each with ONE visible GPU, HIP_VISIBLE_DEVICES) and sums their reports; it never
@@ -40,6 +43,24 @@ def shard(paths, n):
     return [paths[i::n] for i in range(n)]
 
 
+def rate_batched(rater, paths, args):
+    """mode rate with --batch: the documents of a shard as rows of shared windows; returns the characters rated"""
+    from ocrd_keraslm_amd.lib import windows
+    docs = []
+    for path in paths:
+        with open(path, encoding="utf-8") as f:
+            text = windows.normalize(f.read())
+        if len(text) >= 2:
+            docs.append((os.path.basename(path), text, windows.context_from_filename(path)))
+    _, total = rater.rate_batch([d[1] for d in docs], [d[2] for d in docs], streams=args.batch, want_probs=False)
+    for (name, text, _), doc_bits in zip(docs, total):
+        bits = float(doc_bits) / max(len(text) - 1, 1)
+        result = {"document": name, "chars": len(text), "bits_per_char": bits, "perplexity": 2.0 ** bits}
+        with open(os.path.join(args.out, name + ".json"), "w", encoding="utf-8") as f:
+            json.dump(result, f, ensure_ascii=False)
+    return sum(len(d[1]) for d in docs)
+
+
 def worker(args):
     from math import log
     from ocrd_keraslm_amd.lib import Rater, windows
@@ -53,7 +74,10 @@ def worker(args):
     os.makedirs(args.out, exist_ok=True)
     chars = 0
     t0 = time.perf_counter()
-    for path in mine:
+    batched = args.mode == "rate" and args.batch > 0
+    if batched:
+        chars = rate_batched(rater, mine, args)
+    for path in ([] if batched else mine):
         with open(path, encoding="utf-8") as f:
             text = windows.normalize(f.read())
         context = windows.context_from_filename(path)
@@ -83,6 +107,8 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--mode", choices=("rate", "generate"), default="rate")
     ap.add_argument("--out", default="rescored")
+    ap.add_argument("--batch", type=int, default=0,
+                    help="mode rate: documents rated at once per worker, as rows of shared windows (0: one after the other)")
     ap.add_argument("--worker", type=int, default=-1, help=argparse.SUPPRESS)
     ap.add_argument("data", nargs="+")
     args = ap.parse_args()
@@ -106,7 +132,7 @@ def main():
         if same_gpu:
             env["HIP_VISIBLE_DEVICES"] = env["CUDA_VISIBLE_DEVICES"] = "0"
         cmd = [sys.executable, os.path.abspath(__file__), "--model", args.model, "--gpus", str(args.gpus), "--mode", args.mode,
-               "--out", args.out, "--worker", str(g)] + args.data
+               "--batch", str(args.batch), "--out", args.out, "--worker", str(g)] + args.data
         p = subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, text=True)
         if same_gpu:
             # one after the other: the persistent scans assume the GPU to themselves (co-resident workgroups), two
