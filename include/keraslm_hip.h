@@ -16,6 +16,7 @@
  *   model.predict_on_batch, stateful (1,1) step, :566        kl_forward_window with T = 1
  *   model.predict_on_batch, incremental + states, :631       kl_step_batch
  *   model.fit_generator -> train_on_batch, :292-298          kl_train_window + kl_adam_step
+ *   _gen_data_from_files / _vectorize, :977-1158 (training)   kl_assemble_windows (the batches of B streams, on the device)
  *   model.reset_states, :475, :555, callbacks.py:58,69       caller zeroes its state rows
  *
  * Conventions: plain pointers and sizes only; every pointer marked "device" is
@@ -146,6 +147,21 @@ int kl_rate_window(kl_handle* h, int B, int T, const int32_t* idx, const int32_t
 int kl_train_window(kl_handle* h, int B, int T, const int32_t* idx, const int32_t* ctx, const int32_t* tgt,
                     float* states, const float* dropout_masks, float* grads, float* loss_acc, void* ws,
                     size_t ws_bytes, void* stream);
+
+/* Batch assembly of stateful training (rating.py:977-1102 `_gen_data_from_files` -> `_gen_data` -> `_vectorize`, for B
+ * streams at once): the caller keeps the ids of all its texts in one device vector and describes a batch by one row per
+ * stream; one launch writes the three arrays kl_train_window / kl_forward_window read.
+ *   corpus (device int32 [n_corpus])     the ids; a position at or beyond n_corpus reads as 0, no memory is touched there
+ *   plan   (device int64 [B][4 + n_ctx]) per stream: start (position of the window's first id), vlen (how many of the T
+ *          positions hold text: T, or fewer in the tail window of a text), zero_col (input column to zero, -1 = none),
+ *          zero_ctx (context variable to zero, -1 = none), then the stream's n_ctx context values
+ *   idx[b][t]    = t < vlen && t != zero_col ? corpus[start + t] : 0
+ *   tgt[b][t]    = t < vlen ? corpus[start + t + 1] : -1
+ *   ctx[b][t][c] = t < vlen && c != zero_ctx ? context value c : 0     (ctx may be NULL if n_ctx == 0)
+ * (the zero-padded tail of rating.py:1096-1102 and the degraded copies of rating.py:1062-1077).  No handle: the call
+ * depends on no model.  1 <= T <= 1024, 0 <= n_ctx <= 8, B >= 1; KL_ERR_ARG otherwise, and for misaligned pointers. */
+int kl_assemble_windows(const int32_t* corpus, size_t n_corpus, const int64_t* plan, int B, int T, int n_ctx, int32_t* idx,
+                        int32_t* ctx, int32_t* tgt, void* stream);
 
 /* Keras-2.3 Adam with clipvalue (rating.py:178): g <- clip(g,-clip,clip);
  * lr_t = lr*sqrt(1-b2^t)/(1-b1^t); m,v updates; p -= lr_t*m/(sqrt(v)+eps); then

@@ -453,6 +453,26 @@ class HipLM:
             m[0] = 1.0
         return m
 
+    def assemble_windows(self, corpus, plan, T, n_ctx):
+        """The batch of one step from the id corpus in HBM (streams.StreamBatcher): corpus int32 [n] and plan int64
+        [B, 4 + n_ctx] (start, vlen, zero_col, zero_ctx, contexts) on the device -> (idx [B,T], ctx [B,T,n_ctx], tgt [B,T]),
+        int32 device tensors, in one launch (kl_assemble_windows).  It runs on the engine stream: behind the plan's copy
+        on the caller's stream, in front of the train_window / forward_window that consumes the batch."""
+        torch = self.torch
+        B = int(plan.shape[0])
+        if (corpus.dtype != torch.int32 or plan.dtype != torch.int64 or plan.dim() != 2 or plan.shape[1] != 4 + n_ctx
+                or not corpus.is_contiguous() or not plan.is_contiguous()
+                or not corpus.is_cuda or not plan.is_cuda):
+            raise hipabi.KlError("assemble_windows: corpus must be int32 [n], plan int64 [B, 4 + n_ctx], contiguous, on the device")
+        with self._launch():
+            idx = torch.empty((B, T), dtype=torch.int32, device=self.device)
+            tgt = torch.empty((B, T), dtype=torch.int32, device=self.device)
+            ctx = torch.empty((B, T, n_ctx), dtype=torch.int32, device=self.device)
+            hipabi.check(self.lib.kl_assemble_windows(_ptr(corpus), corpus.numel(), _ptr(plan), B, int(T), int(n_ctx),
+                                                      _ptr(idx), _ptr(ctx) if n_ctx else None, _ptr(tgt), self._stream()),
+                         "kl_assemble_windows")
+        return idx, ctx, tgt
+
     def ensure_training_buffers(self):
         torch = self.torch
         if self.grads is None:

@@ -12,6 +12,9 @@ Differences that are deliberate:
     in lockstep per GPU.  1 reproduces the reference's batch_size=1 stateful
     training (rating.py:90-92); larger values are the data-parallel capability
     north_star asks for (each stream has its own carried state and reset points).
+  * `segment_streams` (new, default False): with fewer training (or validation) files than streams, cut the
+    files into contiguous segments on window boundaries and deal segments to the streams instead of files
+    (segments.py); an epoch sees the same windows, the state is reset where a stream enters a segment.
   * `rate_batch` (new): `rate` for many independent texts at once, up to `streams`
     of them sharing each window call (ratebatch.py); every text is rated from a
     zero state, as `reset_states(1); rate(text)` would.
@@ -35,7 +38,7 @@ from random import shuffle
 
 import numpy as np
 
-from . import lattice_beam, modelio, ratebatch, streams, windows
+from . import lattice_beam, modelio, ratebatch, segments, streams, windows
 from .node import Node
 
 PREC_BF16 = 1
@@ -161,6 +164,7 @@ class Rater(object):
         self.device_dropout_masks = True     # ... and their dropout masks drawn on the device (False: by the host generator, as without batching)
         self.batched_streams = True          # the B streams of stateful training advanced together (streams.StreamBatcher)
         self.batched_streams_max_chars = 1 << 30
+        self.segment_streams = False         # fewer files than streams: cut the files into segments, one list of segments per stream (segments.py)
         self._engine_factory = engine_factory
         self._pool = None
         self._ctx_rows = None
@@ -225,25 +229,41 @@ class Rater(object):
         sync.broadcast_params(lm)      # every rank initialised or loaded its own weights: rank 0's count
         B = max(1, int(self.streams))
         n_streams = B * world
-        if len(training_data) < n_streams or len(validation_data) < 1:
+        segment = bool(self.segment_streams)
+        if not segment and (len(training_data) < n_streams or len(validation_data) < 1):
             assert n_streams == 1 or len(training_data) >= n_streams, \
-                "need at least %d training files for %d streams" % (n_streams, n_streams)
+                "need at least %d training files for %d streams (or segment_streams, which cuts the files into that many pieces)" \
+                % (n_streams, n_streams)
         rng = np.random.default_rng(self.seed)
         reset_rows = set()
 
-        def make_streams(files, train):
-            gens = []
-            for s in range(B):
-                gid = rank * B + s
-                mine = files[gid::n_streams] or files[:1]
+        def stream_items(files, train):
+            """what is dealt to the streams: the files -- or, with `segment_streams` and fewer files than streams, their
+            segments (file, lo, hi), the same plan on every rank (segments.plan).  Validation files with fewer windows than
+            streams give one segment per window, and the streams left over fall back to the first item as they do with files."""
+            if segment and len(files) < n_streams:
+                cut = segments.char_plan([self._sizes[id(f)] for f in files], self.length, n_streams, strict=train)
+                if cut:
+                    return [(files[k], lo, hi) for k, lo, hi in cut]
+            return list(files)
 
+        training_items = stream_items(training_data, True)
+        validation_items = stream_items(validation_data, False)
+        if segment:
+            self.logger.info('segment streams: %d training files in %d segments, %d validation files in %d segments, for %d streams',
+                             len(training_data), len(training_items), len(validation_data), len(validation_items), n_streams)
+
+        def make_streams(items, train):
+            gens = []
+            for s, mine in enumerate(segments.deal(items, rank, B, n_streams)):
                 def hook(name, s=s):
                     if train:
                         reset_rows.add(s)    # ResetStatesCallback.reset (callbacks.py:50-53)
-                gens.append(windows.file_windows(mine, self.length, self.mapping[0], train=train, repeat=True, rng=rng,
-                                                 on_new_file=hook, on_unmapped=self._unmapped_input,
-                                                 char_degradation=self.char_degradation,
-                                                 context_degradation=self.context_degradation))
+                generator = windows.segment_windows if isinstance(mine[0], tuple) else windows.file_windows
+                gens.append(generator(mine, self.length, self.mapping[0], train=train, repeat=True, rng=rng,
+                                      on_new_file=hook, on_unmapped=self._unmapped_input,
+                                      char_degradation=self.char_degradation,
+                                      context_degradation=self.context_degradation))
             return gens
 
         def next_batch(gens):
@@ -258,25 +278,26 @@ class Rater(object):
                 xs.append(x); zs.append(z); ys.append(y)
             return np.stack(xs), np.stack(zs), np.stack(ys)
 
-        def make_batcher(files, train):
-            per_stream = [files[rank * B + s::n_streams] or files[:1] for s in range(B)]
-            return streams.StreamBatcher(per_stream, self.length, self.mapping[0], train=train, rng=rng,
+        def make_batcher(items, train):
+            # (an engine with a device assembles the batches there in one launch of its own: HipLM.assemble_windows)
+            return streams.StreamBatcher(segments.deal(items, rank, B, n_streams), self.length, self.mapping[0], train=train, rng=rng,
                                          char_degradation=self.char_degradation, context_degradation=self.context_degradation,
                                          on_unmapped=self._unmapped_input, device=getattr(lm, "device", None),
-                                         codepoints=getattr(self, "_texts", None))
+                                         codepoints=getattr(self, "_texts", None),
+                                         assembler=getattr(lm, "assemble_windows", None))
 
         # (the batched path keeps every file's ids in memory -- in HBM for the HIP engine --, 4 bytes per character;
         #  corpora beyond `batched_streams_max_chars` stay on the generator per stream, which re-reads file by file)
         t_phase = time.perf_counter()
         if self.batched_streams and total_size <= self.batched_streams_max_chars:
-            train_gens = make_batcher(training_data, True)
-            val_gens = make_batcher(validation_data, False)
+            train_gens = make_batcher(training_items, True)
+            val_gens = make_batcher(validation_items, False)
             train_gens.prepare()
             val_gens.prepare()
             timings['encode'] = time.perf_counter() - t_phase
         else:
-            train_gens = make_streams(training_data, True)
-            val_gens = make_streams(validation_data, False)
+            train_gens = make_streams(training_items, True)
+            val_gens = make_streams(validation_items, False)
         self._texts = {}
         draw_masks = getattr(lm, "draw_dropout_masks_device", None) if (self.batched_streams and self.device_dropout_masks) else None
         draw_masks = draw_masks or lm.draw_dropout_masks
@@ -449,6 +470,7 @@ class Rater(object):
             return self._split_data_stateless(data, val_data)
         total_size = 0
         self._texts = {}
+        self._sizes = {}      # id(file) -> characters of its normalised text (what segments.plan cuts)
         chars = set(self.mapping[0].keys())
         steps = self.length
         if val_data:
@@ -468,6 +490,7 @@ class Rater(object):
                 file.seek(0)
                 text, size = windows.read_normalize_file(file)
                 total_size += size
+                self._sizes[id(file)] = size
                 epoch_size += ceil((size - self.length) / steps / self.batch_size)
                 # (the distinct characters through a flag per code point: `set(text)` costs 2.5 ms per 50 k characters;
                 #  the code point vectors are what train() maps to ids, it need not read the files again)

@@ -12,7 +12,11 @@ stream enters a new file) from array state:
   * per step the streams' states (file, next window, pending augmented copies) advance as numpy vectors; only the
     streams that change file or owe an augmented copy (about one in ten) are touched individually;
   * a batch is assembled from (start, valid length, column to zero, context to zero) per stream by one gather and a
-    few masks (`assemble`, numpy on the host or torch on the device -- plumbing, not arithmetic).
+    few masks (`assemble_host` in numpy; on the device one HIP launch, `kl_assemble_windows`, through the `assembler`
+    the engine provides -- or torch operations where there is none).
+
+A stream's items are files, or SEGMENTS of files (segments.py: contiguous runs of a file's windows), when there are
+fewer files than streams; the state machine is the same, it walks a table of segments instead of the table of files.
 
 Random numbers: the generators draw one uniform number per full training window, stream by stream, in batch order
 (rating.py:1062-1077); here the draws of a batch come as ONE vector from the same `numpy.random.Generator`, which
@@ -27,10 +31,16 @@ from . import windows
 
 class StreamBatcher(object):
     def __init__(self, stream_files, length, c_i, train=False, rng=None, char_degradation=0.01, context_degradation=0.1,
-                 on_unmapped=None, device=None, codepoints=None):
-        """stream_files: per stream, the list of open text files it cycles through (at least one each);
+                 on_unmapped=None, device=None, codepoints=None, assembler=None):
+        """stream_files: per stream, the list of open text files it cycles through (at least one each) -- or of segments
+        (file, lo, hi): the characters [lo, hi) of the file's normalised text, cut on window boundaries (segments.py).
+        Every physical file is kept ONCE in the corpus; the streams walk a table of (corpus base, size, context) rows
+        that has one row per file, or one per segment;
         codepoints: optional {id(file): uint32 code points of the normalised text} of files the caller has read
-        already (`Rater._split_data`)"""
+        already (`Rater._split_data`);
+        assembler: optional callable (corpus ids on the device, plan [B, 4 + n_ctx] int64 on the device, T, n_ctx) ->
+        (x, ctx, y) that assembles the batch on the device (`HipLM.assemble_windows`: one HIP launch); without it
+        a device batcher uses torch (`assemble_device_torch`)"""
         self.B = len(stream_files)
         self.T = int(length)
         self.train = bool(train)
@@ -38,6 +48,7 @@ class StreamBatcher(object):
         self.char_degradation = float(char_degradation)
         self.context_degradation = float(context_degradation)
         self.device = device
+        self.assembler = assembler
         self.c_i = c_i
         self.on_unmapped = on_unmapped
         T = self.T
@@ -46,9 +57,11 @@ class StreamBatcher(object):
         self._file_of = {}
         off = 0
         f_base, f_size, f_ctx, self._parts = [], [], [], []
+        segmented = any(isinstance(item, tuple) for files in stream_files for item in files)
         for files in stream_files:
             assert files, "a stream needs at least one file"
             for f in files:
+                f = f[0] if isinstance(f, tuple) else f
                 if id(f) in self._file_of:
                     continue
                 if codepoints is not None and id(f) in codepoints:
@@ -67,6 +80,30 @@ class StreamBatcher(object):
         self._corpus = None
         self.n_ctx = len(f_ctx[0]) if f_ctx else 0
         assert all(len(c) == self.n_ctx for c in f_ctx), "all files must have the same number of context variables"
+        # the physical files: where each lies in the corpus (ids, unmapped characters)
+        self.p_base = np.asarray(f_base, dtype=np.int64)
+        self.p_size = np.asarray(f_size, dtype=np.int64)
+        # what the streams walk: the files themselves, or -- a second table -- their segments (rows of the same shape:
+        # corpus base, size, context; a segment inherits its file's context)
+        if segmented:
+            def key(item):
+                f, lo, hi = item if isinstance(item, tuple) else (item, 0, None)
+                k = self._file_of[id(f)]
+                return k, int(lo), int(self.p_size[k] if hi is None else hi)
+            row_of, f_base, f_size, file_ctx, f_ctx = {}, [], [], f_ctx, []
+            for files in stream_files:
+                for item in files:
+                    k, lo, hi = key(item)
+                    assert 0 <= lo <= hi <= self.p_size[k], "segment outside its file"
+                    assert lo % T == 0, "segments are cut on window boundaries"
+                    if (k, lo, hi) not in row_of:
+                        row_of[(k, lo, hi)] = len(f_base)
+                        f_base.append(int(self.p_base[k]) + lo)
+                        f_size.append(hi - lo)
+                        f_ctx.append(file_ctx[k])
+            row = lambda item: row_of[key(item)]
+        else:
+            row = lambda f: self._file_of[id(f)]
         self.f_base = np.asarray(f_base, dtype=np.int64)
         self.f_size = np.asarray(f_size, dtype=np.int64)
         self.f_ctx = np.asarray(f_ctx, dtype=np.int32).reshape(len(f_base), self.n_ctx)
@@ -74,7 +111,7 @@ class StreamBatcher(object):
         self.f_full = np.array([len(range(T, s, T)) for s in f_size], dtype=np.int64)
         self.f_tail = (self.f_full * T + 1 < self.f_size)
         # ---- per stream: its files (indices), where it stands
-        self.s_files = [np.array([self._file_of[id(f)] for f in files], dtype=np.int64) for files in stream_files]
+        self.s_files = [np.array([row(f) for f in files], dtype=np.int64) for files in stream_files]
         self.s_nfiles = np.array([len(x) for x in self.s_files], dtype=np.int64)
         self.s_pos = np.full(self.B, -1, dtype=np.int64)       # index into s_files (-1: before the first file)
         self.cur = np.zeros(self.B, dtype=np.int64)            # current file
@@ -92,8 +129,8 @@ class StreamBatcher(object):
         if self.on_unmapped is None:
             return
         for pos in positions:
-            k = int(np.searchsorted(self.f_base, pos, side='right')) - 1
-            j = int(pos - self.f_base[k])
+            k = int(np.searchsorted(self.p_base, pos, side='right')) - 1
+            j = int(pos - self.p_base[k])
             self.on_unmapped(chr(int(self._parts[k][j])), j)
 
     @property
@@ -107,7 +144,7 @@ class StreamBatcher(object):
 
             def gather(k):       # (numpy's take releases the interpreter lock: the files spread over the cores)
                 if len(self._parts[k]):
-                    np.take(lut, self._parts[k], out=out[self.f_base[k]:self.f_base[k] + self.f_size[k]], mode='clip')
+                    np.take(lut, self._parts[k], out=out[self.p_base[k]:self.p_base[k] + self.p_size[k]], mode='clip')
             with ThreadPoolExecutor(max(1, min(16, os.cpu_count() or 1))) as pool:
                 list(pool.map(gather, range(len(self._parts))))
             miss = np.nonzero(out[:self._total] < 0)[0]
@@ -130,7 +167,7 @@ class StreamBatcher(object):
                 warnings.simplefilter("ignore")
                 for k, part in enumerate(self._parts):
                     if len(part):
-                        cps[int(self.f_base[k]):int(self.f_base[k]) + len(part)].copy_(
+                        cps[int(self.p_base[k]):int(self.p_base[k]) + len(part)].copy_(
                             torch.from_numpy(part.view(np.int32)), non_blocking=True)
             lut = torch.from_numpy(windows.full_lookup_table(self.c_i)).to(dev)
             ids = lut.index_select(0, cps)
@@ -229,17 +266,29 @@ class StreamBatcher(object):
         z[rows, :, zero_ctx[rows]] = 0
         return x, z, y
 
-    def assemble_device(self, plan):
-        """the same three arrays as int32 torch tensors on `self.device`, gathered from the corpus in HBM"""
+    def _plan_to_device(self, plan):
+        """one small transfer per step: [start | vlen | zero_col | zero_ctx | ctx...] as int64 [B, 4 + n_ctx]"""
         import torch
         start, vlen, zero_col, zero_ctx, ctx, _ = plan
-        dev = self.device
         if self._corpus_dev is None:
             self.prepare()
-        T, B = self.T, self.B
-        # one small transfer per step: [start | vlen | zero_col | zero_ctx | ctx...]
         pack = np.concatenate([start[:, None], vlen[:, None], zero_col[:, None], zero_ctx[:, None], ctx.astype(np.int64)], axis=1)
-        p = torch.from_numpy(np.ascontiguousarray(pack)).to(dev, non_blocking=True)
+        return torch.from_numpy(np.ascontiguousarray(pack)).to(self.device, non_blocking=True)
+
+    def assemble_device(self, plan):
+        """the same three arrays as int32 torch tensors on `self.device`, gathered from the corpus in HBM: by the
+        `assembler` the batcher was given (one HIP launch, kl_assemble_windows), else by torch"""
+        if self.assembler is None:
+            return self.assemble_device_torch(plan)
+        p = self._plan_to_device(plan)
+        return self.assembler(self._corpus_dev, p, self.T, self.n_ctx)
+
+    def assemble_device_torch(self, plan):
+        """the assembly in torch operations (about twenty launches with [B, T] int64 temporaries): what a device batcher
+        without an `assembler` uses, and the second witness of the kernel's test"""
+        import torch
+        dev = self.device
+        p = self._plan_to_device(plan)
         pos = p[:, 0:1] + self._ar[None, :]
         valid = self._ar[None, :] < p[:, 1:2]
         x = torch.where(valid, self._corpus_dev[pos], 0)

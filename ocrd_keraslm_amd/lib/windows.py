@@ -196,6 +196,28 @@ def file_windows(files, length, c_i, train=False, repeat=False, rng=None, on_new
             break
 
 
+def segment_windows(segments, length, c_i, train=False, repeat=False, rng=None, on_new_file=None, on_unmapped=None,
+                    char_degradation=0.01, context_degradation=0.1):
+    """`file_windows` over segments (segments.py): (file, lo, hi) triples, the characters [lo, hi) of the file's normalised
+    text, cut so that `stateful_windows` of the slice yields a run of the file's own windows.  A segment inherits its
+    file's context; `on_new_file(name)` fires on entering every segment (also on wrapping round to the only one): the
+    carried state belongs to the text in front of the cut, which this stream has not read.  Unmapped characters are
+    reported with their position inside the file.  (The file is read again for every segment: this is the path for
+    corpora too large to keep, `Rater.batched_streams_max_chars`.)"""
+    while True:
+        for file, lo, hi in segments:
+            file.seek(0)
+            if on_new_file is not None:
+                on_new_file(file.name)
+            text, _ = read_normalize_file(file)
+            report = None if on_unmapped is None else (lambda char, pos, lo=lo: on_unmapped(char, lo + pos))
+            yield from stateful_windows(text[lo:hi], context_from_filename(file.name), length, c_i, train=train, rng=rng,
+                                        char_degradation=char_degradation, context_degradation=context_degradation,
+                                        on_unmapped=report)
+        if not repeat:
+            break
+
+
 def _vectorize_stateless(sequences, next_ids, context, length, batch_size, c_i, on_unmapped):
     """rating.py:1104-1158 for stateful=False: sequences RIGHT-padded with id 0 to `length`, contexts only under
     the characters, one target id per row (0 = unmapped, -1 = row without a target)"""

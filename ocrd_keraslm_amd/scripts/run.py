@@ -4,8 +4,9 @@
 Same commands, options, defaults and outputs as the reference CLI: train, test,
 apply, generate, print-history, print-charset, prune-charset and the three plot-* views of the
 embeddings (matplotlib / scikit-learn imported on use).
-Additional option on `train`: --streams (stateful streams per GPU, default 1 = the
-reference's batching).  Under `python -m torch.distributed.run` training is
+Additional options on `train`: --streams (stateful streams per GPU, default 1 = the
+reference's batching) and --segment-streams (with fewer files than streams, cut the files
+into contiguous segments on window boundaries, one list of segments per stream).  Under `python -m torch.distributed.run` training is
 data-parallel over the launched ranks (lib/distributed.py).
 """
 from __future__ import absolute_import
@@ -76,8 +77,10 @@ def _load(model, incremental=False):
               type=click.Path(exists=True, dir_okay=True, file_okay=True))
 @click.option('-s', '--streams', default=1, show_default=True, help='stateful streams trained in lockstep per GPU',
               type=click.IntRange(min=1, max=4096))
+@click.option('--segment-streams', is_flag=True, default=False,
+              help='with fewer files than streams, cut the files into segments (on window boundaries) and deal those')
 @click.argument('data', nargs=-1, type=click.Path(exists=True, dir_okay=True, file_okay=True))
-def train(model, ckpt, width, depth, length, val_data, streams, data):
+def train(model, ckpt, width, depth, length, val_data, streams, segment_streams, data):
     """Train a language model from DATA files,
        with parameters WIDTH, DEPTH, and LENGTH.
 
@@ -101,6 +104,7 @@ def train(model, ckpt, width, depth, length, val_data, streams, data):
         print('loading weights from checkpoint for continued training')
     rater.width, rater.depth, rater.length = width, depth, length
     rater.streams = streams
+    rater.segment_streams = segment_streams
     rater.configure()
     if resume:
         if rater.model is None:
