@@ -15,6 +15,7 @@
  *   Rater.rate, :493-529, for many texts at once             kl_rate_window (one text per stream, target-only delivery)
  *   model.predict_on_batch, stateful (1,1) step, :566        kl_forward_window with T = 1
  *   model.predict_on_batch, incremental + states, :631       kl_step_batch
+ *   ... once per character of a lattice edge, :796-851       kl_walk_batch_host (all characters of all hypotheses, one call)
  *   model.fit_generator -> train_on_batch, :292-298          kl_train_window + kl_adam_step
  *   _gen_data_from_files / _vectorize, :977-1158 (training)   kl_assemble_windows (the batches of B streams, on the device)
  *   model.reset_states, :475, :555, callbacks.py:58,69       caller zeroes its state rows
@@ -200,6 +201,37 @@ size_t kl_step_host_workspace_bytes(const kl_handle* h, int n);
 int kl_step_batch_host(kl_handle* h, int n, const int32_t* idx, const int32_t* ctx, const int32_t* slot_in,
                        const int32_t* slot_out, const int32_t* target, float* pool, int head_k, float* probs_host,
                        float* heads_host, uint32_t* done_host, uint32_t ticket, void* ws, size_t ws_bytes, void* stream);
+/* A LATTICE EDGE in one call (rating.py:796-851 rate_best: every hypothesis walks through the fixed text of its
+ * alternative, so all characters it will feed are known before the first step).  Row i takes len[i] steps
+ * (1 <= len[i] <= 1024); idx, target, slot_step and tprob_host are RAGGED: row i occupies entries off[i] .. off[i] + len[i] - 1,
+ * off = prefix sum of len, total = sum of len.  ctx is [n][n_ctx].  All index arrays are HOST arrays.
+ * Semantics: exactly those of len[i] chained kl_step_batch calls on row i --
+ *   step t feeds idx[off + t] into the state step t - 1 left (t = 0: pool slot slot_in[i]) and writes the new state to pool
+ *   slot slot_step[off + t]; tprob_host[off + t] = softmax probability of character target[off + t] after that step (0 is a
+ *   valid target; a target outside 0 .. V - 1 delivers 0.0f); the last slot_step entry of a row holds its final state;
+ *   head_k > 0 also delivers the first head_k state vectors of every row's FINAL state, [n][head_k][W], as
+ *   kl_step_batch_host does.
+ * No slot_step entry may equal a slot_in of the call or another slot_step entry; slots named in slot_in are never written.
+ * Rows may come in any order (the library orders them so that the rows still active at a step form a prefix), n may be any
+ * positive count (more than 256 rows are walked in groups inside the call).
+ * Launches: per step only the cell kernels, indices in the kernel arguments (the conditions of kl_step_batch_host's
+ * 256-hypothesis path: one context variable, widths 64, 128 or a multiple of 256, V <= 65535; KL_HOST_KERNARG=0 disables
+ * it); everything else chains kl_step_batch on ONE staged upload of all indices.  The output layer is deferred in both:
+ * after the last step one launch contracts the top layer's h of all `total` (row, step) pairs with the embedding, keeps
+ * a running maximum and sum per pair and delivers 4 bytes per pair -- no [total][V] array exists.  That launch serves EVERY
+ * vocabulary and width the library accepts (any V, W % 32 == 0): there is no logits-GEMM fall-back.
+ * tprob_host, heads_host, done_host, stage_host: from kl_host_alloc; stage_host >= kl_walk_stage_bytes(h, n, total) bytes:
+ * every index that does not travel in kernel arguments is copied there before the call returns, so the caller's (pageable)
+ * arrays are not read afterwards.  *done_host becomes `ticket` once everything has arrived (kl_step_wait); until then
+ * stage_host and the result buffers belong to the call.  ws: device, >= kl_walk_workspace_bytes(h, n, total), one per
+ * handle and stream.  KL_ERR_ARG (null pointer, n < 1, a len outside 1 .. 1024, head_k out of range), KL_ERR_STATE (not
+ * prepared) and KL_ERR_WORKSPACE are returned before anything is launched. */
+size_t kl_walk_workspace_bytes(const kl_handle* h, int n, int total);   /* total = sum of len[i] */
+size_t kl_walk_stage_bytes(const kl_handle* h, int n, int total);
+int kl_walk_batch_host(kl_handle* h, int n, const int32_t* len, const int32_t* idx, const int32_t* target,
+                       const int32_t* ctx, const int32_t* slot_in, const int32_t* slot_step, float* pool, int head_k,
+                       float* tprob_host, float* heads_host, void* stage_host, uint32_t* done_host, uint32_t ticket,
+                       void* ws, size_t ws_bytes, void* stream);
 /* returns 0 once *done_host == ticket; KL_ERR_LAUNCH / KL_ERR_STATE after timeout_s seconds without it */
 int kl_step_wait(const uint32_t* done_host, uint32_t ticket, double timeout_s);
 

@@ -123,6 +123,7 @@ struct kl_handle {
   void* host_step_ready = nullptr;      // kl_step_batch_host: the workspace whose ticket counter has been zeroed
   std::vector<int32_t> host_pack;       // ... its packed index block for the copy to the device (n > 256, fall-backs)
   bool host_kernarg = true;             // ... indices in the kernel arguments (KL_HOST_KERNARG=0: always the copy)
+  void* walk_ready = nullptr;           // kl_walk_batch_host: the workspace whose ticket counter has been zeroed
   bool inc_ready = false;       // the incremental step's fragment-major operands match the current weights (prepare_incremental)
   bool big_ready = false;       // ... and those of the gather + GEMM path (prepare_big_step)
   int last_only = 0;            // stateless windows: one target per row, at the last position (kl_set_window_mode)
@@ -1974,6 +1975,172 @@ int kl_step_batch_host(kl_handle* h, int n, const int32_t* idx, const int32_t* c
     f.softmax = 0; f.slot_out = dev_idx + 2 * (size_t)n;
     f.target = target ? dev_idx + 3 * (size_t)n : nullptr;
     return kl_launch_step_finish(f, nullptr, s);
+  }
+}
+
+// ---- a lattice edge in one call: every row walks through ALL its characters, no host round trip in between ------------
+// (rating.py:796-851: a track's characters are its alternative's text, known before the first step)
+namespace {
+struct WalkWs {
+  unsigned* counter; int32_t* idx; float* probs; unsigned char* rest; size_t rest_bytes, bytes;
+};
+// staged index words: slot_step | target (caller's ragged order), last slot per row, then -- only where the device-pointer
+// step is chained -- per step idx | slot_in | slot_out | ctx of the rows still active, longest rows first
+size_t walk_head_words(int n, int total) { return 2 * (size_t)total + (size_t)n; }
+size_t walk_stage_words(const kl_handle* h, int n, int total) {
+  return walk_head_words(n, total) + (size_t)total * (3 + (h->cfg.n_ctx > 0 ? h->cfg.n_ctx : 1));
+}
+WalkWs walk_carve(const kl_handle* h, int n, int total, void* ws, size_t ws_bytes) {
+  Carver cv(ws);
+  WalkWs w;
+  w.counter = cv.take<unsigned>(64);                                 // the output launch's ticket counter (zero between calls)
+  w.idx = cv.take<int32_t>(walk_stage_words(h, n, total));
+  w.probs = cv.take<float>((size_t)n * h->cfg.voc_size);            // what the chained device-pointer steps write (never read)
+  const size_t head = align_up(cv.off, 256);
+  w.rest = ws ? reinterpret_cast<unsigned char*>(ws) + head : nullptr;
+  w.bytes = head + kl_step_workspace_bytes(h, n);
+  w.rest_bytes = ws_bytes > head ? ws_bytes - head : 0;
+  return w;
+}
+}  // namespace
+
+size_t kl_walk_workspace_bytes(const kl_handle* h, int n, int total) {
+  if (!h || n < 1 || total < n) return 0;
+  return walk_carve(h, n, total, nullptr, 0).bytes;
+}
+
+size_t kl_walk_stage_bytes(const kl_handle* h, int n, int total) {
+  if (!h || n < 1 || total < n) return 0;
+  return align_up(walk_stage_words(h, n, total) * sizeof(int32_t), 256);
+}
+
+int kl_walk_batch_host(kl_handle* h, int n, const int32_t* len, const int32_t* idx, const int32_t* target, const int32_t* ctx,
+                       const int32_t* slot_in, const int32_t* slot_step, float* pool, int head_k, float* tprob_host,
+                       float* heads_host, void* stage_host, uint32_t* done_host, uint32_t ticket, void* ws, size_t ws_bytes,
+                       void* stream) {
+  if (!h || !len || !idx || !target || !slot_in || !slot_step || !pool || !tprob_host || !stage_host || !done_host || n < 1)
+    return KL_ERR_ARG;
+  if (h->cfg.n_ctx > 0 && !ctx) return KL_ERR_ARG;
+  if (head_k < 0 || head_k > 2 * h->cfg.depth || (head_k > 0 && !heads_host)) return KL_ERR_ARG;
+  long total_l = 0;
+  int max_len = 0;
+  for (int i = 0; i < n; ++i) {
+    if (len[i] < 1 || len[i] > 1024) return KL_ERR_ARG;
+    total_l += len[i];
+    if (len[i] > max_len) max_len = len[i];
+  }
+  if (total_l > 0x3fffffff) return KL_ERR_ARG;
+  if (!h->precision) return KL_ERR_STATE;
+  const int total = (int)total_l;
+  if (!ws || ws_bytes < kl_walk_workspace_bytes(h, n, total)) return KL_ERR_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  const kl_config& c = h->cfg;
+  const int W = c.width, L = c.depth, V = c.voc_size, C = c.n_ctx;
+  const long slot_ld = (long)2 * L * W;
+  Derived& d = h->d;
+  const int split = h->precision;
+  const float* P = h->params;
+  const WalkWs w = walk_carve(h, n, total, ws, ws_bytes);
+  // rows ordered so that those still active at step t form a prefix: longest first, equal lengths in the caller's order
+  // (a counting sort over the lengths 1 .. 1024)
+  static thread_local std::vector<int32_t> order, off, count;
+  order.resize(n); off.resize(n); count.assign(max_len + 2, 0);
+  {
+    int o = 0;
+    for (int i = 0; i < n; ++i) { off[i] = o; o += len[i]; ++count[len[i]]; }
+    int at = 0;
+    for (int l = max_len; l >= 1; --l) { const int k = count[l]; count[l] = at; at += k; }      // first position of length l
+    for (int i = 0; i < n; ++i) order[count[len[i]]++] = i;
+    // (count[l] is now the number of rows of length >= l: the rows active at step l - 1)
+  }
+  int32_t* st = reinterpret_cast<int32_t*>(stage_host);
+  memcpy(st, slot_step, (size_t)total * 4);
+  memcpy(st + total, target, (size_t)total * 4);
+  for (int i = 0; i < n; ++i) st[2 * (size_t)total + i] = slot_step[off[i] + len[i] - 1];
+  const size_t head_words = walk_head_words(n, total);
+  if (w.counter != h->walk_ready) {      // (the counter of a fresh workspace; afterwards every output launch leaves it zero)
+    KL_TRY(kl_zero_async(w.counter, 64 * sizeof(unsigned), s));
+    h->walk_ready = w.counter;
+  }
+  if (!h->inc_ready) KL_TRY(prepare_incremental(h, s));
+  if (!d.EF) return KL_ERR_SHAPE;
+  KlWalkOut f;
+  memset(&f, 0, sizeof(f));
+  f.total = total; f.n = n; f.V = V; f.W = W; f.lo = split == 3; f.head_k = head_k;
+  f.pool = pool; f.slot_ld = slot_ld; f.h_off = 2 * (L - 1) * W; f.EF = d.EF;
+  f.slots = w.idx; f.targets = w.idx + total; f.last = w.idx + 2 * (size_t)total;
+  f.tprob_host = tprob_host; f.heads_host = heads_host; f.done_host = done_host; f.ticket = ticket; f.counter = w.counter;
+  // ---- the 16-unit cell kernels with every index of a step in the kernel arguments, groups of up to 256 rows
+  bool in_range = V <= 65535 && C == 1 && h->inc_small && h->host_kernarg;
+  in_range = in_range && ((W & 255) == 0 || W == 64 || W == 128) && !(W >= 1024 && n > 128);
+  for (int i = 0; i < n && in_range; ++i) in_range = ctx[i] >= 0 && ctx[i] < c.ctx_vocab;
+  for (int p = 0; p < total && in_range; ++p) in_range = idx[p] >= 0 && idx[p] < V;
+  if (in_range) {
+    static thread_local KlHostIdx hx;
+    for (int g0 = 0; g0 < n; g0 += KL_HOST_STEP_MAX) {
+      const int g1 = g0 + KL_HOST_STEP_MAX < n ? g0 + KL_HOST_STEP_MAX : n;
+      const int g_len = len[order[g0]];
+      for (int t = 0; t < g_len; ++t) {
+        const int active = (count[t + 1] < g1 ? count[t + 1] : g1) - g0;      // rows of the group with len > t
+        for (int j = 0; j < active; ++j) {
+          const int r = order[g0 + j], p = off[r] + t;
+          hx.slot_in[j] = t ? slot_step[p - 1] : slot_in[r];
+          hx.slot_out[j] = slot_step[p];
+          hx.idx[j] = (unsigned short)idx[p];
+          hx.ctx[j] = (unsigned short)ctx[r];
+        }
+        for (int l = 0; l < L; ++l) {
+          KlIncCellArgs a;
+          memset(&a, 0, sizeof(a));
+          a.n = active; a.W = W; a.split = split;
+          a.pool = pool; a.slot_ld = slot_ld;
+          a.h_off = 2 * l * W; a.c_off = (2 * l + 1) * W; a.x_off = l > 0 ? 2 * (l - 1) * W : -1;
+          a.UF = d.UF[l]; a.KF = d.KF[l];
+          a.bias = P + h->off_b[l];
+          if (l == 0) {      // (i1 / i2 non-null = "table rows by index"; the values are hx's)
+            a.T1 = d.EK; a.i1 = w.idx; a.T2 = d.CtxK[0]; a.i2 = w.idx;
+          }
+          const int e = kl_launch_inc_cell(a, s, &hx, nullptr);
+          if (e == KL_ERR_SHAPE && (g0 || t || l)) return e;      // (the first launch decides for all: the shapes are the same)
+          if (e == KL_ERR_SHAPE) { in_range = false; break; }
+          if (e) return e;
+        }
+        if (!in_range) break;
+      }
+      if (!in_range) break;
+    }
+    if (in_range) {
+      if (hipMemcpyAsync(w.idx, st, head_words * 4, hipMemcpyHostToDevice, s) != hipSuccess) return KL_ERR_LAUNCH;
+      return kl_launch_walk_out(f, s);
+    }
+  }
+  // ---- everything else: ONE staged upload of all indices, then the device-pointer step chained over the active prefix
+  {
+    const int Cc = C > 0 ? C : 1;
+    size_t at = head_words;
+    static thread_local std::vector<size_t> step_at;
+    step_at.resize(max_len);
+    for (int t = 0; t < max_len; ++t) {
+      const int active = count[t + 1];
+      step_at[t] = at;
+      int32_t* q = st + at;
+      for (int j = 0; j < active; ++j) {
+        const int r = order[j], p = off[r] + t;
+        q[j] = idx[p];
+        q[active + j] = t ? slot_step[p - 1] : slot_in[r];
+        q[2 * (size_t)active + j] = slot_step[p];
+        for (int k = 0; k < Cc; ++k) q[3 * (size_t)active + (size_t)j * Cc + k] = C > 0 ? ctx[(size_t)r * C + k] : 0;
+      }
+      at += (size_t)active * (3 + Cc);
+    }
+    if (hipMemcpyAsync(w.idx, st, at * 4, hipMemcpyHostToDevice, s) != hipSuccess) return KL_ERR_LAUNCH;
+    for (int t = 0; t < max_len; ++t) {
+      const int active = count[t + 1];
+      const int32_t* q = w.idx + step_at[t];
+      KL_TRY(kl_step_batch(h, active, q, C > 0 ? q + 3 * (size_t)active : nullptr, pool, q + active, q + 2 * (size_t)active, w.probs,
+                           w.rest, w.rest_bytes, stream));
+    }
+    return kl_launch_walk_out(f, s);
   }
 }
 

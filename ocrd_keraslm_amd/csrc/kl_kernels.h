@@ -365,6 +365,20 @@ int kl_launch_step_finish(const KlStepFinish& a, const KlHostTargets* tx, hipStr
 // still mean "table rows by index"); slots_copy (device, n ints) receives slot_out for the launches that follow
 int kl_launch_inc_cell(const KlIncCellArgs& a, hipStream_t stream, const KlHostIdx* hx = nullptr, int* slots_copy = nullptr);      // KL_ERR_SHAPE: not applicable
 
+// ---- walk.hip -----------------------------------------------------------
+// the deferred output layer of kl_walk_batch_host: per (row, step) pair p the softmax probability of targets[p] from the top
+// layer's h in pool slot slots[p] (0 where the target is outside 0 .. V - 1), the heads of the rows' final states
+// (slots last[row]), then the arrival word -- all into device-visible host memory, see walk_out_kernel
+struct KlWalkOut {
+  int total, n, V, W, lo, head_k;    // pairs, rows; lo: split precision (EF holds hi and lo planes)
+  const float* pool; long slot_ld; int h_off;       // h_off: float offset of the top layer's h inside a slot
+  const bf16_t* EF;                  // fragment-major embedding (kl_launch_frag_major of [round_up(V, 32)][W])
+  const int* slots; const int* targets; const int* last;      // device: [total], [total], [n]
+  float* tprob_host; float* heads_host; unsigned* done_host; unsigned ticket;
+  unsigned* counter;                 // device, zero between calls
+};
+int kl_launch_walk_out(const KlWalkOut& a, hipStream_t stream);
+
 // ---- step_tile.hip: the same for n >= KL_BIG_STEP_N, TR x 128 tiles with the operands read once (variant: timing builds, 0)
 int kl_launch_inc_tile(const KlIncCellArgs& a, int variant, hipStream_t stream, int rows = -1);      // KL_ERR_SHAPE: not applicable; rows: 64 / 128 per tile, -1 = by size
 // output layer in one launch: probs[n][V] = softmax(h_top . E^T), h_top rows through slot_out (V <= 256, W % 128 == 0)

@@ -98,6 +98,8 @@ class HipLM:
         self.plan_override = None            # width 512: a stream plan to use instead of _plan_512's (tests)
         self._step_ws = None
         self._step_host_ws = None
+        self._walk_ws = None
+        self._wstage = None
         self._hio = None
         self._step_ws_bytes = {}
         self.last_only = False
@@ -107,6 +109,10 @@ class HipLM:
         try:
             if getattr(self, "_hio", None) is not None:
                 self._host_io_free()
+            if getattr(self, "_wstage", None) is not None:
+                self.torch.cuda.synchronize(self.device)
+                self.lib.kl_host_free(self._wstage[0])
+                self._wstage = None
             if getattr(self, "handle", None):
                 self.lib.kl_destroy(self.handle)
                 self.handle = None
@@ -802,6 +808,65 @@ class HipLM:
         if head_k:
             heads = io["np"]["heads"][:n * head_k * self.pwidth].reshape(n, head_k, self.pwidth)[:, :, :self.width].copy()
         return probs, heads
+
+    # ---- a lattice edge in one call (kl_walk_batch_host): every row through all its characters, one wait
+    def _walk_stage(self, nbytes):
+        """the walk's own page-locked staging buffer (kl_host_alloc), kept and grown as needed"""
+        st = getattr(self, "_wstage", None)
+        if st is not None and st[1] >= nbytes:
+            return st[0]
+        if st is not None:
+            self.torch.cuda.synchronize(self.device)      # (nothing may still be reading it)
+            self.lib.kl_host_free(st[0])
+            self._wstage = None
+        cap = max(1 << 16, 1 << (int(nbytes) - 1).bit_length())
+        ptr = self.lib.kl_host_alloc(cap)
+        if not ptr:
+            raise hipabi.KlError("kl_host_alloc(%d) failed" % cap)
+        self._wstage = (ptr, cap)
+        return ptr
+
+    def walk_host(self, lens, idx, target, ctx, slot_in, slot_step, head_k=0, timeout=20.0):
+        """len(lens) rows walked through lens[i] chained LSTM steps each, HOST index arrays in, results on the HOST:
+        idx / target / slot_step are ragged (row i at the prefix sum of lens), ctx [n][n_ctx], slot_in [n].  Step t of a row
+        reads the state step t - 1 left (slot_in[i] for the first) and leaves its own in slot_step[off + t]; returns
+        (tprob, heads): tprob ragged float32, the probability of target[off + t] after step t; heads [n][head_k][W] (the
+        first head_k state vectors of every row's FINAL state) or None.  One engine call and one wait, whatever the lengths."""
+        lens = np.ascontiguousarray(lens, dtype=np.int32).reshape(-1)
+        n = lens.shape[0]
+        total = int(lens.sum())
+        idx = np.ascontiguousarray(idx, dtype=np.int32).reshape(-1)
+        tg = np.ascontiguousarray(target, dtype=np.int32).reshape(-1)
+        so = np.ascontiguousarray(slot_step, dtype=np.int32).reshape(-1)
+        si = np.ascontiguousarray(slot_in, dtype=np.int32).reshape(-1)
+        ctx = np.ascontiguousarray(ctx, dtype=np.int32).reshape(n, -1) if self.n_ctx else None
+        if n < 1 or idx.shape[0] != total or tg.shape[0] != total or so.shape[0] != total or si.shape[0] != n:
+            raise hipabi.KlError("walk_host: %d rows of %d steps in all do not match the index arrays" % (n, total))
+        # (_host_io's probability buffer holds n_cap * V floats: `rows` such that it takes one float per step)
+        io = self._host_io(max(n, -(-total // self.voc_size)), head_k)
+        key = ("walk", n, total)
+        sizes = self._step_ws_bytes.get(key)
+        if sizes is None:
+            if len(self._step_ws_bytes) > 4096:      # (edges come in many shapes: do not keep them all for ever)
+                self._step_ws_bytes.clear()
+            sizes = self._step_ws_bytes[key] = (int(self.lib.kl_walk_workspace_bytes(self.handle, n, total)),
+                                                int(self.lib.kl_walk_stage_bytes(self.handle, n, total)))
+        nws, nstage = sizes
+        if self._walk_ws is None or self._walk_ws.numel() < nws:
+            self._walk_ws = self.torch.empty(max(nws, 1 << 20), dtype=self.torch.uint8, device=self.device)
+        stage = self._walk_stage(nstage)
+        io["ticket"] = ticket = (io["ticket"] % 0x7fffffff) + 1
+        stream = C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
+        hipabi.check(self.lib.kl_walk_batch_host(
+            self.handle, n, lens.ctypes.data, idx.ctypes.data, tg.ctypes.data, ctx.ctypes.data if ctx is not None else None,
+            si.ctypes.data, so.ctypes.data, _ptr(self.pool), int(head_k), io["ptr"]["probs"], io["ptr"]["heads"], stage,
+            io["ptr"]["done"], ticket, _ptr(self._walk_ws), self._walk_ws.numel(), stream), "kl_walk_batch_host")
+        hipabi.check(self.lib.kl_step_wait(io["ptr"]["done"], ticket, float(timeout)), "kl_step_wait")
+        tprob = io["np"]["probs"][:total].copy()
+        heads = None
+        if head_k:
+            heads = io["np"]["heads"][:n * head_k * self.pwidth].reshape(n, head_k, self.pwidth)[:, :, :self.width].copy()
+        return tprob, heads
 
     def to_device_i32(self, a):
         """one host-to-device transfer of an int32 array (rows stay contiguous views)"""

@@ -90,6 +90,7 @@ class EdgeTracks(object):
         # alternative and character, rating.py:830-837) and the confidence term every one of its characters costs
         # (rating.py:839-840)
         get = c_i.get
+        self.c_i = c_i
         self.ids = [[get(char, 0) for char in t] for t in self.text]
         self.unmapped = [[char not in c_i for char in t] for t in self.text]
         self.reported = [set() for _ in alternatives]
@@ -118,6 +119,11 @@ class EdgeTracks(object):
             p = self.pos[i]
             out.append(self.text[self.alt[i]][p - 1] if p else self.incoming[self.parent[i]].value[-1])
         return out
+
+    def first_ids(self):
+        """per incoming hypothesis, the id of its last character: what every track that continues it feeds first"""
+        get = self.c_i.get
+        return [get(h.value[-1], 0) for h in self.incoming]
 
     def targets(self, rows):
         """id of the character each track of the batch consumes next (the one whose probability `advance` looks at)"""
@@ -156,12 +162,120 @@ class EdgeTracks(object):
         return n
 
 
-def decode_edge(tracks, finished, predict, batch_size, max_batches, close_states=None):
+class EdgeTable(object):
+    """What the model says about an edge, computed ahead of the bookkeeping (`walk_edge`): prob[i][k] = probability of the
+    k-th character of track i given its parent hypothesis and its own k preceding characters, final[i] = state handle of
+    track i after its last character (None for a track with an empty alternative: it keeps its parent's state).
+    A track's k-th probability does not depend on which other tracks share a batch -- the margins, the batch order and
+    `max_batches` only decide which entries `decode_edge` looks at."""
+    __slots__ = ("prob", "final", "calls")
+
+    def __init__(self, n):
+        self.prob = [[] for _ in range(n)]
+        self.final = [None] * n
+        self.calls = 0      # engine calls it took (walk_host calls, or chained steps)
+
+
+WALK_SCRATCH_BYTES = 64 << 20      # HBM the intermediate states of ONE walk_host call may occupy (they go back to the pool after it)
+
+
+def walk_slot_budget(slot_bytes):
+    """rows x longest alternative one walk_host call may be asked for: what WALK_SCRATCH_BYTES holds in pool slots
+    (depth 2, width 512: 8 KiB per slot, 8192 slots; an edge of beam width 10 x 8 alternatives x 12 characters needs 960)"""
+    return max(1, WALK_SCRATCH_BYTES // max(1, int(slot_bytes)))
+
+
+def walk_edge(tracks, walk, pool=None, ctx=None, head_k=0, slot_budget=None, predict=None):
+    """The EdgeTable of an edge: every track walked through ALL characters of its alternative before any bookkeeping.
+
+    walk: the engine's `walk_host` (HipLM: kl_walk_batch_host -- all tracks over all their characters in one call, no host
+    round trip between characters).  Per track it is given the ids it feeds (its parent's last character, then its own
+    text without the last character), the ids it consumes (the targets), and the slot of its parent's state.  The final
+    state of every track goes to a fresh handle of `pool` (StatePool.refs), the states in between to slots that are taken
+    from the pool for the call and released right after it.  More than `slot_budget` slots (rows x longest alternative of
+    the edge) are never asked of one call: the tracks are then sent in chunks of slot_budget // longest rows, in track order.
+    ctx: the context ids [n_ctx]; head_k > 0: the first head_k vectors of every final state are attached to its handle
+    (history clustering compares them on the host).
+    walk None (an engine without `walk_host`, e.g. the tests' CPU double): the table is filled by chained
+    predict(chars, states, targets) calls over the tracks still on their way -- the same numbers, one call per character.
+    Tracks with an empty alternative are not sent."""
+    n = len(tracks)
+    table = EdgeTable(n)
+    length, alt, ids = tracks.length, tracks.alt, tracks.ids
+    rows = [i for i in range(n) if length[alt[i]] > 0]
+    if not rows:
+        return table
+    if walk is None:
+        return _chain_edge(tracks, rows, table, predict)
+    c_i_first = tracks.first_ids()
+    longest = max(length[alt[i]] for i in rows)
+    per_call = max(1, (slot_budget or walk_slot_budget(pool.slot_bytes)) // longest)
+    ctx = np.asarray(ctx if ctx is not None else [], dtype=np.int32).reshape(-1)
+    zero = pool.zero_slot
+    for c0 in range(0, len(rows), per_call):
+        chunk = rows[c0:c0 + per_call]
+        lens = [length[alt[i]] for i in chunk]
+        total = sum(lens)
+        finals, final_slots = pool.refs(len(chunk))
+        scratch = pool.take_slots(total - len(chunk))
+        fed, target, slot_step = [], [], []
+        at = 0
+        for i, k, last in zip(chunk, lens, final_slots):
+            own = ids[alt[i]]
+            fed.append(c_i_first[tracks.parent[i]])
+            fed.extend(own[:-1])
+            target.extend(own)
+            slot_step.extend(scratch[at:at + k - 1])
+            slot_step.append(last)
+            at += k - 1
+        slot_in = [tracks.state[i].slot if tracks.state[i] is not None else zero for i in chunk]
+        try:
+            tprob, heads = walk(lens, fed, target, np.tile(ctx, (len(chunk), 1)), slot_in, slot_step, head_k=head_k)
+        finally:
+            pool.release_slots(scratch)
+        table.calls += 1
+        tprob = np.asarray(tprob, dtype=np.float64).tolist()
+        at = 0
+        for j, (i, k) in enumerate(zip(chunk, lens)):
+            table.prob[i] = tprob[at:at + k]
+            at += k
+            if head_k:
+                finals[j].head = heads[j]
+            table.final[i] = finals[j]
+    return table
+
+
+def _chain_edge(tracks, rows, table, predict):
+    """walk_edge without an engine walk: one predict call per character position over the tracks that have one"""
+    length, alt, ids, text = tracks.length, tracks.alt, tracks.ids, tracks.text
+    state = dict((i, tracks.state[i]) for i in rows)
+    t = 0
+    while rows:
+        chars = [text[alt[i]][t - 1] if t else tracks.incoming[tracks.parent[i]].value[-1] for i in rows]
+        target = [ids[alt[i]][t] for i in rows]
+        probs, new_states = predict(chars, [state[i] for i in rows], target)
+        table.calls += 1
+        probs = np.asarray(probs, dtype=np.float64)
+        p_next = (probs if probs.ndim == 1 else probs[np.arange(len(rows)), np.asarray(target)]).tolist()
+        for i, p, s in zip(rows, p_next, new_states):
+            table.prob[i].append(p)
+            state[i] = s
+        t += 1
+        for i in rows:
+            if length[alt[i]] == t:
+                table.final[i] = state.pop(i)
+        rows = [i for i in rows if length[alt[i]] > t]
+    return table
+
+
+def decode_edge(tracks, finished, predict, batch_size, max_batches, close_states=None, table=None):
     """Walk all tracks of an edge through their alternatives (rating.py:796-851).
 
     predict(last_chars, states, targets) -> (probs, new states) with probs [n, V] or -- an engine that delivers only what
     is looked at -- [n], the probabilities of the characters `targets`; close_states(a, b) -> whether two state handles are
-    within the clustering distance (None: no history clustering).  Finished tracks end up in `finished`."""
+    within the clustering distance (None: no history clustering).  Finished tracks end up in `finished`.
+    table (an EdgeTable, `walk_edge`): the probabilities are looked up there instead of asking `predict`, and a track's state
+    becomes its final handle when it consumes its last character (until then it keeps its parent's)."""
     # the waiting list: track numbers + keys.  It starts in creation order (UNSORTED, as in the reference, whose first
     # batch is therefore cut off the end of the creation order) and is kept sorted from the first re-queueing on.
     waiting = list(range(len(tracks)))
@@ -189,7 +303,11 @@ def decode_edge(tracks, finished, predict, batch_size, max_batches, close_states
             break
         # ---- one character on every track of the batch
         target = tracks.targets(batch)
-        probs, new_states = predict(tracks.last_chars(batch), [state[i] for i in batch], target)
+        if table is None:
+            probs, new_states = predict(tracks.last_chars(batch), [state[i] for i in batch], target)
+        else:
+            probs = [table.prob[i][pos[i]] for i in batch]
+            new_states = [table.final[i] if pos[i] + 1 == length[alt[i]] else state[i] for i in batch]
         tracks.advance(batch, probs, new_states, target)
         # ---- back into the waiting list, unless hopeless against its current head
         for i, key in zip(batch, tracks.keys(batch)):

@@ -107,8 +107,29 @@ class StatePool(object):
     def ref(self):
         return StateRef(self, self.take())
 
+    @property
+    def slot_bytes(self):
+        """HBM one slot occupies (at the width the engine's kernels run at)"""
+        return 2 * self.depth * int(getattr(self.engine, "pwidth", None) or self.engine.width) * 4
+
+    def take_slots(self, n):
+        """n bare slots for the duration of one engine call (the states in between of an edge walk); back with `release_slots`"""
+        if n <= 0:
+            return []
+        while len(self.free) < n:
+            self._grow(2 * self.capacity)
+        slots = self.free[-n:]
+        del self.free[-n:]
+        slots.reverse()
+        return slots
+
+    def release_slots(self, slots):
+        self.free.extend(reversed(slots))
+
     def refs(self, n):
         """n fresh handles at once (a beam search takes one per hypothesis and character)"""
+        if n <= 0:                           # (free[-0:] is the whole list)
+            return [], []
         while len(self.free) < n:
             self._grow(2 * self.capacity)
         slots = self.free[-n:]
@@ -164,6 +185,8 @@ class Rater(object):
         self.device_dropout_masks = True     # ... and their dropout masks drawn on the device (False: by the host generator, as without batching)
         self.batched_streams = True          # the B streams of stateful training advanced together (streams.StreamBatcher)
         self.batched_streams_max_chars = 1 << 30
+        self.edge_walk = False               # rate_best: every lattice edge's hypotheses walked through all their characters in ONE engine call (lattice_beam.walk_edge)
+        self.edge_walk_slots = None          # ... slots one such call may be asked for (None: lattice_beam.walk_slot_budget of the pool's slot size)
         self.segment_streams = False         # fewer files than streams: cut the files into segments, one list of segments per stream (segments.py)
         self._engine_factory = engine_factory
         self._pool = None
@@ -1067,14 +1090,19 @@ class Rater(object):
         return [''.join([n.value for n in res.to_sequence()]) for res in best]
 
     def rate_best(self, graph, start_node, end_node, start_traceback=None, context=None, lm_weight=0.5,
-                  beam_width=10, beam_clustering_dist=0):
+                  beam_width=10, beam_clustering_dist=0, edge_walk=None):
         '''Rate a lattice of string alternatives, decoding the best-scoring path
         incrementally (rating.py:712-859).  `graph` is a networkx.DiGraph whose edges
         carry `element` and `alternatives` (objects with `.Unicode`, `.conf`, `.index`).
         Returns (path [(element, alternative, score)], entropy, traceback).
 
         The beam bookkeeping lives in lattice_beam.py: one table of tracks per edge, list operations on track
-        numbers and float keys, tree nodes only for the hypotheses that survive at an edge's destination.'''
+        numbers and float keys, tree nodes only for the hypotheses that survive at an edge's destination.
+
+        edge_walk (None: the attribute `self.edge_walk`): the characters an edge's hypotheses will feed are known in
+        advance, so the model is asked ONCE per edge -- all hypotheses over all their characters in one engine call
+        (HipLM.walk_host; an engine without it: chained steps) -- and the unchanged bookkeeping then reads the probabilities
+        from that table (lattice_beam.walk_edge).  Same paths and costs; what it saves is the host round trip per character.'''
         if not context:
             context = self.underspecify_contexts()
         self._ensure_precision()
@@ -1090,6 +1118,10 @@ class Rater(object):
         def close_states(a, b):
             return all(self._state_distance_below(a, b, k, beam_clustering_dist) for k in range(self.depth))
 
+        if edge_walk is None:
+            edge_walk = self.edge_walk
+        walk = getattr(self.model, "walk_host", None) if edge_walk else None
+        walk_ctx = np.asarray(windows.clamp_context(context), dtype=np.int32) if walk is not None else None
         reached = None
         for source, reached in lattice_beam.lattice_edges(graph, start_node):
             edge = graph.edges[source, reached]
@@ -1101,9 +1133,14 @@ class Rater(object):
             tracks = lattice_beam.EdgeTracks(graph.nodes[source]['traceback'], alternatives, element, self.mapping[0],
                                              lm_weight, self.logger)
             finished = lattice_beam.FinishedBeam(target.get('traceback', []))
+            table = None
+            if edge_walk:
+                table = lattice_beam.walk_edge(tracks, walk, pool=self._state_pool() if walk is not None else None, ctx=walk_ctx,
+                                               head_k=self.depth if clustering else 0, slot_budget=self.edge_walk_slots,
+                                               predict=predict)
             lattice_beam.decode_edge(tracks, finished, predict, self.batch_size,
                                      max(len(a.Unicode) for a in alternatives) * 3,
-                                     close_states if clustering else None)
+                                     close_states if clustering else None, table=table)
             target['traceback'] = [ref if kind == "node" else tracks.node(ref) for kind, ref in finished.items[:beam_width]]
         assert reached == end_node, \
             'breadth-first search failed to reach true end node (%s instead of %d)' % (reached, end_node)

@@ -71,6 +71,8 @@ class KerasRate(Processor):
             self.rater.batch_size = 1
         self.rater.configure()
         self.rater.load_weights(model)
+        # (KERASLM_EDGE_WALK=1: a lattice edge's hypotheses in one engine call instead of one per character, Rater.edge_walk)
+        self.rater.edge_walk = os.environ.get('KERASLM_EDGE_WALK', '') == '1'
         self.logger.debug("Loaded model_file '%s'", model)
 
     # ------------------------------------------------------------------ helpers
