@@ -262,6 +262,16 @@ int kl_test_gemm_tn(const uint16_t* A, const uint16_t* B, void* C, const float* 
  * sum_k A_km[k][m] * B[n][k] (b_km: B_km[k][n]); KL_ERR_SHAPE where it does not apply (M % 256, K % 64) */
 int kl_test_gemm_an(const uint16_t* A_km, const uint16_t* B, float* C, int M, int N, int K, long lda_km, long ldb,
                     long ldc, int c_transposed, int b_km, void* stream);
+/* layer 0's table gradients as segment sums over the time-major rows r = t * B + b of dZ [T*B][ld] (bf16; cols a multiple
+ * of 8): dEK[v][cols] = sum of the rows with idx[b][t] == v in [0, V), dCtxK[c][cols] = sum of those with
+ * ctx[b][t][0] == c in [0, R) (ctx is [B][T][n_ctx]; n_ctx == 0: no context table).  Ids outside their range are dropped,
+ * each table on its own.  Both tables are f32, row-major, and zeroed by the call; ws (16-byte aligned,
+ * kl_test_segment_sums_ws_bytes) needs no preparation.  kl_test_segment_sums_share: the sorted rows one wave of the gather
+ * pass takes.  KL_ERR_SHAPE beyond 65535 (V + 1) * (R + 1) pairs. */
+size_t kl_test_segment_sums_ws_bytes(int B, int T, int n_ctx, int V, int R);
+int kl_test_segment_sums_share(int B, int T);
+int kl_test_segment_sums(const uint16_t* dZ, long ld, int B, int T, int cols, const int32_t* idx, const int32_t* ctx, int n_ctx,
+                         int V, int R, float* dEK, float* dCtxK, void* ws, void* stream);
 int kl_test_thin_gemm(const float* A, long lda, const uint16_t* WT_hi, const uint16_t* WT_lo, long ldw, int M, int N,
                       int K, float* C, long ldc, int split, void* stream);
 

@@ -88,6 +88,9 @@ struct WindowWs {
   bool km_plan = false;               // the weight-gradient GEMMs will read dZ and the activations K-major (row-major as written): no transposed copies
   bf16_t *dZT, *HT, *dlogits, *dlogitsT, *OHT, *dEKT_bf, *dEK_bf;
   std::vector<bf16_t*> OHC;
+  bool segsum = false;                // layer 0's character / first-context sums by sorted segment sums (kl_segsum_applicable): dEKT and
+                                      // dCtxKT[0] then hold the ROW-major tables [Vp][4W], [ctx_vocab][4W]; OHT and OHC[0] are not carved
+  void* seg_ws = nullptr;             // ... the sort's counters, row order and sorted keys (kl_segment_sums_ws_bytes)
   float *dH, *dEKT;
   std::vector<float*> dc0, dc1, dCtxKT;
 };
@@ -173,6 +176,8 @@ struct kl_handle {
   bool regtile = true;          // KL_REGTILE = 0: the backward scan's tiles by LDS-DMA at every size (else through registers from five blocks per step)
   bool scan2_flags = true;      // KL_SCAN2_FLAGS = 0: the backward scan hands over by data sentinels at every size (else by flags from three blocks per step)
   bool flags_zeroed = false;
+  bool segsum = true;           // KL_SEGSUM = 0: layer 0's table gradients as one-hot products (default: sorted segment sums, segsum.hip -- read in
+                                // kl_create, it decides the window workspace's size)
   bool fuse_wg = true;          // KL_FUSE_WG = 0: one launch per weight-gradient product (else products over the same dZ share a pass)
   int scan2_pfb = -1;           // KL_SCAN2_PFB: the same for the backward scan (-1: by shape)
   int wide_fwd_min = 96;        // layer-sequential wide forward scans from this many 64-unit workgroups (KL_WIDE_FWD_MIN; 0 = never)
@@ -300,6 +305,17 @@ size_t carve_derived(const kl_handle* h, void* base, Derived* d) {
   return align_up(cv.off, 256);
 }
 
+// Layer 0's character and first-context gradient sums as sorted segment sums over dZ_0 (segsum.hip) instead of one-hot
+// products?  Asked by carve_window (which arrays exist) and by train_window_body (which launches go out).  The counters of
+// all (character, context value) pairs, invalid ones included, must fit the one-workgroup scan: at most
+// KL_SEGSUM_MAX_BUCKETS = 65535 of them.  No shape class is excluded beyond that: the pass is one read of dZ_0 at any shape, the
+// products it replaces read dZ_0 at least once and the one-hot matrices on top.
+bool kl_segsum_applicable(const kl_handle* h, int B, int T) {
+  const kl_config& c = h->cfg;
+  if (!h->segsum || B < 1 || T < 1 || (long)B * T > 0x7fffffffL) return false;
+  return (long)kl_segment_sums_buckets(c.n_ctx, h->Vp, c.ctx_vocab) <= KL_SEGSUM_MAX_BUCKETS;
+}
+
 size_t carve_window(const kl_handle* h, void* base, int B, int T, int training, WindowWs* out) {
   const kl_config& c = h->cfg;
   const size_t W = c.width, V = c.voc_size, Vp = h->Vp, L = c.depth;
@@ -354,11 +370,13 @@ size_t carve_window(const kl_handle* h, void* base, int B, int T, int training, 
     }
     o.dlogits = cv.take<bf16_t>(BT * Vp);
     o.dlogitsT = cv.take<bf16_t>(Vp * BTp);
-    o.OHT = cv.take<bf16_t>(Vp * BTp);
+    o.segsum = kl_segsum_applicable(h, B, T);
+    o.OHT = o.segsum ? nullptr : cv.take<bf16_t>(Vp * BTp);
+    o.seg_ws = o.segsum ? cv.take<char>(kl_segment_sums_ws_bytes(B, T, c.n_ctx, (int)Vp, c.ctx_vocab)) : nullptr;
     o.OHC.assign(c.n_ctx, nullptr);
     o.dCtxKT.assign(c.n_ctx, nullptr);
     for (int n = 0; n < c.n_ctx; ++n) {
-      o.OHC[n] = cv.take<bf16_t>((size_t)c.ctx_vocab * BTp);
+      o.OHC[n] = (o.segsum && n == 0) ? nullptr : cv.take<bf16_t>((size_t)c.ctx_vocab * BTp);
       o.dCtxKT[n] = cv.take<float>(4 * W * (size_t)c.ctx_vocab);
     }
     o.dH = cv.take<float>(BT * W);
@@ -1051,6 +1069,9 @@ kl_handle* kl_create(const kl_config* cfg) {
   // (read HERE, not with the other switches in kl_bind: it decides how large the derived workspace is -- kl_derived_bytes)
   const char* env8tb = getenv("KL_FWD8_TAB");
   if (env8tb) h->fwd8_tab = atoi(env8tb) != 0;
+  // (... and this one how large a training window's workspace is -- kl_window_workspace_bytes)
+  const char* env9 = getenv("KL_SEGSUM");
+  if (env9) h->segsum = atoi(env9) != 0;
   return h;
 }
 
@@ -1365,14 +1386,24 @@ static int train_window_body(kl_handle* h, int B, int T, const int32_t* idx, con
       }
     } else {
       // layer 0 through the look-up tables: dEK^T = dZ^T . OneHot ; dCtxK_n^T likewise
+      // (segment sums: the characters' and the first context variable's sums from ONE read of dZ's rows in key order, no
+      //  one-hot matrices and no multiplications -- the tables come out row-major, dEK [Vp][4W] and dCtxK_0 [ctx_vocab][4W])
+      const bool seg = w.segsum;
+      bool pair_ctx = false;
+      if (seg) {
+        KL_TRY(kl_launch_segment_sums(w.dZ[l], 4 * W, B, T, 4 * W, idx, ctx, c.n_ctx, Vp, c.ctx_vocab, w.dEKT,
+                                      c.n_ctx > 0 ? w.dCtxKT[0] : nullptr, w.seg_ws, s));
+        KL_TRY(kl_launch_f32_to_bf16_t(w.dEKT, 4 * W, Vp, 4 * W, w.dEKT_bf, nullptr, Vp, 1, s));
+        KL_TRY(kl_launch_f32_to_bf16_t(w.dEKT, 4 * W, Vp, 4 * W, w.dEK_bf, nullptr, 4 * W, 0, s));
+      } else {
       if (kl_launch_onehot_dense(idx, B, T, Vp, 0, 1, w.OHT, BTp, s) == KL_ERR_SHAPE) {
         KL_TRY(kl_zero_async(w.OHT, (size_t)Vp * BTp * sizeof(bf16_t), s));
         KL_TRY(kl_launch_onehot_t(idx, B, T, V, 0, 1, w.OHT, BTp, s));
       }
       KL_TRY(kl_zero_async(w.dEKT, (size_t)4 * W * Vp * sizeof(float), s));
       // (the first context variable's one-hot product rides along with the characters': one pass over dZ for both)
-      bool pair_ctx = dz_km && h->fuse_wg && c.n_ctx >= 1 && (Vp % 128) == 0 &&
-                      kl_gemm_an_applicable(4 * W, Vp + c.ctx_vocab, BT, 4 * W);
+      pair_ctx = dz_km && h->fuse_wg && c.n_ctx >= 1 && (Vp % 128) == 0 &&
+                 kl_gemm_an_applicable(4 * W, Vp + c.ctx_vocab, BT, 4 * W);
       if (pair_ctx) {
         if (kl_launch_onehot_dense(ctx, B, T, c.ctx_vocab, 0, c.n_ctx, w.OHC[0], BTp, s) == KL_ERR_SHAPE) {
           KL_TRY(kl_zero_async(w.OHC[0], (size_t)c.ctx_vocab * BTp * sizeof(bf16_t), s));
@@ -1390,12 +1421,14 @@ static int train_window_body(kl_handle* h, int B, int T, const int32_t* idx, con
       else KL_TRY(kl_launch_gemm_tn(w.dZT, w.OHT, w.dEKT, nullptr, 4 * W, Vp, BTp, BTp, BTp, Vp, 2, ksplit, 1.f, s));
       KL_TRY(kl_launch_f32_to_bf16_t(w.dEKT, Vp, 4 * W, Vp, w.dEKT_bf, nullptr, Vp, 0, s));
       KL_TRY(kl_launch_f32_to_bf16_t(w.dEKT, Vp, 4 * W, Vp, w.dEK_bf, nullptr, 4 * W, 1, s));
+      }
       // dK0[:W] = E^T . dEK      (C[W][4W] = ET[W][Vp] . dEKT[4W][Vp]^T)
       KL_TRY(kl_launch_gemm_tn(d.ET, w.dEKT_bf, grads + h->off_K[0], nullptr, W, 4 * W, Vp, Vp, Vp, 4 * W, 0, 1, 1.f, s));
       // dE += dEK . K0[:W]^T     (C[V][W] = dEK[V][4W] . Kn0[W][4W]^T)
       KL_TRY(kl_launch_gemm_tn(w.dEK_bf, d.Kn[0], grads + h->off_E, nullptr, V, W, 4 * W, 4 * W, 4 * W, W, 2, 1, 1.f, s));
       for (int n = 0; n < c.n_ctx; ++n) {
-        if (!(pair_ctx && n == 0)) {
+        const bool seg_n = seg && n == 0;      // (its sums are there already, row-major)
+        if (!(pair_ctx && n == 0) && !seg_n) {
           if (kl_launch_onehot_dense(ctx, B, T, c.ctx_vocab, n, c.n_ctx, w.OHC[n], BTp, s) == KL_ERR_SHAPE) {
             KL_TRY(kl_zero_async(w.OHC[n], (size_t)c.ctx_vocab * BTp * sizeof(bf16_t), s));
             KL_TRY(kl_launch_onehot_t(ctx, B, T, c.ctx_vocab, n, c.n_ctx, w.OHC[n], BTp, s));
@@ -1407,8 +1440,8 @@ static int train_window_body(kl_handle* h, int B, int T, const int32_t* idx, con
         }
         const size_t krow = (size_t)(W + n * c.ctx_dim) * 4 * W;
         KL_TRY(kl_launch_ctx_grads(P + h->off_Ctx[n], P + h->off_K[0] + krow, 4 * W, c.ctx_vocab, c.ctx_dim,
-                                   w.dCtxKT[n], c.ctx_vocab, 4 * W, grads + h->off_K[0] + krow, 4 * W,
-                                   grads + h->off_Ctx[n], s));
+                                   w.dCtxKT[n], seg_n ? 1 : c.ctx_vocab, 4 * W, grads + h->off_K[0] + krow, 4 * W,
+                                   grads + h->off_Ctx[n], s, seg_n ? 4 * W : 1));
       }
     }
       return 0;
@@ -2181,6 +2214,18 @@ int kl_test_gemm_tn(const uint16_t* A, const uint16_t* B, void* C, const float* 
 int kl_test_gemm_an(const uint16_t* A_km, const uint16_t* B, float* C, int M, int N, int K, long lda_km, long ldb,
                     long ldc, int c_transposed, int b_km, void* stream) {
   return kl_launch_gemm_an(A_km, B, C, M, N, K, lda_km, ldb, ldc, c_transposed, (hipStream_t)stream, b_km);
+}
+
+size_t kl_test_segment_sums_ws_bytes(int B, int T, int n_ctx, int V, int R) {
+  if (B < 1 || T < 1 || V < 1 || n_ctx < 0 || (n_ctx > 0 && R < 1)) return 0;
+  return kl_segment_sums_ws_bytes(B, T, n_ctx, V, R);
+}
+
+int kl_test_segment_sums_share(int B, int T) { return B < 1 || T < 1 ? 0 : kl_segment_sums_share((long)B * T); }
+
+int kl_test_segment_sums(const uint16_t* dZ, long ld, int B, int T, int cols, const int32_t* idx, const int32_t* ctx, int n_ctx,
+                         int V, int R, float* dEK, float* dCtxK, void* ws, void* stream) {
+  return kl_launch_segment_sums(dZ, ld, B, T, cols, idx, ctx, n_ctx, V, R, dEK, dCtxK, ws, (hipStream_t)stream);
 }
 
 int kl_test_thin_gemm(const float* A, long lda, const uint16_t* WT_hi, const uint16_t* WT_lo, long ldw, int M, int N,

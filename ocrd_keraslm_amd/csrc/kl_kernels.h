@@ -317,9 +317,24 @@ int kl_launch_p1_gather(const float* EK, const float* const* ctxk, int n_ctx, co
 int kl_launch_colsum_bf16(const bf16_t* in, long ld, int rows, int cols, float* out, hipStream_t stream);
 int kl_launch_rows_to_state(const void* h_rows, int h_is_f32, const float* c_rows, int B, int W, int L, int layer,
                             float* states, hipStream_t stream);
+// (dT[col][r] at dT[col * ldt + r * ldr]: the transposed sums [N][ldt] with ldr = 1, the row-major ones [R][ldr] with ldt = 1)
 int kl_launch_ctx_grads(const float* Ctx, const float* K0rows, long ldk, int R, int D, const float* dT, long ldt, int N,
-                        float* gK, long ldg, float* gCtx, hipStream_t stream);
+                        float* gK, long ldg, float* gCtx, hipStream_t stream, long ldr = 1);
 int kl_launch_rows_tm_to_bm(const float* in, long ld_in, float* out, int B, int T, int V, hipStream_t stream);
+
+// ---- segsum.hip ---------------------------------------------------------
+// Layer 0's table gradients as segment sums over the time-major rows of dZ [T*B][ld] (bf16, cols of them used):
+//   dEK[v][cols]   = sum of the rows with idx[b][t] == v        (v in [0, V); other characters are dropped)
+//   dCtxK[c][cols] = sum of the rows with ctx[b][t][0] == c     (c in [0, R); other values are dropped, independently)
+// Both tables are row-major f32 and are zeroed here; ws holds the sort's arrays (kl_segment_sums_ws_bytes, 16-byte aligned)
+// and is rebuilt by every call.  n_ctx == 0: no context table.  KL_ERR_SHAPE beyond KL_SEGSUM_MAX_BUCKETS (character,
+// context value) pairs -- (V + 1) * (R + 1) counters, which one workgroup scans out of registers -- or cols % 8, ld % 8.
+#define KL_SEGSUM_MAX_BUCKETS 65535
+int kl_segment_sums_buckets(int n_ctx, int V, int R);
+int kl_segment_sums_share(long BT);      // sorted rows per wave of the gather pass
+size_t kl_segment_sums_ws_bytes(int B, int T, int n_ctx, int V, int R);
+int kl_launch_segment_sums(const bf16_t* dZ, long ld, int B, int T, int cols, const int* idx, const int* ctx, int n_ctx, int V, int R,
+                           float* dEK, float* dCtxK, void* ws, hipStream_t stream);
 
 // ---- rate_pick.hip ------------------------------------------------------
 // tprob[b][t] = softmax(logits[t*B + b])[tgt[b][t]] (0 where tgt < 0); the logits (time-major rows) are left as they are

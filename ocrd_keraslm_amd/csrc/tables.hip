@@ -77,25 +77,26 @@ __global__ void rows_to_state_kernel(const void* __restrict__ h_rows, int h_is_f
 // context-table gradients from dCtxKT [4W][ldt] f32 (transposed segment sums):
 //   gK[d][col]  += sum_r Ctx[r][d] * dCtxKT[col][r]          (rows W+10n.. of K0)
 //   gCtx[r][d]  += sum_col dCtxKT[col][r] * K0[W+10n+d][col]
-__global__ void ctx_grad_k_kernel(const float* __restrict__ Ctx, int R, int D, const float* __restrict__ dT, long ldt,
+// (element [col][r] lies at dT[col * ldt + r * ldr]: ldr = 1 for the transposed table, ldt = 1 for the row-major one)
+__global__ void ctx_grad_k_kernel(const float* __restrict__ Ctx, int R, int D, const float* __restrict__ dT, long ldt, long ldr,
                                   int N, float* __restrict__ gK, long ldg) {
   const long total = (long)D * N;
   for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
     const int d = (int)(e / N), col = (int)(e % N);
     float a = 0.f;
-    for (int r = 0; r < R; ++r) a = fmaf(Ctx[(long)r * D + d], dT[(long)col * ldt + r], a);
+    for (int r = 0; r < R; ++r) a = fmaf(Ctx[(long)r * D + d], dT[(long)col * ldt + r * ldr], a);
     gK[(long)d * ldg + col] += a;
   }
 }
 __global__ void ctx_grad_c_kernel(const float* __restrict__ Krows, long ldk, int R, int D, const float* __restrict__ dT,
-                                  long ldt, int N, float* __restrict__ gCtx) {
+                                  long ldt, long ldr, int N, float* __restrict__ gCtx) {
   // one wave per (r,d)
   const int lane = threadIdx.x & 63;
   const long item = blockIdx.x * (long)(blockDim.x >> 6) + (threadIdx.x >> 6);
   if (item >= (long)R * D) return;
   const int r = (int)(item / D), d = (int)(item % D);
   float a = 0.f;
-  for (int col = lane; col < N; col += 64) a = fmaf(dT[(long)col * ldt + r], Krows[(long)d * ldk + col], a);
+  for (int col = lane; col < N; col += 64) a = fmaf(dT[(long)col * ldt + r * ldr], Krows[(long)d * ldk + col], a);
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off);
   if (lane == 0) gCtx[(long)r * D + d] += a;
@@ -156,12 +157,12 @@ int kl_launch_rows_to_state(const void* h_rows, int h_is_f32, const float* c_row
 }
 
 int kl_launch_ctx_grads(const float* Ctx, const float* K0rows, long ldk, int R, int D, const float* dT, long ldt, int N,
-                        float* gK, long ldg, float* gCtx, hipStream_t stream) {
-  hipLaunchKernelGGL(ctx_grad_k_kernel, dim3(grid_for((long)D * N, 256)), dim3(256), 0, stream, Ctx, R, D, dT, ldt, N,
+                        float* gK, long ldg, float* gCtx, hipStream_t stream, long ldr) {
+  hipLaunchKernelGGL(ctx_grad_k_kernel, dim3(grid_for((long)D * N, 256)), dim3(256), 0, stream, Ctx, R, D, dT, ldt, ldr, N,
                      gK, ldg);
   const long items = (long)R * D;
   hipLaunchKernelGGL(ctx_grad_c_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, stream, K0rows, ldk, R, D, dT,
-                     ldt, N, gCtx);
+                     ldt, ldr, N, gCtx);
   return ok();
 }
 
