@@ -58,6 +58,7 @@ enum {
   KL_ERR_STATE = 3,      /* call order violated (e.g. not bound / not prepared) */
   KL_ERR_WORKSPACE = 4,  /* workspace too small */
   KL_ERR_ARG = 5         /* null or invalid argument */
+  /* (negative values are never returned: the library uses them internally) */
 };
 
 /* precision of the contractions */
@@ -215,8 +216,9 @@ int kl_step_batch_host(kl_handle* h, int n, const int32_t* idx, const int32_t* c
  * Rows may come in any order (the library orders them so that the rows still active at a step form a prefix), n may be any
  * positive count (more than 256 rows are walked in groups inside the call).
  * Launches: per step only the cell kernels, indices in the kernel arguments (the conditions of kl_step_batch_host's
- * 256-hypothesis path: one context variable, widths 64, 128 or a multiple of 256, V <= 65535; KL_HOST_KERNARG=0 disables
- * it); everything else chains kl_step_batch on ONE staged upload of all indices.  The output layer is deferred in both:
+ * 256-hypothesis path: one context variable, widths 64, 128 or a multiple of 256, V <= 65535, ctx_vocab <= 65536;
+ * KL_HOST_KERNARG=0 disables it); everything else chains kl_step_batch on ONE staged upload of all indices.  The output
+ * layer is deferred in both:
  * after the last step one launch contracts the top layer's h of all `total` (row, step) pairs with the embedding, keeps
  * a running maximum and sum per pair and delivers 4 bytes per pair -- no [total][V] array exists.  That launch serves EVERY
  * vocabulary and width the library accepts (any V, W % 32 == 0): there is no logits-GEMM fall-back.

@@ -1701,15 +1701,222 @@ int kl_adam_step(kl_handle* h, const float* grads, float* m, float* v, int t, fl
   return kl_adam_step_scaled(h, grads, 1.0f, m, v, t, lr, b1, b2, eps, clip, stream);
 }
 
+namespace {      // (its functions are `static` as well: inside extern "C" the namespace alone leaves their names exported)
+struct StepWs {
+  float* prow;           // P rows when n_ctx != 1
+  float* z;              // z of the gather + GEMM path
+  bf16_t* A3;            // ... its [hi | lo | hi] activation rows
+  bf16_t* rows[16];      // ... of every layer at once (fused form; config_ok: depth <= 16)
+  size_t bytes;
+};
+static StepWs step_carve(const kl_handle* h, int n, void* ws) {
+  const size_t W = h->cfg.width;
+  Carver cv(ws);
+  StepWs w;
+  w.prow = cv.take<float>((size_t)n * 4 * W);
+  w.z = cv.take<float>((size_t)n * 4 * W);
+  w.A3 = cv.take<bf16_t>((size_t)n * 3 * 2 * W);
+  for (int l = 0; l < h->cfg.depth; ++l) w.rows[l] = cv.take<bf16_t>((size_t)n * 3 * (l == 0 ? 1 : 2) * W);
+  w.bytes = align_up(cv.off, 256);
+  return w;
+}
+
+// what is added to a layer's gate inputs: T1[i1 ? i1[row] : row] + T2[i2[row]] + bias (null: none)
+struct GateSrc { const float* T1; const int32_t* i1; const float* T2; const int32_t* i2; const float* bias; };
+static GateSrc gate_src(const kl_handle* h, int l, const float* prow, const int32_t* idx, const int32_t* ctx) {
+  if (l > 0) return {nullptr, nullptr, nullptr, nullptr, h->params + h->off_b[l]};
+  if (prow) return {prow, nullptr, nullptr, nullptr, nullptr};      // gathered rows: b_0 is folded in
+  return {h->d.EK, idx, h->d.CtxK[0], ctx, h->params + h->off_b[0]};
+}
+
+// layer l of a step on step_tile.hip's / step_small.hip's kernels.  With the indices in the kernel arguments (KlHostIdx):
+// null slot arrays, the device index block as idx and ctx (non-null = "table rows by index"; the values are KlHostIdx's)
+static KlIncCellArgs inc_cell_args(const kl_handle* h, int l, int n, float* pool, const int32_t* slot_in, const int32_t* slot_out,
+                                   const float* prow, const int32_t* idx, const int32_t* ctx) {
+  const int W = h->cfg.width;
+  const GateSrc g = gate_src(h, l, prow, idx, ctx);
+  KlIncCellArgs a;
+  memset(&a, 0, sizeof(a));
+  a.n = n; a.W = W; a.split = h->precision;
+  a.pool = pool; a.slot_ld = (long)2 * h->cfg.depth * W; a.slot_in = slot_in; a.slot_out = slot_out;
+  a.h_off = 2 * l * W; a.c_off = (2 * l + 1) * W; a.x_off = l > 0 ? 2 * (l - 1) * W : -1;
+  a.UF = h->d.UF[l]; a.KF = h->d.KF[l];
+  a.T1 = g.T1; a.i1 = g.i1; a.T2 = g.T2; a.i2 = g.i2; a.bias = g.bias;
+  return a;
+}
+
+// the output layer: logits over the tied embedding from the top layer's new h (pool rows through `slots`) into out[n][V]
+// by the thin GEMM, then (softmax) the softmax in place
+static int output_thin(const kl_handle* h, int n, const float* pool, const int32_t* slots, float* out, bool softmax, hipStream_t s) {
+  const Derived& d = h->d;
+  const int W = h->cfg.width, L = h->cfg.depth, V = h->cfg.voc_size, split = h->precision;
+  KlOperand op;
+  memset(&op, 0, sizeof(op));
+  op.A = pool + (size_t)2 * (L - 1) * W; op.lda = (long)2 * L * W; op.row_index = slots; op.a_is_f32 = 1;
+  op.WT_hi = d.E_hi; op.WT_lo = split == 3 ? d.E_lo : nullptr; op.ldw = W; op.K = W;
+  KL_TRY(kl_launch_thin_gemm(&op, n, V, out, V, nullptr, split, s));
+  return softmax ? kl_launch_softmax_ce(out, V, n, V, nullptr, n, 1, 1.f, nullptr, 0, nullptr, nullptr, 0, s) : 0;
+}
+
+struct StepCall {        // a kl_step_batch call as its kernel paths see it
+  kl_handle* h; int n; const int32_t *idx, *ctx; float* pool; const int32_t *slot_in, *slot_out; float* probs;
+  const float* prow;     // layer 0's gathered gate inputs (n_ctx != 1); null: table rows by idx / ctx
+  hipStream_t s;
+};
+// a path's "not mine".  Not KL_ERR_SHAPE itself: a kernel's KL_ERR_SHAPE at layer 0 decides for all layers (the shapes are the
+// same) and becomes STEP_PASS, at a later layer it is an error and returned.  The public codes are 0 .. 5 (keraslm_hip.h).
+constexpr int STEP_PASS = -1;
+static_assert(STEP_PASS < KL_OK, "STEP_PASS must not be a public return code");
+
+// a launch per layer of inc_tile_kernel / inc_cell_kernel, then the output layer: logits + softmax in one launch where that applies
+static int step_layers(const StepCall& c, bool tiles) {
+  kl_handle* h = c.h;
+  const int W = h->cfg.width, L = h->cfg.depth, V = h->cfg.voc_size;
+  if (!h->inc_ready) KL_TRY(prepare_incremental(h, c.s));
+  for (int l = 0; l < L; ++l) {
+    const KlIncCellArgs a = inc_cell_args(h, l, c.n, c.pool, c.slot_in, c.slot_out, c.prow, c.idx, c.ctx);
+    const int e = tiles ? kl_launch_inc_tile(a, h->tile_var, c.s, h->tile_rows) : kl_launch_inc_cell(a, c.s);
+    if (e == KL_ERR_SHAPE && l == 0) return STEP_PASS;
+    if (e != 0) return e;
+  }
+  if (h->out_fused && c.n >= h->out_fused_min && h->d.EF) {
+    const int e = kl_launch_out_softmax(c.pool, (long)2 * L * W, c.slot_out, 2 * (L - 1) * W, h->d.EF, h->precision, c.n, W, V,
+                                        c.probs, V, c.s);
+    if (e != KL_ERR_SHAPE) return e;
+  }
+  return output_thin(h, c.n, c.pool, c.slot_out, c.probs, true, c.s);
+}
+
+// 256 hypotheses or more, widths of 256, 384, 512, ...: one launch per layer, tiles of 64 hypotheses x 32 units with the
+// state rows read through the pool slots and the weights from the hi / lo arrays as they are (step_tile.hip)
+// (width 1024 already from 129 hypotheses: inc_cell_kernel cannot hold two row tiles of K = 2048 in LDS there, and with one
+//  its W / 16 x n / 16 workgroups read every weight 16 times at 250 hypotheses -- 90 us per step against 51 on 64-row tiles)
+static int step_tiles(const StepCall& c) {
+  const kl_handle* h = c.h;
+  const int n = c.n, W = h->cfg.width, V = h->cfg.voc_size;
+  if (!((n >= KL_BIG_STEP_N || (W >= 1024 && n > 128)) && h->inc_tile && V < 1024 && h->d.EF)) return STEP_PASS;
+  return step_layers(c, true);
+}
+
+// 16 hypotheses and more (the reference's callers feed at most 128 / 256 rows; also whatever the tile kernel does not take:
+// widths 64 and 128): coalesced state rows through LDS, 16-unit workgroups (step_small.hip)
+static int step_cells(const StepCall& c) {
+  const kl_handle* h = c.h;
+  const int n = c.n, V = h->cfg.voc_size;
+  if (!(h->inc_small && n >= h->inc_small_min && (n < KL_BIG_STEP_N || V < 1024)) || !h->d.EF) return STEP_PASS;
+  return step_layers(c, false);
+}
+
+// 256 hypotheses or more and a workspace: gather + split -> one bf16 GEMM over the 3x contraction -> gates
+static int step_gemm(const StepCall& c, void* ws, size_t ws_bytes) {
+  kl_handle* h = c.h;
+  const int n = c.n, W = h->cfg.width, L = h->cfg.depth, V = h->cfg.voc_size;
+  if (!(n >= KL_BIG_STEP_N && ws && ws_bytes >= kl_step_workspace_bytes(h, n))) return STEP_PASS;
+  hipStream_t s = c.s;
+  if (!h->big_ready) KL_TRY(prepare_big_step(h, s));
+  Derived& d = h->d;
+  float* pool = c.pool;
+  const long slot_ld = (long)2 * L * W;
+  const StepWs w = step_carve(h, n, ws);
+  const int nb = h->precision == 3 ? 3 : 1;
+  // fused form: one gather of all layers' recurrent halves, then per layer ONE GEMM whose epilogue is the cell
+  // (gates, c', h', and h' as the next layer's input rows)
+  bool fusable = h->fused_step && (W & 31) == 0 && L <= KL_SCAN_MAXL && V < 1024;
+  for (int l = 0; l < L && fusable; ++l) fusable = d.WTperm[l] != nullptr && ((nb * (l == 0 ? W : 2 * W)) % 64) == 0;
+  if (fusable) {
+    KlGatherRec g;
+    memset(&g, 0, sizeof(g));
+    g.pool = pool; g.slot_ld = slot_ld; g.slot_in = c.slot_in; g.n = n; g.W = W; g.nb = nb;
+    for (int l = 0; l < L; ++l) g.out[l] = w.rows[l];
+    KL_TRY(kl_launch_gather_recurrent(g, L, s));
+    for (int l = 0; l < L; ++l) {
+      const int Kl = l == 0 ? W : 2 * W;
+      const GateSrc src = gate_src(h, l, c.prow, c.idx, c.ctx);
+      KlGateEpi e;
+      memset(&e, 0, sizeof(e));
+      e.W = W; e.T1 = src.T1; e.i1 = src.i1; e.T2 = src.T2; e.i2 = src.i2; e.bias = src.bias;
+      e.c_prev = pool + (size_t)(2 * l + 1) * W; e.c_ld = slot_ld; e.slot_in = c.slot_in;
+      e.c_out = pool + (size_t)(2 * l + 1) * W; e.h_out = pool + (size_t)2 * l * W; e.out_ld = slot_ld; e.slot_out = c.slot_out;
+      if (l + 1 < L) { e.xn = g.out[l + 1]; e.ldn = 3L * 2 * W; e.kn = 2 * W; e.nbn = nb; }
+      KL_TRY(kl_launch_gemm_gates(g.out[l], d.WTperm[l], n, W, nb * Kl, 3L * Kl, &e, s));
+    }
+    return output_thin(h, n, pool, c.slot_out, c.probs, true, s);
+  }
+  for (int l = 0; l < L; ++l) {
+    const int Kl = l == 0 ? W : 2 * W;
+    if (l == 0) {
+      KL_TRY(kl_launch_split_gather(pool, slot_ld, c.slot_in, W, nullptr, 0, nullptr, 0, n, nb, w.A3, 3L * Kl, s));
+    } else {
+      KL_TRY(kl_launch_split_gather(pool + (size_t)2 * (l - 1) * W, slot_ld, c.slot_out, W, pool + (size_t)2 * l * W, slot_ld,
+                                    c.slot_in, W, n, nb, w.A3, 3L * Kl, s));
+    }
+    KL_TRY(kl_launch_gemm_tn(w.A3, d.WTcat[l], w.z, nullptr, n, 4 * W, nb * Kl, 3L * Kl, 3L * Kl, 4 * W, 0, 1, 1.f, s));
+    const GateSrc src = gate_src(h, l, c.prow, c.idx, c.ctx);
+    KL_TRY(kl_launch_gates_rows(w.z, 4 * W, n, W, src.T1, src.i1, src.T2, src.i2, src.bias, pool + (size_t)(2 * l + 1) * W, slot_ld,
+                                c.slot_in, pool + (size_t)(2 * l + 1) * W, pool + (size_t)2 * l * W, slot_ld, c.slot_out, s));
+  }
+  if (V < 1024) return output_thin(h, n, pool, c.slot_out, c.probs, true, s);      // V x W is small: n/32 x V/16 workgroups
+  // wide vocabulary: big tiles pay off for the output projection too
+  KL_TRY(kl_launch_split_gather(pool + (size_t)2 * (L - 1) * W, slot_ld, c.slot_out, W, nullptr, 0, nullptr, 0, n, nb, w.A3, 3L * W, s));
+  KL_TRY(kl_launch_gemm_tn(w.A3, d.Ecat, c.probs, nullptr, n, V, nb * W, 3L * W, 3L * W, V, 0, 1, 1.f, s));
+  return kl_launch_softmax_ce(c.probs, V, n, V, nullptr, n, 1, 1.f, nullptr, 0, nullptr, nullptr, 0, s);
+}
+
+// everything else (fewer than 16 hypotheses, widths the kernels above do not take): a launch per layer of the thin
+// forward-step kernel
+static int step_thin(const StepCall& c) {
+  kl_handle* h = c.h;
+  const int n = c.n, W = h->cfg.width, L = h->cfg.depth, split = h->precision;
+  const long slot_ld = (long)2 * L * W;
+  Derived& d = h->d;
+  float* pool = c.pool;
+  for (int l = 0; l < L; ++l) {
+    const GateSrc src = gate_src(h, l, c.prow, c.idx, c.ctx);
+    KlFwdStep S;
+    memset(&S, 0, sizeof(S));
+    S.n_rows = n; S.W = W; S.split = split;
+    S.T1 = src.T1; S.i1 = src.i1; S.t1_ld = src.T1 ? 4 * W : 0;
+    S.T2 = src.T2; S.i2 = src.i2; S.t2_ld = src.T2 ? 4 * W : 0;
+    S.bias = src.bias;
+    int p = 0;
+    if (l > 0) {      // the layer below's new h . K^T
+      KlOperand& o = S.op[p++];
+      o.A = pool + (size_t)2 * (l - 1) * W; o.lda = slot_ld; o.row_index = c.slot_out; o.a_is_f32 = 1;
+      o.WT_hi = d.KT_hi[l]; o.WT_lo = split == 3 ? d.KT_lo[l] : nullptr; o.ldw = W; o.K = W;
+    }
+    KlOperand& u = S.op[p++];      // this layer's h . U^T
+    u.A = pool + (size_t)2 * l * W; u.lda = slot_ld; u.row_index = c.slot_in; u.a_is_f32 = 1;
+    u.WT_hi = d.UT_hi[l]; u.WT_lo = split == 3 ? d.UT_lo[l] : nullptr; u.ldw = W; u.K = W;
+    S.n_ops = p;
+    S.c_prev = pool + (size_t)(2 * l + 1) * W; S.c_prev_ld = slot_ld; S.c_prev_index = c.slot_in; S.out_index = c.slot_out;
+    S.c_out = pool + (size_t)(2 * l + 1) * W; S.c_out_ld = slot_ld;
+    S.h_out_f32 = pool + (size_t)2 * l * W; S.h_out_f32_ld = slot_ld;
+    KL_TRY(kl_launch_fwd_steps(&S, 1, c.s));
+  }
+  return output_thin(h, n, pool, c.slot_out, c.probs, true, c.s);
+}
+
+// may the indices of a step of n rows travel in the kernel arguments (KlHostIdx: characters and the one context variable
+// as halfwords; inc_cell_hx_kernel's widths)?  The callers still check the range of every index value.
+static bool host_idx_in_kernarg(const kl_handle* h, int n) {
+  const int W = h->cfg.width;
+  return h->cfg.voc_size <= 65535 && h->cfg.ctx_vocab <= 65536 && h->cfg.n_ctx == 1 && h->inc_small && h->d.EF && h->host_kernarg &&
+         ((W & 255) == 0 || W == 64 || W == 128) && !(W >= 1024 && n > 128);
+}
+
+// a host entry point's ticket counter: zeroed when its workspace is not the one remembered (afterwards every delivering
+// launch leaves it zero)
+static int arm_ticket_counter(void*& armed, unsigned* counter, hipStream_t s) {
+  if (armed == counter) return 0;
+  KL_TRY(kl_zero_async(counter, 64 * sizeof(unsigned), s));
+  armed = counter;
+  return 0;
+}
+}  // namespace
+
 size_t kl_step_workspace_bytes(const kl_handle* h, int n) {
   if (!h || n < 1) return 0;
-  Carver cv(nullptr);
-  cv.take<float>((size_t)n * 4 * h->cfg.width);          // P rows when n_ctx != 1
-  cv.take<float>((size_t)n * 4 * h->cfg.width);          // z of the big-n path
-  cv.take<bf16_t>((size_t)n * 3 * 2 * h->cfg.width);     // [hi | lo | hi] activation rows
-  for (int l = 0; l < h->cfg.depth; ++l)                 // ... of every layer at once (fused path)
-    cv.take<bf16_t>((size_t)n * 3 * (l == 0 ? 1 : 2) * h->cfg.width);
-  return align_up(cv.off, 256);
+  return step_carve(h, n, nullptr).bytes;
 }
 
 int kl_step_batch(kl_handle* h, int n, const int32_t* idx, const int32_t* ctx, float* pool, const int32_t* slot_in,
@@ -1717,183 +1924,19 @@ int kl_step_batch(kl_handle* h, int n, const int32_t* idx, const int32_t* ctx, f
   if (!h || !idx || !pool || !slot_in || !slot_out || !probs || n < 1) return KL_ERR_ARG;
   if (h->cfg.n_ctx > 0 && !ctx) return KL_ERR_ARG;
   if (!h->precision) return KL_ERR_STATE;
-  hipStream_t s = (hipStream_t)stream;
-  const kl_config& c = h->cfg;
-  const int W = c.width, L = c.depth, V = c.voc_size;
-  const long slot_ld = (long)2 * L * W;
-  const float* P = h->params;
-  Derived& d = h->d;
-  const int split = h->precision;
-  float* prow = nullptr;
-  if (c.n_ctx != 1) {
-    if (!ws || ws_bytes < kl_step_workspace_bytes(h, n)) return KL_ERR_WORKSPACE;
-    prow = reinterpret_cast<float*>(ws);
-    std::vector<const float*> ctxk(c.n_ctx);
-    for (int k = 0; k < c.n_ctx; ++k) ctxk[k] = d.CtxK[k];
-    // rows are hypotheses: treat as B = n streams, T = 1
-    KL_TRY(kl_launch_p1_gather(d.EK, ctxk.data(), c.n_ctx, P + h->off_b[0], idx, ctx, n, 1, 4 * W, prow, s));
+  StepCall c = {h, n, idx, ctx, pool, slot_in, slot_out, probs, nullptr, (hipStream_t)stream};
+  if (h->cfg.n_ctx != 1) {      // layer 0's gate inputs gathered first (rows are hypotheses: B = n streams, T = 1)
+    const StepWs w = step_carve(h, n, ws);
+    if (!ws || ws_bytes < w.bytes) return KL_ERR_WORKSPACE;
+    const float* ctxk[8];      // (config_ok: n_ctx <= 8)
+    for (int k = 0; k < h->cfg.n_ctx; ++k) ctxk[k] = h->d.CtxK[k];
+    KL_TRY(kl_launch_p1_gather(h->d.EK, ctxk, h->cfg.n_ctx, h->params + h->off_b[0], idx, ctx, n, 1, 4 * h->cfg.width, w.prow, c.s));
+    c.prow = w.prow;
   }
-  // the output layer of every path below: logits over the tied embedding from the top layer's new h, softmax in place
-  auto output_layer = [&]() -> int {
-    if (h->out_fused && n >= h->out_fused_min && d.EF) {
-      if (!h->inc_ready) KL_TRY(prepare_incremental(h, s));
-      const int e = kl_launch_out_softmax(pool, slot_ld, slot_out, 2 * (L - 1) * W, d.EF, split, n, W, V, probs, V, s);
-      if (e != KL_ERR_SHAPE) return e;
-    }
-    KlOperand op;
-    memset(&op, 0, sizeof(op));
-    op.A = pool + (size_t)2 * (L - 1) * W; op.lda = slot_ld; op.row_index = slot_out; op.a_is_f32 = 1;
-    op.WT_hi = d.E_hi; op.WT_lo = split == 3 ? d.E_lo : nullptr; op.ldw = W; op.K = W;
-    KL_TRY(kl_launch_thin_gemm(&op, n, V, probs, V, nullptr, split, s));
-    return kl_launch_softmax_ce(probs, V, n, V, nullptr, n, 1, 1.f, nullptr, 0, nullptr, nullptr, 0, s);
-  };
-  auto cell_args = [&](int l) {
-    KlIncCellArgs a;
-    memset(&a, 0, sizeof(a));
-    a.n = n; a.W = W; a.split = split;
-    a.pool = pool; a.slot_ld = slot_ld; a.slot_in = slot_in; a.slot_out = slot_out;
-    a.h_off = 2 * l * W; a.c_off = (2 * l + 1) * W; a.x_off = l > 0 ? 2 * (l - 1) * W : -1;
-    a.UF = d.UF[l]; a.KF = d.KF[l];
-    if (l == 0) {
-      if (prow) { a.T1 = prow; }
-      else { a.T1 = d.EK; a.i1 = idx; a.T2 = d.CtxK[0]; a.i2 = ctx; a.bias = P + h->off_b[0]; }
-    } else {
-      a.bias = P + h->off_b[l];
-    }
-    return a;
-  };
-  // 256 hypotheses or more, widths of 256, 384, 512, ...: one launch per layer, tiles of 64 hypotheses x 32 units with the
-  // state rows read through the pool slots and the weights from the hi / lo arrays as they are (step_tile.hip)
-  // (width 1024 already from 129 hypotheses: inc_cell_kernel cannot hold two row tiles of K = 2048 in LDS there, and with one
-  //  its W / 16 x n / 16 workgroups read every weight 16 times at 250 hypotheses -- 90 us per step against 51 on 64-row tiles)
-  if ((n >= KL_BIG_STEP_N || (W >= 1024 && n > 128)) && h->inc_tile && V < 1024 && d.EF) {
-    if (!h->inc_ready) KL_TRY(prepare_incremental(h, s));
-    int e = 0;
-    for (int l = 0; l < L && e == 0; ++l) {
-      e = kl_launch_inc_tile(cell_args(l), h->tile_var, s, h->tile_rows);
-      if (e == KL_ERR_SHAPE && l > 0) return e;      // (layer 0 decides for all: the shapes are the same)
-    }
-    if (e == 0) return output_layer();
-    if (e != KL_ERR_SHAPE) return e;
-  }
-  // 16 hypotheses and more (the reference's callers feed at most 128 / 256 rows; also whatever the tile kernel does not take:
-  // widths 64 and 128): coalesced state rows through LDS, 16-unit workgroups (step_small.hip); KL_ERR_SHAPE, or fewer rows:
-  // the gather + GEMM path / the launch-per-layer kernels below
-  if (h->inc_small && n >= h->inc_small_min && (n < KL_BIG_STEP_N || V < 1024)) {
-    int e = d.EF ? 0 : KL_ERR_SHAPE;
-    if (e == 0 && !h->inc_ready) KL_TRY(prepare_incremental(h, s));
-    for (int l = 0; l < L && e == 0; ++l) {
-      e = kl_launch_inc_cell(cell_args(l), s);
-      if (e == KL_ERR_SHAPE && l > 0) return e;      // (layer 0 decides for all: the shapes are the same)
-    }
-    if (e == 0) return output_layer();
-    if (e != KL_ERR_SHAPE) return e;
-  }
-  if (n >= KL_BIG_STEP_N && ws && ws_bytes >= kl_step_workspace_bytes(h, n)) {
-    if (!h->big_ready) KL_TRY(prepare_big_step(h, s));
-    // big-tile path: gather+split -> one bf16 GEMM over the 3x contraction -> gates
-    Carver cv(ws);
-    cv.take<float>((size_t)n * 4 * W);
-    float* z = cv.take<float>((size_t)n * 4 * W);
-    bf16_t* A3 = cv.take<bf16_t>((size_t)n * 3 * 2 * W);
-    const int nb = split == 3 ? 3 : 1;
-    // fused form: one gather of all layers' recurrent halves, then per layer ONE GEMM whose
-    // epilogue is the cell (gates, c', h', and h' as the next layer's input rows)
-    bool fusable = h->fused_step && (W & 31) == 0 && L <= KL_SCAN_MAXL && V < 1024;
-    for (int l = 0; l < L && fusable; ++l) fusable = d.WTperm[l] != nullptr && ((nb * (l == 0 ? W : 2 * W)) % 64) == 0;
-    if (fusable) {
-      KlGatherRec g;
-      memset(&g, 0, sizeof(g));
-      g.pool = pool; g.slot_ld = slot_ld; g.slot_in = slot_in; g.n = n; g.W = W; g.nb = nb;
-      for (int l = 0; l < L; ++l) g.out[l] = cv.take<bf16_t>((size_t)n * 3 * (l == 0 ? 1 : 2) * W);
-      KL_TRY(kl_launch_gather_recurrent(g, L, s));
-      for (int l = 0; l < L; ++l) {
-        const int Kl = l == 0 ? W : 2 * W;
-        const bool tab = l == 0 && !prow;
-        KlGateEpi e;
-        memset(&e, 0, sizeof(e));
-        if (l == 0) { e.T1 = prow ? prow : d.EK; e.i1 = tab ? idx : nullptr; e.T2 = tab ? d.CtxK[0] : nullptr; e.i2 = tab ? ctx : nullptr; }
-        e.bias = (l > 0 || tab) ? P + h->off_b[l] : nullptr;
-        e.c_prev = pool + (size_t)(2 * l + 1) * W; e.c_ld = slot_ld; e.slot_in = slot_in;
-        e.c_out = pool + (size_t)(2 * l + 1) * W; e.h_out = pool + (size_t)2 * l * W; e.out_ld = slot_ld; e.slot_out = slot_out;
-        if (l + 1 < L) { e.xn = g.out[l + 1]; e.ldn = 3L * 2 * W; e.kn = 2 * W; e.nbn = nb; }
-        e.W = W;
-        KL_TRY(kl_launch_gemm_gates(g.out[l], d.WTperm[l], n, W, nb * Kl, 3L * Kl, &e, s));
-      }
-      KlOperand op;
-      memset(&op, 0, sizeof(op));
-      op.A = pool + (size_t)2 * (L - 1) * W; op.lda = slot_ld; op.row_index = slot_out; op.a_is_f32 = 1;
-      op.WT_hi = d.E_hi; op.WT_lo = split == 3 ? d.E_lo : nullptr; op.ldw = W; op.K = W;
-      KL_TRY(kl_launch_thin_gemm(&op, n, V, probs, V, nullptr, split, s));
-      KL_TRY(kl_launch_softmax_ce(probs, V, n, V, nullptr, n, 1, 1.f, nullptr, 0, nullptr, nullptr, 0, s));
-      return 0;
-    }
-    for (int l = 0; l < L; ++l) {
-      const int Kl = l == 0 ? W : 2 * W;
-      if (l == 0) {
-        KL_TRY(kl_launch_split_gather(pool, slot_ld, slot_in, W, nullptr, 0, nullptr, 0, n, nb, A3, 3L * Kl, s));
-      } else {
-        KL_TRY(kl_launch_split_gather(pool + (size_t)2 * (l - 1) * W, slot_ld, slot_out, W, pool + (size_t)2 * l * W, slot_ld,
-                                      slot_in, W, n, nb, A3, 3L * Kl, s));
-      }
-      KL_TRY(kl_launch_gemm_tn(A3, d.WTcat[l], z, nullptr, n, 4 * W, nb * Kl, 3L * Kl, 3L * Kl, 4 * W, 0, 1, 1.f, s));
-      const bool tab = l == 0 && !prow;
-      KL_TRY(kl_launch_gates_rows(z, 4 * W, n, W, l == 0 ? (prow ? prow : d.EK) : nullptr, tab ? idx : nullptr,
-                                  tab ? d.CtxK[0] : nullptr, tab ? ctx : nullptr,
-                                  (l > 0 || tab) ? P + h->off_b[l] : nullptr, pool + (size_t)(2 * l + 1) * W, slot_ld, slot_in,
-                                  pool + (size_t)(2 * l + 1) * W, pool + (size_t)2 * l * W, slot_ld, slot_out, s));
-    }
-    if (V >= 1024) {   // wide vocabulary: big tiles pay off for the output projection too
-      KL_TRY(kl_launch_split_gather(pool + (size_t)2 * (L - 1) * W, slot_ld, slot_out, W, nullptr, 0, nullptr, 0, n, nb, A3, 3L * W, s));
-      KL_TRY(kl_launch_gemm_tn(A3, d.Ecat, probs, nullptr, n, V, nb * W, 3L * W, 3L * W, V, 0, 1, 1.f, s));
-    } else {           // V x W is small: the thin kernel spreads it over n/32 x V/16 workgroups
-      KlOperand op;
-      memset(&op, 0, sizeof(op));
-      op.A = pool + (size_t)2 * (L - 1) * W; op.lda = slot_ld; op.row_index = slot_out; op.a_is_f32 = 1;
-      op.WT_hi = d.E_hi; op.WT_lo = split == 3 ? d.E_lo : nullptr; op.ldw = W; op.K = W;
-      KL_TRY(kl_launch_thin_gemm(&op, n, V, probs, V, nullptr, split, s));
-    }
-    KL_TRY(kl_launch_softmax_ce(probs, V, n, V, nullptr, n, 1, 1.f, nullptr, 0, nullptr, nullptr, 0, s));
-    return 0;
-  }
-  for (int l = 0; l < L; ++l) {
-    KlFwdStep S;
-    memset(&S, 0, sizeof(S));
-    S.n_rows = n; S.W = W; S.split = split;
-    int p = 0;
-    if (l == 0) {
-      if (prow) {
-        S.T1 = prow; S.t1_ld = 4 * W;
-      } else {
-        S.T1 = d.EK; S.i1 = idx; S.t1_ld = 4 * W;
-        S.T2 = d.CtxK[0]; S.i2 = ctx; S.t2_ld = 4 * W;
-        S.bias = P + h->off_b[0];
-      }
-    } else {
-      KlOperand& o = S.op[p++];
-      o.A = pool + (size_t)2 * (l - 1) * W; o.lda = slot_ld; o.row_index = slot_out; o.a_is_f32 = 1;
-      o.WT_hi = d.KT_hi[l]; o.WT_lo = split == 3 ? d.KT_lo[l] : nullptr; o.ldw = W; o.K = W;
-      S.bias = P + h->off_b[l];
-    }
-    {
-      KlOperand& o = S.op[p++];
-      o.A = pool + (size_t)2 * l * W; o.lda = slot_ld; o.row_index = slot_in; o.a_is_f32 = 1;
-      o.WT_hi = d.UT_hi[l]; o.WT_lo = split == 3 ? d.UT_lo[l] : nullptr; o.ldw = W; o.K = W;
-    }
-    S.n_ops = p;
-    S.c_prev = pool + (size_t)(2 * l + 1) * W; S.c_prev_ld = slot_ld; S.c_prev_index = slot_in;
-    S.out_index = slot_out;
-    S.c_out = pool + (size_t)(2 * l + 1) * W; S.c_out_ld = slot_ld;
-    S.h_out_f32 = pool + (size_t)2 * l * W; S.h_out_f32_ld = slot_ld;
-    KL_TRY(kl_launch_fwd_steps(&S, 1, s));
-  }
-  KlOperand op;
-  memset(&op, 0, sizeof(op));
-  op.A = pool + (size_t)2 * (L - 1) * W; op.lda = slot_ld; op.row_index = slot_out; op.a_is_f32 = 1;
-  op.WT_hi = d.E_hi; op.WT_lo = split == 3 ? d.E_lo : nullptr; op.ldw = W; op.K = W;
-  KL_TRY(kl_launch_thin_gemm(&op, n, V, probs, V, nullptr, split, s));
-  KL_TRY(kl_launch_softmax_ce(probs, V, n, V, nullptr, n, 1, 1.f, nullptr, 0, nullptr, nullptr, 0, s));
-  return 0;
+  int e = step_tiles(c);      // the first path that takes the shape
+  if (e == STEP_PASS) e = step_cells(c);
+  if (e == STEP_PASS) e = step_gemm(c, ws, ws_bytes);
+  return e == STEP_PASS ? step_thin(c) : e;
 }
 
 // ---- the incremental step as a beam search issues it: one step per character, the GPU idle in between ----------------
@@ -1929,32 +1972,24 @@ int kl_step_batch_host(kl_handle* h, int n, const int32_t* idx, const int32_t* c
   hipStream_t s = (hipStream_t)stream;
   const kl_config& c = h->cfg;
   const int W = c.width, L = c.depth, V = c.voc_size, C = c.n_ctx;
-  const long slot_ld = (long)2 * L * W;
-  Derived& d = h->d;
   Carver cv(ws);
   unsigned* counter = cv.take<unsigned>(64);
   float* logits = cv.take<float>((size_t)n * V);
   int32_t* dev_idx = cv.take<int32_t>((size_t)n * (4 + (C > 0 ? C : 1)));
   unsigned char* rest = reinterpret_cast<unsigned char*>(ws) + align_up(cv.off, 256);
   const size_t rest_bytes = ws_bytes - align_up(cv.off, 256);
-  if (!h->host_step_ready) {      // (the counter of a fresh workspace; afterwards every finish launch leaves it zero)
-    KL_TRY(kl_zero_async(counter, 64 * sizeof(unsigned), s));
-    h->host_step_ready = ws;
-  } else if (h->host_step_ready != ws) {
-    KL_TRY(kl_zero_async(counter, 64 * sizeof(unsigned), s));
-    h->host_step_ready = ws;
-  }
+  KL_TRY(arm_ticket_counter(h->host_step_ready, counter, s));
   KlStepFinish f;
   memset(&f, 0, sizeof(f));
   f.n = n; f.V = V; f.W = W; f.logits = logits; f.ld = V;
   f.by_target = target != nullptr; f.head_k = head_k;
-  f.pool = pool; f.slot_ld = slot_ld;
+  f.pool = pool; f.slot_ld = (long)2 * L * W;
   f.probs_host = probs_host; f.heads_host = heads_host; f.done_host = done_host; f.ticket = ticket; f.counter = counter;
   // ---- up to 256 hypotheses on the 16-unit cell kernels: every index travels in the kernel arguments
-  bool in_range = n <= KL_HOST_STEP_MAX && V <= 65535 && C == 1 && h->inc_small && d.EF && h->host_kernarg;
+  bool in_range = n <= KL_HOST_STEP_MAX && host_idx_in_kernarg(h, n);
   for (int i = 0; i < n && in_range; ++i)
     in_range = idx[i] >= 0 && idx[i] < V && ctx[i] >= 0 && ctx[i] < c.ctx_vocab && (!target || (target[i] >= 0 && target[i] < V));
-  if (in_range && ((W & 255) == 0 || W == 64 || W == 128) && !(W >= 1024 && n > 128)) {
+  if (in_range) {
     static thread_local KlHostIdx hx;
     static thread_local KlHostTargets tx;
     for (int i = 0; i < n; ++i) {
@@ -1963,29 +1998,14 @@ int kl_step_batch_host(kl_handle* h, int n, const int32_t* idx, const int32_t* c
       if (target) tx.t[i] = (unsigned short)target[i];
     }
     if (!h->inc_ready) KL_TRY(prepare_incremental(h, s));
-    const int split = h->precision;
-    const float* P = h->params;
     int e = 0;
-    for (int l = 0; l < L && e == 0; ++l) {
-      KlIncCellArgs a;
-      memset(&a, 0, sizeof(a));
-      a.n = n; a.W = W; a.split = split;
-      a.pool = pool; a.slot_ld = slot_ld;
-      a.h_off = 2 * l * W; a.c_off = (2 * l + 1) * W; a.x_off = l > 0 ? 2 * (l - 1) * W : -1;
-      a.UF = d.UF[l]; a.KF = d.KF[l];
-      a.bias = P + h->off_b[l];
-      if (l == 0) {      // (i1 / i2 non-null = "table rows by index"; the values are hx's)
-        a.T1 = d.EK; a.i1 = dev_idx; a.T2 = d.CtxK[0]; a.i2 = dev_idx;
-      }
-      e = kl_launch_inc_cell(a, s, &hx, l == 0 ? dev_idx : nullptr);
+    for (int l = 0; l < L && e == 0; ++l) {      // (layer 0 leaves slot_out in dev_idx for the launches behind it)
+      e = kl_launch_inc_cell(inc_cell_args(h, l, n, pool, nullptr, nullptr, nullptr, dev_idx, dev_idx), s, &hx,
+                             l == 0 ? dev_idx : nullptr);
       if (e == KL_ERR_SHAPE && l > 0) return e;
     }
     if (e == 0) {
-      KlOperand op;
-      memset(&op, 0, sizeof(op));
-      op.A = pool + (size_t)2 * (L - 1) * W; op.lda = slot_ld; op.row_index = dev_idx; op.a_is_f32 = 1;
-      op.WT_hi = d.E_hi; op.WT_lo = split == 3 ? d.E_lo : nullptr; op.ldw = W; op.K = W;
-      KL_TRY(kl_launch_thin_gemm(&op, n, V, logits, V, nullptr, split, s));
+      KL_TRY(output_thin(h, n, pool, dev_idx, logits, false, s));
       f.softmax = 1; f.slot_out = dev_idx;
       return kl_launch_step_finish(f, target ? &tx : nullptr, s);
     }
@@ -1993,9 +2013,8 @@ int kl_step_batch_host(kl_handle* h, int n, const int32_t* idx, const int32_t* c
   }
   // ---- everything else: ONE copy of the packed indices to the device, the device-pointer step, delivery by the finish launch
   {
-    const int Cc = C > 0 ? C : 1;
     std::vector<int32_t>& pk = h->host_pack;
-    pk.resize((size_t)n * (4 + Cc));
+    pk.resize((size_t)n * (4 + (C > 0 ? C : 1)));
     memcpy(pk.data(), idx, (size_t)n * 4);
     memcpy(pk.data() + n, slot_in, (size_t)n * 4);
     memcpy(pk.data() + 2 * (size_t)n, slot_out, (size_t)n * 4);
@@ -2069,10 +2088,6 @@ int kl_walk_batch_host(kl_handle* h, int n, const int32_t* len, const int32_t* i
   hipStream_t s = (hipStream_t)stream;
   const kl_config& c = h->cfg;
   const int W = c.width, L = c.depth, V = c.voc_size, C = c.n_ctx;
-  const long slot_ld = (long)2 * L * W;
-  Derived& d = h->d;
-  const int split = h->precision;
-  const float* P = h->params;
   const WalkWs w = walk_carve(h, n, total, ws, ws_bytes);
   // rows ordered so that those still active at step t form a prefix: longest first, equal lengths in the caller's order
   // (a counting sort over the lengths 1 .. 1024)
@@ -2091,29 +2106,25 @@ int kl_walk_batch_host(kl_handle* h, int n, const int32_t* len, const int32_t* i
   memcpy(st + total, target, (size_t)total * 4);
   for (int i = 0; i < n; ++i) st[2 * (size_t)total + i] = slot_step[off[i] + len[i] - 1];
   const size_t head_words = walk_head_words(n, total);
-  if (w.counter != h->walk_ready) {      // (the counter of a fresh workspace; afterwards every output launch leaves it zero)
-    KL_TRY(kl_zero_async(w.counter, 64 * sizeof(unsigned), s));
-    h->walk_ready = w.counter;
-  }
+  KL_TRY(arm_ticket_counter(h->walk_ready, w.counter, s));
   if (!h->inc_ready) KL_TRY(prepare_incremental(h, s));
-  if (!d.EF) return KL_ERR_SHAPE;
+  if (!h->d.EF) return KL_ERR_SHAPE;
   KlWalkOut f;
   memset(&f, 0, sizeof(f));
-  f.total = total; f.n = n; f.V = V; f.W = W; f.lo = split == 3; f.head_k = head_k;
-  f.pool = pool; f.slot_ld = slot_ld; f.h_off = 2 * (L - 1) * W; f.EF = d.EF;
+  f.total = total; f.n = n; f.V = V; f.W = W; f.lo = h->precision == 3; f.head_k = head_k;
+  f.pool = pool; f.slot_ld = (long)2 * L * W; f.h_off = 2 * (L - 1) * W; f.EF = h->d.EF;
   f.slots = w.idx; f.targets = w.idx + total; f.last = w.idx + 2 * (size_t)total;
   f.tprob_host = tprob_host; f.heads_host = heads_host; f.done_host = done_host; f.ticket = ticket; f.counter = w.counter;
   // ---- the 16-unit cell kernels with every index of a step in the kernel arguments, groups of up to 256 rows
-  bool in_range = V <= 65535 && C == 1 && h->inc_small && h->host_kernarg;
-  in_range = in_range && ((W & 255) == 0 || W == 64 || W == 128) && !(W >= 1024 && n > 128);
+  bool in_range = host_idx_in_kernarg(h, n);
   for (int i = 0; i < n && in_range; ++i) in_range = ctx[i] >= 0 && ctx[i] < c.ctx_vocab;
   for (int p = 0; p < total && in_range; ++p) in_range = idx[p] >= 0 && idx[p] < V;
   if (in_range) {
     static thread_local KlHostIdx hx;
-    for (int g0 = 0; g0 < n; g0 += KL_HOST_STEP_MAX) {
+    for (int g0 = 0; g0 < n && in_range; g0 += KL_HOST_STEP_MAX) {
       const int g1 = g0 + KL_HOST_STEP_MAX < n ? g0 + KL_HOST_STEP_MAX : n;
       const int g_len = len[order[g0]];
-      for (int t = 0; t < g_len; ++t) {
+      for (int t = 0; t < g_len && in_range; ++t) {
         const int active = (count[t + 1] < g1 ? count[t + 1] : g1) - g0;      // rows of the group with len > t
         for (int j = 0; j < active; ++j) {
           const int r = order[g0 + j], p = off[r] + t;
@@ -2122,25 +2133,12 @@ int kl_walk_batch_host(kl_handle* h, int n, const int32_t* len, const int32_t* i
           hx.idx[j] = (unsigned short)idx[p];
           hx.ctx[j] = (unsigned short)ctx[r];
         }
-        for (int l = 0; l < L; ++l) {
-          KlIncCellArgs a;
-          memset(&a, 0, sizeof(a));
-          a.n = active; a.W = W; a.split = split;
-          a.pool = pool; a.slot_ld = slot_ld;
-          a.h_off = 2 * l * W; a.c_off = (2 * l + 1) * W; a.x_off = l > 0 ? 2 * (l - 1) * W : -1;
-          a.UF = d.UF[l]; a.KF = d.KF[l];
-          a.bias = P + h->off_b[l];
-          if (l == 0) {      // (i1 / i2 non-null = "table rows by index"; the values are hx's)
-            a.T1 = d.EK; a.i1 = w.idx; a.T2 = d.CtxK[0]; a.i2 = w.idx;
-          }
-          const int e = kl_launch_inc_cell(a, s, &hx, nullptr);
-          if (e == KL_ERR_SHAPE && (g0 || t || l)) return e;      // (the first launch decides for all: the shapes are the same)
-          if (e == KL_ERR_SHAPE) { in_range = false; break; }
-          if (e) return e;
+        for (int l = 0; l < L && in_range; ++l) {
+          const int e = kl_launch_inc_cell(inc_cell_args(h, l, active, pool, nullptr, nullptr, nullptr, w.idx, w.idx), s, &hx, nullptr);
+          if (e == KL_ERR_SHAPE && !(g0 || t || l)) in_range = false;      // (the first launch decides for all: the shapes are the same)
+          else if (e) return e;
         }
-        if (!in_range) break;
       }
-      if (!in_range) break;
     }
     if (in_range) {
       if (hipMemcpyAsync(w.idx, st, head_words * 4, hipMemcpyHostToDevice, s) != hipSuccess) return KL_ERR_LAUNCH;
