@@ -237,6 +237,34 @@ int kl_walk_batch_host(kl_handle* h, int n, const int32_t* len, const int32_t* i
 /* returns 0 once *done_host == ticket; KL_ERR_LAUNCH / KL_ERR_STATE after timeout_s seconds without it */
 int kl_step_wait(const uint32_t* done_host, uint32_t ticket, double timeout_s);
 
+/* One expansion and pruning step of generate's beam search ON THE DEVICE (rating.py:689-707: per hypothesis the 10 most
+ * likely characters with p >= 0.004, every continuation insorted by running cost, the first 256 kept), for `rows`
+ * hypotheses (1 .. 256) fanning out to at most `fan` (1 .. 16) continuations each.  All pointers are DEVICE pointers.
+ *   probs [rows][V] f32     what kl_step_batch just wrote (V = the handle's voc_size; 0 <= p <= 1)
+ *   cum_in [rows] f32       running cost per row, +inf = dead row (no candidates)
+ *   slot_new [rows]         the pool slots that step wrote (a survivor's next slot_in is its parent's entry)
+ *   valid [V] bytes         non-zero = the id may be generated; NULL = every id except 0
+ *   floor                   pass 0.004f (p >= floor is compared in f32; equal to the reference's f64 comparison for every f32 p)
+ * The reference's bookkeeping as a total order:
+ *   candidates of a live row = its `fan` largest probabilities -- equal values by smaller id first (this library's
+ *     definition: the reference leaves such ties to an unstable sort) --, of those the ones with p >= floor, of those the valid
+ *     ids (an invalid id among the `fan` largest still occupies its place);
+ *   cum = cum_in[row] + (-logf(p)): accurate logf, one f32 addition;
+ *   insertion sequence = row * fan + k, k counting a row's candidates from the least to the most probable;
+ *   survivors = the first `rows` candidates by (cum ascending, insertion sequence DESCENDING) -- what insort_left (a later
+ *     equal key goes in front) and truncation after every insertion leave.
+ * Outputs, entry i = survivor i in that order: idx_next (character id), slot_in_next (= slot_new[parent]), cum_next for the
+ * next step; parent_log (row index in THIS step), idx_log, cum_log for the log (a *_log pointer may equal its *_next
+ * pointer).  Entries beyond the survivors: id 0, zero_slot, +inf, parent -1.  *n_live = number of survivors.
+ * ws: device, >= kl_beam_workspace_bytes(h, rows, fan) (0 for arguments out of range), one per handle and stream.
+ * KL_ERR_ARG (null pointer, rows outside 1 .. 256, fan outside 1 .. 16) and KL_ERR_WORKSPACE are returned before anything is
+ * launched.  Two launches on `stream`, no synchronisation, no host memory touched. */
+size_t kl_beam_workspace_bytes(const kl_handle* h, int rows, int fan);
+int kl_beam_expand(kl_handle* h, int rows, int fan, float floor, const float* probs, const uint8_t* valid,
+                   const float* cum_in, const int32_t* slot_new, int32_t zero_slot, int32_t* idx_next,
+                   int32_t* slot_in_next, float* cum_next, int32_t* parent_log, int32_t* idx_log, float* cum_log,
+                   int32_t* n_live, void* ws, size_t ws_bytes, void* stream);
+
 /* Squared L2 distances between state vectors of pool slots, for beam history
  * clustering (rating.py:887-916): out[i] = || pool[a[i]][k] - pool[b[i]][k] ||^2
  * for state entry k (0 = h1, 1 = c1, ...). */

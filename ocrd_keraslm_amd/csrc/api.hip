@@ -2204,6 +2204,29 @@ int kl_state_dist2(const kl_handle* h, int n, const float* pool, const int32_t* 
   return hip_ok(hipGetLastError());
 }
 
+size_t kl_beam_workspace_bytes(const kl_handle* h, int rows, int fan) {
+  if (!h || rows < 1 || rows > KL_BEAM_MAX_ROWS || fan < 1 || fan > KL_BEAM_MAX_FAN) return 0;
+  return kl_beam_ws_bytes(rows, fan);
+}
+
+int kl_beam_expand(kl_handle* h, int rows, int fan, float floor, const float* probs, const uint8_t* valid, const float* cum_in,
+                   const int32_t* slot_new, int32_t zero_slot, int32_t* idx_next, int32_t* slot_in_next, float* cum_next,
+                   int32_t* parent_log, int32_t* idx_log, float* cum_log, int32_t* n_live, void* ws, size_t ws_bytes,
+                   void* stream) {
+  if (!h || !probs || !cum_in || !slot_new || !idx_next || !slot_in_next || !cum_next || !parent_log || !idx_log || !cum_log ||
+      !n_live)
+    return KL_ERR_ARG;
+  if (rows < 1 || rows > KL_BEAM_MAX_ROWS || fan < 1 || fan > KL_BEAM_MAX_FAN) return KL_ERR_ARG;
+  if (!ws || ws_bytes < kl_beam_ws_bytes(rows, fan)) return KL_ERR_WORKSPACE;
+  KlBeamExpand a;
+  memset(&a, 0, sizeof(a));
+  a.rows = rows; a.fan = fan; a.V = h->cfg.voc_size; a.floor = floor;
+  a.probs = probs; a.valid = valid; a.cum_in = cum_in; a.slot_new = slot_new; a.zero_slot = zero_slot;
+  a.idx_next = idx_next; a.slot_in_next = slot_in_next; a.cum_next = cum_next;
+  a.parent_log = parent_log; a.idx_log = idx_log; a.cum_log = cum_log; a.n_live = n_live;
+  return kl_launch_beam_expand(a, ws, (hipStream_t)stream);
+}
+
 int kl_test_gemm_tn(const uint16_t* A, const uint16_t* B, void* C, const float* bias, int M, int N, int K, long lda,
                     long ldb, long ldc, int out_mode, int splits, void* stream) {
   return kl_launch_gemm_tn(A, B, C, bias, M, N, K, lda, ldb, ldc, out_mode, splits, 1.f, (hipStream_t)stream);

@@ -394,6 +394,23 @@ struct KlWalkOut {
 };
 int kl_launch_walk_out(const KlWalkOut& a, hipStream_t stream);
 
+// ---- beam.hip -----------------------------------------------------------
+// one expansion and pruning step of generate's beam search (kl_beam_expand), see beam.hip; all pointers device
+#define KL_BEAM_MAX_ROWS 256
+#define KL_BEAM_MAX_FAN 16
+struct KlBeamExpand {
+  int rows, fan, V; float floor;
+  const float* probs;                // [rows][V]
+  const unsigned char* valid;        // [V], or null: every id except 0
+  const float* cum_in;               // [rows], +inf = dead row
+  const int* slot_new; int zero_slot;
+  int* idx_next; int* slot_in_next; float* cum_next;
+  int* parent_log; int* idx_log; float* cum_log; int* n_live;
+  unsigned long long* keys; int* cand;      // workspace, [rows * fan] each (set by the launcher)
+};
+size_t kl_beam_ws_bytes(int rows, int fan);
+int kl_launch_beam_expand(KlBeamExpand a, void* ws, hipStream_t stream);      // KL_ERR_ARG before anything is launched
+
 // ---- step_tile.hip: the same for n >= KL_BIG_STEP_N, TR x 128 tiles with the operands read once (variant: timing builds, 0)
 int kl_launch_inc_tile(const KlIncCellArgs& a, int variant, hipStream_t stream, int rows = -1);      // KL_ERR_SHAPE: not applicable; rows: 64 / 128 per tile, -1 = by size
 // output layer in one launch: probs[n][V] = softmax(h_top . E^T), h_top rows through slot_out (V <= 256, W % 128 == 0)

@@ -99,6 +99,7 @@ class HipLM:
         self._step_ws = None
         self._step_host_ws = None
         self._walk_ws = None
+        self._beam_ws = None
         self._wstage = None
         self._hio = None
         self._step_ws_bytes = {}
@@ -867,6 +868,84 @@ class HipLM:
         if head_k:
             heads = io["np"]["heads"][:n * head_k * self.pwidth].reshape(n, head_k, self.pwidth)[:, :, :self.width].copy()
         return tprob, heads
+
+    # ---- generate's beam search on the device (kl_beam_expand): expansion and pruning where the probabilities already are
+    def beam_expand(self, probs, cum_in, slot_new, zero_slot, fan, floor, valid=None, out=None):
+        """One expansion and pruning step of generate's search (rating.py:689-707) for the rows of `probs` (device [rows][V]
+        f32, what step_slots returned): cum_in [rows] f32 (+inf: dead row), slot_new [rows] int32 (the slots that step
+        wrote), valid [V] uint8 or None (every id except 0) -- device tensors.  Returns device tensors (idx [rows],
+        slot_in_next [rows], cum_next [rows], parent [rows], n_live [1]); `out` = those five, preallocated.  Launches on the
+        caller's current stream, no synchronisation (the order: genbeam.py, include/keraslm_hip.h)."""
+        torch = self.torch
+        rows = int(probs.shape[0])
+        fan = int(fan)
+        if (probs.dtype != torch.float32 or not probs.is_contiguous() or probs.shape[1] != self.voc_size
+                or cum_in.dtype != torch.float32 or cum_in.numel() != rows or slot_new.dtype != torch.int32
+                or slot_new.numel() != rows or (valid is not None and (valid.dtype != torch.uint8 or valid.numel() != self.voc_size))):
+            raise hipabi.KlError("beam_expand: probs f32 [rows][V], cum_in f32 [rows], slot_new int32 [rows], valid uint8 [V]")
+        if out is None:
+            out = (torch.empty(rows, dtype=torch.int32, device=self.device), torch.empty(rows, dtype=torch.int32, device=self.device),
+                   torch.empty(rows, dtype=torch.float32, device=self.device), torch.empty(rows, dtype=torch.int32, device=self.device),
+                   torch.empty(1, dtype=torch.int32, device=self.device))
+        idx, slot_in, cum, parent, n_live = out
+        key = ("beam", rows, fan)
+        nws = self._step_ws_bytes.get(key)
+        if nws is None:
+            nws = self._step_ws_bytes[key] = int(self.lib.kl_beam_workspace_bytes(self.handle, rows, fan))
+        if self._beam_ws is None or self._beam_ws.numel() < nws:
+            self._beam_ws = torch.empty(max(nws, 1 << 16), dtype=torch.uint8, device=self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        # (the log's row doubles as the next step's input: the *_log and *_next pointers are the same)
+        hipabi.check(self.lib.kl_beam_expand(self.handle, rows, fan, float(floor), _ptr(probs), _ptr(valid), _ptr(cum_in),
+                                             _ptr(slot_new), int(zero_slot), _ptr(idx), _ptr(slot_in), _ptr(cum), _ptr(parent),
+                                             _ptr(idx), _ptr(cum), _ptr(n_live), _ptr(self._beam_ws), self._beam_ws.numel(),
+                                             stream), "kl_beam_expand")
+        return out
+
+    def beam_generate(self, idx0, slot0, ctx, length, rows, fan, floor, valid, slots_a, slots_b, zero_slot):
+        """The whole search of `Rater.generate` enqueued back to back: for step s, step_slots on `rows` rows (dead rows run
+        too: they read zero_slot and write their own slot) into slot set s & 1 (reading the other), then beam_expand.  The
+        first step has one live row (character idx0 in the state of slot0).  No host synchronisation inside the loop; at the
+        end ONE copy brings the log.  Returns (parent [length][rows] int32, idx [length][rows] int32, cum [length][rows]
+        float32, n_live [length] int32) as numpy arrays (genbeam.backtrack reads them).  The pool must hold all slots named."""
+        torch = self.torch
+        length, rows = int(length), int(rows)
+        n = length * rows
+        sets = (np.asarray(slots_a, dtype=np.int32).reshape(-1), np.asarray(slots_b, dtype=np.int32).reshape(-1))
+        if len(sets[0]) != rows or len(sets[1]) != rows or rows < 1 or length < 1:
+            raise hipabi.KlError("beam_generate: two sets of %d slots and a positive length, please" % rows)
+        n_ctx = self.n_ctx
+        # everything the loop reads from the host in ONE upload: slot sets, context rows, the first fringe (cum as its bits)
+        first = np.zeros((3, rows), dtype=np.int32)
+        first[0, 0], first[1, :], first[1, 0] = idx0, zero_slot, slot0
+        first[2, :] = np.array([np.inf], dtype=np.float32).view(np.int32)[0]
+        first[2, 0] = 0
+        head = np.concatenate([sets[0], sets[1], first.reshape(-1),
+                               np.tile(np.asarray(ctx, dtype=np.int32).reshape(1, -1), (rows, 1)).reshape(-1)])
+        with torch.cuda.device(self.device):
+            head_d = self.to_device_i32(head)
+            valid_d = None
+            if valid is not None:
+                valid_d = torch.from_numpy(np.ascontiguousarray(valid, dtype=np.uint8).reshape(-1)).to(self.device, non_blocking=True)
+            set_d = (head_d[:rows], head_d[rows:2 * rows])
+            idx, slot_in, cum = head_d[2 * rows:3 * rows], head_d[3 * rows:4 * rows], head_d[4 * rows:5 * rows].view(torch.float32)
+            ctx_d = head_d[5 * rows:].view(rows, n_ctx) if n_ctx else None
+            log = torch.empty(3 * n + length, dtype=torch.int32, device=self.device)      # parent, idx, cum (bits), live counts
+            parent_rows = log[:n].view(length, rows).unbind(0)
+            idx_rows = log[n:2 * n].view(length, rows).unbind(0)
+            cum_rows = log[2 * n:3 * n].view(torch.float32).view(length, rows).unbind(0)
+            live = log[3 * n:]
+            slot_next = (torch.empty(rows, dtype=torch.int32, device=self.device),
+                         torch.empty(rows, dtype=torch.int32, device=self.device))
+            for s in range(length):
+                new = set_d[s & 1]
+                probs = self.step_slots(idx, ctx_d, slot_in, new)
+                self.beam_expand(probs, cum, new, zero_slot, fan, floor, valid_d,
+                                 out=(idx_rows[s], slot_next[s & 1], cum_rows[s], parent_rows[s], live[s:s + 1]))
+                idx, slot_in, cum = idx_rows[s], slot_next[s & 1], cum_rows[s]
+            host = log.cpu().numpy()      # (the one wait of the search)
+        return (host[:n].reshape(length, rows), host[n:2 * n].reshape(length, rows),
+                host[2 * n:3 * n].view(np.float32).reshape(length, rows), host[3 * n:])
 
     def to_device_i32(self, a):
         """one host-to-device transfer of an int32 array (rows stay contiguous views)"""

@@ -30,6 +30,7 @@ from __future__ import annotations
 
 import json
 import logging
+import os
 import signal
 import time
 from bisect import bisect_left, insort_left
@@ -38,7 +39,7 @@ from random import shuffle
 
 import numpy as np
 
-from . import lattice_beam, modelio, ratebatch, segments, streams, windows
+from . import genbeam, lattice_beam, modelio, ratebatch, segments, streams, windows
 from .node import Node
 
 PREC_BF16 = 1
@@ -187,6 +188,7 @@ class Rater(object):
         self.batched_streams_max_chars = 1 << 30
         self.edge_walk = False               # rate_best: every lattice edge's hypotheses walked through all their characters in ONE engine call (lattice_beam.walk_edge)
         self.edge_walk_slots = None          # ... slots one such call may be asked for (None: lattice_beam.walk_slot_budget of the pool's slot size)
+        self.device_beam = os.environ.get('KERASLM_DEVICE_BEAM', '') == '1'      # generate: the beam's expansion and pruning on the device, the whole search enqueued without a wait (HipLM.beam_generate)
         self.segment_streams = False         # fewer files than streams: cut the files into segments, one list of segments per stream (segments.py)
         self._engine_factory = engine_factory
         self._pool = None
@@ -1042,16 +1044,26 @@ class Rater(object):
         return preds, final_states
 
     # ------------------------------------------------------------------ beam searches
-    def generate(self, prefix, length, context=None, variants=1):
+    def generate(self, prefix, length, context=None, variants=1, device_beam=None):
         '''Generate `length` characters after `prefix` by beam search over the 10 best
         continuations with p >= 0.004 per hypothesis, 256 hypotheses wide
-        (rating.py:642-709).  Returns `variants` strings, each starting with prefix[-1].'''
+        (rating.py:642-709).  Returns `variants` strings, each starting with prefix[-1].
+
+        device_beam (None: the attribute `self.device_beam`, which KERASLM_DEVICE_BEAM=1 turns on): on an engine with
+        `beam_expand` the continuations are chosen and pruned where the probabilities are (kl_beam_expand), all `length`
+        steps are enqueued without a wait and the strings are spelled from one log of back-pointers (genbeam.py).  Same
+        strings; among exactly equal probabilities of one row the smaller id counts as the more probable.
+        The costs of the returned strings are left in `self.generate_costs`.'''
         assert self.status > 1
         assert self.stateful is False
         assert self.incremental is True
         if not context:
             context = self.underspecify_contexts()
         self._ensure_precision()
+        if device_beam is None:
+            device_beam = self.device_beam
+        if device_beam and hasattr(self.model, "beam_expand"):
+            return self._generate_device(prefix, length, context, variants)
         state = None
         for char in prefix[:-1]:
             _, states = self._predict_refs([char], [state], context)
@@ -1087,7 +1099,45 @@ class Rater(object):
                         keys.pop()
                         next_fringe.pop()
         best = next_fringe[0:variants]
+        self.generate_costs = [float(n.cum_cost) for n in best]
         return [''.join([n.value for n in res.to_sequence()]) for res in best]
+
+    def _generate_device(self, prefix, length, context, variants, rows=256, fan=10):
+        '''generate's search on the device (HipLM.beam_generate): the prefix warmed up in one engine call, 2 * rows working
+        slots taken from the pool for the duration (and the pool grown) before anything is enqueued, one wait at the end.'''
+        if length == 0:
+            self.generate_costs = [0.0]
+            return [prefix[-1]]
+        pool = self._state_pool()
+        lm = self.model
+        c_i, i_c = self.mapping
+        ctx = np.asarray(windows.clamp_context(context), dtype=np.int32)
+        warm_ids = [c_i.get(c, 0) for c in prefix[:-1]]
+        walk = getattr(lm, "walk_host", None)
+        slots = pool.take_slots(2 * rows + (len(warm_ids) if walk else 0))
+        try:
+            slot0, state = pool.zero_slot, None
+            if warm_ids and walk:
+                warm = slots[2 * rows:]
+                for at in range(0, len(warm_ids), 1024):      # (a walk's row takes up to 1024 steps)
+                    part = warm_ids[at:at + 1024]
+                    walk([len(part)], part, [0] * len(part), ctx[None, :], [slot0], warm[at:at + len(part)])
+                    slot0 = warm[at + len(part) - 1]
+            else:
+                for char in prefix[:-1]:
+                    _, states = self._predict_refs([char], [state], context)
+                    state = states[0]
+                if state is not None:
+                    slot0 = state.slot
+            valid = np.zeros(self.voc_size, dtype=np.uint8)
+            valid[[i for i in i_c if 0 <= i < self.voc_size]] = 1
+            log = lm.beam_generate(c_i.get(prefix[-1], 0), slot0, ctx, length, rows, fan, np.float32(0.004), valid,
+                                   slots[:rows], slots[rows:2 * rows], pool.zero_slot)
+        finally:
+            pool.release_slots(slots)
+        out = genbeam.backtrack(log, variants, i_c, prefix[-1])
+        self.generate_costs = [float(c) for c in log[2][-1][:len(out)]]
+        return out
 
     def rate_best(self, graph, start_node, end_node, start_traceback=None, context=None, lm_weight=0.5,
                   beam_width=10, beam_clustering_dist=0, edge_walk=None):

@@ -152,10 +152,14 @@ def test(model, data):
 @click.option('-v', '--variants', default=1, help='number of character sequences to sample',
               type=click.IntRange(min=1, max=10000))
 @click.option('-c', '--context', default=None, help='constant meta-data input')
+@click.option('--device-beam', is_flag=True, default=False,
+              help='expand and prune the beam on the GPU, all characters enqueued without a wait (Rater.device_beam)')
 @click.argument('prefix', type=click.STRING)
-def generate(model, number, variants, context, prefix):
+def generate(model, number, variants, context, device_beam, prefix):
     """Apply a language model, generating the most probable characters (starting with PREFIX string)."""
     rater = _load(model, incremental=True)
+    if device_beam:
+        rater.device_beam = True
     ctx = _contexts(context) if context else rater.underspecify_contexts()
     for res in rater.generate(prefix, number, ctx, variants):
         click.echo(prefix[:-1] + res)
