@@ -304,6 +304,26 @@ int kl_test_segment_sums(const uint16_t* dZ, long ld, int B, int T, int cols, co
                          int V, int R, float* dEK, float* dCtxK, void* ws, void* stream);
 int kl_test_thin_gemm(const float* A, long lda, const uint16_t* WT_hi, const uint16_t* WT_lo, long ldw, int M, int N,
                       int K, float* C, long ldc, int split, void* stream);
+/* The output layer of a training window (logits, softmax, clipped cross-entropy, accuracy, dlogits, dH) on caller buffers:
+ * each call is the launcher of one kernel family with its own applicability rule, KL_ERR_SHAPE before anything is launched
+ * where it does not apply.  Rows are time-major (r = t * B + b), tgt is [B][T] (-1 = padded position, < -1 = dummy stream),
+ * dlogits bf16 [rows][ld_dl] (columns from V on written as zeros), rowstat f32 [rows][2] = (loss, hit) per row, both
+ * already scaled by inv_count.
+ *   kl_test_softmax_ce      softmax over f32 logits [rows][ld] (strided kernel, or the one-pass kernel for V <= 256 with V,
+ *                           ld, ld_dl multiples of 4 and ld_dl <= 256); rowstat is written only with loss_acc != NULL, and
+ *                           loss_acc[0], [1] += the sums over the rows (the rowstat reduction)
+ *   kl_test_logits_ce_ws    width 512, V = 256: X bf16 [B*T][512], E bf16 [256][512]; B*T >= 8192, a multiple of 32
+ *   kl_test_logits_ce_w128  width 128: X bf16 [B*T][128], E bf16 [Vp][128] and ET bf16 [128][Vp] with zeros beyond V,
+ *                           V <= Vp <= 256, Vp a multiple of 32; also writes dH f32 [B*T][128] = dlogits . E
+ *   kl_test_dh_ws           width 512, Vp = 256: dH bf16 [M][512] = dlogits [M][256] . ET^T, ET bf16 [512][256];
+ *                           M >= 4096, a multiple of 32 */
+int kl_test_softmax_ce(float* logits, long ld, int rows, int V, const int32_t* tgt, int B, int T, float inv_count, uint16_t* dlogits,
+                       long ld_dl, float* rowstat, float* loss_acc, int last_only, void* stream);
+int kl_test_logits_ce_ws(const uint16_t* X, const uint16_t* E, const int32_t* tgt, uint16_t* dlogits, float* rowstat, int B, int T,
+                         float inv_count, int last_only, void* stream);
+int kl_test_logits_ce_w128(const uint16_t* X, const uint16_t* E, const uint16_t* ET, const int32_t* tgt, uint16_t* dlogits, float* dH,
+                           float* rowstat, int B, int T, int V, int Vp, float inv_count, int last_only, void* stream);
+int kl_test_dh_ws(const uint16_t* dlogits, const uint16_t* ET, uint16_t* dH, long M, void* stream);
 
 #ifdef __cplusplus
 }

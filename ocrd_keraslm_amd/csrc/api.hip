@@ -2257,6 +2257,25 @@ int kl_test_thin_gemm(const float* A, long lda, const uint16_t* WT_hi, const uin
   return kl_launch_thin_gemm(&op, M, N, C, ldc, nullptr, split, (hipStream_t)stream);
 }
 
+int kl_test_softmax_ce(float* logits, long ld, int rows, int V, const int32_t* tgt, int B, int T, float inv_count, uint16_t* dlogits,
+                       long ld_dl, float* rowstat, float* loss_acc, int last_only, void* stream) {
+  return kl_launch_softmax_ce(logits, ld, rows, V, tgt, B, T, inv_count, dlogits, ld_dl, loss_acc, rowstat, 1, (hipStream_t)stream, last_only);
+}
+
+int kl_test_logits_ce_ws(const uint16_t* X, const uint16_t* E, const int32_t* tgt, uint16_t* dlogits, float* rowstat, int B, int T,
+                         float inv_count, int last_only, void* stream) {
+  return kl_launch_logits_ce_ws(X, E, tgt, dlogits, rowstat, B, T, 512, 256, 256, inv_count, last_only, (hipStream_t)stream);
+}
+
+int kl_test_logits_ce_w128(const uint16_t* X, const uint16_t* E, const uint16_t* ET, const int32_t* tgt, uint16_t* dlogits, float* dH,
+                           float* rowstat, int B, int T, int V, int Vp, float inv_count, int last_only, void* stream) {
+  return kl_launch_logits_ce_w128(X, E, ET, tgt, dlogits, dH, rowstat, B, T, 128, V, Vp, inv_count, last_only, (hipStream_t)stream);
+}
+
+int kl_test_dh_ws(const uint16_t* dlogits, const uint16_t* ET, uint16_t* dH, long M, void* stream) {
+  return kl_launch_dh_ws(dlogits, ET, dH, M, 512, 256, (hipStream_t)stream);
+}
+
 }  // extern "C"
 
 // Tuning hook: launch `iters` identical forward cell steps (bf16 A, split 1) on raw

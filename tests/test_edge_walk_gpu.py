@@ -73,6 +73,8 @@ SHAPES = [
     # the staged upload + chained device-pointer step: 0 / 2 context variables, the switch, 300 rows on the tile kernels
     (2, 512, 64, 0, 50, "ragged", 0, {}), (3, 128, 40, 2, 128, "ragged", 3, {}),
     (2, 512, 256, 1, 7, "ragged", 2, {"KL_HOST_KERNARG": "0"}), (2, 512, 256, 1, 300, "ragged", 0, {"KL_HOST_KERNARG": "0"}),
+    # vocabularies of trained models at width 512: no multiple of 16, and more than 256 characters
+    (2, 512, 230, 1, 128, "ragged", 2, {}), (2, 512, 300, 1, 300, "ragged", 0, {}),
 ]
 
 
