@@ -325,6 +325,26 @@ int kl_test_logits_ce_w128(const uint16_t* X, const uint16_t* E, const uint16_t*
                            float* rowstat, int B, int T, int V, int Vp, float inv_count, int last_only, void* stream);
 int kl_test_dh_ws(const uint16_t* dlogits, const uint16_t* ET, uint16_t* dH, long M, void* stream);
 
+/* Test hook: where the handle's most recent kl_train_window of B streams x T steps on workspace ws left what its recurrence
+ * scans wrote, and how to read it.  All arrays are time-major with the padded width W = `width`: row r = block * B + b.
+ *   off_H   bf16 [(T+1)B][W]   outputs, block 0 = the carried-in h, block t + 1 = step t
+ *   off_C   f32  [(T+1)B][W]   cell states, block 0 = the carried-in c; with c_in_cb only blocks 0 and T are written
+ *   off_Cb  bf16 [(T+1)B][W]   cell states as the backward scan read them (c_in_cb only)
+ *   off_G   bf16 [TB][4W]      gate activations i, f, c, o: [4][W] per row, or [W][4] with g_interleaved
+ *   off_dZ  bf16 [TB][4W]      gradients of the gate pre-activations, always [4][W] per row
+ * Byte offsets into ws, per layer.  The rounding points the window's plan chose: p_bf16_mask bit l -- layer l's gate inputs
+ * from the input side (x . K + b) passed through bf16 rows; dh_bf16 -- the gradient from above (output layer and the layer
+ * above) passed through bf16 rows; c_in_cb -- the backward scan read bf16 cell states.  scan2_rows: rows per forward phase of
+ * the second-generation wide scans (0: another family).  Nothing is launched or allocated: the answer was noted when the
+ * window's launch sequence was built, so it also holds for a window that was a replayed graph.  KL_ERR_STATE if no
+ * training window of that shape has run on ws. */
+typedef struct kl_window_view {
+  int32_t depth, width, B, T;
+  int32_t g_interleaved, c_in_cb, dh_bf16, p_bf16_mask, scan2_rows, reserved[7];
+  uint64_t off_H[16], off_C[16], off_Cb[16], off_G[16], off_dZ[16];
+} kl_window_view;
+int kl_test_window_view(const kl_handle* h, int B, int T, const void* ws, kl_window_view* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -86,6 +86,7 @@ struct WindowWs {
   std::vector<bf16_t*> HTf, HdT;      // transposed outputs written by the wide forward scans: [W][(T+1)B], [W][BT]
   bool ht_ready = false;              // ... valid for this window
   bool km_plan = false;               // the weight-gradient GEMMs will read dZ and the activations K-major (row-major as written): no transposed copies
+  unsigned p_bf16_mask = 0;           // bit l: layer l's scan took its gate inputs as bf16 rows (noted for kl_test_window_view)
   bf16_t *dZT, *HT, *dlogits, *dlogitsT, *OHT, *dEKT_bf, *dEK_bf;
   std::vector<bf16_t*> OHC;
   bool segsum = false;                // layer 0's character / first-context sums by sorted segment sums (kl_segsum_applicable): dEKT and
@@ -176,6 +177,15 @@ struct kl_handle {
   bool regtile = true;          // KL_REGTILE = 0: the backward scan's tiles by LDS-DMA at every size (else through registers from five blocks per step)
   bool scan2_flags = true;      // KL_SCAN2_FLAGS = 0: the backward scan hands over by data sentinels at every size (else by flags from three blocks per step)
   bool flags_zeroed = false;
+  // what kl_test_window_view reports: noted by train_window_body per (B, T, workspace) while it builds the launch sequence (a
+  // replayed graph does not run the body again, and windows of other shapes may have run in between)
+  struct ViewNote {
+    int B, T;
+    const void* ws;
+    int scan2_rows, g_interleaved, c_in_cb, dh_bf16;
+    unsigned p_bf16_mask;
+  };
+  std::vector<ViewNote> view_notes;
   bool segsum = true;           // KL_SEGSUM = 0: layer 0's table gradients as one-hot products (default: sorted segment sums, segsum.hip -- read in
                                 // kl_create, it decides the window workspace's size)
   bool fuse_wg = true;          // KL_FUSE_WG = 0: one launch per weight-gradient product (else products over the same dZ share a pass)
@@ -651,6 +661,7 @@ int forward_impl(kl_handle* h, int B, int T, const int* idx, const int* ctx, flo
         a.n_ctx = c.n_ctx;
         a.ids_tm = w.ids_tm;
       }
+      if (a.p_bf16) w.p_bf16_mask |= 1u << l;
       if (took8) {}
       else if (v2) KL_TRY(kl_launch_scan_fwd_wide2(a, w.scan2_rows, s));
       else KL_TRY(kl_launch_scan_fwd_wide(a, s));
@@ -1286,6 +1297,17 @@ static int train_window_body(kl_handle* h, int B, int T, const int32_t* idx, con
   w.scan2_rows = plan_scan2(h, B, T, w.km_plan, true);
   w.scan2_bwd = w.scan2_rows != 0;
   KL_TRY(forward_impl(h, B, T, idx, ctx, states, masks, 1, w, s));
+  {
+    kl_handle::ViewNote note{B, T, ws, w.scan2_rows, w.scan2_bwd ? 1 : 0, (w.scan2_bwd && h->scan2_bf16) ? 1 : 0, w.scan2_bwd ? 1 : 0,
+                             w.p_bf16_mask};
+    bool found = false;
+    for (auto& n : h->view_notes)
+      if (n.B == B && n.T == T && n.ws == ws) { n = note; found = true; }
+    if (!found) {
+      if (h->view_notes.size() >= 64) h->view_notes.erase(h->view_notes.begin());
+      h->view_notes.push_back(note);
+    }
+  }
 
   // F5/F6: logits over the (masked) top-layer outputs, softmax, CE, dlogits
   const bool top_masked = masks != nullptr && L > 1;
@@ -2447,6 +2469,27 @@ extern "C" int kl_train_window(kl_handle* h, int B, int T, const int32_t* idx, c
   });
 }
 
+
+extern "C" int kl_test_window_view(const kl_handle* h, int B, int T, const void* ws, kl_window_view* out) {
+  if (!h || !ws || !out || B < 1 || T < 1) return KL_ERR_ARG;
+  const kl_handle::ViewNote* note = nullptr;
+  for (const auto& n : h->view_notes)
+    if (n.B == B && n.T == T && n.ws == ws) note = &n;
+  if (!note) return KL_ERR_STATE;
+  WindowWs w;
+  carve_window(h, const_cast<void*>(ws), B, T, 1, &w);
+  memset(out, 0, sizeof(*out));
+  out->depth = h->cfg.depth; out->width = h->cfg.width; out->B = B; out->T = T;
+  out->g_interleaved = note->g_interleaved; out->c_in_cb = note->c_in_cb; out->dh_bf16 = note->dh_bf16;
+  out->p_bf16_mask = (int32_t)note->p_bf16_mask; out->scan2_rows = note->scan2_rows;
+  const unsigned char* base = reinterpret_cast<const unsigned char*>(ws);
+  auto off = [&](const void* p) { return (uint64_t)(reinterpret_cast<const unsigned char*>(p) - base); };
+  for (int l = 0; l < h->cfg.depth; ++l) {      // (config_ok: at most 16 layers)
+    out->off_H[l] = off(w.H[l]); out->off_C[l] = off(w.C[l]); out->off_Cb[l] = off(w.Cb[l]);
+    out->off_G[l] = off(w.G[l]); out->off_dZ[l] = off(w.dZ[l]);
+  }
+  return 0;
+}
 
 // ---- per-launch timing of the step kernels (bench.py roofline leg) -----------------
 extern "C" int kl_trace_enable(kl_handle* h, int on) {

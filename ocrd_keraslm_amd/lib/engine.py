@@ -104,6 +104,7 @@ class HipLM:
         self._hio = None
         self._step_ws_bytes = {}
         self.last_only = False
+        self._last_window = None    # (streams run, T, first real stream, real streams, groups) of the last train_window
         self._rng = np.random.default_rng(0)
 
     def __del__(self):
@@ -515,6 +516,7 @@ class HipLM:
                                                       _ptr(self.states), _ptr(masks_d), _ptr(self.grads),
                                                       _ptr(self.loss_acc), _ptr(ws), ws.numel(), self._stream()),
                              "kl_train_window")
+                self._last_window = (B, T, 0, B, 1)
                 return
             # More streams than one launch sequence addresses (the scans index a layer's gate rows, T * B * 4W bf16, with 32-bit
             # buffer offsets: 3072 streams at cfg2), or a count none of the fast kernels takes: the streams are independent, so
@@ -563,6 +565,7 @@ class HipLM:
                         hipabi.check(self.lib.kl_set_loss_rows(self.handle, 0), "kl_set_loss_rows")
                 if Bp != n:
                     self.states[b0:b1] = st[:n]
+                self._last_window = (Bp, T, b0, n, len(parts))
                 if i == 0:
                     torch.mul(self._part_grads, wgt, out=self.grads)
                     self.loss_acc[2] += self._part_loss[2]
@@ -570,6 +573,20 @@ class HipLM:
                     self.grads.add_(self._part_grads, alpha=wgt)
                 self.loss_acc[:2] += wgt * self._part_loss[:2]
                 self.loss_acc[3] = torch.maximum(self.loss_acc[3], self._part_loss[3])
+
+    def window_view(self):
+        """Test hook (kl_test_window_view): where the last train_window left what its recurrence scans wrote.  Returns (view,
+        workspace, info): the kl_window_view, the uint8 workspace tensor its byte offsets point into, and info = dict(B -- streams
+        the kernels ran, dummy streams included --, T, first, n -- the real streams [first, first + n) of the batch that occupy
+        rows [0, n) --, groups).  With several stream groups (groups > 1) the workspace holds the LAST group only.  Decoding:
+        tests/window_ref.py."""
+        if self._last_window is None:
+            raise hipabi.KlError("window_view: no training window has run")
+        B, T, first, n, groups = self._last_window
+        view = hipabi.KlWindowView()
+        self.torch.cuda.synchronize(self.device)
+        hipabi.check(self.lib.kl_test_window_view(self.handle, B, T, _ptr(self._ws), C.byref(view)), "kl_test_window_view")
+        return view, self._ws, dict(B=B, T=T, first=first, n=n, groups=groups)
 
     def _plan_512(self, B, limit):
         """[(streams, run as)] for a batch of B streams at width 512.  The second-generation scans take every multiple of 512

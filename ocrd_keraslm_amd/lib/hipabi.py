@@ -22,6 +22,15 @@ class KlConfig(C.Structure):
                 ("n_ctx", C.c_int32), ("ctx_vocab", C.c_int32), ("ctx_dim", C.c_int32)]
 
 
+class KlWindowView(C.Structure):
+    """kl_window_view of include/keraslm_hip.h (kl_test_window_view)"""
+    _fields_ = [("depth", C.c_int32), ("width", C.c_int32), ("B", C.c_int32), ("T", C.c_int32),
+                ("g_interleaved", C.c_int32), ("c_in_cb", C.c_int32), ("dh_bf16", C.c_int32), ("p_bf16_mask", C.c_int32),
+                ("scan2_rows", C.c_int32), ("reserved", C.c_int32 * 7),
+                ("off_H", C.c_uint64 * 16), ("off_C", C.c_uint64 * 16), ("off_Cb", C.c_uint64 * 16),
+                ("off_G", C.c_uint64 * 16), ("off_dZ", C.c_uint64 * 16)]
+
+
 class KlError(RuntimeError):
     pass
 
@@ -96,6 +105,7 @@ SIGNATURES = {
     "kl_test_logits_ce_w128": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p]),
     "kl_test_dh_ws": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p]),
+    "kl_test_window_view": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(KlWindowView)]),
 }
 
 _lib = None

@@ -169,14 +169,48 @@ def step_batch(cfg, w, idx, ctx, states):
     return probs, out
 
 
-def forward_window(cfg, w, idx, ctx, states, dropout_masks=None, keep_cache=False):
+class Storage:
+    """Where the HIP training path keeps bf16 instead of f32 (the "bf16-storage oracle" of tests/window_ref.py).  Always: the
+    weight matrices K, U, E (not the biases, not the context tables and their rows of K0), the outputs h between steps and
+    layers (masked outputs too), the gate activations kept for the backward pass, dlogits and dZ.  Chosen by the window's
+    plan (kl_test_window_view): p_bf16[l] -- layer l's input side x . K + b passes through bf16 rows; dh_bf16 -- the gradient
+    from above (output layer, layer above) passes through bf16 rows; c_bf16 -- the backward pass reads bf16 cell states."""
+
+    def __init__(self, depth, p_bf16=None, dh_bf16=False, c_bf16=False):
+        self.p_bf16 = [bool(v) for v in (p_bf16 if p_bf16 is not None else [False] * depth)]
+        self.dh_bf16 = bool(dh_bf16)
+        self.c_bf16 = bool(c_bf16)
+
+    def key(self):
+        return (tuple(self.p_bf16), self.dh_bf16, self.c_bf16)
+
+
+def _stored_weights(cfg, w):
+    """the weights as the bf16 path holds them (see Storage)"""
+    W = cfg.width
+    out = dict(w)
+    out["E"] = bf16_round(w["E"]).astype(w["E"].dtype)
+    for l in range(cfg.depth):
+        K = w["K%d" % l]
+        Kr = K.copy()
+        Kr[:W] = bf16_round(K[:W])
+        out["K%d" % l] = Kr
+        out["U%d" % l] = bf16_round(w["U%d" % l]).astype(K.dtype)
+    return out
+
+
+def forward_window(cfg, w, idx, ctx, states, dropout_masks=None, keep_cache=False, storage=None):
     """F1-F5 over one window.  idx [B,T] int, ctx [B,T,n_ctx] int,
     states [h1,c1,..] each [B,W] (carried-in, rating.py:127-128 stateful).
     dropout_masks: None (inference) or list indexed by layer of [B,W] keep-masks
     already scaled by 1/0.9 (None for layer 0) -- time-constant (rating.py:146-152).
+    storage: None (exact arithmetic in the dtype of the inputs) or a Storage: bf16 rounding wherever the HIP
+    training path stores bf16; the cache then holds the rounded gates / h (and c with c_bf16), as that path's workspace does.
     Returns probs [B,T,V], final states, cache (for backward)."""
     W = cfg.width
     B, T = idx.shape
+    if storage is not None:
+        w = _stored_weights(cfg, w)
     x = embed(cfg, w, idx, ctx)  # [B,T,D0]
     cache = {"x": [], "gates": [], "c": [], "h": [], "hpre": [], "states_in": [s.copy() for s in states]}
     new_states = []
@@ -187,12 +221,25 @@ def forward_window(cfg, w, idx, ctx, states, dropout_masks=None, keep_cache=Fals
         if keep_cache:
             gs = np.empty((B, T, 4, W), dtype=x.dtype)
             cs = np.empty((B, T, W), dtype=x.dtype)
+        if storage is not None:
+            h = bf16_round(h).astype(x.dtype)      # (block 0 of the stored outputs)
+            P = x.reshape(B * T, -1) @ K + b
+            if storage.p_bf16[l]:
+                P = bf16_round(P).astype(x.dtype)
+            P = P.reshape(B, T, 4 * W)
         for t in range(T):
-            h, c, (i, f, g, o) = lstm_cell(x[:, t], h, c, K, U, b, W)
+            if storage is None:
+                h, c, (i, f, g, o) = lstm_cell(x[:, t], h, c, K, U, b, W)
+            else:
+                z = P[:, t] + h @ U
+                i, f, g, o = sigmoid(z[:, 0:W]), sigmoid(z[:, W:2 * W]), np.tanh(z[:, 2 * W:3 * W]), sigmoid(z[:, 3 * W:4 * W])
+                c = f * c + i * g
+                h = bf16_round(o * np.tanh(c)).astype(x.dtype)
+                i, f, g, o = (bf16_round(v).astype(x.dtype) for v in (i, f, g, o))
             hs[:, t] = h
             if keep_cache:
                 gs[:, t, 0], gs[:, t, 1], gs[:, t, 2], gs[:, t, 3] = i, f, g, o
-                cs[:, t] = c
+                cs[:, t] = bf16_round(c).astype(x.dtype) if (storage is not None and storage.c_bf16) else c
         new_states += [h, c]
         if keep_cache:
             cache["x"].append(x)
@@ -201,6 +248,8 @@ def forward_window(cfg, w, idx, ctx, states, dropout_masks=None, keep_cache=Fals
             cache["hpre"].append(hs)
         if dropout_masks is not None and l > 0 and dropout_masks[l] is not None:
             x = hs * dropout_masks[l][:, None, :]
+            if storage is not None:
+                x = bf16_round(x).astype(hs.dtype)
         else:
             x = hs
         if keep_cache:
@@ -270,12 +319,22 @@ def regulariser_grads(cfg, w):
     return g
 
 
-def backward_window(cfg, w, idx, ctx, tgt, probs, cache, dropout_masks=None, with_regularisers=True):
+def backward_window(cfg, w, idx, ctx, tgt, probs, cache, dropout_masks=None, with_regularisers=True, keep_dz=False,
+                    storage=None, count=None):
     """B1-B7: gradient of (mean CE [+ regularisers]) w.r.t. all weights.
-    Truncated BPTT: no gradient into the carried-in states."""
+    Truncated BPTT: no gradient into the carried-in states.
+    keep_dz: return (grads, dz) with dz a list per layer of [B,T,4,W] gradients of the gate pre-activations (i,f,c,o).
+    storage: see forward_window (the cache must come from a forward pass with the same storage).
+    count: the positions the mean is taken over (default B*T; a batch with dummy streams or one target per window:
+    the real streams x T, or the real windows)."""
     W = cfg.width
     B, T, V = probs.shape
     dt = probs.dtype
+    if count is None:
+        count = B * T
+    if storage is not None:
+        w = _stored_weights(cfg, w)
+    dzs = [None] * cfg.depth
     grads = {name: np.zeros(shape, dtype=np.float64) for name, shape in cfg.param_shapes()}
     valid = (tgt >= 0)
     tsafe = np.where(valid, tgt, 0)
@@ -285,10 +344,14 @@ def backward_window(cfg, w, idx, ctx, tgt, probs, cache, dropout_masks=None, wit
     dlog = probs * active[..., None]
     onehot = np.zeros_like(probs)
     np.put_along_axis(onehot, tsafe[..., None], active[..., None].astype(dt), axis=-1)
-    dlog = (dlog - onehot) / (B * T)
+    dlog = (dlog - onehot) / count
+    if storage is not None:
+        dlog = bf16_round(dlog).astype(dt)
     hL = cache["h"][-1]
     grads["E"] += dlog.reshape(-1, V).T.astype(np.float64) @ hL.reshape(-1, W).astype(np.float64)
     dx = dlog @ w["E"]  # [B,T,W]
+    if storage is not None and storage.dh_bf16:
+        dx = bf16_round(dx).astype(dt)
     for l in reversed(range(cfg.depth)):
         if dropout_masks is not None and l > 0 and dropout_masks[l] is not None:
             dx = dx * dropout_masks[l][:, None, :]
@@ -313,6 +376,8 @@ def backward_window(cfg, w, idx, ctx, tgt, probs, cache, dropout_masks=None, wit
             dz[:, t, W:2 * W] = df * f * (1 - f)
             dz[:, t, 2 * W:3 * W] = dg * (1 - g * g)
             dz[:, t, 3 * W:4 * W] = do * o * (1 - o)
+            if storage is not None:
+                dz[:, t] = bf16_round(dz[:, t])
             dh_rec = dz[:, t] @ U.T
             dc = dc * f
         hprev = np.concatenate([h0[:, None, :], hs[:, :-1]], axis=1)
@@ -320,7 +385,11 @@ def backward_window(cfg, w, idx, ctx, tgt, probs, cache, dropout_masks=None, wit
         grads["U%d" % l] += hprev.reshape(-1, W).astype(np.float64).T @ dz2
         grads["K%d" % l] += xs.reshape(-1, xs.shape[-1]).astype(np.float64).T @ dz2
         grads["b%d" % l] += dz2.sum(axis=0)
+        if keep_dz:
+            dzs[l] = dz.reshape(B, T, 4, W)
         dx = dz @ K.T
+        if storage is not None and storage.dh_bf16:
+            dx = bf16_round(dx).astype(dt)
     # scatter into embeddings
     np.add.at(grads["E"], idx.reshape(-1), dx[..., :W].reshape(-1, W).astype(np.float64))
     for n in range(cfg.n_ctx):
@@ -330,6 +399,8 @@ def backward_window(cfg, w, idx, ctx, tgt, probs, cache, dropout_masks=None, wit
         rg = regulariser_grads(cfg, w)
         for k, v in rg.items():
             grads[k] += v
+    if keep_dz:
+        return grads, dzs
     return grads
 
 

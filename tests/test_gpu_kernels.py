@@ -802,6 +802,13 @@ def check_train_window_gradients(depth, width, voc, B, T, n_ctx, use_masks, want
     st_got = lm.get_states()
     for k in range(2 * depth):
         assert np.abs(st_got[:, k] - ref_st[k]).max() < 2e-2
+    # what the scans left in the workspace, the checks without tolerance (tests/window_ref.py): no NaN / Inf halfword in H, G, dZ
+    # (a sentinel that survived), the engine's own dummy streams' dZ exactly zero, block 0 = the carried-in state, block T =
+    # the carried-out state.  (Stream groups: the workspace holds the last group.)
+    from tests.window_ref import exact_checks, read_window
+    win = read_window(lm)
+    first, n = win["info"]["first"], win["info"]["n"]
+    exact_checks(win, states[first:first + n], st_got[first:first + n], n, where=(depth, width, voc, B, T, n_ctx))
 
 
 def test_adam_step_matches_oracle():

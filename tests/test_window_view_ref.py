@@ -1,0 +1,186 @@
+"""The tile check of the training window's intermediates (tests/window_ref.py) without a GPU: the oracle's new arguments
+leave its default results untouched, the layout decoders round-trip, the checker catches one wrong tile of every kind, and
+the inputs of every GPU case (tests/test_window_intermediates_gpu.py) keep the floor out of the way -- decided from the f64
+oracle alone."""
+import numpy as np
+import pytest
+
+from oracle import lstm_oracle as O
+from tests import window_ref as R
+from tests.gradcheck import cached_weights
+
+SMALL = R._case("small", "none", {}, (2, 128, 40, 40, 5), "", "")
+
+
+def _weights(case):
+    return cached_weights(case.depth, case.width, case.voc, case.n_ctx, 4, 0.3)
+
+
+def test_no_rounding_requested_is_the_oracle_bit_for_bit():
+    """storage=None, keep_dz and an explicit count of B*T change nothing, and the dz handed back is the dz the bias
+    gradients were summed from"""
+    case = SMALL
+    cfg = O.ModelConfig(case.depth, case.width, case.voc, case.n_ctx)
+    w = {k: v.astype(np.float64) for k, v in _weights(case).items()}
+    inp = R.make_inputs(case)
+    st = [inp["states"][:, k].astype(np.float64) for k in range(2 * case.depth)]
+    om = [None] + [inp["masks"][l].astype(np.float64) for l in range(1, case.depth)]
+    p0, s0, c0 = O.forward_window(cfg, w, inp["idx"], inp["ctx"], st, om, keep_cache=True)
+    p1, s1, c1 = O.forward_window(cfg, w, inp["idx"], inp["ctx"], st, om, keep_cache=True, storage=None)
+    assert np.array_equal(p0, p1) and all(np.array_equal(a, b) for a, b in zip(s0, s1))
+    g0 = O.backward_window(cfg, w, inp["idx"], inp["ctx"], inp["tgt"], p0, c0, om)
+    g1, dz = O.backward_window(cfg, w, inp["idx"], inp["ctx"], inp["tgt"], p1, c1, om, keep_dz=True, storage=None,
+                               count=case.B * case.T)
+    assert set(g0) == set(g1) and all(np.array_equal(g0[k], g1[k]) for k in g0)
+    for l in range(case.depth):
+        assert dz[l].shape == (case.B, case.T, 4, case.width)
+        assert np.array_equal(dz[l].reshape(-1, 4 * case.width).sum(axis=0), g0["b%d" % l])
+    # ... and the storage rounding does something: bf16 numbers where the HIP path stores bf16
+    p2, _s, c2 = O.forward_window(cfg, w, inp["idx"], inp["ctx"], st, om, keep_cache=True, storage=O.Storage(case.depth))
+    for name in ("hpre", "gates"):
+        a = c2[name][0]
+        assert np.array_equal(a, O.bf16_round(a)) and not np.array_equal(a, c0[name][0])
+
+
+@pytest.mark.parametrize("interleaved,cb,width,n", [(0, 0, 128, 40), (1, 1, 128, 40), (1, 0, 100, 33), (0, 1, 100, 24)])
+def test_layout_decoders_round_trip(interleaved, cb, width, n):
+    """canonical arrays -> a workspace as the view describes it -> the same arrays, with gate-interleaved G, bf16 cell
+    states, a padded width (100 of 128) and padded streams (n of 40); everything around them is 0xFF bytes"""
+    L, Wp, B, T = 2, 128, 40, 3
+    rng = np.random.default_rng(3)
+    bf = lambda shape: O.bf16_round(rng.standard_normal(shape).astype(np.float32))
+    arrs = dict(h=[bf((n, T, width)) for _ in range(L)], gates=[bf((n, T, 4, width)) for _ in range(L)],
+                dz=[bf((n, T, 4, width)) for _ in range(L)], h0=[bf((n, width)) for _ in range(L)],
+                c0=[rng.standard_normal((n, width)).astype(np.float32) for _ in range(L)],
+                cT=[rng.standard_normal((n, width)).astype(np.float32) for _ in range(L)])
+    arrs["c"] = [bf((n, T, width)) if cb else rng.standard_normal((n, T, width)).astype(np.float32) for _ in range(L)]
+    if not cb:
+        for l in range(L):
+            arrs["c"][l][:, -1] = arrs["cT"][l]      # (block T is one array)
+    view = dict(depth=L, width=Wp, B=B, T=T, g_interleaved=interleaved, c_in_cb=cb, dh_bf16=0, p_bf16_mask=0, scan2_rows=0)
+    off, offs = 0, {}
+    for key, size in (("off_H", (T + 1) * B * Wp * 2), ("off_C", (T + 1) * B * Wp * 4), ("off_G", T * B * 4 * Wp * 2),
+                      ("off_dZ", T * B * 4 * Wp * 2), ("off_Cb", (T + 1) * B * Wp * 2)):
+        offs[key] = []
+        for _l in range(L):
+            off = (off + 255) // 256 * 256 + 256
+            offs[key].append(off)
+            off += size
+    view.update(offs)
+    ws = R.encode_window(arrs, view)
+    got = R.decode_window(ws, view, width=width, n=n)
+    for key in ("h", "c", "gates", "dz", "h0", "c0", "cT"):
+        for l in range(L):
+            assert np.array_equal(got[key][l], arrs[key][l]), (key, l)
+    # the bytes really lie as the header says: gate g of unit u of stream b at step t
+    import torch
+    t, b, g, u, l = 1, n - 1, 2, width - 1, 1
+    G = ws[view["off_G"][l]:view["off_G"][l] + T * B * 4 * Wp * 2].view(torch.bfloat16)
+    at = (t * B + b) * 4 * Wp + (u * 4 + g if interleaved else g * Wp + u)
+    assert float(G[at]) == arrs["gates"][l][b, t, g, u]
+    # rows and columns beyond the trimmed ones are the fill: the finite check sees them when it is given all of them
+    full = width == Wp and n == B
+    assert got["finite"] == dict(h=full, gates=full, dz=full, cb=full or not cb)
+
+
+@pytest.fixture(scope="module")
+def small_refs():
+    inp = R.make_inputs(SMALL)
+    w = _weights(SMALL)
+    return inp, R.references(SMALL, w, inp), R.references(SMALL, w, inp, O.Storage(SMALL.depth))
+
+
+def _copy(emu):
+    return {k: [a.copy() for a in v] for k, v in emu.items()}
+
+
+def test_checker_passes_the_emulation(small_refs):
+    inp, r64, emu = small_refs
+    rep = R.check_tiles(emu, r64, emu, inp["n_real"])
+    assert all(abs(v["ratio"] - 1.0) < 1e-12 for v in rep.values())
+
+
+@pytest.mark.parametrize("name", R.ARRAYS)
+@pytest.mark.parametrize("kind", ["next step", "swapped blocks", "sentinels"])
+def test_checker_catches_one_wrong_tile(small_refs, name, kind):
+    """synthetic kernel output = the emulation with ONE tile (two for the swap) of one array wrong"""
+    inp, r64, emu = small_refs
+    got = _copy(emu)
+    l, t = 1, 2
+    a = got[name][l]
+    if kind == "next step":
+        a[0:16, t] = a[0:16, t + 1]
+    elif kind == "swapped blocks":
+        a[0:16, t], a[16:32, t] = a[16:32, t].copy(), a[0:16, t].copy()
+    else:
+        a[0:16, t] = np.frombuffer(np.full(1, 0xFFFF0000, dtype=np.uint32).tobytes(), dtype=np.float32)[0]      # bf16 0xFFFF
+    with pytest.raises(AssertionError) as err:
+        R.check_tiles(got, r64, emu, inp["n_real"])
+    text = str(err.value)
+    assert "'%s', 'layer %d', 'step %d', 'block 0'" % (name, l, t) in text
+    assert ("2 tiles" if kind == "swapped blocks" else "1 tiles") in text
+
+
+def test_checker_catches_a_dropped_cell_gradient(small_refs):
+    inp, r64, emu = small_refs
+    got = _copy(emu)
+    l, t, blk = 0, 1, 0
+    got["dz"][l][blk * 16:(blk + 1) * 16, t] = R.zero_dc_tile(emu, l, t, blk)
+    with pytest.raises(AssertionError) as err:
+        R.check_tiles(got, r64, emu, inp["n_real"])
+    assert "'dz', 'layer %d', 'step %d', 'block %d'" % (l, t, blk) in str(err.value) and "1 tiles" in str(err.value)
+
+
+def test_exact_checks_catch_a_sentinel_and_a_dummy_stream_gradient(small_refs):
+    import torch
+    inp, _r64, emu = small_refs
+    case = SMALL
+    L, W, B, T = case.depth, case.width, case.B, case.T
+    st_in = inp["states"]
+    st_out = np.stack([a for l in range(L) for a in (emu["h"][l][:, -1], emu["c"][l][:, -1])], axis=1)
+    arrs = dict(emu, h0=[O.bf16_round(st_in[:, 2 * l]) for l in range(L)], c0=[st_in[:, 2 * l + 1] for l in range(L)],
+                cT=[emu["c"][l][:, -1] for l in range(L)])
+    view = dict(depth=L, width=W, B=B, T=T, g_interleaved=0, c_in_cb=0, dh_bf16=0, p_bf16_mask=0, scan2_rows=0)
+    off = 0
+    for key, size in (("off_H", (T + 1) * B * W * 2), ("off_C", (T + 1) * B * W * 4), ("off_Cb", (T + 1) * B * W * 2),
+                      ("off_G", T * B * 4 * W * 2), ("off_dZ", T * B * 4 * W * 2)):
+        view[key] = [off + l * size for l in range(L)]
+        off += L * size
+    ws = R.encode_window(arrs, view)
+    R.exact_checks(R.decode_window(ws, view), st_in, st_out, inp["n_real"])
+    bad = ws.clone()
+    bad[view["off_dZ"][1] + 2 * (1 * B + 3) * 4 * W:][:32] = 0xFF      # 16 halfwords of step 1, stream 3
+    with pytest.raises(AssertionError, match="NaN"):
+        R.exact_checks(R.decode_window(bad, view), st_in, st_out, inp["n_real"])
+    bad = ws.clone()
+    bad[view["off_dZ"][0] + 2 * (2 * B + B - 1) * 4 * W + 1] = 0x3C      # one halfword of the last (dummy) stream
+    with pytest.raises(AssertionError, match="dummy"):
+        R.exact_checks(R.decode_window(bad, view), st_in, st_out, inp["n_real"])
+    bad = ws.clone()
+    bad[view["off_C"][0] + 5] ^= 1      # one bit of the carried-in cell state
+    with pytest.raises(AssertionError, match="C block 0"):
+        R.exact_checks(R.decode_window(bad, view), st_in, st_out, inp["n_real"])
+
+
+def _input_sets():
+    seen, out = set(), []
+    for case in R.CASES + [R.REPLAY_A, R.REPLAY_B, R.CONSECUTIVE]:
+        key = (case[3:9], case.last_only)
+        if key not in seen:
+            seen.add(key)
+            out.append(case)
+    return out
+
+
+@pytest.mark.parametrize("case", _input_sets(), ids=lambda c: c.name)
+def test_floor_share_of_the_gpu_cases(case):
+    """at most 5 % of the non-dummy tiles of any array and layer may be measured against the floor instead of their own norm
+    (none is, at the chosen inputs), and every case has an all-dummy block and a half-dummy one where it has the rows"""
+    inp = R.make_inputs(case)
+    n_real, B = inp["n_real"], case.B
+    assert (inp["tgt"][n_real:] == -2).all() and (inp["tgt"][:n_real] >= -1).all()
+    if B > 16:
+        assert n_real % 16 == 8 and len(R.dummy_blocks(B, n_real)) == 1
+    share = R.floor_share(R.references(case, _weights(case), inp), n_real, B)
+    print(case.name, "largest floor share %.4f" % max(share.values()))
+    assert max(share.values()) <= R.FLOOR_SHARE_MAX, share
