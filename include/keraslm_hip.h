@@ -13,6 +13,7 @@
  *   model.predict_generator (windows), :516                  kl_forward_window (tgt = NULL)
  *   model.evaluate_generator, :490                           kl_forward_window (tgt != NULL)
  *   Rater.rate, :493-529, for many texts at once             kl_rate_window (one text per stream, target-only delivery)
+ *   ... with the model's top-K characters and the target's rank  kl_rate_window_alts
  *   model.predict_on_batch, stateful (1,1) step, :566        kl_forward_window with T = 1
  *   model.predict_on_batch, incremental + states, :631       kl_step_batch
  *   ... once per character of a lattice edge, :796-851       kl_walk_batch_host (all characters of all hypotheses, one call)
@@ -139,6 +140,25 @@ int kl_forward_window(kl_handle* h, int B, int T, const int32_t* idx, const int3
 size_t kl_rate_workspace_bytes(const kl_handle* h, int B, int T);
 int kl_rate_window(kl_handle* h, int B, int T, const int32_t* idx, const int32_t* ctx, const int32_t* tgt,
                    float* states, float* tprob, double* bits, float* status, void* ws, size_t ws_bytes, void* stream);
+
+/* Rating windows with alternatives: kl_rate_window -- the same recurrence, logits, state advance, bits, status and error
+ * returns -- delivering per position also what the model expected instead.  Within a position the V characters are
+ * ordered by (logit descending, id ascending): v stands before u iff x[v] > x[u], or x[v] == x[u] and v < u (logits are
+ * finite).  1 <= K <= KL_RATE_ALTS_MAX, else KL_ERR_ARG.
+ *   alt_id (device int32 [B][T][K])  alt_id[b][t][j] = the j-th id in that order for j < min(K, V), -1 for j >= V;
+ *   alt_p  (device f32 [B][T][K])    alt_p[b][t][j] = softmax(logits[b][t])[alt_id[b][t][j]], 0.0f where alt_id is -1;
+ *   tprob  (device [B][T], or NULL)  as kl_rate_window delivers it, bit for bit;
+ *   rank   (device int32 [B][T], or NULL)  the position of tgt[b][t] in the order (0: the model's first choice), -1 where
+ *          tgt < 0 or tgt >= V.  Where 0 <= rank < K, alt_id[rank] == tgt and alt_p[rank] == tprob bit for bit.
+ * Where tgt < 0 (padded tail, dummy stream) the position delivers nothing: tprob 0, every alt_id -1, every alt_p 0, rank -1.
+ * tgt, alt_id and alt_p are required (KL_ERR_ARG); bits and status as in kl_rate_window.  8 K + 8 bytes leave the output
+ * layer per position.  ws_bytes >= kl_rate_alts_workspace_bytes(h, B, T, K): the rate workspace plus a staging area for
+ * the results (0 for B, T < 1 or K outside its range). */
+#define KL_RATE_ALTS_MAX 8
+size_t kl_rate_alts_workspace_bytes(const kl_handle* h, int B, int T, int K);
+int kl_rate_window_alts(kl_handle* h, int B, int T, int K, const int32_t* idx, const int32_t* ctx, const int32_t* tgt,
+                        float* states, float* tprob, int32_t* alt_id, float* alt_p, int32_t* rank, double* bits,
+                        float* status, void* ws, size_t ws_bytes, void* stream);
 
 /* One training batch, forward + backward (rating.py:292-298 -> train_on_batch):
  * writes the gradient of (mean CE + embedding regularisers, rating.py:187-246)
@@ -324,6 +344,11 @@ int kl_test_logits_ce_ws(const uint16_t* X, const uint16_t* E, const int32_t* tg
 int kl_test_logits_ce_w128(const uint16_t* X, const uint16_t* E, const uint16_t* ET, const int32_t* tgt, uint16_t* dlogits, float* dH,
                            float* rowstat, int B, int T, int V, int Vp, float inv_count, int last_only, void* stream);
 int kl_test_dh_ws(const uint16_t* dlogits, const uint16_t* ET, uint16_t* dH, long M, void* stream);
+/* the selection kernel of kl_rate_window_alts alone: f32 logits [rows][ld], time-major (r = t * B + b, rows == B * T,
+ * ld >= V), tgt [B][T]; results batch-major as kl_rate_window_alts describes them (tprob and rank may be NULL).  The
+ * register form for V <= 256 with V and ld multiples of 4 (logits 16-byte aligned), the strided form for any other V. */
+int kl_test_rate_topk(const float* logits, long ld, int rows, int V, const int32_t* tgt, int B, int T, int K,
+                      float* tprob, int32_t* alt_id, float* alt_p, int32_t* rank, void* stream);
 
 /* Test hook: where the handle's most recent kl_train_window of B streams x T steps on workspace ws left what its recurrence
  * scans wrote, and how to read it.  All arrays are time-major with the padded width W = `width`: row r = block * B + b.

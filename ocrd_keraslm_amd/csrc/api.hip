@@ -2298,6 +2298,11 @@ int kl_test_dh_ws(const uint16_t* dlogits, const uint16_t* ET, uint16_t* dH, lon
   return kl_launch_dh_ws(dlogits, ET, dH, M, 512, 256, (hipStream_t)stream);
 }
 
+int kl_test_rate_topk(const float* logits, long ld, int rows, int V, const int32_t* tgt, int B, int T, int K,
+                      float* tprob, int32_t* alt_id, float* alt_p, int32_t* rank, void* stream) {
+  return kl_launch_rate_topk(logits, ld, rows, V, tgt, B, T, K, tprob, alt_id, alt_p, rank, (hipStream_t)stream);
+}
+
 }  // extern "C"
 
 // Tuning hook: launch `iters` identical forward cell steps (bf16 A, split 1) on raw
@@ -2442,6 +2447,73 @@ extern "C" int kl_rate_window(kl_handle* h, int B, int T, const int32_t* idx, co
     return hip_ok(hipGetLastError());
   }));
   if (tprob) KL_TRY(hip_ok(hipMemcpyAsync(tprob, w.s_probs, BT * sizeof(float), hipMemcpyDeviceToDevice, s)));
+  return 0;
+}
+
+// ---- rating windows with alternatives: kl_rate_window delivering the top K characters and the target's rank too --------
+// The results are staged behind the rate workspace in an area of their own -- the window's probability staging slot holds
+// B*T*V floats, fewer than the B*T*(2K + 2) words of a call once V < 2K + 2 -- and copied out after the graph, as tprob is.
+namespace {
+
+struct AltsWs {
+  float* tprob;      // [B][T]
+  int* alt_id;       // [B][T][K]
+  float* alt_p;      // [B][T][K]
+  int* rank;         // [B][T]
+};
+
+// the staging area at `base` (the first byte behind the window's workspace): bytes taken
+size_t carve_alts(void* base, size_t BT, int K, AltsWs* out) {
+  Carver cv(base);
+  AltsWs tmp;
+  AltsWs& o = out ? *out : tmp;
+  o.tprob = cv.take<float>(BT);
+  o.alt_id = cv.take<int>(BT * K);
+  o.alt_p = cv.take<float>(BT * K);
+  o.rank = cv.take<int>(BT);
+  return align_up(cv.off, 256);
+}
+
+}  // namespace
+
+extern "C" size_t kl_rate_alts_workspace_bytes(const kl_handle* h, int B, int T, int K) {
+  if (!h || B < 1 || T < 1 || K < 1 || K > KL_RATE_ALTS_MAX) return 0;
+  return carve_window(h, nullptr, B, T, 0, nullptr) + carve_alts(nullptr, (size_t)B * T, K, nullptr);
+}
+
+extern "C" int kl_rate_window_alts(kl_handle* h, int B, int T, int K, const int32_t* idx, const int32_t* ctx,
+                                   const int32_t* tgt, float* states, float* tprob, int32_t* alt_id, float* alt_p,
+                                   int32_t* rank, double* bits, float* status, void* ws, size_t ws_bytes, void* stream) {
+  if (!h || !idx || !states || !ws || B < 1 || T < 1) return KL_ERR_ARG;
+  if (h->cfg.n_ctx > 0 && !ctx) return KL_ERR_ARG;
+  if (!tgt || !alt_id || !alt_p || K < 1 || K > KL_RATE_ALTS_MAX) return KL_ERR_ARG;
+  if (!h->precision || h->last_only) return KL_ERR_STATE;      // (as kl_rate_window)
+  hipStream_t s = (hipStream_t)stream;
+  WindowWs w;
+  AltsWs a;
+  const size_t BT = (size_t)B * T;
+  const size_t n_window = carve_window(h, ws, B, T, 0, &w);      // (a multiple of 256: the staging area starts aligned)
+  if (ws_bytes < n_window + carve_alts(nullptr, BT, K, nullptr)) return KL_ERR_WORKSPACE;
+  carve_alts(reinterpret_cast<unsigned char*>(ws) + n_window, BT, K, &a);
+  KL_TRY(hip_ok(hipMemcpyAsync(w.s_idx, idx, BT * sizeof(int), hipMemcpyDeviceToDevice, s)));
+  if (h->cfg.n_ctx > 0)
+    KL_TRY(hip_ok(hipMemcpyAsync(w.s_ctx, ctx, BT * h->cfg.n_ctx * sizeof(int), hipMemcpyDeviceToDevice, s)));
+  KL_TRY(hip_ok(hipMemcpyAsync(w.s_tgt, tgt, BT * sizeof(int), hipMemcpyDeviceToDevice, s)));
+  // (baked into the captured launches: K, states, status, bits and the workspace -- all in the key; tprob, alt_id, alt_p and
+  // rank are staged, and which of the optional ones the caller takes is in the key's flags)
+  kl_handle::GraphKey key{3, B, T, (tprob ? 1 : 0) | (bits ? 2 : 0) | (rank ? 4 : 0) | (K << 3), h->precision, states, status, ws, bits, 0};
+  KL_TRY(run_graphed(h, key, s, [&]() {
+    const int V = h->cfg.voc_size;
+    KL_TRY(window_logits(h, B, T, w.s_idx, w.s_ctx, states, w, s));
+    KL_TRY(kl_launch_rate_topk(w.logits, V, B * T, V, w.s_tgt, B, T, K, a.tprob, a.alt_id, a.alt_p, a.rank, s));
+    if (bits) KL_TRY(kl_launch_rate_bits(a.tprob, w.s_tgt, B, T, bits, s));
+    if (status) hipLaunchKernelGGL(scan_status_kernel, dim3(1), dim3(64), 0, s, w.scan_status, status);
+    return hip_ok(hipGetLastError());
+  }));
+  if (tprob) KL_TRY(hip_ok(hipMemcpyAsync(tprob, a.tprob, BT * sizeof(float), hipMemcpyDeviceToDevice, s)));
+  KL_TRY(hip_ok(hipMemcpyAsync(alt_id, a.alt_id, BT * K * sizeof(int), hipMemcpyDeviceToDevice, s)));
+  KL_TRY(hip_ok(hipMemcpyAsync(alt_p, a.alt_p, BT * K * sizeof(float), hipMemcpyDeviceToDevice, s)));
+  if (rank) KL_TRY(hip_ok(hipMemcpyAsync(rank, a.rank, BT * sizeof(int), hipMemcpyDeviceToDevice, s)));
   return 0;
 }
 

@@ -343,6 +343,14 @@ int kl_launch_rate_pick(const float* logits, long ld, int rows, int V, const int
 // bits[b] += sum_t -log2(max(tprob[b][t], 1e-99)) over the positions with tgt >= 0, f64, fixed order
 int kl_launch_rate_bits(const float* tprob, const int* tgt, int B, int T, double* bits, hipStream_t stream);
 
+// ---- rate_topk.hip ------------------------------------------------------
+// per row of the same logits, batch-major: the target's probability as kl_launch_rate_pick delivers it (tprob [B][T], may be
+// null), the first K <= KL_RATE_ALTS_MAX ids in the order (logit descending, id ascending) with their probabilities
+// (alt_id, alt_p [B][T][K]; -1 / 0 from the V-th on) and the target's position in that order (rank [B][T], may be null; -1
+// without a target in [0, V)).  Rows with tgt < 0 deliver 0 / -1 / 0 / -1.
+int kl_launch_rate_topk(const float* logits, long ld, int rows, int V, const int* tgt, int B, int T, int K, float* tprob,
+                        int* alt_id, float* alt_p, int* rank, hipStream_t stream);
+
 // ---- step_small.hip -----------------------------------------------------
 // one LSTM cell step of a layer for n hypotheses with pool slots (KL_SMALL_STEP_N <= n < KL_BIG_STEP_N), see inc_cell_kernel
 #define KL_SMALL_STEP_N 16

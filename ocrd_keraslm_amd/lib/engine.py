@@ -88,6 +88,8 @@ class HipLM:
         self._rate_status = None
         self._rate_ws = None
         self._rate_ws_key = None
+        self._rate_alts_ws = None
+        self._rate_alts_ws_key = None
         self.states = None         # [B][2L][W] implicit state of the stateful streams
         self.pool = None            # [slots][2L][W] explicit states of hypotheses
         self.max_streams_per_launch = 0      # 0: what the kernels address (train_window splits larger batches into groups)
@@ -415,6 +417,53 @@ class HipLM:
             self._rate_ws = self.torch.empty(n, dtype=self.torch.uint8, device=self.device)
             self._rate_ws_key = key
         return self._rate_ws
+
+    def rate_window_alts(self, idx, ctx, tgt, k):
+        """`rate_window` delivering per position also what the model expected instead (kl_rate_window_alts): returns the DEVICE
+        tensors tprob [B,T] f32 (what rate_window returns, bit for bit), alt_id [B,T,k] i32 and alt_p [B,T,k] f32 -- the k
+        most probable characters, ordered by (logit descending, id ascending), -1 / 0 from the V-th on -- and rank [B,T] i32,
+        the target's position in that order (0: the model's first choice; -1 without a target).  Positions with tgt < 0
+        deliver 0 / -1 / 0 / -1.  1 <= k <= hipabi.KL_RATE_ALTS_MAX.  Bits go to the same accumulator `rate_bits`, and
+        nothing is synchronised here either (rate_bits_read / rate_status_check)."""
+        torch = self.torch
+        if self.precision == 0:
+            raise hipabi.KlError("weights not prepared")
+        k = int(k)
+        if not 1 <= k <= hipabi.KL_RATE_ALTS_MAX:
+            raise ValueError("k must be in 1..%d (got %d)" % (hipabi.KL_RATE_ALTS_MAX, k))
+        with self._launch():
+            idx_d = self._dev_i32(idx)
+            B, T = idx_d.shape
+            ctx_d = self._dev_i32(ctx) if self.n_ctx else None
+            tgt_d = self._dev_i32(tgt)
+            if self.states is None or self.states.shape[0] != B:
+                self.reset_states(B)
+            if self.rate_bits is None or self.rate_bits.shape[0] != B:
+                self.rate_bits = torch.zeros(B, dtype=torch.float64, device=self.device)
+            if self._rate_status is None:
+                self._rate_status = torch.zeros(4, dtype=torch.float32, device=self.device)
+            tprob = torch.empty((B, T), dtype=torch.float32, device=self.device)
+            alt_id = torch.empty((B, T, k), dtype=torch.int32, device=self.device)
+            alt_p = torch.empty((B, T, k), dtype=torch.float32, device=self.device)
+            rank = torch.empty((B, T), dtype=torch.int32, device=self.device)
+            parts = self._rating_groups(B)
+            ws = self._rate_alts_workspace(max(b1 - b0 for b0, b1 in parts), T, k)
+            for b0, b1 in parts:       # (as rate_window: the batch-major outputs are sliced by stream)
+                hipabi.check(self.lib.kl_rate_window_alts(
+                    self.handle, b1 - b0, T, k, _ptr(idx_d[b0:b1]), _ptr(ctx_d[b0:b1] if ctx_d is not None else None),
+                    _ptr(tgt_d[b0:b1]), _ptr(self.states[b0:b1]), _ptr(tprob[b0:b1]), _ptr(alt_id[b0:b1]), _ptr(alt_p[b0:b1]),
+                    _ptr(rank[b0:b1]), _ptr(self.rate_bits[b0:b1]), _ptr(self._rate_status), _ptr(ws), ws.numel(),
+                    self._stream()), "kl_rate_window_alts")
+        return tprob, alt_id, alt_p, rank
+
+    def _rate_alts_workspace(self, B, T, k):
+        key = (B, T, k)
+        if self._rate_alts_ws_key != key:
+            n = self.lib.kl_rate_alts_workspace_bytes(self.handle, B, T, k)
+            self._rate_alts_ws = None
+            self._rate_alts_ws = self.torch.empty(n, dtype=self.torch.uint8, device=self.device)
+            self._rate_alts_ws_key = key
+        return self._rate_alts_ws
 
     def rate_status_check(self):
         """raise if a scan hand-off timed out in a rate_window call since the last check (synchronises)"""

@@ -9,6 +9,9 @@ text is finished takes the next text at the next call with that row's state zero
 Texts are dealt longest first to the row that is free first (list scheduling), so the number of window calls is at
 most ceil(sum N_i / B) + max N_i for texts of N_i windows (Graham's bound; it holds for any order of the list).
 
+`Rater.rate_alternatives` runs the same plan and delivers, per character, also the model's k most probable characters and
+the rank of the one written: `alternatives_of` states that selection in numpy, `Plan.text_alternatives` slices it per text.
+
 numpy only: the plan is built and tested without an engine.
 """
 from __future__ import annotations
@@ -63,6 +66,88 @@ class Plan(object):
             a = int(self.first[i])
             out[1:] = picked[a:a + int(self.count[i]), int(self.row[i])].reshape(-1)[:size - 1]
         return out
+
+    def text_alternatives(self, i, picked, rank, alt_id, alt_p):
+        """text i's share of `Rater.rate_alternatives`, sliced as text_probs slices: (probs [n] f32, rank [n] i32,
+        alt_ids [n,k] i32, alt_probs [n,k] f32) from the results of all calls -- picked, rank [n_calls][B][T] and alt_id,
+        alt_p [n_calls][B][T][k].  The first character has no prediction: probability 1.0, rank -1, ids -1, probabilities 0."""
+        k = alt_id.shape[-1]
+        size = int(self.sizes[i])
+        n = min(size, 1) if self.count[i] == 0 else size
+        ranks = np.full(n, -1, dtype=np.int32)
+        ids = np.full((n, k), -1, dtype=np.int32)
+        probs = np.zeros((n, k), dtype=np.float32)
+        if self.count[i]:
+            a, c, r = int(self.first[i]), int(self.count[i]), int(self.row[i])
+            ranks[1:] = rank[a:a + c, r].reshape(-1)[:size - 1]
+            ids[1:] = alt_id[a:a + c, r].reshape(-1, k)[:size - 1]
+            probs[1:] = alt_p[a:a + c, r].reshape(-1, k)[:size - 1]
+        return self.text_probs(i, picked), ranks, ids, probs
+
+
+ALTS_MAX = 8      # alternatives per position at most (KL_RATE_ALTS_MAX of the C ABI)
+
+
+class RatedText(object):
+    """One text of `Rater.rate_alternatives`, n characters:
+
+    probs      [n] f32    probability of every character given its predecessors (1.0 for the first), as `rate_batch`
+    rank       [n] i32    position of the character among all the model could have written there, 0 = its first choice
+                          (-1 for the first character)
+    alt_ids    [n,k] i32  the k most probable ids there, most probable first (-1: none -- first character, k > voc_size)
+    alt_probs  [n,k] f32  their probabilities (0 where alt_ids is -1)
+    """
+
+    def __init__(self, probs, rank, alt_ids, alt_probs):
+        self.probs, self.rank, self.alt_ids, self.alt_probs = probs, rank, alt_ids, alt_probs
+
+    @classmethod
+    def unpredicted(cls, n, k):
+        """a text without a single prediction (n = 0 or 1 characters)"""
+        return cls(np.ones(n, dtype=np.float32), np.full(n, -1, dtype=np.int32), np.full((n, k), -1, dtype=np.int32),
+                   np.zeros((n, k), dtype=np.float32))
+
+    def __len__(self):
+        return len(self.probs)
+
+    def chars(self, mapping):
+        """the alternatives as characters, [n][k]: mapping is the Rater's (char -> id, id -> char) pair or its id -> char
+        half; id 0 (the unmapped character) shows as the empty string, no alternative (-1) as None"""
+        i_c = mapping[1] if isinstance(mapping, (tuple, list)) else mapping
+        return [[None if v < 0 else i_c.get(int(v), "") for v in row] for row in self.alt_ids]
+
+
+def alternatives_of(full, y, k):
+    """What the model expected instead, from whole distributions: full [B,T,V] (probabilities, or logits -- any values that
+    order the vocabulary), y [B,T] targets, k >= 1.  Within a position the ids are ordered by (value descending, id
+    ascending) -- a stable sort, so exact ties resolve to the lower id.  Returns
+      tprob  [B,T]    full[b,t,y], 0 where y is no id (y < 0 or y >= V), dtype of `full`
+      alt_id [B,T,k]  int32: the first k ids in that order, -1 from the V-th on
+      alt_p  [B,T,k]  their values in `full`, 0 where alt_id is -1
+      rank   [B,T]    int32: the position of y in the order (0: the first choice; a tied target is counted by id), -1 where
+                      y is no id.
+    A position with y < 0 (padded tail, dummy stream) delivers nothing: 0, -1, 0, -1.  This is the numpy statement of what
+    kl_rate_window_alts computes on the device."""
+    full = np.asarray(full)
+    y = np.asarray(y)
+    B, T, V = full.shape
+    k = int(k)
+    m = min(k, V)
+    order = np.argsort(-full, axis=2, kind="stable")
+    alt_id = np.full((B, T, k), -1, dtype=np.int32)
+    alt_p = np.zeros((B, T, k), dtype=full.dtype)
+    alt_id[:, :, :m] = order[:, :, :m]
+    alt_p[:, :, :m] = np.take_along_axis(full, order[:, :, :m], axis=2)
+    known = (y >= 0) & (y < V)
+    at = np.where(known, y, 0)
+    fy = np.take_along_axis(full, at[:, :, None], axis=2)
+    ahead = (full > fy) | ((full == fy) & (np.arange(V)[None, None, :] < at[:, :, None]))
+    rank = np.where(known, ahead.sum(axis=2), -1).astype(np.int32)
+    tprob = np.where(known, fy[:, :, 0], 0).astype(full.dtype)
+    none = y < 0
+    alt_id[none] = -1
+    alt_p[none] = 0
+    return tprob, alt_id, alt_p, rank
 
 
 def plan(ids, contexts, length, streams):

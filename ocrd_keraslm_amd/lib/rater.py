@@ -881,6 +881,74 @@ class Rater(object):
         lm.rate_status_check()
         return _np(lm.torch.stack(steps)) if want_probs else None
 
+    def rate_alternatives(self, texts, contexts=None, k=3, streams=64):
+        '''`rate_batch` answering also what the model expected instead: returns (rated, bits), both in input order.
+        `rated[i]` is a RatedText over the n characters of the normalised text: `probs` [n] f32 -- what `rate_batch` returns
+        for that text --, `alt_ids` [n,k] i32 and `alt_probs` [n,k] f32 -- the k most probable characters at that position,
+        ordered by (probability descending, id ascending), padded with -1 / 0 beyond the vocabulary --, and `rank` [n] i32,
+        the position of the character that was written in that order (0: the model's first choice).  The first character
+        has no prediction: probability 1.0, rank -1, ids -1, probabilities 0.  `bits[i]`, texts, contexts, streams and the
+        state afterwards (a freshly reset single row) are as in `rate_batch`.  1 <= k <= 8.  Only stateful raters: the
+        stateless one rates through windows of its own (`rate`).'''
+        assert self.status > 1
+        assert self.incremental is False
+        assert self.stateful, "rate_alternatives needs a stateful rater"
+        k = int(k)
+        assert 1 <= k <= ratebatch.ALTS_MAX, "k must be in 1..%d" % ratebatch.ALTS_MAX
+        texts = list(texts)
+        n = len(texts)
+        if contexts is None or len(contexts) == 0:
+            contexts = [self.underspecify_contexts()] * n
+        elif isinstance(contexts[0], (int, np.integer)):
+            contexts = [list(contexts)] * n
+        else:
+            assert len(contexts) == n, "one context list per text"
+            contexts = [list(c) if (c is not None and len(c)) else self.underspecify_contexts() for c in contexts]
+        self._ensure_precision()
+        lm = self.model
+        bits = np.zeros(n, dtype=np.float64)
+        texts = [windows.normalize(t) for t in texts]
+        ids = [windows.encode(t, self.mapping[0], self._unmapped_input) for t in texts]
+        plan = ratebatch.plan(ids, [windows.clamp_context(c) for c in contexts], self.length, streams)
+        if plan is None:       # (nothing but empty texts and single characters)
+            lm.reset_states(1)
+            return [ratebatch.RatedText.unpredicted(len(t), k) for t in texts], bits
+        lm.reset_states(plan.B)
+        if hasattr(lm, 'rate_window_alts'):
+            picked, rank, alt_id, alt_p = self._run_alternatives_plan(plan, bits, k)
+        else:
+            # an engine without the device selection (the tests' CPU double): the whole softmax and the numpy statement
+            steps = []
+            for s in range(plan.n_calls):
+                x, z, y = plan.call(s)
+                if s and plan.starting(s):
+                    lm.reset_states(rows=plan.reset_rows(s))
+                steps.append(ratebatch.alternatives_of(_np(lm.forward_window(x, z, want_probs=True)), y, k))
+            picked, alt_id, alt_p, rank = (np.stack([st[j] for st in steps]) for j in range(4))
+            picked, alt_p = picked.astype(np.float32), alt_p.astype(np.float32)
+            bits[:] = [ratebatch.bits_of(plan.text_probs(i, picked)) for i in range(n)]
+        lm.reset_states(1)
+        return [ratebatch.RatedText(*plan.text_alternatives(i, picked, rank, alt_id, alt_p)) for i in range(n)], bits
+
+    def _run_alternatives_plan(self, plan, bits, k):
+        '''_run_rate_plan through `rate_window_alts`: fills bits and returns (picked, rank [n_calls][B][T], alt_id, alt_p
+        [n_calls][B][T][k]).  One transfer of each at the end.'''
+        lm = self.model
+        lm.rate_bits_read(reset=True)
+        steps, taken = [], []
+        for s in range(plan.n_calls):
+            x, z, y = plan.call(s)
+            if s and plan.starting(s):
+                lm.reset_states(rows=plan.reset_rows(s))
+            steps.append(lm.rate_window_alts(x, z, y, k))
+            ending = plan.ending(s)
+            if ending:
+                taken.append((ending, lm.rate_bits_take([int(plan.row[i]) for i in ending])))
+        bits[np.concatenate([e for e, _ in taken])] = _np(lm.torch.cat([t for _, t in taken]))
+        lm.rate_status_check()
+        picked, alt_id, alt_p, rank = (_np(lm.torch.stack([st[j] for st in steps])) for j in range(4))
+        return picked, rank, alt_id, alt_p
+
     def rate2(self, text, context=None):
         '''Rate a string one by one (rating.py:531-576): resets the state, feeds one
         character per step, returns [(char, prob)] and the perplexity 2^(H/len).'''

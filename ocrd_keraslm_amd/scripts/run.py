@@ -123,15 +123,30 @@ def train(model, ckpt, width, depth, length, val_data, streams, segment_streams,
 @cli.command(short_help='get individual probabilities from language model')
 @click.option('-m', '--model', required=True, help='model file', type=click.Path(dir_okay=False, exists=True))
 @click.option('-c', '--context', default=None, help='constant meta-data input')
+@click.option('--alternatives', default=None, type=click.IntRange(min=1, max=8),
+              help='also list the K characters the model expected most at every position, and the rank of the one written')
 @click.argument('text', type=click.STRING)
-def apply(model, text, context):
+def apply(model, text, context, alternatives):
     """Apply a language model to TEXT string and compute its individual probabilities.
 
        If TEXT is the symbol '-', the string will be read from standard input.
+
+       With --alternatives K the list holds [char, prob, rank, [[alt_char, alt_prob], ...]]
+       per character (rank 0: the model's first choice; the first character has no prediction).
     """
     rater = _load(model)
     if text and text[0] == u"-":
         text = sys.stdin.read()
+    if alternatives:
+        from ..lib import windows
+        rated, bits = rater.rate_alternatives([text], [_contexts(context)] if context else None, k=alternatives)
+        text = windows.normalize(text)
+        one = rated[0]
+        click.echo(pow(2.0, float(bits[0]) / max(len(text), 1)))
+        click.echo(json.dumps([[char, float(one.probs[i]), int(one.rank[i]),
+                                [[c, float(p)] for c, p in zip(chars, one.alt_probs[i])]]
+                               for i, (char, chars) in enumerate(zip(text, one.chars(rater.mapping)))], ensure_ascii=False))
+        return
     ratings, perplexity = rater.rate2(text, _contexts(context) if context else None)
     click.echo(perplexity)
     click.echo(json.dumps(ratings, ensure_ascii=False))
