@@ -285,6 +285,47 @@ int kl_beam_expand(kl_handle* h, int rows, int fan, float floor, const float* pr
                    int32_t* slot_in_next, float* cum_next, int32_t* parent_log, int32_t* idx_log, float* cum_log,
                    int32_t* n_live, void* ws, size_t ws_bytes, void* stream);
 
+/* One DRAWN character per row ON THE DEVICE, for sampling continuations (Rater.sample): `rows` independent chains (1 .. 1024)
+ * advance in lockstep, each continuing from the state it just wrote, so a step is kl_step_batch followed by this call and the
+ * host waits once per text, not once per character.  All pointers are DEVICE pointers.
+ *   probs [rows][V] f32     what kl_step_batch just wrote (V = the handle's voc_size)
+ *   valid [V] bytes         non-zero = the id may be drawn; NULL = every id except 0 (as in kl_beam_expand)
+ *   temperature             >= 0 and finite; 0 = greedy
+ *   top_k                   0 .. 64, 0 = off;  floor >= 0
+ *   seed, step              the random stream and the position in it (one step per character)
+ *   cum_in, cum_next [rows] running cost per chain before and after (they may be the same array)
+ *   idx_next [rows] int32   the drawn id;  u_log [rows] f32, may be NULL: the uniform number the row drew with
+ * Per row r:
+ *   Uniform number.  Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85) with key
+ *     (seed & 0xffffffff, seed >> 32) and counter (step, r, 0, 0); of the first output word x0, u = (x0 >> 8) * 2^-24, in
+ *     [0, 1).  Integer arithmetic only: lib/gensample.py philox_uniform gives the same bits.  u is computed (and logged) at
+ *     every temperature, 0 included.
+ *   Candidates.  The valid ids; if top_k > 0, the first min(top_k, valid ids) of them in the order (p descending, id
+ *     ascending) -- kl_rate_window_alts' total order, taken over the valid ids only --; of those the ids with p >= floor (an
+ *     f32 comparison).  If that leaves none, the single candidate is the first valid id of that order.  If no id is valid,
+ *     the pick is id 0 at cost +inf.
+ *   Pick, temperature == 0: the first candidate of that order.
+ *   Pick otherwise: weight w_v = p_v at temperature 1, else expf((logf(p_v) - logf(p_max)) / temperature), p_max the largest
+ *     candidate probability; p_v == 0 gives weight 0.  S = the sum of the weights.  The pick is the smallest candidate id
+ *     whose running weight sum exceeds u * S, running sums taken in ID-ASCENDING order; if rounding leaves none, the last
+ *     candidate of positive weight.  A candidate of weight 0 is never picked (if every candidate's probability is 0, the pick is
+ *     the first candidate, at cost +inf).  The order of the additions is fixed: two calls on the same inputs pick bit-identically.
+ *   Cost.  cum_next[r] = cum_in[r] + (-logf(p_pick)): accurate logf, one f32 addition, as kl_beam_expand does it.
+ * kl_sample_pick_from is the same call with counter (step, row0 + r, 0, 0) (modulo 2^32): more than 1024 chains are drawn in
+ * groups of rows that continue each other's row numbers, so no two chains share a random number.
+ * ws: device, >= kl_sample_workspace_bytes(h, rows) (0 for rows out of range), one per handle and stream (vocabularies above
+ * 256 keep a row's weights there between summing them and picking; smaller ones do not touch it).
+ * KL_ERR_ARG (null probs / cum_in / idx_next / cum_next, rows outside 1 .. 1024, top_k outside 0 .. 64, temperature negative,
+ * NaN or infinite, floor negative or NaN) and KL_ERR_WORKSPACE are returned before anything is launched.  One launch on
+ * `stream`, no synchronisation, no host memory touched. */
+size_t kl_sample_workspace_bytes(const kl_handle* h, int rows);
+int kl_sample_pick(kl_handle* h, int rows, const float* probs, const uint8_t* valid, float temperature, int top_k,
+                   float floor, uint64_t seed, uint32_t step, const float* cum_in, int32_t* idx_next, float* cum_next,
+                   float* u_log, void* ws, size_t ws_bytes, void* stream);
+int kl_sample_pick_from(kl_handle* h, int rows, uint32_t row0, const float* probs, const uint8_t* valid, float temperature,
+                        int top_k, float floor, uint64_t seed, uint32_t step, const float* cum_in, int32_t* idx_next,
+                        float* cum_next, float* u_log, void* ws, size_t ws_bytes, void* stream);
+
 /* Squared L2 distances between state vectors of pool slots, for beam history
  * clustering (rating.py:887-916): out[i] = || pool[a[i]][k] - pool[b[i]][k] ||^2
  * for state entry k (0 = h1, 1 = c1, ...). */

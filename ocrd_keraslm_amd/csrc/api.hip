@@ -2249,6 +2249,33 @@ int kl_beam_expand(kl_handle* h, int rows, int fan, float floor, const float* pr
   return kl_launch_beam_expand(a, ws, (hipStream_t)stream);
 }
 
+size_t kl_sample_workspace_bytes(const kl_handle* h, int rows) {
+  if (!h || rows < 1 || rows > KL_SAMPLE_MAX_ROWS) return 0;
+  return kl_sample_ws_bytes(rows, h->cfg.voc_size);
+}
+
+int kl_sample_pick_from(kl_handle* h, int rows, uint32_t row0, const float* probs, const uint8_t* valid, float temperature,
+                        int top_k, float floor, uint64_t seed, uint32_t step, const float* cum_in, int32_t* idx_next,
+                        float* cum_next, float* u_log, void* ws, size_t ws_bytes, void* stream) {
+  if (!h || !probs || !cum_in || !idx_next || !cum_next) return KL_ERR_ARG;
+  if (rows < 1 || rows > KL_SAMPLE_MAX_ROWS || top_k < 0 || top_k > KL_SAMPLE_MAX_TOPK) return KL_ERR_ARG;
+  if (!(temperature >= 0.f) || temperature == INFINITY || !(floor >= 0.f)) return KL_ERR_ARG;      // (NaN fails both comparisons)
+  if (!ws || ws_bytes < kl_sample_ws_bytes(rows, h->cfg.voc_size)) return KL_ERR_WORKSPACE;
+  KlSamplePick a;
+  memset(&a, 0, sizeof(a));
+  a.rows = rows; a.V = h->cfg.voc_size; a.top_k = top_k; a.temperature = temperature; a.floor = floor;
+  a.key0 = (unsigned)(seed & 0xffffffffu); a.key1 = (unsigned)(seed >> 32); a.step = step; a.row0 = row0;
+  a.probs = probs; a.valid = valid; a.cum_in = cum_in; a.idx_next = idx_next; a.cum_next = cum_next; a.u_log = u_log;
+  return kl_launch_sample_pick(a, ws, (hipStream_t)stream);
+}
+
+int kl_sample_pick(kl_handle* h, int rows, const float* probs, const uint8_t* valid, float temperature, int top_k, float floor,
+                   uint64_t seed, uint32_t step, const float* cum_in, int32_t* idx_next, float* cum_next, float* u_log, void* ws,
+                   size_t ws_bytes, void* stream) {
+  return kl_sample_pick_from(h, rows, 0, probs, valid, temperature, top_k, floor, seed, step, cum_in, idx_next, cum_next, u_log,
+                             ws, ws_bytes, stream);
+}
+
 int kl_test_gemm_tn(const uint16_t* A, const uint16_t* B, void* C, const float* bias, int M, int N, int K, long lda,
                     long ldb, long ldc, int out_mode, int splits, void* stream) {
   return kl_launch_gemm_tn(A, B, C, bias, M, N, K, lda, ldb, ldc, out_mode, splits, 1.f, (hipStream_t)stream);

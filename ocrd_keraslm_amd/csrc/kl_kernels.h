@@ -419,6 +419,22 @@ struct KlBeamExpand {
 size_t kl_beam_ws_bytes(int rows, int fan);
 int kl_launch_beam_expand(KlBeamExpand a, void* ws, hipStream_t stream);      // KL_ERR_ARG before anything is launched
 
+// ---- sample.hip ---------------------------------------------------------
+// one drawn character per row (kl_sample_pick), see sample.hip; all pointers device
+#define KL_SAMPLE_MAX_ROWS 1024
+#define KL_SAMPLE_MAX_TOPK 64
+struct KlSamplePick {
+  int rows, V, top_k; float temperature, floor;
+  unsigned key0, key1, step, row0;   // Philox key (the seed's halves) and counter (step, row0 + row, 0, 0)
+  const float* probs;                // [rows][V]
+  const unsigned char* valid;        // [V], or null: every id except 0
+  const float* cum_in;               // [rows]; may be cum_next
+  int* idx_next; float* cum_next; float* u_log;      // [rows]; u_log may be null
+  float* w;                          // workspace, [rows][V] (set by the launcher)
+};
+size_t kl_sample_ws_bytes(int rows, int V);
+int kl_launch_sample_pick(KlSamplePick a, void* ws, hipStream_t stream);      // KL_ERR_ARG before anything is launched
+
 // ---- step_tile.hip: the same for n >= KL_BIG_STEP_N, TR x 128 tiles with the operands read once (variant: timing builds, 0)
 int kl_launch_inc_tile(const KlIncCellArgs& a, int variant, hipStream_t stream, int rows = -1);      // KL_ERR_SHAPE: not applicable; rows: 64 / 128 per tile, -1 = by size
 // output layer in one launch: probs[n][V] = softmax(h_top . E^T), h_top rows through slot_out (V <= 256, W % 128 == 0)

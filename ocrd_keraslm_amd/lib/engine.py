@@ -102,6 +102,7 @@ class HipLM:
         self._step_host_ws = None
         self._walk_ws = None
         self._beam_ws = None
+        self._sample_ws = None
         self._wstage = None
         self._hio = None
         self._step_ws_bytes = {}
@@ -1012,6 +1013,84 @@ class HipLM:
             host = log.cpu().numpy()      # (the one wait of the search)
         return (host[:n].reshape(length, rows), host[n:2 * n].reshape(length, rows),
                 host[2 * n:3 * n].view(np.float32).reshape(length, rows), host[3 * n:])
+
+    # ---- sampling on the device (kl_sample_pick): one drawn character per chain where the probabilities already are
+    def sample_pick(self, probs, cum_in, temperature, top_k, floor, seed, step, valid=None, out=None, row0=0):
+        """One drawn character for every row of `probs` (device [rows][V] f32, what step_slots returned): cum_in [rows] f32,
+        valid [V] uint8 or None (every id except 0) -- device tensors.  Row r draws with the uniform number of (seed, step,
+        row0 + r) (gensample.philox_uniform).  Returns device tensors (idx [rows] int32, cum_next [rows] f32, u [rows] f32);
+        `out` = those three, preallocated (cum_next may be cum_in).  Launches on the caller's current stream, no
+        synchronisation (the contract: include/keraslm_hip.h, gensample.py)."""
+        torch = self.torch
+        rows = int(probs.shape[0])
+        if (probs.dtype != torch.float32 or not probs.is_contiguous() or probs.shape[1] != self.voc_size
+                or cum_in.dtype != torch.float32 or cum_in.numel() != rows
+                or (valid is not None and (valid.dtype != torch.uint8 or valid.numel() != self.voc_size))):
+            raise hipabi.KlError("sample_pick: probs f32 [rows][V], cum_in f32 [rows], valid uint8 [V]")
+        if out is None:
+            out = (torch.empty(rows, dtype=torch.int32, device=self.device), torch.empty(rows, dtype=torch.float32, device=self.device),
+                   torch.empty(rows, dtype=torch.float32, device=self.device))
+        idx, cum, u = out
+        key = ("sample", rows)
+        nws = self._step_ws_bytes.get(key)
+        if nws is None:
+            nws = self._step_ws_bytes[key] = int(self.lib.kl_sample_workspace_bytes(self.handle, rows))
+        if self._sample_ws is None or self._sample_ws.numel() < nws:
+            self._sample_ws = torch.empty(max(nws, 1 << 16), dtype=torch.uint8, device=self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        hipabi.check(self.lib.kl_sample_pick_from(self.handle, rows, int(row0) & 0xffffffff, _ptr(probs), _ptr(valid),
+                                                  float(temperature), int(top_k), float(floor), int(seed) & 0xffffffffffffffff,
+                                                  int(step) & 0xffffffff, _ptr(cum_in), _ptr(idx), _ptr(cum), _ptr(u),
+                                                  _ptr(self._sample_ws), self._sample_ws.numel(), stream), "kl_sample_pick")
+        return out
+
+    def sample_generate(self, idx0, slot0, ctx, length, rows, temperature, top_k, floor, seed, valid, slots_a, slots_b, zero_slot,
+                        keep_probs=False, row0=0):
+        """`rows` chains of `Rater.sample` enqueued back to back: for step s, step_slots into slot set s & 1, then sample_pick
+        with step = s.  Row r always continues its own chain -- its next slot_in is the slot it just wrote --; at step 0 every
+        row reads slot0 and feeds idx0.  No host synchronisation inside the loop; at the end ONE copy brings the log.
+        Returns (idx [length][rows] int32, cum [length][rows] float32, u [length][rows] float32) as numpy arrays
+        (gensample.spell reads them); keep_probs: also every step's probabilities [length][rows][V] (for tests).  The pool
+        must hold all slots named; zero_slot is not used (the signature is beam_generate's)."""
+        torch = self.torch
+        length, rows = int(length), int(rows)
+        n = length * rows
+        sets = (np.asarray(slots_a, dtype=np.int32).reshape(-1), np.asarray(slots_b, dtype=np.int32).reshape(-1))
+        if len(sets[0]) != rows or len(sets[1]) != rows or rows < 1 or length < 1:
+            raise hipabi.KlError("sample_generate: two sets of %d slots and a positive length, please" % rows)
+        n_ctx = self.n_ctx
+        # everything the loop reads from the host in ONE upload: slot sets, the first step's inputs (cum 0.0 = zero bits), context rows
+        first = np.zeros((3, rows), dtype=np.int32)
+        first[0, :], first[1, :] = idx0, slot0
+        head = np.concatenate([sets[0], sets[1], first.reshape(-1),
+                               np.tile(np.asarray(ctx, dtype=np.int32).reshape(1, -1), (rows, 1)).reshape(-1)])
+        with torch.cuda.device(self.device):
+            head_d = self.to_device_i32(head)
+            valid_d = None
+            if valid is not None:
+                valid_d = torch.from_numpy(np.ascontiguousarray(valid, dtype=np.uint8).reshape(-1)).to(self.device, non_blocking=True)
+            set_d = (head_d[:rows], head_d[rows:2 * rows])
+            idx, slot_in, cum = head_d[2 * rows:3 * rows], head_d[3 * rows:4 * rows], head_d[4 * rows:5 * rows].view(torch.float32)
+            ctx_d = head_d[5 * rows:].view(rows, n_ctx) if n_ctx else None
+            log = torch.empty(3 * n, dtype=torch.int32, device=self.device)      # idx, cum (bits), u (bits)
+            idx_rows = log[:n].view(length, rows).unbind(0)
+            cum_rows = log[n:2 * n].view(torch.float32).view(length, rows).unbind(0)
+            u_rows = log[2 * n:].view(torch.float32).view(length, rows).unbind(0)
+            kept = []
+            for s in range(length):
+                new = set_d[s & 1]
+                probs = self.step_slots(idx, ctx_d, slot_in, new)
+                self.sample_pick(probs, cum, temperature, top_k, floor, seed, s, valid_d,
+                                 out=(idx_rows[s], cum_rows[s], u_rows[s]), row0=row0)
+                idx, slot_in, cum = idx_rows[s], new, cum_rows[s]
+                if keep_probs:
+                    kept.append(probs)
+            host = log.cpu().numpy()      # (the one wait of the call)
+            out = (host[:n].reshape(length, rows), host[n:2 * n].view(np.float32).reshape(length, rows),
+                   host[2 * n:].view(np.float32).reshape(length, rows))
+            if keep_probs:
+                out += (torch.stack(kept).cpu().numpy(),)
+        return out
 
     def to_device_i32(self, a):
         """one host-to-device transfer of an int32 array (rows stay contiguous views)"""

@@ -16,6 +16,8 @@ LIB_PATH = os.environ.get("KL_LIB") or os.path.join(os.path.dirname(_HERE), "lib
 KL_PREC_BF16 = 1
 KL_PREC_SPLIT = 3
 KL_RATE_ALTS_MAX = 8     # alternatives per position kl_rate_window_alts delivers at most
+KL_SAMPLE_MAX_ROWS = 1024  # chains per kl_sample_pick call
+KL_SAMPLE_MAX_TOPK = 64
 
 
 class KlConfig(C.Structure):
@@ -84,6 +86,13 @@ SIGNATURES = {
     "kl_beam_expand": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "kl_sample_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
+    "kl_sample_pick": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_float, C.c_uint64,
+                                 C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                 C.c_void_p]),
+    "kl_sample_pick_from": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_float,
+                                      C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_size_t, C.c_void_p]),
     "kl_step_wait": (C.c_int, [C.c_void_p, C.c_uint32, C.c_double]),
     "kl_state_dist2": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                  C.c_void_p]),

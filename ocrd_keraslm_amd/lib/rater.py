@@ -39,7 +39,7 @@ from random import shuffle
 
 import numpy as np
 
-from . import genbeam, lattice_beam, modelio, ratebatch, segments, streams, windows
+from . import genbeam, gensample, lattice_beam, modelio, ratebatch, segments, streams, windows
 from .node import Node
 
 PREC_BF16 = 1
@@ -152,6 +152,7 @@ class Rater(object):
     - `Rater.rate` : character string, all at once
     - `Rater.rate_best` : lattice graph
     - `Rater.generate` : alternative list of characters and states
+    - `Rater.sample` : character strings drawn from the model's distribution
     '''
 
     def __init__(self, logger=None, engine_factory=None):
@@ -189,6 +190,7 @@ class Rater(object):
         self.edge_walk = False               # rate_best: every lattice edge's hypotheses walked through all their characters in ONE engine call (lattice_beam.walk_edge)
         self.edge_walk_slots = None          # ... slots one such call may be asked for (None: lattice_beam.walk_slot_budget of the pool's slot size)
         self.device_beam = os.environ.get('KERASLM_DEVICE_BEAM', '') == '1'      # generate: the beam's expansion and pruning on the device, the whole search enqueued without a wait (HipLM.beam_generate)
+        self.sample_keep_probs = False      # sample: keep every step's probabilities in `sample_log` (tests look at what a pick saw)
         self.segment_streams = False         # fewer files than streams: cut the files into segments, one list of segments per stream (segments.py)
         self._engine_factory = engine_factory
         self._pool = None
@@ -1206,6 +1208,111 @@ class Rater(object):
         out = genbeam.backtrack(log, variants, i_c, prefix[-1])
         self.generate_costs = [float(c) for c in log[2][-1][:len(out)]]
         return out
+
+    # ------------------------------------------------------------------ sampling
+    def sample(self, prefix, length, context=None, variants=1, temperature=1.0, top_k=0, floor=0.0, seed=0):
+        '''Draw `variants` continuations of `length` characters after `prefix` from the model's distribution: independent
+        chains, each character drawn from the probabilities its own chain produced (`generate` returns the cheapest strings
+        of a beam search instead).  Returns `variants` strings of 1 + length characters, each starting with prefix[-1]; their
+        model costs (the sum of -log p along the string) are left in `self.sample_costs`.
+
+        temperature: 1 draws from the distribution itself, below 1 sharpens it, 0 always takes the most probable character;
+        top_k > 0 (up to 64): only the top_k most probable characters can be drawn; floor: nor characters with p < floor
+        (the most probable one always can).  Only mapped characters are drawn.  The numbers come from a counter-based
+        generator (Philox4x32-10) keyed by `seed` and counted by (position, chain): the same seed gives the same strings,
+        and chain i does not depend on how many chains are drawn.  The rules in full: gensample.py, include/keraslm_hip.h (kl_sample_pick).
+
+        On an engine with `sample_pick` (HipLM) the characters are drawn where the probabilities are, all `length` steps of up
+        to 1024 chains enqueued without a wait (HipLM.sample_generate); more chains run in groups of 1024 that continue the row
+        numbers.  Other engines step through `_predict_refs` and draw with gensample.pick_host.'''
+        assert self.status > 1
+        assert self.stateful is False
+        assert self.incremental is True
+        variants, length = int(variants), int(length)
+        if variants < 1 or length < 0 or not prefix:
+            raise ValueError("sample: a prefix, a length >= 0 and at least one variant, please")
+        gensample.check_args(temperature, top_k, floor)
+        if not context:
+            context = self.underspecify_contexts()
+        self._ensure_precision()
+        self.sample_log = []
+        if length == 0:
+            self.sample_costs = [0.0] * variants
+            return [prefix[-1]] * variants
+        c_i, i_c = self.mapping
+        valid = np.zeros(self.voc_size, dtype=np.uint8)
+        valid[[i for i in i_c if 0 <= i < self.voc_size]] = 1
+        args = (float(temperature), int(top_k), float(floor), int(seed))
+        if hasattr(self.model, "sample_pick"):
+            logs = self._sample_device(prefix, length, context, variants, valid, args)
+        else:
+            logs = self._sample_host(prefix, length, context, variants, valid, args)
+        self.sample_log = logs
+        self.sample_costs = [float(c) for log in logs for c in log[1][-1]]
+        return [text for log in logs for text in gensample.spell(log, i_c, prefix[-1])]
+
+    def _sample_device(self, prefix, length, context, variants, valid, args):
+        '''sample's chains on the device: the prefix warmed up in one engine call (as _generate_device does), 2 * rows
+        working slots (rows = the chains of a group, at most 1024) taken from the pool for the duration, one wait per group'''
+        pool = self._state_pool()
+        lm = self.model
+        c_i = self.mapping[0]
+        ctx = np.asarray(windows.clamp_context(context), dtype=np.int32)
+        warm_ids = [c_i.get(c, 0) for c in prefix[:-1]]
+        walk = getattr(lm, "walk_host", None)
+        rows = min(variants, gensample.MAX_ROWS)
+        slots = pool.take_slots(2 * rows + (len(warm_ids) if walk else 0))
+        try:
+            slot0, state = pool.zero_slot, None
+            if warm_ids and walk:
+                warm = slots[2 * rows:]
+                for at in range(0, len(warm_ids), 1024):      # (a walk's row takes up to 1024 steps)
+                    part = warm_ids[at:at + 1024]
+                    walk([len(part)], part, [0] * len(part), ctx[None, :], [slot0], warm[at:at + len(part)])
+                    slot0 = warm[at + len(part) - 1]
+            else:
+                for char in prefix[:-1]:
+                    _, states = self._predict_refs([char], [state], context)
+                    state = states[0]
+                if state is not None:
+                    slot0 = state.slot
+            logs = []
+            for row0 in range(0, variants, rows):
+                n = min(rows, variants - row0)
+                logs.append(lm.sample_generate(c_i.get(prefix[-1], 0), slot0, ctx, length, n, *args, valid, slots[:n],
+                                               slots[rows:rows + n], pool.zero_slot,
+                                               keep_probs=self.sample_keep_probs, row0=row0))
+        finally:
+            pool.release_slots(slots)
+        return logs
+
+    def _sample_host(self, prefix, length, context, variants, valid, args):
+        '''the same chains on an engine without `sample_pick`: one `_predict_refs` per character and group, the picks of
+        gensample.pick_host with the same uniform numbers; costs summed at the engine's own precision'''
+        temperature, top_k, floor, seed = args
+        i_c = self.mapping[1]
+        state = None
+        for char in prefix[:-1]:
+            _, states = self._predict_refs([char], [state], context)
+            state = states[0]
+        logs = []
+        for row0 in range(0, variants, gensample.MAX_ROWS):
+            n = min(gensample.MAX_ROWS, variants - row0)
+            chars, states = [prefix[-1]] * n, [state] * n
+            idx_log = np.zeros((length, n), dtype=np.int32)
+            cum_log = np.zeros((length, n), dtype=np.float64)
+            u_log = np.zeros((length, n), dtype=np.float32)
+            cum = np.zeros(n, dtype=np.float64)
+            for s in range(length):
+                probs, states = self._predict_refs(chars, states, context)
+                u_log[s] = gensample.philox_uniform(seed, s, n, row0)
+                idx_log[s] = gensample.pick_host(probs, u_log[s], valid, temperature, top_k, floor)
+                with np.errstate(divide="ignore"):
+                    cum = cum - np.log(np.asarray(probs)[np.arange(n), idx_log[s]].astype(np.float64))
+                cum_log[s] = cum
+                chars = [i_c[int(i)] for i in idx_log[s]]
+            logs.append((idx_log, cum_log, u_log))
+        return logs
 
     def rate_best(self, graph, start_node, end_node, start_traceback=None, context=None, lm_weight=0.5,
                   beam_width=10, beam_clustering_dist=0, edge_walk=None):

@@ -169,14 +169,29 @@ def test(model, data):
 @click.option('-c', '--context', default=None, help='constant meta-data input')
 @click.option('--device-beam', is_flag=True, default=False,
               help='expand and prune the beam on the GPU, all characters enqueued without a wait (Rater.device_beam)')
+@click.option('--sample', is_flag=True, default=False,
+              help='draw the sequences from the model\'s distribution (Rater.sample) instead of searching for the most probable ones')
+@click.option('--temperature', default=1.0, show_default=True, type=click.FloatRange(min=0.0),
+              help='with --sample: below 1 sharpens the distribution, 0 always takes the most probable character')
+@click.option('--top-k', default=0, show_default=True, type=click.IntRange(min=0, max=64),
+              help='with --sample: draw among the K most probable characters only (0: all)')
+@click.option('--seed', default=0, show_default=True, type=click.IntRange(min=0),
+              help='with --sample: the same seed draws the same sequences')
 @click.argument('prefix', type=click.STRING)
-def generate(model, number, variants, context, device_beam, prefix):
-    """Apply a language model, generating the most probable characters (starting with PREFIX string)."""
+def generate(model, number, variants, context, device_beam, sample, temperature, top_k, seed, prefix):
+    """Apply a language model, generating the most probable characters (starting with PREFIX string).
+
+       With --sample the VARIANTS sequences are drawn at random from the model's distribution instead.
+    """
     rater = _load(model, incremental=True)
     if device_beam:
         rater.device_beam = True
     ctx = _contexts(context) if context else rater.underspecify_contexts()
-    for res in rater.generate(prefix, number, ctx, variants):
+    if sample:
+        results = rater.sample(prefix, number, ctx, variants, temperature=temperature, top_k=top_k, seed=seed)
+    else:
+        results = rater.generate(prefix, number, ctx, variants)
+    for res in results:
         click.echo(prefix[:-1] + res)
 
 
