@@ -350,9 +350,15 @@ const char* kl_trace_kernel_name(kl_handle* h, int kind);
 int kl_test_gemm_tn(const uint16_t* A, const uint16_t* B, void* C, const float* bias, int M, int N, int K, long lda,
                     long ldb, long ldc, int out_mode, int splits, void* stream);
 /* the weight-gradient contraction with a K-major A operand: C[m][n] (or C[n][m] if c_transposed) +=
- * sum_k A_km[k][m] * B[n][k] (b_km: B_km[k][n]); KL_ERR_SHAPE where it does not apply (M % 256, K % 64) */
+ * sum_k A_km[k][m] * B[n][k] (b_km: B_km[k][n]); KL_ERR_SHAPE where it does not apply (M % 256, K % 64; K % 32 with
+ * b_km and N a multiple of 256, the shapes of the 256 x 256 tile) */
 int kl_test_gemm_an(const uint16_t* A_km, const uint16_t* B, float* C, int M, int N, int K, long lda_km, long ldb,
                     long ldc, int c_transposed, int b_km, void* stream);
+/* ... and a second product over the same A in the same launch: C2 (+)= A_km^T . B2^T, B2 in the layout b_km names, N a
+ * multiple of 128 (B2 null: the single product).  The 256 x 256 tile serves the pair where N and N2 are multiples of 256. */
+int kl_test_gemm_an2(const uint16_t* A_km, const uint16_t* B, float* C, int M, int N, int K, long lda_km, long ldb, long ldc,
+                     int c_transposed, const uint16_t* B2, float* C2, int N2, long ldb2, long ldc2, int c_transposed2, int b_km,
+                     void* stream);
 /* layer 0's table gradients as segment sums over the time-major rows r = t * B + b of dZ [T*B][ld] (bf16; cols a multiple
  * of 8): dEK[v][cols] = sum of the rows with idx[b][t] == v in [0, V), dCtxK[c][cols] = sum of those with
  * ctx[b][t][0] == c in [0, R) (ctx is [B][T][n_ctx]; n_ctx == 0: no context table).  Ids outside their range are dropped,

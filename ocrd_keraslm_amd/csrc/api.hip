@@ -2286,6 +2286,13 @@ int kl_test_gemm_an(const uint16_t* A_km, const uint16_t* B, float* C, int M, in
   return kl_launch_gemm_an(A_km, B, C, M, N, K, lda_km, ldb, ldc, c_transposed, (hipStream_t)stream, b_km);
 }
 
+int kl_test_gemm_an2(const uint16_t* A_km, const uint16_t* B, float* C, int M, int N, int K, long lda_km, long ldb, long ldc,
+                     int c_transposed, const uint16_t* B2, float* C2, int N2, long ldb2, long ldc2, int c_transposed2, int b_km,
+                     void* stream) {
+  return kl_launch_gemm_an2(A_km, B, C, M, N, K, lda_km, ldb, ldc, c_transposed, B2, C2, N2, ldb2, ldc2, c_transposed2,
+                            (hipStream_t)stream, b_km);
+}
+
 size_t kl_test_segment_sums_ws_bytes(int B, int T, int n_ctx, int V, int R) {
   if (B < 1 || T < 1 || V < 1 || n_ctx < 0 || (n_ctx > 0 && R < 1)) return 0;
   return kl_segment_sums_ws_bytes(B, T, n_ctx, V, R);

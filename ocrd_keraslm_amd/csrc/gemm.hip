@@ -217,7 +217,18 @@ struct KlGemmSecond {
   int c_transposed;
 };
 
-template <int OUT, bool ILV, int RF, int WM, int WN, bool ATR = false, bool BTR = false>
+//
+// TBN x KD x NST = column tile, k-depth of a stage and ring depth: 128 x 64 x 3 everywhere but the weight gradients' wide
+// form, (RF, WM, WN) = (4, 4, 4) with 256 x 32 x 4 or 5 -- a 256 x 256 tile on sixteen waves, each with the same 64 x 64
+// wave tile, K-major operands and split-K atomics only.  Both operand stages are then [32 k][256] images of 512-byte
+// rows, one 1 KiB piece of each per wave and k-step, one fragment set per k-step, and NST - 1 stages in flight.
+// PFR (wide form, five stages): the fragments of k-step kt + 1 are read DURING k-step kt, each into the registers the MFMA
+// group just issued has consumed.  Sixteen waves that pass one barrier per k-step otherwise all read, then all multiply:
+// the matrix pipe idles through every read burst.  With the reads a step ahead a wave's MFMAs are ready at the barrier,
+// the four waves of a SIMD take the pipe in turn and each one's reads hide behind the others' MFMAs.  The barrier of
+// k-step kt then has to see stage kt + 1 landed (one stage less in flight: NST - 2), and stage kt - 1 is still the one
+// that may be restaged behind it -- stage kt's reads were issued in front of that barrier but need not have returned.
+template <int OUT, bool ILV, int RF, int WM, int WN, bool ATR = false, bool BTR = false, int TBN = LBN, int KD = 64, int NST = LSTAGES, bool PFR = false>
 __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_tn_long_kernel(
     const bf16_t* __restrict__ A, const bf16_t* __restrict__ B_, void* __restrict__ Cv_,
     const float* __restrict__ bias, int M, int N_, int K, long lda, long ldb_, long ldc_,
@@ -227,19 +238,24 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_tn_long_kernel(
   void* __restrict__ Cv = Cv_;
   int N = N_, c_t = c_t_;
   long ldb = ldb_, ldc = ldc_;
-  static_assert(!(ATR || BTR) || (RF == 4 && WM == 4 && WN == 2), "K-major operands: 256 x 128 tiles only");
+  static_assert(!(ATR || BTR) || (RF == 4 && WM == 4 && WN == 2 && TBN == 128) || (RF == 4 && WM == 4 && WN == 4 && TBN == 256),
+                "K-major operands: 256 x 128 tiles, or 256 x 256 on sixteen waves");
+  static_assert((TBN == 128 && KD == 64 && NST == 3) || (TBN == 256 && KD == 32 && NST >= 3 && OUT == 2 && ATR && BTR),
+                "256-column tiles: K-major operands, 32-deep stages, split-K atomics");
   constexpr bool PRIO = KL_GEMM_PRIO;
   constexpr int NW = WM * WN;
   constexpr int WROWS = 16 * RF;               // rows per wave
   constexpr int TBM = WROWS * WM;              // tile rows
-  constexpr int WCOLS = LBN / WN;              // columns per wave
+  constexpr int WCOLS = TBN / WN;              // columns per wave
   constexpr int NT = WCOLS / 16;               // column fragments per wave
-  constexpr int PA = TBM / 8 / NW;             // A pieces (8 rows each) per wave and k-step
-  constexpr int PB = LBN / 8 / NW;             // B pieces
+  constexpr int PA = TBM * KD / 512 / NW;      // A pieces (1 KiB: 8 rows of 64 k each) per wave and k-step
+  constexpr int PB = TBN * KD / 512 / NW;      // B pieces
   constexpr int NP = PA + PB;                  // pieces per wave and k-step = the counted vmcnt
   constexpr int NP0 = (NP + 1) / 2;            // ... issued with the first MFMA group
   static_assert(PA >= 1 && PB >= 1 && NP <= 6, "piece split");
-  constexpr int STAGE_BYTES = (TBM + LBN) * 128;
+  constexpr int STAGE_BYTES = (TBM + TBN) * KD * 2;
+  constexpr int A_BYTES = TBM * KD * 2;        // the B image follows the A image
+  constexpr int BROW = TBN * 2;                // bytes of a k-row of the K-major B image
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -261,7 +277,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_tn_long_kernel(
     }
   }
   const int m0 = by * TBM;
-  int n0 = bx * LBN;
+  int n0 = bx * TBN;
   if (second.B != nullptr) {
     if (n0 >= second.n_first) {
       n0 -= second.n_first;
@@ -277,7 +293,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_tn_long_kernel(
   }
   const int kbeg = bz * k_per_split;
   const int kend = min(K, kbeg + k_per_split);
-  const int nkt = (kend - kbeg) / BK;     // host guarantees whole k-tiles
+  const int nkt = (kend - kbeg) / KD;     // host guarantees whole k-tiles
 
   // buffer resources based at this workgroup's first rows; rows past the matrix read as zero
   auto clamp31 = [](long v) { return (int)(v > 0x7fffffffL ? 0x7fffffffL : (v < 0 ? 0 : v)); };
@@ -299,9 +315,10 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_tn_long_kernel(
       continue;
     }
     if (BTR && j >= PA) {
-      // piece p = four k-rows of 256 bytes, 16 lanes each
-      const int krow = 4 * (wave * PB + (j - PA)) + (lane >> 4);
-      const int c = (lane & 15) ^ (2 * ((krow & 3) | (((krow >> 3) & 1) << 2)));
+      // piece p = four k-rows of 256 bytes, 16 lanes each (256-column tiles: two of 512 bytes, as A)
+      constexpr int LPR = BROW / 16;           // lanes per k-row
+      const int krow = (64 / LPR) * (wave * PB + (j - PA)) + lane / LPR;
+      const int c = (lane & (LPR - 1)) ^ (2 * ((krow & 3) | (((krow >> 3) & 1) << 2)));
       vo[j] = (unsigned)((long)krow * ldb * 2 + c * 16);
       continue;
     }
@@ -312,11 +329,11 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_tn_long_kernel(
   const unsigned lds0 = (unsigned)(size_t)(lds_void_t*)smem;
   // the pieces are issued in two halves between the two MFMA groups of a k-step
   auto issue_half = [&](int kt, int stage, int half) {
-    const int soff = (kbeg + kt * BK) * 2;
-    const int soff_a = ATR ? (int)((long)kt * BK * lda * 2) : soff;     // (K-major A: based at kbeg already)
-    const int soff_b = BTR ? (int)((long)kt * BK * ldb * 2) : soff;
+    const int soff = (kbeg + kt * KD) * 2;
+    const int soff_a = ATR ? (int)((long)kt * KD * lda * 2) : soff;     // (K-major A: based at kbeg already)
+    const int soff_b = BTR ? (int)((long)kt * KD * ldb * 2) : soff;
     const unsigned sa = lds0 + stage * STAGE_BYTES + wave * 8 * PA * 128;
-    const unsigned sb = lds0 + stage * STAGE_BYTES + TBM * 128 + wave * 8 * PB * 128;
+    const unsigned sb = lds0 + stage * STAGE_BYTES + A_BYTES + wave * 8 * PB * 128;
 #pragma unroll
     for (int j = half ? NP0 : 0; j < (half ? NP : NP0); ++j) {
       if (j < PA) glds16(rsA, vo[j], soff_a, sa + j * 1024);
@@ -334,8 +351,12 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_tn_long_kernel(
 #pragma unroll
     for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
+  constexpr int AHEAD = NST - 1;               // stages in flight
   if (nkt > 0) issue(0, 0);
   if (nkt > 1) issue(1, 1);
+  if (AHEAD > 2 && nkt > 2) issue(2, 2);
+  if (AHEAD > 3 && nkt > 3) issue(3, 3);
+  static_assert(AHEAD <= 4, "ring start-up");
   const int fr = lane & 15, fq = lane >> 4;
   // K-major A: this lane's part of the transposed-read addresses, one per row fragment (the swizzle
   // term is a lane constant: k-rows s*32 + fq*8 + half*4 + q have (krow & 3) = q, bit 3 = fq & 1)
@@ -353,20 +374,66 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_tn_long_kernel(
     const int fl = 2 * (q | ((fq & 1) << 2));
 #pragma unroll
     for (int j = 0; j < NT; ++j)
-      btr_off[j] = (unsigned)((fq * 8 + q) * 256 + ((((wn * WCOLS + j * 16) >> 3) ^ fl) + (pp >> 1)) * 16 + 8 * (pp & 1));
+      btr_off[j] = (unsigned)((fq * 8 + q) * BROW + ((((wn * WCOLS + j * 16) >> 3) ^ fl) + (pp >> 1)) * 16 + 8 * (pp & 1));
   }
   int stage = 0;
-  for (int kt = 0; kt < nkt; ++kt) {
-    if (kt + 1 < nkt) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NP) : "memory");
+  if (PFR) {
+    static_assert(!PFR || (ATR && BTR && KD == 32 && NST >= 4), "fragment prefetch: the wide form");
+    frag16 fa[RF], fb[NT];
+    auto read_tr = [&](const unsigned char* p, int rowbytes) {
+      frag16 f;
+      const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p));
+      const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p + 4 * rowbytes));
+      // (whole dwords: a halfword-wise copy leaves a VALU instruction, and with it a wait, right behind each read)
+      const uint2 l = __builtin_bit_cast(uint2, lo), h = __builtin_bit_cast(uint2, hi);
+      f.u = uint4{l.x, l.y, h.x, h.y};
+      return f;
+    };
+    if (nkt > 0) {
+      if (nkt >= AHEAD) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((AHEAD - 1) * NP) : "memory");
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+#pragma unroll
+      for (int i = 0; i < RF; ++i) fa[i] = read_tr(smem + atr_off[i], 512);
+#pragma unroll
+      for (int j = 0; j < NT; ++j) fb[j] = read_tr(smem + A_BYTES + btr_off[j], BROW);
+    }
+    for (int kt = 0; kt < nkt; ++kt) {
+      // stage kt + 1 has to have landed: the stages behind it may stay in flight (the last k-steps drain)
+      if (kt + AHEAD - 1 < nkt) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((AHEAD - 2) * NP) : "memory");
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      const int nstage = stage >= 1 ? stage - 1 : NST - 1;
+      if (kt + AHEAD < nkt) issue(kt + AHEAD, nstage);
+      stage = stage + 1 < NST ? stage + 1 : 0;
+      // (behind the last k-step the reads fetch a stage nobody fills any more; their values are dropped)
+      const unsigned char* a_base = smem + stage * STAGE_BYTES;      // (stage kt + 1)
+      const unsigned char* b_base = a_base + A_BYTES;
+#pragma unroll
+      for (int i = 0; i < RF; ++i) {
+        if (PRIO) __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int j = 0; j < NT; ++j) acc[i][j] = mfma16(fa[i].v, fb[j].v, acc[i][j]);
+        if (PRIO) __builtin_amdgcn_s_setprio(0);
+        fa[i] = read_tr(a_base + atr_off[i], 512);
+      }
+#pragma unroll
+      for (int j = 0; j < NT; ++j) fb[j] = read_tr(b_base + btr_off[j], BROW);
+    }
+  }
+  for (int kt = PFR ? nkt : 0; kt < nkt; ++kt) {
+    // (the last AHEAD - 1 k-steps have fewer stages behind them than the count assumes: they drain)
+    if (kt + AHEAD - 1 < nkt) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((AHEAD - 1) * NP) : "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    const bool more = kt + 2 < nkt;
-    const int nstage = stage >= 1 ? stage - 1 : LSTAGES - 1;   // (kt+2) % 3 == (stage+2) % 3
-    if (!ILV && more) issue(kt + 2, nstage);
+    const bool more = kt + AHEAD < nkt;
+    const int nstage = stage >= 1 ? stage - 1 : NST - 1;   // (kt + AHEAD) % NST == (stage + NST - 1) % NST
+    if (!ILV && more) issue(kt + AHEAD, nstage);
     const unsigned char* a_base = smem + stage * STAGE_BYTES;
-    const unsigned char* b_base = a_base + TBM * 128;
+    const unsigned char* b_base = a_base + A_BYTES;
+    constexpr int NS = KD / 32;                // fragment sets per k-step
 #pragma unroll
-    for (int s = 0; s < 2; ++s) {
+    for (int s = 0; s < NS; ++s) {
       frag16 fa[RF], fb[NT];
 #pragma unroll
       for (int i = 0; i < RF; ++i) {
@@ -383,16 +450,19 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_tn_long_kernel(
 #pragma unroll
       for (int j = 0; j < NT; ++j) {
         if (BTR) {
-          const unsigned char* bp = b_base + btr_off[j] + s * 32 * 256;
+          const unsigned char* bp = b_base + btr_off[j] + s * 32 * BROW;
           const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(bp));
-          const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(bp + 4 * 256));
+          const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(bp + 4 * BROW));
           fb[j].s[0] = (bf16_t)lo.x; fb[j].s[1] = (bf16_t)lo.y; fb[j].s[2] = (bf16_t)lo.z; fb[j].s[3] = (bf16_t)lo.w;
           fb[j].s[4] = (bf16_t)hi.x; fb[j].s[5] = (bf16_t)hi.y; fb[j].s[6] = (bf16_t)hi.z; fb[j].s[7] = (bf16_t)hi.w;
         } else {
           fb[j].u = *reinterpret_cast<const uint4*>(b_base + lds_off(wn * WCOLS + j * 16 + fr, s * 4 + fq));
         }
       }
-      if (ILV && more) issue_half(kt + 2, nstage, s);
+      if (ILV && more) {
+        issue_half(kt + AHEAD, nstage, s);
+        if (NS == 1) issue_half(kt + AHEAD, nstage, 1);      // one fragment set: both halves go out behind its reads
+      }
       if (PRIO) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int i = 0; i < RF; ++i)
@@ -400,7 +470,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_tn_long_kernel(
         for (int j = 0; j < NT; ++j) acc[i][j] = mfma16(fa[i].v, fb[j].v, acc[i][j]);
       if (PRIO) __builtin_amdgcn_s_setprio(0);
     }
-    stage = stage + 1 < LSTAGES ? stage + 1 : 0;
+    stage = stage + 1 < NST ? stage + 1 : 0;
   }
 
   if (OUT == 3) {
@@ -860,19 +930,29 @@ int kl_launch_gemm_tn(const bf16_t* A, const bf16_t* B, void* C, const float* bi
 // address one split with 32-bit byte offsets -- more splits where a split's rows would not fit in 2 GiB (the paired
 // launches have twice the column tiles, so half the splits and twice the rows per split: depth 4 / width 1024 /
 // T*B = 262144 fits as a single product and did not as a pair).  Returns the rows per split, 0 = not applicable.
-static int an_rows_per_split(int M, int n_all, int K, long ld_max) {
-  if (M <= 0 || n_all <= 0 || K <= 0 || (M % LBM) || (K % BK)) return 0;
-  const int tiles = (M / LBM) * ((n_all + LBN - 1) / LBN);
+// (tbn, kd: the kernel's column tile and the k-depth of its stages -- 128 and 64, or the wide form's 256 and 32)
+static int an_rows_per_split(int M, int n_all, int K, long ld_max, int tbn = LBN, int kd = BK) {
+  if (M <= 0 || n_all <= 0 || K <= 0 || (M % LBM) || (K % kd)) return 0;
+  const int tiles = (M / LBM) * ((n_all + tbn - 1) / tbn);
   int sp = (256 + tiles - 1) / tiles;          // ~ one workgroup per CU
-  const int nk = K / BK;
+  const int nk = K / kd;
   if (sp > nk / 16) sp = nk / 16;              // at least 16 k-steps per workgroup
   if (sp < 1) sp = 1;
-  int kps = ((nk + sp - 1) / sp) * BK;
-  while ((long)kps * ld_max * 2 >= 0x7fffffffL && kps > BK) {      // 32-bit offsets inside one split
+  int kps = ((nk + sp - 1) / sp) * kd;
+  while ((long)kps * ld_max * 2 >= 0x7fffffffL && kps > kd) {      // 32-bit offsets inside one split
     ++sp;
-    kps = ((nk + sp - 1) / sp) * BK;
+    kps = ((nk + sp - 1) / sp) * kd;
   }
   return (long)kps * ld_max * 2 < 0x7fffffffL ? kps : 0;
+}
+
+// The wide form of the K-major products (256 x 256 tiles on sixteen waves, see gemm_tn_long_kernel): both operands K-major
+// and every product's width a whole number of 256-column tiles.  KL_GEMM_WIDE=0 keeps the 256 x 128 kernel everywhere;
+// KL_GEMM_WIDE_RING=4 the four-stage ring where five stages (all of a CU's 160 KiB) would be granted.
+constexpr int WBN = 256, WBK = 32;
+static bool an_wide(int M, int N, int N2, int b_km) {
+  static const bool on = !(getenv("KL_GEMM_WIDE") && getenv("KL_GEMM_WIDE")[0] == '0');
+  return on && b_km && M > 0 && (M % LBM) == 0 && N > 0 && (N % WBN) == 0 && (N2 % WBN) == 0;
 }
 
 bool kl_gemm_an_applicable(int M, int N, int K, long lda_km) {
@@ -890,10 +970,14 @@ int kl_launch_gemm_an2(const bf16_t* A_km, const bf16_t* B, float* C, int M, int
   long ld_max = lda_km;
   if (b_km && ldb > ld_max) ld_max = ldb;
   if (b_km && B2 != nullptr && ldb2 > ld_max) ld_max = ldb2;
-  const int kps = an_rows_per_split(M, n_all, K, ld_max);
+  const bool wide = an_wide(M, N, B2 != nullptr ? N2 : 0, b_km);
+  int kps = wide ? an_rows_per_split(M, n_all, K, ld_max, WBN, WBK) : 0;
+  const bool go_wide = kps > 0;
+  if (!go_wide) kps = an_rows_per_split(M, n_all, K, ld_max);
   if (kps <= 0) return KL_ERR_SHAPE;
   const int sp = (K + kps - 1) / kps;
-  dim3 grid((n_all + LBN - 1) / LBN, M / LBM, sp);
+  const int tbn = go_wide ? WBN : LBN;
+  dim3 grid((n_all + tbn - 1) / tbn, M / LBM, sp);
   KlGateEpi epi;
   memset(&epi, 0, sizeof(epi));
   KlGemmSecond second;
@@ -907,8 +991,23 @@ int kl_launch_gemm_an2(const bf16_t* A_km, const bf16_t* B, float* C, int M, int
     second.ldc = ldc2;
     second.c_transposed = c_transposed2;
   }
-  const size_t lds = (size_t)LSTAGES * (LBM + LBN) * 128;
   static const int remap = !(getenv("KL_GEMM_XCD") && getenv("KL_GEMM_XCD")[0] == '0');
+  if (go_wide) {
+    static const bool ring4 = getenv("KL_GEMM_WIDE_RING") && getenv("KL_GEMM_WIDE_RING")[0] == '4';
+    static KlLdsGrant grant_5, grant_4;
+    constexpr size_t stage = (size_t)(LBM + WBN) * WBK * 2;
+    if (!ring4 && kl_grant_lds(grant_5, reinterpret_cast<const void*>(&gemm_tn_long_kernel<2, true, 4, 4, 4, true, true, WBN, WBK, 5, true>), 5 * stage) == 0) {
+      hipLaunchKernelGGL((gemm_tn_long_kernel<2, true, 4, 4, 4, true, true, WBN, WBK, 5, true>), grid, dim3(1024), 5 * stage, stream, A_km, B, (void*)C,
+                         (const float*)nullptr, M, N, K, lda_km, ldb, ldc, kps, 1.f, epi, remap, c_transposed, second);
+    } else {
+      (void)hipGetLastError();       // (a refused five-stage grant is not this launch's error)
+      if (kl_grant_lds(grant_4, reinterpret_cast<const void*>(&gemm_tn_long_kernel<2, true, 4, 4, 4, true, true, WBN, WBK, 4>), 4 * stage)) return KL_ERR_LAUNCH;
+      hipLaunchKernelGGL((gemm_tn_long_kernel<2, true, 4, 4, 4, true, true, WBN, WBK, 4>), grid, dim3(1024), 4 * stage, stream, A_km, B, (void*)C,
+                         (const float*)nullptr, M, N, K, lda_km, ldb, ldc, kps, 1.f, epi, remap, c_transposed, second);
+    }
+    return hipGetLastError() == hipSuccess ? 0 : KL_ERR_LAUNCH;
+  }
+  const size_t lds = (size_t)LSTAGES * (LBM + LBN) * 128;
   static KlLdsGrant grant_a, grant_b;
   if (kl_grant_lds(grant_a, reinterpret_cast<const void*>(&gemm_tn_long_kernel<2, true, 4, 4, 2, true, false>), lds)) return KL_ERR_LAUNCH;
   if (kl_grant_lds(grant_b, reinterpret_cast<const void*>(&gemm_tn_long_kernel<2, true, 4, 4, 2, true, true>), lds)) return KL_ERR_LAUNCH;

@@ -106,6 +106,8 @@ SIGNATURES = {
                                   C.c_long, C.c_long, C.c_long, C.c_int, C.c_int, C.c_void_p]),
     "kl_test_gemm_an": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long,
                                   C.c_long, C.c_int, C.c_int, C.c_void_p]),
+    "kl_test_gemm_an2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long,
+                                   C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, C.c_void_p]),
     "kl_test_segment_sums_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "kl_test_segment_sums_share": (C.c_int, [C.c_int, C.c_int]),
     "kl_test_segment_sums": (C.c_int, [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
