@@ -404,16 +404,29 @@ int kl_test_rate_topk(const float* logits, long ld, int rows, int V, const int32
  *   off_Cb  bf16 [(T+1)B][W]   cell states as the backward scan read them (c_in_cb only)
  *   off_G   bf16 [TB][4W]      gate activations i, f, c, o: [4][W] per row, or [W][4] with g_interleaved
  *   off_dZ  bf16 [TB][4W]      gradients of the gate pre-activations, always [4][W] per row
+ *   off_Hd  bf16 [TB][W]       layer l's outputs times its dropout mask, row t * B + b = step t, as the layer above, the output
+ *                              layer and the dK product of the layer above read them; 0 where the layer has none (layer 0, or
+ *                              a window without masks).  Always the row-major array: where the window's weight gradients
+ *                              contract over the transposed copies the wide forward scans write (KL_WG_SCAN_T), the dK
+ *                              product reads that copy of the same numbers, which the view does not report.
  * Byte offsets into ws, per layer.  The rounding points the window's plan chose: p_bf16_mask bit l -- layer l's gate inputs
  * from the input side (x . K + b) passed through bf16 rows; dh_bf16 -- the gradient from above (output layer and the layer
  * above) passed through bf16 rows; c_in_cb -- the backward scan read bf16 cell states.  scan2_rows: rows per forward phase of
  * the second-generation wide scans (0: another family).  Nothing is launched or allocated: the answer was noted when the
  * window's launch sequence was built, so it also holds for a window that was a replayed graph.  KL_ERR_STATE if no
- * training window of that shape has run on ws. */
+ * training window of that shape has run on ws.
+ * The weight-gradient stage behind the scans: wg_route = KL_WG_* bits, exactly one of the first three; wg_pair_mask bit l --
+ * layer l's dU and dK came from one paired launch; wg_db_scan_mask bit l -- layer l's bias gradient was summed by its backward
+ * scan from the f32 values (else by a column sum over the stored bf16 dZ). */
+#define KL_WG_KMAJOR 1     /* products read dZ and the activations as the scans wrote them (K-major plan) */
+#define KL_WG_SCAN_T 2     /* ... contract over the transposed outputs the wide forward scans wrote */
+#define KL_WG_TRANSPOSE 4  /* ... over explicit transposes into buffers padded to a multiple of 8 rows */
+#define KL_WG_SEGSUM 8     /* layer 0: sorted segment sums for the characters and the first context variable (else one-hot products) */
+#define KL_WG_PAIR_CTX 16  /* layer 0: the first context variable's one-hot product shared a launch with the characters' */
 typedef struct kl_window_view {
   int32_t depth, width, B, T;
-  int32_t g_interleaved, c_in_cb, dh_bf16, p_bf16_mask, scan2_rows, reserved[7];
-  uint64_t off_H[16], off_C[16], off_Cb[16], off_G[16], off_dZ[16];
+  int32_t g_interleaved, c_in_cb, dh_bf16, p_bf16_mask, scan2_rows, wg_route, wg_pair_mask, wg_db_scan_mask, reserved[4];
+  uint64_t off_H[16], off_C[16], off_Cb[16], off_G[16], off_dZ[16], off_Hd[16];
 } kl_window_view;
 int kl_test_window_view(const kl_handle* h, int B, int T, const void* ws, kl_window_view* out);
 

@@ -184,6 +184,9 @@ struct kl_handle {
     const void* ws;
     int scan2_rows, g_interleaved, c_in_cb, dh_bf16;
     unsigned p_bf16_mask;
+    // the weight-gradient stage (filled in once the stage's launches are built): KL_WG_* bits, dU / dK pairs and scan-summed
+    // db per layer, layers whose masked outputs Hd were written
+    unsigned wg_route = 0, wg_pair_mask = 0, wg_db_scan_mask = 0, hd_mask = 0;
   };
   std::vector<ViewNote> view_notes;
   bool segsum = true;           // KL_SEGSUM = 0: layer 0's table gradients as one-hot products (default: sorted segment sums, segsum.hip -- read in
@@ -1362,6 +1365,8 @@ static int train_window_body(kl_handle* h, int B, int T, const int32_t* idx, con
   // B3: reverse recurrence -- persistent scan where the shape allows it, else the
   // launch-per-step layer wavefront
   std::vector<char> wg_done(L, 0);
+  // (what kl_test_window_view says about this stage: noted by weight_grads as it chooses)
+  unsigned wg_route = 0, wg_pair_mask = 0, wg_db_scan_mask = 0;
   // B4/B5: weight gradients of one layer, K = B*T contractions over transposed activations
   // dz_km: the contractions over the T*B rows read dZ and the activations K-major, as the scans wrote them
   // (kl_launch_gemm_an, the hardware transpose read) -- no transposed copies at all
@@ -1380,6 +1385,9 @@ static int train_window_body(kl_handle* h, int B, int T, const int32_t* idx, con
       if (pe == KL_ERR_SHAPE) pair_uk = false;
       else KL_TRY(pe);
     }
+    wg_route |= dz_km ? KL_WG_KMAJOR : (w.ht_ready ? KL_WG_SCAN_T : KL_WG_TRANSPOSE);
+    if (pair_uk) wg_pair_mask |= 1u << l;
+    if (db_done) wg_db_scan_mask |= 1u << l;
     if (pair_uk) {
       // (dU and dK done in one pass)
     } else if (dz_km) {
@@ -1444,6 +1452,8 @@ static int train_window_body(kl_handle* h, int B, int T, const int32_t* idx, con
       KL_TRY(kl_launch_f32_to_bf16_t(w.dEKT, Vp, 4 * W, Vp, w.dEKT_bf, nullptr, Vp, 0, s));
       KL_TRY(kl_launch_f32_to_bf16_t(w.dEKT, Vp, 4 * W, Vp, w.dEK_bf, nullptr, 4 * W, 1, s));
       }
+      if (seg) wg_route |= KL_WG_SEGSUM;
+      if (pair_ctx) wg_route |= KL_WG_PAIR_CTX;
       // dK0[:W] = E^T . dEK      (C[W][4W] = ET[W][Vp] . dEKT[4W][Vp]^T)
       KL_TRY(kl_launch_gemm_tn(d.ET, w.dEKT_bf, grads + h->off_K[0], nullptr, W, 4 * W, Vp, Vp, Vp, 4 * W, 0, 1, 1.f, s));
       // dE += dEK . K0[:W]^T     (C[V][W] = dEK[V][4W] . Kn0[W][4W]^T)
@@ -1696,6 +1706,11 @@ static int train_window_body(kl_handle* h, int B, int T, const int32_t* idx, con
 
   for (int l = L - 1; l >= 0; --l)
     if (!wg_done[l]) KL_TRY(weight_grads(l, false, false, w.km_plan));
+  for (auto& n : h->view_notes)
+    if (n.B == B && n.T == T && n.ws == ws) {
+      n.wg_route = wg_route; n.wg_pair_mask = wg_pair_mask; n.wg_db_scan_mask = wg_db_scan_mask;
+      n.hd_mask = masks != nullptr ? ((1u << L) - 1u) & ~1u : 0u;      // (forward_impl: every layer above the first writes Hd)
+    }
 
   // F7: embedding regularisers (training phase only)
   std::vector<const float*> ctabs(c.n_ctx);
@@ -2588,11 +2603,14 @@ extern "C" int kl_test_window_view(const kl_handle* h, int B, int T, const void*
   out->depth = h->cfg.depth; out->width = h->cfg.width; out->B = B; out->T = T;
   out->g_interleaved = note->g_interleaved; out->c_in_cb = note->c_in_cb; out->dh_bf16 = note->dh_bf16;
   out->p_bf16_mask = (int32_t)note->p_bf16_mask; out->scan2_rows = note->scan2_rows;
+  out->wg_route = (int32_t)note->wg_route; out->wg_pair_mask = (int32_t)note->wg_pair_mask;
+  out->wg_db_scan_mask = (int32_t)note->wg_db_scan_mask;
   const unsigned char* base = reinterpret_cast<const unsigned char*>(ws);
   auto off = [&](const void* p) { return (uint64_t)(reinterpret_cast<const unsigned char*>(p) - base); };
   for (int l = 0; l < h->cfg.depth; ++l) {      // (config_ok: at most 16 layers)
     out->off_H[l] = off(w.H[l]); out->off_C[l] = off(w.C[l]); out->off_Cb[l] = off(w.Cb[l]);
     out->off_G[l] = off(w.G[l]); out->off_dZ[l] = off(w.dZ[l]);
+    out->off_Hd[l] = ((note->hd_mask >> l) & 1u) ? off(w.Hd[l]) : 0;
   }
   return 0;
 }

@@ -18,6 +18,8 @@ KL_PREC_SPLIT = 3
 KL_RATE_ALTS_MAX = 8     # alternatives per position kl_rate_window_alts delivers at most
 KL_SAMPLE_MAX_ROWS = 1024  # chains per kl_sample_pick call
 KL_SAMPLE_MAX_TOPK = 64
+# kl_window_view.wg_route
+KL_WG_KMAJOR, KL_WG_SCAN_T, KL_WG_TRANSPOSE, KL_WG_SEGSUM, KL_WG_PAIR_CTX = 1, 2, 4, 8, 16
 
 
 class KlConfig(C.Structure):
@@ -29,9 +31,10 @@ class KlWindowView(C.Structure):
     """kl_window_view of include/keraslm_hip.h (kl_test_window_view)"""
     _fields_ = [("depth", C.c_int32), ("width", C.c_int32), ("B", C.c_int32), ("T", C.c_int32),
                 ("g_interleaved", C.c_int32), ("c_in_cb", C.c_int32), ("dh_bf16", C.c_int32), ("p_bf16_mask", C.c_int32),
-                ("scan2_rows", C.c_int32), ("reserved", C.c_int32 * 7),
+                ("scan2_rows", C.c_int32), ("wg_route", C.c_int32), ("wg_pair_mask", C.c_int32),
+                ("wg_db_scan_mask", C.c_int32), ("reserved", C.c_int32 * 4),
                 ("off_H", C.c_uint64 * 16), ("off_C", C.c_uint64 * 16), ("off_Cb", C.c_uint64 * 16),
-                ("off_G", C.c_uint64 * 16), ("off_dZ", C.c_uint64 * 16)]
+                ("off_G", C.c_uint64 * 16), ("off_dZ", C.c_uint64 * 16), ("off_Hd", C.c_uint64 * 16)]
 
 
 class KlError(RuntimeError):

@@ -809,6 +809,19 @@ def check_train_window_gradients(depth, width, voc, B, T, n_ctx, use_masks, want
     win = read_window(lm)
     first, n = win["info"]["first"], win["info"]["n"]
     exact_checks(win, states[first:first + n], st_got[first:first + n], n, where=(depth, width, voc, B, T, n_ctx))
+    # ... and the weight-gradient stage held to the f64 products of those arrays (tests/window_grads.py), where the window ran as
+    # ONE group on the batch as given.  Layer 0's character rows are left to tests/test_window_grads_gpu.py (their allowance
+    # for sums near a rounding boundary: see the note in tests/window_grads.py).
+    info = win["info"]
+    if (info["groups"], info["B"], info["first"], info["n"]) == (1, B, 0, B):
+        from tests import window_grads as WG
+        from tests.window_ref import read_window_padded
+        report, err = WG.check_window_grads(read_window_padded(lm), idx, ctx, lm.params.detach().cpu().numpy(),
+                                            lm.grads.detach().cpu().numpy(), lm.layout, width=lm.width,
+                                            where=(depth, width, voc, B, T, n_ctx), raise_=False)
+        print("weight gradients against the products of the window's arrays:", WG.route_text(win["view"]), "|", WG.ratio_line(report, depth))
+        if err is not None and err.parts - {WG.CHARACTERS}:
+            raise WG.GradMismatch([f for f in err.failures if f[0] != WG.CHARACTERS], (depth, width, voc, B, T, n_ctx))
 
 
 def test_adam_step_matches_oracle():

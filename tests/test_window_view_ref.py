@@ -57,30 +57,62 @@ def test_layout_decoders_round_trip(interleaved, cb, width, n):
     if not cb:
         for l in range(L):
             arrs["c"][l][:, -1] = arrs["cT"][l]      # (block T is one array)
+    arrs["hd"] = [None, bf((n, T, width))]           # (the masked outputs: layer 0 has none)
     view = dict(depth=L, width=Wp, B=B, T=T, g_interleaved=interleaved, c_in_cb=cb, dh_bf16=0, p_bf16_mask=0, scan2_rows=0)
     off, offs = 0, {}
     for key, size in (("off_H", (T + 1) * B * Wp * 2), ("off_C", (T + 1) * B * Wp * 4), ("off_G", T * B * 4 * Wp * 2),
-                      ("off_dZ", T * B * 4 * Wp * 2), ("off_Cb", (T + 1) * B * Wp * 2)):
+                      ("off_dZ", T * B * 4 * Wp * 2), ("off_Cb", (T + 1) * B * Wp * 2), ("off_Hd", T * B * Wp * 2)):
         offs[key] = []
         for _l in range(L):
             off = (off + 255) // 256 * 256 + 256
             offs[key].append(off)
             off += size
+    offs["off_Hd"][0] = 0
     view.update(offs)
     ws = R.encode_window(arrs, view)
     got = R.decode_window(ws, view, width=width, n=n)
     for key in ("h", "c", "gates", "dz", "h0", "c0", "cT"):
         for l in range(L):
             assert np.array_equal(got[key][l], arrs[key][l]), (key, l)
+    hd = R.decode_hd(ws, view, width=width, n=n)
+    assert hd[0] is None and np.array_equal(hd[1], arrs["hd"][1])
+    assert R.decode_hd(ws, {k: v for k, v in view.items() if k != "off_Hd"}) == [None] * L      # (a view from before the field)
     # the bytes really lie as the header says: gate g of unit u of stream b at step t
     import torch
     t, b, g, u, l = 1, n - 1, 2, width - 1, 1
     G = ws[view["off_G"][l]:view["off_G"][l] + T * B * 4 * Wp * 2].view(torch.bfloat16)
     at = (t * B + b) * 4 * Wp + (u * 4 + g if interleaved else g * Wp + u)
     assert float(G[at]) == arrs["gates"][l][b, t, g, u]
+    t, b, u, l = 2, n - 1, width - 1, 1      # the masked output of unit u of stream b at step t: row t * B + b, no block 0
+    Hd = ws[view["off_Hd"][l]:view["off_Hd"][l] + T * B * Wp * 2].view(torch.bfloat16)
+    assert float(Hd[(t * B + b) * Wp + u]) == arrs["hd"][l][b, t, u]
     # rows and columns beyond the trimmed ones are the fill: the finite check sees them when it is given all of them
     full = width == Wp and n == B
     assert got["finite"] == dict(h=full, gates=full, dz=full, cb=full or not cb)
+
+
+def test_view_struct_and_dict():
+    """the fields from before the weight-gradient stage was added keep their offsets (the scalars in front, the five offset
+    arrays from byte 64 on), the new ones took four of the reserved words and the end of the struct; `view_dict` carries all"""
+    import ctypes as C
+    from ocrd_keraslm_amd.lib import hipabi
+    V = hipabi.KlWindowView
+    scalars = ["depth", "width", "B", "T", "g_interleaved", "c_in_cb", "dh_bf16", "p_bf16_mask", "scan2_rows", "wg_route", "wg_pair_mask",
+               "wg_db_scan_mask", "reserved"]
+    assert [getattr(V, k).offset for k in scalars] == [4 * i for i in range(len(scalars))]
+    arrays = ["off_H", "off_C", "off_Cb", "off_G", "off_dZ", "off_Hd"]
+    assert [getattr(V, k).offset for k in arrays] == [64 + 128 * i for i in range(6)] and C.sizeof(V) == 64 + 128 * 6
+    assert (hipabi.KL_WG_KMAJOR, hipabi.KL_WG_SCAN_T, hipabi.KL_WG_TRANSPOSE, hipabi.KL_WG_SEGSUM, hipabi.KL_WG_PAIR_CTX) == (1, 2, 4, 8, 16)
+    v = V(depth=3, width=128, B=40, T=5, p_bf16_mask=5, wg_route=hipabi.KL_WG_TRANSPOSE | hipabi.KL_WG_SEGSUM, wg_pair_mask=4,
+          wg_db_scan_mask=6)
+    for l in range(3):
+        v.off_H[l], v.off_Hd[l] = 1000 + l, 7000 * l
+    d = R.view_dict(v)
+    assert (d["depth"], d["p_bf16_mask"], d["wg_route"], d["wg_pair_mask"], d["wg_db_scan_mask"]) == (3, 5, 12, 4, 6)
+    assert d["off_H"] == [1000, 1001, 1002] and d["off_Hd"] == [0, 7000, 14000] and len(d["off_dZ"]) == 3
+    from tests import window_grads as WG
+    assert (WG.WG_KMAJOR, WG.WG_SCAN_T, WG.WG_TRANSPOSE, WG.WG_SEGSUM, WG.WG_PAIR_CTX) == (1, 2, 4, 8, 16)
+    assert WG.route_text(d) == "transposes, pairs 001, db by scan 011, layer 0 segment sums"
 
 
 @pytest.fixture(scope="module")

@@ -185,7 +185,9 @@ def _torch():
 
 def view_dict(view):
     d = {k: getattr(view, k) for k in ("depth", "width", "B", "T", "g_interleaved", "c_in_cb", "dh_bf16", "p_bf16_mask", "scan2_rows")}
-    for k in ("off_H", "off_C", "off_Cb", "off_G", "off_dZ"):
+    for k in ("wg_route", "wg_pair_mask", "wg_db_scan_mask"):      # (the weight-gradient stage: tests/window_grads.py)
+        d[k] = getattr(view, k)
+    for k in ("off_H", "off_C", "off_Cb", "off_G", "off_dZ", "off_Hd"):
         d[k] = [int(v) for v in getattr(view, k)[:view.depth]]
     return d
 
@@ -234,10 +236,26 @@ def decode_window(ws, view, width=None, n=None):
     return out
 
 
+def decode_hd(ws, view, width=None, n=None):
+    """The dropout-masked outputs behind `off_Hd`, per layer: [n][T][W] like `decode_window`'s h (row t * B + b = step t), None
+    where the view has none (offset 0: layer 0, a window without masks, a view dict from before the field)."""
+    torch = _torch()
+    L, Wp, B, T = view["depth"], view["width"], view["B"], view["T"]
+    W = Wp if width is None else width
+    n = B if n is None else n
+    out = []
+    for l in range(L):
+        off = view.get("off_Hd", [0] * L)[l]
+        out.append(_rows(ws, off, torch.bfloat16, T, B, Wp)[:, :n, :W].permute(1, 0, 2).float().cpu().numpy() if off else None)
+    return out
+
+
 def window_bytes(view):
     L, Wp, B, T = view["depth"], view["width"], view["B"], view["T"]
     end = 0
     for l in range(L):
+        if view.get("off_Hd", [0] * L)[l]:
+            end = max(end, view["off_Hd"][l] + T * B * Wp * 2)
         end = max(end, view["off_H"][l] + (T + 1) * B * Wp * 2, view["off_C"][l] + (T + 1) * B * Wp * 4,
                   view["off_Cb"][l] + (T + 1) * B * Wp * 2, view["off_G"][l] + T * B * 4 * Wp * 2, view["off_dZ"][l] + T * B * 4 * Wp * 2)
     return end
@@ -272,6 +290,8 @@ def encode_window(arrs, view, fill=0xFF):
         else:
             G.view(T, B, 4, Wp)[:, :n, :, :W] = g
         dZ.view(T, B, 4, Wp)[:, :n, :, :W] = t(arrs["dz"][l]).permute(1, 0, 2, 3).to(torch.bfloat16)
+        if view.get("off_Hd", [0] * L)[l]:
+            _rows(ws, view["off_Hd"][l], torch.bfloat16, T, B, Wp)[:, :n, :W] = t(arrs["hd"][l]).permute(1, 0, 2).to(torch.bfloat16)
     return ws
 
 
@@ -282,6 +302,17 @@ def read_window(lm):
     view, ws, info = lm.window_view()
     vd = view_dict(view)
     out = decode_window(ws, vd, width=lm.width)
+    out["view"], out["info"] = vd, info
+    return out
+
+
+def read_window_padded(lm):
+    """... the same at the PADDED width, with the masked outputs (`decode_hd`) as "hd": what the weight-gradient products of
+    tests/window_grads.py were computed from, every row and column of it"""
+    view, ws, info = lm.window_view()
+    vd = view_dict(view)
+    out = decode_window(ws, vd)
+    out["hd"] = decode_hd(ws, vd)
     out["view"], out["info"] = vd, info
     return out
 
