@@ -135,10 +135,10 @@ struct kl_handle {
   bool sentinel = true;         // wide scans hand off by data sentinels instead of counters (KL_SENTINEL=0: counters)
   bool gemm_an = true;          // weight gradients read the backward scan's dZ K-major, no transposed copy (KL_GEMM_AN=0: dZ^T)
   bool xcd_local = false;       // KL_XCD_LOCAL=1: sentinel hand-off inside one XCD through its L2 (plain stores) where the placement allows
-  bool sentinel_bwd = true;
+  bool sentinel_bwd = true;     // sentinel hand-off for the wide backward scan too (KL_SENTINEL_BWD=0, or KL_SENTINEL=0: counters)
   bool sentinel_roll = true;    // KL_SENTINEL_ROLL=0: pre-fill all of dZ instead of re-arming two steps ahead inside the scan
   bool sentinel_bwd_all = false; // KL_SENTINEL_BWD=2: also with one row block per workgroup
-  bool xcd_local_bwd = false;    // KL_XCD_LOCAL_BWD=1     // the same for the wide backward scan (KL_SENTINEL_BWD=0, or KL_SENTINEL=0: counters)
+  bool xcd_local_bwd = false;    // KL_XCD_LOCAL_BWD=1 (with KL_XCD_LOCAL=1): XCD-local publishes for the wide backward scan too
   bool w32 = true;              // width 1024: the eight-wave scans of lstm_scan_w32.hip (KL_W32=0: the thin scans)
   bool w32_local = false;       // KL_W32_LOCAL=1: ... handing over through the XCD's own L2 where the placement allows (measured slower: 112 vs 104 ms per cfg5 step)
   int w32_min_rb = 8;           // ... from this many row blocks of 16 streams (KL_W32_MIN_RB)
@@ -189,6 +189,15 @@ struct kl_handle {
     unsigned wg_route = 0, wg_pair_mask = 0, wg_db_scan_mask = 0, hd_mask = 0;
   };
   std::vector<ViewNote> view_notes;
+  // the note of (B, T, ws); insert: a new one where there is none (the 64 most recent are kept), else null
+  ViewNote* view_note(int B, int T, const void* ws, bool insert) {
+    for (auto& n : view_notes)
+      if (n.B == B && n.T == T && n.ws == ws) return &n;
+    if (!insert) return nullptr;
+    if (view_notes.size() >= 64) view_notes.erase(view_notes.begin());
+    view_notes.push_back(ViewNote{B, T, ws, 0, 0, 0, 0, 0u});
+    return &view_notes.back();
+  }
   bool segsum = true;           // KL_SEGSUM = 0: layer 0's table gradients as one-hot products (default: sorted segment sums, segsum.hip -- read in
                                 // kl_create, it decides the window workspace's size)
   bool fuse_wg = true;          // KL_FUSE_WG = 0: one launch per weight-gradient product (else products over the same dZ share a pass)
@@ -1233,6 +1242,20 @@ static int window_logits(kl_handle* h, int B, int T, const int32_t* idx, const i
   return kl_launch_thin_gemm(&op, B * T, V, w.logits, V, nullptr, h->precision, s);
 }
 
+// the tail of a forward window in either layout: softmax + CE (means over mean_rows streams), probabilities batch-major, the scans' status
+static int forward_window_tail(kl_handle* h, WindowWs& w, int B, int T, const int32_t* tgt, int mean_rows, float* probs, float* loss_acc, hipStream_t s) {
+  const int V = h->cfg.voc_size;
+  KL_TRY(kl_launch_softmax_ce(w.logits, V, B * T, V, tgt, B, T, 1.0f / (h->last_only ? (float)mean_rows : (float)mean_rows * (float)T),
+                              nullptr, 0, tgt ? loss_acc : nullptr, w.rowstat, 1, s, h->last_only));
+  if (probs) {
+    if (B == 1) KL_TRY(hip_ok(hipMemcpyAsync(probs, w.logits, (size_t)T * V * sizeof(float), hipMemcpyDeviceToDevice, s)));
+    else KL_TRY(kl_launch_rows_tm_to_bm(w.logits, V, probs, B, T, V, s));
+  }
+  // a timed-out hand-off in the persistent scan surfaces as loss_acc[3] != 0
+  if (loss_acc) hipLaunchKernelGGL(scan_status_kernel, dim3(1), dim3(64), 0, s, w.scan_status, loss_acc);
+  return hip_ok(hipGetLastError());
+}
+
 static int forward_window_body(kl_handle* h, int B, int T, const int32_t* idx, const int32_t* ctx, const int32_t* tgt,
                       float* states, float* probs, float* loss_acc, void* ws, size_t ws_bytes, void* stream) {
   if (!h || !idx || !states || !ws || B < 1 || T < 1) return KL_ERR_ARG;
@@ -1246,420 +1269,351 @@ static int forward_window_body(kl_handle* h, int B, int T, const int32_t* idx, c
   // the backward, instead of the launch-per-step inference kernels (1024 x 256 characters: 41 ms -> 4.6 ms).
   if (h->precision == KL_PREC_BF16 && ws_bytes >= carve_window(h, nullptr, B, T, 1, nullptr)) {
     carve_window(h, ws, B, T, 1, &w);
-    const int BT = B * T;
     KL_TRY(kl_zero_async(w.scan_status, (4 + 256) * sizeof(unsigned), s));
     w.km_plan = true;                  // (no transposed outputs: nothing is going to contract over the rows)
     w.scan2_rows = plan_scan2(h, B, T, true, false);
     KL_TRY(forward_impl(h, B, T, idx, ctx, states, nullptr, 1, w, s));
     const bf16_t* Htop = (const bf16_t*)w.H[L - 1] + (size_t)B * W;
-    KL_TRY(kl_launch_gemm_tn(Htop, h->d.E_hi, w.logits, nullptr, BT, V, W, W, W, V, 0, 1, 1.f, s));
+    KL_TRY(kl_launch_gemm_tn(Htop, h->d.E_hi, w.logits, nullptr, B * T, V, W, W, W, V, 0, 1, 1.f, s));
     const int mean_rows = (h->loss_rows > 0 && h->loss_rows <= B) ? h->loss_rows : B;      // (a padded batch: kl_set_loss_rows)
-    KL_TRY(kl_launch_softmax_ce(w.logits, V, BT, V, tgt, B, T, 1.0f / (h->last_only ? (float)mean_rows : (float)mean_rows * (float)T),
-                                nullptr, 0, tgt ? loss_acc : nullptr, w.rowstat, 1, s, h->last_only));
-    if (probs) {
-      if (B == 1) KL_TRY(hip_ok(hipMemcpyAsync(probs, w.logits, (size_t)T * V * sizeof(float), hipMemcpyDeviceToDevice, s)));
-      else KL_TRY(kl_launch_rows_tm_to_bm(w.logits, V, probs, B, T, V, s));
-    }
-    if (loss_acc) hipLaunchKernelGGL(scan_status_kernel, dim3(1), dim3(64), 0, s, w.scan_status, loss_acc);
-    return hip_ok(hipGetLastError());
+    return forward_window_tail(h, w, B, T, tgt, mean_rows, probs, loss_acc, s);
   }
   if (ws_bytes < carve_window(h, ws, B, T, 0, &w)) return KL_ERR_WORKSPACE;
   KL_TRY(window_logits(h, B, T, idx, ctx, states, w, s));
-  KL_TRY(kl_launch_softmax_ce(w.logits, V, B * T, V, tgt, B, T, 1.0f / (h->last_only ? (float)B : (float)B * T), nullptr, 0,
-                              tgt ? loss_acc : nullptr, w.rowstat, 1, s, h->last_only));
-  if (probs) {
-    if (B == 1) KL_TRY(hip_ok(hipMemcpyAsync(probs, w.logits, (size_t)T * V * sizeof(float), hipMemcpyDeviceToDevice, s)));
-    else KL_TRY(kl_launch_rows_tm_to_bm(w.logits, V, probs, B, T, V, s));
-  }
-  // a timed-out hand-off in the persistent scan surfaces as loss_acc[3] != 0
-  if (loss_acc) hipLaunchKernelGGL(scan_status_kernel, dim3(1), dim3(64), 0, s, w.scan_status, loss_acc);
-  return hip_ok(hipGetLastError());
+  return forward_window_tail(h, w, B, T, tgt, B, probs, loss_acc, s);      // (this layout's means are over all B streams)
 }
 
-static int train_window_body(kl_handle* h, int B, int T, const int32_t* idx, const int32_t* ctx, const int32_t* tgt,
-                    float* states, const float* masks, float* grads, float* loss_acc, void* ws, size_t ws_bytes,
-                    void* stream) {
-  if (!h || !idx || !tgt || !states || !grads || !ws || B < 1 || T < 1) return KL_ERR_ARG;
-  if (h->cfg.n_ctx > 0 && !ctx) return KL_ERR_ARG;
-  if (h->precision != KL_PREC_BF16) return KL_ERR_STATE;
-  hipStream_t s = (hipStream_t)stream;
-  WindowWs w;
-  if (ws_bytes < carve_window(h, ws, B, T, 1, &w)) return KL_ERR_WORKSPACE;
-  const kl_config& c = h->cfg;
-  const int W = c.width, V = c.voc_size, Vp = h->Vp, L = c.depth;
-  const int BT = B * T, BTp = round_up_i(BT, 8);
-  const size_t BW = (size_t)B * W;
-  const float* P = h->params;
-  Derived& d = h->d;
-  const int ksplit = BT >= 4096 ? 8 : (BT >= 1024 ? 4 : 1);
+struct TrainCall {       // a kl_train_window call as the stages of its backward half see it
+  kl_handle* h; int B, T; const int32_t *idx, *ctx, *tgt; const float* masks; float *grads, *loss_acc; hipStream_t s;
+  WindowWs& w; kl_handle::ViewNote& note;      // what kl_test_window_view will say about this window: the stages note their routes in it
+  int W, V, Vp, L, BT, BTp; size_t BW;
+  int ksplit;            // split of the B*T contraction in the kl_launch_gemm_tn products
+  long ldtf;             // leading dimension of the scans' transposed outputs HTf: (T+1) B
+  int dh_mode;           // 1: dH travels as bf16 (second-generation backward scan)
+  bool top_masked; float inv_count;
+  bool wide_fits, seq128, sequential;      // which backward scans the shape and the switches allow (train_window_body)
+};
+// a backward-scan path's "not mine" (as STEP_PASS: no public return code -- those are 0 .. 5, keraslm_hip.h)
+constexpr int TRAIN_PASS = -1;
+static_assert(TRAIN_PASS < KL_OK, "TRAIN_PASS must not be a public return code");
 
-  KL_TRY(kl_zero_async(grads, h->n_params * sizeof(float), s));
-  KL_TRY(kl_zero_async(w.scan_status, (4 + 256) * sizeof(unsigned), s));
-  // (M = 4W rows of dZ as the K-major A operand: W % 64 == 0, T*B % 64 == 0)
-  w.km_plan = h->gemm_an && BTp == BT && kl_gemm_an_applicable(4 * W, W, BT, 4 * W);
-  w.scan2_rows = plan_scan2(h, B, T, w.km_plan, true);
-  w.scan2_bwd = w.scan2_rows != 0;
-  KL_TRY(forward_impl(h, B, T, idx, ctx, states, masks, 1, w, s));
-  {
-    kl_handle::ViewNote note{B, T, ws, w.scan2_rows, w.scan2_bwd ? 1 : 0, (w.scan2_bwd && h->scan2_bf16) ? 1 : 0, w.scan2_bwd ? 1 : 0,
-                             w.p_bf16_mask};
-    bool found = false;
-    for (auto& n : h->view_notes)
-      if (n.B == B && n.T == T && n.ws == ws) { n = note; found = true; }
-    if (!found) {
-      if (h->view_notes.size() >= 64) h->view_notes.erase(h->view_notes.begin());
-      h->view_notes.push_back(note);
-    }
+// one operand [B*T][N] of a product that contracts over the B*T rows, in the forms it exists in
+struct RowsOperand {
+  const bf16_t* km; long ld;      // as a scan wrote it, row-major (null: a one-hot matrix, which only has the transposed form)
+  const bf16_t* t; long ldt;      // transposed [N][ldt]: by a scan (B*T columns), one-hot or dZ^T (BTp columns); null: "transpose me" (into w.HT)
+};
+// the (masked) outputs of layer l at steps 1..T: what layer l + 1 and the output layer read
+static RowsOperand layer_out(const TrainCall& c, int l) {
+  const WindowWs& w = c.w;
+  if (c.masks != nullptr && l > 0) return {w.Hd[l], c.W, w.ht_ready ? w.HdT[l] : nullptr, c.BT};
+  return {(const bf16_t*)w.H[l] + c.BW, c.W, w.ht_ready ? w.HTf[l] + c.B : nullptr, c.ldtf};
+}
+
+// One product over the B*T rows: out[M][N] (+)= a^T . x, or with out_t its transpose [N][M]; a = gate or logit gradients, a.t in place
+// where km is off.  km: both operands as they lie in memory (kl_launch_gemm_an, the hardware transpose read), no transposed copies;
+// else over the transposed copies, x's as a scan (or kl_launch_onehot_*) wrote it or made here by an explicit transpose
+static int rows_product(const TrainCall& c, bool km, const RowsOperand& a, int M, const RowsOperand& x, int N, float* out, long ldc, bool out_t) {
+  const bool onehot = x.km == nullptr;
+  if (km) return kl_launch_gemm_an(a.km, onehot ? x.t : x.km, out, M, N, c.BT, a.ld, onehot ? x.ldt : x.ld, ldc, out_t ? 1 : 0, c.s, onehot ? 0 : 1);
+  const bf16_t* xT = x.t;
+  long ldx = x.ldt; int K = onehot ? c.BTp : c.BT;
+  if (!xT) {
+    KL_TRY(kl_launch_transpose_bf16(x.km, x.ld, c.w.HT, c.BTp, c.BT, N, c.s));
+    xT = c.w.HT; ldx = c.BTp; K = c.BTp;
   }
+  return out_t ? kl_launch_gemm_tn(xT, a.t, out, nullptr, N, M, K, ldx, a.ldt, ldc, 2, c.ksplit, 1.f, c.s)
+               : kl_launch_gemm_tn(a.t, xT, out, nullptr, M, N, K, a.ldt, ldx, ldc, 2, c.ksplit, 1.f, c.s);
+}
 
-  // F5/F6: logits over the (masked) top-layer outputs, softmax, CE, dlogits
-  const bool top_masked = masks != nullptr && L > 1;
-  const bf16_t* Htop = top_masked ? w.Hd[L - 1] : (const bf16_t*)w.H[L - 1] + BW;
+// the one-hot matrix [rows][BTp] of variable `var` of src's n_vars: dense where that applies, else zero + scatter; its product's sums [4W][rows] zeroed
+static int onehot(const TrainCall& c, const int32_t* src, int classes, int rows, int var, int n_vars, bf16_t* out, float* sums) {
+  if (kl_launch_onehot_dense(src, c.B, c.T, rows, var, n_vars, out, c.BTp, c.s) == KL_ERR_SHAPE) {
+    KL_TRY(kl_zero_async(out, (size_t)rows * c.BTp * sizeof(bf16_t), c.s));
+    KL_TRY(kl_launch_onehot_t(src, c.B, c.T, classes, var, n_vars, out, c.BTp, c.s));
+  }
+  return kl_zero_async(sums, (size_t)4 * c.W * rows * sizeof(float), c.s);
+}
+
+// F5/F6 + B1, the output layer: logits over the (masked) top-layer outputs, softmax, CE, dlogits; dH = dlogits . E; dE += dlogits^T . Htop
+static int train_output_layer(const TrainCall& c) {
+  kl_handle* h = c.h; WindowWs& w = c.w; const Derived& d = h->d; hipStream_t s = c.s;
+  const int B = c.B, T = c.T, W = c.W, V = c.V, Vp = c.Vp, BT = c.BT, BTp = c.BTp;
+  const RowsOperand top = layer_out(c, c.L - 1);
   // (one kernel where it applies -- V = 256, width 512: the logits never reach memory --, else GEMM + softmax)
-  const int mean_rows = (h->loss_rows > 0 && h->loss_rows <= B) ? h->loss_rows : B;      // (a padded batch: the real streams)
-  const float inv_count = 1.0f / (h->last_only ? (float)mean_rows : (float)mean_rows * (float)T);
   int fe = KL_ERR_SHAPE;
-  if (h->logits_ws && loss_acc != nullptr && w.rowstat != nullptr && V == Vp)
-    fe = kl_launch_logits_ce_ws(Htop, d.E_hi, tgt, w.dlogits, w.rowstat, B, T, W, V, Vp, inv_count, h->last_only, s);
+  if (h->logits_ws && c.loss_acc != nullptr && w.rowstat != nullptr && V == Vp)
+    fe = kl_launch_logits_ce_ws(top.km, d.E_hi, c.tgt, w.dlogits, w.rowstat, B, T, W, V, Vp, c.inv_count, h->last_only, s);
   // (width 128: ... and dH = dlogits . E in the same pass -- lstm_scan_w128.hip; the scans there take dH as f32 rows)
   bool dh_done = false;
-  if (fe == KL_ERR_SHAPE && h->logits_ws && W == 128 && loss_acc != nullptr && w.rowstat != nullptr && !w.scan2_bwd) {
-    fe = kl_launch_logits_ce_w128(Htop, d.E_hi, d.ET, tgt, w.dlogits, w.dH, w.rowstat, B, T, W, V, Vp, inv_count, h->last_only, s);
+  if (fe == KL_ERR_SHAPE && h->logits_ws && W == 128 && c.loss_acc != nullptr && w.rowstat != nullptr && !w.scan2_bwd) {
+    fe = kl_launch_logits_ce_w128(top.km, d.E_hi, d.ET, c.tgt, w.dlogits, w.dH, w.rowstat, B, T, W, V, Vp, c.inv_count, h->last_only, s);
     dh_done = fe == 0;
   }
-  if (fe == 0) {
-    KL_TRY(kl_launch_rowstat_reduce(w.rowstat, BT, loss_acc, s));
-  } else if (fe == KL_ERR_SHAPE) {
-    KL_TRY(kl_launch_gemm_tn(Htop, d.E_hi, w.logits, nullptr, BT, V, W, W, W, V, 0, 1, 1.f, s));
-    KL_TRY(kl_launch_softmax_ce(w.logits, V, BT, V, tgt, B, T, inv_count, w.dlogits, Vp, loss_acc, w.rowstat, 1, s, h->last_only));
-  } else {
-    return fe;
+  if (fe != 0 && fe != KL_ERR_SHAPE) return fe;
+  if (fe == 0) KL_TRY(kl_launch_rowstat_reduce(w.rowstat, BT, c.loss_acc, s));
+  else {
+    KL_TRY(kl_launch_gemm_tn(top.km, d.E_hi, w.logits, nullptr, BT, V, W, W, W, V, 0, 1, 1.f, s));
+    KL_TRY(kl_launch_softmax_ce(w.logits, V, BT, V, c.tgt, B, T, c.inv_count, w.dlogits, Vp, c.loss_acc, w.rowstat, 1, s, h->last_only));
   }
   // B1: dH = dlogits . E ; dE += dlogits^T . Htop
-  // (second-generation backward scan: dH travels as bf16)
-  const int dh_mode = w.scan2_bwd ? 1 : 0;
   int de = KL_ERR_SHAPE;
-  if (dh_mode == 1 && h->logits_ws) de = kl_launch_dh_ws(w.dlogits, d.ET, reinterpret_cast<bf16_t*>(w.dH), BT, W, Vp, s);
+  if (c.dh_mode == 1 && h->logits_ws) de = kl_launch_dh_ws(w.dlogits, d.ET, reinterpret_cast<bf16_t*>(w.dH), BT, W, Vp, s);
   if (dh_done) de = 0;
-  if (de == KL_ERR_SHAPE) de = kl_launch_gemm_tn(w.dlogits, d.ET, w.dH, nullptr, BT, W, Vp, Vp, Vp, W, dh_mode, 1, 1.f, s);
+  if (de == KL_ERR_SHAPE) de = kl_launch_gemm_tn(w.dlogits, d.ET, w.dH, nullptr, BT, W, Vp, Vp, Vp, W, c.dh_mode, 1, 1.f, s);
   KL_TRY(de);
   if (BTp != BT) {
     KL_TRY(kl_zero_async(w.dlogitsT, (size_t)Vp * BTp * sizeof(bf16_t), s));
     KL_TRY(kl_zero_async(w.HT, (size_t)W * BTp * sizeof(bf16_t), s));
     KL_TRY(kl_zero_async(w.dZT, (size_t)4 * W * BTp * sizeof(bf16_t), s));
   }
-  const long ldtf = (long)(T + 1) * B;
+  // (dE with both operands as they lie in memory: the window's plan, and the vocabulary unpadded)
   const bool km_e = w.km_plan && Vp == V && kl_gemm_an_applicable(V, W, BT, Vp);
   if (!km_e) KL_TRY(kl_launch_transpose_bf16(w.dlogits, Vp, w.dlogitsT, BTp, BT, Vp, s));
-  if (km_e) {
-    // dE += dlogits^T . Htop with both operands as they lie in memory
-    KL_TRY(kl_launch_gemm_an(w.dlogits, Htop, grads + h->off_E, V, W, BT, Vp, W, W, 0, s, 1));
-  } else if (w.ht_ready) {
-    const bf16_t* HtopT = top_masked ? w.HdT[L - 1] : w.HTf[L - 1] + B;
-    KL_TRY(kl_launch_gemm_tn(w.dlogitsT, HtopT, grads + h->off_E, nullptr, V, W, BT, BTp, top_masked ? (long)BT : ldtf, W, 2, ksplit, 1.f, s));
-  } else {
-    KL_TRY(kl_launch_transpose_bf16(Htop, W, w.HT, BTp, BT, W, s));
-    KL_TRY(kl_launch_gemm_tn(w.dlogitsT, w.HT, grads + h->off_E, nullptr, V, W, BTp, BTp, BTp, W, 2, ksplit, 1.f, s));
-  }
+  return rows_product(c, km_e, {w.dlogits, Vp, w.dlogitsT, BTp}, V, top, W, c.grads + h->off_E, W, false);
+}
 
-  // B3: reverse recurrence -- persistent scan where the shape allows it, else the
-  // launch-per-step layer wavefront
-  std::vector<char> wg_done(L, 0);
-  // (what kl_test_window_view says about this stage: noted by weight_grads as it chooses)
-  unsigned wg_route = 0, wg_pair_mask = 0, wg_db_scan_mask = 0;
-  // B4/B5: weight gradients of one layer, K = B*T contractions over transposed activations
-  // dz_km: the contractions over the T*B rows read dZ and the activations K-major, as the scans wrote them
-  // (kl_launch_gemm_an, the hardware transpose read) -- no transposed copies at all
-  auto weight_grads = [&](int l, bool dzt_ready, bool db_done, bool dz_km) -> int {
-    if (!dzt_ready && !dz_km) KL_TRY(kl_launch_transpose_bf16(w.dZ[l], 4 * W, w.dZT, BTp, BT, 4 * W, s));
-    // dU_l = Hprev^T . dZ   (Hprev = H blocks 0..T-1)
-    // (dz_km: every product over the layer's dZ rows in as few passes over them as possible -- KlGemmSecond, gemm.hip)
-    // (a pair has twice the column tiles of a single product; where the launcher does not take it -- KL_ERR_SHAPE -- the
-    //  products go out one by one, as km_plan has checked they can)
-    bool pair_uk = dz_km && l > 0 && h->fuse_wg && (W % 128) == 0 && kl_gemm_an_applicable(4 * W, 2 * W, BT, 4 * W);
-    if (pair_uk) {
-      const bool masked_in = masks != nullptr && (l - 1) > 0;
-      const bf16_t* X = masked_in ? w.Hd[l - 1] : (const bf16_t*)w.H[l - 1] + BW;
-      const int pe = kl_launch_gemm_an2(w.dZ[l], (const bf16_t*)w.H[l], grads + h->off_U[l], 4 * W, W, BT, 4 * W, W, 4 * W, 1,
-                                        X, grads + h->off_K[l], W, W, 4 * W, 1, s, 1);
-      if (pe == KL_ERR_SHAPE) pair_uk = false;
+// B5, layer 0 through the look-up tables: dEK^T = dZ_0^T . OneHot ; dCtxK_n^T likewise; from them dK_0, dE and the context tables
+static int table_grads(const TrainCall& c) {
+  kl_handle* h = c.h; WindowWs& w = c.w; const kl_config& cf = h->cfg; const Derived& d = h->d; hipStream_t s = c.s;
+  const int B = c.B, T = c.T, W = c.W, V = c.V, Vp = c.Vp, BT = c.BT, BTp = c.BTp;
+  const bool km = w.km_plan, seg = w.segsum;
+  const RowsOperand dz = {w.dZ[0], 4 * W, w.dZT, BTp};
+  // (segment sums: the characters' and the first context variable's sums from ONE read of dZ's rows in key order, no
+  //  one-hot matrices and no multiplications -- the tables come out row-major, dEK [Vp][4W] and dCtxK_0 [ctx_vocab][4W])
+  bool pair_ctx = false;
+  if (seg) {
+    KL_TRY(kl_launch_segment_sums(w.dZ[0], 4 * W, B, T, 4 * W, c.idx, c.ctx, cf.n_ctx, Vp, cf.ctx_vocab, w.dEKT,
+                                  cf.n_ctx > 0 ? w.dCtxKT[0] : nullptr, w.seg_ws, s));
+    KL_TRY(kl_launch_f32_to_bf16_t(w.dEKT, 4 * W, Vp, 4 * W, w.dEKT_bf, nullptr, Vp, 1, s));
+    KL_TRY(kl_launch_f32_to_bf16_t(w.dEKT, 4 * W, Vp, 4 * W, w.dEK_bf, nullptr, 4 * W, 0, s));
+  } else {
+    KL_TRY(onehot(c, c.idx, V, Vp, 0, 1, w.OHT, w.dEKT));
+    // (the first context variable's one-hot product rides along with the characters': one pass over dZ for both)
+    pair_ctx = km && h->fuse_wg && cf.n_ctx >= 1 && (Vp % 128) == 0 && kl_gemm_an_applicable(4 * W, Vp + cf.ctx_vocab, BT, 4 * W);
+    if (pair_ctx) {
+      KL_TRY(onehot(c, c.ctx, cf.ctx_vocab, cf.ctx_vocab, 0, cf.n_ctx, w.OHC[0], w.dCtxKT[0]));
+      const int pe = kl_launch_gemm_an2(w.dZ[0], w.OHT, w.dEKT, 4 * W, Vp, BT, 4 * W, BTp, Vp, 0,
+                                        w.OHC[0], w.dCtxKT[0], cf.ctx_vocab, BTp, cf.ctx_vocab, 0, s, 0);
+      if (pe == KL_ERR_SHAPE) pair_ctx = false;      // (nothing was launched: both products follow one by one)
       else KL_TRY(pe);
     }
-    wg_route |= dz_km ? KL_WG_KMAJOR : (w.ht_ready ? KL_WG_SCAN_T : KL_WG_TRANSPOSE);
-    if (pair_uk) wg_pair_mask |= 1u << l;
-    if (db_done) wg_db_scan_mask |= 1u << l;
-    if (pair_uk) {
-      // (dU and dK done in one pass)
-    } else if (dz_km) {
-      KL_TRY(kl_launch_gemm_an(w.dZ[l], (const bf16_t*)w.H[l], grads + h->off_U[l], 4 * W, W, BT, 4 * W, W, 4 * W, 1, s, 1));
-    } else if (w.ht_ready) {
-      KL_TRY(kl_launch_gemm_tn(w.HTf[l], w.dZT, grads + h->off_U[l], nullptr, W, 4 * W, BT, ldtf, BTp, 4 * W, 2, ksplit, 1.f, s));
-    } else {
-      KL_TRY(kl_launch_transpose_bf16((const bf16_t*)w.H[l], W, w.HT, BTp, BT, W, s));
-      KL_TRY(kl_launch_gemm_tn(w.HT, w.dZT, grads + h->off_U[l], nullptr, W, 4 * W, BTp, BTp, BTp, 4 * W, 2, ksplit, 1.f, s));
+    // (a one-hot matrix only has the transposed form: K-major dZ against it, or dZ^T)
+    if (!pair_ctx) KL_TRY(rows_product(c, km, dz, 4 * W, {nullptr, 0, w.OHT, BTp}, Vp, w.dEKT, Vp, false));
+    KL_TRY(kl_launch_f32_to_bf16_t(w.dEKT, Vp, 4 * W, Vp, w.dEKT_bf, nullptr, Vp, 0, s));
+    KL_TRY(kl_launch_f32_to_bf16_t(w.dEKT, Vp, 4 * W, Vp, w.dEK_bf, nullptr, 4 * W, 1, s));
+  }
+  c.note.wg_route |= (seg ? KL_WG_SEGSUM : 0) | (pair_ctx ? KL_WG_PAIR_CTX : 0);
+  // dK0[:W] = E^T . dEK      (C[W][4W] = ET[W][Vp] . dEKT[4W][Vp]^T)
+  KL_TRY(kl_launch_gemm_tn(d.ET, w.dEKT_bf, c.grads + h->off_K[0], nullptr, W, 4 * W, Vp, Vp, Vp, 4 * W, 0, 1, 1.f, s));
+  // dE += dEK . K0[:W]^T     (C[V][W] = dEK[V][4W] . Kn0[W][4W]^T)
+  KL_TRY(kl_launch_gemm_tn(w.dEK_bf, d.Kn[0], c.grads + h->off_E, nullptr, V, W, 4 * W, 4 * W, 4 * W, W, 2, 1, 1.f, s));
+  for (int n = 0; n < cf.n_ctx; ++n) {
+    const bool seg_n = seg && n == 0;      // (its sums are there already, row-major)
+    if (!(pair_ctx && n == 0) && !seg_n) {
+      KL_TRY(onehot(c, c.ctx, cf.ctx_vocab, cf.ctx_vocab, n, cf.n_ctx, w.OHC[n], w.dCtxKT[n]));
+      KL_TRY(rows_product(c, km, dz, 4 * W, {nullptr, 0, w.OHC[n], BTp}, cf.ctx_vocab, w.dCtxKT[n], cf.ctx_vocab, false));
     }
-    if (!db_done) KL_TRY(kl_launch_colsum_bf16(w.dZ[l], 4 * W, BT, 4 * W, grads + h->off_b[l], s));   // (the wide backward scan sums db itself)
-    if (l > 0) {
-      // dK_l = X^T . dZ with X = (masked) outputs of layer l-1
-      const bool masked_in = masks != nullptr && (l - 1) > 0;
-      const bf16_t* X = masked_in ? w.Hd[l - 1] : (const bf16_t*)w.H[l - 1] + BW;
-      if (pair_uk) {
-        // (done with dU above)
-      } else if (dz_km) {
-        KL_TRY(kl_launch_gemm_an(w.dZ[l], X, grads + h->off_K[l], 4 * W, W, BT, 4 * W, W, 4 * W, 1, s, 1));
-      } else if (w.ht_ready) {
-        const bf16_t* XT = masked_in ? w.HdT[l - 1] : w.HTf[l - 1] + B;
-        KL_TRY(kl_launch_gemm_tn(XT, w.dZT, grads + h->off_K[l], nullptr, W, 4 * W, BT, masked_in ? (long)BT : ldtf, BTp, 4 * W, 2, ksplit, 1.f, s));
-      } else {
-        KL_TRY(kl_launch_transpose_bf16(X, W, w.HT, BTp, BT, W, s));
-        KL_TRY(kl_launch_gemm_tn(w.HT, w.dZT, grads + h->off_K[l], nullptr, W, 4 * W, BTp, BTp, BTp, 4 * W, 2, ksplit, 1.f, s));
-      }
-    } else {
-      // layer 0 through the look-up tables: dEK^T = dZ^T . OneHot ; dCtxK_n^T likewise
-      // (segment sums: the characters' and the first context variable's sums from ONE read of dZ's rows in key order, no
-      //  one-hot matrices and no multiplications -- the tables come out row-major, dEK [Vp][4W] and dCtxK_0 [ctx_vocab][4W])
-      const bool seg = w.segsum;
-      bool pair_ctx = false;
-      if (seg) {
-        KL_TRY(kl_launch_segment_sums(w.dZ[l], 4 * W, B, T, 4 * W, idx, ctx, c.n_ctx, Vp, c.ctx_vocab, w.dEKT,
-                                      c.n_ctx > 0 ? w.dCtxKT[0] : nullptr, w.seg_ws, s));
-        KL_TRY(kl_launch_f32_to_bf16_t(w.dEKT, 4 * W, Vp, 4 * W, w.dEKT_bf, nullptr, Vp, 1, s));
-        KL_TRY(kl_launch_f32_to_bf16_t(w.dEKT, 4 * W, Vp, 4 * W, w.dEK_bf, nullptr, 4 * W, 0, s));
-      } else {
-      if (kl_launch_onehot_dense(idx, B, T, Vp, 0, 1, w.OHT, BTp, s) == KL_ERR_SHAPE) {
-        KL_TRY(kl_zero_async(w.OHT, (size_t)Vp * BTp * sizeof(bf16_t), s));
-        KL_TRY(kl_launch_onehot_t(idx, B, T, V, 0, 1, w.OHT, BTp, s));
-      }
-      KL_TRY(kl_zero_async(w.dEKT, (size_t)4 * W * Vp * sizeof(float), s));
-      // (the first context variable's one-hot product rides along with the characters': one pass over dZ for both)
-      pair_ctx = dz_km && h->fuse_wg && c.n_ctx >= 1 && (Vp % 128) == 0 &&
-                 kl_gemm_an_applicable(4 * W, Vp + c.ctx_vocab, BT, 4 * W);
-      if (pair_ctx) {
-        if (kl_launch_onehot_dense(ctx, B, T, c.ctx_vocab, 0, c.n_ctx, w.OHC[0], BTp, s) == KL_ERR_SHAPE) {
-          KL_TRY(kl_zero_async(w.OHC[0], (size_t)c.ctx_vocab * BTp * sizeof(bf16_t), s));
-          KL_TRY(kl_launch_onehot_t(ctx, B, T, c.ctx_vocab, 0, c.n_ctx, w.OHC[0], BTp, s));
-        }
-        KL_TRY(kl_zero_async(w.dCtxKT[0], (size_t)4 * W * c.ctx_vocab * sizeof(float), s));
-        const int pe = kl_launch_gemm_an2(w.dZ[l], w.OHT, w.dEKT, 4 * W, Vp, BT, 4 * W, BTp, Vp, 0,
-                                          w.OHC[0], w.dCtxKT[0], c.ctx_vocab, BTp, c.ctx_vocab, 0, s, 0);
-        if (pe == KL_ERR_SHAPE) pair_ctx = false;      // (nothing was launched: both products follow one by one)
-        else KL_TRY(pe);
-      }
-      if (pair_ctx) {
-        // (characters and first context variable done in one pass)
-      } else if (dz_km) KL_TRY(kl_launch_gemm_an(w.dZ[l], w.OHT, w.dEKT, 4 * W, Vp, BT, 4 * W, BTp, Vp, 0, s));
-      else KL_TRY(kl_launch_gemm_tn(w.dZT, w.OHT, w.dEKT, nullptr, 4 * W, Vp, BTp, BTp, BTp, Vp, 2, ksplit, 1.f, s));
-      KL_TRY(kl_launch_f32_to_bf16_t(w.dEKT, Vp, 4 * W, Vp, w.dEKT_bf, nullptr, Vp, 0, s));
-      KL_TRY(kl_launch_f32_to_bf16_t(w.dEKT, Vp, 4 * W, Vp, w.dEK_bf, nullptr, 4 * W, 1, s));
-      }
-      if (seg) wg_route |= KL_WG_SEGSUM;
-      if (pair_ctx) wg_route |= KL_WG_PAIR_CTX;
-      // dK0[:W] = E^T . dEK      (C[W][4W] = ET[W][Vp] . dEKT[4W][Vp]^T)
-      KL_TRY(kl_launch_gemm_tn(d.ET, w.dEKT_bf, grads + h->off_K[0], nullptr, W, 4 * W, Vp, Vp, Vp, 4 * W, 0, 1, 1.f, s));
-      // dE += dEK . K0[:W]^T     (C[V][W] = dEK[V][4W] . Kn0[W][4W]^T)
-      KL_TRY(kl_launch_gemm_tn(w.dEK_bf, d.Kn[0], grads + h->off_E, nullptr, V, W, 4 * W, 4 * W, 4 * W, W, 2, 1, 1.f, s));
-      for (int n = 0; n < c.n_ctx; ++n) {
-        const bool seg_n = seg && n == 0;      // (its sums are there already, row-major)
-        if (!(pair_ctx && n == 0) && !seg_n) {
-          if (kl_launch_onehot_dense(ctx, B, T, c.ctx_vocab, n, c.n_ctx, w.OHC[n], BTp, s) == KL_ERR_SHAPE) {
-            KL_TRY(kl_zero_async(w.OHC[n], (size_t)c.ctx_vocab * BTp * sizeof(bf16_t), s));
-            KL_TRY(kl_launch_onehot_t(ctx, B, T, c.ctx_vocab, n, c.n_ctx, w.OHC[n], BTp, s));
-          }
-          KL_TRY(kl_zero_async(w.dCtxKT[n], (size_t)4 * W * c.ctx_vocab * sizeof(float), s));
-          if (dz_km) KL_TRY(kl_launch_gemm_an(w.dZ[l], w.OHC[n], w.dCtxKT[n], 4 * W, c.ctx_vocab, BT, 4 * W, BTp, c.ctx_vocab, 0, s));
-          else KL_TRY(kl_launch_gemm_tn(w.dZT, w.OHC[n], w.dCtxKT[n], nullptr, 4 * W, c.ctx_vocab, BTp, BTp, BTp,
-                                        c.ctx_vocab, 2, ksplit, 1.f, s));
-        }
-        const size_t krow = (size_t)(W + n * c.ctx_dim) * 4 * W;
-        KL_TRY(kl_launch_ctx_grads(P + h->off_Ctx[n], P + h->off_K[0] + krow, 4 * W, c.ctx_vocab, c.ctx_dim,
-                                   w.dCtxKT[n], seg_n ? 1 : c.ctx_vocab, 4 * W, grads + h->off_K[0] + krow, 4 * W,
-                                   grads + h->off_Ctx[n], s, seg_n ? 4 * W : 1));
-      }
+    const size_t krow = (size_t)(W + n * cf.ctx_dim) * 4 * W;
+    KL_TRY(kl_launch_ctx_grads(h->params + h->off_Ctx[n], h->params + h->off_K[0] + krow, 4 * W, cf.ctx_vocab, cf.ctx_dim,
+                               w.dCtxKT[n], seg_n ? 1 : cf.ctx_vocab, 4 * W, c.grads + h->off_K[0] + krow, 4 * W,
+                               c.grads + h->off_Ctx[n], s, seg_n ? 4 * W : 1));
+  }
+  return 0;
+}
+
+// B4/B5: weight gradients of layer l, contractions over the B*T rows of its dZ (rows_product: K-major where the window's plan
+// says so, w.km_plan).  dzt_ready: the scan wrote dZ^T; db_done: ... and summed db
+static int weight_grads(const TrainCall& c, int l, bool dzt_ready, bool db_done) {
+  kl_handle* h = c.h; WindowWs& w = c.w; hipStream_t s = c.s;
+  const int W = c.W, BT = c.BT; const bool km = w.km_plan;
+  if (!dzt_ready && !km) KL_TRY(kl_launch_transpose_bf16(w.dZ[l], 4 * W, w.dZT, c.BTp, BT, 4 * W, s));
+  // dU_l = Hprev^T . dZ   (Hprev = H blocks 0..T-1); dK_l = X^T . dZ with X = (masked) outputs of layer l-1
+  const RowsOperand dz = {w.dZ[l], 4 * W, w.dZT, c.BTp}, Hprev = {(const bf16_t*)w.H[l], W, w.ht_ready ? w.HTf[l] : nullptr, c.ldtf};
+  // (K-major: every product over the layer's dZ rows in as few passes over them as possible -- KlGemmSecond, gemm.hip)
+  // (a pair has twice the column tiles of a single product; where the launcher does not take it -- KL_ERR_SHAPE -- the
+  //  products go out one by one, as km_plan has checked they can)
+  bool pair_uk = km && l > 0 && h->fuse_wg && (W % 128) == 0 && kl_gemm_an_applicable(4 * W, 2 * W, BT, 4 * W);
+  if (pair_uk) {
+    const int pe = kl_launch_gemm_an2(w.dZ[l], Hprev.km, c.grads + h->off_U[l], 4 * W, W, BT, 4 * W, W, 4 * W, 1,
+                                      layer_out(c, l - 1).km, c.grads + h->off_K[l], W, W, 4 * W, 1, s, 1);
+    if (pe == KL_ERR_SHAPE) pair_uk = false;      // (nothing was launched)
+    else KL_TRY(pe);
+  }
+  c.note.wg_route |= km ? KL_WG_KMAJOR : (w.ht_ready ? KL_WG_SCAN_T : KL_WG_TRANSPOSE);
+  if (pair_uk) c.note.wg_pair_mask |= 1u << l;
+  if (db_done) c.note.wg_db_scan_mask |= 1u << l;
+  if (!pair_uk) KL_TRY(rows_product(c, km, dz, 4 * W, Hprev, W, c.grads + h->off_U[l], 4 * W, true));
+  if (!db_done) KL_TRY(kl_launch_colsum_bf16(w.dZ[l], 4 * W, BT, 4 * W, c.grads + h->off_b[l], s));   // (the wide backward scan sums db itself)
+  if (l == 0) return table_grads(c);
+  if (!pair_uk) KL_TRY(rows_product(c, km, dz, 4 * W, layer_out(c, l - 1), W, c.grads + h->off_K[l], 4 * W, true));
+  return 0;
+}
+
+// what all backward scans are told alike, for layers [first, first + n) as the scan's 0 .. n - 1 (the callers add Kn, hand-off and bias sums)
+static KlScanBwd bwd_scan_args(const TrainCall& c, int first, int n) {
+  const Derived& d = c.h->d;
+  KlScanBwd a;
+  memset(&a, 0, sizeof(a));
+  a.B = c.B; a.T = c.T; a.W = c.W; a.L = n;
+  for (int j = 0; j < n; ++j) {
+    const int l = first + j;
+    a.Un[j] = d.Un[l]; a.G[j] = c.w.G[l]; a.C[j] = c.w.C[l]; a.dZ[j] = c.w.dZ[l];
+    a.mask[j] = (c.masks != nullptr && l > 0) ? c.masks + (size_t)l * c.BW : nullptr;
+  }
+  a.dH = c.w.dH; a.status = c.w.scan_status + 1;
+  return a;
+}
+
+// What layer l's scan hands over from: the dZ rows it is going to publish as sentinels -- all steps, or only the last two (rolling: the
+// scan re-arms step t - 2 while it publishes step t) -- or, for a scan that counts, one layer's counters at zero
+enum ArmMode { ARM_ROLLING, ARM_ALL_STEPS, ARM_COUNTERS };
+static int arm_dz(const TrainCall& c, int l, ArmMode mode) {
+  const size_t T = c.T, BW = c.BW;
+  if (mode == ARM_COUNTERS) return kl_zero_coherent_async(c.w.scan_cnt, (size_t)((c.B + 15) / 16) * T, c.s);
+  const size_t first = mode == ARM_ROLLING ? (T - 2) * BW * 4 : 0, steps = mode == ARM_ROLLING ? 2 : T;
+  return kl_fill_u32_async(c.w.dZ[l] + first, steps * BW * 4 * sizeof(bf16_t), 0xFFFFFFFFu, c.s);
+}
+
+// a whole-window backward scan went out: what the per-launch timing reports about it
+static void trace_bwd_scan(const TrainCall& c, const char* kernel, double flops) {
+  c.h->trace_persistent[1] = true; c.h->trace_name[1] = kernel; c.h->trace_flops[1] = flops;
+  c.h->trace_end(1, c.s);
+}
+
+// Width 128, all layers' workgroups fitting the CUs at once: ONE launch, a layer following the one above it a step behind (it
+// polls the dZ rows that one publishes, which therefore start out as sentinels), then every layer's weight gradients.
+static int bwd_w128_multi(const TrainCall& c) {
+  kl_handle* h = c.h;
+  const int B = c.B, T = c.T, W = c.W, L = c.L;
+  if (!(c.seq128 && h->w128_fuse && h->w128_multi && kl_scan_w128_multi_fits(B, L))) return TRAIN_PASS;
+  KlScanBwd a = bwd_scan_args(c, 0, L);
+  for (int l = 0; l < L; ++l) { a.Kn[l] = h->d.Kn[l]; a.db_l[l] = c.grads + h->off_b[l]; }
+  const bool roll = h->sentinel_roll && T >= 3;      // (rolling sentinels: only the last two steps start out armed)
+  a.sentinel = roll ? 2 : 1;
+  for (int l = 1; l < L; ++l) KL_TRY(arm_dz(c, l, roll ? ARM_ROLLING : ARM_ALL_STEPS));
+  h->trace_begin(1, c.s);
+  const int e = kl_launch_scan_bwd_w128_multi(a, c.s);
+  if (e != 0) return e == KL_ERR_SHAPE ? TRAIN_PASS : e;
+  trace_bwd_scan(c, "lstm_scan_bwd_w128_multi_kernel", (double)(2 * L - 1) * B * T * (2.0 * W * 4.0 * W));      // (recurrent contractions + the from-above ones)
+  for (int l = L - 1; l >= 0; --l) KL_TRY(weight_grads(c, l, false, true));
+  return 0;
+}
+
+enum BwdKernel { BWD_REGTILE, BWD_WIDE2, BWD_WIDE, BWD_W128, BWD_W32, BWD_THIN };
+static const char* const BWD_KERNEL_NAME[] = {"lstm_scan_bwd_regtile_kernel", "lstm_scan_bwd_wide2_kernel", "lstm_scan_bwd_wide_kernel",
+                                              "lstm_scan_bwd_w128_kernel",    "lstm_scan_bwd_w32_kernel",   "lstm_scan_bwd_kernel"};
+
+// one layer's scan on the first kernel that takes it (*ran), `a` adjusted to what that kernel is told: register-tile or wide2, else wide, w128, w32, thin
+static int launch_layer_scan(const TrainCall& c, int l, KlScanBwd& a, bool rt, bool fuse_dx, BwdKernel* ran) {
+  kl_handle* h = c.h; WindowWs& w = c.w; hipStream_t s = c.s;
+  if (w.scan2_bwd) {
+    *ran = rt ? BWD_REGTILE : BWD_WIDE2;
+    return rt ? kl_launch_scan_bwd_regtile(a, s) : kl_launch_scan_bwd_wide2(a, s);      // (KL_ERR_SHAPE: an error, planned together -- plan_scan2)
+  }
+  *ran = BWD_WIDE;
+  int e = h->wide_bwd ? kl_launch_scan_bwd_wide(a, s) : KL_ERR_SHAPE;
+  if (e == KL_ERR_SHAPE && c.seq128) {
+    KlScanBwd a1 = a;
+    a1.dZT = nullptr; a1.sentinel = 0;
+    if (fuse_dx) { a1.Kn[1] = h->d.Kn[l + 1]; a1.dZ[1] = w.dZ[l + 1]; }
+    *ran = BWD_W128; e = kl_launch_scan_bwd_w128(a1, s);
+    if (e == KL_ERR_SHAPE && fuse_dx) return KL_ERR_SHAPE;      // (the dX product was skipped for it)
+    if (e == 0) a.dZT = nullptr;
+  }
+  if (e == KL_ERR_SHAPE && h->w32 && (c.B + 15) / 16 >= h->w32_min_rb && kl_scan_w32_applicable(c.B, c.T, c.W)) {
+    // width 1024: eight-wave workgroups of 32 units (lstm_scan_w32.hip); every step starts out as sentinels
+    if (a.sentinel != 1) KL_TRY(arm_dz(c, l, ARM_ALL_STEPS));
+    a.sentinel = 1; a.dZT = nullptr;
+    a.xcc_slots = h->w32_local ? w.scan_status + 4 : nullptr;
+    *ran = BWD_W32; e = kl_launch_scan_bwd_w32(a, s);
+  }
+  if (e == KL_ERR_SHAPE) {
+    a.dZT = nullptr; a.db = nullptr;
+    if (a.sentinel) KL_TRY(arm_dz(c, l, ARM_COUNTERS));   // (the thin scan counts)
+    *ran = BWD_THIN; e = kl_launch_scan_bwd(a, s);
+  }
+  return e;
+}
+
+// Layer by layer, from the top: where the plan says so (many row blocks, width 1024, deeper than the fused scan's four layers, width 128)
+// and always behind second-generation forward scans.  Per layer: the from-above term for all steps, the hand-off armed, the scan, the
+// layer's weight gradients
+static int bwd_layer_by_layer(const TrainCall& c) {
+  kl_handle* h = c.h; WindowWs& w = c.w; const Derived& d = h->d; hipStream_t s = c.s;
+  const int B = c.B, T = c.T, W = c.W, L = c.L, BT = c.BT, BTp = c.BTp;
+  if (!(c.sequential || w.scan2_bwd)) return TRAIN_PASS;
+  for (int l = L - 1; l >= 0; --l) {
+    // (width 128: the scan of lstm_scan_w128.hip contracts the layer above's dZ rows itself)
+    const bool fuse_dx = c.seq128 && h->w128_fuse && l < L - 1;
+    if (l < L - 1 && !fuse_dx)   // dX_l = dZ_{l+1} . K_{l+1}^T  -> w.dH (free once the layer above has been scanned)
+      KL_TRY(kl_launch_gemm_tn(w.dZ[l + 1], d.Kn[l + 1], w.dH, nullptr, BT, W, 4 * W, 4 * W, 4 * W, W, c.dh_mode, 1, 1.f, s));
+    KlScanBwd a = bwd_scan_args(c, l, 1);
+    a.dHb = reinterpret_cast<const bf16_t*>(w.dH); a.counters = w.scan_cnt;
+    a.Cb = (w.scan2_bwd && h->scan2_bf16) ? w.Cb[l] : nullptr;
+    // (sentinels pay with several row blocks per workgroup, where the next tile is prefetched; with one
+    // block the cheap counter poll beats re-fetching 64 KiB tiles; XCD-local publishes measured slower here)
+    a.sentinel = (w.scan2_bwd || (h->sentinel_bwd && c.wide_fits && (kl_scan_wide_blocks_per_wg(B, W) > 1 || h->sentinel_bwd_all))) ? 1 : 0;
+    // (measured at B = 1024 .. 3072: the request behind the MFMA phase is the best or tied everywhere; at the top of the block
+    //  one tile in ten is requested before it is published, and the re-fetch costs more than the earlier request saves)
+    a.pf_mode = h->scan2_pfb >= 0 ? h->scan2_pfb : 1;
+    a.xcc_slots = (a.sentinel && h->xcd_local_bwd) ? w.scan_status + 4 : nullptr;
+    a.gen = (unsigned)(1 + L + l);
+    const int np_b = w.scan2_bwd ? kl_scan_wide2_phases(B, T, W, 16, 6) : 0;
+    const bool by_flags = w.scan2_bwd && h->scan2_flags && h->flags_zeroed && np_b >= 3;
+    // (from five blocks per step: eight waves, the tile through registers two blocks ahead -- lstm_scan_bwd_regtile_kernel)
+    const bool rt = by_flags && h->regtile && h->scan2_bf16 && np_b >= kl_scan_bwd_regtile_min_np();
+    if (by_flags) {
+      // hand-off by flags (lstm_scan_bwd_wide2_kernel): nothing to arm, the epoch moves on
+      a.flags = d.scan_flags; a.epoch = d.scan_flags + KL_SCAN_FLAGS;
+      // (flags tell before the request whether a tile is there, so it can be asked for TWO blocks ahead, behind the epilogue,
+      //  without the re-fetches that cost the sentinel form -- once five or more blocks lie between a publish and its use)
+      if (h->scan2_pfb < 0) a.pf_mode = np_b >= 5 ? 2 : 1;
+      else if (a.pf_mode == 0) a.pf_mode = 1;
+      KL_TRY(kl_launch_scan_epoch(d.scan_flags, KL_SCAN_FLAGS, d.scan_flags + KL_SCAN_FLAGS, (unsigned)T + 2u, s));
+    } else if (a.sentinel && h->sentinel_roll && T >= 3) {
+      a.sentinel = 2;      // rolling sentinels: only the last two steps start armed
+      KL_TRY(arm_dz(c, l, ARM_ROLLING));
+    } else {      // hand-off by data: the steps the scan is going to publish start out as sentinels; else by counters
+      KL_TRY(arm_dz(c, l, a.sentinel ? ARM_ALL_STEPS : ARM_COUNTERS));
     }
-      return 0;
-  };
-  bool bscanned = false;
-  // Many row blocks (B >= 256 at cfg2): the fused two-layer scan is bound by every
-  // workgroup re-reading its 16 x 4W dZ tile for BOTH contractions.  Run the layers one
-  // after the other instead -- each scan then only carries the recurrent contraction and
-  // twice the row groups fit -- and take the from-above term dZ_{l+1} . K_{l+1}^T for all
-  // steps at once from the big GEMM.
-  const int n_rb_all = (B + 15) / 16, nug = W / 16;
-  const bool thin_fits = (n_rb_all + 512 / nug - 1) / (512 / nug) <= (W == 1024 ? 8 : 4) &&
-                         (long)T * B * 4 * W * 2 <= 0xfffffff0L;      // (the scans address dZ with unsigned 32-bit offsets)
-  const bool wide_fits = h->wide_bwd && kl_scan_bwd_wide_applicable(B, T, W) && BTp == BT && (B & 7) == 0;
-  // (width 1024 has no fused scan at all: always layer by layer)
-  // (... and deeper than four layers: the fused scan's limit)
-  // (width 128: the one-layer scans of lstm_scan_w128.hip, a workgroup per 16-row block with all units)
-  const bool seq128 = h->scan_enabled && h->seq_bwd && h->w128 && B >= h->w128_min && kl_scan_w128_applicable(B, T, W) && !w.scan2_bwd;
-  const bool sequential = seq128 || (h->scan_enabled && h->seq_bwd &&
-                          ((L > 1 && L <= KL_SCAN_MAXL && (W == 512 || W == 256 || W == 128) && n_rb_all > 512 / (L * nug)) ||
-                           W == 1024 || (L > KL_SCAN_MAXL && (W == 512 || W == 256 || W == 128 || W == 64))) &&
-                          (thin_fits || wide_fits));
-  // Width 128, all layers' workgroups fitting the CUs at once: ONE launch, a layer following the one above it a step behind (it
-  // polls the dZ rows that one publishes, which therefore start out as sentinels), then every layer's weight gradients.
-  if (seq128 && h->w128_fuse && h->w128_multi && kl_scan_w128_multi_fits(B, L)) {
-    KlScanBwd a;
-    memset(&a, 0, sizeof(a));
-    a.B = B; a.T = T; a.W = W; a.L = L;
-    for (int l = 0; l < L; ++l) {
-      a.Un[l] = d.Un[l];
-      a.Kn[l] = d.Kn[l];
-      a.G[l] = w.G[l];
-      a.C[l] = w.C[l];
-      a.dZ[l] = w.dZ[l];
-      a.mask[l] = (masks != nullptr && l > 0) ? masks + (size_t)l * BW : nullptr;
-      a.db_l[l] = grads + h->off_b[l];
-    }
-    a.dH = w.dH;
-    a.status = w.scan_status + 1;
-    const bool roll = h->sentinel_roll && T >= 3;      // (rolling sentinels: only the last two steps start out armed)
-    a.sentinel = roll ? 2 : 1;
-    for (int l = 1; l < L; ++l)
-      KL_TRY(kl_fill_u32_async(w.dZ[l] + (roll ? (size_t)(T - 2) * BW * 4 : 0), (size_t)(roll ? 2 : T) * BW * 4 * sizeof(bf16_t), 0xFFFFFFFFu, s));
     h->trace_begin(1, s);
-    const int e = kl_launch_scan_bwd_w128_multi(a, s);
-    if (e != KL_ERR_SHAPE) {
-      KL_TRY(e);
-      h->trace_persistent[1] = true;
-      h->trace_name[1] = "lstm_scan_bwd_w128_multi_kernel";
-      h->trace_flops[1] = (double)(2 * L - 1) * B * T * (2.0 * W * 4.0 * W);      // (recurrent contractions + the from-above ones)
-      h->trace_end(1, s);
-      for (int l = L - 1; l >= 0; --l) {
-        KL_TRY(weight_grads(l, false, true, w.km_plan));
-        wg_done[l] = 1;
-      }
-      bscanned = true;
-    }
+    // wide (64-unit) workgroups share the dZ tile through LDS; the weight-gradient GEMMs read dZ K-major
+    // as it is (km_plan), else the scan also writes dZ^T
+    a.dZT = (!w.km_plan && BTp == BT && (B & 7) == 0) ? w.dZT : nullptr;
+    a.ldt = BTp; a.db = c.grads + h->off_b[l];
+    if (rt) a.xcc_slots = h->rt_local ? w.scan_status + 4 : nullptr;
+    BwdKernel ran;
+    KL_TRY(launch_layer_scan(c, l, a, rt, fuse_dx, &ran));
+    trace_bwd_scan(c, BWD_KERNEL_NAME[ran], (double)B * T * (2.0 * W * 4.0 * W));   // one layer's recurrent contraction
+    // dZ^T lives in ONE buffer: this layer's weight gradients before the next layer's scan
+    // (every kernel but the thin one sums db; the wide ones also write dZ^T where a.dZT is left set)
+    KL_TRY(weight_grads(c, l, a.dZT != nullptr, ran != BWD_THIN));
   }
-  if (!bscanned && (sequential || w.scan2_bwd)) {
-    for (int l = L - 1; l >= 0; --l) {
-      // (width 128: the scan of lstm_scan_w128.hip contracts the layer above's dZ rows itself)
-      const bool fuse_dx = seq128 && h->w128_fuse && l < L - 1;
-      if (l < L - 1 && !fuse_dx)   // dX_l = dZ_{l+1} . K_{l+1}^T  -> w.dH (free once the layer above has been scanned)
-        KL_TRY(kl_launch_gemm_tn(w.dZ[l + 1], d.Kn[l + 1], w.dH, nullptr, BT, W, 4 * W, 4 * W, 4 * W, W, dh_mode, 1, 1.f, s));
-      KlScanBwd a;
-      memset(&a, 0, sizeof(a));
-      a.B = B; a.T = T; a.W = W; a.L = 1;
-      a.Un[0] = d.Un[l];
-      a.G[0] = w.G[l];
-      a.C[0] = w.C[l];
-      a.dZ[0] = w.dZ[l];
-      a.mask[0] = (masks != nullptr && l > 0) ? masks + (size_t)l * BW : nullptr;
-      a.dH = w.dH;
-      a.dHb = reinterpret_cast<const bf16_t*>(w.dH);
-      a.Cb = (w.scan2_bwd && h->scan2_bf16) ? w.Cb[l] : nullptr;
-      a.counters = w.scan_cnt;
-      a.status = w.scan_status + 1;
-      // (sentinels pay with several row blocks per workgroup, where the next tile is prefetched; with one
-      // block the cheap counter poll beats re-fetching 64 KiB tiles; XCD-local publishes measured slower here)
-      a.sentinel = (w.scan2_bwd || (h->sentinel_bwd && wide_fits && (kl_scan_wide_blocks_per_wg(B, W) > 1 || h->sentinel_bwd_all))) ? 1 : 0;
-      // (measured at B = 1024 .. 3072: the request behind the MFMA phase is the best or tied everywhere; at the top of the block
-      //  one tile in ten is requested before it is published, and the re-fetch costs more than the earlier request saves)
-      a.pf_mode = h->scan2_pfb >= 0 ? h->scan2_pfb : 1;
-      a.xcc_slots = (a.sentinel && h->xcd_local_bwd) ? w.scan_status + 4 : nullptr;
-      a.gen = (unsigned)(1 + L + l);
-      const int np_b = w.scan2_bwd ? kl_scan_wide2_phases(B, T, W, 16, 6) : 0;
-      const bool by_flags = w.scan2_bwd && h->scan2_flags && h->flags_zeroed && np_b >= 3;
-      // (from five blocks per step: eight waves, the tile through registers two blocks ahead -- lstm_scan_bwd_regtile_kernel)
-      const bool rt = by_flags && h->regtile && h->scan2_bf16 && np_b >= kl_scan_bwd_regtile_min_np();
-      if (by_flags) {
-        // hand-off by flags (lstm_scan_bwd_wide2_kernel): nothing to arm, the epoch moves on
-        a.flags = d.scan_flags;
-        a.epoch = d.scan_flags + KL_SCAN_FLAGS;
-        // (flags tell before the request whether a tile is there, so it can be asked for TWO blocks ahead, behind the epilogue,
-        //  without the re-fetches that cost the sentinel form -- once five or more blocks lie between a publish and its use)
-        if (h->scan2_pfb < 0) a.pf_mode = kl_scan_wide2_phases(B, T, W, 16, 6) >= 5 ? 2 : 1;
-        else if (a.pf_mode == 0) a.pf_mode = 1;
-        KL_TRY(kl_launch_scan_epoch(d.scan_flags, KL_SCAN_FLAGS, d.scan_flags + KL_SCAN_FLAGS, (unsigned)T + 2u, s));
-      } else if (a.sentinel && h->sentinel_roll && T >= 3) {
-        // rolling sentinels: the scan re-arms step t - 2 while it publishes step t; only the first two start armed
-        a.sentinel = 2;
-        KL_TRY(kl_fill_u32_async(w.dZ[l] + (size_t)(T - 2) * BW * 4, (size_t)2 * BW * 4 * sizeof(bf16_t), 0xFFFFFFFFu, s));
-      } else if (a.sentinel)   // hand-off by data: the steps the scan is going to publish start out as sentinels
-        KL_TRY(kl_fill_u32_async(w.dZ[l], (size_t)T * BW * 4 * sizeof(bf16_t), 0xFFFFFFFFu, s));
-      else
-        KL_TRY(kl_zero_coherent_async(w.scan_cnt, (size_t)n_rb_all * T, s));
-      h->trace_begin(1, s);
-      // wide (64-unit) workgroups share the dZ tile through LDS; the weight-gradient GEMMs read dZ K-major
-      // as it is (dz_km), else the scan also writes dZ^T
-      a.dZT = (!w.km_plan && BTp == BT && (B & 7) == 0) ? w.dZT : nullptr;
-      a.ldt = BTp;
-      a.db = grads + h->off_b[l];
-      if (rt) a.xcc_slots = h->rt_local ? w.scan_status + 4 : nullptr;
-      int e = w.scan2_bwd ? (rt ? kl_launch_scan_bwd_regtile(a, s) : kl_launch_scan_bwd_wide2(a, s)) : (h->wide_bwd ? kl_launch_scan_bwd_wide(a, s) : KL_ERR_SHAPE);
-      bool w32 = false, w128k = false;
-      if (e == KL_ERR_SHAPE && seq128) {
-        KlScanBwd a1 = a;
-        a1.dZT = nullptr;
-        a1.sentinel = 0;
-        if (fuse_dx) { a1.Kn[1] = d.Kn[l + 1]; a1.dZ[1] = w.dZ[l + 1]; }
-        e = kl_launch_scan_bwd_w128(a1, s);
-        if (e == KL_ERR_SHAPE && fuse_dx) return KL_ERR_SHAPE;      // (the dX product was skipped for it)
-        w128k = e == 0;
-        if (w128k) a.dZT = nullptr;
-      }
-      if (e == KL_ERR_SHAPE && !w.scan2_bwd && h->w32 && n_rb_all >= h->w32_min_rb && kl_scan_w32_applicable(B, T, W)) {
-        // width 1024: eight-wave workgroups of 32 units (lstm_scan_w32.hip); every step starts out as sentinels
-        if (a.sentinel != 1) KL_TRY(kl_fill_u32_async(w.dZ[l], (size_t)T * BW * 4 * sizeof(bf16_t), 0xFFFFFFFFu, s));
-        a.sentinel = 1;
-        a.dZT = nullptr;
-        a.xcc_slots = h->w32_local ? w.scan_status + 4 : nullptr;
-        a.gen = (unsigned)(1 + L + l);
-        e = kl_launch_scan_bwd_w32(a, s);
-        w32 = e == 0;
-      }
-      const bool wide = e == 0;
-      if (e == KL_ERR_SHAPE && w.scan2_bwd) return KL_ERR_SHAPE;      // (the forward scans wrote gate-interleaved G: planned together, plan_scan2)
-      if (e == KL_ERR_SHAPE) {
-        a.dZT = nullptr;
-        a.db = nullptr;
-        if (a.sentinel) KL_TRY(kl_zero_coherent_async(w.scan_cnt, (size_t)n_rb_all * T, s));   // (the thin scan counts)
-        e = kl_launch_scan_bwd(a, s);
-      }
-      if (e != 0) return e;
-      {
-        h->trace_persistent[1] = true;
-        h->trace_name[1] = w.scan2_bwd ? (rt ? "lstm_scan_bwd_regtile_kernel" : "lstm_scan_bwd_wide2_kernel")
-                                       : (w128k ? "lstm_scan_bwd_w128_kernel" : w32 ? "lstm_scan_bwd_w32_kernel" : (wide ? "lstm_scan_bwd_wide_kernel" : "lstm_scan_bwd_kernel"));
-        h->trace_flops[1] = (double)B * T * (2.0 * W * 4.0 * W);   // one layer's recurrent contraction
-        h->trace_end(1, s);
-      }
-      // dZ^T lives in ONE buffer: this layer's weight gradients before the next layer's scan
-      KL_TRY(weight_grads(l, wide && a.dZT != nullptr, wide, w.km_plan));
-      wg_done[l] = 1;
-    }
-    bscanned = true;
-  }
-  if (!bscanned && h->scan_enabled && L <= KL_SCAN_MAXL) {
-    KlScanBwd a;
-    memset(&a, 0, sizeof(a));
-    a.B = B; a.T = T; a.W = W; a.L = L;
-    for (int l = 0; l < L; ++l) {
-      a.Un[l] = d.Un[l];
-      a.Kn[l] = d.Kn[l];
-      a.G[l] = w.G[l];
-      a.C[l] = w.C[l];
-      a.dZ[l] = w.dZ[l];
-      a.mask[l] = (masks != nullptr && l > 0) ? masks + (size_t)l * BW : nullptr;
-    }
-    a.dH = w.dH;
-    a.counters = w.scan_cnt;
-    a.status = w.scan_status + 1;
-    KL_TRY(kl_zero_coherent_async(w.scan_cnt, (size_t)L * ((B + 15) / 16) * T, s));
-    h->trace_begin(1, s);
-    const int e = kl_launch_scan_bwd(a, s);
-    if (e == 0) {
-      bscanned = true;
-      h->trace_persistent[1] = true;
-      h->trace_name[1] = "lstm_scan_bwd_kernel";
-      h->trace_flops[1] = (double)B * T * (2.0 * (2.0 * L - 1.0) * W * 4.0 * W);
-      h->trace_end(1, s);
-    } else if (e != KL_ERR_SHAPE) {
-      return e;
-    }
-  }
-  for (int dgl = 0; !bscanned && dgl < T + L - 1; ++dgl) {
+  return 0;
+}
+
+// the fused thin scan: all layers (at most KL_SCAN_MAXL) in one launch, hand-off by counters
+static int bwd_fused_thin(const TrainCall& c) {
+  kl_handle* h = c.h;
+  const int B = c.B, T = c.T, W = c.W, L = c.L;
+  if (!(h->scan_enabled && L <= KL_SCAN_MAXL)) return TRAIN_PASS;
+  KlScanBwd a = bwd_scan_args(c, 0, L);
+  a.counters = c.w.scan_cnt;
+  for (int l = 0; l < L; ++l) a.Kn[l] = h->d.Kn[l];
+  KL_TRY(kl_zero_coherent_async(c.w.scan_cnt, (size_t)L * ((B + 15) / 16) * T, c.s));      // (all layers' counters)
+  h->trace_begin(1, c.s);
+  const int e = kl_launch_scan_bwd(a, c.s);
+  if (e != 0) return e == KL_ERR_SHAPE ? TRAIN_PASS : e;
+  trace_bwd_scan(c, "lstm_scan_bwd_kernel", (double)B * T * (2.0 * (2.0 * L - 1.0) * W * 4.0 * W));
+  return 0;
+}
+
+// everything else: the launch-per-step layer wavefront (diagonal dgl: layer l runs step T - 1 - (dgl - (L - 1 - l)))
+static int bwd_wavefront(const TrainCall& c) {
+  kl_handle* h = c.h; WindowWs& w = c.w; const Derived& d = h->d; hipStream_t s = c.s;
+  const int B = c.B, T = c.T, W = c.W, L = c.L;
+  const size_t BW = c.BW; const float* masks = c.masks;
+  for (int dgl = 0; dgl < T + L - 1; ++dgl) {
     KlBwdStep steps[16];     // one per layer (config_ok: depth <= 16); launched in packs of 4 below
     int ns = 0;
     for (int j = 0; j < L; ++j) {
@@ -1677,7 +1631,7 @@ static int train_window_body(kl_handle* h, int B, int T, const int32_t* idx, con
         if (masks != nullptr && l > 0) { S.op0_mask = masks + (size_t)l * BW; S.op0_mask_ld = W; }
       } else {
         S.dh_in = w.dH + (size_t)t * BW; S.dh_in_ld = W;
-        if (top_masked) { S.dh_mask = masks + (size_t)l * BW; S.dh_mask_ld = W; }
+        if (c.top_masked) { S.dh_mask = masks + (size_t)l * BW; S.dh_mask_ld = W; }
       }
       if (t < T - 1) {   // recurrent: dZ_l[t+1] . U_l^T
         KlOperand& o = S.op[p++];
@@ -1703,20 +1657,68 @@ static int train_window_body(kl_handle* h, int B, int T, const int32_t* idx, con
       if (steady && dgl % 8 == 7) h->trace_end(1, s);
     }
   }
+  return 0;
+}
 
-  for (int l = L - 1; l >= 0; --l)
-    if (!wg_done[l]) KL_TRY(weight_grads(l, false, false, w.km_plan));
-  for (auto& n : h->view_notes)
-    if (n.B == B && n.T == T && n.ws == ws) {
-      n.wg_route = wg_route; n.wg_pair_mask = wg_pair_mask; n.wg_db_scan_mask = wg_db_scan_mask;
-      n.hd_mask = masks != nullptr ? ((1u << L) - 1u) & ~1u : 0u;      // (forward_impl: every layer above the first writes Hd)
-    }
-
+static int train_window_body(kl_handle* h, int B, int T, const int32_t* idx, const int32_t* ctx, const int32_t* tgt,
+                    float* states, const float* masks, float* grads, float* loss_acc, void* ws, size_t ws_bytes,
+                    void* stream) {
+  hipStream_t s = (hipStream_t)stream;      // (kl_train_window has checked the arguments)
+  WindowWs w;
+  if (ws_bytes < carve_window(h, ws, B, T, 1, &w)) return KL_ERR_WORKSPACE;
+  const kl_config& cf = h->cfg;
+  const int W = cf.width, V = cf.voc_size, Vp = h->Vp, L = cf.depth;
+  const int BT = B * T, BTp = round_up_i(BT, 8);
+  const float* P = h->params;
+  KL_TRY(kl_zero_async(grads, h->n_params * sizeof(float), s));
+  KL_TRY(kl_zero_async(w.scan_status, (4 + 256) * sizeof(unsigned), s));
+  // (M = 4W rows of dZ as the K-major A operand: W % 64 == 0, T*B % 64 == 0)
+  w.km_plan = h->gemm_an && BTp == BT && kl_gemm_an_applicable(4 * W, W, BT, 4 * W);
+  w.scan2_rows = plan_scan2(h, B, T, w.km_plan, true);
+  w.scan2_bwd = w.scan2_rows != 0;
+  KL_TRY(forward_impl(h, B, T, idx, ctx, states, masks, 1, w, s));
+  // Many row blocks (B >= 256 at cfg2): the fused two-layer scan is bound by every
+  // workgroup re-reading its 16 x 4W dZ tile for BOTH contractions.  Run the layers one
+  // after the other instead -- each scan then only carries the recurrent contraction and
+  // twice the row groups fit -- and take the from-above term dZ_{l+1} . K_{l+1}^T for all
+  // steps at once from the big GEMM.
+  const int n_rb_all = (B + 15) / 16, nug = W / 16;
+  const bool thin_fits = (n_rb_all + 512 / nug - 1) / (512 / nug) <= (W == 1024 ? 8 : 4) &&
+                         (long)T * B * 4 * W * 2 <= 0xfffffff0L;      // (the scans address dZ with unsigned 32-bit offsets)
+  const bool wide_fits = h->wide_bwd && kl_scan_bwd_wide_applicable(B, T, W) && BTp == BT && (B & 7) == 0;
+  // (width 1024 has no fused scan at all: always layer by layer)
+  // (... and deeper than four layers: the fused scan's limit)
+  // (width 128: the one-layer scans of lstm_scan_w128.hip, a workgroup per 16-row block with all units)
+  const bool seq128 = h->scan_enabled && h->seq_bwd && h->w128 && B >= h->w128_min && kl_scan_w128_applicable(B, T, W) && !w.scan2_bwd;
+  const bool sequential = seq128 || (h->scan_enabled && h->seq_bwd &&
+                          ((L > 1 && L <= KL_SCAN_MAXL && (W == 512 || W == 256 || W == 128) && n_rb_all > 512 / (L * nug)) ||
+                           W == 1024 || (L > KL_SCAN_MAXL && (W == 512 || W == 256 || W == 128 || W == 64))) &&
+                          (thin_fits || wide_fits));
+  const int mean_rows = (h->loss_rows > 0 && h->loss_rows <= B) ? h->loss_rows : B;      // (a padded batch: the real streams)
+  const TrainCall c = {h, B, T, idx, ctx, tgt, masks, grads, loss_acc, s, w, *h->view_note(B, T, ws, true), W, V, Vp, L, BT, BTp, (size_t)B * W,
+                       /*ksplit*/ BT >= 4096 ? 8 : (BT >= 1024 ? 4 : 1), /*ldtf*/ (long)(T + 1) * B,
+                       /*dh_mode*/ w.scan2_bwd ? 1 : 0,      // (second-generation backward scan: dH travels as bf16)
+                       /*top_masked*/ masks != nullptr && L > 1,
+                       /*inv_count*/ 1.0f / (h->last_only ? (float)mean_rows : (float)mean_rows * (float)T), wide_fits, seq128, sequential};
+  c.note = kl_handle::ViewNote{B, T, ws, w.scan2_rows, w.scan2_bwd ? 1 : 0, (w.scan2_bwd && h->scan2_bf16) ? 1 : 0, w.scan2_bwd ? 1 : 0,
+                               w.p_bf16_mask};
+  c.note.hd_mask = masks != nullptr ? ((1u << L) - 1u) & ~1u : 0u;      // (forward_impl: every layer above the first writes Hd)
+  KL_TRY(train_output_layer(c));
+  // B3: reverse recurrence -- the first path that takes the window, in this order; the first two issue each layer's weight
+  // gradients themselves (dZ^T lives in one buffer), the other two leave them all to the end
+  int e = bwd_w128_multi(c);
+  if (e == TRAIN_PASS) e = bwd_layer_by_layer(c);
+  if (e == TRAIN_PASS) {
+    e = bwd_fused_thin(c);
+    if (e == TRAIN_PASS) e = bwd_wavefront(c);
+    for (int l = L - 1; l >= 0 && e == 0; --l) e = weight_grads(c, l, false, false);
+  }
+  KL_TRY(e);
   // F7: embedding regularisers (training phase only)
-  std::vector<const float*> ctabs(c.n_ctx);
-  std::vector<float*> gctabs(c.n_ctx);
-  for (int n = 0; n < c.n_ctx; ++n) { ctabs[n] = P + h->off_Ctx[n]; gctabs[n] = grads + h->off_Ctx[n]; }
-  KL_TRY(kl_launch_regulariser_grads(P + h->off_E, V, W, ctabs.data(), c.n_ctx, c.ctx_vocab, c.ctx_dim,
+  std::vector<const float*> ctabs(cf.n_ctx);
+  std::vector<float*> gctabs(cf.n_ctx);
+  for (int n = 0; n < cf.n_ctx; ++n) { ctabs[n] = P + h->off_Ctx[n]; gctabs[n] = grads + h->off_Ctx[n]; }
+  KL_TRY(kl_launch_regulariser_grads(P + h->off_E, V, W, ctabs.data(), cf.n_ctx, cf.ctx_vocab, cf.ctx_dim,
                                      grads + h->off_E, gctabs.data(), loss_acc, w.reg_scratch, s));
   // a timed-out hand-off in a persistent scan surfaces as loss_acc[3] != 0
   hipLaunchKernelGGL(scan_status_kernel, dim3(1), dim3(64), 0, s, w.scan_status, loss_acc);
@@ -2593,9 +2595,7 @@ extern "C" int kl_train_window(kl_handle* h, int B, int T, const int32_t* idx, c
 
 extern "C" int kl_test_window_view(const kl_handle* h, int B, int T, const void* ws, kl_window_view* out) {
   if (!h || !ws || !out || B < 1 || T < 1) return KL_ERR_ARG;
-  const kl_handle::ViewNote* note = nullptr;
-  for (const auto& n : h->view_notes)
-    if (n.B == B && n.T == T && n.ws == ws) note = &n;
+  const kl_handle::ViewNote* note = const_cast<kl_handle*>(h)->view_note(B, T, ws, false);
   if (!note) return KL_ERR_STATE;
   WindowWs w;
   carve_window(h, const_cast<void*>(ws), B, T, 1, &w);
