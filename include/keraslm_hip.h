@@ -391,6 +391,11 @@ int kl_test_logits_ce_ws(const uint16_t* X, const uint16_t* E, const int32_t* tg
 int kl_test_logits_ce_w128(const uint16_t* X, const uint16_t* E, const uint16_t* ET, const int32_t* tgt, uint16_t* dlogits, float* dH,
                            float* rowstat, int B, int T, int V, int Vp, float inv_count, int last_only, void* stream);
 int kl_test_dh_ws(const uint16_t* dlogits, const uint16_t* ET, uint16_t* dH, long M, void* stream);
+/* The embedding regularisers of a training window on caller buffers, one table X f32 [R][D] per call: mode 0 the
+ * characters' rule, mode 1 the context tables'.  gX [R][D] += the gradient, loss_acc[2] += the value (loss_acc[0], [1] are
+ * not touched); scratch: 3 * D + R + 8 floats.  The window's own launcher with that table alone (a character table without
+ * context tables, or a context table without characters); KL_ERR_SHAPE where it refuses the shape. */
+int kl_test_regulariser_grads(const float* X, int R, int D, int mode, float* gX, float* loss_acc, float* scratch, void* stream);
 /* the selection kernel of kl_rate_window_alts alone: f32 logits [rows][ld], time-major (r = t * B + b, rows == B * T,
  * ld >= V), tgt [B][T]; results batch-major as kl_rate_window_alts describes them (tprob and rank may be NULL).  The
  * register form for V <= 256 with V and ld multiples of 4 (logits 16-byte aligned), the strided form for any other V. */
@@ -417,16 +422,25 @@ int kl_test_rate_topk(const float* logits, long ld, int rows, int V, const int32
  * training window of that shape has run on ws.
  * The weight-gradient stage behind the scans: wg_route = KL_WG_* bits, exactly one of the first three; wg_pair_mask bit l --
  * layer l's dU and dK came from one paired launch; wg_db_scan_mask bit l -- layer l's bias gradient was summed by its backward
- * scan from the f32 values (else by a column sum over the stored bf16 dZ). */
+ * scan from the f32 values (else by a column sum over the stored bf16 dZ).
+ * The output layer in front of them: off_dlogits -- bf16 [TB][ld_dlogits], ld_dlogits = the vocabulary padded to the table
+ * rows Vp, row t * B + b = step t: the gradient of the logits as the output-layer kernels stored it and as dH and dE read it
+ * (columns from V on are zeros); a region of its own in the workspace, intact when kl_train_window returns.  out_route =
+ * KL_OUT_* bits: which of the output-layer kernel families ran, and which form of dlogits the dE product contracted over. */
 #define KL_WG_KMAJOR 1     /* products read dZ and the activations as the scans wrote them (K-major plan) */
 #define KL_WG_SCAN_T 2     /* ... contract over the transposed outputs the wide forward scans wrote */
 #define KL_WG_TRANSPOSE 4  /* ... over explicit transposes into buffers padded to a multiple of 8 rows */
 #define KL_WG_SEGSUM 8     /* layer 0: sorted segment sums for the characters and the first context variable (else one-hot products) */
 #define KL_WG_PAIR_CTX 16  /* layer 0: the first context variable's one-hot product shared a launch with the characters' */
+#define KL_OUT_LOGITS_WS 1    /* logits, softmax, CE and dlogits in one kernel (width 512, V = 256; else GEMM + softmax, or the next) */
+#define KL_OUT_LOGITS_W128 2  /* ... the width-128 kernel, and dH came with it */
+#define KL_OUT_DH_WS 4        /* dH by the width-512 kernel (else with the logits, or a GEMM) */
+#define KL_OUT_DE_KMAJOR 8    /* dE contracted over dlogits as stored (else over its explicit transpose) */
 typedef struct kl_window_view {
   int32_t depth, width, B, T;
-  int32_t g_interleaved, c_in_cb, dh_bf16, p_bf16_mask, scan2_rows, wg_route, wg_pair_mask, wg_db_scan_mask, reserved[4];
+  int32_t g_interleaved, c_in_cb, dh_bf16, p_bf16_mask, scan2_rows, wg_route, wg_pair_mask, wg_db_scan_mask, out_route, reserved[3];
   uint64_t off_H[16], off_C[16], off_Cb[16], off_G[16], off_dZ[16], off_Hd[16];
+  uint64_t off_dlogits, ld_dlogits;
 } kl_window_view;
 int kl_test_window_view(const kl_handle* h, int B, int T, const void* ws, kl_window_view* out);
 

@@ -187,6 +187,7 @@ struct kl_handle {
     // the weight-gradient stage (filled in once the stage's launches are built): KL_WG_* bits, dU / dK pairs and scan-summed
     // db per layer, layers whose masked outputs Hd were written
     unsigned wg_route = 0, wg_pair_mask = 0, wg_db_scan_mask = 0, hd_mask = 0;
+    unsigned out_route = 0;      // the output layer in front of them: KL_OUT_* bits
   };
   std::vector<ViewNote> view_notes;
   // the note of (B, T, ws); insert: a new one where there is none (the 64 most recent are kept), else null
@@ -1350,6 +1351,7 @@ static int train_output_layer(const TrainCall& c) {
     dh_done = fe == 0;
   }
   if (fe != 0 && fe != KL_ERR_SHAPE) return fe;
+  if (fe == 0) c.note.out_route |= dh_done ? KL_OUT_LOGITS_W128 : KL_OUT_LOGITS_WS;
   if (fe == 0) KL_TRY(kl_launch_rowstat_reduce(w.rowstat, BT, c.loss_acc, s));
   else {
     KL_TRY(kl_launch_gemm_tn(top.km, d.E_hi, w.logits, nullptr, BT, V, W, W, W, V, 0, 1, 1.f, s));
@@ -1358,6 +1360,7 @@ static int train_output_layer(const TrainCall& c) {
   // B1: dH = dlogits . E ; dE += dlogits^T . Htop
   int de = KL_ERR_SHAPE;
   if (c.dh_mode == 1 && h->logits_ws) de = kl_launch_dh_ws(w.dlogits, d.ET, reinterpret_cast<bf16_t*>(w.dH), BT, W, Vp, s);
+  if (de == 0) c.note.out_route |= KL_OUT_DH_WS;
   if (dh_done) de = 0;
   if (de == KL_ERR_SHAPE) de = kl_launch_gemm_tn(w.dlogits, d.ET, w.dH, nullptr, BT, W, Vp, Vp, Vp, W, c.dh_mode, 1, 1.f, s);
   KL_TRY(de);
@@ -1368,6 +1371,7 @@ static int train_output_layer(const TrainCall& c) {
   }
   // (dE with both operands as they lie in memory: the window's plan, and the vocabulary unpadded)
   const bool km_e = w.km_plan && Vp == V && kl_gemm_an_applicable(V, W, BT, Vp);
+  if (km_e) c.note.out_route |= KL_OUT_DE_KMAJOR;
   if (!km_e) KL_TRY(kl_launch_transpose_bf16(w.dlogits, Vp, w.dlogitsT, BTp, BT, Vp, s));
   return rows_product(c, km_e, {w.dlogits, Vp, w.dlogitsT, BTp}, V, top, W, c.grads + h->off_E, W, false);
 }
@@ -2349,6 +2353,12 @@ int kl_test_dh_ws(const uint16_t* dlogits, const uint16_t* ET, uint16_t* dH, lon
   return kl_launch_dh_ws(dlogits, ET, dH, M, 512, 256, (hipStream_t)stream);
 }
 
+int kl_test_regulariser_grads(const float* X, int R, int D, int mode, float* gX, float* loss_acc, float* scratch, void* stream) {
+  if (!X || !gX || !scratch || R < 1 || D < 1 || (mode != 0 && mode != 1)) return KL_ERR_ARG;
+  if (mode == 0) return kl_launch_regulariser_grads(X, R, D, nullptr, 0, 0, 0, gX, nullptr, loss_acc, scratch, (hipStream_t)stream);
+  return kl_launch_regulariser_grads(nullptr, 0, 0, &X, 1, R, D, nullptr, &gX, loss_acc, scratch, (hipStream_t)stream);
+}
+
 int kl_test_rate_topk(const float* logits, long ld, int rows, int V, const int32_t* tgt, int B, int T, int K,
                       float* tprob, int32_t* alt_id, float* alt_p, int32_t* rank, void* stream) {
   return kl_launch_rate_topk(logits, ld, rows, V, tgt, B, T, K, tprob, alt_id, alt_p, rank, (hipStream_t)stream);
@@ -2604,7 +2614,7 @@ extern "C" int kl_test_window_view(const kl_handle* h, int B, int T, const void*
   out->g_interleaved = note->g_interleaved; out->c_in_cb = note->c_in_cb; out->dh_bf16 = note->dh_bf16;
   out->p_bf16_mask = (int32_t)note->p_bf16_mask; out->scan2_rows = note->scan2_rows;
   out->wg_route = (int32_t)note->wg_route; out->wg_pair_mask = (int32_t)note->wg_pair_mask;
-  out->wg_db_scan_mask = (int32_t)note->wg_db_scan_mask;
+  out->wg_db_scan_mask = (int32_t)note->wg_db_scan_mask; out->out_route = (int32_t)note->out_route;
   const unsigned char* base = reinterpret_cast<const unsigned char*>(ws);
   auto off = [&](const void* p) { return (uint64_t)(reinterpret_cast<const unsigned char*>(p) - base); };
   for (int l = 0; l < h->cfg.depth; ++l) {      // (config_ok: at most 16 layers)
@@ -2612,6 +2622,7 @@ extern "C" int kl_test_window_view(const kl_handle* h, int B, int T, const void*
     out->off_G[l] = off(w.G[l]); out->off_dZ[l] = off(w.dZ[l]);
     out->off_Hd[l] = ((note->hd_mask >> l) & 1u) ? off(w.Hd[l]) : 0;
   }
+  out->off_dlogits = off(w.dlogits); out->ld_dlogits = (uint64_t)h->Vp;
   return 0;
 }
 

@@ -20,6 +20,8 @@ KL_SAMPLE_MAX_ROWS = 1024  # chains per kl_sample_pick call
 KL_SAMPLE_MAX_TOPK = 64
 # kl_window_view.wg_route
 KL_WG_KMAJOR, KL_WG_SCAN_T, KL_WG_TRANSPOSE, KL_WG_SEGSUM, KL_WG_PAIR_CTX = 1, 2, 4, 8, 16
+# kl_window_view.out_route
+KL_OUT_LOGITS_WS, KL_OUT_LOGITS_W128, KL_OUT_DH_WS, KL_OUT_DE_KMAJOR = 1, 2, 4, 8
 
 
 class KlConfig(C.Structure):
@@ -32,9 +34,10 @@ class KlWindowView(C.Structure):
     _fields_ = [("depth", C.c_int32), ("width", C.c_int32), ("B", C.c_int32), ("T", C.c_int32),
                 ("g_interleaved", C.c_int32), ("c_in_cb", C.c_int32), ("dh_bf16", C.c_int32), ("p_bf16_mask", C.c_int32),
                 ("scan2_rows", C.c_int32), ("wg_route", C.c_int32), ("wg_pair_mask", C.c_int32),
-                ("wg_db_scan_mask", C.c_int32), ("reserved", C.c_int32 * 4),
+                ("wg_db_scan_mask", C.c_int32), ("out_route", C.c_int32), ("reserved", C.c_int32 * 3),
                 ("off_H", C.c_uint64 * 16), ("off_C", C.c_uint64 * 16), ("off_Cb", C.c_uint64 * 16),
-                ("off_G", C.c_uint64 * 16), ("off_dZ", C.c_uint64 * 16), ("off_Hd", C.c_uint64 * 16)]
+                ("off_G", C.c_uint64 * 16), ("off_dZ", C.c_uint64 * 16), ("off_Hd", C.c_uint64 * 16),
+                ("off_dlogits", C.c_uint64), ("ld_dlogits", C.c_uint64)]
 
 
 class KlError(RuntimeError):
@@ -124,6 +127,7 @@ SIGNATURES = {
     "kl_test_logits_ce_w128": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p]),
     "kl_test_dh_ws": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p]),
+    "kl_test_regulariser_grads": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kl_test_rate_topk": (C.c_int, [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kl_test_window_view": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(KlWindowView)]),

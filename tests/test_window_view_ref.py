@@ -93,18 +93,22 @@ def test_layout_decoders_round_trip(interleaved, cb, width, n):
 
 def test_view_struct_and_dict():
     """the fields from before the weight-gradient stage was added keep their offsets (the scalars in front, the five offset
-    arrays from byte 64 on), the new ones took four of the reserved words and the end of the struct; `view_dict` carries all"""
+    arrays from byte 64 on), the new ones took four of the reserved words and the end of the struct; the output layer's took
+    one more reserved word (out_route) and two words behind off_Hd; `view_dict` carries all"""
     import ctypes as C
     from ocrd_keraslm_amd.lib import hipabi
     V = hipabi.KlWindowView
     scalars = ["depth", "width", "B", "T", "g_interleaved", "c_in_cb", "dh_bf16", "p_bf16_mask", "scan2_rows", "wg_route", "wg_pair_mask",
-               "wg_db_scan_mask", "reserved"]
+               "wg_db_scan_mask", "out_route", "reserved"]
     assert [getattr(V, k).offset for k in scalars] == [4 * i for i in range(len(scalars))]
     arrays = ["off_H", "off_C", "off_Cb", "off_G", "off_dZ", "off_Hd"]
-    assert [getattr(V, k).offset for k in arrays] == [64 + 128 * i for i in range(6)] and C.sizeof(V) == 64 + 128 * 6
+    assert [getattr(V, k).offset for k in arrays] == [64 + 128 * i for i in range(6)]
+    assert (V.off_dlogits.offset, V.ld_dlogits.offset, C.sizeof(V)) == (64 + 128 * 6, 64 + 128 * 6 + 8, 64 + 128 * 6 + 16)
+    assert V.reserved.size == 12 and V.reserved.offset + V.reserved.size == 64
+    assert (hipabi.KL_OUT_LOGITS_WS, hipabi.KL_OUT_LOGITS_W128, hipabi.KL_OUT_DH_WS, hipabi.KL_OUT_DE_KMAJOR) == (1, 2, 4, 8)
     assert (hipabi.KL_WG_KMAJOR, hipabi.KL_WG_SCAN_T, hipabi.KL_WG_TRANSPOSE, hipabi.KL_WG_SEGSUM, hipabi.KL_WG_PAIR_CTX) == (1, 2, 4, 8, 16)
     v = V(depth=3, width=128, B=40, T=5, p_bf16_mask=5, wg_route=hipabi.KL_WG_TRANSPOSE | hipabi.KL_WG_SEGSUM, wg_pair_mask=4,
-          wg_db_scan_mask=6)
+          wg_db_scan_mask=6, out_route=hipabi.KL_OUT_LOGITS_WS | hipabi.KL_OUT_DH_WS | hipabi.KL_OUT_DE_KMAJOR, off_dlogits=123456, ld_dlogits=352)
     for l in range(3):
         v.off_H[l], v.off_Hd[l] = 1000 + l, 7000 * l
     d = R.view_dict(v)
@@ -113,6 +117,36 @@ def test_view_struct_and_dict():
     from tests import window_grads as WG
     assert (WG.WG_KMAJOR, WG.WG_SCAN_T, WG.WG_TRANSPOSE, WG.WG_SEGSUM, WG.WG_PAIR_CTX) == (1, 2, 4, 8, 16)
     assert WG.route_text(d) == "transposes, pairs 001, db by scan 011, layer 0 segment sums"
+    from tests import table_grads as TG
+    assert (d["out_route"], d["off_dlogits"], d["ld_dlogits"]) == (13, 123456, 352)
+    assert (TG.OUT_LOGITS_WS, TG.OUT_LOGITS_W128, TG.OUT_DH_WS, TG.OUT_DE_KMAJOR) == (1, 2, 4, 8)
+    assert TG.route_text(d) == WG.route_text(d) + "; output layer: logits by one kernel (width 512), dH by width-512 kernel, dE k-major"
+    assert TG.route_text(dict(d, out_route=2)).endswith("logits by one kernel with dH (width 128), dH by with the logits, dE over dlogits^T")
+    assert TG.route_text(dict(d, out_route=0)).endswith("logits by GEMM + softmax, dH by GEMM, dE over dlogits^T")
+
+
+def test_dlogits_round_trip():
+    """[B*T][V] -> bf16 rows of ld_dlogits behind off_dlogits -> the same numbers, zeros in the padded columns, and nothing
+    else of the workspace touched; a view from before the fields decodes to None (as off_Hd's does, above)"""
+    L, Wp, B, T, V, Vp = 1, 32, 5, 3, 30, 32
+    view = dict(depth=L, width=Wp, B=B, T=T, g_interleaved=0, c_in_cb=0, dh_bf16=0, p_bf16_mask=0, scan2_rows=0)
+    off = 0
+    for key, size in (("off_H", (T + 1) * B * Wp * 2), ("off_C", (T + 1) * B * Wp * 4), ("off_Cb", (T + 1) * B * Wp * 2),
+                      ("off_G", T * B * 4 * Wp * 2), ("off_dZ", T * B * 4 * Wp * 2)):
+        view[key] = [off]
+        off += size
+    assert R.decode_dlogits(None, view) is None
+    before = R.window_bytes(view)
+    view["off_dlogits"], view["ld_dlogits"] = off + 64, Vp
+    assert R.window_bytes(view) == off + 64 + B * T * Vp * 2 > before
+    import torch
+    ws = torch.zeros(R.window_bytes(view), dtype=torch.uint8)
+    dl = O.bf16_round(np.random.default_rng(1).standard_normal((B * T, V)).astype(np.float32) * 1e-3)
+    R.encode_dlogits(ws, view, dl)
+    got = R.decode_dlogits(ws, view)
+    assert got.shape == (B * T, Vp) and np.array_equal(got[:, :V], dl) and not got[:, V:].any() and not ws[:off + 64].any()
+    t, b, v = 2, 4, 29      # the bytes lie as the header says: row t * B + b, column v of ld_dlogits
+    assert float(ws[off + 64:].view(torch.bfloat16)[(t * B + b) * Vp + v]) == dl[t * B + b, v]
 
 
 @pytest.fixture(scope="module")

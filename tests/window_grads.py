@@ -42,8 +42,8 @@ References are numpy f64 over the decoded values; rows are time-major, r = t * B
                     part (CHARACTERS) so that it does not hide the other products
   padding           entries of dU, dK, db in rows and columns of padded hidden units: exactly 0
 
-Out of scope: dE and the context tables' gradients -- dlogits is not in the view and the regularisers dominate both
-(tests/gradcheck.py keeps covering them); stream groups -- the workspace holds the last group only.
+dE, the context tables' gradients and the regularisers: tests/table_grads.py, through the view's off_dlogits and with
+regulariser-neutral tables.  Out of scope: stream groups -- the workspace holds the last group only.
 
 A failure names the array, the layer, the 64 x 64 tile of the worst element and the route the stage took.
 """

@@ -5,7 +5,8 @@ tests/test_window_intermediates_gpu.py (every scan family against the references
 of tests/test_gpu_kernels.py (the exact checks only).
 
 * `decode_window` / `encode_window`: the arrays behind a `kl_window_view` (include/keraslm_hip.h) <-> canonical numpy arrays,
-  h and c [L][B][T][W], gates and dz [L][B][T][4][W] in i,f,c,o order.
+  h and c [L][B][T][W], gates and dz [L][B][T][4][W] in i,f,c,o order; `decode_dlogits` / `encode_dlogits`: the output layer's
+  gradient of the logits, [B*T][Vp] time-major.
 * `references`: the f64 oracle and the "bf16-storage oracle" (oracle.lstm_oracle.Storage: the same arithmetic in f32 with bf16
   rounding wherever the HIP path stores bf16, following the flags of the view) -- both from oracle/lstm_oracle.py alone.
 * `check_tiles`: a TILE is one layer x one step x 16 consecutive streams, the hand-off unit of every scan.  Tile error =
@@ -189,6 +190,8 @@ def view_dict(view):
         d[k] = getattr(view, k)
     for k in ("off_H", "off_C", "off_Cb", "off_G", "off_dZ", "off_Hd"):
         d[k] = [int(v) for v in getattr(view, k)[:view.depth]]
+    for k in ("out_route", "off_dlogits", "ld_dlogits"):      # (the output layer: tests/table_grads.py)
+        d[k] = int(getattr(view, k))
     return d
 
 
@@ -250,9 +253,31 @@ def decode_hd(ws, view, width=None, n=None):
     return out
 
 
+def decode_dlogits(ws, view):
+    """The gradient of the logits behind `off_dlogits`: [B*T][Vp] f32, time-major (row t * B + b = step t), every row and padded
+    column of it; None for a view from before the field (ld_dlogits 0)"""
+    torch = _torch()
+    ld = view.get("ld_dlogits", 0)
+    if not ld:
+        return None
+    rows = view["B"] * view["T"]
+    off = view["off_dlogits"]
+    return ws[off:off + rows * ld * 2].view(torch.bfloat16).view(rows, ld).float().cpu().numpy()
+
+
+def encode_dlogits(ws, view, dlogits):
+    """the inverse of `decode_dlogits`, into a workspace that `encode_window` laid out: [B*T][<= Vp] f32 -> bf16 rows of ld_dlogits"""
+    torch = _torch()
+    rows, ld, off = view["B"] * view["T"], view["ld_dlogits"], view["off_dlogits"]
+    a = np.asarray(dlogits, dtype=np.float32)
+    assert a.shape[0] == rows and a.shape[1] <= ld, (a.shape, rows, ld)
+    ws[off:off + rows * ld * 2].view(torch.bfloat16).view(rows, ld)[:, :a.shape[1]] = torch.from_numpy(a).to(torch.bfloat16)
+    return ws
+
+
 def window_bytes(view):
     L, Wp, B, T = view["depth"], view["width"], view["B"], view["T"]
-    end = 0
+    end = view.get("off_dlogits", 0) + B * T * view.get("ld_dlogits", 0) * 2
     for l in range(L):
         if view.get("off_Hd", [0] * L)[l]:
             end = max(end, view["off_Hd"][l] + T * B * Wp * 2)
@@ -313,6 +338,7 @@ def read_window_padded(lm):
     vd = view_dict(view)
     out = decode_window(ws, vd)
     out["hd"] = decode_hd(ws, vd)
+    out["dlogits"] = decode_dlogits(ws, vd)      # (the output layer's: tests/table_grads.py)
     out["view"], out["info"] = vd, info
     return out
 
