@@ -122,6 +122,13 @@ int kl_set_window_mode(kl_handle* h, int last_only);
  * (rating.py:178, Keras' mean over the batch). */
 int kl_set_loss_rows(kl_handle* h, int rows);
 
+/* Ids outside their table (kl_forward_window, kl_train_window).  The caller passes 0 <= idx < voc_size and 0 <= ctx <
+ * ctx_vocab; nothing here checks them, and most kernels read the row an id names.  The training forward at width 512 (the
+ * second-generation wide scans, which also serve bf16 validation windows on a training-size workspace) is the exception, with
+ * ONE rule on all three routes layer 0's gate inputs take there -- table offsets, gathered rows, the table of all (character,
+ * context value) sums: idx is read clamped to [0, voc_size - 1], every ctx value clamped to [0, ctx_vocab - 1] (past the end:
+ * the last row; negative: the first).  The sorted segment sums of kl_train_window's backward pass DROP such a position from
+ * the table gradients instead, each table on its own (kl_test_segment_sums). */
 int kl_forward_window(kl_handle* h, int B, int T, const int32_t* idx, const int32_t* ctx, const int32_t* tgt,
                       float* states, float* probs, float* loss_acc, void* ws, size_t ws_bytes, void* stream);
 
@@ -443,6 +450,47 @@ typedef struct kl_window_view {
   uint64_t off_dlogits, ld_dlogits;
 } kl_window_view;
 int kl_test_window_view(const kl_handle* h, int B, int T, const void* ws, kl_window_view* out);
+
+/* Test hook: where kl_bind carved every operand array the kernels read instead of the parameter vector, and which of them
+ * match the bound parameters now.  Byte offsets into the bound derived buffer; per-layer arrays have 16 entries, per-context
+ * arrays 8.  W = width, V = voc_size, Vp = V padded to the table rows; bf16 unless stated; gate column order i, f, c, o.
+ *   UT_hi/lo, KT_hi/lo [4W][W]  U_l^T, K_l^T (layer 0: rows [0, W) of K0), hi = RNE bf16, lo = RNE bf16 of the remainder
+ *   Un, Kn [W][4W]              the same weights untransposed (hi)
+ *   E_hi/lo [Vp][W], ET [W][Vp] the embedding, zeros beyond V
+ *   EK f32 [V][4W]              E . K0[:W];   CtxK[n] f32 [ctx_vocab][4W] = Ctx_n . K0[W + n ctx_dim ..]
+ *   KTp[l] [4W][W], bp[l] f32 [4W]   row u*4+g <- g*W+u of KT_hi[l] / b_l, layers from 1 on (mask_il bit l)
+ *   EKp f32 [V][W][4] = EK + b_0, CtxKp[n] f32 [ctx_vocab][W][4]   the same interleave of the tables
+ *   comb [V ctx_vocab][W][4]    bf16(EKp[v] + CtxKp[0][c]); carved only where has_comb
+ *   UF[l], KF[l] (mask_KF bit l: layers from 1 on), EF   fragment-major [rows/16][W/32][planes][64][8] of UT, KT, E: one plane
+ *                               (hi) in bf16 precision, two (hi, lo) in split precision
+ *   WTcat[l] [4W][3 K_l]        blocks [hi | hi | lo], K_0 = W (U^T), K_l = 2W (K^T then U^T); bf16 precision writes block 0 only
+ *   WTperm[l]                   WTcat[l] with row g*W+u at (u/32)*128 + g*32 + u%32
+ *   Ecat [Vp][3W]               [hi | hi | lo] of E, zeros beyond V; bf16 precision writes block 0 only
+ * An offset is meaningful only where its mask says the array is carved (has_comb, mask_il, mask_KF; everything else always is).
+ * current = KL_DV_* bits: the groups written from the bound parameters by the last kl_prepare / kl_adam_step or built
+ * since.  The library cannot see a caller's own writes to the parameter vector: after those, kl_prepare is due as ever.
+ * Nothing is launched or allocated.  KL_ERR_STATE before kl_bind. */
+#define KL_DV_EAGER 1        /* UT_hi, KT_hi, Un, Kn, E_hi, ET, EK, CtxK */
+#define KL_DV_LO 2           /* UT_lo, KT_lo, E_lo: written in split precision only */
+#define KL_DV_INTERLEAVED 4  /* KTp, bp, EKp, CtxKp: written in bf16 precision at width 512 with the second-generation scans on */
+#define KL_DV_INC 8          /* UF, KF, EF: built on the first incremental step after a change of the operands */
+#define KL_DV_BIG 16         /* WTcat, WTperm, Ecat: built on the first step that takes the gather + GEMM path */
+#define KL_DV_COMB 32        /* comb: built by every window that gathers from it */
+typedef struct kl_derived_view {
+  int32_t depth, width, voc_size, Vp, n_ctx, ctx_vocab, ctx_dim, precision;
+  int32_t current, has_comb, mask_il, mask_KF, reserved[4];
+  uint64_t off_UT_hi[16], off_UT_lo[16], off_KT_hi[16], off_KT_lo[16], off_Un[16], off_Kn[16];
+  uint64_t off_KTp[16], off_bp[16], off_UF[16], off_KF[16], off_WTcat[16], off_WTperm[16];
+  uint64_t off_CtxK[8], off_CtxKp[8];
+  uint64_t off_E_hi, off_E_lo, off_ET, off_EK, off_EKp, off_comb, off_EF, off_Ecat;
+  uint64_t bytes;      /* kl_derived_bytes */
+} kl_derived_view;
+int kl_test_derived_view(const kl_handle* h, kl_derived_view* out);
+/* Test hook: build the lazily built operand groups now, each by the launches its first user issues -- mask bit 0 the
+ * incremental step's (KL_DV_INC), bit 1 the gather + GEMM path's (KL_DV_BIG), bit 2 the table of all sums (KL_DV_COMB).
+ * KL_ERR_STATE before kl_prepare, KL_ERR_ARG for an empty mask or other bits, KL_ERR_SHAPE for bit 2 where comb is not
+ * carved or the interleaved tables it sums are not current; all before anything is launched. */
+int kl_test_prepare_lazy(kl_handle* h, int mask, void* stream);
 
 #ifdef __cplusplus
 }

@@ -130,6 +130,8 @@ struct kl_handle {
   void* walk_ready = nullptr;           // kl_walk_batch_host: the workspace whose ticket counter has been zeroed
   bool inc_ready = false;       // the incremental step's fragment-major operands match the current weights (prepare_incremental)
   bool big_ready = false;       // ... and those of the gather + GEMM path (prepare_big_step)
+  bool il_ready = false;        // the gate-interleaved set was written by the last prepare_impl (kl_test_derived_view)
+  bool comb_ready = false;      // ... and the table of all sums built from it since (build_comb: for kl_test_derived_view only -- a replayed window rebuilds it unnoted)
   int last_only = 0;            // stateless windows: one target per row, at the last position (kl_set_window_mode)
   int loss_rows = 0;            // rows the training means are taken over when the batch carries dummy streams (kl_set_loss_rows; 0: B)
   bool sentinel = true;         // wide scans hand off by data sentinels instead of counters (KL_SENTINEL=0: counters)
@@ -466,7 +468,9 @@ int prepare_impl(kl_handle* h, int precision, hipStream_t s) {
     const float* Kc = P + h->off_K[0] + (size_t)(W + n * c.ctx_dim) * 4 * W;
     KL_TRY(kl_launch_small_table(P + h->off_Ctx[n], c.ctx_vocab, c.ctx_dim, Kc, 4 * W, 4 * W, d.CtxK[n], 4 * W, s));
   }
-  if (precision == KL_PREC_BF16 && h->scan2 && W == 512) {
+  h->il_ready = precision == KL_PREC_BF16 && h->scan2 && W == 512;
+  h->comb_ready = false;
+  if (h->il_ready) {
     // gate-interleaved copies for the second-generation wide scans
     for (int l = 1; l < c.depth; ++l) {
       KL_TRY(kl_launch_permute_gate_rows_bf16(d.KT_hi[l], d.KTp[l], W, W, s));
@@ -528,6 +532,15 @@ int prepare_big_step(kl_handle* h, hipStream_t s) {
   KL_TRY(kl_launch_f32_to_bf16_t(E, W, V, W, d.Ecat, split ? d.Ecat + 2 * W : nullptr, 3 * W, 0, s));
   if (split) KL_TRY(kl_launch_f32_to_bf16_t(E, W, V, W, d.Ecat + W, nullptr, 3 * W, 0, s));
   h->big_ready = true;
+  return 0;
+}
+
+// (3) every gate-input row layer 0 can ask for: 200 MiB, ~0.05 ms -- built by every window that gathers from it (no "already
+// built" test: a captured window is replayed after later updates of the operands, and must then build it again)
+int build_comb(kl_handle* h, hipStream_t s) {
+  const kl_config& c = h->cfg;
+  KL_TRY(kl_launch_comb_table(h->d.EKp, h->d.CtxKp[0], c.voc_size, c.ctx_vocab, 4 * c.width, h->d.comb, s));
+  h->comb_ready = true;
   return 0;
 }
 
@@ -606,10 +619,8 @@ int forward_impl(kl_handle* h, int B, int T, const int* idx, const int* ctx, flo
         a.P = w.P1;
         a.p_bf16 = v2 && h->scan2_bf16 ? 1 : 0;
       } else if (f8_tab) {
-        // every gate-input row layer 0 can ask for: 200 MiB, ~0.05 ms -- built by every window that gathers from it (no "already
-        // built" flag: a captured window is replayed after later updates of the operands, and must then build it again)
-        KL_TRY(kl_launch_comb_table(d.EKp, d.CtxKp[0], c.voc_size, c.ctx_vocab, 4 * W, d.comb, s));
-        KL_TRY(kl_launch_rows_tm(idx, ctx, c.n_ctx, B, T, c.ctx_vocab, w.ids_tm, s));
+        KL_TRY(build_comb(h, s));
+        KL_TRY(kl_launch_rows_tm(idx, ctx, c.n_ctx, B, T, c.voc_size, c.ctx_vocab, w.ids_tm, s));
         a.P = reinterpret_cast<const float*>(d.comb);
         a.p_bf16 = 1;
         a.ids_tm = w.ids_tm;      // (here: row numbers of d.comb, [T][B])
@@ -2623,6 +2634,50 @@ extern "C" int kl_test_window_view(const kl_handle* h, int B, int T, const void*
     out->off_Hd[l] = ((note->hd_mask >> l) & 1u) ? off(w.Hd[l]) : 0;
   }
   out->off_dlogits = off(w.dlogits); out->ld_dlogits = (uint64_t)h->Vp;
+  return 0;
+}
+
+extern "C" int kl_test_derived_view(const kl_handle* h, kl_derived_view* out) {
+  if (!h || !out) return KL_ERR_ARG;
+  if (!h->derived_ws) return KL_ERR_STATE;
+  const kl_config& c = h->cfg;
+  const Derived& d = h->d;
+  memset(out, 0, sizeof(*out));
+  out->depth = c.depth; out->width = c.width; out->voc_size = c.voc_size; out->Vp = h->Vp;
+  out->n_ctx = c.n_ctx; out->ctx_vocab = c.ctx_vocab; out->ctx_dim = c.ctx_dim; out->precision = h->precision;
+  if (h->precision) {
+    out->current = KL_DV_EAGER | (h->precision == KL_PREC_SPLIT ? KL_DV_LO : 0) | (h->il_ready ? KL_DV_INTERLEAVED : 0) |
+                   (h->inc_ready ? KL_DV_INC : 0) | (h->big_ready ? KL_DV_BIG : 0) | (h->comb_ready ? KL_DV_COMB : 0);
+  }
+  const unsigned char* base = reinterpret_cast<const unsigned char*>(h->derived_ws);
+  auto off = [&](const void* p) { return p ? (uint64_t)(reinterpret_cast<const unsigned char*>(p) - base) : (uint64_t)0; };
+  for (int l = 0; l < c.depth; ++l) {      // (config_ok: at most 16 layers, 8 context variables)
+    out->off_UT_hi[l] = off(d.UT_hi[l]); out->off_UT_lo[l] = off(d.UT_lo[l]);
+    out->off_KT_hi[l] = off(d.KT_hi[l]); out->off_KT_lo[l] = off(d.KT_lo[l]);
+    out->off_Un[l] = off(d.Un[l]); out->off_Kn[l] = off(d.Kn[l]);
+    out->off_KTp[l] = off(d.KTp[l]); out->off_bp[l] = off(d.bp[l]);
+    out->off_UF[l] = off(d.UF[l]); out->off_KF[l] = off(d.KF[l]);
+    out->off_WTcat[l] = off(d.WTcat[l]); out->off_WTperm[l] = off(d.WTperm[l]);
+    if (d.KTp[l]) out->mask_il |= 1 << l;
+    if (d.KF[l]) out->mask_KF |= 1 << l;
+  }
+  for (int n = 0; n < c.n_ctx; ++n) { out->off_CtxK[n] = off(d.CtxK[n]); out->off_CtxKp[n] = off(d.CtxKp[n]); }
+  out->off_E_hi = off(d.E_hi); out->off_E_lo = off(d.E_lo); out->off_ET = off(d.ET);
+  out->off_EK = off(d.EK); out->off_EKp = off(d.EKp); out->off_EF = off(d.EF); out->off_Ecat = off(d.Ecat);
+  out->has_comb = d.comb ? 1 : 0;
+  out->off_comb = off(d.comb);
+  out->bytes = (uint64_t)carve_derived(h, nullptr, nullptr);
+  return 0;
+}
+
+extern "C" int kl_test_prepare_lazy(kl_handle* h, int mask, void* stream) {
+  if (!h || mask < 1 || mask > 7) return KL_ERR_ARG;
+  if (!h->precision) return KL_ERR_STATE;
+  if ((mask & 4) && (!h->d.comb || !h->il_ready)) return KL_ERR_SHAPE;
+  hipStream_t s = (hipStream_t)stream;
+  if (mask & 1) KL_TRY(prepare_incremental(h, s));
+  if (mask & 2) KL_TRY(prepare_big_step(h, s));
+  if (mask & 4) KL_TRY(build_comb(h, s));
   return 0;
 }
 

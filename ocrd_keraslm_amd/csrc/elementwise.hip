@@ -532,12 +532,18 @@ __global__ void comb_table_kernel(const float* __restrict__ A, const float* __re
     reinterpret_cast<uint4*>(out)[e] = o;
   }
 }
-__global__ void rows_tm_kernel(const int* __restrict__ idx, const int* __restrict__ ctx, int n_ctx, int Bn, int T, int R2, int* __restrict__ out) {
+// (both ids clamped to their tables, as ids_tm_kernel and p_gather_il_kernel read them: a context value of R2 would
+//  otherwise name the NEXT character's first row)
+__global__ void rows_tm_kernel(const int* __restrict__ idx, const int* __restrict__ ctx, int n_ctx, int Bn, int T, int V, int R2, int* __restrict__ out) {
   const long total = (long)Bn * T;
   for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
     const int b = (int)(e % Bn), t = (int)(e / Bn);
     const long src = (long)b * T + t;
-    out[e] = idx[src] * R2 + (n_ctx > 0 ? ctx[src * n_ctx] : 0);
+    int id = idx[src];
+    id = id < 0 ? 0 : (id >= V ? V - 1 : id);
+    int c = n_ctx > 0 ? ctx[src * n_ctx] : 0;
+    c = c < 0 ? 0 : (c >= R2 ? R2 - 1 : c);
+    out[e] = id * R2 + c;
   }
 }
 
@@ -547,8 +553,9 @@ int kl_launch_comb_table(const float* A, const float* B, int R1, int R2, int N, 
   hipLaunchKernelGGL(comb_table_kernel, dim3(grid_for(total, 256)), dim3(256), 0, stream, A, B, R2, N / 8, out, total);
   return ok();
 }
-int kl_launch_rows_tm(const int* idx, const int* ctx, int n_ctx, int Bn, int T, int R2, int* out, hipStream_t stream) {
-  hipLaunchKernelGGL(rows_tm_kernel, dim3(grid_for((long)Bn * T, 256)), dim3(256), 0, stream, idx, ctx, n_ctx, Bn, T, R2, out);
+int kl_launch_rows_tm(const int* idx, const int* ctx, int n_ctx, int Bn, int T, int V, int R2, int* out, hipStream_t stream) {
+  if (V < 1 || R2 < 1) return KL_ERR_SHAPE;
+  hipLaunchKernelGGL(rows_tm_kernel, dim3(grid_for((long)Bn * T, 256)), dim3(256), 0, stream, idx, ctx, n_ctx, Bn, T, V, R2, out);
   return ok();
 }
 

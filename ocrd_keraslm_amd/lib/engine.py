@@ -638,6 +638,20 @@ class HipLM:
         hipabi.check(self.lib.kl_test_window_view(self.handle, B, T, _ptr(self._ws), C.byref(view)), "kl_test_window_view")
         return view, self._ws, dict(B=B, T=T, first=first, n=n, groups=groups)
 
+    def derived_view(self):
+        """Test hook (kl_test_derived_view): where every operand array derived from the parameters lies and which groups of
+        them match the parameters now.  Returns (view, derived): the kl_derived_view and the uint8 tensor its byte offsets
+        point into, at the PADDED width.  Decoding and the arrays' definitions: tests/derived_ref.py."""
+        view = hipabi.KlDerivedView()
+        self.torch.cuda.synchronize(self.device)
+        hipabi.check(self.lib.kl_test_derived_view(self.handle, C.byref(view)), "kl_test_derived_view")
+        return view, self.derived
+
+    def prepare_lazy(self, mask):
+        """Test hook (kl_test_prepare_lazy): build the lazily built operand groups now (hipabi.KL_LAZY_* bits)."""
+        with self._launch():
+            hipabi.check(self.lib.kl_test_prepare_lazy(self.handle, int(mask), self._stream()), "kl_test_prepare_lazy")
+
     def _plan_512(self, B, limit):
         """[(streams, run as)] for a batch of B streams at width 512.  The second-generation scans take every multiple of 512
         from 1024 to 3072 streams (32 row groups x 2 .. 6 row blocks of 16, lstm_scan2.hip) and are faster per stream than the

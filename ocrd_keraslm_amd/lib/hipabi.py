@@ -22,6 +22,9 @@ KL_SAMPLE_MAX_TOPK = 64
 KL_WG_KMAJOR, KL_WG_SCAN_T, KL_WG_TRANSPOSE, KL_WG_SEGSUM, KL_WG_PAIR_CTX = 1, 2, 4, 8, 16
 # kl_window_view.out_route
 KL_OUT_LOGITS_WS, KL_OUT_LOGITS_W128, KL_OUT_DH_WS, KL_OUT_DE_KMAJOR = 1, 2, 4, 8
+# kl_derived_view.current; the first three bits of the mask of kl_test_prepare_lazy
+KL_DV_EAGER, KL_DV_LO, KL_DV_INTERLEAVED, KL_DV_INC, KL_DV_BIG, KL_DV_COMB = 1, 2, 4, 8, 16, 32
+KL_LAZY_INC, KL_LAZY_BIG, KL_LAZY_COMB = 1, 2, 4
 
 
 class KlConfig(C.Structure):
@@ -38,6 +41,17 @@ class KlWindowView(C.Structure):
                 ("off_H", C.c_uint64 * 16), ("off_C", C.c_uint64 * 16), ("off_Cb", C.c_uint64 * 16),
                 ("off_G", C.c_uint64 * 16), ("off_dZ", C.c_uint64 * 16), ("off_Hd", C.c_uint64 * 16),
                 ("off_dlogits", C.c_uint64), ("ld_dlogits", C.c_uint64)]
+
+
+class KlDerivedView(C.Structure):
+    """kl_derived_view of include/keraslm_hip.h (kl_test_derived_view)"""
+    _fields_ = ([(n, C.c_int32) for n in ("depth", "width", "voc_size", "Vp", "n_ctx", "ctx_vocab", "ctx_dim", "precision",
+                                          "current", "has_comb", "mask_il", "mask_KF")] + [("reserved", C.c_int32 * 4)] +
+                [("off_" + n, C.c_uint64 * 16) for n in ("UT_hi", "UT_lo", "KT_hi", "KT_lo", "Un", "Kn", "KTp", "bp", "UF", "KF",
+                                                         "WTcat", "WTperm")] +
+                [("off_CtxK", C.c_uint64 * 8), ("off_CtxKp", C.c_uint64 * 8)] +
+                [("off_" + n, C.c_uint64) for n in ("E_hi", "E_lo", "ET", "EK", "EKp", "comb", "EF", "Ecat")] +
+                [("bytes", C.c_uint64)])
 
 
 class KlError(RuntimeError):
@@ -131,6 +145,8 @@ SIGNATURES = {
     "kl_test_rate_topk": (C.c_int, [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kl_test_window_view": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(KlWindowView)]),
+    "kl_test_derived_view": (C.c_int, [C.c_void_p, C.POINTER(KlDerivedView)]),
+    "kl_test_prepare_lazy": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
 }
 
 _lib = None
