@@ -14,6 +14,7 @@
  *   model.evaluate_generator, :490                           kl_forward_window (tgt != NULL)
  *   Rater.rate, :493-529, for many texts at once             kl_rate_window (one text per stream, target-only delivery)
  *   ... with the model's top-K characters and the target's rank  kl_rate_window_alts
+ *   ... for a whole corpus, on the training forward (bf16)    kl_rate_window_bulk, kl_rate_scatter, kl_rate_text_bits
  *   model.predict_on_batch, stateful (1,1) step, :566        kl_forward_window with T = 1
  *   model.predict_on_batch, incremental + states, :631       kl_step_batch
  *   ... once per character of a lattice edge, :796-851       kl_walk_batch_host (all characters of all hypotheses, one call)
@@ -166,6 +167,31 @@ size_t kl_rate_alts_workspace_bytes(const kl_handle* h, int B, int T, int K);
 int kl_rate_window_alts(kl_handle* h, int B, int T, int K, const int32_t* idx, const int32_t* ctx, const int32_t* tgt,
                         float* states, float* tprob, int32_t* alt_id, float* alt_p, int32_t* rank, double* bits,
                         float* status, void* ws, size_t ws_bytes, void* stream);
+
+/* Bulk rating: kl_rate_window on the training forward.  Arguments, tprob / bits / status and error returns are those of
+ * kl_rate_window; the recurrence, the logits and the state advance are those of kl_forward_window in KL_PREC_BF16 on a
+ * training-size workspace, bit for bit (the wide persistent scans and the ring GEMM of a validation window, which take
+ * thousands of streams per launch; bf16 accuracy: probabilities within 1e-2 of f64, where kl_rate_window in split
+ * precision holds 2e-5).  KL_ERR_STATE unless the handle is prepared in KL_PREC_BF16, and after kl_set_window_mode(h, 1);
+ * KL_ERR_WORKSPACE below kl_rate_bulk_workspace_bytes(h, B, T) = kl_window_workspace_bytes(h, B, T, 1) (0 for B, T < 1);
+ * KL_ERR_ARG as in kl_rate_window; all before anything is launched.  The id rule of the training forward at width 512
+ * holds here too (see kl_forward_window). */
+size_t kl_rate_bulk_workspace_bytes(const kl_handle* h, int B, int T);
+int kl_rate_window_bulk(kl_handle* h, int B, int T, const int32_t* idx, const int32_t* ctx, const int32_t* tgt,
+                        float* states, float* tprob, double* bits, float* status, void* ws, size_t ws_bytes, void* stream);
+
+/* Results of rating windows in corpus order: the way back from the batches kl_assemble_windows makes.  No handle.
+ * kl_rate_scatter: tprob (device f32 [B][T]) as a rating window delivered it for the batch of `plan` (the array
+ *   kl_assemble_windows read: device int64 [B][4 + n_ctx], of which only start and vlen are used).  For 0 <= t < min(vlen, T)
+ *   with 0 <= start + 1 + t < n_out:  out[start + 1 + t] = tprob[b][t]  -- the probability of the character tgt[b][t] was read
+ *   from, at that character's position.  A bit copy; nothing else is written, a row with vlen <= 0 writes nothing.
+ * kl_rate_text_bits: offsets (device int64 [n_texts + 1], ascending): text i occupies probs[offsets[i] .. offsets[i+1] - 1].
+ *   bits[i] (device f64 [n_texts]) is OVERWRITTEN with -sum log2(max((double)probs[j], 1e-99)) over j = offsets[i] + 1 ..
+ *   offsets[i+1] - 1 (the first character has no prediction; fewer than two characters give 0), one wave per text, summed
+ *   in a fixed order: two calls on the same input give the same bits.
+ * KL_ERR_ARG for null pointers, B, T or n_texts < 1, n_ctx outside 0 .. 8, misaligned pointers.  One launch each on `stream`. */
+int kl_rate_scatter(const float* tprob, const int64_t* plan, int B, int T, int n_ctx, float* out, size_t n_out, void* stream);
+int kl_rate_text_bits(const float* probs, const int64_t* offsets, int n_texts, double* bits, void* stream);
 
 /* One training batch, forward + backward (rating.py:292-298 -> train_on_batch):
  * writes the gradient of (mean CE + embedding regularisers, rating.py:187-246)

@@ -1268,6 +1268,20 @@ static int forward_window_tail(kl_handle* h, WindowWs& w, int B, int T, const in
   return hip_ok(hipGetLastError());
 }
 
+// ... and of a bf16 window on the TRAINING layout: the training forward -- persistent wide / fused scans and the big GEMMs --
+// without the backward, instead of the launch-per-step inference kernels.  Shared by kl_forward_window (validation windows)
+// and kl_rate_window_bulk, which differ in what they make of the logits.
+static int window_logits_training(kl_handle* h, int B, int T, const int32_t* idx, const int32_t* ctx, float* states, WindowWs& w,
+                                  hipStream_t s) {
+  const int W = h->cfg.width, V = h->cfg.voc_size, L = h->cfg.depth;
+  KL_TRY(kl_zero_async(w.scan_status, (4 + 256) * sizeof(unsigned), s));
+  w.km_plan = true;                  // (no transposed outputs: nothing is going to contract over the rows)
+  w.scan2_rows = plan_scan2(h, B, T, true, false);
+  KL_TRY(forward_impl(h, B, T, idx, ctx, states, nullptr, 1, w, s));
+  const bf16_t* Htop = (const bf16_t*)w.H[L - 1] + (size_t)B * W;
+  return kl_launch_gemm_tn(Htop, h->d.E_hi, w.logits, nullptr, B * T, V, W, W, W, V, 0, 1, 1.f, s);
+}
+
 static int forward_window_body(kl_handle* h, int B, int T, const int32_t* idx, const int32_t* ctx, const int32_t* tgt,
                       float* states, float* probs, float* loss_acc, void* ws, size_t ws_bytes, void* stream) {
   if (!h || !idx || !states || !ws || B < 1 || T < 1) return KL_ERR_ARG;
@@ -1275,18 +1289,11 @@ static int forward_window_body(kl_handle* h, int B, int T, const int32_t* idx, c
   if (!h->precision) return KL_ERR_STATE;
   hipStream_t s = (hipStream_t)stream;
   WindowWs w;
-  const int W = h->cfg.width, V = h->cfg.voc_size, L = h->cfg.depth;
   // Windows in bf16 precision (validation after each epoch, rating.py:300-306: a fifth of every epoch's data) with
-  // a training-size workspace take the TRAINING forward -- persistent wide / fused scans and the big GEMMs -- without
-  // the backward, instead of the launch-per-step inference kernels (1024 x 256 characters: 41 ms -> 4.6 ms).
+  // a training-size workspace take the TRAINING forward (window_logits_training; 1024 x 256 characters: 41 ms -> 4.6 ms).
   if (h->precision == KL_PREC_BF16 && ws_bytes >= carve_window(h, nullptr, B, T, 1, nullptr)) {
     carve_window(h, ws, B, T, 1, &w);
-    KL_TRY(kl_zero_async(w.scan_status, (4 + 256) * sizeof(unsigned), s));
-    w.km_plan = true;                  // (no transposed outputs: nothing is going to contract over the rows)
-    w.scan2_rows = plan_scan2(h, B, T, true, false);
-    KL_TRY(forward_impl(h, B, T, idx, ctx, states, nullptr, 1, w, s));
-    const bf16_t* Htop = (const bf16_t*)w.H[L - 1] + (size_t)B * W;
-    KL_TRY(kl_launch_gemm_tn(Htop, h->d.E_hi, w.logits, nullptr, B * T, V, W, W, W, V, 0, 1, 1.f, s));
+    KL_TRY(window_logits_training(h, B, T, idx, ctx, states, w, s));
     const int mean_rows = (h->loss_rows > 0 && h->loss_rows <= B) ? h->loss_rows : B;      // (a padded batch: kl_set_loss_rows)
     return forward_window_tail(h, w, B, T, tgt, mean_rows, probs, loss_acc, s);
   }
@@ -2513,6 +2520,46 @@ extern "C" int kl_rate_window(kl_handle* h, int B, int T, const int32_t* idx, co
   KL_TRY(run_graphed(h, key, s, [&]() {
     const int V = h->cfg.voc_size;
     KL_TRY(window_logits(h, B, T, w.s_idx, w.s_ctx, states, w, s));
+    if (pick) KL_TRY(kl_launch_rate_pick(w.logits, V, B * T, V, w.s_tgt, B, T, w.s_probs, s));
+    if (bits) KL_TRY(kl_launch_rate_bits(w.s_probs, w.s_tgt, B, T, bits, s));
+    if (status) hipLaunchKernelGGL(scan_status_kernel, dim3(1), dim3(64), 0, s, w.scan_status, status);
+    return hip_ok(hipGetLastError());
+  }));
+  if (tprob) KL_TRY(hip_ok(hipMemcpyAsync(tprob, w.s_probs, BT * sizeof(float), hipMemcpyDeviceToDevice, s)));
+  return 0;
+}
+
+// ---- bulk rating: kl_rate_window on the training forward -----------------------------------------------------------
+// kl_rate_window's delivery behind the recurrence and logits of a bf16 validation window (window_logits_training): the wide
+// persistent scans take thousands of streams per launch where the split-precision scan of the inference layout takes 256.
+// The workspace is the training window's; its probability staging slot holds the [B][T] picks.
+extern "C" size_t kl_rate_bulk_workspace_bytes(const kl_handle* h, int B, int T) {
+  if (!h || B < 1 || T < 1) return 0;
+  return carve_window(h, nullptr, B, T, 1, nullptr);
+}
+
+extern "C" int kl_rate_window_bulk(kl_handle* h, int B, int T, const int32_t* idx, const int32_t* ctx, const int32_t* tgt,
+                                   float* states, float* tprob, double* bits, float* status, void* ws, size_t ws_bytes,
+                                   void* stream) {
+  if (!h || !idx || !states || !ws || B < 1 || T < 1) return KL_ERR_ARG;
+  if (h->cfg.n_ctx > 0 && !ctx) return KL_ERR_ARG;
+  if ((tprob || bits) && !tgt) return KL_ERR_ARG;
+  if (h->precision != KL_PREC_BF16 || h->last_only) return KL_ERR_STATE;      // (the training forward is bf16's; last_only as kl_rate_window)
+  hipStream_t s = (hipStream_t)stream;
+  WindowWs w;
+  if (ws_bytes < carve_window(h, nullptr, B, T, 1, nullptr)) return KL_ERR_WORKSPACE;
+  carve_window(h, ws, B, T, 1, &w);
+  const size_t BT = (size_t)B * T;
+  const bool pick = tprob || bits;
+  KL_TRY(hip_ok(hipMemcpyAsync(w.s_idx, idx, BT * sizeof(int), hipMemcpyDeviceToDevice, s)));
+  if (h->cfg.n_ctx > 0)
+    KL_TRY(hip_ok(hipMemcpyAsync(w.s_ctx, ctx, BT * h->cfg.n_ctx * sizeof(int), hipMemcpyDeviceToDevice, s)));
+  if (pick) KL_TRY(hip_ok(hipMemcpyAsync(w.s_tgt, tgt, BT * sizeof(int), hipMemcpyDeviceToDevice, s)));
+  // (baked into the captured launches as in kl_rate_window; a kind of its own: the same arrays may serve both calls)
+  kl_handle::GraphKey key{4, B, T, (tprob ? 1 : 0) | (bits ? 2 : 0), h->precision, states, status, ws, bits, 1};
+  KL_TRY(run_graphed(h, key, s, [&]() {
+    const int V = h->cfg.voc_size;
+    KL_TRY(window_logits_training(h, B, T, w.s_idx, w.s_ctx, states, w, s));
     if (pick) KL_TRY(kl_launch_rate_pick(w.logits, V, B * T, V, w.s_tgt, B, T, w.s_probs, s));
     if (bits) KL_TRY(kl_launch_rate_bits(w.s_probs, w.s_tgt, B, T, bits, s));
     if (status) hipLaunchKernelGGL(scan_status_kernel, dim3(1), dim3(64), 0, s, w.scan_status, status);

@@ -419,6 +419,96 @@ class HipLM:
             self._rate_ws_key = key
         return self._rate_ws
 
+    # ------------------------------------------------------------------ bulk rating: rating windows on the training forward
+    def rate_window_bulk(self, idx_d, ctx_d, tgt_d, want_probs=True):
+        """`rate_window` on the bf16 training forward (kl_rate_window_bulk): the wide persistent scans take thousands of
+        streams per launch.  idx_d [B,T], ctx_d [B,T,n_ctx], tgt_d [B,T]: int32 DEVICE tensors (as `assemble_windows` makes
+        them); returns a DEVICE tensor [B,T] f32 (None without want_probs).  Prepares bf16 precision if the handle is in
+        another.  Streams are grouped and padded with dummy streams (idx 0, tgt -1, zero state: they deliver nothing and take
+        no bits) as `forward_window` does for validation windows.  Bits and status as in `rate_window`."""
+        torch = self.torch
+        if self.precision == 0:
+            raise hipabi.KlError("weights not prepared")
+        if self.precision != hipabi.KL_PREC_BF16:
+            self.prepare(hipabi.KL_PREC_BF16)
+        with self._launch():
+            idx_d, tgt_d = self._dev_i32(idx_d), self._dev_i32(tgt_d)
+            B, T = idx_d.shape
+            ctx_d = self._dev_i32(ctx_d) if self.n_ctx else None
+            if self.states is None or self.states.shape[0] != B:
+                self.reset_states(B)
+            if self.rate_bits is None or self.rate_bits.shape[0] != B:
+                self.rate_bits = torch.zeros(B, dtype=torch.float64, device=self.device)
+            if self._rate_status is None:
+                self._rate_status = torch.zeros(4, dtype=torch.float32, device=self.device)
+            tprob = torch.empty((B, T), dtype=torch.float32, device=self.device) if want_probs else None
+            parts = self._stream_groups(B, T)
+            padded = [self._padded_streams(b1 - b0, T) for b0, b1 in parts]
+            ws = self._workspace(max(padded), T, True)
+            for (b0, b1), Bp in zip(parts, padded):
+                n = b1 - b0
+                x, c, y, st = idx_d[b0:b1], (ctx_d[b0:b1] if ctx_d is not None else None), tgt_d[b0:b1], self.states[b0:b1]
+                p = tprob[b0:b1] if tprob is not None else None
+                bits = self.rate_bits[b0:b1]
+                if Bp != n:
+                    x = torch.nn.functional.pad(x, (0, 0, 0, Bp - n))
+                    y = torch.nn.functional.pad(y, (0, 0, 0, Bp - n), value=-1)
+                    if c is not None:
+                        c = torch.nn.functional.pad(c, (0, 0, 0, 0, 0, Bp - n))
+                    st = self._pad_states.get(Bp)
+                    if st is None:
+                        st = self._pad_states[Bp] = torch.zeros((Bp,) + tuple(self.states.shape[1:]), dtype=torch.float32,
+                                                                device=self.device)
+                    st[:n] = self.states[b0:b1]
+                    st[n:] = 0
+                    if want_probs:
+                        p = torch.empty((Bp, T), dtype=torch.float32, device=self.device)
+                    bits = torch.zeros(Bp, dtype=torch.float64, device=self.device)
+                hipabi.check(self.lib.kl_rate_window_bulk(
+                    self.handle, Bp, T, _ptr(x), _ptr(c), _ptr(y), _ptr(st), _ptr(p), _ptr(bits), _ptr(self._rate_status),
+                    _ptr(ws), ws.numel(), self._stream()), "kl_rate_window_bulk")
+                if Bp != n:
+                    self.states[b0:b1] = st[:n]
+                    self.rate_bits[b0:b1] += bits[:n]
+                    if want_probs:
+                        tprob[b0:b1] = p[:n]
+        return tprob
+
+    def reset_states_where(self, mask_d):
+        """zero the state rows mask_d (bool DEVICE tensor [B]) names: one masked fill, no index list"""
+        with self._launch():
+            self.states.masked_fill_(mask_d.view(-1, 1, 1), 0.0)
+
+    def rate_scatter(self, tprob, plan, n_ctx, out):
+        """kl_rate_scatter: a call's target probabilities tprob [B,T] (f32 DEVICE tensor) to the places of their characters in
+        out (f32 DEVICE vector shaped like the id corpus): out[start + 1 + t] = tprob[b][t] for t < min(vlen, T), start and
+        vlen from plan (int64 DEVICE tensor [B, 4 + n_ctx], what `assemble_windows` read).  In place, no synchronisation."""
+        torch = self.torch
+        B, T = int(tprob.shape[0]), int(tprob.shape[1])
+        if (tprob.dtype != torch.float32 or out.dtype != torch.float32 or plan.dtype != torch.int64 or plan.dim() != 2
+                or tuple(plan.shape) != (B, 4 + n_ctx) or out.dim() != 1
+                or not (tprob.is_contiguous() and plan.is_contiguous() and out.is_contiguous())
+                or not (tprob.is_cuda and plan.is_cuda and out.is_cuda)):
+            raise hipabi.KlError("rate_scatter: tprob f32 [B, T], plan int64 [B, 4 + n_ctx], out f32 [n], contiguous, on the device")
+        with self._launch():
+            hipabi.check(self.lib.kl_rate_scatter(_ptr(tprob), _ptr(plan), B, T, int(n_ctx), _ptr(out), out.numel(),
+                                                  self._stream()), "kl_rate_scatter")
+        return out
+
+    def rate_text_bits(self, probs, offsets):
+        """kl_rate_text_bits: bits [n] (f64 DEVICE tensor) = per text -sum log2(max(p, 1e-99)) over all but its first character;
+        probs f32 DEVICE vector, offsets int64 DEVICE tensor [n + 1], ascending.  No synchronisation."""
+        torch = self.torch
+        if (probs.dtype != torch.float32 or offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 2
+                or not (probs.is_contiguous() and offsets.is_contiguous()) or not (probs.is_cuda and offsets.is_cuda)):
+            raise hipabi.KlError("rate_text_bits: probs f32 [n], offsets int64 [n_texts + 1], contiguous, on the device")
+        n = offsets.numel() - 1
+        with self._launch():
+            bits = torch.empty(n, dtype=torch.float64, device=self.device)
+            hipabi.check(self.lib.kl_rate_text_bits(_ptr(probs), _ptr(offsets), n, _ptr(bits), self._stream()),
+                         "kl_rate_text_bits")
+        return bits
+
     def rate_window_alts(self, idx, ctx, tgt, k):
         """`rate_window` delivering per position also what the model expected instead (kl_rate_window_alts): returns the DEVICE
         tensors tprob [B,T] f32 (what rate_window returns, bit for bit), alt_id [B,T,k] i32 and alt_p [B,T,k] f32 -- the k

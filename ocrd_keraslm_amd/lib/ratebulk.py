@@ -1,0 +1,159 @@
+"""Scheduler of bulk rating (`Rater.rate_batch(precision="bf16")`): many independent texts as plan rows over one id corpus.
+
+`ratebatch.plan` builds the `[B][T]` index arrays of every call on the host.  Here the ids of all texts lie end to end in ONE
+vector that is uploaded once (text i at offset o_i), and a call is described by what `kl_assemble_windows` reads: one int64
+row `[start, vlen, zero_col, zero_ctx, ctx_0 ..]` per stream.  The way back is `kl_rate_scatter` (a call's `[B][T]` target
+probabilities to the positions of their characters in a vector shaped like the corpus) and `kl_rate_text_bits` (one f64 sum
+per text over that vector).
+
+Rules of the plan:
+  * text i of n_i characters has n_i - 1 predictions; window w of a call of length T has start = o_i + done and
+    vlen = min(T, n_i - 1 - done), `done` being the predictions of the text's earlier windows;
+  * the windows of a text are consecutive calls of one row, and a row takes a new text only at a call boundary (its state is
+    zeroed there) -- as in `ratebatch.plan`; a row with nothing to do has vlen 0: idx 0, tgt -1, no target, no bits;
+  * texts of more than `length` predictions run at T = length, dealt longest first to the row that is free first;
+  * texts that fit one window are sorted by length and taken in groups of `streams`; a group runs at T = its longest text's
+    prediction count rounded up to a multiple of 32 (at least 3, at most `length`): few distinct (B, T) shapes, and a corpus
+    of 50-character lines does not run 256-step windows.
+
+`windows_host`, `scatter_host` and `text_bits_host` state in numpy what kl_assemble_windows, kl_rate_scatter and
+kl_rate_text_bits compute.  numpy only: the plan is built and tested without an engine.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+MIN_T = 3          # shorter windows fall off the persistent scans (engine.HipLM._padded_streams)
+ROUND_T = 32       # short-text groups: T is rounded up to a multiple of this
+
+
+class Call(object):
+    """One window call: T, the int64 plan rows [B, 4 + n_ctx] and reset [B] bool -- the rows whose state is zeroed before it."""
+
+    def __init__(self, T, rows, reset):
+        self.T, self.rows, self.reset = int(T), rows, reset
+
+    @property
+    def B(self):
+        return int(self.rows.shape[0])
+
+
+class Plan(object):
+    """What `plan` returns: calls (in order), offsets int64 [n + 1] (text i is corpus[offsets[i]:offsets[i + 1]]), sizes,
+    n_ctx, and per text (input order) its row, first call and number of windows (0: no prediction, row -1)."""
+
+    def __init__(self, calls, offsets, sizes, n_ctx, row, first, count):
+        self.calls, self.offsets, self.sizes, self.n_ctx = calls, offsets, sizes, n_ctx
+        self.row, self.first, self.count = row, first, count
+
+    @property
+    def n_calls(self):
+        return len(self.calls)
+
+    @property
+    def total(self):
+        return int(self.offsets[-1])
+
+
+def _rows(B, n_ctx):
+    rows = np.zeros((B, 4 + n_ctx), dtype=np.int64)
+    rows[:, 2:4] = -1          # (zero_col, zero_ctx: rating degrades nothing)
+    return rows
+
+
+def plan(sizes, contexts, length, streams):
+    """sizes: characters per text; contexts: one (clamped) context list per text; length: the longest window; streams: upper
+    limit of rows per call.  Returns a Plan (without calls if no text has a prediction)."""
+    sizes = np.asarray(sizes, dtype=np.int64).reshape(-1)
+    n = len(sizes)
+    length = int(length)
+    streams = max(1, int(streams))
+    n_ctx = len(contexts[0]) if n else 0
+    ctx = np.asarray(contexts, dtype=np.int64).reshape(n, n_ctx)
+    offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    preds = np.maximum(sizes - 1, 0)
+    row = np.full(n, -1, dtype=np.int64)
+    first = np.zeros(n, dtype=np.int64)
+    count = -(-preds // length)
+    calls = []
+    # texts of several windows: list scheduling at T = length, longest first
+    long_ = [int(i) for i in np.argsort(-count, kind="stable") if preds[i] > length]
+    if long_:
+        B = min(streams, len(long_))
+        free = np.zeros(B, dtype=np.int64)
+        for i in long_:
+            r = int(np.argmin(free))
+            row[i], first[i] = r, free[r]
+            free[r] += count[i]
+        for s in range(int(free.max())):
+            calls.append(Call(length, _rows(B, n_ctx), np.zeros(B, dtype=bool)))
+        for i in long_:
+            for w in range(int(count[i])):
+                c = calls[int(first[i]) + w]
+                done = w * length
+                c.rows[row[i], 0] = offsets[i] + done
+                c.rows[row[i], 1] = min(length, int(preds[i]) - done)
+                c.rows[row[i], 4:] = ctx[i]
+                c.reset[row[i]] = w == 0
+    # texts of one window: sorted by length, in groups of `streams`, each group as short as its longest text allows
+    short = [int(i) for i in np.argsort(preds, kind="stable") if 0 < preds[i] <= length]
+    for a in range(0, len(short), streams):
+        group = np.array(short[a:a + streams], dtype=np.int64)
+        T = -(-int(preds[group].max()) // ROUND_T) * ROUND_T
+        T = min(max(T, MIN_T), length)
+        rows = _rows(len(group), n_ctx)
+        rows[:, 0] = offsets[group]
+        rows[:, 1] = preds[group]
+        rows[:, 4:] = ctx[group]
+        row[group] = np.arange(len(group))
+        first[group] = len(calls)
+        calls.append(Call(T, rows, np.ones(len(group), dtype=bool)))
+    return Plan(calls, offsets, sizes, n_ctx, row, first, count)
+
+
+def windows_host(corpus, rows, T):
+    """what kl_assemble_windows makes of plan rows: (idx [B,T], ctx [B,T,n_ctx], tgt [B,T]) int32; positions outside the
+    corpus read as 0"""
+    corpus = np.asarray(corpus, dtype=np.int32)
+    rows = np.asarray(rows, dtype=np.int64)
+    B, n_ctx = rows.shape[0], rows.shape[1] - 4
+    t = np.arange(T, dtype=np.int64)[None, :]
+    start = rows[:, 0:1]
+    vlen = np.clip(rows[:, 1:2], 0, T)
+    live = t < vlen
+
+    def read(at):
+        ok = (at >= 0) & (at < len(corpus))
+        return np.where(ok, corpus[np.where(ok, at, 0)] if len(corpus) else 0, 0)
+
+    zero_col = np.where((rows[:, 2:3] >= 0) & (rows[:, 2:3] < T), rows[:, 2:3], -1)
+    idx = np.where(live & (t != zero_col), read(start + t), 0).astype(np.int32)
+    tgt = np.where(live, read(start + t + 1), -1).astype(np.int32)
+    keep = np.arange(n_ctx)[None, :] != rows[:, 3:4]
+    ctx = (live[:, :, None] * (rows[:, 4:] * keep)[:, None, :]).astype(np.int32)
+    return idx, ctx, tgt
+
+
+def scatter_host(tprob, rows, out):
+    """what kl_rate_scatter does: out[start + 1 + t] = tprob[b][t] for t < min(vlen, T), inside out; in place, returns out"""
+    tprob = np.asarray(tprob)
+    B, T = tprob.shape
+    n = len(out)
+    for b in range(B):
+        start, vlen = int(rows[b, 0]), int(min(max(rows[b, 1], 0), T))
+        for t in range(vlen):
+            g = start + 1 + t
+            if 0 <= g < n:
+                out[g] = tprob[b, t]
+    return out
+
+
+def text_bits_host(probs, offsets):
+    """what kl_rate_text_bits computes: per text -sum log2(max(p, 1e-99)) over all but its first character, f64"""
+    probs = np.asarray(probs)
+    out = np.zeros(len(offsets) - 1, dtype=np.float64)
+    for i in range(len(out)):
+        p = probs[int(offsets[i]) + 1:int(offsets[i + 1])].astype(np.float64)
+        if len(p):
+            out[i] = -np.log2(np.maximum(p, 1e-99)).sum()
+    return out

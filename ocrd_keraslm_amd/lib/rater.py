@@ -39,7 +39,7 @@ from random import shuffle
 
 import numpy as np
 
-from . import genbeam, gensample, lattice_beam, modelio, ratebatch, segments, streams, windows
+from . import genbeam, gensample, lattice_beam, modelio, ratebatch, ratebulk, segments, streams, windows
 from .node import Node
 
 PREC_BF16 = 1
@@ -807,16 +807,27 @@ class Rater(object):
                 break
         return probs
 
-    def rate_batch(self, texts, contexts=None, streams=64, want_probs=True):
+    def rate_batch(self, texts, contexts=None, streams=64, want_probs=True, precision="split"):
         '''Rate many INDEPENDENT texts at once: `probs[i]` (float32 array, one entry per character of the normalised
         text) is what `self.model.reset_states(1); self.rate(texts[i], contexts[i])` returns, `bits[i]` (float64) is
         -sum(log2(max(p, 1e-99))) over `probs[i][1:]`; both in input order.  contexts: None, one context list for all
         texts, or one per text.  Up to `streams` texts share a window call, one per row (ratebatch.py); the HIP engine
         delivers one float per character (`rate_window`), or -- want_probs=False, which returns (None, bits) -- one
         double per text.  Unlike `rate`, a batch call neither continues the implicit state of earlier `rate` calls
-        nor leaves one behind: afterwards the state is a freshly reset single row.'''
+        nor leaves one behind: afterwards the state is a freshly reset single row.
+
+        precision: "split" (default) rates in the split-precision inference kernels, ~f32 accuracy.  "bf16" is bulk rating
+        for whole corpora: the windows run on the bf16 training forward (`rate_window_bulk`: thousands of streams per
+        launch; probabilities within 1e-2 of the reference instead of 1e-3), the ids of all texts and the whole plan are
+        uploaded once (ratebulk.py), short texts run in windows as short as they are, and with want_probs=False only the
+        bits leave the device.  Same return contract; a stateless rater raises ValueError.  The next split-precision
+        call restores split precision by itself.'''
         assert self.status > 1
         assert self.incremental is False
+        if precision not in ("split", "bf16"):
+            raise ValueError('precision must be "split" or "bf16" (got %r)' % (precision,))
+        if precision == "bf16" and not self.stateful:
+            raise ValueError('rate_batch(precision="bf16") needs a stateful rater: bulk rating runs stateful windows')
         texts = list(texts)
         n = len(texts)
         if contexts is None or len(contexts) == 0:
@@ -826,8 +837,11 @@ class Rater(object):
         else:
             assert len(contexts) == n, "one context list per text"
             contexts = [list(c) if (c is not None and len(c)) else self.underspecify_contexts() for c in contexts]
-        self._ensure_precision()
         lm = self.model
+        if precision == "bf16" and hasattr(lm, 'rate_window_bulk'):
+            return self._rate_batch_bulk(texts, contexts, streams, want_probs)
+        # (an engine without rate_window_bulk -- the tests' CPU double -- runs the ordinary plan)
+        self._ensure_precision()
         bits = np.zeros(n, dtype=np.float64)
         if not self.stateful:
             # (the stateless rater's windows are batches of 128 already: the loop itself)
@@ -862,6 +876,47 @@ class Rater(object):
         if not want_probs:
             return None, bits
         return [plan.text_probs(i, picked) for i in range(n)], bits
+
+    def _rate_batch_bulk(self, texts, contexts, streams, want_probs):
+        '''rate_batch on the bf16 training forward: one upload (ids, plan rows and reset masks of all calls), per call
+        assemble_windows -> rate_window_bulk -> rate_scatter on the device, then one rate_text_bits and one transfer'''
+        lm = self.model
+        torch = lm.torch
+        n = len(texts)
+        texts = [windows.normalize(t) for t in texts]
+        ids = [windows.encode(t, self.mapping[0], self._unmapped_input) for t in texts]
+        sizes = [len(a) for a in ids]
+        plan = ratebulk.plan(sizes, [windows.clamp_context(c) for c in contexts], self.length, streams)
+        bits = np.zeros(n, dtype=np.float64)
+        if not plan.calls:       # (nothing but empty texts and single characters)
+            lm.reset_states(1)
+            return ([np.ones(len(t), dtype=np.float32) for t in texts] if want_probs else None), bits
+        n_ctx = plan.n_ctx
+        bounds = np.concatenate([[0], np.cumsum([c.B for c in plan.calls])])
+        corpus = torch.from_numpy(np.concatenate(ids).astype(np.int32)).to(lm.device)
+        rows = torch.from_numpy(np.concatenate([c.rows for c in plan.calls])).to(lm.device)
+        reset = torch.from_numpy(np.concatenate([c.reset for c in plan.calls])).to(lm.device)
+        offsets = torch.from_numpy(plan.offsets).to(lm.device)
+        out = torch.ones(plan.total, dtype=torch.float32, device=lm.device)      # (1.0: a text's first character)
+        B = None
+        for s, call in enumerate(plan.calls):
+            a, b = int(bounds[s]), int(bounds[s + 1])
+            if call.B != B:
+                B = call.B
+                lm.reset_states(B)      # (another number of rows: all of them start from zero)
+            elif call.reset.any():
+                lm.reset_states_where(reset[a:b])
+            x, z, y = lm.assemble_windows(corpus, rows[a:b], call.T, n_ctx)
+            p = lm.rate_window_bulk(x, z, y, want_probs=True)
+            lm.rate_scatter(p, rows[a:b], n_ctx, out)
+        bits_d = lm.rate_text_bits(out, offsets)
+        bits[:] = _np(bits_d)
+        lm.rate_bits_read(reset=True)      # (the per-stream sums are not used here; also raises on a timed-out scan hand-off)
+        lm.reset_states(1)
+        if not want_probs:
+            return None, bits
+        flat = _np(out)
+        return [flat[int(plan.offsets[i]):int(plan.offsets[i + 1])].copy() for i in range(n)], bits
 
     def _run_rate_plan(self, plan, bits, want_probs):
         '''the window calls of a ratebatch.Plan on the HIP engine: fills bits (per text) from the device's f64 sums

@@ -4,6 +4,8 @@
 Same commands, options, defaults and outputs as the reference CLI: train, test,
 apply, generate, print-history, print-charset, prune-charset and the three plot-* views of the
 embeddings (matplotlib / scikit-learn imported on use).
+Additional command `score`: bits per character and perplexity of every DATA file, all files rated at once
+(Rater.rate_batch; --precision bf16 takes the bulk path on the training forward).
 Additional options on `train`: --streams (stateful streams per GPU, default 1 = the
 reference's batching) and --segment-streams (with fewer files than streams, cut the files
 into contiguous segments on window boundaries, one list of segments per stream).  Under `python -m torch.distributed.run` training is
@@ -20,7 +22,7 @@ import click
 
 from .. import lib
 
-COMMAND_ORDER = ['train', 'test', 'apply', 'generate', 'print-history', 'print-charset', 'prune-charset',
+COMMAND_ORDER = ['train', 'test', 'score', 'apply', 'generate', 'print-history', 'print-charset', 'prune-charset',
                  'plot-char-embeddings-similarity', 'plot-context-embeddings-similarity', 'plot-context-embeddings-projection']
 
 
@@ -159,6 +161,38 @@ def test(model, data):
     """Apply a language model to DATA files and compute its overall perplexity."""
     rater = _load(model)
     click.echo(rater.test(_open_all(data)))
+
+
+@cli.command(short_help='get bits per character and perplexity of every file')
+@click.option('-m', '--model', default="model.h5", show_default=True, help='model file', type=click.Path(dir_okay=False, exists=True))
+@click.option('-s', '--streams', default=64, show_default=True, help='files rated in lockstep, one per row of a window call',
+              type=click.IntRange(min=1, max=4096))
+@click.option('--precision', default='split', show_default=True, type=click.Choice(['split', 'bf16']),
+              help='split: the inference kernels, ~f32 accuracy; bf16: bulk rating on the training forward '
+                   '(probabilities within 1e-2, several times the throughput on many files)')
+@click.argument('data', nargs=-1, type=click.Path(exists=True, dir_okay=True, file_okay=True))
+def score(model, streams, precision, data):
+    """Apply a language model to DATA files and print one JSON line per file:
+       characters, bits per character and perplexity.
+
+       Every file is rated on its own, from a zero state (unlike `test`, which carries the
+       state from file to file); its context comes from its name, as in `test` and `train`.
+    """
+    from ..lib import windows
+    rater = _load(model)
+    names, texts, contexts = [], [], []
+    for file in _open_all(data):
+        with file:
+            texts.append(windows.normalize(file.read()))
+        names.append(file.name)
+        contexts.append(windows.context_from_filename(file.name))
+    if not texts:
+        return
+    _, bits = rater.rate_batch(texts, contexts, streams=streams, want_probs=False, precision=precision)
+    for name, text, total in zip(names, texts, bits):
+        per_char = float(total) / max(len(text) - 1, 1)
+        click.echo(json.dumps({"file": name, "chars": len(text), "bits_per_char": per_char, "perplexity": 2.0 ** per_char},
+                              ensure_ascii=False))
 
 
 @cli.command(short_help='sample characters from language model')

@@ -11,6 +11,13 @@ buffers allocated), then the legs are alternated a, b, c, a, b, c, ... in the sa
 a leg is repeated inside one timing until it lasts at least `--min-seconds`.  Reported: the median chars/s of each
 leg and the spread (max - min) / median of its repeats.  One JSON line on stdout, also written to --out.
 
+  python tools/bench_rate_batch.py --bulk [--out profiles/rate_bulk.json] [--repeats 5]
+
+--bulk compares the two precisions of `rate_batch` on corpus-sized inputs, cfg2 size only: 1024 documents of 2048
+characters at 256, 1024 and 3072 streams, and 20 000 lines of 30 to 90 characters at 1024 streams.  Legs: "split"
+(rate_batch as ever), "bf16" (precision="bf16": bulk rating on the training forward) and both with want_probs=False;
+warmed up, alternated, median of --repeats (at least 5) timings; also the largest |p_bf16 - p_split| over all characters.
+
 Needs the GPU: there is no fallback.
 """
 import argparse
@@ -64,9 +71,59 @@ def timed(fn, sync, inner):
     return (time.perf_counter() - t0) / inner
 
 
+def bulk_sets():
+    rng = np.random.default_rng(2025)
+    docs = documents(rng, [2048] * 1024)
+    lines = documents(rng, rng.integers(30, 91, 20000))
+    return [("1024x2048@256", docs, 256), ("1024x2048@1024", docs, 1024), ("1024x2048@3072", docs, 3072),
+            ("20000lines@1024", lines, 1024)]
+
+
+def bulk(args, sync):
+    """split against bf16 on the same texts"""
+    import torch
+    repeats = max(5, args.repeats)
+    rater = make_rater(**MODELS["cfg2"])
+    rater.model.init_weights(seed=3, emb_std=0.3)      # (embeddings large enough for peaked distributions: |dp| means something)
+    context = [17]
+    result = {"tool": "bench_rate_batch --bulk", "device": torch.cuda.get_device_name(0), "repeats": repeats,
+              "model": dict(MODELS["cfg2"], voc_size=len(ALPHABET) + 1), "sets": {}}
+    for name, docs, streams in bulk_sets():
+        chars = sum(len(d) for d in docs)
+        legs = {}
+        for prec in ("split", "bf16"):
+            legs[prec] = lambda prec=prec: rater.rate_batch(docs, context, streams=streams, precision=prec)
+            legs[prec + "_bits"] = lambda prec=prec: rater.rate_batch(docs, context, streams=streams, want_probs=False,
+                                                                      precision=prec)
+        p_split, _ = legs["split"]()
+        p_bf16, _ = legs["bf16"]()
+        gap = max(float(np.abs(a - b).max()) for a, b in zip(p_split, p_bf16) if len(a))
+        inner = {}
+        for leg, fn in legs.items():
+            fn()
+            inner[leg] = max(1, int(np.ceil(args.min_seconds / max(timed(fn, sync, 1), 1e-6))))
+        times = dict((leg, []) for leg in legs)
+        for _ in range(repeats):
+            for leg, fn in legs.items():
+                times[leg].append(timed(fn, sync, inner[leg]))
+        row = {"documents": len(docs), "chars": chars, "streams": streams, "max_abs_dp": gap}
+        for leg, ts in times.items():
+            med = statistics.median(ts)
+            row[leg] = {"chars_per_s": chars / med, "seconds": med, "spread": (max(ts) - min(ts)) / med,
+                        "runs_per_timing": inner[leg]}
+        row["speedup"] = row["bf16"]["chars_per_s"] / row["split"]["chars_per_s"]
+        row["speedup_bits"] = row["bf16_bits"]["chars_per_s"] / row["split_bits"]["chars_per_s"]
+        result["sets"][name] = row
+        print("%-16s split %10.0f  bf16 %10.0f (%.2fx)  bits only %10.0f / %10.0f (%.2fx) chars/s  max |dp| %.3g" % (
+            name, row["split"]["chars_per_s"], row["bf16"]["chars_per_s"], row["speedup"], row["split_bits"]["chars_per_s"],
+            row["bf16_bits"]["chars_per_s"], row["speedup_bits"], gap), file=sys.stderr)
+    return result
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rate_batch.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/rate_batch.json, with --bulk profiles/rate_bulk.json")
+    ap.add_argument("--bulk", action="store_true", help="split against bf16 precision on corpus-sized inputs")
     ap.add_argument("--streams", type=int, default=64)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--min-seconds", type=float, default=0.3)
@@ -76,6 +133,10 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("bench_rate_batch: no GPU visible (the rater has no CPU path)")
     sync = torch.cuda.synchronize
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "rate_bulk.json" if args.bulk else "rate_batch.json")
+    if args.bulk:
+        return emit(bulk(args, sync), args.out)
     sets = document_sets()
     result = {"tool": "bench_rate_batch", "device": torch.cuda.get_device_name(0), "streams": args.streams,
               "repeats": args.repeats, "models": {}}
@@ -114,10 +175,14 @@ def main():
                 model, name, row["loop"]["chars_per_s"], row["rate_batch"]["chars_per_s"], row["speedup"],
                 row["rate_batch_bits"]["chars_per_s"], row["speedup_bits"]), file=sys.stderr)
         result["models"][model] = dict(MODELS[model], voc_size=len(ALPHABET) + 1, sets=rows)
+    emit(result, args.out)
+
+
+def emit(result, out):
     line = json.dumps(result)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
             f.write(line + "\n")
     print(line)
 

@@ -3,7 +3,7 @@
 each other through the carried state / traceback, rate.py:150-186, 263-265), so they are dealt round-robin to one
 process per GPU and NOTHING is exchanged between the processes ("no collectives").
 
-  python tools/rescore_shard.py --model model.h5 --gpus 8 [--mode rate|generate] [--batch N] [--out DIR] FILE_OR_DIR ...
+  python tools/rescore_shard.py --model model.h5 --gpus 8 [--mode rate|generate] [--batch N [--bf16]] [--out DIR] FILE_OR_DIR ...
 
 mode rate      per document: Rater.rate over the whole text (context = ceil(year / 10) from `author_title_year.txt`
                names, rating.py:993-999), state reset between documents; writes <out>/<name>.json with the mean
@@ -11,6 +11,8 @@ mode rate      per document: Rater.rate over the whole text (context = ceil(year
                --batch N (default 0: one document after the other): a worker rates its documents N at a time as the
                rows of shared windows (Rater.rate_batch, one document per row, the next one moves up when a row is
                done) and fetches one number per document from the GPU; same files, same figures
+               --bf16 (with --batch): bulk rating on the bf16 training forward (rate_batch(precision="bf16")): the documents'
+               ids are uploaded once and every window call is planned on the device; probabilities within 1e-2 instead of 1e-3
 mode generate  per document: its first line is the prompt; Rater.generate continues it by 64 characters, 3 variants
 
 The parent only starts the workers (each with ONE visible GPU, HIP_VISIBLE_DEVICES) and sums their reports; it never
@@ -52,7 +54,8 @@ def rate_batched(rater, paths, args):
             text = windows.normalize(f.read())
         if len(text) >= 2:
             docs.append((os.path.basename(path), text, windows.context_from_filename(path)))
-    _, total = rater.rate_batch([d[1] for d in docs], [d[2] for d in docs], streams=args.batch, want_probs=False)
+    _, total = rater.rate_batch([d[1] for d in docs], [d[2] for d in docs], streams=args.batch, want_probs=False,
+                                 precision="bf16" if args.bf16 else "split")
     for (name, text, _), doc_bits in zip(docs, total):
         bits = float(doc_bits) / max(len(text) - 1, 1)
         result = {"document": name, "chars": len(text), "bits_per_char": bits, "perplexity": 2.0 ** bits}
@@ -109,6 +112,7 @@ def main():
     ap.add_argument("--out", default="rescored")
     ap.add_argument("--batch", type=int, default=0,
                     help="mode rate: documents rated at once per worker, as rows of shared windows (0: one after the other)")
+    ap.add_argument("--bf16", action="store_true", help="with --batch: bulk rating on the bf16 training forward")
     ap.add_argument("--worker", type=int, default=-1, help=argparse.SUPPRESS)
     ap.add_argument("data", nargs="+")
     args = ap.parse_args()
@@ -132,7 +136,7 @@ def main():
         if same_gpu:
             env["HIP_VISIBLE_DEVICES"] = env["CUDA_VISIBLE_DEVICES"] = "0"
         cmd = [sys.executable, os.path.abspath(__file__), "--model", args.model, "--gpus", str(args.gpus), "--mode", args.mode,
-               "--batch", str(args.batch), "--out", args.out, "--worker", str(g)] + args.data
+               "--batch", str(args.batch), "--out", args.out, "--worker", str(g)] + (["--bf16"] if args.bf16 else []) + args.data
         p = subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, text=True)
         if same_gpu:
             # one after the other: the persistent scans assume the GPU to themselves (co-resident workgroups), two
