@@ -15,6 +15,7 @@
  *   Rater.rate, :493-529, for many texts at once             kl_rate_window (one text per stream, target-only delivery)
  *   ... with the model's top-K characters and the target's rank  kl_rate_window_alts
  *   ... for a whole corpus, on the training forward (bf16)    kl_rate_window_bulk, kl_rate_scatter, kl_rate_text_bits
+ *   ... with alternatives, and the suspect positions picked out  kl_rate_window_alts_bulk, kl_rate_scatter_alts, kl_rate_select
  *   model.predict_on_batch, stateful (1,1) step, :566        kl_forward_window with T = 1
  *   model.predict_on_batch, incremental + states, :631       kl_step_batch
  *   ... once per character of a lattice edge, :796-851       kl_walk_batch_host (all characters of all hypotheses, one call)
@@ -192,6 +193,55 @@ int kl_rate_window_bulk(kl_handle* h, int B, int T, const int32_t* idx, const in
  * KL_ERR_ARG for null pointers, B, T or n_texts < 1, n_ctx outside 0 .. 8, misaligned pointers.  One launch each on `stream`. */
 int kl_rate_scatter(const float* tprob, const int64_t* plan, int B, int T, int n_ctx, float* out, size_t n_out, void* stream);
 int kl_rate_text_bits(const float* probs, const int64_t* offsets, int n_texts, double* bits, void* stream);
+
+/* Bulk rating with alternatives: kl_rate_window_alts' delivery behind kl_rate_window_bulk's recurrence and logits.
+ * Arguments, outputs (tprob, alt_id, alt_p, rank, bits, status), the order within a position and the rule for positions
+ * without a target are those of kl_rate_window_alts; tgt, alt_id and alt_p are required, 1 <= K <= KL_RATE_ALTS_MAX.  tprob,
+ * the state advance and bits are bit for bit those of kl_rate_window_bulk on the same inputs; where 0 <= rank < K,
+ * alt_id[rank] == tgt and alt_p[rank] == tprob bit for bit.  KL_ERR_STATE unless the handle is prepared in KL_PREC_BF16, and
+ * after kl_set_window_mode(h, 1); KL_ERR_WORKSPACE below kl_rate_alts_bulk_workspace_bytes(h, B, T, K) =
+ * kl_rate_bulk_workspace_bytes(h, B, T) plus the staging area of the results (0 for B, T < 1 or K outside its range);
+ * KL_ERR_ARG as in kl_rate_window_alts; all before anything is launched.  The id rule of the training forward at width 512
+ * holds here too (see kl_forward_window). */
+size_t kl_rate_alts_bulk_workspace_bytes(const kl_handle* h, int B, int T, int K);
+int kl_rate_window_alts_bulk(kl_handle* h, int B, int T, int K, const int32_t* idx, const int32_t* ctx, const int32_t* tgt,
+                             float* states, float* tprob, int32_t* alt_id, float* alt_p, int32_t* rank, double* bits,
+                             float* status, void* ws, size_t ws_bytes, void* stream);
+
+/* kl_rate_scatter for all four results of one kl_rate_window_alts(_bulk) call.  No handle.  tprob, rank (device [B][T]) and
+ * alt_id, alt_p (device [B][T][K]) as the call delivered them for the batch of `plan` (device int64 [B][4 + n_ctx]).  For
+ * 0 <= t < min(vlen, T) with 0 <= g = start + 1 + t < n_out:  out_prob[g] = tprob[b][t], out_rank[g] = rank[b][t],
+ * out_alt_id[g][0 .. K-1] = alt_id[b][t][0 .. K-1], out_alt_p[g][0 .. K-1] = alt_p[b][t][0 .. K-1]  (out_prob, out_rank:
+ * device [n_out]; out_alt_id, out_alt_p: device [n_out][K]).  Bit copies; nothing else is written, a row with vlen <= 0
+ * writes nothing.  All pointers are required.  KL_ERR_ARG for null pointers, B or T < 1, K outside 1 .. KL_RATE_ALTS_MAX,
+ * n_ctx outside 0 .. 8, misaligned pointers.  One launch on `stream`. */
+int kl_rate_scatter_alts(const float* tprob, const int32_t* rank, const int32_t* alt_id, const float* alt_p, const int64_t* plan,
+                         int B, int T, int K, int n_ctx, float* out_prob, int32_t* out_rank, int32_t* out_alt_id,
+                         float* out_alt_p, size_t n_out, void* stream);
+
+/* Ordered selection over corpus-order results (what kl_rate_scatter_alts filled): the suspect positions.  No handle.
+ * probs (device f32 [n]), rank (device int32 [n]), alt_id (device int32 [n][K]), alt_p (device f32 [n][K]).  Position j
+ * (0 <= j < n) is selected iff  rank[j] >= min_rank && probs[j] <= max_prob  -- an f32 comparison, so a NaN probability is
+ * never selected; min_rank >= 0 is required, so rank -1 (no prediction: a text's first character) never is either.
+ *   count   (device int64 [1])  the number of selected positions, whatever `capacity` is;
+ *   for i < min(count, capacity), entry i describes the i-th selected position in ascending j:
+ *   sel_pos (device int64 [capacity]) = j;  sel_prob (f32 [capacity]), sel_rank (int32 [capacity]), sel_alt_id (int32
+ *   [capacity][K]) and sel_alt_p (f32 [capacity][K]) are bit copies of probs[j], rank[j], alt_id[j][..], alt_p[j][..].
+ * Entries from min(count, capacity) on are not written.  capacity == 0 allows null sel_* pointers: the counting call.  The
+ * order does not depend on scheduling and two calls on the same input give identical output: every workgroup counts the
+ * selected among its KL_RATE_SELECT_BLOCK consecutive positions, ONE workgroup of KL_RATE_SELECT_SCAN_THREADS threads turns
+ * the counts into exclusive offsets (in rounds, for any number of blocks) and the total, and a third launch recomputes the
+ * flags and places the records (the counting call stops after the second) -- plain launches on `stream`, no atomics, no
+ * workgroup waits for another.  ws: device scratch of kl_rate_select_workspace_bytes(n) bytes (one int64 per block, 0 for
+ * n < 1 or n > 2^40), 8-byte aligned.  KL_ERR_ARG for null inputs, count or ws, n < 1, K outside 1 .. KL_RATE_ALTS_MAX,
+ * min_rank < 0, a NaN max_prob, null sel_* with capacity > 0, misaligned pointers; KL_ERR_WORKSPACE if ws_bytes is too
+ * small; both before any launch. */
+#define KL_RATE_SELECT_BLOCK 1024
+#define KL_RATE_SELECT_SCAN_THREADS 256
+size_t kl_rate_select_workspace_bytes(size_t n);
+int kl_rate_select(const float* probs, const int32_t* rank, const int32_t* alt_id, const float* alt_p, size_t n, int K,
+                   float max_prob, int min_rank, size_t capacity, int64_t* sel_pos, float* sel_prob, int32_t* sel_rank,
+                   int32_t* sel_alt_id, float* sel_alt_p, int64_t* count, void* ws, size_t ws_bytes, void* stream);
 
 /* One training batch, forward + backward (rating.py:292-298 -> train_on_batch):
  * writes the gradient of (mean CE + embedding regularisers, rating.py:187-246)

@@ -2600,30 +2600,38 @@ extern "C" size_t kl_rate_alts_workspace_bytes(const kl_handle* h, int B, int T,
   return carve_window(h, nullptr, B, T, 0, nullptr) + carve_alts(nullptr, (size_t)B * T, K, nullptr);
 }
 
-extern "C" int kl_rate_window_alts(kl_handle* h, int B, int T, int K, const int32_t* idx, const int32_t* ctx,
-                                   const int32_t* tgt, float* states, float* tprob, int32_t* alt_id, float* alt_p,
-                                   int32_t* rank, double* bits, float* status, void* ws, size_t ws_bytes, void* stream) {
+namespace {
+
+// kl_rate_window_alts (training = 0: window_logits on the inference layout, any prepared precision, graph kind 3) and
+// kl_rate_window_alts_bulk (training = 1: window_logits_training on the training layout, bf16 only, graph kind 5) differ in
+// nothing else: the selection, the bits and the staging area behind the window's workspace are the same
+int rate_window_alts_impl(kl_handle* h, int training, int B, int T, int K, const int32_t* idx, const int32_t* ctx,
+                          const int32_t* tgt, float* states, float* tprob, int32_t* alt_id, float* alt_p, int32_t* rank,
+                          double* bits, float* status, void* ws, size_t ws_bytes, void* stream) {
   if (!h || !idx || !states || !ws || B < 1 || T < 1) return KL_ERR_ARG;
   if (h->cfg.n_ctx > 0 && !ctx) return KL_ERR_ARG;
   if (!tgt || !alt_id || !alt_p || K < 1 || K > KL_RATE_ALTS_MAX) return KL_ERR_ARG;
-  if (!h->precision || h->last_only) return KL_ERR_STATE;      // (as kl_rate_window)
+  if ((training ? h->precision != KL_PREC_BF16 : !h->precision) || h->last_only) return KL_ERR_STATE;      // (as kl_rate_window / _bulk)
   hipStream_t s = (hipStream_t)stream;
   WindowWs w;
   AltsWs a;
   const size_t BT = (size_t)B * T;
-  const size_t n_window = carve_window(h, ws, B, T, 0, &w);      // (a multiple of 256: the staging area starts aligned)
+  const size_t n_window = carve_window(h, nullptr, B, T, training, nullptr);      // (a multiple of 256: the staging area starts aligned)
   if (ws_bytes < n_window + carve_alts(nullptr, BT, K, nullptr)) return KL_ERR_WORKSPACE;
+  carve_window(h, ws, B, T, training, &w);
   carve_alts(reinterpret_cast<unsigned char*>(ws) + n_window, BT, K, &a);
   KL_TRY(hip_ok(hipMemcpyAsync(w.s_idx, idx, BT * sizeof(int), hipMemcpyDeviceToDevice, s)));
   if (h->cfg.n_ctx > 0)
     KL_TRY(hip_ok(hipMemcpyAsync(w.s_ctx, ctx, BT * h->cfg.n_ctx * sizeof(int), hipMemcpyDeviceToDevice, s)));
   KL_TRY(hip_ok(hipMemcpyAsync(w.s_tgt, tgt, BT * sizeof(int), hipMemcpyDeviceToDevice, s)));
   // (baked into the captured launches: K, states, status, bits and the workspace -- all in the key; tprob, alt_id, alt_p and
-  // rank are staged, and which of the optional ones the caller takes is in the key's flags)
-  kl_handle::GraphKey key{3, B, T, (tprob ? 1 : 0) | (bits ? 2 : 0) | (rank ? 4 : 0) | (K << 3), h->precision, states, status, ws, bits, 0};
+  // rank are staged, and which of the optional ones the caller takes is in the key's flags.  A kind per layout: the same
+  // arrays may serve both calls)
+  kl_handle::GraphKey key{training ? 5 : 3, B, T, (tprob ? 1 : 0) | (bits ? 2 : 0) | (rank ? 4 : 0) | (K << 3), h->precision, states, status, ws, bits, training};
   KL_TRY(run_graphed(h, key, s, [&]() {
     const int V = h->cfg.voc_size;
-    KL_TRY(window_logits(h, B, T, w.s_idx, w.s_ctx, states, w, s));
+    KL_TRY(training ? window_logits_training(h, B, T, w.s_idx, w.s_ctx, states, w, s)
+                    : window_logits(h, B, T, w.s_idx, w.s_ctx, states, w, s));
     KL_TRY(kl_launch_rate_topk(w.logits, V, B * T, V, w.s_tgt, B, T, K, a.tprob, a.alt_id, a.alt_p, a.rank, s));
     if (bits) KL_TRY(kl_launch_rate_bits(a.tprob, w.s_tgt, B, T, bits, s));
     if (status) hipLaunchKernelGGL(scan_status_kernel, dim3(1), dim3(64), 0, s, w.scan_status, status);
@@ -2634,6 +2642,28 @@ extern "C" int kl_rate_window_alts(kl_handle* h, int B, int T, int K, const int3
   KL_TRY(hip_ok(hipMemcpyAsync(alt_p, a.alt_p, BT * K * sizeof(float), hipMemcpyDeviceToDevice, s)));
   if (rank) KL_TRY(hip_ok(hipMemcpyAsync(rank, a.rank, BT * sizeof(int), hipMemcpyDeviceToDevice, s)));
   return 0;
+}
+
+}  // namespace
+
+extern "C" int kl_rate_window_alts(kl_handle* h, int B, int T, int K, const int32_t* idx, const int32_t* ctx,
+                                   const int32_t* tgt, float* states, float* tprob, int32_t* alt_id, float* alt_p,
+                                   int32_t* rank, double* bits, float* status, void* ws, size_t ws_bytes, void* stream) {
+  return rate_window_alts_impl(h, 0, B, T, K, idx, ctx, tgt, states, tprob, alt_id, alt_p, rank, bits, status, ws, ws_bytes, stream);
+}
+
+// ---- bulk rating with alternatives: kl_rate_window_alts' delivery on the training forward ----------------------------------
+// kl_rate_window_bulk's recurrence and logits (window_logits_training on a training-size workspace), then the selection and
+// the bits of kl_rate_window_alts; the results are staged behind the training window's workspace as carve_alts lays them out.
+extern "C" size_t kl_rate_alts_bulk_workspace_bytes(const kl_handle* h, int B, int T, int K) {
+  if (!h || B < 1 || T < 1 || K < 1 || K > KL_RATE_ALTS_MAX) return 0;
+  return carve_window(h, nullptr, B, T, 1, nullptr) + carve_alts(nullptr, (size_t)B * T, K, nullptr);
+}
+
+extern "C" int kl_rate_window_alts_bulk(kl_handle* h, int B, int T, int K, const int32_t* idx, const int32_t* ctx,
+                                        const int32_t* tgt, float* states, float* tprob, int32_t* alt_id, float* alt_p,
+                                        int32_t* rank, double* bits, float* status, void* ws, size_t ws_bytes, void* stream) {
+  return rate_window_alts_impl(h, 1, B, T, K, idx, ctx, tgt, states, tprob, alt_id, alt_p, rank, bits, status, ws, ws_bytes, stream);
 }
 
 extern "C" int kl_train_window(kl_handle* h, int B, int T, const int32_t* idx, const int32_t* ctx, const int32_t* tgt,

@@ -1,11 +1,12 @@
-// Results of bulk rating in corpus order (kl_rate_scatter, kl_rate_text_bits).
+// Results of bulk rating in corpus order (kl_rate_scatter, kl_rate_scatter_alts, kl_rate_text_bits).
 //
 // Bulk rating (Rater.rate_batch, precision "bf16") keeps the ids of all texts in one device vector, as stateful training
 // does, and describes a window call by the plan rows kl_assemble_windows reads.  These two kernels are the way back:
 // rate_scatter puts the [B][T] target probabilities of one call where their characters stand in that vector -- the
 // prediction made at corpus position start + t is about the character at start + t + 1 --, and rate_text_bits sums
 // -log2(max(p, 1e-99)) (rating.py:531-576) per text over the finished vector, in f64 and in a fixed order, as rate_bits_kernel
-// (rate_pick.hip) does per stream.  Neither depends on a model: no handle.
+// (rate_pick.hip) does per stream.  rate_scatter_alts is rate_scatter for the four results of a window with alternatives
+// (kl_rate_window_alts_bulk).  None depends on a model: no handle.
 #include "keraslm_hip.h"
 #include "kl_common.h"
 
@@ -25,6 +26,40 @@ __global__ void __launch_bounds__(256) rate_scatter_kernel(const uint32_t* __res
   for (int t = threadIdx.x; t < vlen; t += blockDim.x) {
     const long long g = start + 1 + t;
     if (g >= 0 && g < n_out) out[g] = p[t];
+  }
+}
+
+// one workgroup per stream, all four results of a call: the [B][T] planes as rate_scatter_kernel moves them, the [B][T][K]
+// planes element by element -- K words per position, and consecutive positions of a row are consecutive in the corpus, so that
+// a row's words stay contiguous on both sides
+__global__ void __launch_bounds__(256) rate_scatter_alts_kernel(const uint32_t* __restrict__ tprob,
+                                                                const uint32_t* __restrict__ rank,
+                                                                const uint32_t* __restrict__ alt_id,
+                                                                const uint32_t* __restrict__ alt_p,
+                                                                const long long* __restrict__ plan, int T, int K, int n_ctx,
+                                                                uint32_t* __restrict__ out_prob, uint32_t* __restrict__ out_rank,
+                                                                uint32_t* __restrict__ out_alt_id,
+                                                                uint32_t* __restrict__ out_alt_p, long long n_out) {
+  const int b = blockIdx.x;
+  const long long* row = plan + (long long)b * (4 + n_ctx);
+  const long long start = row[0], vl = row[1];
+  const int vlen = vl < 0 ? 0 : (vl > T ? T : (int)vl);
+  const long long at = (long long)b * T;
+  for (int t = threadIdx.x; t < vlen; t += blockDim.x) {
+    const long long g = start + 1 + t;
+    if (g >= 0 && g < n_out) {
+      out_prob[g] = tprob[at + t];
+      out_rank[g] = rank[at + t];
+    }
+  }
+  for (int e = threadIdx.x; e < vlen * K; e += blockDim.x) {
+    const int t = e / K;
+    const long long g = start + 1 + t;
+    if (g >= 0 && g < n_out) {
+      const long long to = g * K + (e - t * K);
+      out_alt_id[to] = alt_id[at * K + e];
+      out_alt_p[to] = alt_p[at * K + e];
+    }
   }
 }
 
@@ -58,6 +93,27 @@ extern "C" int kl_rate_scatter(const float* tprob, const int64_t* plan, int B, i
   hipLaunchKernelGGL(rate_scatter_kernel, dim3(B), dim3(threads), 0, static_cast<hipStream_t>(stream),
                      reinterpret_cast<const uint32_t*>(tprob), reinterpret_cast<const long long*>(plan), T, n_ctx,
                      reinterpret_cast<uint32_t*>(out), (long long)n_out);
+  return hipGetLastError() == hipSuccess ? KL_OK : KL_ERR_LAUNCH;
+}
+
+extern "C" int kl_rate_scatter_alts(const float* tprob, const int32_t* rank, const int32_t* alt_id, const float* alt_p,
+                                    const int64_t* plan, int B, int T, int K, int n_ctx, float* out_prob, int32_t* out_rank,
+                                    int32_t* out_alt_id, float* out_alt_p, size_t n_out, void* stream) {
+  if (!tprob || !rank || !alt_id || !alt_p || !plan || !out_prob || !out_rank || !out_alt_id || !out_alt_p) return KL_ERR_ARG;
+  if (B < 1 || T < 1 || K < 1 || K > KL_RATE_ALTS_MAX) return KL_ERR_ARG;
+  if (n_ctx < 0 || n_ctx > KL_SCATTER_MAX_CTX || n_out > (size_t)1 << 40) return KL_ERR_ARG;
+  const void* words[] = {tprob, rank, alt_id, alt_p, out_prob, out_rank, out_alt_id, out_alt_p};
+  for (const void* p : words)
+    if (reinterpret_cast<uintptr_t>(p) & 3) return KL_ERR_ARG;
+  if (reinterpret_cast<uintptr_t>(plan) & 7) return KL_ERR_ARG;
+  long long threads = ((long long)T * K + 63) / 64 * 64;
+  if (threads > 256) threads = 256;
+  hipLaunchKernelGGL(rate_scatter_alts_kernel, dim3(B), dim3((unsigned)threads), 0, static_cast<hipStream_t>(stream),
+                     reinterpret_cast<const uint32_t*>(tprob), reinterpret_cast<const uint32_t*>(rank),
+                     reinterpret_cast<const uint32_t*>(alt_id), reinterpret_cast<const uint32_t*>(alt_p),
+                     reinterpret_cast<const long long*>(plan), T, K, n_ctx, reinterpret_cast<uint32_t*>(out_prob),
+                     reinterpret_cast<uint32_t*>(out_rank), reinterpret_cast<uint32_t*>(out_alt_id),
+                     reinterpret_cast<uint32_t*>(out_alt_p), (long long)n_out);
   return hipGetLastError() == hipSuccess ? KL_OK : KL_ERR_LAUNCH;
 }
 

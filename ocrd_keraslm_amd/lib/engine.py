@@ -90,6 +90,9 @@ class HipLM:
         self._rate_ws_key = None
         self._rate_alts_ws = None
         self._rate_alts_ws_key = None
+        self._rate_alts_bulk_ws = None
+        self._rate_alts_bulk_ws_key = None
+        self._rate_select_ws = None
         self.states = None         # [B][2L][W] implicit state of the stateful streams
         self.pool = None            # [slots][2L][W] explicit states of hypotheses
         self.max_streams_per_launch = 0      # 0: what the kernels address (train_window splits larger batches into groups)
@@ -555,6 +558,140 @@ class HipLM:
             self._rate_alts_ws = self.torch.empty(n, dtype=self.torch.uint8, device=self.device)
             self._rate_alts_ws_key = key
         return self._rate_alts_ws
+
+    # ------------------------------------------------------------------ bulk rating with alternatives, suspect positions
+    def rate_window_alts_bulk(self, idx_d, ctx_d, tgt_d, k):
+        """`rate_window_alts` on the bf16 training forward (kl_rate_window_alts_bulk): idx_d [B,T], ctx_d [B,T,n_ctx], tgt_d
+        [B,T] int32 DEVICE tensors (as `assemble_windows` makes them); returns the DEVICE tensors (tprob [B,T] f32 -- what
+        `rate_window_bulk` returns, bit for bit --, alt_id [B,T,k] i32, alt_p [B,T,k] f32, rank [B,T] i32).  Prepares bf16
+        precision if the handle is in another; streams are grouped and padded with dummy streams (idx 0, tgt -1, zero state:
+        they deliver nothing and take no bits) exactly as `rate_window_bulk` does.  Bits and status as in `rate_window`."""
+        torch = self.torch
+        if self.precision == 0:
+            raise hipabi.KlError("weights not prepared")
+        k = int(k)
+        if not 1 <= k <= hipabi.KL_RATE_ALTS_MAX:
+            raise ValueError("k must be in 1..%d (got %d)" % (hipabi.KL_RATE_ALTS_MAX, k))
+        if self.precision != hipabi.KL_PREC_BF16:
+            self.prepare(hipabi.KL_PREC_BF16)
+        with self._launch():
+            idx_d, tgt_d = self._dev_i32(idx_d), self._dev_i32(tgt_d)
+            B, T = idx_d.shape
+            ctx_d = self._dev_i32(ctx_d) if self.n_ctx else None
+            if self.states is None or self.states.shape[0] != B:
+                self.reset_states(B)
+            if self.rate_bits is None or self.rate_bits.shape[0] != B:
+                self.rate_bits = torch.zeros(B, dtype=torch.float64, device=self.device)
+            if self._rate_status is None:
+                self._rate_status = torch.zeros(4, dtype=torch.float32, device=self.device)
+            tprob = torch.empty((B, T), dtype=torch.float32, device=self.device)
+            alt_id = torch.empty((B, T, k), dtype=torch.int32, device=self.device)
+            alt_p = torch.empty((B, T, k), dtype=torch.float32, device=self.device)
+            rank = torch.empty((B, T), dtype=torch.int32, device=self.device)
+            parts = self._stream_groups(B, T)
+            padded = [self._padded_streams(b1 - b0, T) for b0, b1 in parts]
+            ws = self._rate_alts_bulk_workspace(max(padded), T, k)
+            for (b0, b1), Bp in zip(parts, padded):
+                n = b1 - b0
+                x, c, y, st = idx_d[b0:b1], (ctx_d[b0:b1] if ctx_d is not None else None), tgt_d[b0:b1], self.states[b0:b1]
+                out = [tprob[b0:b1], alt_id[b0:b1], alt_p[b0:b1], rank[b0:b1]]
+                bits = self.rate_bits[b0:b1]
+                if Bp != n:
+                    x = torch.nn.functional.pad(x, (0, 0, 0, Bp - n))
+                    y = torch.nn.functional.pad(y, (0, 0, 0, Bp - n), value=-1)
+                    if c is not None:
+                        c = torch.nn.functional.pad(c, (0, 0, 0, 0, 0, Bp - n))
+                    st = self._pad_states.get(Bp)
+                    if st is None:
+                        st = self._pad_states[Bp] = torch.zeros((Bp,) + tuple(self.states.shape[1:]), dtype=torch.float32,
+                                                                device=self.device)
+                    st[:n] = self.states[b0:b1]
+                    st[n:] = 0
+                    out = [torch.empty((Bp,) + tuple(t.shape[1:]), dtype=t.dtype, device=self.device) for t in out]
+                    bits = torch.zeros(Bp, dtype=torch.float64, device=self.device)
+                hipabi.check(self.lib.kl_rate_window_alts_bulk(
+                    self.handle, Bp, T, k, _ptr(x), _ptr(c), _ptr(y), _ptr(st), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
+                    _ptr(out[3]), _ptr(bits), _ptr(self._rate_status), _ptr(ws), ws.numel(), self._stream()),
+                    "kl_rate_window_alts_bulk")
+                if Bp != n:
+                    self.states[b0:b1] = st[:n]
+                    self.rate_bits[b0:b1] += bits[:n]
+                    for whole, part in zip((tprob, alt_id, alt_p, rank), out):
+                        whole[b0:b1] = part[:n]
+        return tprob, alt_id, alt_p, rank
+
+    def _rate_alts_bulk_workspace(self, B, T, k):
+        key = (B, T, k)
+        if self._rate_alts_bulk_ws_key != key:
+            n = self.lib.kl_rate_alts_bulk_workspace_bytes(self.handle, B, T, k)
+            self._rate_alts_bulk_ws = None
+            self._rate_alts_bulk_ws = self.torch.empty(n, dtype=self.torch.uint8, device=self.device)
+            self._rate_alts_bulk_ws_key = key
+        return self._rate_alts_bulk_ws
+
+    def rate_scatter_alts(self, tprob, rank, alt_id, alt_p, plan, n_ctx, out_prob, out_rank, out_alt_id, out_alt_p):
+        """kl_rate_scatter_alts: `rate_scatter` for all four results of a `rate_window_alts(_bulk)` call (DEVICE tensors tprob,
+        rank [B,T], alt_id, alt_p [B,T,k]) into corpus-order DEVICE arrays out_prob f32 [n], out_rank i32 [n], out_alt_id i32
+        [n,k], out_alt_p f32 [n,k]: position start + 1 + t takes [b][t] for t < min(vlen, T), start and vlen from plan (int64
+        DEVICE tensor [B, 4 + n_ctx]).  In place, no synchronisation."""
+        torch = self.torch
+        B, T = int(tprob.shape[0]), int(tprob.shape[1])
+        k = int(alt_id.shape[-1])
+        n = out_prob.numel()
+        tensors = (tprob, rank, alt_id, alt_p, plan, out_prob, out_rank, out_alt_id, out_alt_p)
+        if ([t.dtype for t in tensors] != [torch.float32, torch.int32, torch.int32, torch.float32, torch.int64, torch.float32,
+                                           torch.int32, torch.int32, torch.float32]
+                or tuple(rank.shape) != (B, T) or tuple(alt_id.shape) != (B, T, k) or tuple(alt_p.shape) != (B, T, k)
+                or plan.dim() != 2 or tuple(plan.shape) != (B, 4 + n_ctx) or out_prob.dim() != 1
+                or tuple(out_rank.shape) != (n,) or tuple(out_alt_id.shape) != (n, k) or tuple(out_alt_p.shape) != (n, k)
+                or not all(t.is_contiguous() and t.is_cuda for t in tensors)):
+            raise hipabi.KlError("rate_scatter_alts: tprob f32 / rank i32 [B, T], alt_id i32 / alt_p f32 [B, T, k], plan int64 "
+                                 "[B, 4 + n_ctx], out_prob f32 / out_rank i32 [n], out_alt_id i32 / out_alt_p f32 [n, k], "
+                                 "contiguous, on the device")
+        with self._launch():
+            hipabi.check(self.lib.kl_rate_scatter_alts(
+                _ptr(tprob), _ptr(rank), _ptr(alt_id), _ptr(alt_p), _ptr(plan), B, T, k, int(n_ctx), _ptr(out_prob),
+                _ptr(out_rank), _ptr(out_alt_id), _ptr(out_alt_p), n, self._stream()), "kl_rate_scatter_alts")
+
+    def rate_select(self, probs, rank, alt_id, alt_p, max_prob, min_rank):
+        """kl_rate_select over corpus-order DEVICE arrays (probs f32 [n], rank i32 [n], alt_id i32 [n,k], alt_p f32 [n,k]): the
+        positions j with rank[j] >= min_rank and probs[j] <= float32(max_prob), ascending, as DEVICE tensors (pos i64 [m], prob
+        f32 [m], rank i32 [m], alt_id i32 [m,k], alt_p f32 [m,k]).  One counting call, one read of the count -- the only
+        wait --, buffers of exactly that size, one writing call; nothing more is launched when the count is 0."""
+        torch = self.torch
+        n = probs.numel()
+        k = int(alt_id.shape[-1]) if alt_id.dim() == 2 else 0
+        tensors = (probs, rank, alt_id, alt_p)
+        if ([t.dtype for t in tensors] != [torch.float32, torch.int32, torch.int32, torch.float32] or probs.dim() != 1
+                or tuple(rank.shape) != (n,) or tuple(alt_id.shape) != (n, k) or tuple(alt_p.shape) != (n, k)
+                or not all(t.is_contiguous() and t.is_cuda for t in tensors)):
+            raise hipabi.KlError("rate_select: probs f32 / rank i32 [n], alt_id i32 / alt_p f32 [n, k], contiguous, on the device")
+        min_rank = int(min_rank)
+        max_prob = float(np.float32(max_prob))
+        if min_rank < 0 or max_prob != max_prob:
+            raise ValueError("rate_select: min_rank >= 0 and max_prob not NaN")
+        dev = self.device
+        empty = lambda m: (torch.empty(m, dtype=torch.int64, device=dev), torch.empty(m, dtype=torch.float32, device=dev),
+                           torch.empty(m, dtype=torch.int32, device=dev), torch.empty((m, k), dtype=torch.int32, device=dev),
+                           torch.empty((m, k), dtype=torch.float32, device=dev))
+        if n == 0:
+            return empty(0)
+        with self._launch():
+            n_ws = self.lib.kl_rate_select_workspace_bytes(n)
+            if self._rate_select_ws is None or self._rate_select_ws.numel() < n_ws:
+                self._rate_select_ws = None
+                self._rate_select_ws = torch.empty(n_ws, dtype=torch.uint8, device=dev)
+            ws = self._rate_select_ws
+            count = torch.zeros(1, dtype=torch.int64, device=dev)
+            call = lambda m, out: hipabi.check(self.lib.kl_rate_select(
+                _ptr(probs), _ptr(rank), _ptr(alt_id), _ptr(alt_p), n, k, max_prob, min_rank, m, _ptr(out[0]), _ptr(out[1]),
+                _ptr(out[2]), _ptr(out[3]), _ptr(out[4]), _ptr(count), _ptr(ws), ws.numel(), self._stream()), "kl_rate_select")
+            call(0, (None,) * 5)
+            m = int(count.item())
+            out = empty(m)
+            if m:
+                call(m, out)
+        return out
 
     def rate_status_check(self):
         """raise if a scan hand-off timed out in a rate_window call since the last check (synchronises)"""

@@ -16,6 +16,8 @@ LIB_PATH = os.environ.get("KL_LIB") or os.path.join(os.path.dirname(_HERE), "lib
 KL_PREC_BF16 = 1
 KL_PREC_SPLIT = 3
 KL_RATE_ALTS_MAX = 8     # alternatives per position kl_rate_window_alts delivers at most
+KL_RATE_SELECT_BLOCK = 1024          # positions per workgroup of kl_rate_select
+KL_RATE_SELECT_SCAN_THREADS = 256    # ... and blocks per round of its one offsets workgroup
 KL_SAMPLE_MAX_ROWS = 1024  # chains per kl_sample_pick call
 KL_SAMPLE_MAX_TOPK = 64
 # kl_window_view.wg_route
@@ -85,6 +87,16 @@ SIGNATURES = {
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "kl_rate_scatter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "kl_rate_text_bits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "kl_rate_alts_bulk_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "kl_rate_window_alts_bulk": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_size_t, C.c_void_p]),
+    "kl_rate_scatter_alts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                       C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "kl_rate_select_workspace_bytes": (C.c_size_t, [C.c_size_t]),
+    "kl_rate_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_int,
+                                 C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_size_t, C.c_void_p]),
     "kl_train_window": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "kl_assemble_windows": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,

@@ -117,6 +117,27 @@ class RatedText(object):
         return [[None if v < 0 else i_c.get(int(v), "") for v in row] for row in self.alt_ids]
 
 
+class Suspects(object):
+    """One text's share of `Rater.suspects`, m suspect characters:
+
+    positions  [m] i64    index into the normalised text, ascending
+    probs      [m] f32    probability of the character written there
+    rank       [m] i32    its position among all the model could have written there
+    alt_ids    [m,k] i32  the k most probable ids there, most probable first (-1: none)
+    alt_probs  [m,k] f32  their probabilities (0 where alt_ids is -1)
+    """
+
+    def __init__(self, positions, probs, rank, alt_ids, alt_probs):
+        self.positions, self.probs, self.rank, self.alt_ids, self.alt_probs = positions, probs, rank, alt_ids, alt_probs
+
+    def __len__(self):
+        return len(self.positions)
+
+    def chars(self, mapping):
+        """the alternatives as characters, [m][k], as `RatedText.chars`"""
+        return RatedText.chars(self, mapping)
+
+
 def alternatives_of(full, y, k):
     """What the model expected instead, from whole distributions: full [B,T,V] (probabilities, or logits -- any values that
     order the vocabulary), y [B,T] targets, k >= 1.  Within a position the ids are ordered by (value descending, id

@@ -17,7 +17,9 @@ Rules of the plan:
     of 50-character lines does not run 256-step windows.
 
 `windows_host`, `scatter_host` and `text_bits_host` state in numpy what kl_assemble_windows, kl_rate_scatter and
-kl_rate_text_bits compute.  numpy only: the plan is built and tested without an engine.
+kl_rate_text_bits compute; `scatter_alts_host` and `select_host` what kl_rate_scatter_alts and kl_rate_select do for rating
+with alternatives (`Rater.rate_alternatives(precision="bf16")`, `Rater.suspects`).  numpy only: the plan is built and tested
+without an engine.
 """
 from __future__ import annotations
 
@@ -146,6 +148,40 @@ def scatter_host(tprob, rows, out):
             if 0 <= g < n:
                 out[g] = tprob[b, t]
     return out
+
+
+def scatter_alts_host(tprob, rank, alt_id, alt_p, rows, out_prob, out_rank, out_alt_id, out_alt_p):
+    """what kl_rate_scatter_alts does: `scatter_host` for the four results of a call with alternatives -- position
+    g = start + 1 + t takes tprob[b][t], rank[b][t] and the K-wide rows alt_id[b][t], alt_p[b][t] for t < min(vlen, T), inside
+    the outputs ([n], [n], [n, K], [n, K]); in place, returns the four outputs"""
+    tprob = np.asarray(tprob)
+    B, T = tprob.shape
+    n = len(out_prob)
+    for b in range(B):
+        start, vlen = int(rows[b, 0]), int(min(max(rows[b, 1], 0), T))
+        for t in range(vlen):
+            g = start + 1 + t
+            if 0 <= g < n:
+                out_prob[g] = tprob[b, t]
+                out_rank[g] = rank[b, t]
+                out_alt_id[g] = alt_id[b, t]
+                out_alt_p[g] = alt_p[b, t]
+    return out_prob, out_rank, out_alt_id, out_alt_p
+
+
+def select_host(probs, rank, alt_id, alt_p, max_prob, min_rank):
+    """what kl_rate_select computes: the positions j with rank[j] >= min_rank and probs[j] <= float32(max_prob), ascending --
+    an f32 comparison: a NaN probability is never selected, and min_rank >= 0 keeps rank -1 (no prediction) out.  Returns
+    (pos int64 [m], prob [m], rank [m], alt_id [m, K], alt_p [m, K]), copies of the selected rows."""
+    min_rank = int(min_rank)
+    limit = np.float32(max_prob)
+    if min_rank < 0 or np.isnan(limit):
+        raise ValueError("min_rank >= 0 and max_prob not NaN")
+    probs, rank, alt_id, alt_p = np.asarray(probs), np.asarray(rank), np.asarray(alt_id), np.asarray(alt_p)
+    with np.errstate(invalid="ignore"):
+        keep = (rank >= min_rank) & (probs.astype(np.float32, copy=False) <= limit)
+    pos = np.nonzero(keep)[0].astype(np.int64)
+    return pos, probs[pos], rank[pos], alt_id[pos], alt_p[pos]
 
 
 def text_bits_host(probs, offsets):

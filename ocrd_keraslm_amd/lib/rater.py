@@ -938,7 +938,7 @@ class Rater(object):
         lm.rate_status_check()
         return _np(lm.torch.stack(steps)) if want_probs else None
 
-    def rate_alternatives(self, texts, contexts=None, k=3, streams=64):
+    def rate_alternatives(self, texts, contexts=None, k=3, streams=64, precision="split"):
         '''`rate_batch` answering also what the model expected instead: returns (rated, bits), both in input order.
         `rated[i]` is a RatedText over the n characters of the normalised text: `probs` [n] f32 -- what `rate_batch` returns
         for that text --, `alt_ids` [n,k] i32 and `alt_probs` [n,k] f32 -- the k most probable characters at that position,
@@ -946,9 +946,19 @@ class Rater(object):
         the position of the character that was written in that order (0: the model's first choice).  The first character
         has no prediction: probability 1.0, rank -1, ids -1, probabilities 0.  `bits[i]`, texts, contexts, streams and the
         state afterwards (a freshly reset single row) are as in `rate_batch`.  1 <= k <= 8.  Only stateful raters: the
-        stateless one rates through windows of its own (`rate`).'''
+        stateless one rates through windows of its own (`rate`).
+
+        precision: "split" (default) rates in the split-precision inference kernels.  "bf16" is `rate_batch`'s bulk path
+        with alternatives (`rate_window_alts_bulk`, `rate_scatter_alts`): the same plan (ratebulk.py), one upload, the
+        results kept in corpus order on the device -- (8k + 8) bytes per character -- and one transfer at the end; `probs`
+        are bit for bit those of `rate_batch(precision="bf16")`.  Same return contract; a stateless rater raises
+        ValueError; the state and precision afterwards are as after `rate_batch(precision="bf16")`.'''
         assert self.status > 1
         assert self.incremental is False
+        if precision not in ("split", "bf16"):
+            raise ValueError('precision must be "split" or "bf16" (got %r)' % (precision,))
+        if precision == "bf16" and not self.stateful:
+            raise ValueError('rate_alternatives(precision="bf16") needs a stateful rater: bulk rating runs stateful windows')
         assert self.stateful, "rate_alternatives needs a stateful rater"
         k = int(k)
         assert 1 <= k <= ratebatch.ALTS_MAX, "k must be in 1..%d" % ratebatch.ALTS_MAX
@@ -961,6 +971,15 @@ class Rater(object):
         else:
             assert len(contexts) == n, "one context list per text"
             contexts = [list(c) if (c is not None and len(c)) else self.underspecify_contexts() for c in contexts]
+        if precision == "bf16" and hasattr(self.model, 'rate_window_alts_bulk'):
+            # (an engine without rate_window_alts_bulk -- the tests' CPU double -- runs the ordinary path below)
+            plan, arrays, bits = self._alternatives_in_corpus_order(texts, contexts, k, streams, "bf16")
+            if arrays is None:
+                return [ratebatch.RatedText.unpredicted(int(m), k) for m in plan.sizes], bits
+            probs, rank, alt_id, alt_p = (_np(a) for a in arrays)
+            cut = [(int(plan.offsets[i]), int(plan.offsets[i + 1])) for i in range(n)]
+            return [ratebatch.RatedText(probs[a:b].copy(), rank[a:b].copy(), alt_id[a:b].copy(), alt_p[a:b].copy())
+                    for a, b in cut], bits
         self._ensure_precision()
         lm = self.model
         bits = np.zeros(n, dtype=np.float64)
@@ -1005,6 +1024,107 @@ class Rater(object):
         lm.rate_status_check()
         picked, alt_id, alt_p, rank = (_np(lm.torch.stack([st[j] for st in steps])) for j in range(4))
         return picked, rank, alt_id, alt_p
+
+    def _alternatives_in_corpus_order(self, texts, contexts, k, streams, precision):
+        '''the bulk plan (ratebulk.plan: rows reused, short texts in short windows) with alternatives, everything kept on the
+        device: one upload (ids, plan rows, reset masks and offsets of all calls), per call assemble_windows ->
+        rate_window_alts_bulk ("bf16") or rate_window_alts ("split", the inference workspace) -> rate_scatter_alts, then one
+        rate_text_bits.  Returns (plan, (probs [n], rank [n], alt_id [n,k], alt_p [n,k]) DEVICE tensors in corpus order, bits);
+        the tensors are None if no text has a prediction.  A text's first character keeps 1.0 / -1 / -1 / 0.'''
+        lm = self.model
+        torch = lm.torch
+        n = len(texts)
+        if contexts is None or len(contexts) == 0:      # (None, one context list for all texts, or one per text: as rate_batch)
+            contexts = [self.underspecify_contexts()] * n
+        elif isinstance(contexts[0], (int, np.integer)):
+            contexts = [list(contexts)] * n
+        else:
+            assert len(contexts) == n, "one context list per text"
+            contexts = [list(c) if (c is not None and len(c)) else self.underspecify_contexts() for c in contexts]
+        texts = [windows.normalize(t) for t in texts]
+        ids = [windows.encode(t, self.mapping[0], self._unmapped_input) for t in texts]
+        plan = ratebulk.plan([len(a) for a in ids], [windows.clamp_context(c) for c in contexts], self.length, streams)
+        bits = np.zeros(n, dtype=np.float64)
+        if precision == "split":
+            self._ensure_precision()
+        if not plan.calls:       # (nothing but empty texts and single characters)
+            lm.reset_states(1)
+            return plan, None, bits
+        n_ctx = plan.n_ctx
+        bounds = np.concatenate([[0], np.cumsum([c.B for c in plan.calls])])
+        corpus = torch.from_numpy(np.concatenate(ids).astype(np.int32)).to(lm.device)
+        rows = torch.from_numpy(np.concatenate([c.rows for c in plan.calls])).to(lm.device)
+        reset = torch.from_numpy(np.concatenate([c.reset for c in plan.calls])).to(lm.device)
+        offsets = torch.from_numpy(plan.offsets).to(lm.device)
+        out_prob = torch.ones(plan.total, dtype=torch.float32, device=lm.device)
+        out_rank = torch.full((plan.total,), -1, dtype=torch.int32, device=lm.device)
+        out_alt_id = torch.full((plan.total, k), -1, dtype=torch.int32, device=lm.device)
+        out_alt_p = torch.zeros((plan.total, k), dtype=torch.float32, device=lm.device)
+        rate = lm.rate_window_alts_bulk if precision == "bf16" else lm.rate_window_alts
+        B = None
+        for s, call in enumerate(plan.calls):
+            a, b = int(bounds[s]), int(bounds[s + 1])
+            if call.B != B:
+                B = call.B
+                lm.reset_states(B)      # (another number of rows: all of them start from zero)
+            elif call.reset.any():
+                lm.reset_states_where(reset[a:b])
+            x, z, y = lm.assemble_windows(corpus, rows[a:b], call.T, n_ctx)
+            p, ai, ap, rk = rate(x, z, y, k)
+            lm.rate_scatter_alts(p, rk, ai, ap, rows[a:b], n_ctx, out_prob, out_rank, out_alt_id, out_alt_p)
+        bits[:] = _np(lm.rate_text_bits(out_prob, offsets))
+        lm.rate_bits_read(reset=True)      # (the per-stream sums are not used here; also raises on a timed-out scan hand-off)
+        lm.reset_states(1)
+        return plan, (out_prob, out_rank, out_alt_id, out_alt_p), bits
+
+    def suspects(self, texts, contexts=None, k=3, streams=1024, max_prob=0.01, min_rank=1, precision="bf16"):
+        '''Where are the characters the model does not believe, and what would it have written there?  Returns (found, bits),
+        both in input order: `found[i]` is a ratebatch.Suspects holding exactly the rows j of
+        `rate_alternatives(texts, contexts, k, streams, precision)[0][i]` with rank[j] >= min_rank and
+        probs[j] <= np.float32(max_prob), in ascending j (`positions`); `bits` is as in `rate_batch`.  A text's first
+        character has no prediction and is never a suspect (min_rank >= 0 is required).
+
+        precision "bf16" (default) rates on the bulk path and picks the suspects out on the device (`rate_select` over the
+        whole corpus): what leaves the device is count * (8k + 16) bytes plus the bits.  "split" runs the same plan through
+        the split-precision `rate_window_alts`.  Either way the results of ALL texts stay on the device in corpus order
+        until the selection: (8k + 8) bytes of device memory per character.  Only stateful raters; the state afterwards is a
+        freshly reset single row, the precision that of the path taken.'''
+        assert self.status > 1
+        assert self.incremental is False
+        if precision not in ("split", "bf16"):
+            raise ValueError('precision must be "split" or "bf16" (got %r)' % (precision,))
+        if not self.stateful:
+            raise ValueError('suspects needs a stateful rater: it rates through stateful windows')
+        k, min_rank = int(k), int(min_rank)
+        assert 1 <= k <= ratebatch.ALTS_MAX, "k must be in 1..%d" % ratebatch.ALTS_MAX
+        limit = np.float32(max_prob)
+        if min_rank < 0:
+            raise ValueError("min_rank must be >= 0 (got %d): a character without a prediction is no suspect" % min_rank)
+        if np.isnan(limit):
+            raise ValueError("max_prob must not be NaN")
+        texts = list(texts)
+        n = len(texts)
+        lm = self.model
+        if not hasattr(lm, 'rate_window_alts_bulk'):
+            # an engine without the device path (the tests' CPU double): rate_alternatives' fallback and the numpy statement
+            rated, bits = self.rate_alternatives(texts, contexts, k=k, streams=streams, precision=precision)
+            found = []
+            for one in rated:
+                found.append(ratebatch.Suspects(*ratebulk.select_host(one.probs, one.rank, one.alt_ids, one.alt_probs,
+                                                                      limit, min_rank)))
+            return found, bits
+        plan, arrays, bits = self._alternatives_in_corpus_order(texts, contexts, k, streams, precision)
+        if arrays is None:
+            pos, found = np.zeros(0, dtype=np.int64), (np.zeros(0, dtype=np.float32), np.zeros(0, dtype=np.int32),
+                                                       np.zeros((0, k), dtype=np.int32), np.zeros((0, k), dtype=np.float32))
+        else:
+            sel = [_np(t) for t in lm.rate_select(*arrays, max_prob=float(limit), min_rank=min_rank)]
+            pos, found = sel[0], sel[1:]
+        # (positions ascend over the corpus: a text's share is one slice)
+        lo = np.searchsorted(pos, plan.offsets[:-1], side="left")
+        hi = np.searchsorted(pos, plan.offsets[1:], side="left")
+        return [ratebatch.Suspects(pos[a:b] - plan.offsets[i], *(f[a:b].copy() for f in found))
+                for i, (a, b) in enumerate(zip(lo, hi))], bits
 
     def rate2(self, text, context=None):
         '''Rate a string one by one (rating.py:531-576): resets the state, feeds one

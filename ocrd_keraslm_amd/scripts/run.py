@@ -6,6 +6,8 @@ apply, generate, print-history, print-charset, prune-charset and the three plot-
 embeddings (matplotlib / scikit-learn imported on use).
 Additional command `score`: bits per character and perplexity of every DATA file, all files rated at once
 (Rater.rate_batch; --precision bf16 takes the bulk path on the training forward).
+Additional command `suspects`: per DATA file the characters the model does not believe, with what it expected instead
+(Rater.suspects: rated in bulk, picked out on the device).
 Additional options on `train`: --streams (stateful streams per GPU, default 1 = the
 reference's batching) and --segment-streams (with fewer files than streams, cut the files
 into contiguous segments on window boundaries, one list of segments per stream).  Under `python -m torch.distributed.run` training is
@@ -22,7 +24,7 @@ import click
 
 from .. import lib
 
-COMMAND_ORDER = ['train', 'test', 'score', 'apply', 'generate', 'print-history', 'print-charset', 'prune-charset',
+COMMAND_ORDER = ['train', 'test', 'score', 'suspects', 'apply', 'generate', 'print-history', 'print-charset', 'prune-charset',
                  'plot-char-embeddings-similarity', 'plot-context-embeddings-similarity', 'plot-context-embeddings-projection']
 
 
@@ -193,6 +195,44 @@ def score(model, streams, precision, data):
         per_char = float(total) / max(len(text) - 1, 1)
         click.echo(json.dumps({"file": name, "chars": len(text), "bits_per_char": per_char, "perplexity": 2.0 ** per_char},
                               ensure_ascii=False))
+
+
+@cli.command(short_help='list the characters of every file that the model does not believe')
+@click.option('-m', '--model', default="model.h5", show_default=True, help='model file', type=click.Path(dir_okay=False, exists=True))
+@click.option('-s', '--streams', default=1024, show_default=True, help='files rated in lockstep, one per row of a window call',
+              type=click.IntRange(min=1, max=4096))
+@click.option('--precision', default='bf16', show_default=True, type=click.Choice(['bf16', 'split']),
+              help='bf16: bulk rating on the training forward; split: the inference kernels, ~f32 accuracy')
+@click.option('-k', 'k', default=3, show_default=True, type=click.IntRange(min=1, max=8),
+              help='characters the model expected most, listed per suspect')
+@click.option('--max-prob', default=0.01, show_default=True, type=click.FLOAT,
+              help='a suspect has at most this probability')
+@click.option('--min-rank', default=1, show_default=True, type=click.IntRange(min=0),
+              help='... and at least this rank among the characters the model could have written (0: its first choice)')
+@click.argument('data', nargs=-1, type=click.Path(exists=True, dir_okay=True, file_okay=True))
+def suspects(model, streams, precision, k, max_prob, min_rank, data):
+    """Apply a language model to DATA files and print one JSON line per file: characters, bits per
+       character and the suspect characters as [position, char, prob, rank, [[alt_char, alt_prob], ...]].
+
+       Files are read, and given their contexts, as `score` does.  Only the suspects leave the device.
+    """
+    from ..lib import windows
+    rater = _load(model)
+    names, texts, contexts = [], [], []
+    for file in _open_all(data):
+        with file:
+            texts.append(windows.normalize(file.read()))
+        names.append(file.name)
+        contexts.append(windows.context_from_filename(file.name))
+    if not texts:
+        return
+    found, bits = rater.suspects(texts, contexts, k=k, streams=streams, max_prob=max_prob, min_rank=min_rank,
+                                 precision=precision)
+    for name, text, one, total in zip(names, texts, found, bits):
+        rows = [[int(j), text[int(j)], float(p), int(r), [[c, float(q)] for c, q in zip(chars, probs)]]
+                for j, p, r, chars, probs in zip(one.positions, one.probs, one.rank, one.chars(rater.mapping), one.alt_probs)]
+        click.echo(json.dumps({"file": name, "chars": len(text), "bits_per_char": float(total) / max(len(text) - 1, 1),
+                               "suspects": rows}, ensure_ascii=False))
 
 
 @cli.command(short_help='sample characters from language model')
