@@ -16,6 +16,7 @@
  *   ... with the model's top-K characters and the target's rank  kl_rate_window_alts
  *   ... for a whole corpus, on the training forward (bf16)    kl_rate_window_bulk, kl_rate_scatter, kl_rate_text_bits
  *   ... with alternatives, and the suspect positions picked out  kl_rate_window_alts_bulk, kl_rate_scatter_alts, kl_rate_select
+ *   ... and the suspects' alternatives rescored against what follows  kl_variant_windows (rows for kl_rate_window(_bulk))
  *   model.predict_on_batch, stateful (1,1) step, :566        kl_forward_window with T = 1
  *   model.predict_on_batch, incremental + states, :631       kl_step_batch
  *   ... once per character of a lattice edge, :796-851       kl_walk_batch_host (all characters of all hypotheses, one call)
@@ -242,6 +243,31 @@ size_t kl_rate_select_workspace_bytes(size_t n);
 int kl_rate_select(const float* probs, const int32_t* rank, const int32_t* alt_id, const float* alt_p, size_t n, int K,
                    float max_prob, int min_rank, size_t capacity, int64_t* sel_pos, float* sel_prob, int32_t* sel_rank,
                    int32_t* sel_alt_id, float* sel_alt_p, int64_t* count, void* ws, size_t ws_bytes, void* stream);
+
+/* Hypothesis windows of the selected positions (what kl_rate_select wrote): rows for kl_rate_window(_bulk) that rate the text
+ * FOLLOWING a suspect under each variant of it.  No handle.  corpus (device int32 [n_corpus]) and offsets (device int64
+ * [n_texts + 1], ascending, repeated values -- empty texts -- allowed) as in kl_rate_text_bits; text_ctx (device int32
+ * [n_texts][n_ctx], NULL iff n_ctx == 0) the context values of every text; sel_pos (device int64 [S]) corpus positions and
+ * sel_alt_id (device int32 [S][K]) their alternatives.  A suspect at g = sel_pos[s] lies in text i, offsets[i] <= g <
+ * offsets[i+1] (binary search); w = corpus[g], L = min(left, g - offsets[i]), A = min(ahead, offsets[i+1] - 1 - g).  It has
+ * R = K + 1 + deletions variants, row b = s * R + v:
+ *   v = 0        q = x[g-L .. g-1], w, x[g+1 .. g+A]        invalid if L == 0 or g lies outside [0, min(n_corpus,
+ *                                                           offsets[n_texts])) or in front of offsets[0]
+ *   v = 1 .. K   the same with a = sel_alt_id[s][v-1] for w  invalid if v = 0 is, or a < 0, or a == w
+ *   v = K + 1    q = x[g-L .. g-1], x[g+1 .. g+A]            (deletions == 1 only) invalid if v = 0 is, or A == 0
+ * With len the length of q, a valid row is  idx[b][t] = q[t] for t < len - 1, else 0;  tgt[b][t] = q[t+1] for
+ * L - 1 <= t < len - 1, else -1;  ctx[b][t][c] = text_ctx[i][c] for t < len - 1, else 0;  valid[b] = 1  -- a window from a
+ * zero state over it predicts the variant's character, if it has one, and the A characters after it, and nothing else.  An
+ * invalid row is a dummy stream: idx 0, ctx 0, tgt -1 everywhere, valid[b] = 0.  idx, tgt (device int32 [S*R][T]), ctx
+ * (device int32 [S*R][T][n_ctx]) and valid (device int32 [S*R]) are written in every word, nothing outside them is touched;
+ * a corpus position outside [0, min(n_corpus, offsets[n_texts])) reads as 0 without touching memory.  One workgroup per row,
+ * one launch on `stream`, no atomics, no workgroup waits for another: the output does not depend on scheduling.
+ * KL_ERR_ARG, before any launch, for null pointers (ctx and text_ctx may be null only with n_ctx == 0), S or n_texts < 1,
+ * K outside 1 .. KL_RATE_ALTS_MAX, left < 1, ahead < 0, T < left + ahead or T > 1024, n_ctx outside 0 .. 8, deletions outside
+ * {0, 1}, S * R > 2^22, n_corpus > 2^40, misaligned pointers (4 bytes; offsets and sel_pos 8). */
+int kl_variant_windows(const int32_t* corpus, size_t n_corpus, const int64_t* offsets, int n_texts, const int32_t* text_ctx,
+                       int n_ctx, const int64_t* sel_pos, const int32_t* sel_alt_id, int S, int K, int left, int ahead,
+                       int deletions, int T, int32_t* idx, int32_t* ctx, int32_t* tgt, int32_t* valid, void* stream);
 
 /* One training batch, forward + backward (rating.py:292-298 -> train_on_batch):
  * writes the gradient of (mean CE + embedding regularisers, rating.py:187-246)

@@ -693,6 +693,45 @@ class HipLM:
                 call(m, out)
         return out
 
+    def variant_windows(self, corpus_d, offsets_d, text_ctx_d, sel_pos_d, sel_alt_id_d, left, ahead, deletions, T):
+        """kl_variant_windows: the hypothesis rows of S suspects, built on the device in one launch.  corpus_d int32 [n] and
+        offsets_d int64 [n_texts + 1] as bulk rating keeps them, text_ctx_d int32 [n_texts, n_ctx] (None without contexts),
+        sel_pos_d int64 [S] and sel_alt_id_d int32 [S, K] as `rate_select` returns them (or slices of them) -- all DEVICE
+        tensors.  Returns the DEVICE tensors (idx [S*R, T], ctx [S*R, T, n_ctx], tgt [S*R, T], valid [S*R]) int32 with
+        R = K + 1 + deletions, row s * R + v: what `ratebulk.variant_windows_host` states.  No synchronisation."""
+        torch = self.torch
+        n_ctx = 0 if text_ctx_d is None else int(text_ctx_d.shape[-1])
+        tensors = [corpus_d, offsets_d, sel_pos_d, sel_alt_id_d] + ([text_ctx_d] if n_ctx else [])
+        kinds = [torch.int32, torch.int64, torch.int64, torch.int32] + ([torch.int32] if n_ctx else [])
+        n_texts = offsets_d.numel() - 1
+        S = int(sel_pos_d.numel())
+        if ([t.dtype for t in tensors] != kinds or corpus_d.dim() != 1 or offsets_d.dim() != 1 or sel_pos_d.dim() != 1
+                or sel_alt_id_d.dim() != 2 or sel_alt_id_d.shape[0] != S
+                or (n_ctx and tuple(text_ctx_d.shape) != (n_texts, n_ctx))
+                or not all(t.is_contiguous() and t.is_cuda for t in tensors)):
+            raise hipabi.KlError("variant_windows: corpus int32 [n], offsets int64 [n_texts + 1], text_ctx int32 [n_texts, n_ctx], "
+                                 "sel_pos int64 [S], sel_alt_id int32 [S, K], contiguous, on the device")
+        K = int(sel_alt_id_d.shape[1])
+        left, ahead, deletions, T = int(left), int(ahead), int(bool(deletions)), int(T)
+        rows = S * (K + 1 + deletions)
+        with self._launch():
+            idx = torch.empty((rows, T), dtype=torch.int32, device=self.device)
+            tgt = torch.empty((rows, T), dtype=torch.int32, device=self.device)
+            ctx = torch.empty((rows, T, n_ctx), dtype=torch.int32, device=self.device)
+            valid = torch.empty(rows, dtype=torch.int32, device=self.device)
+            hipabi.check(self.lib.kl_variant_windows(
+                _ptr(corpus_d), corpus_d.numel(), _ptr(offsets_d), n_texts, _ptr(text_ctx_d) if n_ctx else None, n_ctx,
+                _ptr(sel_pos_d), _ptr(sel_alt_id_d), S, K, left, ahead, deletions, T, _ptr(idx), _ptr(ctx) if n_ctx else None,
+                _ptr(tgt), _ptr(valid), self._stream()), "kl_variant_windows")
+        return idx, ctx, tgt, valid
+
+    def rate_bits_take_all(self):
+        """the accumulated bits of ALL streams as a DEVICE tensor (f64 [B]), the accumulators zeroed; no synchronisation"""
+        with self._launch():
+            out = self.rate_bits.clone()
+            self.rate_bits.zero_()
+        return out
+
     def rate_status_check(self):
         """raise if a scan hand-off timed out in a rate_window call since the last check (synchronises)"""
         if self._rate_status is not None and float(self._rate_status[3].item()) != 0.0:

@@ -138,6 +138,41 @@ class Suspects(object):
         return RatedText.chars(self, mapping)
 
 
+class Corrections(Suspects):
+    """One text's share of `Rater.corrections`: the m suspects of `Rater.suspects` (the five arrays above, bit for bit) and
+    what rescoring their alternatives against the text that follows proposes.  With k alternatives and R = k + 1 (+ 1 with
+    deletions) variants per suspect -- 0: the character as written, v = 1 .. k: alt_ids[:, v-1] in its place, k + 1: the
+    character dropped --:
+
+    cost       [m,R] f64  bits of the variant's character and the characters after it (+inf: no such variant)
+    best_id    [m] i32    the id proposed in place of the character; NO_PROPOSAL (-1): none, DELETE (-2): drop the character
+    gain       [m] f64    bits saved by the proposal against the text as written (0.0 without a proposal)
+    """
+    NO_PROPOSAL = -1
+    DELETE = -2
+
+    def __init__(self, positions, probs, rank, alt_ids, alt_probs, cost, best_id, gain):
+        Suspects.__init__(self, positions, probs, rank, alt_ids, alt_probs)
+        self.cost, self.best_id, self.gain = cost, best_id, gain
+
+    def proposals(self, mapping):
+        """the proposals as characters, [m]: None for no proposal, "" for a deletion, else the character -- the unmapped id 0
+        has no character to write and shows as None too.  mapping as in `RatedText.chars`."""
+        i_c = mapping[1] if isinstance(mapping, (tuple, list)) else mapping
+        return ["" if v == self.DELETE else (i_c.get(int(v)) if v >= 0 else None) for v in self.best_id]
+
+    def apply(self, text, mapping):
+        """the (normalised) text with the proposals applied, from right to left so that positions stay true; a proposal of the
+        unmapped id 0 leaves the character as written"""
+        chars = list(text)
+        proposed = self.proposals(mapping)
+        for j in range(len(self.positions) - 1, -1, -1):
+            at, new = int(self.positions[j]), proposed[j]
+            if new is not None and 0 <= at < len(chars):
+                chars[at:at + 1] = [new] if new else []
+        return "".join(chars)
+
+
 def alternatives_of(full, y, k):
     """What the model expected instead, from whole distributions: full [B,T,V] (probabilities, or logits -- any values that
     order the vocabulary), y [B,T] targets, k >= 1.  Within a position the ids are ordered by (value descending, id

@@ -1025,22 +1025,18 @@ class Rater(object):
         picked, alt_id, alt_p, rank = (_np(lm.torch.stack([st[j] for st in steps])) for j in range(4))
         return picked, rank, alt_id, alt_p
 
-    def _alternatives_in_corpus_order(self, texts, contexts, k, streams, precision):
+    def _alternatives_in_corpus_order(self, texts, contexts, k, streams, precision, keep=None):
         '''the bulk plan (ratebulk.plan: rows reused, short texts in short windows) with alternatives, everything kept on the
         device: one upload (ids, plan rows, reset masks and offsets of all calls), per call assemble_windows ->
         rate_window_alts_bulk ("bf16") or rate_window_alts ("split", the inference workspace) -> rate_scatter_alts, then one
         rate_text_bits.  Returns (plan, (probs [n], rank [n], alt_id [n,k], alt_p [n,k]) DEVICE tensors in corpus order, bits);
-        the tensors are None if no text has a prediction.  A text's first character keeps 1.0 / -1 / -1 / 0.'''
+        the tensors are None if no text has a prediction.  A text's first character keeps 1.0 / -1 / -1 / 0.  A dict passed as
+        `keep` receives what stays on the device for a caller that goes on there (`corrections`): corpus (int32 [n]), offsets
+        (int64 [n_texts + 1]) and text_ctx (int32 [n_texts, n_ctx], the clamped contexts of every text).'''
         lm = self.model
         torch = lm.torch
         n = len(texts)
-        if contexts is None or len(contexts) == 0:      # (None, one context list for all texts, or one per text: as rate_batch)
-            contexts = [self.underspecify_contexts()] * n
-        elif isinstance(contexts[0], (int, np.integer)):
-            contexts = [list(contexts)] * n
-        else:
-            assert len(contexts) == n, "one context list per text"
-            contexts = [list(c) if (c is not None and len(c)) else self.underspecify_contexts() for c in contexts]
+        contexts = self._contexts_per_text(contexts, n)
         texts = [windows.normalize(t) for t in texts]
         ids = [windows.encode(t, self.mapping[0], self._unmapped_input) for t in texts]
         plan = ratebulk.plan([len(a) for a in ids], [windows.clamp_context(c) for c in contexts], self.length, streams)
@@ -1056,6 +1052,9 @@ class Rater(object):
         rows = torch.from_numpy(np.concatenate([c.rows for c in plan.calls])).to(lm.device)
         reset = torch.from_numpy(np.concatenate([c.reset for c in plan.calls])).to(lm.device)
         offsets = torch.from_numpy(plan.offsets).to(lm.device)
+        if keep is not None:
+            text_ctx = np.asarray([windows.clamp_context(c) for c in contexts], dtype=np.int32).reshape(n, n_ctx)
+            keep.update(corpus=corpus, offsets=offsets, text_ctx=torch.from_numpy(text_ctx).to(lm.device))
         out_prob = torch.ones(plan.total, dtype=torch.float32, device=lm.device)
         out_rank = torch.full((plan.total,), -1, dtype=torch.int32, device=lm.device)
         out_alt_id = torch.full((plan.total, k), -1, dtype=torch.int32, device=lm.device)
@@ -1125,6 +1124,136 @@ class Rater(object):
         hi = np.searchsorted(pos, plan.offsets[1:], side="left")
         return [ratebatch.Suspects(pos[a:b] - plan.offsets[i], *(f[a:b].copy() for f in found))
                 for i, (a, b) in enumerate(zip(lo, hi))], bits
+
+    def corrections(self, texts, contexts=None, k=3, streams=1024, max_prob=0.01, min_rank=1, left=64, ahead=8, deletions=False,
+                    min_gain=1.0, precision="bf16"):
+        '''`suspects`, and for every suspect: does the text that FOLLOWS read better with one of the model's alternatives than
+        with the character that was written?  Returns (found, bits), both in input order; `bits` and texts, contexts, k,
+        streams, max_prob, min_rank and precision are as in `suspects`, and `found[i]` is a ratebatch.Corrections: the five
+        arrays of `suspects(...)[0][i]`, bit for bit, plus `cost` [m,R] f64, `best_id` [m] i32 and `gain` [m] f64.
+
+        A suspect at position j of a text of n characters has R = k + 1 + deletions variants: 0 the character as written,
+        v = 1 .. k the alternative alt_ids[:, v-1] in its place (no variant where that is -1 or the character itself), k + 1
+        (deletions only) the character dropped (no variant at the text's last character).  With L = min(left, j) and
+        A = min(ahead, n - 1 - j), a variant's cost is -sum log2(max(p, 1e-99)), in f64, over the predictions of its own
+        character (if it has one) and the A characters after it, made by a stateful window that starts from a ZERO state and
+        has read the L characters in front of the suspect; +inf where there is no such variant.  `best_id` is the id of the
+        variant v >= 1 of least cost (the smallest v among equal costs; Corrections.DELETE = -2 for the dropped character) and
+        `gain` = cost[0] - cost[best] in bits -- kept only where gain >= min_gain, else Corrections.NO_PROPOSAL = -1 and 0.0.
+        `Corrections.apply(text, mapping)` writes the kept proposals into a text.
+
+        The left context is cut at `left` characters and starts from a zero state: exact for a suspect within the first `left`
+        characters of its text, beyond that an approximation -- one that the written variant and its alternatives share, so the
+        comparison between them stays fair.  The first-pass alternatives are the model's guess from the left context alone;
+        `cost[:, 0]` is therefore NOT derived from `probs`.
+
+        On the HIP engine the id corpus, the text offsets, the contexts and the selection stay on the device; suspects are taken
+        in chunks of max(1, streams // R): zero states, `variant_windows` at T = max(left + ahead, 3), one `rate_window_bulk`
+        ("bf16") or `rate_window` ("split"), the rows' f64 bits are the costs.  Beyond the suspects' records (8k + 16 bytes each)
+        12 * R bytes per suspect leave the device.  ValueError for a stateless rater, left < 1, ahead < 0 or
+        left + ahead > 1024.  State and precision afterwards are as after `suspects`.'''
+        assert self.status > 1
+        assert self.incremental is False
+        if precision not in ("split", "bf16"):
+            raise ValueError('precision must be "split" or "bf16" (got %r)' % (precision,))
+        if not self.stateful:
+            raise ValueError('corrections needs a stateful rater: it rates through stateful windows')
+        left, ahead, deletions = int(left), int(ahead), int(bool(deletions))
+        if left < 1 or ahead < 0 or left + ahead > 1024:
+            raise ValueError("left >= 1, ahead >= 0 and left + ahead <= 1024 (got %d, %d)" % (left, ahead))
+        k, min_rank = int(k), int(min_rank)
+        assert 1 <= k <= ratebatch.ALTS_MAX, "k must be in 1..%d" % ratebatch.ALTS_MAX
+        limit = np.float32(max_prob)
+        if min_rank < 0:
+            raise ValueError("min_rank must be >= 0 (got %d): a character without a prediction is no suspect" % min_rank)
+        if np.isnan(limit):
+            raise ValueError("max_prob must not be NaN")
+        texts = list(texts)
+        n = len(texts)
+        lm = self.model
+        R = k + 1 + deletions
+        chunk = max(1, int(streams) // R)
+        T = max(left + ahead, ratebulk.MIN_T)
+        empty = (np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.float32), np.zeros(0, dtype=np.int32),
+                 np.zeros((0, k), dtype=np.int32), np.zeros((0, k), dtype=np.float32))
+        if hasattr(lm, 'variant_windows'):
+            keep = {}
+            plan, arrays, bits = self._alternatives_in_corpus_order(texts, contexts, k, streams, precision, keep=keep)
+            offsets = plan.offsets
+            sel_d = lm.rate_select(*arrays, max_prob=float(limit), min_rank=min_rank) if arrays is not None else None
+            del arrays
+            S = int(sel_d[0].numel()) if sel_d is not None else 0
+            sel = [_np(t) for t in sel_d] if S else empty
+            costs, valids = [], []
+            for a in range(0, S, chunk):
+                b = min(S, a + chunk)
+                x, z, y, ok = lm.variant_windows(keep["corpus"], keep["offsets"], keep["text_ctx"] if lm.n_ctx else None,
+                                                 sel_d[0][a:b], sel_d[3][a:b], left, ahead, deletions, T)
+                lm.reset_states(int(x.shape[0]))
+                if precision == "bf16":
+                    lm.rate_window_bulk(x, z, y, want_probs=False)
+                else:
+                    lm.rate_window(x, z, y, want_probs=False)
+                costs.append(lm.rate_bits_take_all())
+                valids.append(ok)
+            if S:
+                cost, valid = _np(lm.torch.cat(costs)).reshape(S, R), _np(lm.torch.cat(valids)).reshape(S, R)
+                lm.rate_status_check()
+                lm.reset_states(1)
+        else:
+            # an engine without the device path (the tests' CPU double): `suspects`, the numpy statement of the windows, the
+            # whole softmax of every window and the logs summed on the host
+            found, bits = self.suspects(texts, contexts, k=k, streams=streams, max_prob=max_prob, min_rank=min_rank,
+                                        precision=precision)
+            ids = [windows.encode(windows.normalize(t), self.mapping[0]) for t in texts]
+            offsets = np.concatenate([[0], np.cumsum([len(a) for a in ids])]).astype(np.int64)
+            sel = [np.concatenate([getattr(f, name) for f in found]) if n else e
+                   for name, e in zip(("positions", "probs", "rank", "alt_ids", "alt_probs"), empty)]
+            sel[0] = sel[0] + np.repeat(offsets[:-1], [len(f) for f in found])
+            S = len(sel[0])
+            if S:
+                corpus = np.concatenate(ids).astype(np.int32)
+                text_ctx = np.asarray([windows.clamp_context(c) for c in self._contexts_per_text(contexts, n)], dtype=np.int32)
+                text_ctx = text_ctx.reshape(n, -1)
+                cost, valid = np.zeros(S * R, dtype=np.float64), np.zeros(S * R, dtype=np.int32)
+                for a in range(0, S, chunk):
+                    b = min(S, a + chunk)
+                    x, z, y, ok = ratebulk.variant_windows_host(corpus, offsets, text_ctx, sel[0][a:b], sel[3][a:b], left, ahead,
+                                                                deletions, T)
+                    lm.reset_states(len(x))
+                    full = _np(lm.forward_window(x, z, want_probs=True)).astype(np.float64)
+                    p = np.take_along_axis(full, np.maximum(y, 0)[:, :, None], axis=2)[:, :, 0]
+                    cost[a * R:b * R] = -np.where(y >= 0, np.log2(np.maximum(p, 1e-99)), 0.0).sum(axis=1)
+                    valid[a * R:b * R] = ok
+                cost, valid = cost.reshape(S, R), valid.reshape(S, R)
+                lm.reset_states(1)
+        if not S:
+            cost, valid = np.zeros((0, R), dtype=np.float64), np.zeros((0, R), dtype=np.int32)
+        cost, best, gain = ratebulk.variant_pick_host(cost, valid)
+        best_id = np.full(S, ratebatch.Corrections.NO_PROPOSAL, dtype=np.int32)
+        swap = np.nonzero((best >= 1) & (best <= k))[0]
+        best_id[swap] = sel[3][swap, best[swap] - 1]
+        best_id[best == k + 1] = ratebatch.Corrections.DELETE
+        with np.errstate(invalid="ignore"):
+            drop = (best == 0) | ~(gain >= float(min_gain))
+        best_id[drop] = ratebatch.Corrections.NO_PROPOSAL
+        gain[drop] = 0.0
+        # (positions ascend over the corpus: a text's share is one slice)
+        pos = sel[0]
+        lo = np.searchsorted(pos, offsets[:-1], side="left")
+        hi = np.searchsorted(pos, offsets[1:], side="left")
+        return [ratebatch.Corrections(pos[a:b] - offsets[i], *([f[a:b].copy() for f in sel[1:]]
+                                                               + [cost[a:b].copy(), best_id[a:b].copy(), gain[a:b].copy()]))
+                for i, (a, b) in enumerate(zip(lo, hi))], bits
+
+    def _contexts_per_text(self, contexts, n):
+        '''None, one context list for all texts, or one per text -> one list per text (as `rate_batch` reads them)'''
+        if contexts is None or len(contexts) == 0:
+            return [self.underspecify_contexts()] * n
+        if isinstance(contexts[0], (int, np.integer)):
+            return [list(contexts)] * n
+        assert len(contexts) == n, "one context list per text"
+        return [list(c) if (c is not None and len(c)) else self.underspecify_contexts() for c in contexts]
 
     def rate2(self, text, context=None):
         '''Rate a string one by one (rating.py:531-576): resets the state, feeds one

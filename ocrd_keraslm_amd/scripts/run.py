@@ -8,6 +8,8 @@ Additional command `score`: bits per character and perplexity of every DATA file
 (Rater.rate_batch; --precision bf16 takes the bulk path on the training forward).
 Additional command `suspects`: per DATA file the characters the model does not believe, with what it expected instead
 (Rater.suspects: rated in bulk, picked out on the device).
+Additional command `correct`: the suspects of every DATA file with their alternatives rescored against the text that follows,
+and what that proposes to write instead (Rater.corrections); --apply also gives the corrected text.
 Additional options on `train`: --streams (stateful streams per GPU, default 1 = the
 reference's batching) and --segment-streams (with fewer files than streams, cut the files
 into contiguous segments on window boundaries, one list of segments per stream).  Under `python -m torch.distributed.run` training is
@@ -24,7 +26,7 @@ import click
 
 from .. import lib
 
-COMMAND_ORDER = ['train', 'test', 'score', 'suspects', 'apply', 'generate', 'print-history', 'print-charset', 'prune-charset',
+COMMAND_ORDER = ['train', 'test', 'score', 'suspects', 'correct', 'apply', 'generate', 'print-history', 'print-charset', 'prune-charset',
                  'plot-char-embeddings-similarity', 'plot-context-embeddings-similarity', 'plot-context-embeddings-projection']
 
 
@@ -233,6 +235,60 @@ def suspects(model, streams, precision, k, max_prob, min_rank, data):
                 for j, p, r, chars, probs in zip(one.positions, one.probs, one.rank, one.chars(rater.mapping), one.alt_probs)]
         click.echo(json.dumps({"file": name, "chars": len(text), "bits_per_char": float(total) / max(len(text) - 1, 1),
                                "suspects": rows}, ensure_ascii=False))
+
+
+@cli.command(short_help='propose corrections for the characters of every file that the model does not believe')
+@click.option('-m', '--model', default="model.h5", show_default=True, help='model file', type=click.Path(dir_okay=False, exists=True))
+@click.option('-s', '--streams', default=1024, show_default=True, help='rows of a window call: files in the first pass, hypotheses in the second',
+              type=click.IntRange(min=1, max=4096))
+@click.option('--precision', default='bf16', show_default=True, type=click.Choice(['bf16', 'split']),
+              help='bf16: bulk rating on the training forward; split: the inference kernels, ~f32 accuracy')
+@click.option('-k', 'k', default=3, show_default=True, type=click.IntRange(min=1, max=8),
+              help='characters the model expected most, tried per suspect')
+@click.option('--max-prob', default=0.01, show_default=True, type=click.FLOAT,
+              help='a suspect has at most this probability')
+@click.option('--min-rank', default=1, show_default=True, type=click.IntRange(min=0),
+              help='... and at least this rank among the characters the model could have written (0: its first choice)')
+@click.option('--left', default=64, show_default=True, type=click.IntRange(min=1, max=1024),
+              help='characters in front of a suspect that a hypothesis is read from (from a zero state)')
+@click.option('--ahead', default=8, show_default=True, type=click.IntRange(min=0, max=1023),
+              help='characters after a suspect that a hypothesis is held against')
+@click.option('--deletions', is_flag=True, default=False, help='also try dropping the suspect character')
+@click.option('--min-gain', default=1.0, show_default=True, type=click.FLOAT,
+              help='a proposal must save at least this many bits against the text as written')
+@click.option('--apply', 'apply_', is_flag=True, default=False, help='also give the text with the proposals applied ("corrected")')
+@click.argument('data', nargs=-1, type=click.Path(exists=True, dir_okay=True, file_okay=True))
+def correct(model, streams, precision, k, max_prob, min_rank, left, ahead, deletions, min_gain, apply_, data):
+    """Apply a language model to DATA files and print one JSON line per file, as `suspects` does, with
+       "corrections": one [position, written, proposed, gain] per suspect -- proposed is null for no
+       proposal and "" for dropping the character, gain the bits the proposal saves over the LEFT characters
+       in front of the suspect and the AHEAD characters after it.  With --apply the line also holds the
+       corrected text.
+    """
+    from ..lib import windows
+    if left + ahead > 1024:
+        raise click.UsageError("--left + --ahead must not exceed 1024")
+    rater = _load(model)
+    names, texts, contexts = [], [], []
+    for file in _open_all(data):
+        with file:
+            texts.append(windows.normalize(file.read()))
+        names.append(file.name)
+        contexts.append(windows.context_from_filename(file.name))
+    if not texts:
+        return
+    found, bits = rater.corrections(texts, contexts, k=k, streams=streams, max_prob=max_prob, min_rank=min_rank, left=left,
+                                    ahead=ahead, deletions=deletions, min_gain=min_gain, precision=precision)
+    for name, text, one, total in zip(names, texts, found, bits):
+        rows = [[int(j), text[int(j)], float(p), int(r), [[c, float(q)] for c, q in zip(chars, probs)]]
+                for j, p, r, chars, probs in zip(one.positions, one.probs, one.rank, one.chars(rater.mapping), one.alt_probs)]
+        proposals = [[int(j), text[int(j)], new, float(g)]
+                     for j, new, g in zip(one.positions, one.proposals(rater.mapping), one.gain)]
+        line = {"file": name, "chars": len(text), "bits_per_char": float(total) / max(len(text) - 1, 1), "suspects": rows,
+                "corrections": proposals}
+        if apply_:
+            line["corrected"] = one.apply(text, rater.mapping)
+        click.echo(json.dumps(line, ensure_ascii=False))
 
 
 @cli.command(short_help='sample characters from language model')
