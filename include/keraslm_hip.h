@@ -17,6 +17,7 @@
  *   ... for a whole corpus, on the training forward (bf16)    kl_rate_window_bulk, kl_rate_scatter, kl_rate_text_bits
  *   ... with alternatives, and the suspect positions picked out  kl_rate_window_alts_bulk, kl_rate_scatter_alts, kl_rate_select
  *   ... and the suspects' alternatives rescored against what follows  kl_variant_windows (rows for kl_rate_window(_bulk))
+ *   ... with a lost character inserted in front of the suspect         kl_edit_windows
  *   model.predict_on_batch, stateful (1,1) step, :566        kl_forward_window with T = 1
  *   model.predict_on_batch, incremental + states, :631       kl_step_batch
  *   ... once per character of a lattice edge, :796-851       kl_walk_batch_host (all characters of all hypotheses, one call)
@@ -268,6 +269,24 @@ int kl_rate_select(const float* probs, const int32_t* rank, const int32_t* alt_i
 int kl_variant_windows(const int32_t* corpus, size_t n_corpus, const int64_t* offsets, int n_texts, const int32_t* text_ctx,
                        int n_ctx, const int64_t* sel_pos, const int32_t* sel_alt_id, int S, int K, int left, int ahead,
                        int deletions, int T, int32_t* idx, int32_t* ctx, int32_t* tgt, int32_t* valid, void* stream);
+
+/* kl_variant_windows with insertion hypotheses: for a character the text has lost in front of the suspect.  Arguments, rows,
+ * outputs and launch as kl_variant_windows; with L, A, w as there, a suspect has
+ *   R = K + 1 + deletions + K * insertions
+ * variants, row b = s * R + v.  The rows v = 0 .. K + deletions are kl_variant_windows' rows at its indices; with
+ * insertions == 1 there are K more:
+ *   v = K + 1 + deletions + j  (j = 0 .. K-1)   q = x[g-L .. g-1], a, w, x[g+1 .. g+A]  with a = sel_alt_id[s][j],
+ *                                               len = L + 2 + A;  invalid if v = 0 is, or a < 0
+ * a == w is valid (a doubled character that lost its twin), and so is the unmapped id 0, as it is for substitution.  The rule
+ * per word is kl_variant_windows': idx[b][t] = q[t] for t < len - 1, else 0;  tgt[b][t] = q[t+1] for L - 1 <= t < len - 1,
+ * else -1;  ctx[b][t][c] = text_ctx[i][c] for t < len - 1, else 0;  valid[b] = 1  -- a window from a zero state over an
+ * insertion row predicts a, then w, then the A characters after it.  An invalid row is the same dummy stream.  A fed row is
+ * up to left + ahead + 1 long: T >= left + ahead + insertions.  insertions == 0 is kl_variant_windows, word for word.
+ * KL_ERR_ARG, before any launch, for everything kl_variant_windows rejects, insertions outside {0, 1},
+ * T < left + ahead + insertions, S * R > 2^22 (with this R). */
+int kl_edit_windows(const int32_t* corpus, size_t n_corpus, const int64_t* offsets, int n_texts, const int32_t* text_ctx,
+                    int n_ctx, const int64_t* sel_pos, const int32_t* sel_alt_id, int S, int K, int left, int ahead, int deletions,
+                    int insertions, int T, int32_t* idx, int32_t* ctx, int32_t* tgt, int32_t* valid, void* stream);
 
 /* One training batch, forward + backward (rating.py:292-298 -> train_on_batch):
  * writes the gradient of (mean CE + embedding regularisers, rating.py:187-246)

@@ -693,12 +693,15 @@ class HipLM:
                 call(m, out)
         return out
 
-    def variant_windows(self, corpus_d, offsets_d, text_ctx_d, sel_pos_d, sel_alt_id_d, left, ahead, deletions, T):
-        """kl_variant_windows: the hypothesis rows of S suspects, built on the device in one launch.  corpus_d int32 [n] and
+    def variant_windows(self, corpus_d, offsets_d, text_ctx_d, sel_pos_d, sel_alt_id_d, left, ahead, deletions, T,
+                        insertions=False):
+        """kl_edit_windows (kl_variant_windows with insertion rows): the hypothesis rows of S suspects, built on the device in one launch.  corpus_d int32 [n] and
         offsets_d int64 [n_texts + 1] as bulk rating keeps them, text_ctx_d int32 [n_texts, n_ctx] (None without contexts),
         sel_pos_d int64 [S] and sel_alt_id_d int32 [S, K] as `rate_select` returns them (or slices of them) -- all DEVICE
         tensors.  Returns the DEVICE tensors (idx [S*R, T], ctx [S*R, T, n_ctx], tgt [S*R, T], valid [S*R]) int32 with
-        R = K + 1 + deletions, row s * R + v: what `ratebulk.variant_windows_host` states.  No synchronisation."""
+        R = K + 1 + deletions + K * insertions, row s * R + v: what `ratebulk.variant_windows_host` states (insertions: every
+        alternative once more, in front of the written character; T >= left + ahead + 1 then).  hipabi.KlError for what the
+        entry point rejects.  No synchronisation."""
         torch = self.torch
         n_ctx = 0 if text_ctx_d is None else int(text_ctx_d.shape[-1])
         tensors = [corpus_d, offsets_d, sel_pos_d, sel_alt_id_d] + ([text_ctx_d] if n_ctx else [])
@@ -712,17 +715,19 @@ class HipLM:
             raise hipabi.KlError("variant_windows: corpus int32 [n], offsets int64 [n_texts + 1], text_ctx int32 [n_texts, n_ctx], "
                                  "sel_pos int64 [S], sel_alt_id int32 [S, K], contiguous, on the device")
         K = int(sel_alt_id_d.shape[1])
-        left, ahead, deletions, T = int(left), int(ahead), int(bool(deletions)), int(T)
-        rows = S * (K + 1 + deletions)
+        left, ahead, deletions, T, insertions = int(left), int(ahead), int(bool(deletions)), int(T), int(insertions)
+        if insertions not in (0, 1):
+            raise hipabi.KlError("variant_windows: insertions is a flag (got %d)" % insertions)
+        rows = S * (K + 1 + deletions + K * insertions)
         with self._launch():
             idx = torch.empty((rows, T), dtype=torch.int32, device=self.device)
             tgt = torch.empty((rows, T), dtype=torch.int32, device=self.device)
             ctx = torch.empty((rows, T, n_ctx), dtype=torch.int32, device=self.device)
             valid = torch.empty(rows, dtype=torch.int32, device=self.device)
-            hipabi.check(self.lib.kl_variant_windows(
+            hipabi.check(self.lib.kl_edit_windows(
                 _ptr(corpus_d), corpus_d.numel(), _ptr(offsets_d), n_texts, _ptr(text_ctx_d) if n_ctx else None, n_ctx,
-                _ptr(sel_pos_d), _ptr(sel_alt_id_d), S, K, left, ahead, deletions, T, _ptr(idx), _ptr(ctx) if n_ctx else None,
-                _ptr(tgt), _ptr(valid), self._stream()), "kl_variant_windows")
+                _ptr(sel_pos_d), _ptr(sel_alt_id_d), S, K, left, ahead, deletions, insertions, T, _ptr(idx),
+                _ptr(ctx) if n_ctx else None, _ptr(tgt), _ptr(valid), self._stream()), "kl_edit_windows")
         return idx, ctx, tgt, valid
 
     def rate_bits_take_all(self):

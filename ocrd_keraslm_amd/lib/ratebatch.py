@@ -141,35 +141,61 @@ class Suspects(object):
 class Corrections(Suspects):
     """One text's share of `Rater.corrections`: the m suspects of `Rater.suspects` (the five arrays above, bit for bit) and
     what rescoring their alternatives against the text that follows proposes.  With k alternatives and R = k + 1 (+ 1 with
-    deletions) variants per suspect -- 0: the character as written, v = 1 .. k: alt_ids[:, v-1] in its place, k + 1: the
-    character dropped --:
+    deletions, + k with insertions) variants per suspect -- 0: the character as written, v = 1 .. k: alt_ids[:, v-1] in its
+    place, k + 1 (deletions): the character dropped, from k + 1 + deletions on (insertions): alt_ids[:, j] inserted in front
+    of the character, j = 0 .. k-1 --:
 
-    cost       [m,R] f64  bits of the variant's character and the characters after it (+inf: no such variant)
-    best_id    [m] i32    the id proposed in place of the character; NO_PROPOSAL (-1): none, DELETE (-2): drop the character
+    cost       [m,R] f64  bits of the variant's character(s) and the characters after it (+inf: no such variant)
+    best_id    [m] i32    the id proposed in place of the character, or in front of it; NO_PROPOSAL (-1): none, DELETE (-2):
+                          drop the character
     gain       [m] f64    bits saved by the proposal against the text as written (0.0 without a proposal)
+    best_op    [m] i32    what the proposal does: OP_NONE, OP_SUBSTITUTE (best_id for the character), OP_DELETE, OP_INSERT
+                          (best_id in front of the character, which stays); derived from best_id where it is not given
     """
     NO_PROPOSAL = -1
     DELETE = -2
+    OP_NONE, OP_SUBSTITUTE, OP_DELETE, OP_INSERT = 0, 1, 2, 3
 
-    def __init__(self, positions, probs, rank, alt_ids, alt_probs, cost, best_id, gain):
+    def __init__(self, positions, probs, rank, alt_ids, alt_probs, cost, best_id, gain, best_op=None):
         Suspects.__init__(self, positions, probs, rank, alt_ids, alt_probs)
         self.cost, self.best_id, self.gain = cost, best_id, gain
+        if best_op is None:
+            ids = np.asarray(best_id)
+            best_op = np.where(ids >= 0, self.OP_SUBSTITUTE, np.where(ids == self.DELETE, self.OP_DELETE, self.OP_NONE))
+            best_op = best_op.astype(np.int32)
+        self.best_op = best_op
 
     def proposals(self, mapping):
-        """the proposals as characters, [m]: None for no proposal, "" for a deletion, else the character -- the unmapped id 0
-        has no character to write and shows as None too.  mapping as in `RatedText.chars`."""
+        """the proposals as characters, [m]: None for no proposal, "" for a deletion, else the character (substituted, or
+        inserted: `best_op` says which, `edits` gives what replaces the written character) -- the unmapped id 0 has no
+        character to write and shows as None too.  mapping as in `RatedText.chars`."""
         i_c = mapping[1] if isinstance(mapping, (tuple, list)) else mapping
         return ["" if v == self.DELETE else (i_c.get(int(v)) if v >= 0 else None) for v in self.best_id]
 
+    def edits(self, text, mapping):
+        """per suspect the string that replaces text[position], [m]: "" drops the character, "x" substitutes it, "xw" inserts
+        x in front of the written w; None for no proposal, a proposal of the unmapped id 0 (no character to write) and a
+        position outside the text.  text is the normalised text, mapping as in `RatedText.chars`."""
+        out = []
+        for at, op, new in zip(self.positions, self.best_op, self.proposals(mapping)):
+            at = int(at)
+            if new is None or op == self.OP_NONE or not 0 <= at < len(text):
+                out.append(None)
+            elif op == self.OP_INSERT:
+                out.append(new + text[at])
+            else:
+                out.append(new)
+        return out
+
     def apply(self, text, mapping):
-        """the (normalised) text with the proposals applied, from right to left so that positions stay true; a proposal of the
-        unmapped id 0 leaves the character as written"""
+        """the (normalised) text with the proposals applied (`edits`), from right to left so that positions stay true; a
+        proposal of the unmapped id 0 leaves the character as written"""
         chars = list(text)
-        proposed = self.proposals(mapping)
+        edits = self.edits(text, mapping)
         for j in range(len(self.positions) - 1, -1, -1):
-            at, new = int(self.positions[j]), proposed[j]
-            if new is not None and 0 <= at < len(chars):
-                chars[at:at + 1] = [new] if new else []
+            if edits[j] is not None:
+                at = int(self.positions[j])
+                chars[at:at + 1] = list(edits[j])
         return "".join(chars)
 
 

@@ -19,7 +19,7 @@ Rules of the plan:
 `windows_host`, `scatter_host` and `text_bits_host` state in numpy what kl_assemble_windows, kl_rate_scatter and
 kl_rate_text_bits compute; `scatter_alts_host` and `select_host` what kl_rate_scatter_alts and kl_rate_select do for rating
 with alternatives (`Rater.rate_alternatives(precision="bf16")`, `Rater.suspects`); `variant_windows_host` what
-kl_variant_windows makes of the suspects for `Rater.corrections`, and `variant_pick_host` is the choice among a suspect's
+kl_variant_windows / kl_edit_windows make of the suspects for `Rater.corrections`, and `variant_pick_host` is the choice among a suspect's
 variants (numpy on every path: S * R doubles).  numpy only: the plan is built and tested without an engine.
 """
 from __future__ import annotations
@@ -196,30 +196,37 @@ def text_bits_host(probs, offsets):
     return out
 
 
-def variant_windows_host(corpus, offsets, text_ctx, sel_pos, sel_alt_id, left, ahead, deletions, T):
-    """what kl_variant_windows makes of S suspects (sel_pos [S] corpus positions, sel_alt_id [S, K] their alternatives): the
-    R = K + 1 + deletions hypothesis rows of each, row b = s * R + v.  For g = sel_pos[s] in text i (offsets[i] <= g <
+def variant_windows_host(corpus, offsets, text_ctx, sel_pos, sel_alt_id, left, ahead, deletions, T, insertions=0):
+    """what kl_variant_windows (kl_edit_windows with insertions) makes of S suspects (sel_pos [S] corpus positions, sel_alt_id
+    [S, K] their alternatives): the R = K + 1 + deletions + K * insertions hypothesis rows of each, row b = s * R + v.  For g = sel_pos[s] in text i (offsets[i] <= g <
     offsets[i + 1]), w = corpus[g], L = min(left, g - offsets[i]), A = min(ahead, offsets[i + 1] - 1 - g):
       v = 0       q = x[g-L .. g-1], w, x[g+1 .. g+A]           invalid if L == 0 or g is in no text or beyond the corpus
       v = 1 .. K  the same with a = sel_alt_id[s][v-1] for w    invalid if v = 0 is, or a < 0, or a == w
       v = K + 1   q = x[g-L .. g-1], x[g+1 .. g+A]              (deletions only) invalid if v = 0 is, or A == 0
+      v = K + 1 + deletions + j, j = 0 .. K-1  (insertions only: a character the text has lost in front of the suspect)
+                  q = x[g-L .. g-1], a, w, x[g+1 .. g+A]        with a = sel_alt_id[s][j], len = L + 2 + A; invalid if v = 0
+                                                                is, or a < 0 -- a == w (a doubled character that lost its
+                                                                twin) and the unmapped id 0 are valid
     A valid row: idx[t] = q[t] for t < len - 1, else 0; tgt[t] = q[t+1] for L - 1 <= t < len - 1, else -1; ctx[t] =
-    text_ctx[i] for t < len - 1, else 0.  An invalid row is a dummy stream (idx 0, ctx 0, tgt -1).  text_ctx: [n_texts, n_ctx]
-    (None: no contexts).  Positions outside [0, min(len(corpus), offsets[-1])) read as 0.
+    text_ctx[i] for t < len - 1, else 0 -- a window from a zero state over an insertion row predicts a, then w, then the A
+    characters after it.  An invalid row is a dummy stream (idx 0, ctx 0, tgt -1).  text_ctx: [n_texts, n_ctx] (None: no
+    contexts).  Positions outside [0, min(len(corpus), offsets[-1])) read as 0.  A fed row is up to left + ahead + insertions
+    long: left + ahead + insertions <= T <= 1024.  The rows v <= K + deletions do not depend on `insertions`.
     Returns (idx [S*R, T], ctx [S*R, T, n_ctx], tgt [S*R, T], valid [S*R]) int32."""
     corpus = np.asarray(corpus, dtype=np.int32).reshape(-1)
     offsets = np.asarray(offsets, dtype=np.int64).reshape(-1)
     g = np.asarray(sel_pos, dtype=np.int64).reshape(-1)
     alts = np.asarray(sel_alt_id, dtype=np.int32)
     S, K = alts.shape
-    left, ahead, deletions, T = int(left), int(ahead), int(deletions), int(T)
+    left, ahead, deletions, T, insertions = int(left), int(ahead), int(deletions), int(T), int(insertions)
     n_texts = len(offsets) - 1
     if (S != len(g) or S < 1 or n_texts < 1 or K < 1 or left < 1 or ahead < 0 or deletions not in (0, 1)
-            or not left + ahead <= T <= 1024):
-        raise ValueError("variant_windows_host: S, n_texts, K, left >= 1, ahead >= 0, deletions in {0, 1}, left + ahead <= T <= 1024")
+            or insertions not in (0, 1) or not left + ahead + insertions <= T <= 1024):
+        raise ValueError("variant_windows_host: S, n_texts, K, left >= 1, ahead >= 0, deletions and insertions in {0, 1}, "
+                         "left + ahead + insertions <= T <= 1024")
     text_ctx = np.zeros((n_texts, 0), dtype=np.int32) if text_ctx is None else np.asarray(text_ctx, dtype=np.int32)
     text_ctx = text_ctx.reshape(n_texts, -1)
-    R = K + 1 + deletions
+    R = K + 1 + deletions + K * insertions
     limit = min(len(corpus), int(offsets[-1]))
 
     def read(at):
@@ -234,8 +241,10 @@ def variant_windows_host(corpus, offsets, text_ctx, sel_pos, sel_alt_id, left, a
     A = np.where(found, np.minimum(ahead, offsets[i + 1] - 1 - g), 0)
     base = found & (L >= 1)
     w = read(g)
-    # per variant [S, R]: the character in the suspect's place (if any) and whether the row is valid
-    char = np.concatenate([w[:, None], alts] + ([np.zeros((S, 1), dtype=np.int32)] if deletions else []), axis=1)
+    # per variant [S, R]: the character at q[L] (if the variant has one of its own), how many characters stand for the
+    # suspect (0 dropped, 1, 2 with one inserted in front of it) and whether the row is valid
+    char = np.concatenate([w[:, None], alts] + ([np.zeros((S, 1), dtype=np.int32)] if deletions else [])
+                          + ([alts] if insertions else []), axis=1)
     has = np.ones(R, dtype=np.int64)
     valid = np.empty((S, R), dtype=bool)
     valid[:, 0] = base
@@ -243,12 +252,16 @@ def variant_windows_host(corpus, offsets, text_ctx, sel_pos, sel_alt_id, left, a
     if deletions:
         has[K + 1] = 0
         valid[:, K + 1] = base & (A > 0)
+    if insertions:
+        has[K + 1 + deletions:] = 2
+        valid[:, K + 1 + deletions:] = base[:, None] & (alts >= 0)
     t = np.arange(T + 1, dtype=np.int64)[None, None, :]
     L3, g3 = L[:, None, None], g[:, None, None]
     has3 = has[None, :, None]
     length = L3 + has3 + A[:, None, None]
+    # from t = L on the corpus is read one ahead (the character dropped) or one behind (one inserted in front of it)
     q = read(g3 - L3 + t + (1 - has3) * (t >= L3))
-    q = np.where((has3 == 1) & (t == L3), char[:, :, None], q)
+    q = np.where((has3 >= 1) & (t == L3), char[:, :, None], q)
     fed = valid[:, :, None] & (t[:, :, :T] < length - 1)
     idx = np.where(fed, q[:, :, :T], 0).astype(np.int32)
     tgt = np.where(fed & (t[:, :, :T] >= L3 - 1), q[:, :, 1:], -1).astype(np.int32)
@@ -261,7 +274,8 @@ def variant_pick_host(cost, valid):
     """the choice among a suspect's variants: cost [S, R] f64 (bits of the text around the suspect under variant v; v = 0 is
     the text as written), valid [S, R].  Returns (cost with +inf where invalid, best [S] int32, gain [S] f64): best is the
     valid v >= 1 of least cost, the smallest such v among equal costs, 0 if there is none; gain = cost[0] - cost[best] in bits
-    (negative where every variant reads worse than what was written), 0.0 where best is 0."""
+    (negative where every variant reads worse than what was written), 0.0 where best is 0.  Generic in R: with the rows of
+    `variant_windows_host` the tie rule orders substitution < deletion < insertion, and within a kind by alternative rank."""
     cost = np.array(cost, dtype=np.float64, copy=True)
     valid = np.asarray(valid).astype(bool)
     S, R = cost.shape

@@ -1126,21 +1126,27 @@ class Rater(object):
                 for i, (a, b) in enumerate(zip(lo, hi))], bits
 
     def corrections(self, texts, contexts=None, k=3, streams=1024, max_prob=0.01, min_rank=1, left=64, ahead=8, deletions=False,
-                    min_gain=1.0, precision="bf16"):
+                    min_gain=1.0, precision="bf16", insertions=False):
         '''`suspects`, and for every suspect: does the text that FOLLOWS read better with one of the model's alternatives than
         with the character that was written?  Returns (found, bits), both in input order; `bits` and texts, contexts, k,
         streams, max_prob, min_rank and precision are as in `suspects`, and `found[i]` is a ratebatch.Corrections: the five
-        arrays of `suspects(...)[0][i]`, bit for bit, plus `cost` [m,R] f64, `best_id` [m] i32 and `gain` [m] f64.
+        arrays of `suspects(...)[0][i]`, bit for bit, plus `cost` [m,R] f64, `best_id` [m] i32, `gain` [m] f64 and `best_op`
+        [m] i32.
 
-        A suspect at position j of a text of n characters has R = k + 1 + deletions variants: 0 the character as written,
-        v = 1 .. k the alternative alt_ids[:, v-1] in its place (no variant where that is -1 or the character itself), k + 1
-        (deletions only) the character dropped (no variant at the text's last character).  With L = min(left, j) and
-        A = min(ahead, n - 1 - j), a variant's cost is -sum log2(max(p, 1e-99)), in f64, over the predictions of its own
-        character (if it has one) and the A characters after it, made by a stateful window that starts from a ZERO state and
-        has read the L characters in front of the suspect; +inf where there is no such variant.  `best_id` is the id of the
-        variant v >= 1 of least cost (the smallest v among equal costs; Corrections.DELETE = -2 for the dropped character) and
-        `gain` = cost[0] - cost[best] in bits -- kept only where gain >= min_gain, else Corrections.NO_PROPOSAL = -1 and 0.0.
-        `Corrections.apply(text, mapping)` writes the kept proposals into a text.
+        A suspect at position j of a text of n characters has R = k + 1 + deletions + k * insertions variants: 0 the character
+        as written, v = 1 .. k the alternative alt_ids[:, v-1] in its place (no variant where that is -1 or the character
+        itself), k + 1 (deletions only) the character dropped (no variant at the text's last character), and (insertions only)
+        v = k + 1 + deletions + j, j = 0 .. k-1, the alternative alt_ids[:, j] inserted IN FRONT of the written character -- a
+        character the text has lost (no variant where that is -1; the written character doubled is one).  With L = min(left, j)
+        and A = min(ahead, n - 1 - j), a variant's cost is -sum log2(max(p, 1e-99)), in f64, over the predictions of its own
+        character(s) (none, one, or the inserted and the written one) and the A characters after it, made by a stateful window
+        that starts from a ZERO state and has read the L characters in front of the suspect; +inf where there is no such
+        variant.  An insertion explains the same written characters as variant 0 under a true text one character longer, as a
+        deletion does under one that is shorter.  `best_id` is the id of the variant v >= 1 of least cost (the smallest v among
+        equal costs: substitution before deletion before insertion; Corrections.DELETE = -2 for the dropped character),
+        `best_op` says which edit it is (Corrections.OP_SUBSTITUTE, OP_DELETE, OP_INSERT) and `gain` = cost[0] - cost[best] in
+        bits -- kept only where gain >= min_gain, else Corrections.NO_PROPOSAL = -1, OP_NONE and 0.0.
+        `Corrections.apply(text, mapping)` writes the kept proposals into a text, `Corrections.edits` lists them.
 
         The left context is cut at `left` characters and starts from a zero state: exact for a suspect within the first `left`
         characters of its text, beyond that an approximation -- one that the written variant and its alternatives share, so the
@@ -1148,19 +1154,20 @@ class Rater(object):
         `cost[:, 0]` is therefore NOT derived from `probs`.
 
         On the HIP engine the id corpus, the text offsets, the contexts and the selection stay on the device; suspects are taken
-        in chunks of max(1, streams // R): zero states, `variant_windows` at T = max(left + ahead, 3), one `rate_window_bulk`
-        ("bf16") or `rate_window` ("split"), the rows' f64 bits are the costs.  Beyond the suspects' records (8k + 16 bytes each)
-        12 * R bytes per suspect leave the device.  ValueError for a stateless rater, left < 1, ahead < 0 or
-        left + ahead > 1024.  State and precision afterwards are as after `suspects`.'''
+        in chunks of max(1, streams // R): zero states, `variant_windows` at T = max(left + ahead + insertions, 3), one
+        `rate_window_bulk` ("bf16") or `rate_window` ("split"), the rows' f64 bits are the costs.  Beyond the suspects' records
+        (8k + 16 bytes each) 12 * R bytes per suspect leave the device.  ValueError for a stateless rater, left < 1, ahead < 0 or
+        left + ahead + insertions > 1024.  State and precision afterwards are as after `suspects`.'''
         assert self.status > 1
         assert self.incremental is False
         if precision not in ("split", "bf16"):
             raise ValueError('precision must be "split" or "bf16" (got %r)' % (precision,))
         if not self.stateful:
             raise ValueError('corrections needs a stateful rater: it rates through stateful windows')
-        left, ahead, deletions = int(left), int(ahead), int(bool(deletions))
-        if left < 1 or ahead < 0 or left + ahead > 1024:
-            raise ValueError("left >= 1, ahead >= 0 and left + ahead <= 1024 (got %d, %d)" % (left, ahead))
+        left, ahead, deletions, insertions = int(left), int(ahead), int(bool(deletions)), int(bool(insertions))
+        if left < 1 or ahead < 0 or left + ahead + insertions > 1024:
+            raise ValueError("left >= 1, ahead >= 0 and left + ahead%s <= 1024 (got %d, %d)"
+                             % (" + 1 (insertions)" if insertions else "", left, ahead))
         k, min_rank = int(k), int(min_rank)
         assert 1 <= k <= ratebatch.ALTS_MAX, "k must be in 1..%d" % ratebatch.ALTS_MAX
         limit = np.float32(max_prob)
@@ -1171,9 +1178,9 @@ class Rater(object):
         texts = list(texts)
         n = len(texts)
         lm = self.model
-        R = k + 1 + deletions
+        R = k + 1 + deletions + k * insertions
         chunk = max(1, int(streams) // R)
-        T = max(left + ahead, ratebulk.MIN_T)
+        T = max(left + ahead + insertions, ratebulk.MIN_T)
         empty = (np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.float32), np.zeros(0, dtype=np.int32),
                  np.zeros((0, k), dtype=np.int32), np.zeros((0, k), dtype=np.float32))
         if hasattr(lm, 'variant_windows'):
@@ -1188,7 +1195,8 @@ class Rater(object):
             for a in range(0, S, chunk):
                 b = min(S, a + chunk)
                 x, z, y, ok = lm.variant_windows(keep["corpus"], keep["offsets"], keep["text_ctx"] if lm.n_ctx else None,
-                                                 sel_d[0][a:b], sel_d[3][a:b], left, ahead, deletions, T)
+                                                 sel_d[0][a:b], sel_d[3][a:b], left, ahead, deletions, T,
+                                                 insertions=bool(insertions))
                 lm.reset_states(int(x.shape[0]))
                 if precision == "bf16":
                     lm.rate_window_bulk(x, z, y, want_probs=False)
@@ -1219,7 +1227,7 @@ class Rater(object):
                 for a in range(0, S, chunk):
                     b = min(S, a + chunk)
                     x, z, y, ok = ratebulk.variant_windows_host(corpus, offsets, text_ctx, sel[0][a:b], sel[3][a:b], left, ahead,
-                                                                deletions, T)
+                                                                deletions, T, insertions)
                     lm.reset_states(len(x))
                     full = _np(lm.forward_window(x, z, want_probs=True)).astype(np.float64)
                     p = np.take_along_axis(full, np.maximum(y, 0)[:, :, None], axis=2)[:, :, 0]
@@ -1230,20 +1238,31 @@ class Rater(object):
         if not S:
             cost, valid = np.zeros((0, R), dtype=np.float64), np.zeros((0, R), dtype=np.int32)
         cost, best, gain = ratebulk.variant_pick_host(cost, valid)
-        best_id = np.full(S, ratebatch.Corrections.NO_PROPOSAL, dtype=np.int32)
+        # best v -> edit: 1 .. k substitute alt_ids[v-1]; k + 1 with deletions: delete; from k + 1 + deletions on: insert
+        Cor = ratebatch.Corrections
+        best_id = np.full(S, Cor.NO_PROPOSAL, dtype=np.int32)
+        best_op = np.full(S, Cor.OP_NONE, dtype=np.int32)
         swap = np.nonzero((best >= 1) & (best <= k))[0]
         best_id[swap] = sel[3][swap, best[swap] - 1]
-        best_id[best == k + 1] = ratebatch.Corrections.DELETE
+        best_op[swap] = Cor.OP_SUBSTITUTE
+        if deletions:
+            best_id[best == k + 1] = Cor.DELETE
+            best_op[best == k + 1] = Cor.OP_DELETE
+        put = np.nonzero(best >= k + 1 + deletions)[0]
+        best_id[put] = sel[3][put, best[put] - (k + 1 + deletions)]
+        best_op[put] = Cor.OP_INSERT
         with np.errstate(invalid="ignore"):
             drop = (best == 0) | ~(gain >= float(min_gain))
-        best_id[drop] = ratebatch.Corrections.NO_PROPOSAL
+        best_id[drop] = Cor.NO_PROPOSAL
+        best_op[drop] = Cor.OP_NONE
         gain[drop] = 0.0
         # (positions ascend over the corpus: a text's share is one slice)
         pos = sel[0]
         lo = np.searchsorted(pos, offsets[:-1], side="left")
         hi = np.searchsorted(pos, offsets[1:], side="left")
         return [ratebatch.Corrections(pos[a:b] - offsets[i], *([f[a:b].copy() for f in sel[1:]]
-                                                               + [cost[a:b].copy(), best_id[a:b].copy(), gain[a:b].copy()]))
+                                                               + [cost[a:b].copy(), best_id[a:b].copy(), gain[a:b].copy(),
+                                                                  best_op[a:b].copy()]))
                 for i, (a, b) in enumerate(zip(lo, hi))], bits
 
     def _contexts_per_text(self, contexts, n):

@@ -9,7 +9,8 @@ Additional command `score`: bits per character and perplexity of every DATA file
 Additional command `suspects`: per DATA file the characters the model does not believe, with what it expected instead
 (Rater.suspects: rated in bulk, picked out on the device).
 Additional command `correct`: the suspects of every DATA file with their alternatives rescored against the text that follows,
-and what that proposes to write instead (Rater.corrections); --apply also gives the corrected text.
+and what that proposes to write instead (Rater.corrections); --deletions also tries dropping the character, --insertions a
+lost character in front of it; --apply also gives the corrected text.
 Additional options on `train`: --streams (stateful streams per GPU, default 1 = the
 reference's batching) and --segment-streams (with fewer files than streams, cut the files
 into contiguous segments on window boundaries, one list of segments per stream).  Under `python -m torch.distributed.run` training is
@@ -254,20 +255,23 @@ def suspects(model, streams, precision, k, max_prob, min_rank, data):
 @click.option('--ahead', default=8, show_default=True, type=click.IntRange(min=0, max=1023),
               help='characters after a suspect that a hypothesis is held against')
 @click.option('--deletions', is_flag=True, default=False, help='also try dropping the suspect character')
+@click.option('--insertions', is_flag=True, default=False,
+              help='also try each expected character in front of the suspect: a character the text has lost')
 @click.option('--min-gain', default=1.0, show_default=True, type=click.FLOAT,
               help='a proposal must save at least this many bits against the text as written')
 @click.option('--apply', 'apply_', is_flag=True, default=False, help='also give the text with the proposals applied ("corrected")')
 @click.argument('data', nargs=-1, type=click.Path(exists=True, dir_okay=True, file_okay=True))
-def correct(model, streams, precision, k, max_prob, min_rank, left, ahead, deletions, min_gain, apply_, data):
+def correct(model, streams, precision, k, max_prob, min_rank, left, ahead, deletions, insertions, min_gain, apply_, data):
     """Apply a language model to DATA files and print one JSON line per file, as `suspects` does, with
-       "corrections": one [position, written, proposed, gain] per suspect -- proposed is null for no
-       proposal and "" for dropping the character, gain the bits the proposal saves over the LEFT characters
-       in front of the suspect and the AHEAD characters after it.  With --apply the line also holds the
-       corrected text.
+       "corrections": one [position, written, proposed, gain] per suspect -- proposed is what replaces the
+       written character: null for no proposal, "" for dropping it, one character for another in its place
+       and (--insertions) two for a lost character in front of it; gain the bits the proposal saves over the
+       LEFT characters in front of the suspect and the AHEAD characters after it.  With --apply the line also
+       holds the corrected text.
     """
     from ..lib import windows
-    if left + ahead > 1024:
-        raise click.UsageError("--left + --ahead must not exceed 1024")
+    if left + ahead + int(insertions) > 1024:
+        raise click.UsageError("--left + --ahead%s must not exceed 1024" % (" + 1 (--insertions)" if insertions else ""))
     rater = _load(model)
     names, texts, contexts = [], [], []
     for file in _open_all(data):
@@ -278,12 +282,13 @@ def correct(model, streams, precision, k, max_prob, min_rank, left, ahead, delet
     if not texts:
         return
     found, bits = rater.corrections(texts, contexts, k=k, streams=streams, max_prob=max_prob, min_rank=min_rank, left=left,
-                                    ahead=ahead, deletions=deletions, min_gain=min_gain, precision=precision)
+                                    ahead=ahead, deletions=deletions, min_gain=min_gain, precision=precision,
+                                    insertions=insertions)
     for name, text, one, total in zip(names, texts, found, bits):
         rows = [[int(j), text[int(j)], float(p), int(r), [[c, float(q)] for c, q in zip(chars, probs)]]
                 for j, p, r, chars, probs in zip(one.positions, one.probs, one.rank, one.chars(rater.mapping), one.alt_probs)]
         proposals = [[int(j), text[int(j)], new, float(g)]
-                     for j, new, g in zip(one.positions, one.proposals(rater.mapping), one.gain)]
+                     for j, new, g in zip(one.positions, one.edits(text, rater.mapping), one.gain)]
         line = {"file": name, "chars": len(text), "bits_per_char": float(total) / max(len(text) - 1, 1), "suspects": rows,
                 "corrections": proposals}
         if apply_:

@@ -4,7 +4,7 @@ before it -- `Rater.suspects`, the hypothesis windows built in numpy on the host
 numpy.
 
   python tools/bench_corrections.py [--out profiles/rate_corrections.json] [--repeats 5] [-k 3] [--suspect-share 0.02]
-                                    [--min-rank 1] [--left 64] [--ahead 8] [--deletions] [--min-gain 1.0]
+                                    [--min-rank 1] [--left 64] [--ahead 8] [--deletions] [--insertions] [--min-gain 1.0]
 
 The corpus-sized inputs of bench_suspects.py, cfg2 size (depth 2, width 512, length 256): 1024 documents of 2048 characters
 and 20 000 lines of 30 to 90 characters, both at 1024 streams.  The benchmark's model is untrained, and at a fixed threshold
@@ -24,6 +24,10 @@ Legs:
 The parent leg takes a chunk's bits with rate_bits_take(rows), an index upload per chunk; corrections takes all rows at once.
 Also reported, from one run each outside the timings: that both legs give identical costs, and the largest
 |cost_bf16 - cost_split| over the variants of the suspects both precisions found with the same alternatives.
+--insertions measures every set twice in the same run, first as without the flag and then with insertion hypotheses
+(`Rater.corrections(insertions=True)`, R = 2k + 1 + deletions rows per suspect; the parent leg builds the same rows with
+variant_windows_host(insertions=1)), adds a "first_pass" leg (Rater.suspects alone) so that the second pass of either can be
+told apart, and writes the result under the key "insertions" of --out, whose other content stays as it is.
 Host clock around work that ends in a device synchronise; every leg is warmed up once, then the legs are alternated in the
 same process; a leg is repeated inside one timing until it lasts at least --min-seconds; the median of --repeats (at least
 5) timings and the spread (max - min) / median.  One JSON line on stdout, also written to --out.
@@ -31,6 +35,7 @@ same process; a leg is repeated inside one timing until it lasts at least --min-
 Needs the GPU: there is no fallback.
 """
 import argparse
+import json
 import os
 import statistics
 import sys
@@ -56,6 +61,7 @@ def main():
     ap.add_argument("--left", type=int, default=64)
     ap.add_argument("--ahead", type=int, default=8)
     ap.add_argument("--deletions", action="store_true")
+    ap.add_argument("--insertions", action="store_true")
     ap.add_argument("--min-gain", type=float, default=1.0)
     args = ap.parse_args()
     import torch
@@ -65,8 +71,6 @@ def main():
     sync = torch.cuda.synchronize
     repeats = max(5, args.repeats)
     k, left, ahead, deletions = args.k, args.left, args.ahead, int(args.deletions)
-    R = k + 1 + deletions
-    T = max(left + ahead, ratebulk.MIN_T)
     rater = make_rater(**MODELS["cfg2"])
     rater.model.init_weights(seed=3, emb_std=0.3)      # (as bench_rate_batch --bulk: peaked distributions)
     lm = rater.model
@@ -75,117 +79,148 @@ def main():
               "suspect_share": args.suspect_share, "min_rank": args.min_rank, "left": left, "ahead": ahead,
               "deletions": bool(deletions), "min_gain": args.min_gain,
               "model": dict(MODELS["cfg2"], voc_size=len(ALPHABET) + 1), "sets": {}}
-    for name, docs, streams in corpus_sets():
-        chars = sum(len(d) for d in docs)
-        chunk = max(1, streams // R)
-        probs, _ = rater.rate_batch(docs, context, streams=streams, precision="bf16")
-        max_prob = float(np.quantile(np.concatenate([p[1:] for p in probs]), args.suspect_share))
-        del probs
-        common = dict(k=k, streams=streams, max_prob=max_prob, min_rank=args.min_rank)
-        held = {}
+    for insertions in ([0, 1] if args.insertions else [0]):
+        R = k + 1 + deletions + k * insertions
+        T = max(left + ahead + insertions, ratebulk.MIN_T)
+        sets = {}
+        for name, docs, streams in corpus_sets():
+            chars = sum(len(d) for d in docs)
+            chunk = max(1, streams // R)
+            probs, _ = rater.rate_batch(docs, context, streams=streams, precision="bf16")
+            max_prob = float(np.quantile(np.concatenate([p[1:] for p in probs]), args.suspect_share))
+            del probs
+            common = dict(k=k, streams=streams, max_prob=max_prob, min_rank=args.min_rank)
+            held = {}
 
-        def corrections(precision="bf16"):
-            return rater.corrections(docs, context, left=left, ahead=ahead, deletions=bool(deletions), min_gain=args.min_gain,
-                                     precision=precision, **common)
+            def corrections(precision="bf16"):
+                return rater.corrections(docs, context, left=left, ahead=ahead, deletions=bool(deletions), min_gain=args.min_gain,
+                                         precision=precision, insertions=bool(insertions), **common)
 
-        def host_windows(corpus, offsets, text_ctx, pos, alts, a):
-            return ratebulk.variant_windows_host(corpus, offsets, text_ctx, pos[a:a + chunk], alts[a:a + chunk], left, ahead,
-                                                 deletions, T)
+            def host_windows(corpus, offsets, text_ctx, pos, alts, a):
+                return ratebulk.variant_windows_host(corpus, offsets, text_ctx, pos[a:a + chunk], alts[a:a + chunk], left, ahead,
+                                                     deletions, T, insertions)
 
-        def host_inputs(found):
-            ids = [windows.encode(windows.normalize(t), rater.mapping[0]) for t in docs]
-            offsets = np.concatenate([[0], np.cumsum([len(a) for a in ids])]).astype(np.int64)
-            pos = np.concatenate([f.positions + offsets[i] for i, f in enumerate(found)])
-            alts = np.concatenate([f.alt_ids for f in found])
-            text_ctx = np.asarray([windows.clamp_context(context)] * len(docs), dtype=np.int32)
-            return np.concatenate(ids).astype(np.int32), offsets, text_ctx, pos, alts
+            def host_inputs(found):
+                ids = [windows.encode(windows.normalize(t), rater.mapping[0]) for t in docs]
+                offsets = np.concatenate([[0], np.cumsum([len(a) for a in ids])]).astype(np.int64)
+                pos = np.concatenate([f.positions + offsets[i] for i, f in enumerate(found)])
+                alts = np.concatenate([f.alt_ids for f in found])
+                text_ctx = np.asarray([windows.clamp_context(context)] * len(docs), dtype=np.int32)
+                return np.concatenate(ids).astype(np.int32), offsets, text_ctx, pos, alts
 
-        def parent():
-            found, bits = rater.suspects(docs, context, precision="bf16", **common)
-            corpus, offsets, text_ctx, pos, alts = host_inputs(found)
-            S = len(pos)
-            cost, valid = [], []
-            for a in range(0, S, chunk):
-                x, z, y, ok = host_windows(corpus, offsets, text_ctx, pos, alts, a)
-                lm.reset_states(len(x))
-                lm.rate_window_bulk(x, z, y, want_probs=False)
-                cost.append(lm.rate_bits_take(np.arange(len(x))))
-                valid.append(ok)
-            if not S:
-                return found, bits, np.zeros((0, R)), np.zeros(0, dtype=np.int32), np.zeros(0)
-            cost = torch.cat(cost).cpu().numpy().reshape(S, R)
-            lm.rate_status_check()
-            lm.reset_states(1)
-            return (found, bits) + ratebulk.variant_pick_host(cost, np.concatenate(valid).reshape(S, R))
+            def parent():
+                found, bits = rater.suspects(docs, context, precision="bf16", **common)
+                corpus, offsets, text_ctx, pos, alts = host_inputs(found)
+                S = len(pos)
+                cost, valid = [], []
+                for a in range(0, S, chunk):
+                    x, z, y, ok = host_windows(corpus, offsets, text_ctx, pos, alts, a)
+                    lm.reset_states(len(x))
+                    lm.rate_window_bulk(x, z, y, want_probs=False)
+                    cost.append(lm.rate_bits_take(np.arange(len(x))))
+                    valid.append(ok)
+                if not S:
+                    return found, bits, np.zeros((0, R)), np.zeros(0, dtype=np.int32), np.zeros(0)
+                cost = torch.cat(cost).cpu().numpy().reshape(S, R)
+                lm.rate_status_check()
+                lm.reset_states(1)
+                return (found, bits) + ratebulk.variant_pick_host(cost, np.concatenate(valid).reshape(S, R))
 
-        def windows_device():
-            pos, alts = held["sel"]
-            for a in range(0, pos.numel(), chunk):
-                lm.variant_windows(held["corpus"], held["offsets"], held["text_ctx"], pos[a:a + chunk], alts[a:a + chunk], left,
-                                   ahead, deletions, T)
+            def windows_device():
+                pos, alts = held["sel"]
+                for a in range(0, pos.numel(), chunk):
+                    lm.variant_windows(held["corpus"], held["offsets"], held["text_ctx"], pos[a:a + chunk], alts[a:a + chunk], left,
+                                       ahead, deletions, T, insertions=bool(insertions))
 
-        def encode_host():
-            host_inputs(held["found"])
+            def encode_host():
+                host_inputs(held["found"])
 
-        def windows_host():
-            corpus, offsets, text_ctx, pos, alts = held["host"]
-            for a in range(0, len(pos), chunk):
-                host_windows(corpus, offsets, text_ctx, pos, alts, a)
+            def first_pass():
+                rater.suspects(docs, context, precision="bf16", **common)
 
-        # one run of each outside the timings: the two legs agree, and bf16 against split
-        found, _ = corrections()
-        count = sum(len(f) for f in found)
-        p_cost = parent()[2]
-        cost = np.concatenate([f.cost for f in found])
-        identical = bool(cost.shape == p_cost.shape and np.array_equal(cost.view(np.uint64), p_cost.view(np.uint64)))
-        split, _ = corrections("split")
-        worst, compared = 0.0, 0
-        for a, b in zip(found, split):
-            _, ia, ib = np.intersect1d(a.positions, b.positions, return_indices=True)
-            same = (a.alt_ids[ia] == b.alt_ids[ib]).all(axis=1)
-            ca, cb = a.cost[ia][same], b.cost[ib][same]
-            both = np.isfinite(ca) & np.isfinite(cb)
-            if both.any():
-                worst = max(worst, float(np.abs(ca[both] - cb[both]).max()))
-                compared += int(both.sum())
-        keep = {}
-        _, arrays, _ = rater._alternatives_in_corpus_order(docs, context, k, streams, "bf16", keep=keep)
-        sel = lm.rate_select(*arrays, max_prob=max_prob, min_rank=args.min_rank)
-        held.update(keep, sel=(sel[0], sel[3]), host=host_inputs(found), found=found)
-        del arrays, sel
-        legs = {"corrections": corrections, "parent": parent, "windows": windows_device, "windows_host": windows_host,
-                "encode_host": encode_host}
-        inner = {}
-        for leg, fn in legs.items():
-            fn()
-            inner[leg] = max(1, int(np.ceil(args.min_seconds / max(timed(fn, sync, 1), 1e-6))))
-        times = dict((leg, []) for leg in legs)
-        for _ in range(repeats):
+            def windows_host():
+                corpus, offsets, text_ctx, pos, alts = held["host"]
+                for a in range(0, len(pos), chunk):
+                    host_windows(corpus, offsets, text_ctx, pos, alts, a)
+
+            # one run of each outside the timings: the two legs agree, and bf16 against split
+            found, _ = corrections()
+            count = sum(len(f) for f in found)
+            p_cost = parent()[2]
+            cost = np.concatenate([f.cost for f in found])
+            identical = bool(cost.shape == p_cost.shape and np.array_equal(cost.view(np.uint64), p_cost.view(np.uint64)))
+            split, _ = corrections("split")
+            worst, compared = 0.0, 0
+            for a, b in zip(found, split):
+                _, ia, ib = np.intersect1d(a.positions, b.positions, return_indices=True)
+                same = (a.alt_ids[ia] == b.alt_ids[ib]).all(axis=1)
+                ca, cb = a.cost[ia][same], b.cost[ib][same]
+                both = np.isfinite(ca) & np.isfinite(cb)
+                if both.any():
+                    worst = max(worst, float(np.abs(ca[both] - cb[both]).max()))
+                    compared += int(both.sum())
+            keep = {}
+            _, arrays, _ = rater._alternatives_in_corpus_order(docs, context, k, streams, "bf16", keep=keep)
+            sel = lm.rate_select(*arrays, max_prob=max_prob, min_rank=args.min_rank)
+            held.update(keep, sel=(sel[0], sel[3]), host=host_inputs(found), found=found)
+            del arrays, sel
+            legs = {"corrections": corrections, "parent": parent, "windows": windows_device, "windows_host": windows_host,
+                    "encode_host": encode_host}
+            if args.insertions:
+                legs["first_pass"] = first_pass
+            inner = {}
             for leg, fn in legs.items():
-                times[leg].append(timed(fn, sync, inner[leg]))
-        held.clear()
-        row = {"documents": len(docs), "chars": chars, "streams": streams, "max_prob": max_prob, "suspects_found": count,
-               "variants_per_suspect": R, "window_length": T, "suspects_per_chunk": chunk,
-               "proposals_kept": int(sum((f.best_id != -1).sum() for f in found)),
-               "costs_identical_to_parent": identical,
-               "max_abs_cost_bf16_minus_split": worst, "variants_compared_with_split": compared,
-               "bytes_from_device_second_pass": count * 12 * R,
-               "bytes_to_device_second_pass_parent": count * R * T * 4 * (2 + len(context))}
-        for leg, ts in times.items():
-            med = statistics.median(ts)
-            row[leg] = {"chars_per_s": chars / med, "seconds": med, "spread": (max(ts) - min(ts)) / med,
-                        "runs_per_timing": inner[leg]}
-        row["speedup"] = row["corrections"]["chars_per_s"] / row["parent"]["chars_per_s"]
-        row["windows_share"] = row["windows"]["seconds"] / row["corrections"]["seconds"]
-        row["windows_host_share_of_parent"] = row["windows_host"]["seconds"] / row["parent"]["seconds"]
-        row["encode_host_share_of_parent"] = row["encode_host"]["seconds"] / row["parent"]["seconds"]
-        result["sets"][name] = row
-        print("%-16s corrections %10.0f  parent %10.0f chars/s (%.2fx)  %d suspects  windows %.1f %% (host: %.1f %% of parent)  "
-              "encode %.1f %% of parent  identical %s  |bf16 - split| <= %.3g over %d" % (
-                  name, row["corrections"]["chars_per_s"], row["parent"]["chars_per_s"], row["speedup"], count,
-                  100.0 * row["windows_share"], 100.0 * row["windows_host_share_of_parent"],
-                  100.0 * row["encode_host_share_of_parent"], identical, worst, compared),
-              file=sys.stderr)
+                fn()
+                inner[leg] = max(1, int(np.ceil(args.min_seconds / max(timed(fn, sync, 1), 1e-6))))
+            times = dict((leg, []) for leg in legs)
+            for _ in range(repeats):
+                for leg, fn in legs.items():
+                    times[leg].append(timed(fn, sync, inner[leg]))
+            held.clear()
+            row = {"documents": len(docs), "chars": chars, "streams": streams, "max_prob": max_prob, "suspects_found": count,
+                   "variants_per_suspect": R, "window_length": T, "suspects_per_chunk": chunk,
+                   "proposals_kept": int(sum((f.best_id != -1).sum() for f in found)),
+                   "costs_identical_to_parent": identical,
+                   "max_abs_cost_bf16_minus_split": worst, "variants_compared_with_split": compared,
+                   "bytes_from_device_second_pass": count * 12 * R,
+                   "bytes_to_device_second_pass_parent": count * R * T * 4 * (2 + len(context))}
+            for leg, ts in times.items():
+                med = statistics.median(ts)
+                row[leg] = {"chars_per_s": chars / med, "seconds": med, "spread": (max(ts) - min(ts)) / med,
+                            "runs_per_timing": inner[leg]}
+            row["speedup"] = row["corrections"]["chars_per_s"] / row["parent"]["chars_per_s"]
+            row["windows_share"] = row["windows"]["seconds"] / row["corrections"]["seconds"]
+            row["windows_host_share_of_parent"] = row["windows_host"]["seconds"] / row["parent"]["seconds"]
+            row["encode_host_share_of_parent"] = row["encode_host"]["seconds"] / row["parent"]["seconds"]
+            if args.insertions:
+                row["second_pass_seconds"] = row["corrections"]["seconds"] - row["first_pass"]["seconds"]
+            sets[name] = row
+            print("%-16s corrections %10.0f  parent %10.0f chars/s (%.2fx)  %d suspects  windows %.1f %% (host: %.1f %% of parent)  "
+                  "encode %.1f %% of parent  identical %s  |bf16 - split| <= %.3g over %d" % (
+                      name, row["corrections"]["chars_per_s"], row["parent"]["chars_per_s"], row["speedup"], count,
+                      100.0 * row["windows_share"], 100.0 * row["windows_host_share_of_parent"],
+                      100.0 * row["encode_host_share_of_parent"], identical, worst, compared),
+                  file=sys.stderr)
+        if not args.insertions:
+            result["sets"] = sets
+            continue
+        # both measurements of a set side by side, and what the insertion rows cost the second pass
+        for name, row in sets.items():
+            one = result["sets"].setdefault(name, {})
+            one["with_insertions" if insertions else "without_insertions"] = row
+            if insertions:
+                before = one["without_insertions"]
+                one["rows_ratio"] = row["variants_per_suspect"] / before["variants_per_suspect"]
+                one["second_pass_seconds_ratio"] = row["second_pass_seconds"] / before["second_pass_seconds"]
+                one["corrections_seconds_ratio"] = row["corrections"]["seconds"] / before["corrections"]["seconds"]
+    if args.insertions:
+        # under a key of its own: the file's other content (the run without the flag) stays as it is
+        whole = {}
+        if args.out and os.path.exists(args.out):
+            with open(args.out) as f:
+                whole = json.load(f)
+        whole["insertions"] = result
+        result = whole
     emit(result, args.out)
 
 
