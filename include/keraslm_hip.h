@@ -487,6 +487,18 @@ int kl_test_gemm_an(const uint16_t* A_km, const uint16_t* B, float* C, int M, in
 int kl_test_gemm_an2(const uint16_t* A_km, const uint16_t* B, float* C, int M, int N, int K, long lda_km, long ldb, long ldc,
                      int c_transposed, const uint16_t* B2, float* C2, int N2, long ldb2, long ldc2, int c_transposed2, int b_km,
                      void* stream);
+/* Where kl_test_gemm_tn would take a call, decided on the host from the same arguments (c_addr: the address C would have,
+ * has_bias: whether a bias is given) and the same KL_GEMM_* switches; nothing is launched and no device is needed.
+ * Returns 0 = KL_ERR_SHAPE, 1 = long split-K (256 x 128 ring, K >= 8192, accumulating), 2 = persistent workgroups,
+ * 3 = long, one 256 x 128 tile per workgroup, 4 = its 64 x 128 tile, 5 = gemm_tn_kernel with 64-row tiles, 6 = with 128-row
+ * tiles, 7 = an empty product (M, N or K <= 0: the call answers 0 and launches nothing); *eff_splits (optional): the K
+ * splits the launch would run with. */
+int kl_test_gemm_tn_route(int M, int N, int K, long lda, long ldb, long ldc, int out_mode, int splits, size_t c_addr, int has_bias,
+                          int* eff_splits);
+/* ... and kl_test_gemm_an (N2 = 0) / kl_test_gemm_an2 (N2 > 0): 0 = not applicable (KL_ERR_SHAPE), 1 = the 256 x 128 tile,
+ * 2 = the wide form (256 x 256; its ring depth is the LDS grant's answer and not reported), 3 = an empty product;
+ * *rows_per_split (optional): the rows of K one split takes. */
+int kl_test_gemm_an_route(int M, int N, int N2, int K, long lda_km, long ldb, long ldb2, int b_km, int* rows_per_split);
 /* layer 0's table gradients as segment sums over the time-major rows r = t * B + b of dZ [T*B][ld] (bf16; cols a multiple
  * of 8): dEK[v][cols] = sum of the rows with idx[b][t] == v in [0, V), dCtxK[c][cols] = sum of those with
  * ctx[b][t][0] == c in [0, R) (ctx is [B][T][n_ctx]; n_ctx == 0: no context table).  Ids outside their range are dropped,
@@ -499,6 +511,10 @@ int kl_test_segment_sums(const uint16_t* dZ, long ld, int B, int T, int cols, co
                          int V, int R, float* dEK, float* dCtxK, void* ws, void* stream);
 int kl_test_thin_gemm(const float* A, long lda, const uint16_t* WT_hi, const uint16_t* WT_lo, long ldw, int M, int N,
                       int K, float* C, long ldc, int split, void* stream);
+/* ... with every form of the operand: A f32 or (a_is_f32 = 0) bf16, an optional gather of A's rows (row_index, int32 on the
+ * device: output row r contracts A row row_index[r]) and an optional bias[N], added once */
+int kl_test_thin_gemm_ex(const void* A, long lda, int a_is_f32, const int32_t* row_index, const uint16_t* WT_hi, const uint16_t* WT_lo,
+                         long ldw, int M, int N, int K, float* C, long ldc, const float* bias, int split, void* stream);
 /* The output layer of a training window (logits, softmax, clipped cross-entropy, accuracy, dlogits, dH) on caller buffers:
  * each call is the launcher of one kernel family with its own applicability rule, KL_ERR_SHAPE before anything is launched
  * where it does not apply.  Rows are time-major (r = t * B + b), tgt is [B][T] (-1 = padded position, < -1 = dummy stream),

@@ -2332,6 +2332,19 @@ int kl_test_gemm_an2(const uint16_t* A_km, const uint16_t* B, float* C, int M, i
                             (hipStream_t)stream, b_km);
 }
 
+int kl_test_gemm_tn_route(int M, int N, int K, long lda, long ldb, long ldc, int out_mode, int splits, size_t c_addr, int has_bias,
+                          int* eff_splits) {
+  const KlGemmTnRoute rt = kl_gemm_tn_route(reinterpret_cast<const void*>(c_addr), has_bias != 0, M, N, K, lda, ldb, ldc, out_mode, splits);
+  if (eff_splits) *eff_splits = rt.splits;
+  return rt.route;
+}
+
+int kl_test_gemm_an_route(int M, int N, int N2, int K, long lda_km, long ldb, long ldb2, int b_km, int* rows_per_split) {
+  const KlGemmAnRoute rt = kl_gemm_an_route(N2 > 0, M, N, N2, K, lda_km, ldb, ldb2, b_km);
+  if (rows_per_split) *rows_per_split = rt.rows_per_split;
+  return rt.route;
+}
+
 size_t kl_test_segment_sums_ws_bytes(int B, int T, int n_ctx, int V, int R) {
   if (B < 1 || T < 1 || V < 1 || n_ctx < 0 || (n_ctx > 0 && R < 1)) return 0;
   return kl_segment_sums_ws_bytes(B, T, n_ctx, V, R);
@@ -2350,6 +2363,14 @@ int kl_test_thin_gemm(const float* A, long lda, const uint16_t* WT_hi, const uin
   memset(&op, 0, sizeof(op));
   op.A = A; op.lda = lda; op.a_is_f32 = 1; op.WT_hi = WT_hi; op.WT_lo = WT_lo; op.ldw = ldw; op.K = K;
   return kl_launch_thin_gemm(&op, M, N, C, ldc, nullptr, split, (hipStream_t)stream);
+}
+
+int kl_test_thin_gemm_ex(const void* A, long lda, int a_is_f32, const int32_t* row_index, const uint16_t* WT_hi, const uint16_t* WT_lo,
+                         long ldw, int M, int N, int K, float* C, long ldc, const float* bias, int split, void* stream) {
+  KlOperand op;
+  memset(&op, 0, sizeof(op));
+  op.A = A; op.lda = lda; op.a_is_f32 = a_is_f32 ? 1 : 0; op.row_index = row_index; op.WT_hi = WT_hi; op.WT_lo = WT_lo; op.ldw = ldw; op.K = K;
+  return kl_launch_thin_gemm(&op, M, N, C, ldc, bias, split, (hipStream_t)stream);
 }
 
 int kl_test_softmax_ce(float* logits, long ld, int rows, int V, const int32_t* tgt, int B, int T, float inv_count, uint16_t* dlogits,

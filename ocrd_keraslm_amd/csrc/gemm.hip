@@ -845,11 +845,13 @@ int launch_long(int out_mode, dim3 grid, hipStream_t stream, const bf16_t* A, co
 
 }  // namespace
 
-// out_mode: 0 f32 store, 1 bf16 store, 2 f32 atomic accumulate (split-K allowed)
-int kl_launch_gemm_tn(const bf16_t* A, const bf16_t* B, void* C, const float* bias, int M, int N, int K,
-                      long lda, long ldb, long ldc, int out_mode, int splits, float alpha, hipStream_t stream) {
-  if (M <= 0 || N <= 0 || K <= 0) return 0;
-  if ((K & 7) || (lda & 7) || (ldb & 7)) return KL_ERR_SHAPE;
+// The route kl_launch_gemm_tn takes, decided on the host from the arguments of the call (the address of C and whether
+// there is a bias among them) and the KL_GEMM_* switches, each read once per process.  The launcher acts on this answer
+// and on nothing else, so a test can ask where a shape lands without launching anything.
+KlGemmTnRoute kl_gemm_tn_route(const void* C, bool has_bias, int M, int N, int K, long lda, long ldb, long ldc, int out_mode,
+                               int splits) {
+  if (M <= 0 || N <= 0 || K <= 0) return KlGemmTnRoute{KL_TN_EMPTY, 0, 0};
+  if ((K & 7) || (lda & 7) || (ldb & 7)) return KlGemmTnRoute{KL_TN_ERR_SHAPE, 0, 0};
   if (splits < 1) splits = 1;
   if (out_mode != 2) splits = 1;
   // long-K shapes (weight gradients): one 256 x 128 tile per CU, K split to fill the chip
@@ -863,19 +865,44 @@ int kl_launch_gemm_tn(const bf16_t* A, const bf16_t* B, void* C, const float* bi
     if (sp < 1) sp = 1;
     const int kps = ((nk + sp - 1) / sp) * BK;
     sp = (K + kps - 1) / kps;
-    dim3 grid((N + LBN - 1) / LBN, (M + LBM - 1) / LBM, sp);
-    const int e = launch_long(out_mode, grid, stream, A, B, C, bias, M, N, K, lda, ldb, ldc, kps, alpha);
-    if (e != 0) return e;
-    return hipGetLastError() == hipSuccess ? 0 : KL_ERR_LAUNCH;
+    return KlGemmTnRoute{KL_TN_LONG_SPLIT, sp, kps};
   }
   // many-row shapes (activations x weights): the same ring, one tile per workgroup, no split
   static const bool small_all = getenv("KL_GEMM_SMALL_ALL") && getenv("KL_GEMM_SMALL_ALL")[0] == '1';   // experiment
   static const bool pers = !(getenv("KL_GEMM_PERS") && getenv("KL_GEMM_PERS")[0] == '0');
   // (measured at M = 262144: K = 512 -- P, logits -- 8-10 % faster than one workgroup per tile; K = 2048 and K = 256 not)
   if (pers && !small_all && long_mode >= 2 && long_ok && (out_mode == 0 || out_mode == 1) && K >= 6 * BK && K <= 16 * BK && (N & 3) == 0 && (ldc & 3) == 0 &&
-      ((size_t)C & 15) == 0 && (bias == nullptr || N <= 2048) &&
-      (long)((M + LBM - 1) / LBM) * ((N + LBN - 1) / LBN) >= 512) {
-    // many-row shapes with several tiles per CU: persistent workgroups (see gemm_tn_pers_kernel)
+      ((size_t)C & 15) == 0 && (!has_bias || N <= 2048) &&
+      (long)((M + LBM - 1) / LBM) * ((N + LBN - 1) / LBN) >= 512)
+    return KlGemmTnRoute{KL_TN_PERS, 1, K};      // several tiles per CU: persistent workgroups (see gemm_tn_pers_kernel)
+  if (!small_all && long_mode >= 2 && long_ok && splits == 1 && K >= 256 && (long)((M + LBM - 1) / LBM) * ((N + LBN - 1) / LBN) >= 256)
+    return KlGemmTnRoute{KL_TN_LONG, 1, K};
+  // M ~ 1e3 rows (the incremental step's GEMMs): 64 x 128 tiles of the same ring
+  if (long_mode >= 2 && long_ok && splits == 1 && K >= 512 && M >= 256 &&
+      (long)((M + 63) / 64) * ((N + LBN - 1) / LBN) >= 64)
+    return KlGemmTnRoute{KL_TN_LONG64, 1, K};
+  int k_per_split = (K + splits - 1) / splits;
+  k_per_split = ((k_per_split + BK - 1) / BK) * BK;
+  splits = (K + k_per_split - 1) / k_per_split;
+  const int nbx = (N + BN - 1) / BN;
+  // 64-row tiles when 128-row tiles cannot give every CU a workgroup
+  const bool small = (long)nbx * ((M + 127) / 128) * splits < 256 && M > 64;
+  return KlGemmTnRoute{small ? KL_TN_BM64 : KL_TN_BM128, splits, k_per_split};
+}
+
+// out_mode: 0 f32 store, 1 bf16 store, 2 f32 atomic accumulate (split-K allowed)
+int kl_launch_gemm_tn(const bf16_t* A, const bf16_t* B, void* C, const float* bias, int M, int N, int K,
+                      long lda, long ldb, long ldc, int out_mode, int splits, float alpha, hipStream_t stream) {
+  const KlGemmTnRoute rt = kl_gemm_tn_route(C, bias != nullptr, M, N, K, lda, ldb, ldc, out_mode, splits);
+  if (rt.route == KL_TN_EMPTY) return 0;
+  if (rt.route == KL_TN_ERR_SHAPE) return KL_ERR_SHAPE;
+  if (rt.route == KL_TN_LONG_SPLIT) {
+    dim3 grid((N + LBN - 1) / LBN, (M + LBM - 1) / LBM, rt.splits);
+    const int e = launch_long(out_mode, grid, stream, A, B, C, bias, M, N, K, lda, ldb, ldc, rt.k_per_split, alpha);
+    if (e != 0) return e;
+    return hipGetLastError() == hipSuccess ? 0 : KL_ERR_LAUNCH;
+  }
+  if (rt.route == KL_TN_PERS) {
     static int n_wg = 0;
     if (!n_wg) {
       int dev = 0;
@@ -891,32 +918,25 @@ int kl_launch_gemm_tn(const bf16_t* A, const bf16_t* B, void* C, const float* bi
                        alpha, tiles_n, total, out_mode == 1 ? 1 : 0);
     return hipGetLastError() == hipSuccess ? 0 : KL_ERR_LAUNCH;
   }
-  if (!small_all && long_mode >= 2 && long_ok && splits == 1 && K >= 256 && (long)((M + LBM - 1) / LBM) * ((N + LBN - 1) / LBN) >= 256) {
+  if (rt.route == KL_TN_LONG) {
     dim3 grid((N + LBN - 1) / LBN, (M + LBM - 1) / LBM, 1);
     const int e = launch_long(out_mode, grid, stream, A, B, C, bias, M, N, K, lda, ldb, ldc, K, alpha);
     if (e != 0) return e;
     return hipGetLastError() == hipSuccess ? 0 : KL_ERR_LAUNCH;
   }
-  // M ~ 1e3 rows (the incremental step's GEMMs): 64 x 128 tiles of the same ring
-  if (long_mode >= 2 && long_ok && splits == 1 && K >= 512 && M >= 256 &&
-      (long)((M + 63) / 64) * ((N + LBN - 1) / LBN) >= 64) {
+  if (rt.route == KL_TN_LONG64) {
     dim3 grid((N + LBN - 1) / LBN, (M + 63) / 64, 1);
     const int e = launch_long_t<2, 2, 4>(out_mode, grid, stream, A, B, C, bias, M, N, K, lda, ldb, ldc, K, alpha);
     if (e != 0) return e;
     return hipGetLastError() == hipSuccess ? 0 : KL_ERR_LAUNCH;
   }
-  int k_per_split = (K + splits - 1) / splits;
-  k_per_split = ((k_per_split + BK - 1) / BK) * BK;
-  splits = (K + k_per_split - 1) / k_per_split;
   const int nbx = (N + BN - 1) / BN;
-  // 64-row tiles when 128-row tiles cannot give every CU a workgroup
-  const bool small = (long)nbx * ((M + 127) / 128) * splits < 256 && M > 64;
-  if (small) {
-    dim3 grid(nbx, (M + 63) / 64, splits);
-    launch_bm<64>(out_mode, grid, stream, A, B, C, bias, M, N, K, lda, ldb, ldc, k_per_split, alpha);
+  if (rt.route == KL_TN_BM64) {
+    dim3 grid(nbx, (M + 63) / 64, rt.splits);
+    launch_bm<64>(out_mode, grid, stream, A, B, C, bias, M, N, K, lda, ldb, ldc, rt.k_per_split, alpha);
   } else {
-    dim3 grid(nbx, (M + 127) / 128, splits);
-    launch_bm<128>(out_mode, grid, stream, A, B, C, bias, M, N, K, lda, ldb, ldc, k_per_split, alpha);
+    dim3 grid(nbx, (M + 127) / 128, rt.splits);
+    launch_bm<128>(out_mode, grid, stream, A, B, C, bias, M, N, K, lda, ldb, ldc, rt.k_per_split, alpha);
   }
   return hipGetLastError() == hipSuccess ? 0 : KL_ERR_LAUNCH;
 }
@@ -960,21 +980,33 @@ bool kl_gemm_an_applicable(int M, int N, int K, long lda_km) {
   return an_rows_per_split(M, N, K, lda_km) > 0;
 }
 
-int kl_launch_gemm_an2(const bf16_t* A_km, const bf16_t* B, float* C, int M, int N, int K, long lda_km, long ldb, long ldc,
-                       int c_transposed, const bf16_t* B2, float* C2, int N2, long ldb2, long ldc2, int c_transposed2,
-                       hipStream_t stream, int b_km) {
-  if (M <= 0 || N <= 0 || K <= 0) return 0;
-  if (B2 != nullptr && ((N % LBN) || N2 <= 0 || (ldb2 & 7) || (!b_km && ldb2 >= (1L << 22)))) return KL_ERR_SHAPE;
-  const int n_all = B2 != nullptr ? N + N2 : N;
-  if ((lda_km & 7) || (ldb & 7) || (!b_km && ldb >= (1L << 22))) return KL_ERR_SHAPE;
+// The route kl_launch_gemm_an2 takes (pair: a second product rides along), from the same arguments and switches as the
+// launch; whether the wide form then runs on five or four stages is the LDS grant's answer and not part of it.
+KlGemmAnRoute kl_gemm_an_route(bool pair, int M, int N, int N2, int K, long lda_km, long ldb, long ldb2, int b_km) {
+  if (M <= 0 || N <= 0 || K <= 0) return KlGemmAnRoute{KL_AN_EMPTY, 0};
+  if (pair && ((N % LBN) || N2 <= 0 || (ldb2 & 7) || (!b_km && ldb2 >= (1L << 22)))) return KlGemmAnRoute{KL_AN_NONE, 0};
+  const int n_all = pair ? N + N2 : N;
+  if ((lda_km & 7) || (ldb & 7) || (!b_km && ldb >= (1L << 22))) return KlGemmAnRoute{KL_AN_NONE, 0};
   long ld_max = lda_km;
   if (b_km && ldb > ld_max) ld_max = ldb;
-  if (b_km && B2 != nullptr && ldb2 > ld_max) ld_max = ldb2;
-  const bool wide = an_wide(M, N, B2 != nullptr ? N2 : 0, b_km);
+  if (b_km && pair && ldb2 > ld_max) ld_max = ldb2;
+  const bool wide = an_wide(M, N, pair ? N2 : 0, b_km);
   int kps = wide ? an_rows_per_split(M, n_all, K, ld_max, WBN, WBK) : 0;
   const bool go_wide = kps > 0;
   if (!go_wide) kps = an_rows_per_split(M, n_all, K, ld_max);
-  if (kps <= 0) return KL_ERR_SHAPE;
+  if (kps <= 0) return KlGemmAnRoute{KL_AN_NONE, 0};
+  return KlGemmAnRoute{go_wide ? KL_AN_WIDE : KL_AN_256x128, kps};
+}
+
+int kl_launch_gemm_an2(const bf16_t* A_km, const bf16_t* B, float* C, int M, int N, int K, long lda_km, long ldb, long ldc,
+                       int c_transposed, const bf16_t* B2, float* C2, int N2, long ldb2, long ldc2, int c_transposed2,
+                       hipStream_t stream, int b_km) {
+  const KlGemmAnRoute rt = kl_gemm_an_route(B2 != nullptr, M, N, N2, K, lda_km, ldb, ldb2, b_km);
+  if (rt.route == KL_AN_EMPTY) return 0;
+  if (rt.route == KL_AN_NONE) return KL_ERR_SHAPE;
+  const int n_all = B2 != nullptr ? N + N2 : N;
+  const int kps = rt.rows_per_split;
+  const bool go_wide = rt.route == KL_AN_WIDE;
   const int sp = (K + kps - 1) / kps;
   const int tbn = go_wide ? WBN : LBN;
   dim3 grid((n_all + tbn - 1) / tbn, M / LBM, sp);

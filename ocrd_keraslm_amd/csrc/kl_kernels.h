@@ -65,6 +65,18 @@ int kl_launch_gemm_an2(const bf16_t* A_km, const bf16_t* B, float* C, int M, int
                        int c_transposed, const bf16_t* B2, float* C2, int N2, long ldb2, long ldc2, int c_transposed2,
                        hipStream_t stream, int b_km);
 
+// Where a call of the two launchers above lands (host only, nothing is launched): the launchers act on these answers.
+// kl_launch_gemm_tn: the kernel, the K splits it runs with and the k-range of one split
+enum { KL_TN_ERR_SHAPE = 0, KL_TN_LONG_SPLIT = 1, KL_TN_PERS = 2, KL_TN_LONG = 3, KL_TN_LONG64 = 4, KL_TN_BM64 = 5, KL_TN_BM128 = 6,
+       KL_TN_EMPTY = 7 };      // (EMPTY: M, N or K <= 0 -- nothing to do, the launcher answers 0)
+struct KlGemmTnRoute { int route, splits, k_per_split; };
+KlGemmTnRoute kl_gemm_tn_route(const void* C, bool has_bias, int M, int N, int K, long lda, long ldb, long ldc, int out_mode,
+                               int splits);
+// kl_launch_gemm_an2 (pair: with a second product): the kernel and the rows of K one split takes
+enum { KL_AN_NONE = 0, KL_AN_256x128 = 1, KL_AN_WIDE = 2, KL_AN_EMPTY = 3 };
+struct KlGemmAnRoute { int route, rows_per_split; };
+KlGemmAnRoute kl_gemm_an_route(bool pair, int M, int N, int N2, int K, long lda_km, long ldb, long ldb2, int b_km);
+
 // ---- lstm_step.hip ------------------------------------------------------
 // One (activation, weight) operand pair of a thin fused step: rows of A are
 // contracted with rows of WT (both K-contiguous).

@@ -151,12 +151,18 @@ SIGNATURES = {
                                   C.c_long, C.c_int, C.c_int, C.c_void_p]),
     "kl_test_gemm_an2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long,
                                    C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, C.c_void_p]),
+    "kl_test_gemm_tn_route": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long, C.c_int, C.c_int, C.c_size_t,
+                                        C.c_int, C.POINTER(C.c_int)]),
+    "kl_test_gemm_an_route": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long, C.c_int,
+                                        C.POINTER(C.c_int)]),
     "kl_test_segment_sums_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "kl_test_segment_sums_share": (C.c_int, [C.c_int, C.c_int]),
     "kl_test_segment_sums": (C.c_int, [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                        C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kl_test_thin_gemm": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_int,
                                     C.c_int, C.c_void_p, C.c_long, C.c_int, C.c_void_p]),
+    "kl_test_thin_gemm_ex": (C.c_int, [C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_int,
+                                       C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_void_p]),
     "kl_test_softmax_ce": (C.c_int, [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float,
                                      C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "kl_test_logits_ce_ws": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
