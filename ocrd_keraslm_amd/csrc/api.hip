@@ -2484,6 +2484,24 @@ extern "C" int kl_set_window_mode(kl_handle* h, int last_only) {
   return 0;
 }
 
+namespace {
+
+// the caller's idx / ctx / tgt (and a training window's masks) into the window's staging slots: what a captured body reads
+int stage_window(const kl_handle* h, const WindowWs& w, int B, int T, const int32_t* idx, const int32_t* ctx,
+                 const int32_t* tgt, const float* masks, hipStream_t s) {
+  const size_t BT = (size_t)B * T;
+  KL_TRY(hip_ok(hipMemcpyAsync(w.s_idx, idx, BT * sizeof(int), hipMemcpyDeviceToDevice, s)));
+  if (h->cfg.n_ctx > 0)
+    KL_TRY(hip_ok(hipMemcpyAsync(w.s_ctx, ctx, BT * h->cfg.n_ctx * sizeof(int), hipMemcpyDeviceToDevice, s)));
+  if (tgt) KL_TRY(hip_ok(hipMemcpyAsync(w.s_tgt, tgt, BT * sizeof(int), hipMemcpyDeviceToDevice, s)));
+  if (masks)
+    KL_TRY(hip_ok(hipMemcpyAsync(w.s_masks, masks, (size_t)h->cfg.depth * B * h->cfg.width * sizeof(float),
+                                 hipMemcpyDeviceToDevice, s)));
+  return 0;
+}
+
+}  // namespace
+
 extern "C" int kl_forward_window(kl_handle* h, int B, int T, const int32_t* idx, const int32_t* ctx, const int32_t* tgt,
                                  float* states, float* probs, float* loss_acc, void* ws, size_t ws_bytes,
                                  void* stream) {
@@ -2497,10 +2515,7 @@ extern "C" int kl_forward_window(kl_handle* h, int B, int T, const int32_t* idx,
   const int layout = (h->precision == KL_PREC_BF16 && ws_bytes >= carve_window(h, nullptr, B, T, 1, nullptr)) ? 1 : 0;
   if (ws_bytes < carve_window(h, ws, B, T, layout, &w)) return KL_ERR_WORKSPACE;
   const size_t BT = (size_t)B * T;
-  KL_TRY(hip_ok(hipMemcpyAsync(w.s_idx, idx, BT * sizeof(int), hipMemcpyDeviceToDevice, s)));
-  if (h->cfg.n_ctx > 0)
-    KL_TRY(hip_ok(hipMemcpyAsync(w.s_ctx, ctx, BT * h->cfg.n_ctx * sizeof(int), hipMemcpyDeviceToDevice, s)));
-  if (tgt) KL_TRY(hip_ok(hipMemcpyAsync(w.s_tgt, tgt, BT * sizeof(int), hipMemcpyDeviceToDevice, s)));
+  KL_TRY(stage_window(h, w, B, T, idx, ctx, tgt, nullptr, s));
   kl_handle::GraphKey key{0, B, T, (tgt ? 1 : 0) | (probs ? 2 : 0) | (h->last_only ? 4 : 0) | (h->loss_rows << 3), h->precision, states, loss_acc, ws, nullptr, layout};      // (loss_rows: baked into the captured launches)
   KL_TRY(run_graphed(h, key, s, [&]() {
     return forward_window_body(h, B, T, w.s_idx, w.s_ctx, tgt ? w.s_tgt : nullptr, states, probs ? w.s_probs : nullptr,
@@ -2511,88 +2526,18 @@ extern "C" int kl_forward_window(kl_handle* h, int B, int T, const int32_t* idx,
   return 0;
 }
 
-// ---- rating windows with target-only delivery (rating.py:493-529 `rate`, many texts at once) ----------------
-// The window of kl_forward_window in the inference layout, but what leaves it is one float per position -- the
-// probability of the character that follows -- and/or one f64 sum per stream; the [B][T][V] softmax is never formed.
-// The workspace is the inference window's: its probability staging slot holds the [B][T] picks instead.
-extern "C" size_t kl_rate_workspace_bytes(const kl_handle* h, int B, int T) {
-  if (!h || B < 1 || T < 1) return 0;
-  return carve_window(h, nullptr, B, T, 0, nullptr);
-}
-
-extern "C" int kl_rate_window(kl_handle* h, int B, int T, const int32_t* idx, const int32_t* ctx, const int32_t* tgt,
-                              float* states, float* tprob, double* bits, float* status, void* ws, size_t ws_bytes,
-                              void* stream) {
-  if (!h || !idx || !states || !ws || B < 1 || T < 1) return KL_ERR_ARG;
-  if (h->cfg.n_ctx > 0 && !ctx) return KL_ERR_ARG;
-  if ((tprob || bits) && !tgt) return KL_ERR_ARG;
-  if (!h->precision || h->last_only) return KL_ERR_STATE;      // (one target per window is the stateless graph's: kl_forward_window)
-  hipStream_t s = (hipStream_t)stream;
-  WindowWs w;
-  if (ws_bytes < carve_window(h, ws, B, T, 0, &w)) return KL_ERR_WORKSPACE;
-  const size_t BT = (size_t)B * T;
-  const bool pick = tprob || bits;
-  KL_TRY(hip_ok(hipMemcpyAsync(w.s_idx, idx, BT * sizeof(int), hipMemcpyDeviceToDevice, s)));
-  if (h->cfg.n_ctx > 0)
-    KL_TRY(hip_ok(hipMemcpyAsync(w.s_ctx, ctx, BT * h->cfg.n_ctx * sizeof(int), hipMemcpyDeviceToDevice, s)));
-  if (pick) KL_TRY(hip_ok(hipMemcpyAsync(w.s_tgt, tgt, BT * sizeof(int), hipMemcpyDeviceToDevice, s)));
-  // (baked into the captured launches: states, status, bits and the workspace -- all in the key; tprob is staged)
-  kl_handle::GraphKey key{2, B, T, (tprob ? 1 : 0) | (bits ? 2 : 0), h->precision, states, status, ws, bits, 0};
-  KL_TRY(run_graphed(h, key, s, [&]() {
-    const int V = h->cfg.voc_size;
-    KL_TRY(window_logits(h, B, T, w.s_idx, w.s_ctx, states, w, s));
-    if (pick) KL_TRY(kl_launch_rate_pick(w.logits, V, B * T, V, w.s_tgt, B, T, w.s_probs, s));
-    if (bits) KL_TRY(kl_launch_rate_bits(w.s_probs, w.s_tgt, B, T, bits, s));
-    if (status) hipLaunchKernelGGL(scan_status_kernel, dim3(1), dim3(64), 0, s, w.scan_status, status);
-    return hip_ok(hipGetLastError());
-  }));
-  if (tprob) KL_TRY(hip_ok(hipMemcpyAsync(tprob, w.s_probs, BT * sizeof(float), hipMemcpyDeviceToDevice, s)));
-  return 0;
-}
-
-// ---- bulk rating: kl_rate_window on the training forward -----------------------------------------------------------
-// kl_rate_window's delivery behind the recurrence and logits of a bf16 validation window (window_logits_training): the wide
-// persistent scans take thousands of streams per launch where the split-precision scan of the inference layout takes 256.
-// The workspace is the training window's; its probability staging slot holds the [B][T] picks.
-extern "C" size_t kl_rate_bulk_workspace_bytes(const kl_handle* h, int B, int T) {
-  if (!h || B < 1 || T < 1) return 0;
-  return carve_window(h, nullptr, B, T, 1, nullptr);
-}
-
-extern "C" int kl_rate_window_bulk(kl_handle* h, int B, int T, const int32_t* idx, const int32_t* ctx, const int32_t* tgt,
-                                   float* states, float* tprob, double* bits, float* status, void* ws, size_t ws_bytes,
-                                   void* stream) {
-  if (!h || !idx || !states || !ws || B < 1 || T < 1) return KL_ERR_ARG;
-  if (h->cfg.n_ctx > 0 && !ctx) return KL_ERR_ARG;
-  if ((tprob || bits) && !tgt) return KL_ERR_ARG;
-  if (h->precision != KL_PREC_BF16 || h->last_only) return KL_ERR_STATE;      // (the training forward is bf16's; last_only as kl_rate_window)
-  hipStream_t s = (hipStream_t)stream;
-  WindowWs w;
-  if (ws_bytes < carve_window(h, nullptr, B, T, 1, nullptr)) return KL_ERR_WORKSPACE;
-  carve_window(h, ws, B, T, 1, &w);
-  const size_t BT = (size_t)B * T;
-  const bool pick = tprob || bits;
-  KL_TRY(hip_ok(hipMemcpyAsync(w.s_idx, idx, BT * sizeof(int), hipMemcpyDeviceToDevice, s)));
-  if (h->cfg.n_ctx > 0)
-    KL_TRY(hip_ok(hipMemcpyAsync(w.s_ctx, ctx, BT * h->cfg.n_ctx * sizeof(int), hipMemcpyDeviceToDevice, s)));
-  if (pick) KL_TRY(hip_ok(hipMemcpyAsync(w.s_tgt, tgt, BT * sizeof(int), hipMemcpyDeviceToDevice, s)));
-  // (baked into the captured launches as in kl_rate_window; a kind of its own: the same arrays may serve both calls)
-  kl_handle::GraphKey key{4, B, T, (tprob ? 1 : 0) | (bits ? 2 : 0), h->precision, states, status, ws, bits, 1};
-  KL_TRY(run_graphed(h, key, s, [&]() {
-    const int V = h->cfg.voc_size;
-    KL_TRY(window_logits_training(h, B, T, w.s_idx, w.s_ctx, states, w, s));
-    if (pick) KL_TRY(kl_launch_rate_pick(w.logits, V, B * T, V, w.s_tgt, B, T, w.s_probs, s));
-    if (bits) KL_TRY(kl_launch_rate_bits(w.s_probs, w.s_tgt, B, T, bits, s));
-    if (status) hipLaunchKernelGGL(scan_status_kernel, dim3(1), dim3(64), 0, s, w.scan_status, status);
-    return hip_ok(hipGetLastError());
-  }));
-  if (tprob) KL_TRY(hip_ok(hipMemcpyAsync(tprob, w.s_probs, BT * sizeof(float), hipMemcpyDeviceToDevice, s)));
-  return 0;
-}
-
-// ---- rating windows with alternatives: kl_rate_window delivering the top K characters and the target's rank too --------
-// The results are staged behind the rate workspace in an area of their own -- the window's probability staging slot holds
-// B*T*V floats, fewer than the B*T*(2K + 2) words of a call once V < 2K + 2 -- and copied out after the graph, as tprob is.
+// ---- rating windows (rating.py:493-529 `rate`, many texts at once) --------------------------------------------
+// The window of kl_forward_window, but the [B][T][V] softmax is never formed.  Four deliveries of one body, rate_window_impl:
+//                             layout                                  K    leaves the window
+//   kl_rate_window            0: inference (window_logits)            0    the target's probability per position and/or
+//   kl_rate_window_bulk       1: training (window_logits_training)    0      one f64 sum of bits per stream
+//   kl_rate_window_alts       0                                       >0   ... and the top K characters and the target's rank
+//   kl_rate_window_alts_bulk  1                                       >0
+// Layout 0 takes any prepared precision and 256 streams per scan launch; layout 1 is bf16's: the wide persistent scans of
+// a validation window take thousands of streams per launch.  The workspace is the layout's window (carve_window); with
+// K = 0 its probability staging slot holds the [B][T] picks.  With K > 0 the results are staged behind it in an area of
+// their own (carve_alts) -- the slot holds B*T*V floats, fewer than the B*T*(2K + 2) words of a call once V < 2K + 2 --
+// and copied out after the graph, as tprob is.
 namespace {
 
 struct AltsWs {
@@ -2614,51 +2559,43 @@ size_t carve_alts(void* base, size_t BT, int K, AltsWs* out) {
   return align_up(cv.off, 256);
 }
 
-}  // namespace
-
-extern "C" size_t kl_rate_alts_workspace_bytes(const kl_handle* h, int B, int T, int K) {
-  if (!h || B < 1 || T < 1 || K < 1 || K > KL_RATE_ALTS_MAX) return 0;
-  return carve_window(h, nullptr, B, T, 0, nullptr) + carve_alts(nullptr, (size_t)B * T, K, nullptr);
-}
-
-namespace {
-
-// kl_rate_window_alts (training = 0: window_logits on the inference layout, any prepared precision, graph kind 3) and
-// kl_rate_window_alts_bulk (training = 1: window_logits_training on the training layout, bf16 only, graph kind 5) differ in
-// nothing else: the selection, the bits and the staging area behind the window's workspace are the same
-int rate_window_alts_impl(kl_handle* h, int training, int B, int T, int K, const int32_t* idx, const int32_t* ctx,
-                          const int32_t* tgt, float* states, float* tprob, int32_t* alt_id, float* alt_p, int32_t* rank,
-                          double* bits, float* status, void* ws, size_t ws_bytes, void* stream) {
+int rate_window_impl(kl_handle* h, int layout, int K, int B, int T, const int32_t* idx, const int32_t* ctx,
+                     const int32_t* tgt, float* states, float* tprob, int32_t* alt_id, float* alt_p, int32_t* rank,
+                     double* bits, float* status, void* ws, size_t ws_bytes, void* stream) {
+  const bool alts = K != 0;
   if (!h || !idx || !states || !ws || B < 1 || T < 1) return KL_ERR_ARG;
   if (h->cfg.n_ctx > 0 && !ctx) return KL_ERR_ARG;
-  if (!tgt || !alt_id || !alt_p || K < 1 || K > KL_RATE_ALTS_MAX) return KL_ERR_ARG;
-  if ((training ? h->precision != KL_PREC_BF16 : !h->precision) || h->last_only) return KL_ERR_STATE;      // (as kl_rate_window / _bulk)
+  if (alts ? !tgt || !alt_id || !alt_p || K < 1 || K > KL_RATE_ALTS_MAX : (tprob || bits) && !tgt) return KL_ERR_ARG;
+  // (the training forward is bf16's; one target per window is the stateless graph's: kl_forward_window)
+  if ((layout ? h->precision != KL_PREC_BF16 : !h->precision) || h->last_only) return KL_ERR_STATE;
   hipStream_t s = (hipStream_t)stream;
   WindowWs w;
-  AltsWs a;
+  AltsWs a{};
   const size_t BT = (size_t)B * T;
-  const size_t n_window = carve_window(h, nullptr, B, T, training, nullptr);      // (a multiple of 256: the staging area starts aligned)
-  if (ws_bytes < n_window + carve_alts(nullptr, BT, K, nullptr)) return KL_ERR_WORKSPACE;
-  carve_window(h, ws, B, T, training, &w);
-  carve_alts(reinterpret_cast<unsigned char*>(ws) + n_window, BT, K, &a);
-  KL_TRY(hip_ok(hipMemcpyAsync(w.s_idx, idx, BT * sizeof(int), hipMemcpyDeviceToDevice, s)));
-  if (h->cfg.n_ctx > 0)
-    KL_TRY(hip_ok(hipMemcpyAsync(w.s_ctx, ctx, BT * h->cfg.n_ctx * sizeof(int), hipMemcpyDeviceToDevice, s)));
-  KL_TRY(hip_ok(hipMemcpyAsync(w.s_tgt, tgt, BT * sizeof(int), hipMemcpyDeviceToDevice, s)));
+  const size_t n_window = carve_window(h, nullptr, B, T, layout, nullptr);      // (a multiple of 256: the staging area starts aligned)
+  if (ws_bytes < n_window + (alts ? carve_alts(nullptr, BT, K, nullptr) : 0)) return KL_ERR_WORKSPACE;
+  carve_window(h, ws, B, T, layout, &w);
+  if (alts) carve_alts(reinterpret_cast<unsigned char*>(ws) + n_window, BT, K, &a);
+  else a.tprob = w.s_probs;
+  const bool pick = alts || tprob || bits;
+  KL_TRY(stage_window(h, w, B, T, idx, ctx, pick ? tgt : nullptr, nullptr, s));
   // (baked into the captured launches: K, states, status, bits and the workspace -- all in the key; tprob, alt_id, alt_p and
-  // rank are staged, and which of the optional ones the caller takes is in the key's flags.  A kind per layout: the same
-  // arrays may serve both calls)
-  kl_handle::GraphKey key{training ? 5 : 3, B, T, (tprob ? 1 : 0) | (bits ? 2 : 0) | (rank ? 4 : 0) | (K << 3), h->precision, states, status, ws, bits, training};
+  // rank are staged, and which of the optional ones the caller takes is in the key's flags.  A kind per delivery and
+  // layout: the same arrays may serve all four calls)
+  const int flags = (tprob ? 1 : 0) | (bits ? 2 : 0) | (alts ? (rank ? 4 : 0) | (K << 3) : 0);
+  kl_handle::GraphKey key{(alts ? 3 : 2) + 2 * layout, B, T, flags, h->precision, states, status, ws, bits, layout};
   KL_TRY(run_graphed(h, key, s, [&]() {
     const int V = h->cfg.voc_size;
-    KL_TRY(training ? window_logits_training(h, B, T, w.s_idx, w.s_ctx, states, w, s)
-                    : window_logits(h, B, T, w.s_idx, w.s_ctx, states, w, s));
-    KL_TRY(kl_launch_rate_topk(w.logits, V, B * T, V, w.s_tgt, B, T, K, a.tprob, a.alt_id, a.alt_p, a.rank, s));
+    KL_TRY(layout ? window_logits_training(h, B, T, w.s_idx, w.s_ctx, states, w, s)
+                  : window_logits(h, B, T, w.s_idx, w.s_ctx, states, w, s));
+    if (alts) KL_TRY(kl_launch_rate_topk(w.logits, V, B * T, V, w.s_tgt, B, T, K, a.tprob, a.alt_id, a.alt_p, a.rank, s));
+    else if (pick) KL_TRY(kl_launch_rate_pick(w.logits, V, B * T, V, w.s_tgt, B, T, a.tprob, s));
     if (bits) KL_TRY(kl_launch_rate_bits(a.tprob, w.s_tgt, B, T, bits, s));
     if (status) hipLaunchKernelGGL(scan_status_kernel, dim3(1), dim3(64), 0, s, w.scan_status, status);
     return hip_ok(hipGetLastError());
   }));
   if (tprob) KL_TRY(hip_ok(hipMemcpyAsync(tprob, a.tprob, BT * sizeof(float), hipMemcpyDeviceToDevice, s)));
+  if (!alts) return 0;
   KL_TRY(hip_ok(hipMemcpyAsync(alt_id, a.alt_id, BT * K * sizeof(int), hipMemcpyDeviceToDevice, s)));
   KL_TRY(hip_ok(hipMemcpyAsync(alt_p, a.alt_p, BT * K * sizeof(float), hipMemcpyDeviceToDevice, s)));
   if (rank) KL_TRY(hip_ok(hipMemcpyAsync(rank, a.rank, BT * sizeof(int), hipMemcpyDeviceToDevice, s)));
@@ -2667,24 +2604,50 @@ int rate_window_alts_impl(kl_handle* h, int training, int B, int T, int K, const
 
 }  // namespace
 
-extern "C" int kl_rate_window_alts(kl_handle* h, int B, int T, int K, const int32_t* idx, const int32_t* ctx,
-                                   const int32_t* tgt, float* states, float* tprob, int32_t* alt_id, float* alt_p,
-                                   int32_t* rank, double* bits, float* status, void* ws, size_t ws_bytes, void* stream) {
-  return rate_window_alts_impl(h, 0, B, T, K, idx, ctx, tgt, states, tprob, alt_id, alt_p, rank, bits, status, ws, ws_bytes, stream);
+extern "C" size_t kl_rate_workspace_bytes(const kl_handle* h, int B, int T) {
+  if (!h || B < 1 || T < 1) return 0;
+  return carve_window(h, nullptr, B, T, 0, nullptr);
 }
 
-// ---- bulk rating with alternatives: kl_rate_window_alts' delivery on the training forward ----------------------------------
-// kl_rate_window_bulk's recurrence and logits (window_logits_training on a training-size workspace), then the selection and
-// the bits of kl_rate_window_alts; the results are staged behind the training window's workspace as carve_alts lays them out.
+extern "C" size_t kl_rate_bulk_workspace_bytes(const kl_handle* h, int B, int T) {
+  if (!h || B < 1 || T < 1) return 0;
+  return carve_window(h, nullptr, B, T, 1, nullptr);
+}
+
+extern "C" size_t kl_rate_alts_workspace_bytes(const kl_handle* h, int B, int T, int K) {
+  if (!h || B < 1 || T < 1 || K < 1 || K > KL_RATE_ALTS_MAX) return 0;
+  return carve_window(h, nullptr, B, T, 0, nullptr) + carve_alts(nullptr, (size_t)B * T, K, nullptr);
+}
+
 extern "C" size_t kl_rate_alts_bulk_workspace_bytes(const kl_handle* h, int B, int T, int K) {
   if (!h || B < 1 || T < 1 || K < 1 || K > KL_RATE_ALTS_MAX) return 0;
   return carve_window(h, nullptr, B, T, 1, nullptr) + carve_alts(nullptr, (size_t)B * T, K, nullptr);
 }
 
+extern "C" int kl_rate_window(kl_handle* h, int B, int T, const int32_t* idx, const int32_t* ctx, const int32_t* tgt,
+                              float* states, float* tprob, double* bits, float* status, void* ws, size_t ws_bytes,
+                              void* stream) {
+  return rate_window_impl(h, 0, 0, B, T, idx, ctx, tgt, states, tprob, nullptr, nullptr, nullptr, bits, status, ws, ws_bytes, stream);
+}
+
+extern "C" int kl_rate_window_bulk(kl_handle* h, int B, int T, const int32_t* idx, const int32_t* ctx, const int32_t* tgt,
+                                   float* states, float* tprob, double* bits, float* status, void* ws, size_t ws_bytes,
+                                   void* stream) {
+  return rate_window_impl(h, 1, 0, B, T, idx, ctx, tgt, states, tprob, nullptr, nullptr, nullptr, bits, status, ws, ws_bytes, stream);
+}
+
+extern "C" int kl_rate_window_alts(kl_handle* h, int B, int T, int K, const int32_t* idx, const int32_t* ctx,
+                                   const int32_t* tgt, float* states, float* tprob, int32_t* alt_id, float* alt_p,
+                                   int32_t* rank, double* bits, float* status, void* ws, size_t ws_bytes, void* stream) {
+  if (K == 0) return KL_ERR_ARG;      // (rate_window_impl reads K = 0 as target-only delivery)
+  return rate_window_impl(h, 0, K, B, T, idx, ctx, tgt, states, tprob, alt_id, alt_p, rank, bits, status, ws, ws_bytes, stream);
+}
+
 extern "C" int kl_rate_window_alts_bulk(kl_handle* h, int B, int T, int K, const int32_t* idx, const int32_t* ctx,
                                         const int32_t* tgt, float* states, float* tprob, int32_t* alt_id, float* alt_p,
                                         int32_t* rank, double* bits, float* status, void* ws, size_t ws_bytes, void* stream) {
-  return rate_window_alts_impl(h, 1, B, T, K, idx, ctx, tgt, states, tprob, alt_id, alt_p, rank, bits, status, ws, ws_bytes, stream);
+  if (K == 0) return KL_ERR_ARG;
+  return rate_window_impl(h, 1, K, B, T, idx, ctx, tgt, states, tprob, alt_id, alt_p, rank, bits, status, ws, ws_bytes, stream);
 }
 
 extern "C" int kl_train_window(kl_handle* h, int B, int T, const int32_t* idx, const int32_t* ctx, const int32_t* tgt,
@@ -2696,14 +2659,7 @@ extern "C" int kl_train_window(kl_handle* h, int B, int T, const int32_t* idx, c
   hipStream_t s = (hipStream_t)stream;
   WindowWs w;
   if (ws_bytes < carve_window(h, ws, B, T, 1, &w)) return KL_ERR_WORKSPACE;
-  const size_t BT = (size_t)B * T;
-  KL_TRY(hip_ok(hipMemcpyAsync(w.s_idx, idx, BT * sizeof(int), hipMemcpyDeviceToDevice, s)));
-  if (h->cfg.n_ctx > 0)
-    KL_TRY(hip_ok(hipMemcpyAsync(w.s_ctx, ctx, BT * h->cfg.n_ctx * sizeof(int), hipMemcpyDeviceToDevice, s)));
-  KL_TRY(hip_ok(hipMemcpyAsync(w.s_tgt, tgt, BT * sizeof(int), hipMemcpyDeviceToDevice, s)));
-  if (masks)
-    KL_TRY(hip_ok(hipMemcpyAsync(w.s_masks, masks, (size_t)h->cfg.depth * B * h->cfg.width * sizeof(float),
-                                 hipMemcpyDeviceToDevice, s)));
+  KL_TRY(stage_window(h, w, B, T, idx, ctx, tgt, masks, s));
   kl_handle::GraphKey key{1, B, T, (masks ? 1 : 0) | (h->last_only ? 4 : 0), h->precision, states, loss_acc, ws, grads, h->loss_rows};      // (last field: the count baked into the captured launches)
   return run_graphed(h, key, s, [&]() {
     return train_window_body(h, B, T, w.s_idx, w.s_ctx, w.s_tgt, states, masks ? w.s_masks : nullptr, grads, loss_acc,

@@ -82,16 +82,11 @@ class HipLM:
         self.adam_v = None
         self.adam_t = 0
         self.loss_acc = torch.zeros(4, dtype=torch.float32, device=self.device)
-        self._ws = None
-        self._ws_key = None
+        for slot in self._WS_SLOTS.values():      # (the workspace buffers and what they were sized for: _workspace)
+            setattr(self, slot, None)
+            setattr(self, slot + "_key", None)
         self.rate_bits = None       # [B] f64: bits per stream accumulated by rate_window
         self._rate_status = None
-        self._rate_ws = None
-        self._rate_ws_key = None
-        self._rate_alts_ws = None
-        self._rate_alts_ws_key = None
-        self._rate_alts_bulk_ws = None
-        self._rate_alts_bulk_ws_key = None
         self._rate_select_ws = None
         self.states = None         # [B][2L][W] implicit state of the stateful streams
         self.pool = None            # [slots][2L][W] explicit states of hypotheses
@@ -282,14 +277,48 @@ class HipLM:
         self.precision = int(precision)
 
     # ------------------------------------------------------------------ windows
-    def _workspace(self, B, T, training):
-        key = (B, T, bool(training))
-        if self._ws_key != key:
-            n = self.lib.kl_window_workspace_bytes(self.handle, B, T, 1 if training else 0)
-            self._ws = None
-            self._ws = self.torch.empty(n, dtype=self.torch.uint8, device=self.device)
-            self._ws_key = key
-        return self._ws
+    # kl_<kind>_workspace_bytes -> the attribute that holds the kind's buffer (its key in <attribute>_key)
+    _WS_SLOTS = {"window": "_ws", "rate": "_rate_ws", "rate_alts": "_rate_alts_ws", "rate_alts_bulk": "_rate_alts_bulk_ws"}
+
+    def _workspace(self, B, T, *tail, kind="window"):
+        """the kind's workspace for B streams of T characters, kept until another size is asked for.  tail: what else its size
+        depends on -- (training,) for "window", () for "rate", (k,) for "rate_alts" and "rate_alts_bulk"."""
+        slot = self._WS_SLOTS[kind]
+        key = (B, T) + tail
+        if getattr(self, slot + "_key") != key:
+            n = getattr(self.lib, "kl_%s_workspace_bytes" % kind)(self.handle, B, T, *map(int, tail))
+            setattr(self, slot, None)      # (the old buffer goes back to the allocator before the new one is taken)
+            setattr(self, slot, self.torch.empty(n, dtype=self.torch.uint8, device=self.device))
+            setattr(self, slot + "_key", key)
+        return getattr(self, slot)
+
+    def _pad_group(self, b0, b1, Bp, idx_d, ctx_d, tgt_d, fill):
+        """streams [b0, b1) of a batch as a group of Bp >= b1 - b0: returns (idx, ctx, tgt, states) of the group, ctx and tgt None
+        where the batch has none.  Bp beyond the real streams are dummy streams: idx 0, ctx 0, tgt `fill`, zero state -- the
+        states then a buffer of their own (one per padded count: its address is part of the replayed launch sequence's key)
+        that `_unpad_states` copies back."""
+        torch = self.torch
+        n = b1 - b0
+        x, st = idx_d[b0:b1], self.states[b0:b1]
+        c = ctx_d[b0:b1] if ctx_d is not None else None
+        y = tgt_d[b0:b1] if tgt_d is not None else None
+        if Bp != n:
+            x = torch.nn.functional.pad(x, (0, 0, 0, Bp - n))
+            if y is not None:
+                y = torch.nn.functional.pad(y, (0, 0, 0, Bp - n), value=fill)
+            if c is not None:
+                c = torch.nn.functional.pad(c, (0, 0) * (c.dim() - 1) + (0, Bp - n))
+            st = self._pad_states.get(Bp)
+            if st is None:
+                st = self._pad_states[Bp] = torch.zeros((Bp,) + tuple(self.states.shape[1:]), dtype=torch.float32,
+                                                        device=self.device)
+            st[:n] = self.states[b0:b1]
+            st[n:] = 0
+        return x, c, y, st
+
+    def _unpad_states(self, b0, b1, st):
+        if st.shape[0] != b1 - b0:
+            self.states[b0:b1] = st[:b1 - b0]
 
     def set_window_mode(self, last_only):
         """False (default): the stateful graph -- a target at every position, means over B*T positions.
@@ -348,20 +377,9 @@ class HipLM:
                 for (b0, b1), Bp in zip(parts, padded):
                     n = b1 - b0
                     self._part_loss.zero_()
-                    x, c, st = idx_d[b0:b1], (ctx_d[b0:b1] if ctx_d is not None else None), self.states[b0:b1]
-                    y = tgt_d[b0:b1] if tgt_d is not None else None
+                    # (-2, not the -1 of a padded tail: a dummy stream is no hit for the accuracy either)
+                    x, c, y, st = self._pad_group(b0, b1, Bp, idx_d, ctx_d, tgt_d, -2)
                     if Bp != n:
-                        x = torch.nn.functional.pad(x, (0, 0, 0, Bp - n))
-                        if y is not None:      # (-2, not the -1 of a padded tail: a dummy stream is no hit for the accuracy either)
-                            y = torch.nn.functional.pad(y, (0, 0, 0, Bp - n), value=-2)
-                        if c is not None:
-                            c = torch.nn.functional.pad(c, (0, 0) * (c.dim() - 1) + (0, Bp - n))
-                        st = self._pad_states.get(Bp)
-                        if st is None:
-                            st = self._pad_states[Bp] = torch.zeros((Bp,) + tuple(self.states.shape[1:]), dtype=torch.float32,
-                                                                    device=self.device)
-                        st[:n] = self.states[b0:b1]
-                        st[n:] = 0
                         hipabi.check(self.lib.kl_set_loss_rows(self.handle, n), "kl_set_loss_rows")
                     try:
                         hipabi.check(self.lib.kl_forward_window(self.handle, Bp, T, _ptr(x), _ptr(c), _ptr(y), _ptr(st),
@@ -371,8 +389,7 @@ class HipLM:
                     finally:
                         if Bp != n:
                             hipabi.check(self.lib.kl_set_loss_rows(self.handle, 0), "kl_set_loss_rows")
-                    if Bp != n:
-                        self.states[b0:b1] = st[:n]
+                    self._unpad_states(b0, b1, st)
                     self.loss_acc[:2] += (n / B) * self._part_loss[:2]
                     self.loss_acc[3] = torch.maximum(self.loss_acc[3], self._part_loss[3])
             if want_probs and float(self.loss_acc[3].item()) != 0.0:
@@ -381,16 +398,24 @@ class HipLM:
                 raise hipabi.KlError("persistent scan hand-off timed out (kl_forward_window)")
         return probs
 
-    # ------------------------------------------------------------------ rating windows, target-only delivery
-    def rate_window(self, idx, ctx, tgt, want_probs=True):
-        """One window of B independent stateful streams as `forward_window` runs it, delivering per position only the
-        probability of the target: idx [B,T], ctx [B,T,n_ctx], tgt [B,T] (< 0: no target, probability 0).
-        Returns a DEVICE tensor [B,T] f32 (None without want_probs) and adds -log2(max(p, 1e-99)) over each stream's
-        valid positions to the f64 accumulator `rate_bits` [B] (rate_bits_read).  Nothing is synchronised here: a timed-out
-        scan hand-off surfaces as KlError in rate_bits_read / rate_status_check."""
+    # ------------------------------------------------------------------ rating windows: one call, four deliveries
+    def _rate_call(self, idx, ctx, tgt, k, bulk, want_probs=True):
+        """What the four rate_window methods do.  k None: the target's probability only (tprob, or None without want_probs);
+        else also the k most probable characters and the target's rank (tprob, alt_id, alt_p, rank).  bulk: on the bf16
+        training forward, streams grouped and padded as `forward_window` does for validation windows, with the training
+        window's workspace when k is None; else on the inference layout in `_rating_groups`, unpadded."""
         torch = self.torch
         if self.precision == 0:
             raise hipabi.KlError("weights not prepared")
+        alts = k is not None
+        if alts:
+            k = int(k)
+            if not 1 <= k <= hipabi.KL_RATE_ALTS_MAX:
+                raise ValueError("k must be in 1..%d (got %d)" % (hipabi.KL_RATE_ALTS_MAX, k))
+        if bulk and self.precision != hipabi.KL_PREC_BF16:
+            self.prepare(hipabi.KL_PREC_BF16)
+        name = "kl_rate_window" + ("_alts" if alts else "") + ("_bulk" if bulk else "")
+        fn = getattr(self.lib, name)
         with self._launch():
             idx_d = self._dev_i32(idx)
             B, T = idx_d.shape
@@ -402,80 +427,65 @@ class HipLM:
                 self.rate_bits = torch.zeros(B, dtype=torch.float64, device=self.device)
             if self._rate_status is None:
                 self._rate_status = torch.zeros(4, dtype=torch.float32, device=self.device)
-            tprob = torch.empty((B, T), dtype=torch.float32, device=self.device) if want_probs else None
-            parts = self._rating_groups(B)
-            ws = self._rate_workspace(max(b1 - b0 for b0, b1 in parts), T)
-            for b0, b1 in parts:       # (streams are independent: more than one launch sequence takes run as groups)
-                hipabi.check(self.lib.kl_rate_window(
-                    self.handle, b1 - b0, T, _ptr(idx_d[b0:b1]), _ptr(ctx_d[b0:b1] if ctx_d is not None else None),
-                    _ptr(tgt_d[b0:b1]), _ptr(self.states[b0:b1]), _ptr(tprob[b0:b1] if tprob is not None else None),
-                    _ptr(self.rate_bits[b0:b1]), _ptr(self._rate_status), _ptr(ws), ws.numel(), self._stream()),
-                    "kl_rate_window")
-        return tprob
+            # (streams are independent: more than one launch sequence takes run as groups, the batch-major outputs sliced by stream)
+            parts = self._stream_groups(B, T) if bulk else self._rating_groups(B)
+            padded = [self._padded_streams(b1 - b0, T) if bulk else b1 - b0 for b0, b1 in parts]
+            if alts:
+                ws = self._workspace(max(padded), T, k, kind="rate_alts_bulk" if bulk else "rate_alts")
+                outs = [torch.empty((B, T) + tail, dtype=dtype, device=self.device) for tail, dtype in
+                        (((), torch.float32), ((k,), torch.int32), ((k,), torch.float32), ((), torch.int32))]
+            else:
+                ws = self._workspace(max(padded), T, True) if bulk else self._workspace(max(padded), T, kind="rate")
+                outs = [torch.empty((B, T), dtype=torch.float32, device=self.device)] if want_probs else []
+            for (b0, b1), Bp in zip(parts, padded):
+                n = b1 - b0
+                x, c, y, st = self._pad_group(b0, b1, Bp, idx_d, ctx_d, tgt_d, -1)
+                out, bits = [t[b0:b1] for t in outs], self.rate_bits[b0:b1]
+                if Bp != n:
+                    out = [torch.empty((Bp,) + tuple(t.shape[1:]), dtype=t.dtype, device=self.device) for t in outs]
+                    bits = torch.zeros(Bp, dtype=torch.float64, device=self.device)
+                hipabi.check(fn(self.handle, Bp, T, *([k] if alts else []), _ptr(x), _ptr(c), _ptr(y), _ptr(st),
+                                *([_ptr(t) for t in out] or [_ptr(None)]), _ptr(bits), _ptr(self._rate_status), _ptr(ws), ws.numel(),
+                                self._stream()), name)
+                if Bp != n:
+                    self._unpad_states(b0, b1, st)
+                    self.rate_bits[b0:b1] += bits[:n]
+                    for whole, part in zip(outs, out):
+                        whole[b0:b1] = part[:n]
+        return tuple(outs) if alts else (outs[0] if outs else None)
 
-    def _rate_workspace(self, B, T):
-        key = (B, T)
-        if self._rate_ws_key != key:
-            n = self.lib.kl_rate_workspace_bytes(self.handle, B, T)
-            self._rate_ws = None
-            self._rate_ws = self.torch.empty(n, dtype=self.torch.uint8, device=self.device)
-            self._rate_ws_key = key
-        return self._rate_ws
+    def rate_window(self, idx, ctx, tgt, want_probs=True):
+        """One window of B independent stateful streams as `forward_window` runs it, delivering per position only the
+        probability of the target: idx [B,T], ctx [B,T,n_ctx], tgt [B,T] (< 0: no target, probability 0).
+        Returns a DEVICE tensor [B,T] f32 (None without want_probs) and adds -log2(max(p, 1e-99)) over each stream's
+        valid positions to the f64 accumulator `rate_bits` [B] (rate_bits_read).  Nothing is synchronised here: a timed-out
+        scan hand-off surfaces as KlError in rate_bits_read / rate_status_check."""
+        return self._rate_call(idx, ctx, tgt, None, False, want_probs)
 
-    # ------------------------------------------------------------------ bulk rating: rating windows on the training forward
     def rate_window_bulk(self, idx_d, ctx_d, tgt_d, want_probs=True):
         """`rate_window` on the bf16 training forward (kl_rate_window_bulk): the wide persistent scans take thousands of
         streams per launch.  idx_d [B,T], ctx_d [B,T,n_ctx], tgt_d [B,T]: int32 DEVICE tensors (as `assemble_windows` makes
         them); returns a DEVICE tensor [B,T] f32 (None without want_probs).  Prepares bf16 precision if the handle is in
         another.  Streams are grouped and padded with dummy streams (idx 0, tgt -1, zero state: they deliver nothing and take
         no bits) as `forward_window` does for validation windows.  Bits and status as in `rate_window`."""
-        torch = self.torch
-        if self.precision == 0:
-            raise hipabi.KlError("weights not prepared")
-        if self.precision != hipabi.KL_PREC_BF16:
-            self.prepare(hipabi.KL_PREC_BF16)
-        with self._launch():
-            idx_d, tgt_d = self._dev_i32(idx_d), self._dev_i32(tgt_d)
-            B, T = idx_d.shape
-            ctx_d = self._dev_i32(ctx_d) if self.n_ctx else None
-            if self.states is None or self.states.shape[0] != B:
-                self.reset_states(B)
-            if self.rate_bits is None or self.rate_bits.shape[0] != B:
-                self.rate_bits = torch.zeros(B, dtype=torch.float64, device=self.device)
-            if self._rate_status is None:
-                self._rate_status = torch.zeros(4, dtype=torch.float32, device=self.device)
-            tprob = torch.empty((B, T), dtype=torch.float32, device=self.device) if want_probs else None
-            parts = self._stream_groups(B, T)
-            padded = [self._padded_streams(b1 - b0, T) for b0, b1 in parts]
-            ws = self._workspace(max(padded), T, True)
-            for (b0, b1), Bp in zip(parts, padded):
-                n = b1 - b0
-                x, c, y, st = idx_d[b0:b1], (ctx_d[b0:b1] if ctx_d is not None else None), tgt_d[b0:b1], self.states[b0:b1]
-                p = tprob[b0:b1] if tprob is not None else None
-                bits = self.rate_bits[b0:b1]
-                if Bp != n:
-                    x = torch.nn.functional.pad(x, (0, 0, 0, Bp - n))
-                    y = torch.nn.functional.pad(y, (0, 0, 0, Bp - n), value=-1)
-                    if c is not None:
-                        c = torch.nn.functional.pad(c, (0, 0, 0, 0, 0, Bp - n))
-                    st = self._pad_states.get(Bp)
-                    if st is None:
-                        st = self._pad_states[Bp] = torch.zeros((Bp,) + tuple(self.states.shape[1:]), dtype=torch.float32,
-                                                                device=self.device)
-                    st[:n] = self.states[b0:b1]
-                    st[n:] = 0
-                    if want_probs:
-                        p = torch.empty((Bp, T), dtype=torch.float32, device=self.device)
-                    bits = torch.zeros(Bp, dtype=torch.float64, device=self.device)
-                hipabi.check(self.lib.kl_rate_window_bulk(
-                    self.handle, Bp, T, _ptr(x), _ptr(c), _ptr(y), _ptr(st), _ptr(p), _ptr(bits), _ptr(self._rate_status),
-                    _ptr(ws), ws.numel(), self._stream()), "kl_rate_window_bulk")
-                if Bp != n:
-                    self.states[b0:b1] = st[:n]
-                    self.rate_bits[b0:b1] += bits[:n]
-                    if want_probs:
-                        tprob[b0:b1] = p[:n]
-        return tprob
+        return self._rate_call(idx_d, ctx_d, tgt_d, None, True, want_probs)
+
+    def rate_window_alts(self, idx, ctx, tgt, k):
+        """`rate_window` delivering per position also what the model expected instead (kl_rate_window_alts): returns the DEVICE
+        tensors tprob [B,T] f32 (what rate_window returns, bit for bit), alt_id [B,T,k] i32 and alt_p [B,T,k] f32 -- the k
+        most probable characters, ordered by (logit descending, id ascending), -1 / 0 from the V-th on -- and rank [B,T] i32,
+        the target's position in that order (0: the model's first choice; -1 without a target).  Positions with tgt < 0
+        deliver 0 / -1 / 0 / -1.  1 <= k <= hipabi.KL_RATE_ALTS_MAX.  Bits go to the same accumulator `rate_bits`, and
+        nothing is synchronised here either (rate_bits_read / rate_status_check)."""
+        return self._rate_call(idx, ctx, tgt, k, False)
+
+    def rate_window_alts_bulk(self, idx_d, ctx_d, tgt_d, k):
+        """`rate_window_alts` on the bf16 training forward (kl_rate_window_alts_bulk): idx_d [B,T], ctx_d [B,T,n_ctx], tgt_d
+        [B,T] int32 DEVICE tensors (as `assemble_windows` makes them); returns the DEVICE tensors (tprob [B,T] f32 -- what
+        `rate_window_bulk` returns, bit for bit --, alt_id [B,T,k] i32, alt_p [B,T,k] f32, rank [B,T] i32).  Prepares bf16
+        precision if the handle is in another; streams are grouped and padded with dummy streams (idx 0, tgt -1, zero state:
+        they deliver nothing and take no bits) exactly as `rate_window_bulk` does.  Bits and status as in `rate_window`."""
+        return self._rate_call(idx_d, ctx_d, tgt_d, k, True)
 
     def reset_states_where(self, mask_d):
         """zero the state rows mask_d (bool DEVICE tensor [B]) names: one masked fill, no index list"""
@@ -511,123 +521,6 @@ class HipLM:
             hipabi.check(self.lib.kl_rate_text_bits(_ptr(probs), _ptr(offsets), n, _ptr(bits), self._stream()),
                          "kl_rate_text_bits")
         return bits
-
-    def rate_window_alts(self, idx, ctx, tgt, k):
-        """`rate_window` delivering per position also what the model expected instead (kl_rate_window_alts): returns the DEVICE
-        tensors tprob [B,T] f32 (what rate_window returns, bit for bit), alt_id [B,T,k] i32 and alt_p [B,T,k] f32 -- the k
-        most probable characters, ordered by (logit descending, id ascending), -1 / 0 from the V-th on -- and rank [B,T] i32,
-        the target's position in that order (0: the model's first choice; -1 without a target).  Positions with tgt < 0
-        deliver 0 / -1 / 0 / -1.  1 <= k <= hipabi.KL_RATE_ALTS_MAX.  Bits go to the same accumulator `rate_bits`, and
-        nothing is synchronised here either (rate_bits_read / rate_status_check)."""
-        torch = self.torch
-        if self.precision == 0:
-            raise hipabi.KlError("weights not prepared")
-        k = int(k)
-        if not 1 <= k <= hipabi.KL_RATE_ALTS_MAX:
-            raise ValueError("k must be in 1..%d (got %d)" % (hipabi.KL_RATE_ALTS_MAX, k))
-        with self._launch():
-            idx_d = self._dev_i32(idx)
-            B, T = idx_d.shape
-            ctx_d = self._dev_i32(ctx) if self.n_ctx else None
-            tgt_d = self._dev_i32(tgt)
-            if self.states is None or self.states.shape[0] != B:
-                self.reset_states(B)
-            if self.rate_bits is None or self.rate_bits.shape[0] != B:
-                self.rate_bits = torch.zeros(B, dtype=torch.float64, device=self.device)
-            if self._rate_status is None:
-                self._rate_status = torch.zeros(4, dtype=torch.float32, device=self.device)
-            tprob = torch.empty((B, T), dtype=torch.float32, device=self.device)
-            alt_id = torch.empty((B, T, k), dtype=torch.int32, device=self.device)
-            alt_p = torch.empty((B, T, k), dtype=torch.float32, device=self.device)
-            rank = torch.empty((B, T), dtype=torch.int32, device=self.device)
-            parts = self._rating_groups(B)
-            ws = self._rate_alts_workspace(max(b1 - b0 for b0, b1 in parts), T, k)
-            for b0, b1 in parts:       # (as rate_window: the batch-major outputs are sliced by stream)
-                hipabi.check(self.lib.kl_rate_window_alts(
-                    self.handle, b1 - b0, T, k, _ptr(idx_d[b0:b1]), _ptr(ctx_d[b0:b1] if ctx_d is not None else None),
-                    _ptr(tgt_d[b0:b1]), _ptr(self.states[b0:b1]), _ptr(tprob[b0:b1]), _ptr(alt_id[b0:b1]), _ptr(alt_p[b0:b1]),
-                    _ptr(rank[b0:b1]), _ptr(self.rate_bits[b0:b1]), _ptr(self._rate_status), _ptr(ws), ws.numel(),
-                    self._stream()), "kl_rate_window_alts")
-        return tprob, alt_id, alt_p, rank
-
-    def _rate_alts_workspace(self, B, T, k):
-        key = (B, T, k)
-        if self._rate_alts_ws_key != key:
-            n = self.lib.kl_rate_alts_workspace_bytes(self.handle, B, T, k)
-            self._rate_alts_ws = None
-            self._rate_alts_ws = self.torch.empty(n, dtype=self.torch.uint8, device=self.device)
-            self._rate_alts_ws_key = key
-        return self._rate_alts_ws
-
-    # ------------------------------------------------------------------ bulk rating with alternatives, suspect positions
-    def rate_window_alts_bulk(self, idx_d, ctx_d, tgt_d, k):
-        """`rate_window_alts` on the bf16 training forward (kl_rate_window_alts_bulk): idx_d [B,T], ctx_d [B,T,n_ctx], tgt_d
-        [B,T] int32 DEVICE tensors (as `assemble_windows` makes them); returns the DEVICE tensors (tprob [B,T] f32 -- what
-        `rate_window_bulk` returns, bit for bit --, alt_id [B,T,k] i32, alt_p [B,T,k] f32, rank [B,T] i32).  Prepares bf16
-        precision if the handle is in another; streams are grouped and padded with dummy streams (idx 0, tgt -1, zero state:
-        they deliver nothing and take no bits) exactly as `rate_window_bulk` does.  Bits and status as in `rate_window`."""
-        torch = self.torch
-        if self.precision == 0:
-            raise hipabi.KlError("weights not prepared")
-        k = int(k)
-        if not 1 <= k <= hipabi.KL_RATE_ALTS_MAX:
-            raise ValueError("k must be in 1..%d (got %d)" % (hipabi.KL_RATE_ALTS_MAX, k))
-        if self.precision != hipabi.KL_PREC_BF16:
-            self.prepare(hipabi.KL_PREC_BF16)
-        with self._launch():
-            idx_d, tgt_d = self._dev_i32(idx_d), self._dev_i32(tgt_d)
-            B, T = idx_d.shape
-            ctx_d = self._dev_i32(ctx_d) if self.n_ctx else None
-            if self.states is None or self.states.shape[0] != B:
-                self.reset_states(B)
-            if self.rate_bits is None or self.rate_bits.shape[0] != B:
-                self.rate_bits = torch.zeros(B, dtype=torch.float64, device=self.device)
-            if self._rate_status is None:
-                self._rate_status = torch.zeros(4, dtype=torch.float32, device=self.device)
-            tprob = torch.empty((B, T), dtype=torch.float32, device=self.device)
-            alt_id = torch.empty((B, T, k), dtype=torch.int32, device=self.device)
-            alt_p = torch.empty((B, T, k), dtype=torch.float32, device=self.device)
-            rank = torch.empty((B, T), dtype=torch.int32, device=self.device)
-            parts = self._stream_groups(B, T)
-            padded = [self._padded_streams(b1 - b0, T) for b0, b1 in parts]
-            ws = self._rate_alts_bulk_workspace(max(padded), T, k)
-            for (b0, b1), Bp in zip(parts, padded):
-                n = b1 - b0
-                x, c, y, st = idx_d[b0:b1], (ctx_d[b0:b1] if ctx_d is not None else None), tgt_d[b0:b1], self.states[b0:b1]
-                out = [tprob[b0:b1], alt_id[b0:b1], alt_p[b0:b1], rank[b0:b1]]
-                bits = self.rate_bits[b0:b1]
-                if Bp != n:
-                    x = torch.nn.functional.pad(x, (0, 0, 0, Bp - n))
-                    y = torch.nn.functional.pad(y, (0, 0, 0, Bp - n), value=-1)
-                    if c is not None:
-                        c = torch.nn.functional.pad(c, (0, 0, 0, 0, 0, Bp - n))
-                    st = self._pad_states.get(Bp)
-                    if st is None:
-                        st = self._pad_states[Bp] = torch.zeros((Bp,) + tuple(self.states.shape[1:]), dtype=torch.float32,
-                                                                device=self.device)
-                    st[:n] = self.states[b0:b1]
-                    st[n:] = 0
-                    out = [torch.empty((Bp,) + tuple(t.shape[1:]), dtype=t.dtype, device=self.device) for t in out]
-                    bits = torch.zeros(Bp, dtype=torch.float64, device=self.device)
-                hipabi.check(self.lib.kl_rate_window_alts_bulk(
-                    self.handle, Bp, T, k, _ptr(x), _ptr(c), _ptr(y), _ptr(st), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
-                    _ptr(out[3]), _ptr(bits), _ptr(self._rate_status), _ptr(ws), ws.numel(), self._stream()),
-                    "kl_rate_window_alts_bulk")
-                if Bp != n:
-                    self.states[b0:b1] = st[:n]
-                    self.rate_bits[b0:b1] += bits[:n]
-                    for whole, part in zip((tprob, alt_id, alt_p, rank), out):
-                        whole[b0:b1] = part[:n]
-        return tprob, alt_id, alt_p, rank
-
-    def _rate_alts_bulk_workspace(self, B, T, k):
-        key = (B, T, k)
-        if self._rate_alts_bulk_ws_key != key:
-            n = self.lib.kl_rate_alts_bulk_workspace_bytes(self.handle, B, T, k)
-            self._rate_alts_bulk_ws = None
-            self._rate_alts_bulk_ws = self.torch.empty(n, dtype=self.torch.uint8, device=self.device)
-            self._rate_alts_bulk_ws_key = key
-        return self._rate_alts_bulk_ws
 
     def rate_scatter_alts(self, tprob, rank, alt_id, alt_p, plan, n_ctx, out_prob, out_rank, out_alt_id, out_alt_p):
         """kl_rate_scatter_alts: `rate_scatter` for all four results of a `rate_window_alts(_bulk)` call (DEVICE tensors tprob,
@@ -855,25 +748,14 @@ class HipLM:
                 wgt = n / B
                 self._part_loss.zero_()
                 m = masks_d[:, b0:b1] if masks_d is not None else None
-                c = ctx_d[b0:b1] if ctx_d is not None else None
-                x, y, st = idx_d[b0:b1], tgt_d[b0:b1], self.states[b0:b1]
+                # (-2, not the -1 of a padded tail: Keras counts an all-zero target row as a hit when class 0 wins, a dummy stream
+                #  must not be counted at all)
+                x, c, y, st = self._pad_group(b0, b1, Bp, idx_d, ctx_d, tgt_d, -2)
                 if Bp != n:
-                    x = torch.nn.functional.pad(x, (0, 0, 0, Bp - n))
-                    # (-2, not the -1 of a padded tail: Keras counts an all-zero target row as a hit when class 0 wins, a dummy stream
-                    #  must not be counted at all)
-                    y = torch.nn.functional.pad(y, (0, 0, 0, Bp - n), value=-2)
-                    if c is not None:
-                        c = torch.nn.functional.pad(c, (0, 0) * (c.dim() - 1) + (0, Bp - n))
                     if m is not None:
                         # (the dummy streams' keep-masks repeat real streams': the register-tile backward scan keeps a mask as
                         #  one bit per cell plus ONE scale per thread and refuses a mask with a second non-zero value)
                         m = torch.cat([m, m[:, :Bp - n]], dim=1)
-                    st = self._pad_states.get(Bp)
-                    if st is None:      # (one buffer per padded count: its address is part of the replayed launch sequence's key)
-                        st = self._pad_states[Bp] = torch.zeros((Bp,) + tuple(self.states.shape[1:]), dtype=torch.float32,
-                                                                device=self.device)
-                    st[:n] = self.states[b0:b1]
-                    st[n:] = 0
                     hipabi.check(self.lib.kl_set_loss_rows(self.handle, n), "kl_set_loss_rows")
                 if m is not None:
                     m = m.contiguous()
@@ -884,8 +766,7 @@ class HipLM:
                 finally:
                     if Bp != n:
                         hipabi.check(self.lib.kl_set_loss_rows(self.handle, 0), "kl_set_loss_rows")
-                if Bp != n:
-                    self.states[b0:b1] = st[:n]
+                self._unpad_states(b0, b1, st)
                 self._last_window = (Bp, T, b0, n, len(parts))
                 if i == 0:
                     torch.mul(self._part_grads, wgt, out=self.grads)

@@ -822,25 +822,18 @@ class Rater(object):
         uploaded once (ratebulk.py), short texts run in windows as short as they are, and with want_probs=False only the
         bits leave the device.  Same return contract; a stateless rater raises ValueError.  The next split-precision
         call restores split precision by itself.'''
-        assert self.status > 1
-        assert self.incremental is False
-        if precision not in ("split", "bf16"):
-            raise ValueError('precision must be "split" or "bf16" (got %r)' % (precision,))
-        if precision == "bf16" and not self.stateful:
-            raise ValueError('rate_batch(precision="bf16") needs a stateful rater: bulk rating runs stateful windows')
-        texts = list(texts)
+        texts, contexts = self._rating_request("rate_batch", texts, contexts, precision)[:2]
         n = len(texts)
-        if contexts is None or len(contexts) == 0:
-            contexts = [self.underspecify_contexts()] * n
-        elif isinstance(contexts[0], (int, np.integer)):
-            contexts = [list(contexts)] * n
-        else:
-            assert len(contexts) == n, "one context list per text"
-            contexts = [list(c) if (c is not None and len(c)) else self.underspecify_contexts() for c in contexts]
         lm = self.model
         if precision == "bf16" and hasattr(lm, 'rate_window_bulk'):
-            return self._rate_batch_bulk(texts, contexts, streams, want_probs)
-        # (an engine without rate_window_bulk -- the tests' CPU double -- runs the ordinary plan)
+            # (an engine without rate_window_bulk -- the tests' CPU double -- runs the ordinary plan)
+            plan, arrays, bits = self._rate_in_corpus_order(texts, contexts, 0, streams, "bf16")
+            if not want_probs:
+                return None, bits
+            if arrays is None:
+                return [np.ones(int(m), dtype=np.float32) for m in plan.sizes], bits
+            flat = _np(arrays[0])
+            return [flat[int(plan.offsets[i]):int(plan.offsets[i + 1])].copy() for i in range(n)], bits
         self._ensure_precision()
         bits = np.zeros(n, dtype=np.float64)
         if not self.stateful:
@@ -858,85 +851,83 @@ class Rater(object):
             lm.reset_states(1)
             return ([np.ones(len(t), dtype=np.float32) for t in texts] if want_probs else None), bits
         lm.reset_states(plan.B)
-        if hasattr(lm, 'rate_window'):
-            picked = self._run_rate_plan(plan, bits, want_probs)
+        picked = self._run_plan(plan, 0, bits, want_probs)
+        lm.reset_states(1)
+        if not want_probs:
+            return None, bits
+        return [plan.text_probs(i, picked[0]) for i in range(n)], bits
+
+    def _rating_request(self, method, texts, contexts, precision, k=None, max_prob=None, min_rank=None):
+        '''What `rate_batch`, `rate_alternatives`, `suspects` and `corrections` (`method`) check of a request before they rate:
+        returns (texts as a list, one context list per text, k, np.float32(max_prob), min_rank) -- the last three None where
+        the method has no such argument (k: rate_batch; max_prob and min_rank: all but suspects and corrections).'''
+        assert self.status > 1
+        assert self.incremental is False
+        if precision not in ("split", "bf16"):
+            raise ValueError('precision must be "split" or "bf16" (got %r)' % (precision,))
+        if not self.stateful:
+            if min_rank is not None:
+                raise ValueError('%s needs a stateful rater: it rates through stateful windows' % method)
+            if precision == "bf16":
+                raise ValueError('%s(precision="bf16") needs a stateful rater: bulk rating runs stateful windows' % method)
+            assert k is None, "%s needs a stateful rater" % method
+        limit = None
+        if k is not None:
+            k = int(k)
+            assert 1 <= k <= ratebatch.ALTS_MAX, "k must be in 1..%d" % ratebatch.ALTS_MAX
+        if min_rank is not None:
+            min_rank, limit = int(min_rank), np.float32(max_prob)
+            if min_rank < 0:
+                raise ValueError("min_rank must be >= 0 (got %d): a character without a prediction is no suspect" % min_rank)
+            if np.isnan(limit):
+                raise ValueError("max_prob must not be NaN")
+        texts = list(texts)
+        return texts, self._contexts_per_text(contexts, len(texts)), k, limit, min_rank
+
+    def _run_plan(self, plan, k, bits, want_probs=True):
+        '''The window calls of a ratebatch.Plan (its states reset to plan.B rows by the caller): rows that start a text are
+        reset, every call is rated, `bits` (per text) is filled.  Returns the host arrays [picked [n_calls][B][T]] (k == 0;
+        None on the HIP engine without want_probs) or [picked, alt_id, alt_p, rank] (k > 0; alt_id, alt_p [n_calls][B][T][k]).
+        The HIP engine delivers per call what `rate_window` / `rate_window_alts` return and takes a text's bits from the
+        device's f64 sums where it ends, one transfer of each at the end; an engine without these calls (the tests' CPU
+        double) delivers the whole softmax of `forward_window`, picked from on the host.'''
+        lm = self.model
+        device = hasattr(lm, 'rate_window_alts' if k else 'rate_window')
+        taken = []
+        if device:
+            lm.rate_bits_read(reset=True)
+
+            def rate(s, x, z, y):
+                out = lm.rate_window_alts(x, z, y, k) if k else (lm.rate_window(x, z, y, want_probs=want_probs),)
+                ending = plan.ending(s)
+                if ending:       # (a row's sum belongs to the text that ends here: take it, the next text starts from zero)
+                    taken.append((ending, lm.rate_bits_take([int(plan.row[i]) for i in ending])))
+                return out
         else:
-            # an engine without target-only delivery (the tests' CPU double): the whole softmax and a pick on the host
-            steps = []
-            for s in range(plan.n_calls):
-                x, z, y = plan.call(s)
-                if s and plan.starting(s):
-                    lm.reset_states(rows=plan.reset_rows(s))
+            def rate(s, x, z, y):
                 full = _np(lm.forward_window(x, z, want_probs=True))
+                if k:
+                    return ratebatch.alternatives_of(full, y, k)
                 p = np.take_along_axis(full, np.maximum(y, 0)[:, :, None], axis=2)[:, :, 0]
-                steps.append(np.where(y >= 0, p, 0.0).astype(np.float32))
-            picked = np.stack(steps)
-            bits[:] = [ratebatch.bits_of(plan.text_probs(i, picked)) for i in range(n)]
-        lm.reset_states(1)
-        if not want_probs:
-            return None, bits
-        return [plan.text_probs(i, picked) for i in range(n)], bits
-
-    def _rate_batch_bulk(self, texts, contexts, streams, want_probs):
-        '''rate_batch on the bf16 training forward: one upload (ids, plan rows and reset masks of all calls), per call
-        assemble_windows -> rate_window_bulk -> rate_scatter on the device, then one rate_text_bits and one transfer'''
-        lm = self.model
-        torch = lm.torch
-        n = len(texts)
-        texts = [windows.normalize(t) for t in texts]
-        ids = [windows.encode(t, self.mapping[0], self._unmapped_input) for t in texts]
-        sizes = [len(a) for a in ids]
-        plan = ratebulk.plan(sizes, [windows.clamp_context(c) for c in contexts], self.length, streams)
-        bits = np.zeros(n, dtype=np.float64)
-        if not plan.calls:       # (nothing but empty texts and single characters)
-            lm.reset_states(1)
-            return ([np.ones(len(t), dtype=np.float32) for t in texts] if want_probs else None), bits
-        n_ctx = plan.n_ctx
-        bounds = np.concatenate([[0], np.cumsum([c.B for c in plan.calls])])
-        corpus = torch.from_numpy(np.concatenate(ids).astype(np.int32)).to(lm.device)
-        rows = torch.from_numpy(np.concatenate([c.rows for c in plan.calls])).to(lm.device)
-        reset = torch.from_numpy(np.concatenate([c.reset for c in plan.calls])).to(lm.device)
-        offsets = torch.from_numpy(plan.offsets).to(lm.device)
-        out = torch.ones(plan.total, dtype=torch.float32, device=lm.device)      # (1.0: a text's first character)
-        B = None
-        for s, call in enumerate(plan.calls):
-            a, b = int(bounds[s]), int(bounds[s + 1])
-            if call.B != B:
-                B = call.B
-                lm.reset_states(B)      # (another number of rows: all of them start from zero)
-            elif call.reset.any():
-                lm.reset_states_where(reset[a:b])
-            x, z, y = lm.assemble_windows(corpus, rows[a:b], call.T, n_ctx)
-            p = lm.rate_window_bulk(x, z, y, want_probs=True)
-            lm.rate_scatter(p, rows[a:b], n_ctx, out)
-        bits_d = lm.rate_text_bits(out, offsets)
-        bits[:] = _np(bits_d)
-        lm.rate_bits_read(reset=True)      # (the per-stream sums are not used here; also raises on a timed-out scan hand-off)
-        lm.reset_states(1)
-        if not want_probs:
-            return None, bits
-        flat = _np(out)
-        return [flat[int(plan.offsets[i]):int(plan.offsets[i + 1])].copy() for i in range(n)], bits
-
-    def _run_rate_plan(self, plan, bits, want_probs):
-        '''the window calls of a ratebatch.Plan on the HIP engine: fills bits (per text) from the device's f64 sums
-        and returns the picked probabilities [n_calls][B][T] (None without want_probs).  One transfer of each at the end.'''
-        lm = self.model
-        lm.rate_bits_read(reset=True)
-        steps, taken = [], []
+                return (np.where(y >= 0, p, 0.0),)
+        steps = []
         for s in range(plan.n_calls):
             x, z, y = plan.call(s)
             if s and plan.starting(s):
                 lm.reset_states(rows=plan.reset_rows(s))
-            p = lm.rate_window(x, z, y, want_probs=want_probs)
-            if want_probs:
-                steps.append(p)
-            ending = plan.ending(s)
-            if ending:       # (a row's sum belongs to the text that ends here: take it, the next text starts from zero)
-                taken.append((ending, lm.rate_bits_take([int(plan.row[i]) for i in ending])))
-        bits[np.concatenate([e for e, _ in taken])] = _np(lm.torch.cat([t for _, t in taken]))
-        lm.rate_status_check()
-        return _np(lm.torch.stack(steps)) if want_probs else None
+            steps.append(rate(s, x, z, y))
+        if device:
+            bits[np.concatenate([e for e, _ in taken])] = _np(lm.torch.cat([t for _, t in taken]))
+            lm.rate_status_check()
+            if not want_probs:
+                return None
+            return [_np(lm.torch.stack([st[j] for st in steps])) for j in range(len(steps[0]))]
+        cols = [np.stack([st[j] for st in steps]) for j in range(len(steps[0]))]
+        cols[0] = cols[0].astype(np.float32)
+        if k:
+            cols[2] = cols[2].astype(np.float32)
+        bits[:] = [ratebatch.bits_of(plan.text_probs(i, cols[0])) for i in range(len(bits))]
+        return cols
 
     def rate_alternatives(self, texts, contexts=None, k=3, streams=64, precision="split"):
         '''`rate_batch` answering also what the model expected instead: returns (rated, bits), both in input order.
@@ -953,27 +944,11 @@ class Rater(object):
         results kept in corpus order on the device -- (8k + 8) bytes per character -- and one transfer at the end; `probs`
         are bit for bit those of `rate_batch(precision="bf16")`.  Same return contract; a stateless rater raises
         ValueError; the state and precision afterwards are as after `rate_batch(precision="bf16")`.'''
-        assert self.status > 1
-        assert self.incremental is False
-        if precision not in ("split", "bf16"):
-            raise ValueError('precision must be "split" or "bf16" (got %r)' % (precision,))
-        if precision == "bf16" and not self.stateful:
-            raise ValueError('rate_alternatives(precision="bf16") needs a stateful rater: bulk rating runs stateful windows')
-        assert self.stateful, "rate_alternatives needs a stateful rater"
-        k = int(k)
-        assert 1 <= k <= ratebatch.ALTS_MAX, "k must be in 1..%d" % ratebatch.ALTS_MAX
-        texts = list(texts)
+        texts, contexts, k = self._rating_request("rate_alternatives", texts, contexts, precision, k)[:3]
         n = len(texts)
-        if contexts is None or len(contexts) == 0:
-            contexts = [self.underspecify_contexts()] * n
-        elif isinstance(contexts[0], (int, np.integer)):
-            contexts = [list(contexts)] * n
-        else:
-            assert len(contexts) == n, "one context list per text"
-            contexts = [list(c) if (c is not None and len(c)) else self.underspecify_contexts() for c in contexts]
         if precision == "bf16" and hasattr(self.model, 'rate_window_alts_bulk'):
             # (an engine without rate_window_alts_bulk -- the tests' CPU double -- runs the ordinary path below)
-            plan, arrays, bits = self._alternatives_in_corpus_order(texts, contexts, k, streams, "bf16")
+            plan, arrays, bits = self._rate_in_corpus_order(texts, contexts, k, streams, "bf16")
             if arrays is None:
                 return [ratebatch.RatedText.unpredicted(int(m), k) for m in plan.sizes], bits
             probs, rank, alt_id, alt_p = (_np(a) for a in arrays)
@@ -990,53 +965,22 @@ class Rater(object):
             lm.reset_states(1)
             return [ratebatch.RatedText.unpredicted(len(t), k) for t in texts], bits
         lm.reset_states(plan.B)
-        if hasattr(lm, 'rate_window_alts'):
-            picked, rank, alt_id, alt_p = self._run_alternatives_plan(plan, bits, k)
-        else:
-            # an engine without the device selection (the tests' CPU double): the whole softmax and the numpy statement
-            steps = []
-            for s in range(plan.n_calls):
-                x, z, y = plan.call(s)
-                if s and plan.starting(s):
-                    lm.reset_states(rows=plan.reset_rows(s))
-                steps.append(ratebatch.alternatives_of(_np(lm.forward_window(x, z, want_probs=True)), y, k))
-            picked, alt_id, alt_p, rank = (np.stack([st[j] for st in steps]) for j in range(4))
-            picked, alt_p = picked.astype(np.float32), alt_p.astype(np.float32)
-            bits[:] = [ratebatch.bits_of(plan.text_probs(i, picked)) for i in range(n)]
+        picked, alt_id, alt_p, rank = self._run_plan(plan, k, bits)
         lm.reset_states(1)
         return [ratebatch.RatedText(*plan.text_alternatives(i, picked, rank, alt_id, alt_p)) for i in range(n)], bits
 
-    def _run_alternatives_plan(self, plan, bits, k):
-        '''_run_rate_plan through `rate_window_alts`: fills bits and returns (picked, rank [n_calls][B][T], alt_id, alt_p
-        [n_calls][B][T][k]).  One transfer of each at the end.'''
-        lm = self.model
-        lm.rate_bits_read(reset=True)
-        steps, taken = [], []
-        for s in range(plan.n_calls):
-            x, z, y = plan.call(s)
-            if s and plan.starting(s):
-                lm.reset_states(rows=plan.reset_rows(s))
-            steps.append(lm.rate_window_alts(x, z, y, k))
-            ending = plan.ending(s)
-            if ending:
-                taken.append((ending, lm.rate_bits_take([int(plan.row[i]) for i in ending])))
-        bits[np.concatenate([e for e, _ in taken])] = _np(lm.torch.cat([t for _, t in taken]))
-        lm.rate_status_check()
-        picked, alt_id, alt_p, rank = (_np(lm.torch.stack([st[j] for st in steps])) for j in range(4))
-        return picked, rank, alt_id, alt_p
-
-    def _alternatives_in_corpus_order(self, texts, contexts, k, streams, precision, keep=None):
-        '''the bulk plan (ratebulk.plan: rows reused, short texts in short windows) with alternatives, everything kept on the
-        device: one upload (ids, plan rows, reset masks and offsets of all calls), per call assemble_windows ->
-        rate_window_alts_bulk ("bf16") or rate_window_alts ("split", the inference workspace) -> rate_scatter_alts, then one
-        rate_text_bits.  Returns (plan, (probs [n], rank [n], alt_id [n,k], alt_p [n,k]) DEVICE tensors in corpus order, bits);
-        the tensors are None if no text has a prediction.  A text's first character keeps 1.0 / -1 / -1 / 0.  A dict passed as
-        `keep` receives what stays on the device for a caller that goes on there (`corrections`): corpus (int32 [n]), offsets
-        (int64 [n_texts + 1]) and text_ctx (int32 [n_texts, n_ctx], the clamped contexts of every text).'''
+    def _rate_in_corpus_order(self, texts, contexts, k, streams, precision, keep=None):
+        '''The bulk plan (ratebulk.plan: rows reused, short texts in short windows) over texts with one context list each
+        (`_contexts_per_text`), everything kept on the device: one upload (ids, plan rows, reset masks and offsets of all
+        calls), per call assemble_windows -> the window call -> a scatter, then one rate_text_bits.  k == 0: probabilities only (rate_window_bulk for "bf16", rate_window for "split" -- the inference
+        workspace --, rate_scatter); k > 0: with alternatives (rate_window_alts_bulk or rate_window_alts, rate_scatter_alts).
+        Returns (plan, DEVICE tensors in corpus order, bits): (probs [n],) or (probs [n], rank [n], alt_id [n,k], alt_p [n,k]);
+        None instead of the tensors if no text has a prediction.  A text's first character keeps 1.0 / -1 / -1 / 0.  A dict
+        passed as `keep` receives what stays on the device for a caller that goes on there (`corrections`): corpus (int32
+        [n]), offsets (int64 [n_texts + 1]) and text_ctx (int32 [n_texts, n_ctx], the clamped contexts of every text).'''
         lm = self.model
         torch = lm.torch
         n = len(texts)
-        contexts = self._contexts_per_text(contexts, n)
         texts = [windows.normalize(t) for t in texts]
         ids = [windows.encode(t, self.mapping[0], self._unmapped_input) for t in texts]
         plan = ratebulk.plan([len(a) for a in ids], [windows.clamp_context(c) for c in contexts], self.length, streams)
@@ -1055,11 +999,12 @@ class Rater(object):
         if keep is not None:
             text_ctx = np.asarray([windows.clamp_context(c) for c in contexts], dtype=np.int32).reshape(n, n_ctx)
             keep.update(corpus=corpus, offsets=offsets, text_ctx=torch.from_numpy(text_ctx).to(lm.device))
-        out_prob = torch.ones(plan.total, dtype=torch.float32, device=lm.device)
-        out_rank = torch.full((plan.total,), -1, dtype=torch.int32, device=lm.device)
-        out_alt_id = torch.full((plan.total, k), -1, dtype=torch.int32, device=lm.device)
-        out_alt_p = torch.zeros((plan.total, k), dtype=torch.float32, device=lm.device)
-        rate = lm.rate_window_alts_bulk if precision == "bf16" else lm.rate_window_alts
+        out = [torch.ones(plan.total, dtype=torch.float32, device=lm.device)]      # (1.0: a text's first character)
+        if k:      # (rank, alt_id, alt_p)
+            out += [torch.full((plan.total,), -1, dtype=torch.int32, device=lm.device),
+                    torch.full((plan.total, k), -1, dtype=torch.int32, device=lm.device),
+                    torch.zeros((plan.total, k), dtype=torch.float32, device=lm.device)]
+        bulk = precision == "bf16"
         B = None
         for s, call in enumerate(plan.calls):
             a, b = int(bounds[s]), int(bounds[s + 1])
@@ -1069,12 +1014,31 @@ class Rater(object):
             elif call.reset.any():
                 lm.reset_states_where(reset[a:b])
             x, z, y = lm.assemble_windows(corpus, rows[a:b], call.T, n_ctx)
-            p, ai, ap, rk = rate(x, z, y, k)
-            lm.rate_scatter_alts(p, rk, ai, ap, rows[a:b], n_ctx, out_prob, out_rank, out_alt_id, out_alt_p)
-        bits[:] = _np(lm.rate_text_bits(out_prob, offsets))
+            if k:
+                p, ai, ap, rk = (lm.rate_window_alts_bulk if bulk else lm.rate_window_alts)(x, z, y, k)
+                lm.rate_scatter_alts(p, rk, ai, ap, rows[a:b], n_ctx, *out)
+            else:
+                p = (lm.rate_window_bulk if bulk else lm.rate_window)(x, z, y, want_probs=True)
+                lm.rate_scatter(p, rows[a:b], n_ctx, out[0])
+        bits[:] = _np(lm.rate_text_bits(out[0], offsets))
         lm.rate_bits_read(reset=True)      # (the per-stream sums are not used here; also raises on a timed-out scan hand-off)
         lm.reset_states(1)
-        return plan, (out_prob, out_rank, out_alt_id, out_alt_p), bits
+        return plan, tuple(out), bits
+
+    @staticmethod
+    def _empty_selection(k):
+        '''a selection without a suspect, as `rate_select` shapes it: (positions, probs, rank, alt_ids [0,k], alt_probs [0,k])'''
+        return [np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.float32), np.zeros(0, dtype=np.int32),
+                np.zeros((0, k), dtype=np.int32), np.zeros((0, k), dtype=np.float32)]
+
+    @staticmethod
+    def _selection_per_text(sel, offsets):
+        '''A corpus-ordered selection (sel[0]: ascending corpus positions; sel[1:]: arrays with one row per position) cut per
+        text: [(positions within the text, copies of its rows of sel[1:] ...)].  Positions ascend: a text's share is one slice.'''
+        pos = sel[0]
+        lo = np.searchsorted(pos, offsets[:-1], side="left")
+        hi = np.searchsorted(pos, offsets[1:], side="left")
+        return [[pos[a:b] - offsets[i]] + [f[a:b].copy() for f in sel[1:]] for i, (a, b) in enumerate(zip(lo, hi))]
 
     def suspects(self, texts, contexts=None, k=3, streams=1024, max_prob=0.01, min_rank=1, precision="bf16"):
         '''Where are the characters the model does not believe, and what would it have written there?  Returns (found, bits),
@@ -1088,21 +1052,7 @@ class Rater(object):
         the split-precision `rate_window_alts`.  Either way the results of ALL texts stay on the device in corpus order
         until the selection: (8k + 8) bytes of device memory per character.  Only stateful raters; the state afterwards is a
         freshly reset single row, the precision that of the path taken.'''
-        assert self.status > 1
-        assert self.incremental is False
-        if precision not in ("split", "bf16"):
-            raise ValueError('precision must be "split" or "bf16" (got %r)' % (precision,))
-        if not self.stateful:
-            raise ValueError('suspects needs a stateful rater: it rates through stateful windows')
-        k, min_rank = int(k), int(min_rank)
-        assert 1 <= k <= ratebatch.ALTS_MAX, "k must be in 1..%d" % ratebatch.ALTS_MAX
-        limit = np.float32(max_prob)
-        if min_rank < 0:
-            raise ValueError("min_rank must be >= 0 (got %d): a character without a prediction is no suspect" % min_rank)
-        if np.isnan(limit):
-            raise ValueError("max_prob must not be NaN")
-        texts = list(texts)
-        n = len(texts)
+        texts, contexts, k, limit, min_rank = self._rating_request("suspects", texts, contexts, precision, k, max_prob, min_rank)
         lm = self.model
         if not hasattr(lm, 'rate_window_alts_bulk'):
             # an engine without the device path (the tests' CPU double): rate_alternatives' fallback and the numpy statement
@@ -1112,18 +1062,12 @@ class Rater(object):
                 found.append(ratebatch.Suspects(*ratebulk.select_host(one.probs, one.rank, one.alt_ids, one.alt_probs,
                                                                       limit, min_rank)))
             return found, bits
-        plan, arrays, bits = self._alternatives_in_corpus_order(texts, contexts, k, streams, precision)
+        plan, arrays, bits = self._rate_in_corpus_order(texts, contexts, k, streams, precision)
         if arrays is None:
-            pos, found = np.zeros(0, dtype=np.int64), (np.zeros(0, dtype=np.float32), np.zeros(0, dtype=np.int32),
-                                                       np.zeros((0, k), dtype=np.int32), np.zeros((0, k), dtype=np.float32))
+            sel = self._empty_selection(k)
         else:
             sel = [_np(t) for t in lm.rate_select(*arrays, max_prob=float(limit), min_rank=min_rank)]
-            pos, found = sel[0], sel[1:]
-        # (positions ascend over the corpus: a text's share is one slice)
-        lo = np.searchsorted(pos, plan.offsets[:-1], side="left")
-        hi = np.searchsorted(pos, plan.offsets[1:], side="left")
-        return [ratebatch.Suspects(pos[a:b] - plan.offsets[i], *(f[a:b].copy() for f in found))
-                for i, (a, b) in enumerate(zip(lo, hi))], bits
+        return [ratebatch.Suspects(*one) for one in self._selection_per_text(sel, plan.offsets)], bits
 
     def corrections(self, texts, contexts=None, k=3, streams=1024, max_prob=0.01, min_rank=1, left=64, ahead=8, deletions=False,
                     min_gain=1.0, precision="bf16", insertions=False):
@@ -1158,56 +1102,37 @@ class Rater(object):
         `rate_window_bulk` ("bf16") or `rate_window` ("split"), the rows' f64 bits are the costs.  Beyond the suspects' records
         (8k + 16 bytes each) 12 * R bytes per suspect leave the device.  ValueError for a stateless rater, left < 1, ahead < 0 or
         left + ahead + insertions > 1024.  State and precision afterwards are as after `suspects`.'''
-        assert self.status > 1
-        assert self.incremental is False
-        if precision not in ("split", "bf16"):
-            raise ValueError('precision must be "split" or "bf16" (got %r)' % (precision,))
-        if not self.stateful:
-            raise ValueError('corrections needs a stateful rater: it rates through stateful windows')
+        texts, contexts, k, limit, min_rank = self._rating_request("corrections", texts, contexts, precision, k, max_prob,
+                                                                    min_rank)
         left, ahead, deletions, insertions = int(left), int(ahead), int(bool(deletions)), int(bool(insertions))
         if left < 1 or ahead < 0 or left + ahead + insertions > 1024:
             raise ValueError("left >= 1, ahead >= 0 and left + ahead%s <= 1024 (got %d, %d)"
                              % (" + 1 (insertions)" if insertions else "", left, ahead))
-        k, min_rank = int(k), int(min_rank)
-        assert 1 <= k <= ratebatch.ALTS_MAX, "k must be in 1..%d" % ratebatch.ALTS_MAX
-        limit = np.float32(max_prob)
-        if min_rank < 0:
-            raise ValueError("min_rank must be >= 0 (got %d): a character without a prediction is no suspect" % min_rank)
-        if np.isnan(limit):
-            raise ValueError("max_prob must not be NaN")
-        texts = list(texts)
         n = len(texts)
         lm = self.model
         R = k + 1 + deletions + k * insertions
         chunk = max(1, int(streams) // R)
         T = max(left + ahead + insertions, ratebulk.MIN_T)
-        empty = (np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.float32), np.zeros(0, dtype=np.int32),
-                 np.zeros((0, k), dtype=np.int32), np.zeros((0, k), dtype=np.float32))
-        if hasattr(lm, 'variant_windows'):
+        device = hasattr(lm, 'variant_windows')
+        # per path: the suspects (sel, in corpus order), then two callables for a chunk [a, b) of them -- `build` makes the
+        # variants' windows (idx, ctx, tgt, valid), `rate` runs them from zero states and returns their costs, one per row
+        if device:
             keep = {}
-            plan, arrays, bits = self._alternatives_in_corpus_order(texts, contexts, k, streams, precision, keep=keep)
+            plan, arrays, bits = self._rate_in_corpus_order(texts, contexts, k, streams, precision, keep=keep)
             offsets = plan.offsets
             sel_d = lm.rate_select(*arrays, max_prob=float(limit), min_rank=min_rank) if arrays is not None else None
             del arrays
             S = int(sel_d[0].numel()) if sel_d is not None else 0
-            sel = [_np(t) for t in sel_d] if S else empty
-            costs, valids = [], []
-            for a in range(0, S, chunk):
-                b = min(S, a + chunk)
-                x, z, y, ok = lm.variant_windows(keep["corpus"], keep["offsets"], keep["text_ctx"] if lm.n_ctx else None,
-                                                 sel_d[0][a:b], sel_d[3][a:b], left, ahead, deletions, T,
-                                                 insertions=bool(insertions))
-                lm.reset_states(int(x.shape[0]))
-                if precision == "bf16":
-                    lm.rate_window_bulk(x, z, y, want_probs=False)
-                else:
-                    lm.rate_window(x, z, y, want_probs=False)
-                costs.append(lm.rate_bits_take_all())
-                valids.append(ok)
-            if S:
-                cost, valid = _np(lm.torch.cat(costs)).reshape(S, R), _np(lm.torch.cat(valids)).reshape(S, R)
-                lm.rate_status_check()
-                lm.reset_states(1)
+            sel = [_np(t) for t in sel_d] if S else self._empty_selection(k)
+            cat = lm.torch.cat
+
+            def build(a, b):
+                return lm.variant_windows(keep["corpus"], keep["offsets"], keep["text_ctx"] if lm.n_ctx else None,
+                                          sel_d[0][a:b], sel_d[3][a:b], left, ahead, deletions, T, insertions=bool(insertions))
+
+            def rate(x, z, y):      # (the rows' f64 bits are the costs)
+                (lm.rate_window_bulk if precision == "bf16" else lm.rate_window)(x, z, y, want_probs=False)
+                return lm.rate_bits_take_all()
         else:
             # an engine without the device path (the tests' CPU double): `suspects`, the numpy statement of the windows, the
             # whole softmax of every window and the logs summed on the host
@@ -1216,26 +1141,34 @@ class Rater(object):
             ids = [windows.encode(windows.normalize(t), self.mapping[0]) for t in texts]
             offsets = np.concatenate([[0], np.cumsum([len(a) for a in ids])]).astype(np.int64)
             sel = [np.concatenate([getattr(f, name) for f in found]) if n else e
-                   for name, e in zip(("positions", "probs", "rank", "alt_ids", "alt_probs"), empty)]
+                   for name, e in zip(("positions", "probs", "rank", "alt_ids", "alt_probs"), self._empty_selection(k))]
             sel[0] = sel[0] + np.repeat(offsets[:-1], [len(f) for f in found])
             S = len(sel[0])
+            cat = np.concatenate
             if S:
                 corpus = np.concatenate(ids).astype(np.int32)
-                text_ctx = np.asarray([windows.clamp_context(c) for c in self._contexts_per_text(contexts, n)], dtype=np.int32)
-                text_ctx = text_ctx.reshape(n, -1)
-                cost, valid = np.zeros(S * R, dtype=np.float64), np.zeros(S * R, dtype=np.int32)
-                for a in range(0, S, chunk):
-                    b = min(S, a + chunk)
-                    x, z, y, ok = ratebulk.variant_windows_host(corpus, offsets, text_ctx, sel[0][a:b], sel[3][a:b], left, ahead,
-                                                                deletions, T, insertions)
-                    lm.reset_states(len(x))
-                    full = _np(lm.forward_window(x, z, want_probs=True)).astype(np.float64)
-                    p = np.take_along_axis(full, np.maximum(y, 0)[:, :, None], axis=2)[:, :, 0]
-                    cost[a * R:b * R] = -np.where(y >= 0, np.log2(np.maximum(p, 1e-99)), 0.0).sum(axis=1)
-                    valid[a * R:b * R] = ok
-                cost, valid = cost.reshape(S, R), valid.reshape(S, R)
-                lm.reset_states(1)
-        if not S:
+                text_ctx = np.asarray([windows.clamp_context(c) for c in contexts], dtype=np.int32).reshape(n, -1)
+
+            def build(a, b):
+                return ratebulk.variant_windows_host(corpus, offsets, text_ctx, sel[0][a:b], sel[3][a:b], left, ahead,
+                                                     deletions, T, insertions)
+
+            def rate(x, z, y):
+                full = _np(lm.forward_window(x, z, want_probs=True)).astype(np.float64)
+                p = np.take_along_axis(full, np.maximum(y, 0)[:, :, None], axis=2)[:, :, 0]
+                return -np.where(y >= 0, np.log2(np.maximum(p, 1e-99)), 0.0).sum(axis=1)
+        costs, valids = [], []
+        for a in range(0, S, chunk):
+            x, z, y, ok = build(a, min(S, a + chunk))
+            lm.reset_states(int(x.shape[0]))
+            costs.append(rate(x, z, y))
+            valids.append(ok)
+        if S:
+            cost, valid = _np(cat(costs)).reshape(S, R), _np(cat(valids)).reshape(S, R)
+            if device:
+                lm.rate_status_check()
+            lm.reset_states(1)
+        else:
             cost, valid = np.zeros((0, R), dtype=np.float64), np.zeros((0, R), dtype=np.int32)
         cost, best, gain = ratebulk.variant_pick_host(cost, valid)
         # best v -> edit: 1 .. k substitute alt_ids[v-1]; k + 1 with deletions: delete; from k + 1 + deletions on: insert
@@ -1256,14 +1189,8 @@ class Rater(object):
         best_id[drop] = Cor.NO_PROPOSAL
         best_op[drop] = Cor.OP_NONE
         gain[drop] = 0.0
-        # (positions ascend over the corpus: a text's share is one slice)
-        pos = sel[0]
-        lo = np.searchsorted(pos, offsets[:-1], side="left")
-        hi = np.searchsorted(pos, offsets[1:], side="left")
-        return [ratebatch.Corrections(pos[a:b] - offsets[i], *([f[a:b].copy() for f in sel[1:]]
-                                                               + [cost[a:b].copy(), best_id[a:b].copy(), gain[a:b].copy(),
-                                                                  best_op[a:b].copy()]))
-                for i, (a, b) in enumerate(zip(lo, hi))], bits
+        return [ratebatch.Corrections(*one)
+                for one in self._selection_per_text(list(sel) + [cost, best_id, gain, best_op], offsets)], bits
 
     def _contexts_per_text(self, contexts, n):
         '''None, one context list for all texts, or one per text -> one list per text (as `rate_batch` reads them)'''

@@ -326,7 +326,16 @@ def test_rate_window_alts_against_the_oracle(depth, width, voc, B, T, n_ctx, tol
 def test_rate_window_alts_groups_of_streams():
     """more streams than one launch sequence of the split-precision scan takes (HipLM._rating_groups): the batch-major
     outputs are sliced by stream"""
-    depth, width, voc, n_ctx, B, T, K = 2, 512, 256, 1, 300, 4, 3
+    groups_of_streams(3)
+
+
+def test_rate_window_alts_groups_of_streams_k8():
+    """... with the widest rows the outputs have (K = 8): a group's slice of alt_id / alt_p is 8 * T words per stream"""
+    groups_of_streams(8)
+
+
+def groups_of_streams(K):
+    depth, width, voc, n_ctx, B, T = 2, 512, 256, 1, 300, 4
     cfg, w, lm = make_model(depth, width, voc, n_ctx)
     lm.set_weights(w, 3)
     assert len(lm._rating_groups(B)) > 1

@@ -160,7 +160,7 @@ def main():
                     worst = max(worst, float(np.abs(ca[both] - cb[both]).max()))
                     compared += int(both.sum())
             keep = {}
-            _, arrays, _ = rater._alternatives_in_corpus_order(docs, context, k, streams, "bf16", keep=keep)
+            _, arrays, _ = rater._rate_in_corpus_order(docs, [context] * len(docs), k, streams, "bf16", keep=keep)
             sel = lm.rate_select(*arrays, max_prob=max_prob, min_rank=args.min_rank)
             held.update(keep, sel=(sel[0], sel[3]), host=host_inputs(found), found=found)
             del arrays, sel

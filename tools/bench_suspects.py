@@ -95,7 +95,7 @@ def main():
         found, _ = suspects()
         count = sum(len(f) for f in found)
         count_parent = sum(len(f[0]) for f in parent()[0])
-        plan, arrays, _ = rater._alternatives_in_corpus_order(docs, context, k, streams, "bf16")
+        plan, arrays, _ = rater._rate_in_corpus_order(docs, [context] * len(docs), k, streams, "bf16")
         held.update(plan=plan, arrays=arrays)
         legs = {"suspects": suspects, "parent": parent, "selection": selection}
         inner = {}
