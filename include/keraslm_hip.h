@@ -628,6 +628,40 @@ int kl_test_derived_view(const kl_handle* h, kl_derived_view* out);
  * KL_ERR_STATE before kl_prepare, KL_ERR_ARG for an empty mask or other bits, KL_ERR_SHAPE for bit 2 where comb is not
  * carved or the interleaved tables it sums are not current; all before anything is launched. */
 int kl_test_prepare_lazy(kl_handle* h, int mask, void* stream);
+/* Test hook, host only: the route a step of n hypotheses takes on this handle -- the plan kl_step_batch (host = 0; has_ws:
+ * a workspace of at least kl_step_workspace_bytes(h, n) is passed) or kl_step_batch_host (host = 1; has_ws is ignored, its
+ * workspace always holds the step's) itself asks before it launches, not a copy of its rules.
+ *   layers     KL_STEP_TILES: a launch per layer on tile_rows x 128 tiles, XCD partition px x py (0, 0: none);
+ *              KL_STEP_CELLS: a launch per layer of the 16-unit cell kernel with nmt[l] row tiles per workgroup, gen[l] = the
+ *              instantiation for widths 64 and 128; KL_STEP_GEMM_FUSED / KL_STEP_GEMM_PLAIN: gather + GEMM with the cell
+ *              in its epilogue / + a gates kernel; KL_STEP_THIN: a launch per layer of the thin forward-step kernel
+ *   out        KL_STEP_OUT_FUSED: logits + softmax in one launch; KL_STEP_OUT_THIN: thin GEMM + softmax (host = 1 with the
+ *              indices in the kernel arguments: the softmax is the delivering launch's); KL_STEP_OUT_BIG: gather + GEMM + softmax
+ *   idx        KL_STEP_IDX_DEVICE: the caller's device arrays; KL_STEP_IDX_KERNARG: in the kernel arguments, provided every
+ *              index value of the call is in range (else the packed copy); KL_STEP_IDX_PACKED: one copy of the packed
+ *              indices, then the device-pointer step
+ *   gathered   layer 0's gate inputs are gathered into the workspace first (n_ctx != 1)
+ *   lo         the lo planes of states and weights are used (split precision; 0 before kl_prepare)
+ * Fields of other routes are 0.  Nothing is launched or allocated.  KL_ERR_STATE before kl_bind, KL_ERR_ARG for n < 1,
+ * KL_ERR_WORKSPACE where the step would return it (n_ctx != 1 without a workspace). */
+#define KL_STEP_TILES 1
+#define KL_STEP_CELLS 2
+#define KL_STEP_GEMM_FUSED 3
+#define KL_STEP_GEMM_PLAIN 4
+#define KL_STEP_THIN 5
+#define KL_STEP_OUT_FUSED 1
+#define KL_STEP_OUT_THIN 2
+#define KL_STEP_OUT_BIG 3
+#define KL_STEP_IDX_DEVICE 1
+#define KL_STEP_IDX_KERNARG 2
+#define KL_STEP_IDX_PACKED 3
+typedef struct kl_step_route {
+  int32_t layers, out, idx, lo, gathered, depth;
+  int32_t tile_rows, px, py;
+  int32_t nmt[16], gen[16];
+  int32_t reserved[7];
+} kl_step_route;
+int kl_test_step_route(const kl_handle* h, int n, int has_ws, int host, kl_step_route* out);
 
 #ifdef __cplusplus
 }

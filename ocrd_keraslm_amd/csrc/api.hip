@@ -1312,7 +1312,7 @@ struct TrainCall {       // a kl_train_window call as the stages of its backward
   bool top_masked; float inv_count;
   bool wide_fits, seq128, sequential;      // which backward scans the shape and the switches allow (train_window_body)
 };
-// a backward-scan path's "not mine" (as STEP_PASS: no public return code -- those are 0 .. 5, keraslm_hip.h)
+// a backward-scan path's "not mine" (no public return code -- those are 0 .. 5, keraslm_hip.h)
 constexpr int TRAIN_PASS = -1;
 static_assert(TRAIN_PASS < KL_OK, "TRAIN_PASS must not be a public return code");
 
@@ -1824,55 +1824,84 @@ struct StepCall {        // a kl_step_batch call as its kernel paths see it
   const float* prow;     // layer 0's gathered gate inputs (n_ctx != 1); null: table rows by idx / ctx
   hipStream_t s;
 };
-// a path's "not mine".  Not KL_ERR_SHAPE itself: a kernel's KL_ERR_SHAPE at layer 0 decides for all layers (the shapes are the
-// same) and becomes STEP_PASS, at a later layer it is an error and returned.  The public codes are 0 .. 5 (keraslm_hip.h).
-constexpr int STEP_PASS = -1;
-static_assert(STEP_PASS < KL_OK, "STEP_PASS must not be a public return code");
 
-// a launch per layer of inc_tile_kernel / inc_cell_kernel, then the output layer: logits + softmax in one launch where that applies
-static int step_layers(const StepCall& c, bool tiles) {
+// ---- the plan of a step: the kernels a call of n rows goes to.  kl_step_batch and kl_step_batch_host ask it before they
+// launch anything, kl_test_step_route reports it; what a launcher does with a shape is its own plan function
+// (kl_plan_inc_tile, kl_plan_inc_cell, kl_plan_out_softmax), which the launcher itself asks again.
+struct StepPlan {
+  int layers, out;              // KL_STEP_*, KL_STEP_OUT_* (keraslm_hip.h)
+  KlIncTilePlan tile;           // KL_STEP_TILES
+  KlIncCellPlan cell[16];       // KL_STEP_CELLS, per layer (config_ok: depth <= 16)
+};
+
+// inc_cell_kernel for every layer of the step?  (All layers are asked before the first is launched: where the layers above
+// the first do not fit in LDS -- K = 2W there --, the step goes to another path whole.)
+static bool plan_cells(const kl_handle* h, int n, bool host_idx, KlIncCellPlan* cell) {
+  for (int l = 0; l < h->cfg.depth; ++l)
+    if (!h->d.UF[l] || kl_plan_inc_cell(n, h->cfg.width, l > 0, host_idx, &cell[l]) != 0) return false;
+  return true;
+}
+
+// The first path that takes the shape, in this order:
+// tiles -- 256 hypotheses or more, widths of 256, 512, 768, ...: one launch per layer, tiles of 64 (128) hypotheses x 32 units
+//   with the state rows read through the pool slots and the weights from the hi / lo arrays as they are (step_tile.hip)
+//   (width 1024 already from 129 hypotheses: inc_cell_kernel cannot hold two row tiles of K = 2048 in LDS there, and with one
+//    its W / 16 x n / 16 workgroups read every weight 16 times at 250 hypotheses -- 90 us per step against 51 on 64-row tiles);
+// cells -- 16 hypotheses and more (the reference's callers feed at most 128 / 256 rows; also whatever the tile kernel does not
+//   take: widths 64 and 128): coalesced state rows through LDS, 16-unit workgroups (step_small.hip);
+// gemm -- 256 hypotheses or more and a workspace: gather + split -> one bf16 GEMM over the 3x contraction -> gates; fused
+//   form: the cell is the GEMM's epilogue;
+// thin -- everything else (fewer than 16 hypotheses, widths the kernels above do not take): a launch per layer of the thin
+//   forward-step kernel.
+// Behind tiles and cells the output layer is logits + softmax in one launch where that applies, else thin GEMM + softmax;
+// behind the GEMMs the thin GEMM while V x W is small (n/32 x V/16 workgroups), else big tiles for the output projection too.
+static StepPlan step_plan(const kl_handle* h, int n, bool has_ws) {
+  const int W = h->cfg.width, L = h->cfg.depth, V = h->cfg.voc_size;
+  const Derived& d = h->d;
+  StepPlan p;
+  memset(&p, 0, sizeof(p));
+  if ((n >= KL_BIG_STEP_N || (W >= 1024 && n > 128)) && h->inc_tile && V < 1024 && d.EF && d.UF[0] &&
+      kl_plan_inc_tile(n, W, h->tile_rows, &p.tile) == 0)
+    p.layers = KL_STEP_TILES;
+  else if (h->inc_small && n >= h->inc_small_min && (n < KL_BIG_STEP_N || V < 1024) && d.EF && plan_cells(h, n, false, p.cell))
+    p.layers = KL_STEP_CELLS;
+  if (p.layers) {
+    const bool fused = h->out_fused && n >= h->out_fused_min && kl_plan_out_softmax(n, W, V, h->precision == 3, nullptr) == 0;
+    p.out = fused ? KL_STEP_OUT_FUSED : KL_STEP_OUT_THIN;
+    return p;
+  }
+  if (n >= KL_BIG_STEP_N && has_ws) {
+    const int nb = h->precision == 3 ? 3 : 1;
+    bool fusable = h->fused_step && (W & 31) == 0 && L <= KL_SCAN_MAXL && V < 1024;
+    for (int l = 0; l < L && fusable; ++l) fusable = d.WTperm[l] != nullptr && ((nb * (l == 0 ? W : 2 * W)) % 64) == 0;
+    p.layers = fusable ? KL_STEP_GEMM_FUSED : KL_STEP_GEMM_PLAIN;
+    p.out = V < 1024 ? KL_STEP_OUT_THIN : KL_STEP_OUT_BIG;
+    return p;
+  }
+  p.layers = KL_STEP_THIN;
+  p.out = KL_STEP_OUT_THIN;
+  return p;
+}
+
+// tiles / cells: a launch per layer of inc_tile_kernel / inc_cell_kernel, then the output layer
+// (the plan has asked the launchers' own rules: a KL_ERR_SHAPE from one of them is an error here)
+static int step_layers(const StepCall& c, const StepPlan& p) {
   kl_handle* h = c.h;
   const int W = h->cfg.width, L = h->cfg.depth, V = h->cfg.voc_size;
   if (!h->inc_ready) KL_TRY(prepare_incremental(h, c.s));
   for (int l = 0; l < L; ++l) {
     const KlIncCellArgs a = inc_cell_args(h, l, c.n, c.pool, c.slot_in, c.slot_out, c.prow, c.idx, c.ctx);
-    const int e = tiles ? kl_launch_inc_tile(a, h->tile_var, c.s, h->tile_rows) : kl_launch_inc_cell(a, c.s);
-    if (e == KL_ERR_SHAPE && l == 0) return STEP_PASS;
-    if (e != 0) return e;
+    KL_TRY(p.layers == KL_STEP_TILES ? kl_launch_inc_tile(a, h->tile_var, c.s, h->tile_rows) : kl_launch_inc_cell(a, c.s));
   }
-  if (h->out_fused && c.n >= h->out_fused_min && h->d.EF) {
-    const int e = kl_launch_out_softmax(c.pool, (long)2 * L * W, c.slot_out, 2 * (L - 1) * W, h->d.EF, h->precision, c.n, W, V,
-                                        c.probs, V, c.s);
-    if (e != KL_ERR_SHAPE) return e;
-  }
+  if (p.out == KL_STEP_OUT_FUSED)
+    return kl_launch_out_softmax(c.pool, (long)2 * L * W, c.slot_out, 2 * (L - 1) * W, h->d.EF, h->precision, c.n, W, V, c.probs, V, c.s);
   return output_thin(h, c.n, c.pool, c.slot_out, c.probs, true, c.s);
 }
 
-// 256 hypotheses or more, widths of 256, 384, 512, ...: one launch per layer, tiles of 64 hypotheses x 32 units with the
-// state rows read through the pool slots and the weights from the hi / lo arrays as they are (step_tile.hip)
-// (width 1024 already from 129 hypotheses: inc_cell_kernel cannot hold two row tiles of K = 2048 in LDS there, and with one
-//  its W / 16 x n / 16 workgroups read every weight 16 times at 250 hypotheses -- 90 us per step against 51 on 64-row tiles)
-static int step_tiles(const StepCall& c) {
-  const kl_handle* h = c.h;
-  const int n = c.n, W = h->cfg.width, V = h->cfg.voc_size;
-  if (!((n >= KL_BIG_STEP_N || (W >= 1024 && n > 128)) && h->inc_tile && V < 1024 && h->d.EF)) return STEP_PASS;
-  return step_layers(c, true);
-}
-
-// 16 hypotheses and more (the reference's callers feed at most 128 / 256 rows; also whatever the tile kernel does not take:
-// widths 64 and 128): coalesced state rows through LDS, 16-unit workgroups (step_small.hip)
-static int step_cells(const StepCall& c) {
-  const kl_handle* h = c.h;
-  const int n = c.n, V = h->cfg.voc_size;
-  if (!(h->inc_small && n >= h->inc_small_min && (n < KL_BIG_STEP_N || V < 1024)) || !h->d.EF) return STEP_PASS;
-  return step_layers(c, false);
-}
-
-// 256 hypotheses or more and a workspace: gather + split -> one bf16 GEMM over the 3x contraction -> gates
-static int step_gemm(const StepCall& c, void* ws, size_t ws_bytes) {
+// gemm: gather + split -> one bf16 GEMM over the 3x contraction -> gates
+static int step_gemm(const StepCall& c, const StepPlan& p, void* ws) {
   kl_handle* h = c.h;
   const int n = c.n, W = h->cfg.width, L = h->cfg.depth, V = h->cfg.voc_size;
-  if (!(n >= KL_BIG_STEP_N && ws && ws_bytes >= kl_step_workspace_bytes(h, n))) return STEP_PASS;
   hipStream_t s = c.s;
   if (!h->big_ready) KL_TRY(prepare_big_step(h, s));
   Derived& d = h->d;
@@ -1882,9 +1911,7 @@ static int step_gemm(const StepCall& c, void* ws, size_t ws_bytes) {
   const int nb = h->precision == 3 ? 3 : 1;
   // fused form: one gather of all layers' recurrent halves, then per layer ONE GEMM whose epilogue is the cell
   // (gates, c', h', and h' as the next layer's input rows)
-  bool fusable = h->fused_step && (W & 31) == 0 && L <= KL_SCAN_MAXL && V < 1024;
-  for (int l = 0; l < L && fusable; ++l) fusable = d.WTperm[l] != nullptr && ((nb * (l == 0 ? W : 2 * W)) % 64) == 0;
-  if (fusable) {
+  if (p.layers == KL_STEP_GEMM_FUSED) {
     KlGatherRec g;
     memset(&g, 0, sizeof(g));
     g.pool = pool; g.slot_ld = slot_ld; g.slot_in = c.slot_in; g.n = n; g.W = W; g.nb = nb;
@@ -1916,15 +1943,14 @@ static int step_gemm(const StepCall& c, void* ws, size_t ws_bytes) {
     KL_TRY(kl_launch_gates_rows(w.z, 4 * W, n, W, src.T1, src.i1, src.T2, src.i2, src.bias, pool + (size_t)(2 * l + 1) * W, slot_ld,
                                 c.slot_in, pool + (size_t)(2 * l + 1) * W, pool + (size_t)2 * l * W, slot_ld, c.slot_out, s));
   }
-  if (V < 1024) return output_thin(h, n, pool, c.slot_out, c.probs, true, s);      // V x W is small: n/32 x V/16 workgroups
+  if (p.out == KL_STEP_OUT_THIN) return output_thin(h, n, pool, c.slot_out, c.probs, true, s);      // V x W is small: n/32 x V/16 workgroups
   // wide vocabulary: big tiles pay off for the output projection too
   KL_TRY(kl_launch_split_gather(pool + (size_t)2 * (L - 1) * W, slot_ld, c.slot_out, W, nullptr, 0, nullptr, 0, n, nb, w.A3, 3L * W, s));
   KL_TRY(kl_launch_gemm_tn(w.A3, d.Ecat, c.probs, nullptr, n, V, nb * W, 3L * W, 3L * W, V, 0, 1, 1.f, s));
   return kl_launch_softmax_ce(c.probs, V, n, V, nullptr, n, 1, 1.f, nullptr, 0, nullptr, nullptr, 0, s);
 }
 
-// everything else (fewer than 16 hypotheses, widths the kernels above do not take): a launch per layer of the thin
-// forward-step kernel
+// thin: a launch per layer of the thin forward-step kernel
 static int step_thin(const StepCall& c) {
   kl_handle* h = c.h;
   const int n = c.n, W = h->cfg.width, L = h->cfg.depth, split = h->precision;
@@ -1965,6 +1991,12 @@ static bool host_idx_in_kernarg(const kl_handle* h, int n) {
          ((W & 255) == 0 || W == 64 || W == 128) && !(W >= 1024 && n > 128);
 }
 
+// kl_step_batch_host: the indices in the kernel arguments of the 16-unit cell kernels?  (Up to 256 hypotheses, any number
+// from 1 on; else the packed copy and the device-pointer step.)
+static bool step_host_kernarg(const kl_handle* h, int n, KlIncCellPlan* cell) {
+  return n <= KL_HOST_STEP_MAX && host_idx_in_kernarg(h, n) && plan_cells(h, n, true, cell);
+}
+
 // a host entry point's ticket counter: zeroed when its workspace is not the one remembered (afterwards every delivering
 // launch leaves it zero)
 static int arm_ticket_counter(void*& armed, unsigned* counter, hipStream_t s) {
@@ -1994,10 +2026,14 @@ int kl_step_batch(kl_handle* h, int n, const int32_t* idx, const int32_t* ctx, f
     KL_TRY(kl_launch_p1_gather(h->d.EK, ctxk, h->cfg.n_ctx, h->params + h->off_b[0], idx, ctx, n, 1, 4 * h->cfg.width, w.prow, c.s));
     c.prow = w.prow;
   }
-  int e = step_tiles(c);      // the first path that takes the shape
-  if (e == STEP_PASS) e = step_cells(c);
-  if (e == STEP_PASS) e = step_gemm(c, ws, ws_bytes);
-  return e == STEP_PASS ? step_thin(c) : e;
+  const StepPlan p = step_plan(h, n, ws && ws_bytes >= kl_step_workspace_bytes(h, n));
+  switch (p.layers) {
+    case KL_STEP_TILES:
+    case KL_STEP_CELLS: return step_layers(c, p);
+    case KL_STEP_GEMM_FUSED:
+    case KL_STEP_GEMM_PLAIN: return step_gemm(c, p, ws);
+    default: return step_thin(c);
+  }
 }
 
 // ---- the incremental step as a beam search issues it: one step per character, the GPU idle in between ----------------
@@ -2047,7 +2083,8 @@ int kl_step_batch_host(kl_handle* h, int n, const int32_t* idx, const int32_t* c
   f.pool = pool; f.slot_ld = (long)2 * L * W;
   f.probs_host = probs_host; f.heads_host = heads_host; f.done_host = done_host; f.ticket = ticket; f.counter = counter;
   // ---- up to 256 hypotheses on the 16-unit cell kernels: every index travels in the kernel arguments
-  bool in_range = n <= KL_HOST_STEP_MAX && host_idx_in_kernarg(h, n);
+  KlIncCellPlan cells[16];
+  bool in_range = step_host_kernarg(h, n, cells);
   for (int i = 0; i < n && in_range; ++i)
     in_range = idx[i] >= 0 && idx[i] < V && ctx[i] >= 0 && ctx[i] < c.ctx_vocab && (!target || (target[i] >= 0 && target[i] < V));
   if (in_range) {
@@ -2059,18 +2096,12 @@ int kl_step_batch_host(kl_handle* h, int n, const int32_t* idx, const int32_t* c
       if (target) tx.t[i] = (unsigned short)target[i];
     }
     if (!h->inc_ready) KL_TRY(prepare_incremental(h, s));
-    int e = 0;
-    for (int l = 0; l < L && e == 0; ++l) {      // (layer 0 leaves slot_out in dev_idx for the launches behind it)
-      e = kl_launch_inc_cell(inc_cell_args(h, l, n, pool, nullptr, nullptr, nullptr, dev_idx, dev_idx), s, &hx,
-                             l == 0 ? dev_idx : nullptr);
-      if (e == KL_ERR_SHAPE && l > 0) return e;
-    }
-    if (e == 0) {
-      KL_TRY(output_thin(h, n, pool, dev_idx, logits, false, s));
-      f.softmax = 1; f.slot_out = dev_idx;
-      return kl_launch_step_finish(f, target ? &tx : nullptr, s);
-    }
-    if (e != KL_ERR_SHAPE) return e;
+    for (int l = 0; l < L; ++l)      // (layer 0 leaves slot_out in dev_idx for the launches behind it)
+      KL_TRY(kl_launch_inc_cell(inc_cell_args(h, l, n, pool, nullptr, nullptr, nullptr, dev_idx, dev_idx), s, &hx,
+                                l == 0 ? dev_idx : nullptr));
+    KL_TRY(output_thin(h, n, pool, dev_idx, logits, false, s));
+    f.softmax = 1; f.slot_out = dev_idx;
+    return kl_launch_step_finish(f, target ? &tx : nullptr, s);
   }
   // ---- everything else: ONE copy of the packed indices to the device, the device-pointer step, delivery by the finish launch
   {
@@ -2721,6 +2752,31 @@ extern "C" int kl_test_derived_view(const kl_handle* h, kl_derived_view* out) {
   out->has_comb = d.comb ? 1 : 0;
   out->off_comb = off(d.comb);
   out->bytes = (uint64_t)carve_derived(h, nullptr, nullptr);
+  return 0;
+}
+
+extern "C" int kl_test_step_route(const kl_handle* h, int n, int has_ws, int host, kl_step_route* out) {
+  if (!h || !out || n < 1) return KL_ERR_ARG;
+  if (!h->params) return KL_ERR_STATE;
+  const int L = h->cfg.depth;
+  memset(out, 0, sizeof(*out));
+  StepPlan p;
+  memset(&p, 0, sizeof(p));
+  if (host && step_host_kernarg(h, n, p.cell)) {
+    p.layers = KL_STEP_CELLS;
+    p.out = KL_STEP_OUT_THIN;
+    out->idx = KL_STEP_IDX_KERNARG;
+  } else {
+    if (h->cfg.n_ctx != 1 && !host && !has_ws) return KL_ERR_WORKSPACE;
+    p = step_plan(h, n, host || has_ws);
+    out->idx = host ? KL_STEP_IDX_PACKED : KL_STEP_IDX_DEVICE;
+    out->gathered = h->cfg.n_ctx != 1;
+  }
+  out->layers = p.layers; out->out = p.out; out->depth = L;
+  out->lo = h->precision == KL_PREC_SPLIT;
+  if (p.layers == KL_STEP_TILES) { out->tile_rows = p.tile.rows; out->px = p.tile.px; out->py = p.tile.py; }
+  if (p.layers == KL_STEP_CELLS)
+    for (int l = 0; l < L; ++l) { out->nmt[l] = p.cell[l].nmt; out->gen[l] = p.cell[l].gen; }
   return 0;
 }
 

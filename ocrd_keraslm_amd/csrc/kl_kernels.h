@@ -400,6 +400,10 @@ int kl_launch_step_finish(const KlStepFinish& a, const KlHostTargets* tx, hipStr
 // hx != null: the indices come from *hx (slot_in / slot_out / the VALUES behind i1 / i2 of `a` are ignored; i1 / i2 non-null
 // still mean "table rows by index"); slots_copy (device, n ints) receives slot_out for the launches that follow
 int kl_launch_inc_cell(const KlIncCellArgs& a, hipStream_t stream, const KlHostIdx* hx = nullptr, int* slots_copy = nullptr);      // KL_ERR_SHAPE: not applicable
+// what kl_launch_inc_cell does with a shape (asked by the launch itself and by the step's plan, api.hip): row tiles per
+// workgroup (2 from 129 rows on, where both fit in LDS), the instantiation for widths 64 / 128, dynamic LDS bytes
+struct KlIncCellPlan { int nmt, gen; size_t lds; };
+int kl_plan_inc_cell(int n, int W, bool has_x, bool host_idx, KlIncCellPlan* out);      // 0, or KL_ERR_SHAPE: not applicable
 
 // ---- walk.hip -----------------------------------------------------------
 // the deferred output layer of kl_walk_batch_host: per (row, step) pair p the softmax probability of targets[p] from the top
@@ -450,9 +454,14 @@ int kl_launch_sample_pick(KlSamplePick a, void* ws, hipStream_t stream);      //
 
 // ---- step_tile.hip: the same for n >= KL_BIG_STEP_N, TR x 128 tiles with the operands read once (variant: timing builds, 0)
 int kl_launch_inc_tile(const KlIncCellArgs& a, int variant, hipStream_t stream, int rows = -1);      // KL_ERR_SHAPE: not applicable; rows: 64 / 128 per tile, -1 = by size
+// ... and what it does with a shape: rows per tile, the tile grid (unit blocks x row tiles) and its partition over the XCDs
+// (px * py == 8, or both 0: tiles in launch order)
+struct KlIncTilePlan { int rows, nx, ny, px, py; };
+int kl_plan_inc_tile(int n, int W, int rows, KlIncTilePlan* out);      // 0, or KL_ERR_SHAPE: not applicable
 // output layer in one launch: probs[n][V] = softmax(h_top . E^T), h_top rows through slot_out (V <= 256, W % 128 == 0)
 int kl_launch_out_softmax(const float* pool, long slot_ld, const int* slot_out, int h_off, const bf16_t* EF, int split,
                           int n, int W, int V, float* probs, long ldp, hipStream_t stream);      // KL_ERR_SHAPE: not applicable
+int kl_plan_out_softmax(int n, int W, int V, bool lo, size_t* lds);      // 0 (*lds: dynamic LDS bytes), or KL_ERR_SHAPE: not applicable
 // [rows][K] bf16 hi (+ lo) -> fragment-major [rows / 16][K / 32][planes][64][8] (the operands of the two launchers above)
 int kl_launch_frag_major(const bf16_t* hi, const bf16_t* lo, int rows, int K, long ld, bf16_t* out, hipStream_t stream);
 

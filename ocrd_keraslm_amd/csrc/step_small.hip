@@ -452,22 +452,35 @@ extern "C" int kl_test_read_inc_stamps(unsigned long long* out) {
 }
 #endif
 
-// one LSTM cell step of layer `l` for n hypotheses with pool slots; KL_ERR_SHAPE = not applicable (the caller takes the
-// launch-per-layer kernels of lstm_step.hip).
-int kl_launch_inc_cell(const KlIncCellArgs& p, hipStream_t stream, const KlHostIdx* hx, int* slots_copy) {
-  const int W = p.W;
-  if (p.n < 1 || ((W & 255) && W != 64 && W != 128) || !p.pool || !p.UF) return KL_ERR_SHAPE;
-  if (!hx && (!p.slot_in || !p.slot_out)) return KL_ERR_SHAPE;
-  if (hx && p.n > KL_HOST_STEP_MAX) return KL_ERR_SHAPE;
-  const bool lo = p.split == 3;
-  if (p.x_off >= 0 && !p.KF) return KL_ERR_ARG;
-  const int K = p.x_off >= 0 ? 2 * W : W;
-  const bool gen = (W & 255) != 0;                 // widths 64 and 128: K = 64, 128 or 256, a staging piece spans rows or x and h
-  int nmt = p.n > 128 ? 2 : 1;
+// the launcher's shape rules.  Two row tiles per workgroup from 129 rows on -- unless their planes (16 NMT rows x K x hi + lo)
+// do not fit in LDS: then one (layer 1 of width 768, the layers above the first of width 1024).
+int kl_plan_inc_cell(int n, int W, bool has_x, bool host_idx, KlIncCellPlan* out) {
+  if (n < 1 || ((W & 255) && W != 64 && W != 128)) return KL_ERR_SHAPE;
+  if (host_idx && n > KL_HOST_STEP_MAX) return KL_ERR_SHAPE;
+  const int K = has_x ? 2 * W : W;
+  int nmt = n > 128 ? 2 : 1;
   if ((size_t)16 * nmt * K * 4 > LDS_LIMIT) nmt = 1;
   size_t lds = (size_t)16 * nmt * K * 4;
   if (lds < (size_t)8 * nmt * 4 * 16 * 17 * 4) lds = (size_t)8 * nmt * 4 * 16 * 17 * 4;      // (the partial tiles re-use the planes' room)
   if (lds > LDS_LIMIT) return KL_ERR_SHAPE;
+  out->nmt = nmt;
+  out->gen = (W & 255) != 0;                       // widths 64 and 128: K = 64, 128 or 256, a staging piece spans rows or x and h
+  out->lds = lds;
+  return 0;
+}
+
+// one LSTM cell step of layer `l` for n hypotheses with pool slots; KL_ERR_SHAPE = not applicable (the caller takes the
+// launch-per-layer kernels of lstm_step.hip).
+int kl_launch_inc_cell(const KlIncCellArgs& p, hipStream_t stream, const KlHostIdx* hx, int* slots_copy) {
+  const int W = p.W;
+  KlIncCellPlan plan;
+  if (kl_plan_inc_cell(p.n, W, p.x_off >= 0, hx != nullptr, &plan) != 0 || !p.pool || !p.UF) return KL_ERR_SHAPE;
+  if (!hx && (!p.slot_in || !p.slot_out)) return KL_ERR_SHAPE;
+  if (p.x_off >= 0 && !p.KF) return KL_ERR_ARG;
+  const bool lo = p.split == 3;
+  const bool gen = plan.gen != 0;
+  const int nmt = plan.nmt;
+  const size_t lds = plan.lds;
   IncCell a;
   a.n = p.n; a.W = W; a.pool = p.pool; a.slot_ld = p.slot_ld; a.slot_in = p.slot_in; a.slot_out = p.slot_out;
   a.h_off = p.h_off; a.c_off = p.c_off; a.x_off = p.x_off;

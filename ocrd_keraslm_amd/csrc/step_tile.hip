@@ -575,7 +575,7 @@ int kl_launch_frag_major(const bf16_t* hi, const bf16_t* lo, int rows, int K, lo
 }
 
 template <int TR>
-static int launch_inc_tile(const KlIncCellArgs& p, int variant, hipStream_t stream) {
+static int launch_inc_tile(const KlIncCellArgs& p, const KlIncTilePlan& plan, int variant, hipStream_t stream) {
   const int W = p.W;
   const bool lo = p.split == 3;
   IncTile a;
@@ -584,19 +584,7 @@ static int launch_inc_tile(const KlIncCellArgs& p, int variant, hipStream_t stre
   a.h_off = p.h_off; a.c_off = p.c_off; a.x_off = p.x_off;
   a.UF = p.UF; a.KF = p.KF;
   a.T1 = p.T1; a.i1 = p.i1; a.T2 = p.T2; a.i2 = p.i2; a.bias = p.bias;
-  a.nx = W / 32;
-  a.ny = (p.n + TR - 1) / TR;
-  // XCD partition of the tile grid: the split (px unit-block groups x py row-tile groups) with the fewest operand bytes per
-  // XCD (a unit block's weights are 128 rows of K, a row tile's states TR rows)
-  if (((a.nx * a.ny) & 7) == 0) {
-    long best = -1;
-    for (int px = 1; px <= 8; px *= 2) {
-      const int py = 8 / px;
-      if (a.nx % px || a.ny % py) continue;
-      const long cost = (long)(a.nx / px) * TC + (long)(a.ny / py) * TR;
-      if (best < 0 || cost < best) { best = cost; a.px = px; a.py = py; }
-    }
-  }
+  a.nx = plan.nx; a.ny = plan.ny; a.px = plan.px; a.py = plan.py;
   size_t lds = (size_t)2 * (lo ? 2 : 1) * TR * 128;      // two stages of the state rows' planes ...
   if (lds < (size_t)TR * (TC + 4) * 4) lds = (size_t)TR * (TC + 4) * 4;      // ... or the epilogue's f32 tile
 #define KL_IT_CASE(LO_, VAR_)                                                                                               \
@@ -613,32 +601,61 @@ static int launch_inc_tile(const KlIncCellArgs& p, int variant, hipStream_t stre
   return hipGetLastError() == hipSuccess ? 0 : KL_ERR_LAUNCH;
 }
 
-// one LSTM cell step of a layer for n hypotheses with pool slots; KL_ERR_SHAPE = not applicable (the caller takes
-// step_small.hip's kernel or step_big.hip's gather + GEMM path).  Tiles of 128 rows once 64-row tiles would be two or more
-// per CU (width 1024 from 512 hypotheses, width 512 from 2048): a unit block's weights are then read by half as many tiles
-// -- the launches run at the L2's rate, so the bytes are the time.  (rows = -1: by that rule; KL_TILE_ROWS forces 64 / 128.)
-int kl_launch_inc_tile(const KlIncCellArgs& p, int variant, hipStream_t stream, int rows) {
-  const int W = p.W;
-  if (p.n < 1 || (W & 255) || !p.pool || !p.slot_in || !p.slot_out || !p.UF) return KL_ERR_SHAPE;
+// the launcher's shape rules.  Tiles of 128 rows once 64-row tiles would be two or more per CU (width 1024 from 512
+// hypotheses, width 512 from 2048): a unit block's weights are then read by half as many tiles -- the launches run at the
+// L2's rate, so the bytes are the time.  (rows = -1: by that rule; KL_TILE_ROWS forces 64 / 128.)
+int kl_plan_inc_tile(int n, int W, int rows, KlIncTilePlan* out) {
+  if (n < 1 || (W & 255)) return KL_ERR_SHAPE;
   if ((long)8 * W * W >= (1L << 31)) return KL_ERR_SHAPE;
+  if (rows != 64 && rows != 128) rows = (long)(W / 32) * ((n + 63) / 64) >= 512 ? 128 : 64;
+  out->rows = rows;
+  out->nx = W / 32;
+  out->ny = (n + rows - 1) / rows;
+  out->px = out->py = 0;
+  // XCD partition of the tile grid: the split (px unit-block groups x py row-tile groups) with the fewest operand bytes per
+  // XCD (a unit block's weights are 128 rows of K, a row tile's states `rows` rows)
+  if (((out->nx * out->ny) & 7) == 0) {
+    long best = -1;
+    for (int px = 1; px <= 8; px *= 2) {
+      const int py = 8 / px;
+      if (out->nx % px || out->ny % py) continue;
+      const long cost = (long)(out->nx / px) * TC + (long)(out->ny / py) * rows;
+      if (best < 0 || cost < best) { best = cost; out->px = px; out->py = py; }
+    }
+  }
+  return 0;
+}
+
+// one LSTM cell step of a layer for n hypotheses with pool slots; KL_ERR_SHAPE = not applicable (the caller takes
+// step_small.hip's kernel or step_big.hip's gather + GEMM path)
+int kl_launch_inc_tile(const KlIncCellArgs& p, int variant, hipStream_t stream, int rows) {
+  KlIncTilePlan plan;
+  if (kl_plan_inc_tile(p.n, p.W, rows, &plan) != 0 || !p.pool || !p.slot_in || !p.slot_out || !p.UF) return KL_ERR_SHAPE;
   if (p.x_off >= 0 && !p.KF) return KL_ERR_ARG;
-  if (rows != 64 && rows != 128) rows = (long)(W / 32) * ((p.n + 63) / 64) >= 512 ? 128 : 64;
-  return rows == 128 ? launch_inc_tile<128>(p, variant, stream) : launch_inc_tile<64>(p, variant, stream);
+  return plan.rows == 128 ? launch_inc_tile<128>(p, plan, variant, stream) : launch_inc_tile<64>(p, plan, variant, stream);
+}
+
+// the output launcher's shape rules: vocabularies up to 256, widths 128, 256, 512, ..., 16 h rows (hi + lo) and the logits tile in LDS
+int kl_plan_out_softmax(int n, int W, int V, bool lo, size_t* lds) {
+  if (n < 1 || V < 1 || V > 256 || (W != 128 && (W & 255))) return KL_ERR_SHAPE;
+  const size_t need = (size_t)(lo ? 2 : 1) * 16 * W * 2 + (size_t)16 * 260 * 4;
+  if (need > 150 * 1024) return KL_ERR_SHAPE;
+  if (lds) *lds = need;
+  return 0;
 }
 
 // probs[n][V] = softmax(h_top . E^T) for the top layer's new h rows (pool slots slot_out); KL_ERR_SHAPE = not applicable (the
 // caller takes the thin GEMM + the softmax kernel)
 int kl_launch_out_softmax(const float* pool, long slot_ld, const int* slot_out, int h_off, const bf16_t* EF, int split,
                           int n, int W, int V, float* probs, long ldp, hipStream_t stream) {
-  if (n < 1 || V < 1 || V > 256 || (W != 128 && (W & 255)) || !pool || !slot_out || !EF || !probs) return KL_ERR_SHAPE;
+  const bool lo = split == 3;
+  size_t lds = 0;
+  if (kl_plan_out_softmax(n, W, V, lo, &lds) != 0 || !pool || !slot_out || !EF || !probs) return KL_ERR_SHAPE;
   OutSoftmax a;
   memset(&a, 0, sizeof(a));
   a.n = n; a.W = W; a.V = V; a.pool = pool; a.slot_ld = slot_ld; a.slot_out = slot_out; a.h_off = h_off;
   a.EF = EF; a.probs = probs; a.ldp = ldp;
-  const bool lo = split == 3;
   a.lo = lo;
-  const size_t lds = (size_t)(lo ? 2 : 1) * 16 * W * 2 + (size_t)16 * 260 * 4;
-  if (lds > 150 * 1024) return KL_ERR_SHAPE;
   const dim3 grid((n + 15) / 16);
   static KlLdsGrant grant[2];      // (per instantiation and device: the attribute is set when a launch needs more than any before)
   const void* fn = lo ? reinterpret_cast<const void*>(&out_softmax_kernel<true>) : reinterpret_cast<const void*>(&out_softmax_kernel<false>);

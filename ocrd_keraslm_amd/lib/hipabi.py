@@ -27,6 +27,10 @@ KL_OUT_LOGITS_WS, KL_OUT_LOGITS_W128, KL_OUT_DH_WS, KL_OUT_DE_KMAJOR = 1, 2, 4, 
 # kl_derived_view.current; the first three bits of the mask of kl_test_prepare_lazy
 KL_DV_EAGER, KL_DV_LO, KL_DV_INTERLEAVED, KL_DV_INC, KL_DV_BIG, KL_DV_COMB = 1, 2, 4, 8, 16, 32
 KL_LAZY_INC, KL_LAZY_BIG, KL_LAZY_COMB = 1, 2, 4
+# kl_step_route.layers / .out / .idx
+KL_STEP_TILES, KL_STEP_CELLS, KL_STEP_GEMM_FUSED, KL_STEP_GEMM_PLAIN, KL_STEP_THIN = 1, 2, 3, 4, 5
+KL_STEP_OUT_FUSED, KL_STEP_OUT_THIN, KL_STEP_OUT_BIG = 1, 2, 3
+KL_STEP_IDX_DEVICE, KL_STEP_IDX_KERNARG, KL_STEP_IDX_PACKED = 1, 2, 3
 
 
 class KlConfig(C.Structure):
@@ -54,6 +58,12 @@ class KlDerivedView(C.Structure):
                 [("off_CtxK", C.c_uint64 * 8), ("off_CtxKp", C.c_uint64 * 8)] +
                 [("off_" + n, C.c_uint64) for n in ("E_hi", "E_lo", "ET", "EK", "EKp", "comb", "EF", "Ecat")] +
                 [("bytes", C.c_uint64)])
+
+
+class KlStepRoute(C.Structure):
+    """kl_step_route of include/keraslm_hip.h (kl_test_step_route)"""
+    _fields_ = ([(n, C.c_int32) for n in ("layers", "out", "idx", "lo", "gathered", "depth", "tile_rows", "px", "py")] +
+                [("nmt", C.c_int32 * 16), ("gen", C.c_int32 * 16), ("reserved", C.c_int32 * 7)])
 
 
 class KlError(RuntimeError):
@@ -176,6 +186,7 @@ SIGNATURES = {
     "kl_test_window_view": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(KlWindowView)]),
     "kl_test_derived_view": (C.c_int, [C.c_void_p, C.POINTER(KlDerivedView)]),
     "kl_test_prepare_lazy": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "kl_test_step_route": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(KlStepRoute)]),
 }
 
 _lib = None

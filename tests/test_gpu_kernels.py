@@ -143,31 +143,39 @@ def make_model(depth, width, voc, n_ctx=1, seed=4, emb_std=0.5):
     return cfg, w, lm
 
 
+# (the routes named here are what kl_test_step_route reports for the shape at its physical width -- 96 and 100 run at 128, 200
+#  at 256, 768 at 1024 -- with a workspace and no KL_* switch set; tests/test_step_contract_gpu.py asserts the routes of its cases)
 @pytest.mark.parametrize("depth,width,voc,n,n_ctx", [(2, 64, 50, 5, 1), (2, 512, 256, 70, 1), (1, 128, 40, 33, 1),
                                                      (3, 96, 30, 17, 2),
-                                                     # 16 <= n < 256: 16-unit workgroups, state rows through LDS (step_small.hip), one / two row tiles,
-                                                     # K = W and 2W, two weight groups per wave at width 1024, several context variables
-                                                     (2, 512, 256, 128, 1), (2, 512, 256, 200, 1), (3, 256, 40, 100, 2), (4, 1024, 64, 130, 2),
-                                                     # ... widths 64 and 128 (K = 64 / 128: a staging instruction covers several rows), few and many rows
+                                                     # 16 <= n < 256: inc_cell_kernel (step_small.hip), one row tile per workgroup up to 128 rows,
+                                                     # two above, K = W and 2W, several context variables (thin before: fewer than 16 rows, width 64)
+                                                     (2, 512, 256, 128, 1), (2, 512, 256, 200, 1), (3, 256, 40, 100, 2),
+                                                     # width 1024 above 128 rows: inc_tile_kernel on 64-row tiles, px 8
+                                                     (4, 1024, 64, 130, 2),
+                                                     # ... widths 64 and 128 (inc_cell_kernel's GEN instantiation: a staging instruction covers several
+                                                     # rows), at any number of rows from 16 on; 520 rows of width 128: out_softmax_kernel behind it
                                                      (2, 64, 50, 40, 1), (2, 64, 50, 300, 0), (2, 128, 60, 128, 1), (3, 128, 60, 520, 2),
                                                      (1, 512, 64, 97, 0),
-                                                     # n >= 256: big-tile path (step_big.hip)
+                                                     # n >= 256: width 512 on inc_tile_kernel (64-row tiles, px 8), width 128 on inc_cell_kernel with two
+                                                     # row tiles; thin GEMM + softmax behind both
                                                      (2, 512, 256, 300, 1), (3, 96, 30, 260, 2), (1, 128, 40, 257, 1),
-                                                     # n >= 256, widths of 256, 512, 768, ...: one launch per layer on 64 x 128 tiles with the state
-                                                     # rows read through the pool slots (step_tile.hip): whole and ragged row tiles, tile grids that
-                                                     # are / are not dealt to the XCDs as rectangles, 0 / 1 / 2 context variables
+                                                     # n >= 256, widths of 256, 512, 1024: one launch per layer on 64 x 128 tiles with the state
+                                                     # rows read through the pool slots (step_tile.hip): whole and ragged row tiles, px 8 and px 4 x py 2,
+                                                     # 0 / 1 / 2 context variables; out_softmax_kernel from 512 rows on
                                                      (2, 256, 40, 320, 1), (3, 768, 50, 512, 0), (2, 512, 256, 1024, 1), (2, 512, 64, 449, 2),
                                                      # ... 128-row tiles (two or more 64-row tiles per CU), the last one ragged
                                                      (2, 1024, 64, 1030, 1),
-                                                     # cfg5 topology (small and big-n paths)
+                                                     # cfg5 topology: inc_cell_kernel with one row tile, inc_tile_kernel on 64-row tiles
                                                      (4, 1024, 64, 20, 2), (4, 1024, 64, 272, 2),
-                                                     # wide vocabulary (V >= 1024): output projection through the big GEMM too
+                                                     # wide vocabulary (V >= 1024): from 256 rows the plain gather + GEMM + gates_rows and the output
+                                                     # projection through the big GEMM; below, inc_cell_kernel and the thin GEMM
                                                      (2, 128, 1100, 300, 1), (1, 64, 1500, 40, 0),
-                                                     # zero-padded widths (small and big-n paths)
+                                                     # zero-padded widths: inc_cell_kernel at 128, inc_tile_kernel at 256
                                                      (2, 100, 50, 30, 1), (2, 200, 50, 260, 1),
-                                                     # deeper than four layers
+                                                     # deeper than four layers: the thin kernel (12 rows), inc_cell_kernel with two row tiles
                                                      (6, 128, 30, 12, 1), (6, 128, 30, 260, 1),
-                                                     # vocabularies of trained models (len(chars) + 1: ragged, between 100 and 300), and one between 256 and 1024
+                                                     # vocabularies of trained models (len(chars) + 1: ragged, between 100 and 300), and one between 256
+                                                     # and 1024: thin GEMM + softmax behind the cell and tile kernels (out_softmax_kernel ends at V = 256)
                                                      (2, 512, 230, 128, 1), (2, 512, 300, 300, 1), (2, 512, 700, 1024, 1), (2, 128, 230, 40, 1)])
 def test_step_batch_parity(depth, width, voc, n, n_ctx):
     """S1 (rating.py:578-639): chained incremental steps through pool slots."""
