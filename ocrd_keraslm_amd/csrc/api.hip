@@ -563,462 +563,461 @@ int plan_scan2(const kl_handle* h, int B, int T, bool km_plan, bool need_bwd) {
   return p32 ? 32 : 0;
 }
 
-// forward over one window; fills ws (activations) and states
-int forward_impl(kl_handle* h, int B, int T, const int* idx, const int* ctx, float* states, const float* masks,
-                 int training, WindowWs& w, hipStream_t s) {
-  const kl_config& c = h->cfg;
-  const int W = c.width, L = c.depth;
-  const size_t BW = (size_t)B * W;
-  const float* P = h->params;
-  Derived& d = h->d;
-  const int split = training ? 1 : h->precision;
-  std::vector<const float*> ctxk(c.n_ctx);
-  for (int n = 0; n < c.n_ctx; ++n) ctxk[n] = d.CtxK[n];
-  for (int l = 0; l < L; ++l)
-    KL_TRY(kl_launch_state_to_rows(states, B, W, L, l, training ? (bf16_t*)w.H[l] : nullptr,
-                                   training ? nullptr : (float*)w.H[l], w.C[l], s));
-  auto hrow = [&](int l, int block) -> const void* {
-    return training ? (const void*)((bf16_t*)w.H[l] + (size_t)block * BW) : (const void*)((float*)w.H[l] + (size_t)block * BW);
-  };
-  bool scanned = false;
-  // Many streams (B >= 512 at cfg2): one layer per launch with 64-unit workgroups.  The
-  // input contraction of layers >= 1 comes from one big GEMM over all steps, layer 0
-  // reads the look-up tables directly, and the scans also leave H^T for the weight gradients.
-  const int n_rb = (B + 15) / 16;
-  w.ht_ready = false;
-  if (training && h->scan_enabled && h->wide_fwd_min > 0 && kl_scan_fwd_wide_applicable(B, T, W) &&
-      n_rb * (W / 64) >= h->wide_fwd_min) {
-    for (int l = 0; l < L; ++l) {
-      if (!w.km_plan) KL_TRY(kl_launch_transpose_bf16((const bf16_t*)w.H[l], W, w.HTf[l], (long)(T + 1) * B, B, W, s));
-      const bool masked = masks != nullptr && l > 0;
-      KlScanFwdWide a;
-      memset(&a, 0, sizeof(a));
-      a.B = B; a.T = T; a.W = W;
-      a.UT = d.UT_hi[l];
-      const bool v2 = w.scan2_rows != 0;
-      // the eight-wave scan (lstm_scan_fwd8.hip) takes bf16 P rows only: layer 0's gate inputs are gathered in front of it
-      // (layer 0 with one context variable stays on the 16-wave scan's table mode: gathering its P rows first costs more --
-      //  1.25 ms at 3072 streams -- than the eight-wave scan saves; KL_FWD8=2 takes it for layer 0 as well)
-      // (layer 0 with one context variable: the eight-wave scan gathers its rows from the table of all sums -- d.comb)
-      const bool f8_tab = v2 && l == 0 && h->fwd8 && h->fwd8_tab && !h->fwd8_all && d.comb != nullptr && c.n_ctx == 1 && w.scan2_rows == 32 &&
-                          h->scan2_bf16 && h->sentinel_roll && T >= 3 && h->fwd8_ls;
-      const bool f8 = v2 && h->fwd8 && w.scan2_rows == 32 && h->scan2_bf16 && h->sentinel_roll && T >= 3 &&
-                      (l > 0 || c.n_ctx > 1 || h->fwd8_all || f8_tab);
-      if (l > 0) {
-        const bool masked_in = masks != nullptr && (l - 1) > 0;
-        const bf16_t* X = masked_in ? w.Hd[l - 1] : (const bf16_t*)w.H[l - 1] + BW;
-        // (second generation: P in bf16, gate-interleaved -- half the bytes written here and read by the scan)
-        // (weight-stationary kernel where it applies -- width 512, bf16 P -- else the ring GEMM)
-        int pe = KL_ERR_SHAPE;
-        if (v2 && h->scan2_bf16 && h->proj_ws)
-          pe = kl_launch_proj_ws(X, d.KTp[l], d.bp[l], reinterpret_cast<bf16_t*>(w.P1), (long)B * T, W, w.scan_status, s);
-        if (pe == KL_ERR_SHAPE)
-          pe = kl_launch_gemm_tn(X, v2 ? d.KTp[l] : d.KT_hi[l], w.P1, v2 ? d.bp[l] : P + h->off_b[l], B * T, 4 * W, W, W, W, 4 * W,
-                                 v2 && h->scan2_bf16 ? 1 : 0, 1, 1.f, s);
-        KL_TRY(pe);
-        a.P = w.P1;
-        a.p_bf16 = v2 && h->scan2_bf16 ? 1 : 0;
-      } else if (f8_tab) {
-        KL_TRY(build_comb(h, s));
-        KL_TRY(kl_launch_rows_tm(idx, ctx, c.n_ctx, B, T, c.voc_size, c.ctx_vocab, w.ids_tm, s));
-        a.P = reinterpret_cast<const float*>(d.comb);
-        a.p_bf16 = 1;
-        a.ids_tm = w.ids_tm;      // (here: row numbers of d.comb, [T][B])
-        a.V = c.voc_size; a.ctx_vocab = c.ctx_vocab;
-      } else if (v2 && (c.n_ctx > 1 || f8)) {
-        // several context variables: the scan's table mode adds ONE context row to the character row, so the gate inputs
-        // of layer 0 are gathered into P rows first (as the layers above get them from proj_ws_kernel)
-        KL_TRY(kl_launch_p_gather_il(d.EKp, d.CtxKp.data(), c.n_ctx, idx, ctx, B, T, W, c.voc_size, c.ctx_vocab,
-                                     reinterpret_cast<bf16_t*>(w.P1), s));
-        a.P = w.P1;
-        a.p_bf16 = 1;
-      } else if (v2) {
-        KL_TRY(kl_launch_ids_tm(idx, ctx, c.n_ctx, B, T, W, c.voc_size, c.ctx_vocab, w.ids_tm, s));
-        a.EK = d.EKp;
-        a.CtxK[0] = c.n_ctx > 0 ? d.CtxKp[0] : nullptr;
-        a.n_ctx = c.n_ctx;
-        a.ids_tm = w.ids_tm;
-        a.V = c.voc_size; a.ctx_vocab = c.ctx_vocab;
-      } else {
-        a.EK = d.EK;
-        for (int n = 0; n < c.n_ctx; ++n) a.CtxK[n] = d.CtxK[n];
-        a.n_ctx = c.n_ctx;
-        a.idx = idx; a.ctx = ctx;
-        a.bias = P + h->off_b[0];
-      }
-      a.H = (bf16_t*)w.H[l]; a.C = w.C[l]; a.G = w.G[l];
-      a.Cb = (v2 && w.scan2_bwd && h->scan2_bf16) ? w.Cb[l] : nullptr;      // (the backward scans read the cell states as bf16, blocks 0..T)
-      a.Hd = masked ? w.Hd[l] : nullptr;
-      a.mask = masked ? masks + (size_t)l * BW : nullptr;
-      a.HT = w.km_plan ? nullptr : w.HTf[l]; a.ldt = (long)(T + 1) * B;       // (K-major GEMMs: no transposed outputs)
-      a.HdT = (masked && !w.km_plan) ? w.HdT[l] : nullptr; a.ldt_d = (long)B * T;
-      a.counters = w.scan_cnt;
-      a.status = w.scan_status;
-      a.sentinel = h->sentinel ? 1 : 0;
-      a.xcc_slots = (a.sentinel && h->xcd_local) ? w.scan_status + 4 : nullptr;
+// ---- the forward half of a window: kl_train_window, kl_rate_window and its kin, kl_forward_window in both layouts ----
+struct FwdCall {       // a forward pass over one window as its scan families see it
+  kl_handle* h; int B, T; const int *idx, *ctx; float* states; const float* masks; int training, split; WindowWs& w; hipStream_t s;
+  int W, L; size_t BW; int n_rb;      // n_rb: row blocks of 16 streams
+};
+// a scan family's "not mine" (no public return code -- those are 0 .. 5, keraslm_hip.h)
+constexpr int FWD_PASS = -1;
+static_assert(FWD_PASS < KL_OK, "FWD_PASS must not be a public return code");
+
+// row block `block` of layer l's H (0: the carried-in state, t + 1: what step t leaves), bf16 in the training layout, else f32
+static const void* h_rows(const FwdCall& c, int l, int block) {
+  return c.training ? (const void*)((bf16_t*)c.w.H[l] + (size_t)block * c.BW) : (const void*)((float*)c.w.H[l] + (size_t)block * c.BW);
+}
+// training layout: the bf16 rows layer l > 0 reads at steps 0 .. T-1 -- the outputs of layer l - 1, masked where that layer drops out
+static const bf16_t* layer_in(const FwdCall& c, int l) {
+  return (c.masks != nullptr && l - 1 > 0) ? c.w.Hd[l - 1] : (const bf16_t*)c.w.H[l - 1] + c.BW;
+}
+// ... and where layer l writes its own masked outputs, with its mask (both null: no dropout on this layer)
+struct LayerMask { bf16_t* Hd; const float* mask; };
+static LayerMask layer_mask(const FwdCall& c, int l) {
+  if (c.masks == nullptr || l == 0) return {nullptr, nullptr};
+  return {c.w.Hd[l], c.masks + (size_t)l * c.BW};
+}
+// layer 0's gate inputs for all steps, gathered from the look-up tables: P1 = EK[idx] + sum_n CtxK_n[ctx_n] + b_0
+static int gather_layer0(const FwdCall& c) {
+  const kl_handle* h = c.h; const kl_config& cf = h->cfg;
+  std::vector<const float*> ctxk(h->d.CtxK.begin(), h->d.CtxK.end());
+  return kl_launch_p1_gather(h->d.EK, ctxk.data(), cf.n_ctx, h->params + h->off_b[0], c.idx, c.ctx, c.B, c.T, 4 * c.W, c.w.P1, c.s);
+}
+// The gate inputs of layer l > 0 for all steps, one product over layer_in's rows: P1 = X . K_l^T + b_l (p_bf16: as bf16 rows).  il: from the
+// gate-interleaved operands of the second-generation scans; ws: ... on the weight-stationary kernel where it takes the shape, else the ring GEMM
+static int project_inputs(const FwdCall& c, int l, bool il, bool p_bf16, bool ws) {
+  const kl_handle* h = c.h; const Derived& d = h->d; const int W = c.W;
+  const bf16_t* X = layer_in(c, l);
+  if (ws) {
+    const int e = kl_launch_proj_ws(X, d.KTp[l], d.bp[l], reinterpret_cast<bf16_t*>(c.w.P1), (long)c.B * c.T, W, c.w.scan_status, c.s);
+    if (e != KL_ERR_SHAPE) return e;
+  }
+  return kl_launch_gemm_tn(X, il ? d.KTp[l] : d.KT_hi[l], c.w.P1, il ? d.bp[l] : h->params + h->off_b[l], c.B * c.T, 4 * W, W, W, W, 4 * W,
+                           p_bf16 ? 1 : 0, 1, 1.f, c.s);
+}
+
+enum ArmMode { ARM_ROLLING, ARM_ALL_STEPS, ARM_COUNTERS };      // (arm_publish here, arm_dz in the backward half)
+// What a layer's scan hands over from: the row blocks it is going to publish, from `rows` on, as sentinels -- all T steps, or only the
+// first two (rolling: the scan arms block t + 3 while it publishes block t + 1) -- or, for a scan that counts, one layer's counters at zero
+static int arm_publish(const FwdCall& c, bf16_t* rows, ArmMode mode) {
+  if (mode == ARM_COUNTERS) return kl_zero_coherent_async(c.w.scan_cnt, (size_t)c.n_rb * c.T, c.s);
+  return kl_fill_u32_async(rows, (size_t)(mode == ARM_ROLLING ? 2 : c.T) * c.BW * sizeof(bf16_t), 0xFFFFFFFFu, c.s);
+}
+// a whole-window forward scan went out: what the per-launch timing reports about it
+static void trace_fwd_scan(const FwdCall& c, const char* kernel, double flops) {
+  c.h->trace_persistent[0] = true; c.h->trace_name[0] = kernel; c.h->trace_flops[0] = flops;
+  c.h->trace_end(0, c.s);
+}
+// one layer's recurrent contraction over the window
+static double layer_flops(const FwdCall& c) { return (double)c.B * c.T * (2.0 * c.W * 4.0 * c.W); }
+
+// what the wide and the width-128 scans of layer l are told alike (the families add the input side and the hand-off)
+static KlScanFwdWide wide_layer_args(const FwdCall& c, int l) {
+  const LayerMask m = layer_mask(c, l);
+  KlScanFwdWide a;
+  memset(&a, 0, sizeof(a));
+  a.B = c.B; a.T = c.T; a.W = c.W; a.UT = c.h->d.UT_hi[l];
+  a.H = (bf16_t*)c.w.H[l]; a.C = c.w.C[l]; a.G = c.w.G[l];
+  a.Hd = m.Hd; a.mask = m.mask; a.status = c.w.scan_status;
+  return a;
+}
+// layer 0 straight from the f32 look-up tables, by the window's own indices (first-generation wide scans, width 128)
+static void wide_tables(const FwdCall& c, KlScanFwdWide& a) {
+  const kl_handle* h = c.h; const kl_config& cf = h->cfg;
+  a.P = nullptr; a.EK = h->d.EK; a.n_ctx = cf.n_ctx; a.idx = c.idx; a.ctx = c.ctx; a.bias = h->params + h->off_b[0];
+  for (int n = 0; n < cf.n_ctx; ++n) a.CtxK[n] = h->d.CtxK[n];
+}
+// the 16-wave wide scans' own table mode for layer 0 (second generation): character row + ONE context row, by time-major row offsets
+static int wide2_table_mode(const FwdCall& c, KlScanFwdWide& a) {
+  const kl_config& cf = c.h->cfg; const Derived& d = c.h->d;
+  KL_TRY(kl_launch_ids_tm(c.idx, c.ctx, cf.n_ctx, c.B, c.T, c.W, cf.voc_size, cf.ctx_vocab, c.w.ids_tm, c.s));
+  a.P = nullptr; a.p_bf16 = 0; a.ids_tm = c.w.ids_tm;
+  a.EK = d.EKp; a.CtxK[0] = cf.n_ctx > 0 ? d.CtxKp[0] : nullptr; a.n_ctx = cf.n_ctx; a.V = cf.voc_size; a.ctx_vocab = cf.ctx_vocab;
+  return 0;
+}
+// where layer l of a wide scan takes its gate inputs from (v2: second generation; f8, f8_tab: fwd_wide_layer)
+static int wide_inputs(const FwdCall& c, int l, bool v2, bool f8, bool f8_tab, KlScanFwdWide& a) {
+  kl_handle* h = c.h; WindowWs& w = c.w; const kl_config& cf = h->cfg; const Derived& d = h->d; hipStream_t s = c.s;
+  if (l > 0) {
+    // (second generation: P in bf16, gate-interleaved -- half the bytes written here and read by the scan)
+    const bool p_bf16 = v2 && h->scan2_bf16;
+    KL_TRY(project_inputs(c, l, v2, p_bf16, p_bf16 && h->proj_ws));
+    a.P = w.P1; a.p_bf16 = p_bf16 ? 1 : 0;
+  } else if (f8_tab) {
+    KL_TRY(build_comb(h, s));
+    KL_TRY(kl_launch_rows_tm(c.idx, c.ctx, cf.n_ctx, c.B, c.T, cf.voc_size, cf.ctx_vocab, w.ids_tm, s));
+    a.P = reinterpret_cast<const float*>(d.comb); a.p_bf16 = 1;
+    a.ids_tm = w.ids_tm;      // (here: row numbers of d.comb, [T][B])
+    a.V = cf.voc_size; a.ctx_vocab = cf.ctx_vocab;
+  } else if (v2 && (cf.n_ctx > 1 || f8)) {
+    // several context variables: the scan's table mode adds ONE context row to the character row, so the gate inputs
+    // of layer 0 are gathered into P rows first (as the layers above get them from proj_ws_kernel)
+    KL_TRY(kl_launch_p_gather_il(d.EKp, d.CtxKp.data(), cf.n_ctx, c.idx, c.ctx, c.B, c.T, c.W, cf.voc_size, cf.ctx_vocab, reinterpret_cast<bf16_t*>(w.P1), s));
+    a.P = w.P1; a.p_bf16 = 1;
+  } else if (v2) return wide2_table_mode(c, a);
+  else wide_tables(c, a);
+  return 0;
+}
+
+// one layer of the wide family: its input side, the hand-off armed, then the first scan that takes it -- eight-wave, second or first generation
+static int fwd_wide_layer(const FwdCall& c, int l) {
+  kl_handle* h = c.h; WindowWs& w = c.w; const kl_config& cf = h->cfg; const Derived& d = h->d; hipStream_t s = c.s;
+  const int B = c.B, T = c.T, W = c.W;
+  if (!w.km_plan) KL_TRY(kl_launch_transpose_bf16((const bf16_t*)w.H[l], W, w.HTf[l], (long)(T + 1) * B, B, W, s));
+  KlScanFwdWide a = wide_layer_args(c, l);
+  const bool v2 = w.scan2_rows != 0;
+  // the eight-wave scan (lstm_scan_fwd8.hip) takes bf16 P rows only: layer 0's gate inputs are gathered in front of it
+  // (layer 0 with one context variable stays on the 16-wave scan's table mode: gathering its P rows first costs more -- 1.25 ms at 3072
+  //  streams -- than the eight-wave scan saves; KL_FWD8=2 takes it for layer 0 as well; else it gathers them from the table of all sums, d.comb)
+  const bool f8_tab = v2 && l == 0 && h->fwd8 && h->fwd8_tab && !h->fwd8_all && d.comb != nullptr && cf.n_ctx == 1 && w.scan2_rows == 32 &&
+                      h->scan2_bf16 && h->sentinel_roll && T >= 3 && h->fwd8_ls;
+  const bool f8 = v2 && h->fwd8 && w.scan2_rows == 32 && h->scan2_bf16 && h->sentinel_roll && T >= 3 &&
+                  (l > 0 || cf.n_ctx > 1 || h->fwd8_all || f8_tab);
+  KL_TRY(wide_inputs(c, l, v2, f8, f8_tab, a));
+  a.Cb = (v2 && w.scan2_bwd && h->scan2_bf16) ? w.Cb[l] : nullptr;      // (the backward scans read the cell states as bf16, blocks 0..T)
+  a.HT = w.km_plan ? nullptr : w.HTf[l]; a.ldt = (long)(T + 1) * B;       // (K-major GEMMs: no transposed outputs)
+  a.HdT = (a.Hd && !w.km_plan) ? w.HdT[l] : nullptr; a.ldt_d = (long)B * T;
+  a.counters = w.scan_cnt; a.sentinel = h->sentinel ? 1 : 0;
+  a.xcc_slots = (a.sentinel && h->xcd_local) ? w.scan_status + 4 : nullptr;
+  a.gen = (unsigned)(1 + l);                   // (the posts are zeroed once per window: a token per launch)
+  // hand-off by data: the blocks the scan is going to publish start out as sentinels (rolling: only the first two); else by counters
+  if (a.sentinel && v2 && h->sentinel_roll && T >= 3) a.sentinel = 2;
+  KL_TRY(arm_publish(c, a.H + c.BW, a.sentinel == 2 ? ARM_ROLLING : a.sentinel ? ARM_ALL_STEPS : ARM_COUNTERS));
+  // (two phases ahead needs the rows to have been published a phase before the request: three or more phases per workgroup)
+  a.pf_mode = h->scan2_pf >= 0 ? h->scan2_pf : (v2 && kl_scan_wide2_phases(B, T, W, w.scan2_rows, w.scan2_rows == 16 ? 5 : 4) >= 3 ? 2 : 1);
+  h->trace_begin(0, s);      // (every layer's scan launch is timed while tracing)
+  bool took8 = false;
+  if (f8 && a.sentinel == 2) {
+    KlScanFwdWide a8 = a;
+    a8.xcc_slots = h->fwd8_local ? w.scan_status + 4 : nullptr;
+    a8.pf_mode = h->fwd8_pf >= 0 ? h->fwd8_pf : (h->fwd8_ls ? 0 : 1);      // (measured at 3072 streams: two-barrier form 3.06 / 3.32 / 3.30 ms per launch with pf 0 / 1 / 3)
+    const int e8 = kl_launch_scan_fwd8(a8, s, h->fwd8_ls);
+    if (e8 != KL_ERR_SHAPE) KL_TRY(e8);
+    took8 = e8 == 0;
+  }
+  if (!took8 && f8_tab) KL_TRY(wide2_table_mode(c, a));      // (the eight-wave scan did not take the shape: the 16-wave scan's own table mode)
+  if (a.p_bf16) w.p_bf16_mask |= 1u << l;
+  if (!took8) KL_TRY(v2 ? kl_launch_scan_fwd_wide2(a, w.scan2_rows, s) : kl_launch_scan_fwd_wide(a, s));
+  trace_fwd_scan(c, took8 ? "lstm_scan_fwd8_kernel" : v2 ? "lstm_scan_fwd_wide2_kernel" : "lstm_scan_fwd_wide_kernel", layer_flops(c));
+  return 0;
+}
+
+// Many streams (B >= 512 at cfg2), widths 512 and 256: one layer per launch with 64-unit workgroups.  The input contraction of
+// layers >= 1 comes from one big GEMM over all steps, layer 0 reads the look-up tables directly, and the scans also leave H^T
+// for the weight gradients (w.ht_ready: only here, and not where those read K-major).
+static int fwd_wide(const FwdCall& c) {
+  const kl_handle* h = c.h;
+  c.w.ht_ready = false;
+  if (!(c.training && h->scan_enabled && h->wide_fwd_min > 0 && kl_scan_fwd_wide_applicable(c.B, c.T, c.W) &&
+        c.n_rb * (c.W / 64) >= h->wide_fwd_min)) return FWD_PASS;
+  for (int l = 0; l < c.L; ++l) KL_TRY(fwd_wide_layer(c, l));
+  c.w.ht_ready = !c.w.km_plan;
+  return 0;
+}
+
+// Width 128 (the reference's own model sizes): a workgroup = a 16-row block of streams with ALL hidden units of a layer -- no
+// hand-off of state between workgroups (lstm_scan_w128.hip).  Layer 0 takes its gate inputs straight from the look-up tables
+// (up to two context variables; else the rows gather_layer0 left), the layers above it contract their inputs inside the scan.
+static bool fwd_w128_mine(const FwdCall& c) {
+  const kl_handle* h = c.h;
+  return c.training && h->scan_enabled && h->w128 && c.B >= h->w128_min && kl_scan_w128_applicable(c.B, c.T, c.W);
+}
+// ... layer 0 from the tables: the one family that does not read gather_layer0's rows
+static bool fwd_w128_tables(const FwdCall& c) {
+  return fwd_w128_mine(c) && c.h->w128_tables && c.h->cfg.n_ctx <= kl_scan_w128_tables_max_ctx();
+}
+static int w128_single(const FwdCall& c, const KlScanFwdWide& a) {
+  c.h->trace_begin(0, c.s);
+  KL_TRY(kl_launch_scan_fwd_w128(a, c.s));
+  trace_fwd_scan(c, "lstm_scan_fwd_w128_kernel", layer_flops(c));
+  return 0;
+}
+// All layers in one launch where that fits the CUs (layers x 16-row blocks <= 256: up to 2048 streams at depth 2): a layer
+// follows the one below it a step behind, polling the rows that one publishes -- which therefore start out as sentinels.
+static int w128_multi(const FwdCall& c, KlScanFwdWide* layer_args) {
+  kl_handle* h = c.h;
+  if (!kl_scan_w128_multi_fits(c.B, c.L)) return FWD_PASS;
+  const bool roll = h->sentinel_roll && c.T >= 3;      // (rolling sentinels: only the first two steps start out armed)
+  for (int l = 1; l < c.L; ++l) {
+    layer_args[l - 1].sentinel = roll ? 2 : 1;
+    KL_TRY(arm_publish(c, const_cast<bf16_t*>(layer_args[l].X), roll ? ARM_ROLLING : ARM_ALL_STEPS));
+  }
+  h->trace_begin(0, c.s);
+  const int e = kl_launch_scan_fwd_w128_multi(layer_args, c.L, c.s);
+  if (e != 0) return e == KL_ERR_SHAPE ? FWD_PASS : e;
+  trace_fwd_scan(c, "lstm_scan_fwd_w128_multi_kernel", (double)(2 * c.L - 1) * layer_flops(c));      // (recurrent contractions + the input ones)
+  return 0;
+}
+static int fwd_w128(const FwdCall& c) {
+  const kl_handle* h = c.h; const int L = c.L;
+  if (!fwd_w128_mine(c)) return FWD_PASS;
+  const bool tabs = fwd_w128_tables(c);
+  KlScanFwdWide layer_args[KL_SCAN_MAXL];
+  const bool try_multi = h->w128_multi && h->w128_fuse && L >= 2 && L <= KL_SCAN_MAXL;
+  for (int l = 0; l < L; ++l) {
+    KlScanFwdWide& a = layer_args[l < KL_SCAN_MAXL ? l : 0];
+    a = wide_layer_args(c, l);
+    a.P = c.w.P1;
+    if (l == 0 && tabs) wide_tables(c, a);
+    if (l > 0 && !h->w128_fuse) KL_TRY(project_inputs(c, l, false, false, false));
+    if (l > 0 && h->w128_fuse) {      // the input contraction inside the scan: no P rows, no product over all steps
+      a.P = nullptr; a.KT = h->d.KT_hi[l]; a.X = layer_in(c, l); a.bias = h->params + h->off_b[l];
+    }
+    if (!try_multi) KL_TRY(w128_single(c, a));
+  }
+  if (!try_multi) return 0;
+  const int e = w128_multi(c, layer_args);
+  if (e != FWD_PASS) return e;
+  for (int l = 0; l < L; ++l) KL_TRY(w128_single(c, layer_args[l]));      // (the multi launch did not take the shape)
+  return 0;
+}
+
+// what a thin, w32 (KlScanFwd) or split-precision (KlScanFwdSplit) scan over n layers is told whichever it is
+template <class A> static A scan_args(const FwdCall& c, int n) {
+  A a;
+  memset(&a, 0, sizeof(a));
+  a.B = c.B; a.T = c.T; a.W = c.W; a.L = n;
+  a.P1 = c.w.P1; a.counters = c.w.scan_cnt; a.status = c.w.scan_status;
+  return a;
+}
+// layer l as the scan's layer j; input_side: ... with K_l^T and b_l (l > 0), for a scan that contracts the layer's inputs itself
+static void thin_layer_args(const FwdCall& c, KlScanFwd& a, int l, int j, bool input_side) {
+  const kl_handle* h = c.h; const LayerMask m = layer_mask(c, l);
+  a.UT[j] = h->d.UT_hi[l];
+  if (input_side && l > 0) { a.KT[j] = h->d.KT_hi[l]; a.bias[j] = h->params + h->off_b[l]; }
+  a.H[j] = (bf16_t*)c.w.H[l]; a.C[j] = c.w.C[l]; a.G[j] = c.w.G[l];
+  a.Hd[j] = m.Hd; a.mask[j] = m.mask;
+}
+
+// Width 1024 (the cfg5 topology): the recurrent weights of 16 units alone fill half of a 256-thread workgroup's registers, so neither
+// the fused scans (U and K resident) nor the 64-unit wide scans apply.  One layer per launch with the thin workgroups instead, the
+// input side from one GEMM over all steps as in the wide path (layer 0: gather_layer0's rows).  The same layer-by-layer launches
+// serve models deeper than the fused scans' four layers (the reference takes up to ten, scripts/run.py:35).
+static int fwd_layer_by_layer(const FwdCall& c) {
+  kl_handle* h = c.h; WindowWs& w = c.w; hipStream_t s = c.s;
+  const int B = c.B, T = c.T, W = c.W, L = c.L;
+  if (!(c.training && h->scan_enabled && (W == 1024 || L > KL_SCAN_MAXL))) return FWD_PASS;
+  for (int l = 0; l < L; ++l) {
+    if (l > 0) KL_TRY(project_inputs(c, l, false, false, false));
+    KlScanFwd a = scan_args<KlScanFwd>(c, 1);
+    thin_layer_args(c, a, l, 0, false);
+    // width 1024 from eight row blocks: eight-wave workgroups of 32 units, the state tile through LDS, hand-off by
+    // data sentinels inside one XCD (lstm_scan_w32.hip); else the thin workgroups with their counters
+    const bool w32 = h->w32 && c.n_rb >= h->w32_min_rb && kl_scan_w32_applicable(B, T, W);
+    if (w32) {
+      a.sentinel = 1;
+      a.xcc_slots = h->w32_local ? w.scan_status + 4 : nullptr;
       a.gen = (unsigned)(1 + l);                   // (the posts are zeroed once per window: a token per launch)
-      if (a.sentinel && v2 && h->sentinel_roll && T >= 3) {
-        // rolling sentinels: the scan arms block t + 3 while it publishes block t + 1; only the first two start armed
-        a.sentinel = 2;
-        KL_TRY(kl_fill_u32_async((bf16_t*)w.H[l] + BW, (size_t)2 * BW * sizeof(bf16_t), 0xFFFFFFFFu, s));
-      } else if (a.sentinel)   // hand-off by data: the blocks the scan is going to publish start out as sentinels
-        KL_TRY(kl_fill_u32_async((bf16_t*)w.H[l] + BW, (size_t)T * BW * sizeof(bf16_t), 0xFFFFFFFFu, s));
-      else
-        KL_TRY(kl_zero_coherent_async(w.scan_cnt, (size_t)n_rb * T, s));
-      // (two phases ahead needs the rows to have been published a phase before the request: three or more phases per workgroup)
-      a.pf_mode = h->scan2_pf >= 0 ? h->scan2_pf : (v2 && kl_scan_wide2_phases(B, T, W, w.scan2_rows, w.scan2_rows == 16 ? 5 : 4) >= 3 ? 2 : 1);
-      h->trace_begin(0, s);      // (every layer's scan launch is timed while tracing)
-      bool took8 = false;
-      if (f8 && a.sentinel == 2) {
-        KlScanFwdWide a8 = a;
-        a8.xcc_slots = h->fwd8_local ? w.scan_status + 4 : nullptr;
-        a8.pf_mode = h->fwd8_pf >= 0 ? h->fwd8_pf : (h->fwd8_ls ? 0 : 1);      // (measured at 3072 streams: two-barrier form 3.06 / 3.32 / 3.30 ms per launch with pf 0 / 1 / 3)
-        const int e8 = kl_launch_scan_fwd8(a8, s, h->fwd8_ls);
-        if (e8 != KL_ERR_SHAPE) KL_TRY(e8);
-        took8 = e8 == 0;
-      }
-      if (!took8 && f8_tab) {      // (the eight-wave scan did not take the shape: the 16-wave scan's own table mode)
-        KL_TRY(kl_launch_ids_tm(idx, ctx, c.n_ctx, B, T, W, c.voc_size, c.ctx_vocab, w.ids_tm, s));
-        a.P = nullptr; a.p_bf16 = 0;
-        a.EK = d.EKp;
-        a.CtxK[0] = d.CtxKp[0];
-        a.n_ctx = c.n_ctx;
-        a.ids_tm = w.ids_tm;
-      }
-      if (a.p_bf16) w.p_bf16_mask |= 1u << l;
-      if (took8) {}
-      else if (v2) KL_TRY(kl_launch_scan_fwd_wide2(a, w.scan2_rows, s));
-      else KL_TRY(kl_launch_scan_fwd_wide(a, s));
-      {
-        h->trace_persistent[0] = true;
-        h->trace_name[0] = took8 ? "lstm_scan_fwd8_kernel" : v2 ? "lstm_scan_fwd_wide2_kernel" : "lstm_scan_fwd_wide_kernel";
-        h->trace_flops[0] = (double)B * T * (2.0 * W * 4.0 * W);   // one layer's recurrent contraction
-        h->trace_end(0, s);
-      }
     }
-    scanned = true;
-    w.ht_ready = !w.km_plan;
+    KL_TRY(arm_publish(c, a.H[0] + c.BW, w32 ? ARM_ALL_STEPS : ARM_COUNTERS));
+    h->trace_begin(0, s);      // (every layer's scan launch is timed while tracing)
+    const int e = w32 ? kl_launch_scan_fwd_w32(a, s) : kl_launch_scan_fwd(a, s);
+    if (e == KL_ERR_SHAPE && l == 0) {
+      // too many row blocks: a later family takes the window (P1 still holds gather_layer0's rows: this gather repeats it -- DESIGN.md, the forward half)
+      KL_TRY(gather_layer0(c));
+      return FWD_PASS;
+    }
+    if (e != 0) return e;
+    trace_fwd_scan(c, w32 ? "lstm_scan_fwd_w32_kernel" : "lstm_scan_fwd_kernel", layer_flops(c));
   }
-  // Width 128 (the reference's own model sizes): a workgroup = a 16-row block of streams with ALL hidden units of a layer -- no
-  // hand-off of state between workgroups (lstm_scan_w128.hip).  Layer 0 takes its gate inputs straight from the look-up tables
-  // (up to two context variables; else the rows gathered here), the layers above it contract their inputs inside the scan.
-  const bool w128_path = !scanned && training && h->scan_enabled && h->w128 && B >= h->w128_min && kl_scan_w128_applicable(B, T, W);
-  const bool w128_tabs = w128_path && h->w128_tables && c.n_ctx <= kl_scan_w128_tables_max_ctx();
-  if (!scanned && !w128_tabs)
-    KL_TRY(kl_launch_p1_gather(d.EK, ctxk.data(), c.n_ctx, P + h->off_b[0], idx, ctx, B, T, 4 * W, w.P1, s));
-  if (w128_path) {
-    KlScanFwdWide layer_args[KL_SCAN_MAXL];
-    const bool try_multi = h->w128_multi && h->w128_fuse && L >= 2 && L <= KL_SCAN_MAXL;
-    for (int l = 0; l < L; ++l) {
-      const bool masked = masks != nullptr && l > 0;
-      KlScanFwdWide& a = layer_args[l < KL_SCAN_MAXL ? l : 0];
-      memset(&a, 0, sizeof(a));
-      a.B = B; a.T = T; a.W = W;
-      a.UT = d.UT_hi[l];
-      a.P = w.P1;
-      if (l == 0 && w128_tabs) {
-        a.P = nullptr; a.EK = d.EK; a.n_ctx = c.n_ctx; a.idx = idx; a.ctx = ctx; a.bias = P + h->off_b[0];
-        for (int n = 0; n < c.n_ctx; ++n) a.CtxK[n] = ctxk[n];
-      }
-      if (l > 0) {
-        const bool masked_in = masks != nullptr && (l - 1) > 0;
-        const bf16_t* X = masked_in ? w.Hd[l - 1] : (const bf16_t*)w.H[l - 1] + BW;
-        if (h->w128_fuse) {      // the input contraction inside the scan: no P rows, no product over all steps
-          a.P = nullptr; a.KT = d.KT_hi[l]; a.X = X; a.bias = P + h->off_b[l];
-        } else {
-          KL_TRY(kl_launch_gemm_tn(X, d.KT_hi[l], w.P1, P + h->off_b[l], B * T, 4 * W, W, W, W, 4 * W, 0, 1, 1.f, s));
-        }
-      }
-      a.H = (bf16_t*)w.H[l]; a.C = w.C[l]; a.G = w.G[l];
-      a.Hd = masked ? w.Hd[l] : nullptr;
-      a.mask = masked ? masks + (size_t)l * BW : nullptr;
-      a.status = w.scan_status;
-      if (try_multi) continue;
-      h->trace_begin(0, s);
-      KL_TRY(kl_launch_scan_fwd_w128(a, s));
-      h->trace_persistent[0] = true;
-      h->trace_name[0] = "lstm_scan_fwd_w128_kernel";
-      h->trace_flops[0] = (double)B * T * (2.0 * W * 4.0 * W);
-      h->trace_end(0, s);
+  return 0;
+}
+
+// ---- rating windows in split precision: the scans exchange their state as (hi, lo) bf16 planes ----
+// (as thin_layer_args)
+static void split_layer_args(const FwdCall& c, KlScanFwdSplit& a, int l, int j, bool input_side) {
+  const kl_handle* h = c.h; const Derived& d = h->d;
+  a.UT_hi[j] = d.UT_hi[l]; a.UT_lo[j] = d.UT_lo[l];
+  if (input_side && l > 0) { a.KT_hi[j] = d.KT_hi[l]; a.KT_lo[j] = d.KT_lo[l]; a.bias[j] = h->params + h->off_b[l]; }
+  a.Xhi[j] = c.w.Xhi[l]; a.Xlo[j] = c.w.Xlo[l]; a.Hf[j] = (float*)c.w.H[l]; a.C[j] = c.w.C[l];
+}
+// layer l's carried-in state as (hi, lo) planes
+static int split_planes(const FwdCall& c, int l) {
+  return kl_launch_f32_to_bf16_t((const float*)c.w.H[l], c.W, c.B, c.W, c.w.Xhi[l], c.w.Xlo[l], c.W, 0, c.s);
+}
+// hand-off by data: the blocks of both planes that layer l's scan is going to publish start out as sentinels
+static int arm_split(const FwdCall& c, int l) {
+  KL_TRY(arm_publish(c, c.w.Xhi[l] + c.BW, ARM_ALL_STEPS));
+  return arm_publish(c, c.w.Xlo[l] + c.BW, ARM_ALL_STEPS);
+}
+// width 1024 (cfg5), where the layers run one after the other: the shapes whose planes the sentinel scans can index
+static bool split_w1024(const FwdCall& c, int max_rb) {
+  const kl_handle* h = c.h;
+  return !c.training && c.split == KL_PREC_SPLIT && h->scan_enabled && h->split_sentinel && c.W == 1024 && c.n_rb <= max_rb &&
+         (long)(c.T + 1) * c.B * c.W * 2 <= 0x7fffffffL;
+}
+
+// Width 1024 with few streams (two row blocks at most): eight units per workgroup, so that U and K fit and TWO layers
+// run as a wavefront per launch (256 workgroups, one per CU): half the chain of fwd_split_layers
+static int fwd_split_pairs(const FwdCall& c) {
+  if (!(split_w1024(c, 2) && c.h->split8)) return FWD_PASS;
+  for (int l0 = 0; l0 < c.L; l0 += 2) {
+    const int nl = c.L - l0 < 2 ? c.L - l0 : 2;
+    if (l0 + nl > KL_SCAN_MAXL) return FWD_PASS;
+    KlScanFwdSplit a = scan_args<KlScanFwdSplit>(c, nl);
+    a.l0 = l0; a.units8 = 1;
+    for (int l = (l0 > 0 ? l0 - 1 : 0); l < l0 + nl; ++l) split_layer_args(c, a, l, l, true);
+    a.sentinel = 1;
+    for (int l = l0; l < l0 + nl; ++l) {
+      KL_TRY(split_planes(c, l));
+      KL_TRY(arm_split(c, l));
     }
-    if (try_multi) {
-      // All layers in one launch where that fits the CUs (layers x 16-row blocks <= 256: up to 2048 streams at depth 2): a layer
-      // follows the one below it a step behind, polling the rows that one publishes -- which therefore start out as sentinels.
-      bool multi = kl_scan_w128_multi_fits(B, L);
-      if (multi) {
-        const bool roll = h->sentinel_roll && T >= 3;      // (rolling sentinels: only the first two steps start out armed)
-        for (int l = 1; l < L; ++l) {
-          layer_args[l - 1].sentinel = roll ? 2 : 1;
-          KL_TRY(kl_fill_u32_async(const_cast<bf16_t*>(layer_args[l].X), (size_t)(roll ? 2 : T) * BW * sizeof(bf16_t), 0xFFFFFFFFu, s));
-        }
-        h->trace_begin(0, s);
-        const int e = kl_launch_scan_fwd_w128_multi(layer_args, L, s);
-        if (e == KL_ERR_SHAPE) multi = false;
-        else KL_TRY(e);
-      }
-      if (multi) {
-        h->trace_persistent[0] = true;
-        h->trace_name[0] = "lstm_scan_fwd_w128_multi_kernel";
-        h->trace_flops[0] = (double)L * B * T * (2.0 * W * 4.0 * W) + (double)(L - 1) * B * T * (2.0 * W * 4.0 * W);
-        h->trace_end(0, s);
-      } else {
-        for (int l = 0; l < L; ++l) {
-          h->trace_begin(0, s);
-          KL_TRY(kl_launch_scan_fwd_w128(layer_args[l], s));
-          h->trace_persistent[0] = true;
-          h->trace_name[0] = "lstm_scan_fwd_w128_kernel";
-          h->trace_flops[0] = (double)B * T * (2.0 * W * 4.0 * W);
-          h->trace_end(0, s);
-        }
-      }
-    }
-    scanned = true;
+    const int e = kl_launch_scan_fwd_split(a, c.s);
+    if (e == KL_ERR_SHAPE && l0 == 0) return FWD_PASS;      // (fewer than 256 CUs: layer by layer)
+    if (e != 0) return e;
   }
-  // Width 1024 (the cfg5 topology): the recurrent weights of 16 units alone fill half of a 256-thread
-  // workgroup's registers, so neither the fused scans (U and K resident) nor the 64-unit wide scans apply.
-  // One layer per launch with the thin workgroups instead, the input side from one GEMM over all steps as
-  // in the wide path (layer 0: the table gather above).
-  // The same layer-by-layer launches serve models deeper than the fused scans' four layers (the reference takes up to
-  // ten, scripts/run.py:35).
-  if (!scanned && training && h->scan_enabled && (W == 1024 || L > KL_SCAN_MAXL)) {
-    bool all = true;
-    for (int l = 0; l < L && all; ++l) {
-      if (l > 0) {
-        const bool masked_in = masks != nullptr && (l - 1) > 0;
-        const bf16_t* X = masked_in ? w.Hd[l - 1] : (const bf16_t*)w.H[l - 1] + BW;
-        KL_TRY(kl_launch_gemm_tn(X, d.KT_hi[l], w.P1, P + h->off_b[l], B * T, 4 * W, W, W, W, 4 * W, 0, 1, 1.f, s));
-      }
-      const bool masked = masks != nullptr && l > 0;
-      KlScanFwd a;
-      memset(&a, 0, sizeof(a));
-      a.B = B; a.T = T; a.W = W; a.L = 1;
-      a.UT[0] = d.UT_hi[l];
-      a.H[0] = (bf16_t*)w.H[l];
-      a.C[0] = w.C[l];
-      a.G[0] = w.G[l];
-      a.Hd[0] = masked ? w.Hd[l] : nullptr;
-      a.mask[0] = masked ? masks + (size_t)l * BW : nullptr;
-      a.P1 = w.P1;
-      a.counters = w.scan_cnt;
-      a.status = w.scan_status;
-      // width 1024 from eight row blocks: eight-wave workgroups of 32 units, the state tile through LDS, hand-off by
-      // data sentinels inside one XCD (lstm_scan_w32.hip); else the thin workgroups with their counters
-      const bool w32 = h->w32 && (B + 15) / 16 >= h->w32_min_rb && kl_scan_w32_applicable(B, T, W);
-      if (w32) {
-        a.sentinel = 1;
-        a.xcc_slots = h->w32_local ? w.scan_status + 4 : nullptr;
-        a.gen = (unsigned)(1 + l);                   // (the posts are zeroed once per window: a token per launch)
-        KL_TRY(kl_fill_u32_async((bf16_t*)w.H[l] + BW, (size_t)T * BW * sizeof(bf16_t), 0xFFFFFFFFu, s));
-      } else {
-        KL_TRY(kl_zero_coherent_async(w.scan_cnt, (size_t)((B + 15) / 16) * T, s));
-      }
-      h->trace_begin(0, s);      // (every layer's scan launch is timed while tracing)
-      const int e = w32 ? kl_launch_scan_fwd_w32(a, s) : kl_launch_scan_fwd(a, s);
-      if (e == KL_ERR_SHAPE && l == 0) {
-        all = false;          // (too many row blocks: the launch-per-step path below takes the window, P1 is in place)
-      } else if (e != 0) {
-        return e;
-      } else {
-        h->trace_persistent[0] = true;
-        h->trace_name[0] = w32 ? "lstm_scan_fwd_w32_kernel" : "lstm_scan_fwd_kernel";
-        h->trace_flops[0] = (double)B * T * (2.0 * W * 4.0 * W);
-        h->trace_end(0, s);
-      }
+  return 0;
+}
+
+// Width 1024: the (hi, lo) planes of the recurrent weights of 16 units are a workgroup's whole register budget, so the layers run
+// one after the other -- per layer ONE split-precision product over all steps for the input side (layer 0: gather_layer0's rows),
+// then the persistent scan with U alone (was: a launch per step and layer wavefront, 18 ms per 1 x 512 window)
+static int fwd_split_layers(const FwdCall& c) {
+  kl_handle* h = c.h; WindowWs& w = c.w; const Derived& d = h->d; hipStream_t s = c.s;
+  const int B = c.B, T = c.T, W = c.W;
+  if (!split_w1024(c, 16)) return FWD_PASS;
+  for (int l = 0; l < c.L; ++l) {
+    const float* bias = h->params + h->off_b[l];
+    if (l > 0 && B * T >= 2048) {
+      // many rows: the three products of the split (hi.hi + bias, lo.hi, hi.lo) on the big-tile GEMM, over the (hi, lo)
+      // planes the scan below left behind (the thin GEMM re-reads the weights per 32 rows: 2.9 ms per layer at 16 x 512 rows)
+      const bf16_t* xh = w.Xhi[l - 1] + c.BW;
+      const bf16_t* xl = w.Xlo[l - 1] + c.BW;
+      KL_TRY(kl_launch_gemm_tn(xh, d.KT_hi[l], w.P1, bias, B * T, 4 * W, W, W, W, 4 * W, 0, 1, 1.f, s));
+      KL_TRY(kl_launch_gemm_tn(xl, d.KT_hi[l], w.P1, nullptr, B * T, 4 * W, W, W, W, 4 * W, 2, 1, 1.f, s));
+      KL_TRY(kl_launch_gemm_tn(xh, d.KT_lo[l], w.P1, nullptr, B * T, 4 * W, W, W, W, 4 * W, 2, 1, 1.f, s));
+    } else if (l > 0) {
+      KlOperand op;
+      memset(&op, 0, sizeof(op));
+      op.A = h_rows(c, l - 1, 1); op.lda = W; op.a_is_f32 = 1;
+      op.WT_hi = d.KT_hi[l]; op.WT_lo = d.KT_lo[l]; op.ldw = W; op.K = W;
+      KL_TRY(kl_launch_thin_gemm(&op, B * T, 4 * W, w.P1, 4 * W, bias, KL_PREC_SPLIT, s));
     }
-    if (all) scanned = true;
-    else KL_TRY(kl_launch_p1_gather(d.EK, ctxk.data(), c.n_ctx, P + h->off_b[0], idx, ctx, B, T, 4 * W, w.P1, s));
+    KlScanFwdSplit a = scan_args<KlScanFwdSplit>(c, 1);
+    split_layer_args(c, a, l, 0, false);
+    a.sentinel = 1;
+    KL_TRY(split_planes(c, l));
+    KL_TRY(arm_split(c, l));
+    KL_TRY(kl_launch_scan_fwd_split(a, s));
   }
-  // rating windows in split precision at width 1024 (cfg5): the (hi, lo) planes of the recurrent weights of 16 units are a
-  // workgroup's whole register budget, so the layers run one after the other -- per layer ONE split-precision product
-  // over all steps for the input side (layer 0: the table gather above), then the persistent scan with U alone
-  // (was: a launch per step and layer wavefront, 18 ms per 1 x 512 window)
-  // ... and with few streams (two row blocks at most): eight units per workgroup, so that U and K fit and TWO layers
-  // run as a wavefront per launch (256 workgroups, one per CU): half the chain
-  if (!scanned && !training && split == KL_PREC_SPLIT && h->scan_enabled && h->split_sentinel && h->split8 && W == 1024 &&
-      (B + 15) / 16 <= 2 && (long)(T + 1) * B * W * 2 <= 0x7fffffffL) {
-    bool all = true;
-    for (int l0 = 0; l0 < L && all; l0 += 2) {
-      const int nl = L - l0 < 2 ? L - l0 : 2;
-      KlScanFwdSplit a;
-      memset(&a, 0, sizeof(a));
-      a.B = B; a.T = T; a.W = W; a.L = nl; a.l0 = l0; a.units8 = 1;
-      if (l0 + nl > KL_SCAN_MAXL) { all = false; break; }
-      for (int l = (l0 > 0 ? l0 - 1 : 0); l < l0 + nl; ++l) {
-        a.UT_hi[l] = d.UT_hi[l]; a.UT_lo[l] = d.UT_lo[l];
-        a.KT_hi[l] = l > 0 ? d.KT_hi[l] : nullptr; a.KT_lo[l] = l > 0 ? d.KT_lo[l] : nullptr;
-        a.bias[l] = l > 0 ? P + h->off_b[l] : nullptr;
-        a.Xhi[l] = w.Xhi[l]; a.Xlo[l] = w.Xlo[l];
-        a.Hf[l] = (float*)w.H[l];
-        a.C[l] = w.C[l];
-      }
-      a.P1 = w.P1;
-      a.counters = w.scan_cnt;
-      a.status = w.scan_status;
-      a.sentinel = 1;
-      for (int l = l0; l < l0 + nl; ++l) {
-        KL_TRY(kl_launch_f32_to_bf16_t((const float*)w.H[l], W, B, W, w.Xhi[l], w.Xlo[l], W, 0, s));
-        KL_TRY(kl_fill_u32_async(w.Xhi[l] + BW, (size_t)T * BW * sizeof(bf16_t), 0xFFFFFFFFu, s));
-        KL_TRY(kl_fill_u32_async(w.Xlo[l] + BW, (size_t)T * BW * sizeof(bf16_t), 0xFFFFFFFFu, s));
-      }
-      const int e = kl_launch_scan_fwd_split(a, s);
-      if (e == KL_ERR_SHAPE && l0 == 0) all = false;      // (fewer than 256 CUs: layer by layer below)
-      else if (e != 0) return e;
-    }
-    if (all) scanned = true;
+  return 0;
+}
+
+// one persistent launch for all layers and steps, hand-off by sentinels or (KL_SPLIT_SENTINEL=0) by counters zeroed write-through
+static int fwd_split_fused(const FwdCall& c) {
+  const kl_handle* h = c.h; const int L = c.L;
+  if (!(!c.training && c.split == KL_PREC_SPLIT && h->scan_enabled && L <= KL_SCAN_MAXL)) return FWD_PASS;
+  KlScanFwdSplit a = scan_args<KlScanFwdSplit>(c, L);
+  for (int l = 0; l < L; ++l) split_layer_args(c, a, l, l, true);
+  for (int l = 0; l < L; ++l) KL_TRY(split_planes(c, l));
+  a.sentinel = h->split_sentinel ? 1 : 0;
+  if (a.sentinel)
+    for (int l = 0; l < L; ++l) KL_TRY(arm_split(c, l));
+  else
+    KL_TRY(kl_zero_coherent_async(c.w.scan_cnt, (size_t)L * c.n_rb * c.T, c.s));      // (all layers' counters)
+  const int e = kl_launch_scan_fwd_split(a, c.s);
+  return e == KL_ERR_SHAPE ? FWD_PASS : e;
+}
+
+// the fused thin training scan: all layers (at most KL_SCAN_MAXL) and steps in one launch where the shape allows it, hand-off by counters
+static int fwd_fused_thin(const FwdCall& c) {
+  kl_handle* h = c.h; const int L = c.L;
+  if (!(c.training && h->scan_enabled && L <= KL_SCAN_MAXL)) return FWD_PASS;
+  KlScanFwd a = scan_args<KlScanFwd>(c, L);
+  for (int l = 0; l < L; ++l) thin_layer_args(c, a, l, l, true);
+  KL_TRY(kl_zero_coherent_async(c.w.scan_cnt, (size_t)L * c.n_rb * c.T, c.s));      // (all layers' counters)
+  h->trace_begin(0, c.s);
+  const int e = kl_launch_scan_fwd(a, c.s);
+  if (e != 0) return e == KL_ERR_SHAPE ? FWD_PASS : e;
+  trace_fwd_scan(c, "lstm_scan_fwd_kernel", (2.0 * L - 1.0) * layer_flops(c));   // U_l for all l, K_l for l >= 1
+  return 0;
+}
+
+// step t of layer l as the launch-per-step kernel takes it: z = [X . K_l^T + b_l | P1 rows (layer 0)] + h_{t-1} . U_l^T, then the cell
+static KlFwdStep wavefront_step(const FwdCall& c, int l, int t) {
+  const kl_handle* h = c.h; const WindowWs& w = c.w; const Derived& d = h->d;
+  const int B = c.B, W = c.W; const size_t BW = c.BW;
+  const bool lo = c.split == KL_PREC_SPLIT;
+  KlFwdStep S;
+  memset(&S, 0, sizeof(S));
+  S.n_rows = B; S.W = W; S.split = c.split; S.n_ops = l > 0 ? 2 : 1;
+  KlOperand& u = S.op[S.n_ops - 1];      // the recurrent side comes last
+  u.A = h_rows(c, l, t); u.a_is_f32 = c.training ? 0 : 1; u.lda = W;
+  u.WT_hi = d.UT_hi[l]; u.WT_lo = lo ? d.UT_lo[l] : nullptr; u.ldw = W; u.K = W;
+  if (l > 0) {
+    KlOperand& o = S.op[0];
+    o.A = c.training ? (const void*)(layer_in(c, l) + (size_t)t * BW) : h_rows(c, l - 1, t + 1); o.a_is_f32 = c.training ? 0 : 1;
+    o.lda = W; o.WT_hi = d.KT_hi[l]; o.WT_lo = lo ? d.KT_lo[l] : nullptr; o.ldw = W; o.K = W;
+    S.bias = h->params + h->off_b[l];
+  } else {
+    S.T1 = w.P1 + (size_t)t * B * 4 * W; S.t1_ld = 4 * W;
   }
-  if (!scanned && !training && split == KL_PREC_SPLIT && h->scan_enabled && h->split_sentinel && W == 1024 &&
-      (B + 15) / 16 <= 16 && (long)(T + 1) * B * W * 2 <= 0x7fffffffL) {
-    for (int l = 0; l < L; ++l) {
-      if (l > 0 && B * T >= 2048) {
-        // many rows: the three products of the split (hi.hi + bias, lo.hi, hi.lo) on the big-tile GEMM, over the (hi, lo)
-        // planes the scan below left behind (the thin GEMM re-reads the weights per 32 rows: 2.9 ms per layer at 16 x 512 rows)
-        const bf16_t* xh = w.Xhi[l - 1] + BW;
-        const bf16_t* xl = w.Xlo[l - 1] + BW;
-        KL_TRY(kl_launch_gemm_tn(xh, d.KT_hi[l], w.P1, P + h->off_b[l], B * T, 4 * W, W, W, W, 4 * W, 0, 1, 1.f, s));
-        KL_TRY(kl_launch_gemm_tn(xl, d.KT_hi[l], w.P1, nullptr, B * T, 4 * W, W, W, W, 4 * W, 2, 1, 1.f, s));
-        KL_TRY(kl_launch_gemm_tn(xh, d.KT_lo[l], w.P1, nullptr, B * T, 4 * W, W, W, W, 4 * W, 2, 1, 1.f, s));
-      } else if (l > 0) {
-        KlOperand op;
-        memset(&op, 0, sizeof(op));
-        op.A = (float*)w.H[l - 1] + BW; op.lda = W; op.a_is_f32 = 1;
-        op.WT_hi = d.KT_hi[l]; op.WT_lo = d.KT_lo[l]; op.ldw = W; op.K = W;
-        KL_TRY(kl_launch_thin_gemm(&op, B * T, 4 * W, w.P1, 4 * W, P + h->off_b[l], KL_PREC_SPLIT, s));
-      }
-      KlScanFwdSplit a;
-      memset(&a, 0, sizeof(a));
-      a.B = B; a.T = T; a.W = W; a.L = 1;
-      a.UT_hi[0] = d.UT_hi[l]; a.UT_lo[0] = d.UT_lo[l];
-      a.Xhi[0] = w.Xhi[l]; a.Xlo[0] = w.Xlo[l];
-      a.Hf[0] = (float*)w.H[l];
-      a.C[0] = w.C[l];
-      a.P1 = w.P1;
-      a.counters = w.scan_cnt;
-      a.status = w.scan_status;
-      a.sentinel = 1;
-      KL_TRY(kl_launch_f32_to_bf16_t((const float*)w.H[l], W, B, W, w.Xhi[l], w.Xlo[l], W, 0, s));
-      KL_TRY(kl_fill_u32_async(w.Xhi[l] + BW, (size_t)T * BW * sizeof(bf16_t), 0xFFFFFFFFu, s));
-      KL_TRY(kl_fill_u32_async(w.Xlo[l] + BW, (size_t)T * BW * sizeof(bf16_t), 0xFFFFFFFFu, s));
-      KL_TRY(kl_launch_scan_fwd_split(a, s));
+  S.c_prev = w.C[l] + (size_t)t * BW; S.c_prev_ld = W;
+  S.c_out = w.C[l] + (size_t)(t + 1) * BW; S.c_out_ld = W;
+  if (c.training) {
+    const LayerMask m = layer_mask(c, l);
+    S.h_out_bf16 = (bf16_t*)w.H[l] + (size_t)(t + 1) * BW; S.h_out_bf16_ld = W;
+    S.gates_out = w.G[l] + (size_t)t * B * 4 * W; S.gates_ld = 4 * W;
+    if (m.mask) {
+      S.hmask = m.mask; S.hmask_ld = W;
+      S.hd_out_bf16 = m.Hd + (size_t)t * BW; S.hd_out_ld = W;
     }
-    scanned = true;
+  } else {
+    S.h_out_f32 = (float*)w.H[l] + (size_t)(t + 1) * BW; S.h_out_f32_ld = W;
   }
-  // rating windows in split precision: one persistent launch for all layers and steps
-  if (!scanned && !training && split == KL_PREC_SPLIT && h->scan_enabled && L <= KL_SCAN_MAXL) {
-    KlScanFwdSplit a;
-    memset(&a, 0, sizeof(a));
-    a.B = B; a.T = T; a.W = W; a.L = L;
-    for (int l = 0; l < L; ++l) {
-      a.UT_hi[l] = d.UT_hi[l]; a.UT_lo[l] = d.UT_lo[l];
-      a.KT_hi[l] = l > 0 ? d.KT_hi[l] : nullptr; a.KT_lo[l] = l > 0 ? d.KT_lo[l] : nullptr;
-      a.bias[l] = l > 0 ? P + h->off_b[l] : nullptr;
-      a.Xhi[l] = w.Xhi[l]; a.Xlo[l] = w.Xlo[l];
-      a.Hf[l] = (float*)w.H[l];
-      a.C[l] = w.C[l];
-    }
-    a.P1 = w.P1;
-    a.counters = w.scan_cnt;
-    a.status = w.scan_status;
-    // the carried-in state as (hi, lo) planes; hand-off counters zeroed write-through
-    for (int l = 0; l < L; ++l)
-      KL_TRY(kl_launch_f32_to_bf16_t((const float*)w.H[l], W, B, W, w.Xhi[l], w.Xlo[l], W, 0, s));
-    a.sentinel = h->split_sentinel ? 1 : 0;
-    if (a.sentinel) {      // hand-off by data: the blocks the scan is going to publish start out as sentinels
-      for (int l = 0; l < L; ++l) {
-        KL_TRY(kl_fill_u32_async(w.Xhi[l] + BW, (size_t)T * BW * sizeof(bf16_t), 0xFFFFFFFFu, s));
-        KL_TRY(kl_fill_u32_async(w.Xlo[l] + BW, (size_t)T * BW * sizeof(bf16_t), 0xFFFFFFFFu, s));
-      }
-    } else {
-      KL_TRY(kl_zero_coherent_async(w.scan_cnt, (size_t)L * ((B + 15) / 16) * T, s));
-    }
-    const int e = kl_launch_scan_fwd_split(a, s);
-    if (e == 0) scanned = true;
-    else if (e != KL_ERR_SHAPE) return e;
-  }
-  // persistent scan (one launch for all layers and steps) where the shape allows it
-  if (!scanned && training && h->scan_enabled && L <= KL_SCAN_MAXL) {
-    KlScanFwd a;
-    memset(&a, 0, sizeof(a));
-    a.B = B; a.T = T; a.W = W; a.L = L;
-    for (int l = 0; l < L; ++l) {
-      a.UT[l] = d.UT_hi[l];
-      a.KT[l] = l > 0 ? d.KT_hi[l] : nullptr;
-      a.bias[l] = l > 0 ? P + h->off_b[l] : nullptr;
-      a.H[l] = (bf16_t*)w.H[l];
-      a.C[l] = w.C[l];
-      a.G[l] = w.G[l];
-      const bool masked = masks != nullptr && l > 0;
-      a.Hd[l] = masked ? w.Hd[l] : nullptr;
-      a.mask[l] = masked ? masks + (size_t)l * BW : nullptr;
-    }
-    a.P1 = w.P1;
-    a.counters = w.scan_cnt;
-    a.status = w.scan_status;
-    KL_TRY(kl_zero_coherent_async(w.scan_cnt, (size_t)L * ((B + 15) / 16) * T, s));
-    h->trace_begin(0, s);
-    const int e = kl_launch_scan_fwd(a, s);
-    if (e == 0) {
-      scanned = true;
-      h->trace_persistent[0] = true;
-      h->trace_name[0] = "lstm_scan_fwd_kernel";
-      h->trace_flops[0] = (double)B * T * (2.0 * (2.0 * L - 1.0) * W * 4.0 * W);   // U_l for all l, K_l for l >= 1
-      h->trace_end(0, s);
-    } else if (e != KL_ERR_SHAPE) {
-      return e;
-    }
-  }
-  for (int dgl = 0; !scanned && dgl < T + L - 1; ++dgl) {
+  return S;
+}
+
+// everything else: the launch-per-step layer wavefront (diagonal dgl: layer l runs step dgl - l)
+static int fwd_wavefront(const FwdCall& c) {
+  kl_handle* h = c.h; const int T = c.T, L = c.L;
+  for (int dgl = 0; dgl < T + L - 1; ++dgl) {
     KlFwdStep steps[16];     // one per layer (config_ok: depth <= 16); launched in packs of 4 below
     int ns = 0;
-    for (int l = 0; l < L; ++l) {
-      const int t = dgl - l;
-      if (t < 0 || t >= T) continue;
-      KlFwdStep& S = steps[ns++];
-      memset(&S, 0, sizeof(S));
-      S.n_rows = B; S.W = W; S.split = split;
-      int p = 0;
-      if (l > 0) {
-        KlOperand& o = S.op[p++];
-        const bool masked_in = training && masks != nullptr && (l - 1) > 0;
-        if (masked_in) {
-          o.A = w.Hd[l - 1] + (size_t)t * BW; o.a_is_f32 = 0;
-        } else {
-          o.A = hrow(l - 1, t + 1); o.a_is_f32 = training ? 0 : 1;
-        }
-        o.lda = W; o.WT_hi = d.KT_hi[l]; o.WT_lo = split == 3 ? d.KT_lo[l] : nullptr; o.ldw = W; o.K = W;
-        S.bias = P + h->off_b[l];
-      } else {
-        S.T1 = w.P1 + (size_t)t * B * 4 * W; S.t1_ld = 4 * W;
-      }
-      {
-        KlOperand& o = S.op[p++];
-        o.A = hrow(l, t); o.a_is_f32 = training ? 0 : 1; o.lda = W;
-        o.WT_hi = d.UT_hi[l]; o.WT_lo = split == 3 ? d.UT_lo[l] : nullptr; o.ldw = W; o.K = W;
-      }
-      S.n_ops = p;
-      S.c_prev = w.C[l] + (size_t)t * BW; S.c_prev_ld = W;
-      S.c_out = w.C[l] + (size_t)(t + 1) * BW; S.c_out_ld = W;
-      if (training) {
-        S.h_out_bf16 = (bf16_t*)w.H[l] + (size_t)(t + 1) * BW; S.h_out_bf16_ld = W;
-        S.gates_out = w.G[l] + (size_t)t * B * 4 * W; S.gates_ld = 4 * W;
-        if (l > 0 && masks != nullptr) {
-          S.hmask = masks + (size_t)l * BW; S.hmask_ld = W;
-          S.hd_out_bf16 = w.Hd[l] + (size_t)t * BW; S.hd_out_ld = W;
-        }
-      } else {
-        S.h_out_f32 = (float*)w.H[l] + (size_t)(t + 1) * BW; S.h_out_f32_ld = W;
-      }
-    }
+    for (int l = 0; l < L; ++l)
+      if (dgl - l >= 0 && dgl - l < T) steps[ns++] = wavefront_step(c, l, dgl - l);
     // a launch packs at most 4 independent steps
     for (int i = 0; i < ns; i += 4) {
       // trace: one event pair brackets 8 consecutive steady-state launches (dgl = 8k .. 8k+7)
       const bool steady = (ns == L) && dgl >= L && dgl + 8 < T;
-      if (steady && dgl % 8 == 0) h->trace_begin(0, s);
-      KL_TRY(kl_launch_fwd_steps(steps + i, ns - i < 4 ? ns - i : 4, s));
-      if (steady && dgl % 8 == 7) h->trace_end(0, s);
+      if (steady && dgl % 8 == 0) h->trace_begin(0, c.s);
+      KL_TRY(kl_launch_fwd_steps(steps + i, ns - i < 4 ? ns - i : 4, c.s));
+      if (steady && dgl % 8 == 7) h->trace_end(0, c.s);
     }
   }
+  return 0;
+}
+
+// forward over one window; fills ws (activations) and states: the carried-in state into row block 0, the first scan family that
+// takes the window (asked in this order), the last row block back into the state
+int forward_impl(kl_handle* h, int B, int T, const int* idx, const int* ctx, float* states, const float* masks,
+                 int training, WindowWs& w, hipStream_t s) {
+  const int W = h->cfg.width, L = h->cfg.depth;
+  const FwdCall c = {h, B, T, idx, ctx, states, masks, training, training ? 1 : h->precision, w, s, W, L, (size_t)B * W, (B + 15) / 16};
   for (int l = 0; l < L; ++l)
-    KL_TRY(kl_launch_rows_to_state(hrow(l, T), training ? 0 : 1, w.C[l] + (size_t)T * BW, B, W, L, l, states, s));
+    KL_TRY(kl_launch_state_to_rows(states, B, W, L, l, training ? (bf16_t*)w.H[l] : nullptr, training ? nullptr : (float*)w.H[l], w.C[l], s));
+  int e = fwd_wide(c);
+  // (every family below reads layer 0's gate inputs as P1 rows, but width 128 where it reads the tables itself)
+  if (e == FWD_PASS && !fwd_w128_tables(c)) KL_TRY(gather_layer0(c));
+  if (e == FWD_PASS) e = fwd_w128(c);
+  if (e == FWD_PASS) e = fwd_layer_by_layer(c);
+  if (e == FWD_PASS) e = fwd_split_pairs(c);
+  if (e == FWD_PASS) e = fwd_split_layers(c);
+  if (e == FWD_PASS) e = fwd_split_fused(c);
+  if (e == FWD_PASS) e = fwd_fused_thin(c);
+  if (e == FWD_PASS) e = fwd_wavefront(c);
+  KL_TRY(e);
+  for (int l = 0; l < L; ++l)
+    KL_TRY(kl_launch_rows_to_state(h_rows(c, l, T), training ? 0 : 1, w.C[l] + (size_t)T * c.BW, B, W, L, l, states, s));
   return 0;
 }
 
@@ -1488,7 +1487,6 @@ static KlScanBwd bwd_scan_args(const TrainCall& c, int first, int n) {
 
 // What layer l's scan hands over from: the dZ rows it is going to publish as sentinels -- all steps, or only the last two (rolling: the
 // scan re-arms step t - 2 while it publishes step t) -- or, for a scan that counts, one layer's counters at zero
-enum ArmMode { ARM_ROLLING, ARM_ALL_STEPS, ARM_COUNTERS };
 static int arm_dz(const TrainCall& c, int l, ArmMode mode) {
   const size_t T = c.T, BW = c.BW;
   if (mode == ARM_COUNTERS) return kl_zero_coherent_async(c.w.scan_cnt, (size_t)((c.B + 15) / 16) * T, c.s);
