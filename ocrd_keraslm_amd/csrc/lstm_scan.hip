@@ -33,6 +33,9 @@
 // times out cleanly through the bounded spins.
 //
 // The above describes the fused thin scans (lstm_scan_fwd_kernel / lstm_scan_bwd_kernel, few row blocks).
+// The rating windows' split-precision scans (lstm_scan_fwd_split_kernel, _sent_kernel, _sent8_kernel) are the same decomposition
+// with (hi, lo) operands; they share the sentinel look (split_fetch) and the launcher's grid plan (plan_scan_split), and are
+// otherwise three kernels on purpose: see the note above lstm_scan_fwd_split_kernel.
 // For many streams the layer-sequential WIDE scans further down take over: one layer per launch,
 // 1024-thread workgroups of 64 hidden units that fetch the state tile once and share it through LDS,
 // hand-off by data sentinels instead of counters (re-armed inside the backward scan), the next row
@@ -255,6 +258,10 @@ __global__ __launch_bounds__(256, 2) void lstm_scan_fwd_kernel(const KlScanFwd a
 // bf16 planes (Xhi, Xlo); the f32 outputs the logits need are stored off the hand-off
 // chain.  Weights take 4 x the registers of the training kernel (U, K) x (hi, lo):
 // one 256-thread workgroup per CU.
+// (Three kernels with much the same text.  Folding them into one inlined body, or moving more than split_fetch into shared
+//  helpers -- the MFMA triple, the gate-input gather, the epilogue were tried --, changed the compiled schedule of the step
+//  loop every time: registers, the waits around the sentinel check, in two instantiations the occupancy; rating windows came
+//  out 1-3 % slower.  profiles/split_scan_refactor_ab.json has the measurements.)
 template <int KSTEPS, int MAXRB>
 __global__ __launch_bounds__(256, 1) void lstm_scan_fwd_split_kernel(const KlScanFwdSplit a) {
   // K is split over KW waves (four; fewer for widths below 128, where the other waves contribute zero tiles)
@@ -429,6 +436,31 @@ __global__ __launch_bounds__(256, 1) void lstm_scan_fwd_split_kernel(const KlSca
   }
 }
 
+// The sentinel hand-off's look at one operand (both sentinel kernels below): the fragments this wave is going to multiply,
+// loaded until none of them shows a sentinel (`poll` false: loaded once).  Gives up -- alive = false, wave-uniform -- once
+// this wave has looked SPIN_LIMIT times or another has raised the status word (read every 64 looks).
+template <int KQ>
+__device__ __forceinline__ void split_fetch(const __amdgpu_buffer_rsrc_t& rh, const __amdgpu_buffer_rsrc_t& rl, unsigned abase, bool poll,
+                                          bool& alive, unsigned* status, uint4 (&fh)[KQ], uint4 (&fl)[KQ]) {
+  for (unsigned spin = 0;; ++spin) {
+    unsigned any = 0;
+#pragma unroll
+    for (int j = 0; j < KQ; ++j) {
+      fh[j] = load16_sc1(rh, abase + j * 64);
+      fl[j] = load16_sc1(rl, abase + j * 64);
+    }
+#pragma unroll
+    for (int j = 0; j < KQ; ++j)
+      any |= fh[j].x | fh[j].y | fh[j].z | fh[j].w | fl[j].x | fl[j].y | fl[j].z | fl[j].w;
+    if (!poll || !alive || __all((any & 0x40004000u) == 0)) break;
+    if ((spin & 63) == 63 && __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) alive = false;
+    if (spin >= SPIN_LIMIT) {
+      __hip_atomic_store(status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      alive = false;
+    }
+  }
+}
+
 // The same scan with the hand-off carried by the DATA (the rating window at the reference's batching, 1 x 256, is one
 // latency chain of T + L - 1 steps: profiles/r02_rating_window_B1_kernel_stats.csv had 4.25 us per step, of which the
 // counter protocol -- drain the write-through stores, barrier, atomic add, poll, barrier, only then load -- is most).
@@ -505,27 +537,6 @@ __global__ __launch_bounds__(256, 1) void lstm_scan_fwd_split_sent_kernel(const 
   bool alive = true;                 // (wave-uniform: false once this wave or any other has given up)
   int par = 0;
 
-  // the fragments of one operand, loaded until none of them is a sentinel (`poll` false: loaded once)
-  auto fetch = [&](const __amdgpu_buffer_rsrc_t& rh, const __amdgpu_buffer_rsrc_t& rl, unsigned abase, bool poll,
-                   uint4 (&fh)[KQ], uint4 (&fl)[KQ]) {
-    for (unsigned spin = 0;; ++spin) {
-      unsigned any = 0;
-#pragma unroll
-      for (int j = 0; j < KQ; ++j) {
-        fh[j] = load16_sc1(rh, abase + j * 64);
-        fl[j] = load16_sc1(rl, abase + j * 64);
-      }
-#pragma unroll
-      for (int j = 0; j < KQ; ++j)
-        any |= fh[j].x | fh[j].y | fh[j].z | fh[j].w | fl[j].x | fl[j].y | fl[j].z | fl[j].w;
-      if (!poll || !alive || __all((any & 0x40004000u) == 0)) break;
-      if ((spin & 63) == 63 && __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) alive = false;
-      if (spin >= SPIN_LIMIT) {
-        __hip_atomic_store(status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        alive = false;
-      }
-    }
-  };
 
   for (int t = 0; t < T; ++t) {
 #pragma unroll
@@ -550,7 +561,7 @@ __global__ __launch_bounds__(256, 1) void lstm_scan_fwd_split_sent_kernel(const 
       for (int g = 0; g < 4; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
       uint4 ahi[KQ], alo[KQ];
       if (IN && has_in) {      // (the layer below runs ahead: normally there at the first look)
-        fetch(rs_ihi, rs_ilo, abase, true, ahi, alo);
+        split_fetch<KQ>(rs_ihi, rs_ilo, abase, true, alive, status, ahi, alo);
 #pragma unroll
         for (int j = 0; j < (IN ? KQ : 1); ++j) {
           frag16 fh, fl;
@@ -567,7 +578,7 @@ __global__ __launch_bounds__(256, 1) void lstm_scan_fwd_split_sent_kernel(const 
           }
         }
       }
-      fetch(rs_hi, rs_lo, abase, t > 0, ahi, alo);
+      split_fetch<KQ>(rs_hi, rs_lo, abase, t > 0, alive, status, ahi, alo);
 #pragma unroll
       for (int j = 0; j < KQ; ++j) {
         frag16 fh, fl;
@@ -689,27 +700,6 @@ __global__ __launch_bounds__(256, 1) void lstm_scan_fwd_split_sent8_kernel(const
   bool alive = true;                 // (wave-uniform: false once this wave or any other has given up)
   int par = 0;
 
-  // the fragments of one operand, loaded until none of them is a sentinel (`poll` false: loaded once)
-  auto fetch = [&](const __amdgpu_buffer_rsrc_t& rh, const __amdgpu_buffer_rsrc_t& rl, unsigned abase, bool poll,
-                   uint4 (&fh)[KQ], uint4 (&fl)[KQ]) {
-    for (unsigned spin = 0;; ++spin) {
-      unsigned any = 0;
-#pragma unroll
-      for (int j = 0; j < KQ; ++j) {
-        fh[j] = load16_sc1(rh, abase + j * 64);
-        fl[j] = load16_sc1(rl, abase + j * 64);
-      }
-#pragma unroll
-      for (int j = 0; j < KQ; ++j)
-        any |= fh[j].x | fh[j].y | fh[j].z | fh[j].w | fl[j].x | fl[j].y | fl[j].z | fl[j].w;
-      if (!poll || !alive || __all((any & 0x40004000u) == 0)) break;
-      if ((spin & 63) == 63 && __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) alive = false;
-      if (spin >= SPIN_LIMIT) {
-        __hip_atomic_store(status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        alive = false;
-      }
-    }
-  };
 
   for (int t = 0; t < T; ++t) {
 #pragma unroll
@@ -734,7 +724,7 @@ __global__ __launch_bounds__(256, 1) void lstm_scan_fwd_split_sent8_kernel(const
       for (int g = 0; g < 2; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
       uint4 ahi[KQ], alo[KQ];
       if (has_in) {      // (the layer below runs ahead: normally there at the first look)
-        fetch(rs_ihi, rs_ilo, abase, true, ahi, alo);
+        split_fetch<KQ>(rs_ihi, rs_ilo, abase, true, alive, status, ahi, alo);
 #pragma unroll
         for (int j = 0; j < KQ; ++j) {
           frag16 fh, fl;
@@ -751,7 +741,7 @@ __global__ __launch_bounds__(256, 1) void lstm_scan_fwd_split_sent8_kernel(const
           }
         }
       }
-      fetch(rs_hi, rs_lo, abase, t > 0, ahi, alo);
+      split_fetch<KQ>(rs_hi, rs_lo, abase, t > 0, alive, status, ahi, alo);
 #pragma unroll
       for (int j = 0; j < KQ; ++j) {
         frag16 fh, fl;
@@ -1867,57 +1857,63 @@ int kl_launch_scan_fwd_wide(KlScanFwdWide a, hipStream_t stream) {
   return hipGetLastError() == hipSuccess ? 0 : KL_ERR_LAUNCH;
 }
 
+// Grid plan of the split-precision scans: one 256-thread workgroup per CU (the weights fill the register file), `col_tasks`
+// workgroups per row group, at most `cap` row blocks per workgroup.  Sets a.n_rb and a.n_rg; false = not applicable.
+static bool plan_scan_split(KlScanFwdSplit& a, int col_tasks, int cap, int* per_wg) {
+  if (a.B < 1 || a.T < 1) return false;
+  if ((long)(a.T + 1) * a.B * a.W * 2 > 0x7fffffffL) return false;      // 32-bit buffer offsets into the (hi, lo) planes
+  a.n_rb = (a.B + 15) / 16;
+  // (g = 0 where a row group alone is more workgroups than the chip has CUs.  scan_cus() is clamped to 256, and that clamp
+  //  is what refuses col_tasks > 256 here -- the row-group arithmetic of the kernels was laid out for at most 256: a
+  //  change to the clamp has to put that refusal back)
+  int g = scan_cus() / col_tasks;
+  if (g < 1) return false;
+  if (g > a.n_rb) g = a.n_rb;
+  a.n_rg = g;
+  *per_wg = (a.n_rb + g - 1) / g;
+  return *per_wg <= cap;
+}
+
+// the split kernels' own tables: per_wg <= 4 here (KL_SCAN_DISPATCH's <16, 8> arm could never be launched)
+#define KL_SPLIT_CASE(KERNEL, ...) hipLaunchKernelGGL((KERNEL<__VA_ARGS__>), grid, block, 0, stream, a)
+#define KL_SPLIT_ROWS(KERNEL, KS, ...)                                        \
+  do {                                                                        \
+    if (per_wg == 1) KL_SPLIT_CASE(KERNEL, KS, 1, ##__VA_ARGS__);             \
+    else if (per_wg == 2) KL_SPLIT_CASE(KERNEL, KS, 2, ##__VA_ARGS__);        \
+    else KL_SPLIT_CASE(KERNEL, KS, 4, ##__VA_ARGS__);                         \
+  } while (0)
+#define KL_SPLIT_DISPATCH(KERNEL)                                             \
+  do {                                                                        \
+    if (W == 512) KL_SPLIT_ROWS(KERNEL, 16);                                  \
+    else if (W == 256) KL_SPLIT_ROWS(KERNEL, 8);                              \
+    else if (W == 128) KL_SPLIT_ROWS(KERNEL, 4);                              \
+    else KL_SPLIT_ROWS(KERNEL, 2);                                            \
+  } while (0)
+
 // Split-precision inference scan (all layers fused).  KL_ERR_SHAPE = not applicable.
 int kl_launch_scan_fwd_split(KlScanFwdSplit a, hipStream_t stream) {
   const int W = a.W;
+  int per_wg = 0;
   if (W == 1024 && a.units8) {
-    // a.L (one or two) layers from a.l0 as a wavefront, eight units per workgroup, one workgroup per CU
-    if (a.L < 1 || a.L > 2 || !a.sentinel || a.B < 1 || a.T < 1) return KL_ERR_SHAPE;
-    if ((long)(a.T + 1) * a.B * W * 2 > 0x7fffffffL) return KL_ERR_SHAPE;
-    a.n_rb = (a.B + 15) / 16;
-    const int col_tasks = a.L * (W / 8);
-    int g = scan_cus() / col_tasks;
-    if (g < 1) return KL_ERR_SHAPE;
-    if (g > a.n_rb) g = a.n_rb;
-    a.n_rg = g;
-    const int per_wg = (a.n_rb + g - 1) / g;
-    if (per_wg > 2) return KL_ERR_SHAPE;
-    dim3 grid(col_tasks * g), block(256);
-    if (per_wg == 1) hipLaunchKernelGGL((lstm_scan_fwd_split_sent8_kernel<32, 1>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((lstm_scan_fwd_split_sent8_kernel<32, 2>), grid, block, 0, stream, a);
-    return hipGetLastError() == hipSuccess ? 0 : KL_ERR_LAUNCH;
-  }
-  if (W == 1024) {
+    // a.L (one or two) layers from a.l0 as a wavefront, eight units per workgroup, data sentinels only
+    if (a.L < 1 || a.L > 2 || !a.sentinel || !plan_scan_split(a, a.L * (W / 8), 2, &per_wg)) return KL_ERR_SHAPE;
+    dim3 grid(a.L * (W / 8) * a.n_rg), block(256);
+    if (per_wg == 1) KL_SPLIT_CASE(lstm_scan_fwd_split_sent8_kernel, 32, 1);
+    else KL_SPLIT_CASE(lstm_scan_fwd_split_sent8_kernel, 32, 2);
+  } else if (W == 1024) {
     // one layer per launch, the input side precomputed in P1, data sentinels only (the caller's layer-sequential path)
-    if (a.L != 1 || !a.sentinel || a.B < 1 || a.T < 1) return KL_ERR_SHAPE;
-    if ((long)(a.T + 1) * a.B * W * 2 > 0x7fffffffL) return KL_ERR_SHAPE;
-    a.n_rb = (a.B + 15) / 16;
-    int g = scan_cus() / (W / 16);
-    if (g < 1) return KL_ERR_SHAPE;
-    if (g > a.n_rb) g = a.n_rb;
-    a.n_rg = g;
-    const int per_wg = (a.n_rb + g - 1) / g;
-    if (per_wg > 4) return KL_ERR_SHAPE;
-    dim3 grid((W / 16) * g), block(256);
-    if (per_wg == 1) hipLaunchKernelGGL((lstm_scan_fwd_split_sent_kernel<32, 1, false>), grid, block, 0, stream, a);
-    else if (per_wg == 2) hipLaunchKernelGGL((lstm_scan_fwd_split_sent_kernel<32, 2, false>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((lstm_scan_fwd_split_sent_kernel<32, 4, false>), grid, block, 0, stream, a);
-    return hipGetLastError() == hipSuccess ? 0 : KL_ERR_LAUNCH;
+    if (a.L != 1 || !a.sentinel || !plan_scan_split(a, W / 16, 4, &per_wg)) return KL_ERR_SHAPE;
+    dim3 grid((W / 16) * a.n_rg), block(256);
+    KL_SPLIT_ROWS(lstm_scan_fwd_split_sent_kernel, 32, false);
+  } else {
+    if (W != 512 && W != 256 && W != 128 && W != 64) return KL_ERR_SHAPE;
+    if (a.L < 1 || a.L > KL_SCAN_MAXL || !plan_scan_split(a, a.L * (W / 16), 4, &per_wg)) return KL_ERR_SHAPE;
+    dim3 grid(a.L * (W / 16) * a.n_rg), block(256);
+    if (a.sentinel) KL_SPLIT_DISPATCH(lstm_scan_fwd_split_sent_kernel);
+    else KL_SPLIT_DISPATCH(lstm_scan_fwd_split_kernel);
   }
-  if (W != 512 && W != 256 && W != 128 && W != 64) return KL_ERR_SHAPE;
-  if (a.L < 1 || a.L > KL_SCAN_MAXL || a.B < 1 || a.T < 1) return KL_ERR_SHAPE;
-  const int col_tasks = a.L * (W / 16);
-  if (col_tasks > 256) return KL_ERR_SHAPE;
-  if ((long)(a.T + 1) * a.B * W * 2 > 0x7fffffffL) return KL_ERR_SHAPE;
-  a.n_rb = (a.B + 15) / 16;
-  int g = scan_cus() / col_tasks;        // one workgroup per CU (the weights fill the register file)
-  if (g < 1) return KL_ERR_SHAPE;
-  if (g > a.n_rb) g = a.n_rb;
-  a.n_rg = g;
-  const int per_wg = (a.n_rb + g - 1) / g;
-  if (per_wg > 4) return KL_ERR_SHAPE;
-  dim3 grid(col_tasks * g), block(256);
-  if (a.sentinel) KL_SCAN_DISPATCH(lstm_scan_fwd_split_sent_kernel);
-  else KL_SCAN_DISPATCH(lstm_scan_fwd_split_kernel);
   return hipGetLastError() == hipSuccess ? 0 : KL_ERR_LAUNCH;
 }
+#undef KL_SPLIT_CASE
+#undef KL_SPLIT_ROWS
+#undef KL_SPLIT_DISPATCH

@@ -434,6 +434,28 @@ def test_step_batch_bf16_within_1e3():
     assert worst < 1e-3, worst
 
 
+# The cases of test_forward_window_parity / test_forward_window_counter_handoff that exist to reach ONE arm of the split-precision
+# scans' dispatch: (depth, width, B) -> row blocks per workgroup there.  Parity alone would also hold on another arm (or on the
+# launch-per-step kernels, which take what the launcher refuses), so the conditions under which the case reaches its arm are
+# asserted before any work: 256 compute units, the batch in one piece, and the launcher's arithmetic giving the arm.
+SPLIT_ARM_CASES = {(4, 64, 257): 2, (4, 64, 769): 4, (4, 128, 129): 2, (4, 128, 385): 4, (4, 256, 65): 2, (4, 256, 193): 4,
+                   (4, 512, 33): 2, (1, 1024, 65): 2, (1, 1024, 193): 4}
+
+
+def _check_split_arm(lm, depth, width, B):
+    want = SPLIT_ARM_CASES.get((depth, width, B))
+    if want is None:
+        return
+    cus = lm.torch.cuda.get_device_properties(lm.device).multi_processor_count
+    assert cus >= 256, "this case was chosen for 256 compute units (the scans' grid plan clamps there); %d here" % cus
+    assert lm.pwidth == width and lm._rating_groups(B) == [(0, B)]
+    n_rb = (B + 15) // 16
+    if width == 1024:      # one layer per launch; more than two row blocks (not the eight-unit scan), at most sixteen
+        assert 2 < n_rb <= 16
+    g = min(256 // ((1 if width == 1024 else depth) * (width // 16)), n_rb)
+    assert -(-n_rb // g) == want
+
+
 @pytest.mark.parametrize("depth,width,voc,B,T,n_ctx", [(2, 64, 50, 1, 32, 1), (2, 128, 60, 3, 16, 1),
                                                        (1, 128, 40, 1, 64, 1), (2, 512, 256, 2, 24, 1),
                                                        (3, 64, 30, 2, 7, 2),
@@ -451,11 +473,32 @@ def test_step_batch_bf16_within_1e3():
                                                        (6, 128, 30, 5, 9, 1), (9, 64, 20, 2, 6, 2),
                                                        # more streams than the persistent split-precision scan takes in one call
                                                        # (256 at depth 2 / width 512, 128 at depth 3): groups of streams
-                                                       (2, 512, 64, 300, 4, 1), (3, 512, 40, 270, 3, 2)])
+                                                       (2, 512, 64, 300, 4, 1), (3, 512, 40, 270, 3, 2),
+                                                       # every row-blocks-per-workgroup arm of the split-precision scans'
+                                                       # dispatch (the <width / 32, 2 or 4> instantiations), at the smallest
+                                                       # stream count that reaches it.  The counts ASSUME 256 CUs (on fewer the
+                                                       # arms move): kl_launch_scan_fwd_split has row groups g = 256 / (depth *
+                                                       # width / 16), row blocks n = ceil(B / 16) and ceil(n / g) of them per
+                                                       # workgroup; HipLM._rating_groups keeps B <= 64 g streams in one piece.
+                                                       #   width 64, depth 4: g = 16 (one piece up to 1024 streams);
+                                                       #     B = 257 -> n = 17 -> 2;  B = 769 -> n = 49 -> 4
+                                                       (4, 64, 30, 257, 3, 1), (4, 64, 30, 769, 3, 1),
+                                                       #   width 128, depth 4: g = 8 (512);  B = 129 -> 9 -> 2;  385 -> 25 -> 4
+                                                       (4, 128, 30, 129, 3, 1), (4, 128, 30, 385, 3, 1),
+                                                       #   width 256, depth 4: g = 4 (256);  B = 65 -> 5 -> 2;  193 -> 13 -> 4
+                                                       (4, 256, 30, 65, 3, 1), (4, 256, 30, 193, 3, 1),
+                                                       #   width 512, depth 4: g = 2 (128);  B = 33 -> 3 -> 2  (4: the 200-stream
+                                                       #   case above, depth 2: g = 4, n = 13)
+                                                       (4, 512, 30, 33, 3, 1),
+                                                       #   width 1024, one layer per launch without input weights: g = 256 / 64
+                                                       #   = 4 (256); more than two row blocks, so not the eight-unit scan, and at
+                                                       #   most 16, fwd_split_layers' limit;  B = 65 -> 5 -> 2;  193 -> 13 -> 4
+                                                       (1, 1024, 30, 65, 3, 1), (1, 1024, 30, 193, 3, 1)])
 def test_forward_window_parity(depth, width, voc, B, T, n_ctx):
     """F1-F6 stateful windows (rating.py:490, 516): two consecutive windows carry state."""
     from ocrd_keraslm_amd.lib import hipabi
     cfg, w, lm = make_model(depth, width, voc, n_ctx)
+    _check_split_arm(lm, depth, width, B)
     lm.set_weights(w, hipabi.KL_PREC_SPLIT)
     lm.reset_states(B)
     rng = np.random.default_rng(9)
@@ -485,7 +528,11 @@ def test_forward_window_width_1024_layer_by_layer(monkeypatch):
     test_forward_window_parity(4, 1024, 64, 2, 6, 2)
 
 
-@pytest.mark.parametrize("depth,width,voc,B,T,n_ctx", [(3, 256, 30, 40, 9, 2), (2, 512, 256, 1, 64, 1)])
+@pytest.mark.parametrize("depth,width,voc,B,T,n_ctx", [(3, 256, 30, 40, 9, 2), (2, 512, 256, 1, 64, 1),
+                                                       # two and four row blocks per workgroup (the arithmetic: see the
+                                                       # cases of test_forward_window_parity; 256 CUs assumed)
+                                                       (4, 64, 30, 257, 3, 1), (4, 64, 30, 769, 3, 1),
+                                                       (4, 256, 30, 65, 3, 1), (4, 256, 30, 193, 3, 1)])
 def test_forward_window_counter_handoff(monkeypatch, depth, width, voc, B, T, n_ctx):
     """the split-precision scan with its counter hand-off (KL_SPLIT_SENTINEL=0; the default hands over by data sentinels)"""
     monkeypatch.setenv("KL_SPLIT_SENTINEL", "0")
