@@ -18,6 +18,7 @@
  *   ... with alternatives, and the suspect positions picked out  kl_rate_window_alts_bulk, kl_rate_scatter_alts, kl_rate_select
  *   ... and the suspects' alternatives rescored against what follows  kl_variant_windows (rows for kl_rate_window(_bulk))
  *   ... with a lost character inserted in front of the suspect         kl_edit_windows
+ *   ... for caller-supplied replacements of spans of the text          kl_span_windows, kl_span_pick
  *   model.predict_on_batch, stateful (1,1) step, :566        kl_forward_window with T = 1
  *   model.predict_on_batch, incremental + states, :631       kl_step_batch
  *   ... once per character of a lattice edge, :796-851       kl_walk_batch_host (all characters of all hypotheses, one call)
@@ -287,6 +288,53 @@ int kl_variant_windows(const int32_t* corpus, size_t n_corpus, const int64_t* of
 int kl_edit_windows(const int32_t* corpus, size_t n_corpus, const int64_t* offsets, int n_texts, const int32_t* text_ctx,
                     int n_ctx, const int64_t* sel_pos, const int32_t* sel_alt_id, int S, int K, int left, int ahead, int deletions,
                     int insertions, int T, int32_t* idx, int32_t* ctx, int32_t* tgt, int32_t* valid, void* stream);
+
+/* Hypothesis windows of spans with caller-supplied replacements: the general form of kl_edit_windows, for readings that come
+ * from outside the model (a second OCR engine, a lexicon, a table of confusions).  No handle.  corpus, offsets and text_ctx as
+ * in kl_edit_windows.  Span s < S replaces the D = span_len[s] (device int32 [S], D >= 0; 0: an insertion in front of g)
+ * written characters at corpus position g = span_start[s] (device int64 [S]) of text i = span_text[s] (device int32 [S]); it
+ * owns the candidates span_first[s] .. span_first[s+1]-1 (device int64 [S + 1], ascending, span_first[0] == 0,
+ * span_first[S] == C; a span may own none), and candidate c is the id string r = pool[cand_off[c] .. cand_off[c+1]-1] (pool
+ * device int32 [n_pool], NULL only with n_pool == 0; cand_off device int64 [C + 1], ascending) of any length m >= 0 (0: the
+ * span dropped).  Rows are numbered over all spans, N = S + C: span s has rows span_first[s] + s .. span_first[s+1] + s, the
+ * first the text as written (r = w = x[g .. g+D-1]), then its candidates in order.  A call builds rows row0 .. row0 + rows - 1
+ * into outputs of `rows` rows (the caller takes the row space in chunks); a row's span is found by binary search over
+ * span_first[s] + s.  With n_read = min(n_corpus, offsets[n_texts]), M = max_len, L = min(left, g - offsets[i]) and
+ * A = min(ahead, offsets[i+1] - g - D):
+ *   span base       0 <= i < n_texts, 0 <= D <= M, offsets[i] <= g, g + D <= min(offsets[i+1], n_read), L >= 1
+ *   written row     valid iff the base holds and D + A >= 1
+ *   candidate row   valid iff the written row is, 0 <= m <= M, every id of r is >= 0, m + A >= 1 and r != w as id strings
+ *                   (two different unmapped characters are both id 0 and count as equal); a candidate whose range does not
+ *                   lie inside the pool, or whose index is not in [0, C), is invalid
+ * A valid row has q = x[g-L .. g-1], r, x[g+D .. g+D+A-1], len = L + m + A, and kl_variant_windows' rule per word:
+ * idx[b][t] = q[t] for t < len - 1, else 0;  tgt[b][t] = q[t+1] for L - 1 <= t < len - 1, else -1;  ctx[b][t][c] =
+ * text_ctx[i][c] for t < len - 1, else 0;  valid[b] = 1  -- a window from a zero state over it predicts r and the A characters
+ * after the span, and nothing else.  An invalid row is the dummy stream: idx 0, ctx 0, tgt -1, valid[b] = 0.  idx, tgt (device
+ * int32 [rows][T]), ctx (device int32 [rows][T][n_ctx]) and valid (device int32 [rows]) are written in every word, nothing
+ * outside them is touched; a corpus position outside [0, n_read) reads as 0 without touching memory.  One workgroup per row,
+ * one launch on `stream`, no atomics, no workgroup waits for another.  With D = 1 and the candidates [a_0] .. [a_K-1], [],
+ * [a_0, w] .. [a_K-1, w] the rows are kl_edit_windows(deletions = 1, insertions = 1)'s, word for word.
+ * KL_ERR_ARG, before any launch, for null pointers (ctx and text_ctx may be null only with n_ctx == 0, pool only with
+ * n_pool == 0), S, n_texts or rows < 1, C < 0, row0 < 0, row0 + rows > S + C, left < 1, ahead < 0, max_len outside
+ * 1 .. KL_SPAN_LEN_MAX, T < left + ahead + max_len - 1 or T > 1024, n_ctx outside 0 .. 8, rows > 2^22, n_corpus, n_pool or
+ * C > 2^40, misaligned pointers (4 bytes; offsets, span_start, span_first and cand_off 8). */
+#define KL_SPAN_LEN_MAX 64
+int kl_span_windows(const int32_t* corpus, size_t n_corpus, const int64_t* offsets, int n_texts, const int32_t* text_ctx,
+                    int n_ctx, const int32_t* span_text, const int64_t* span_start, const int32_t* span_len,
+                    const int64_t* span_first, int S, const int32_t* pool, size_t n_pool, const int64_t* cand_off, int64_t C,
+                    int64_t row0, int rows, int left, int ahead, int max_len, int T, int32_t* idx, int32_t* ctx, int32_t* tgt,
+                    int32_t* valid, void* stream);
+
+/* The choice among every span's candidates, on the device.  cost (device f64 [S + C]) and valid (device int32 [S + C]) per row
+ * of kl_span_windows' numbering (the rows' bits; what kl_span_windows said), span_first as there.  best[s] (device int32 [S])
+ * is the index j within the span's candidates of the valid candidate of least cost, the smallest j among equal costs (a NaN
+ * cost is never chosen); gain[s] (device f64 [S]) = cost[written] - cost[best].  best = -1 and gain = 0.0 where the written
+ * row is invalid, where no candidate is valid, or where !(gain >= min_gain).  cost_out (device f64 [S + C], may be NULL, may
+ * be cost itself) receives cost with +inf where the row is invalid.  One wave per span, one launch on `stream`, a fixed order
+ * of reduction: two calls on the same input agree bit for bit.  KL_ERR_ARG, before the launch, for null pointers (but
+ * cost_out), S < 1, C < 0 or > 2^40, misaligned pointers (valid and best 4 bytes, the others 8). */
+int kl_span_pick(const double* cost, const int32_t* valid, const int64_t* span_first, int S, int64_t C, double min_gain,
+                 int32_t* best, double* gain, double* cost_out, void* stream);
 
 /* One training batch, forward + backward (rating.py:292-298 -> train_on_batch):
  * writes the gradient of (mean CE + embedding regularisers, rating.py:187-246)

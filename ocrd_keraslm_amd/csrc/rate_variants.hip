@@ -11,42 +11,15 @@
 // per word).  An inserted alternative sits in front of the written character: q is one id longer, and T >= left + ahead + 1
 // is required.  q (at most left + 1 + insertions + ahead <= T + 1 ids) comes in as lane-consecutive dwords and is parked in
 // LDS; every thread then owns four consecutive output positions and stores them as one 16-byte word, single dwords in front of the
-// first 16-byte boundary of a row and behind its last whole group (the rows of assemble.hip, whose emit_row this repeats).
+// first 16-byte boundary of a row and behind its last whole group (emit_row of kl_emit_row.h, as the rows of assemble.hip).
 // An invalid row leaves as a dummy stream (idx 0, ctx 0, tgt -1).  Every word of the four outputs is written by exactly one
 // thread of one workgroup: no atomics, no workgroup waits for another, nothing depends on scheduling.  Corpus addresses are
 // 64-bit; a position outside [0, min(n_corpus, offsets[n_texts])) reads as 0 without touching memory.  No model: no handle.
 #include "keraslm_hip.h"
 #include "kl_common.h"
+#include "kl_emit_row.h"
 
 namespace {
-
-constexpr int KL_VAR_MAX_T = 1024;
-constexpr int KL_VAR_MAX_CTX = 8;
-constexpr long long KL_VAR_MAX_ROWS = 1ll << 22;      // (rows * 256 threads stay below 2^32)
-constexpr int KL_VAR_MAX_Q = KL_VAR_MAX_T + 4;        // ids of the staging array
-// the longest q: left + 2 + ahead ids with an insertion, left + ahead + 1 <= T <= KL_VAR_MAX_T
-static_assert(KL_VAR_MAX_T + 1 <= KL_VAR_MAX_Q, "the staging array holds the longest hypothesis");
-
-// out[0 .. n): four consecutive positions per thread as one 16-byte store from the first 16-byte boundary on, single
-// dwords in front of it and behind the last whole group
-template <class F>
-__device__ __forceinline__ void emit_row(int32_t* __restrict__ out, int n, F value) {
-  const int lead = (int)(((16u - (unsigned)(reinterpret_cast<uintptr_t>(out) & 15u)) & 15u) >> 2);
-  if ((int)threadIdx.x < lead && (int)threadIdx.x < n) out[threadIdx.x] = value((int)threadIdx.x);
-  for (int p = lead + 4 * (int)threadIdx.x; p < n; p += 4 * (int)blockDim.x) {
-    if (p + 4 <= n) {
-      int4 v;
-      v.x = value(p);
-      v.y = value(p + 1);
-      v.z = value(p + 2);
-      v.w = value(p + 3);
-      *reinterpret_cast<int4*>(out + p) = v;
-    } else {
-      for (int k = 0; k < 4; ++k)
-        if (p + k < n) out[p + k] = value(p + k);
-    }
-  }
-}
 
 __global__ void __launch_bounds__(256) variant_windows_kernel(
     const int32_t* __restrict__ corpus, long long n_corpus, const long long* __restrict__ offsets, int n_texts,

@@ -623,6 +623,69 @@ class HipLM:
                 _ptr(ctx) if n_ctx else None, _ptr(tgt), _ptr(valid), self._stream()), "kl_edit_windows")
         return idx, ctx, tgt, valid
 
+    def span_windows(self, corpus_d, offsets_d, text_ctx_d, span_text_d, span_start_d, span_len_d, span_first_d, pool_d,
+                     cand_off_d, row0, rows, left, ahead, max_len, T):
+        """kl_span_windows: hypothesis rows row0 .. row0 + rows - 1 of S spans with caller-supplied replacements, built on the
+        device in one launch.  corpus_d int32 [n], offsets_d int64 [n_texts + 1] and text_ctx_d int32 [n_texts, n_ctx] (None
+        without contexts) as in `variant_windows`; span_text_d int32 [S], span_start_d int64 [S], span_len_d int32 [S],
+        span_first_d int64 [S + 1], pool_d int32 [n_pool] and cand_off_d int64 [C + 1] -- all DEVICE tensors; S + C is the
+        number of rows there are.  Returns the DEVICE tensors (idx [rows, T], ctx [rows, T, n_ctx], tgt [rows, T], valid
+        [rows]) int32: what `ratebulk.span_windows_host` states.  hipabi.KlError for what the entry point rejects.  No
+        synchronisation (span_first_d[S] == C is the caller's word)."""
+        torch = self.torch
+        n_ctx = 0 if text_ctx_d is None else int(text_ctx_d.shape[-1])
+        tensors = [corpus_d, offsets_d, span_text_d, span_start_d, span_len_d, span_first_d, pool_d, cand_off_d]
+        kinds = [torch.int32, torch.int64, torch.int32, torch.int64, torch.int32, torch.int64, torch.int32, torch.int64]
+        if n_ctx:
+            tensors.append(text_ctx_d)
+            kinds.append(torch.int32)
+        if (any(t is None for t in tensors) or [t.dtype for t in tensors] != kinds or any(t.dim() != 1 for t in tensors[:8])
+                or span_first_d.numel() < 2 or cand_off_d.numel() < 1 or offsets_d.numel() < 2
+                or not span_text_d.numel() == span_start_d.numel() == span_len_d.numel() == span_first_d.numel() - 1
+                or (n_ctx and tuple(text_ctx_d.shape) != (offsets_d.numel() - 1, n_ctx))
+                or not all(t.is_contiguous() and t.is_cuda for t in tensors)):
+            raise hipabi.KlError("span_windows: corpus int32 [n], offsets int64 [n_texts + 1], text_ctx int32 [n_texts, n_ctx], "
+                                 "span_text int32 [S], span_start int64 [S], span_len int32 [S], span_first int64 [S + 1], "
+                                 "pool int32 [n_pool], cand_off int64 [C + 1], contiguous, on the device")
+        n_texts = offsets_d.numel() - 1
+        S, C = int(span_text_d.numel()), int(cand_off_d.numel()) - 1
+        row0, rows, left, ahead, max_len, T = int(row0), int(rows), int(left), int(ahead), int(max_len), int(T)
+        if rows < 1 or T < 1 or not -2 ** 63 <= row0 < 2 ** 63:
+            raise hipabi.KlError("span_windows: rows >= 1, T >= 1 (got %d, %d)" % (rows, T))
+        with self._launch():
+            idx = torch.empty((rows, T), dtype=torch.int32, device=self.device)
+            tgt = torch.empty((rows, T), dtype=torch.int32, device=self.device)
+            ctx = torch.empty((rows, T, n_ctx), dtype=torch.int32, device=self.device)
+            valid = torch.empty(rows, dtype=torch.int32, device=self.device)
+            hipabi.check(self.lib.kl_span_windows(
+                _ptr(corpus_d), corpus_d.numel(), _ptr(offsets_d), n_texts, _ptr(text_ctx_d) if n_ctx else None, n_ctx,
+                _ptr(span_text_d), _ptr(span_start_d), _ptr(span_len_d), _ptr(span_first_d), S,
+                _ptr(pool_d) if pool_d.numel() else None, pool_d.numel(), _ptr(cand_off_d), C, row0, rows, left, ahead, max_len,
+                T, _ptr(idx), _ptr(ctx) if n_ctx else None, _ptr(tgt), _ptr(valid), self._stream()), "kl_span_windows")
+        return idx, ctx, tgt, valid
+
+    def span_pick(self, cost_d, valid_d, span_first_d, min_gain, want_costs=True):
+        """kl_span_pick: the choice among every span's candidates, on the device.  cost_d f64 [S + C] and valid_d int32 [S + C]
+        per row of `span_windows`' numbering, span_first_d int64 [S + 1] -- DEVICE tensors.  Returns the DEVICE tensors (best
+        int32 [S], gain f64 [S], cost with +inf where invalid f64 [S + C] -- None without want_costs): what
+        `ratebulk.span_pick_host` states.  No synchronisation."""
+        torch = self.torch
+        tensors = (cost_d, valid_d, span_first_d)
+        if (any(t is None for t in tensors) or [t.dtype for t in tensors] != [torch.float64, torch.int32, torch.int64]
+                or any(t.dim() != 1 for t in tensors) or span_first_d.numel() < 2 or cost_d.numel() != valid_d.numel()
+                or cost_d.numel() < span_first_d.numel() - 1 or not all(t.is_contiguous() and t.is_cuda for t in tensors)):
+            raise hipabi.KlError("span_pick: cost f64 [S + C], valid int32 [S + C], span_first int64 [S + 1], contiguous, on the "
+                                 "device")
+        S = int(span_first_d.numel()) - 1
+        C = int(cost_d.numel()) - S
+        with self._launch():
+            best = torch.empty(S, dtype=torch.int32, device=self.device)
+            gain = torch.empty(S, dtype=torch.float64, device=self.device)
+            out = torch.empty(S + C, dtype=torch.float64, device=self.device) if want_costs else None
+            hipabi.check(self.lib.kl_span_pick(_ptr(cost_d), _ptr(valid_d), _ptr(span_first_d), S, C, float(min_gain), _ptr(best),
+                                               _ptr(gain), _ptr(out), self._stream()), "kl_span_pick")
+        return best, gain, out
+
     def rate_bits_take_all(self):
         """the accumulated bits of ALL streams as a DEVICE tensor (f64 [B]), the accumulators zeroed; no synchronisation"""
         with self._launch():

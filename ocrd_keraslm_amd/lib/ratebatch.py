@@ -199,6 +199,81 @@ class Corrections(Suspects):
         return "".join(chars)
 
 
+class Rescored(object):
+    """One text's share of `Rater.rescore`: its m spans in the order they were given and what rating the caller's candidates
+    against the text around them proposes.  Span j is text[starts[j]:ends[j]] and owns candidates[first[j]:first[j + 1]]:
+
+    starts, ends  [m] i64          the span in the normalised text (ends[j] == starts[j]: an insertion in front of starts[j])
+    first         [m + 1] i64      where a span's candidates begin
+    candidates    [first[m]] str   the (normalised) replacement strings, "" drops the span
+    cost0         [m] f64          bits of the text as written over the span and the characters after it (+inf: the span has
+                                   no prediction to be held against); None without want_costs
+    cost          [first[m]] f64   the same with the candidate in place of the span (+inf: no such hypothesis); None without
+                                   want_costs
+    best          [m] i32          the index within the span's candidates of the one proposed, -1: none
+    gain          [m] f64          bits saved by the proposal against the text as written (0.0 without a proposal)
+    """
+
+    def __init__(self, starts, ends, first, candidates, cost0, cost, best, gain):
+        self.starts, self.ends, self.first, self.candidates = starts, ends, first, candidates
+        self.cost0, self.cost, self.best, self.gain = cost0, cost, best, gain
+
+    def __len__(self):
+        return len(self.starts)
+
+    def proposals(self):
+        """per span the string proposed in its place, [m]: None for no proposal, "" for dropping the span"""
+        return [None if b < 0 else self.candidates[int(a) + int(b)] for a, b in zip(self.first[:-1], self.best)]
+
+    def apply(self, text):
+        """the (normalised) text with the kept proposals written: they are taken in descending gain (ties: the earlier start,
+        then the order given), one that overlaps a span already taken is skipped -- [a, b) and [c, d) overlap where a < d and
+        c < b, and two insertions at the same place do --, and the taken ones are written from right to left so that
+        positions stay true"""
+        new = self.proposals()
+        order = sorted((j for j in range(len(new)) if new[j] is not None),
+                       key=lambda j: (-float(self.gain[j]), int(self.starts[j]), j))
+        taken = []
+        for j in order:
+            a, b = int(self.starts[j]), int(self.ends[j])
+            if not 0 <= a <= b <= len(text):
+                continue
+            if any((a < d and c < b) or (a == b == c == d) for c, d, _ in taken):
+                continue
+            taken.append((a, b, new[j]))
+        chars = list(text)
+        for a, b, string in sorted(taken, key=lambda e: (e[0], e[1]), reverse=True):
+            chars[a:b] = list(string)
+        return "".join(chars)
+
+
+def confusion_edits(texts, rules, at=None):
+    """Edits for `Rater.rescore` from a table of known confusions: rules is a list of (source, [replacements]) with a non-empty
+    source; one edit (i, start, end, replacements) per occurrence of a source in the NFC-normalised texts[i], overlapping
+    occurrences included, ordered by text, start and rule.  Sources and replacements are normalised too; "" among the
+    replacements drops the source.  With `at` (per text an array of positions, e.g. `Suspects.positions`) only occurrences whose
+    span holds one of these positions are kept.  Host only."""
+    rules = [(windows.normalize(source), [windows.normalize(r) for r in replacements]) for source, replacements in rules]
+    if any(not source for source, _ in rules):
+        raise ValueError("confusion_edits: a rule needs a non-empty source")
+    if at is not None and len(at) != len(texts):
+        raise ValueError("confusion_edits: one array of positions per text")
+    edits = []
+    for i, text in enumerate(texts):
+        text = windows.normalize(text)
+        marks = None if at is None else np.sort(np.asarray(at[i], dtype=np.int64).reshape(-1))
+        here = []
+        for n, (source, replacements) in enumerate(rules):
+            start = text.find(source)
+            while start >= 0:
+                end = start + len(source)
+                if marks is None or np.searchsorted(marks, start, side="left") < np.searchsorted(marks, end, side="left"):
+                    here.append((start, n, end, replacements))
+                start = text.find(source, start + 1)
+        edits += [(i, start, end, list(replacements)) for start, n, end, replacements in sorted(here, key=lambda e: e[:2])]
+    return edits
+
+
 def alternatives_of(full, y, k):
     """What the model expected instead, from whole distributions: full [B,T,V] (probabilities, or logits -- any values that
     order the vocabulary), y [B,T] targets, k >= 1.  Within a position the ids are ordered by (value descending, id

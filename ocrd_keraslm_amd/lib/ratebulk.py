@@ -20,7 +20,9 @@ Rules of the plan:
 kl_rate_text_bits compute; `scatter_alts_host` and `select_host` what kl_rate_scatter_alts and kl_rate_select do for rating
 with alternatives (`Rater.rate_alternatives(precision="bf16")`, `Rater.suspects`); `variant_windows_host` what
 kl_variant_windows / kl_edit_windows make of the suspects for `Rater.corrections`, and `variant_pick_host` is the choice among a suspect's
-variants (numpy on every path: S * R doubles).  numpy only: the plan is built and tested without an engine.
+variants (numpy on every path: S * R doubles); `span_windows_host` and `span_pick_host` what kl_span_windows and kl_span_pick
+make of spans with caller-supplied replacements for `Rater.rescore`.  numpy only: the plan is built and tested without an
+engine.
 """
 from __future__ import annotations
 
@@ -291,3 +293,154 @@ def variant_pick_host(cost, valid):
         rows = np.nonzero(any_valid)[0]
         gain[rows] = cost[rows, 0] - cost[rows, best[rows]]
     return cost, best, gain
+
+
+SPAN_LEN_MAX = 64      # ids of a span and of a candidate at most (KL_SPAN_LEN_MAX of the C ABI)
+
+
+def span_windows_host(corpus, offsets, text_ctx, span_text, span_start, span_len, span_first, pool, cand_off, row0, rows, left,
+                      ahead, max_len, T):
+    """what kl_span_windows makes of S spans with caller-supplied replacements: span s replaces the D = span_len[s] >= 0 written
+    characters at corpus position g = span_start[s] of text i = span_text[s] (D = 0: an insertion in front of g) and owns the
+    candidates span_first[s] .. span_first[s+1]-1 (span_first [S + 1] ascending from 0 to C; a span may own none); candidate c
+    is the id string r = pool[cand_off[c] .. cand_off[c+1]-1] (cand_off [C + 1] ascending) of any length m >= 0 (0: the span
+    dropped).  Rows are numbered over all spans, N = S + C: span s has rows span_first[s] + s .. span_first[s+1] + s, the first
+    the text as written (r = w = x[g .. g+D-1]), then its candidates in order; the call builds rows row0 .. row0 + rows - 1.
+    With n_read = min(len(corpus), offsets[-1]), M = max_len, L = min(left, g - offsets[i]), A = min(ahead, offsets[i+1] - g - D):
+      span base      0 <= i < n_texts, 0 <= D <= M, offsets[i] <= g, g + D <= min(offsets[i+1], n_read), L >= 1
+      written row    valid iff the base holds and D + A >= 1
+      candidate row  valid iff the written row is, 0 <= m <= M, every id of r is >= 0, m + A >= 1 and r != w as id strings (two
+                     different unmapped characters are both id 0 and count as equal); a candidate whose range does not lie
+                     inside the pool, or whose index is not in [0, C), is invalid
+    A valid row has q = x[g-L .. g-1], r, x[g+D .. g+D+A-1], len = L + m + A, and `variant_windows_host`'s rule per word:
+    idx[t] = q[t] for t < len - 1, else 0; tgt[t] = q[t+1] for L - 1 <= t < len - 1, else -1; ctx[t] = text_ctx[i] for
+    t < len - 1, else 0.  An invalid row is a dummy stream (idx 0, ctx 0, tgt -1).  text_ctx: [n_texts, n_ctx] (None: no
+    contexts).  Positions outside [0, n_read) read as 0.  1 <= M <= 64, left + ahead + M - 1 <= T <= 1024.
+    Returns (idx [rows, T], ctx [rows, T, n_ctx], tgt [rows, T], valid [rows]) int32."""
+    corpus = np.asarray(corpus, dtype=np.int32).reshape(-1)
+    offsets = np.asarray(offsets, dtype=np.int64).reshape(-1)
+    span_text = np.asarray(span_text, dtype=np.int64).reshape(-1)
+    span_start = np.asarray(span_start, dtype=np.int64).reshape(-1)
+    span_len = np.asarray(span_len, dtype=np.int64).reshape(-1)
+    span_first = np.asarray(span_first, dtype=np.int64).reshape(-1)
+    pool = np.asarray(pool, dtype=np.int32).reshape(-1)
+    cand_off = np.asarray(cand_off, dtype=np.int64).reshape(-1)
+    S, C = len(span_first) - 1, len(cand_off) - 1
+    row0, rows, left, ahead, M, T = int(row0), int(rows), int(left), int(ahead), int(max_len), int(T)
+    n_texts = len(offsets) - 1
+    if (S < 1 or C < 0 or n_texts < 1 or not len(span_text) == len(span_start) == len(span_len) == S or rows < 1 or row0 < 0
+            or row0 + rows > S + C or left < 1 or ahead < 0 or not 1 <= M <= SPAN_LEN_MAX
+            or not left + ahead + M - 1 <= T <= 1024):
+        raise ValueError("span_windows_host: S, n_texts, rows >= 1, 0 <= row0, row0 + rows <= S + C, left >= 1, ahead >= 0, "
+                         "1 <= max_len <= 64, left + ahead + max_len - 1 <= T <= 1024")
+    text_ctx = np.zeros((n_texts, 0), dtype=np.int32) if text_ctx is None else np.asarray(text_ctx, dtype=np.int32)
+    text_ctx = text_ctx.reshape(n_texts, -1)
+    n_read = min(len(corpus), int(offsets[-1]))
+
+    def read(at):
+        ok = (at >= 0) & (at < n_read)
+        return np.where(ok, corpus[np.where(ok, at, 0)] if len(corpus) else 0, 0).astype(np.int32)
+
+    # the span of row b: the last s with span_first[s] + s <= b; v = 0 is the text as written, else candidate v - 1 of the span
+    b = row0 + np.arange(rows, dtype=np.int64)
+    keys = span_first[:S] + np.arange(S, dtype=np.int64)
+    s = np.searchsorted(keys, b, side="right") - 1
+    found = s >= 0
+    s = np.maximum(s, 0)
+    v = b - keys[s]
+    written = v == 0
+    i, g, D = span_text[s], span_start[s], span_len[s]
+    ok = found & (i >= 0) & (i < n_texts) & (D >= 0) & (D <= M)
+    i = np.clip(i, 0, n_texts - 1)
+    o0, o1 = offsets[i], offsets[i + 1]
+    lim = np.minimum(o1, n_read)
+    ok &= (o0 <= g) & (g <= lim)
+    ok &= D <= np.where(ok, lim - g, -1)
+    L = np.where(ok, np.minimum(left, g - o0), 0)
+    A = np.where(ok, np.minimum(ahead, o1 - g - D), 0)
+    ok &= (L >= 1) & (D + A >= 1)
+    # the candidate's range in the pool
+    c = span_first[s] + v - 1
+    known = ~written & (c >= 0) & (c < C)
+    c = np.clip(c, 0, max(C - 1, 0))
+    ends = np.concatenate([cand_off, cand_off[-1:]])
+    lo, hi = ends[c], ends[c + 1]
+    known &= (lo >= 0) & (hi >= lo) & (hi - lo <= M) & (hi <= len(pool))
+    m = np.where(written, D, np.where(known, hi - lo, 0))
+    ok &= written | (known & (m + A >= 1))
+    m = np.where(ok, m, 0)
+    # r [rows, M]: the written characters, or the candidate's ids
+    k = np.arange(M, dtype=np.int64)[None, :]
+    w = read(g[:, None] + k)
+    at = np.clip(lo[:, None] + k, 0, max(len(pool) - 1, 0))
+    own = pool[at] if len(pool) else np.zeros((rows, M), dtype=np.int32)
+    r = np.where(written[:, None], w, own)
+    inside = k < m[:, None]
+    negative = (inside & (r < 0)).any(axis=1)
+    differs = (m != D) | (inside & (r != w)).any(axis=1)
+    ok &= written | (~negative & differs)
+    m = np.where(ok, m, 0)
+    # q [rows, T + 1]
+    t = np.arange(T + 1, dtype=np.int64)[None, :]
+    L2, m2, g2, D2 = L[:, None], m[:, None], g[:, None], D[:, None]
+    length = np.where(ok, L + m + A, 0)[:, None]
+    q = np.where(t < L2, read(g2 - L2 + t), read(g2 + D2 + t - L2 - m2))
+    q = np.where((t >= L2) & (t < L2 + m2), np.take_along_axis(r, np.clip(t - L2, 0, M - 1), axis=1), q)
+    fed = ok[:, None] & (t[:, :T] < length - 1)
+    idx = np.where(fed, q[:, :T], 0).astype(np.int32)
+    tgt = np.where(fed & (t[:, :T] >= L2 - 1), q[:, 1:], -1).astype(np.int32)
+    ctx = (fed[:, :, None] * text_ctx[i][:, None, :]).astype(np.int32)
+    return idx, ctx, tgt, ok.astype(np.int32)
+
+
+def span_pick_host(cost, valid, span_first, min_gain):
+    """what kl_span_pick computes: cost [S + C] f64 and valid [S + C] per row of `span_windows_host`'s numbering, span_first
+    [S + 1].  Returns (best [S] int32, gain [S] f64, cost with +inf where invalid): best is the index j within the span's
+    candidates of the valid candidate of least cost, the smallest j among equal costs (a NaN cost is never chosen);
+    gain = cost[written] - cost[best]; best = -1 and gain = 0.0 where the written row is invalid, where no candidate is valid,
+    or where not gain >= min_gain -- `variant_pick_host`'s rule plus `Rater.corrections`' drop rule, generic in the count."""
+    cost = np.array(cost, dtype=np.float64, copy=True).reshape(-1)
+    valid = np.asarray(valid).reshape(-1) != 0
+    span_first = np.asarray(span_first, dtype=np.int64).reshape(-1)
+    S = len(span_first) - 1
+    C = int(span_first[-1]) if S >= 0 else 0
+    if S < 1 or span_first[0] != 0 or (np.diff(span_first) < 0).any() or len(cost) != S + C or len(valid) != S + C:
+        raise ValueError("span_pick_host: span_first [S + 1] ascending from 0 to C, cost and valid [S + C]")
+    count = np.diff(span_first)
+    written = span_first[:S] + np.arange(S, dtype=np.int64)
+    best = np.full(S, -1, dtype=np.int32)
+    gain = np.zeros(S, dtype=np.float64)
+    if C:
+        sid = np.repeat(np.arange(S, dtype=np.int64), count)
+        j = np.arange(C, dtype=np.int64) - span_first[sid]
+        row = written[sid] + 1 + j
+        out = ~(valid[row] & ~np.isnan(cost[row]))
+        key = np.where(out, 0.0, cost[row])
+        order = np.lexsort((j, key, out, sid))      # per span: the candidates that may be chosen first, by (cost, j)
+        has = np.nonzero(count > 0)[0]
+        first = order[span_first[has]]
+        some = ~out[first] & valid[written[has]]
+        has, first = has[some], first[some]
+        with np.errstate(invalid="ignore"):
+            saved = cost[written[has]] - cost[row[first]]
+            keep = saved >= float(min_gain)
+        best[has[keep]] = j[first[keep]]
+        gain[has[keep]] = saved[keep]
+    cost[~valid] = np.inf
+    return best, gain, cost
+
+
+def span_chunks(span_first, streams):
+    """the row space of S spans (`span_windows_host`'s numbering) cut for `Rater.rescore`: consecutive whole spans while the
+    chunk has at most `streams` rows, a span with more rows than that a chunk of its own.  Returns [(row0, row1)]."""
+    span_first = np.asarray(span_first, dtype=np.int64).reshape(-1)
+    S = len(span_first) - 1
+    keys = span_first + np.arange(S + 1, dtype=np.int64)      # the first row of every span, and the number of rows
+    streams = max(1, int(streams))
+    out = []
+    a = 0
+    while a < S:
+        b = max(a + 1, int(np.searchsorted(keys, keys[a] + streams, side="right")) - 1)
+        out.append((int(keys[a]), int(keys[b])))
+        a = b
+    return out

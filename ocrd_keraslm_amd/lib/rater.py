@@ -1192,6 +1192,146 @@ class Rater(object):
         return [ratebatch.Corrections(*one)
                 for one in self._selection_per_text(list(sel) + [cost, best_id, gain, best_op], offsets)], bits
 
+    def rescore(self, texts, edits, contexts=None, streams=1024, left=64, ahead=8, min_gain=1.0, precision="bf16", want_costs=True):
+        '''Does a text read better with one of the caller's replacements for a span of it?  `corrections` for readings that come
+        from outside the model -- a second OCR engine, a lexicon, a table of confusions (`ratebatch.confusion_edits`) --, many
+        characters for many.  edits is a sequence of (i, start, end, candidates): [start, end) is a span of the NFC-normalised
+        texts[i] (end == start: an insertion in front of start), candidates a list of replacement strings, normalised by the
+        call and encoded with the rater's mapping; "" drops the span.  Returns `found`, one ratebatch.Rescored per text holding
+        that text's spans in the order given (the texts without a span share one empty result).
+
+        With D = end - start, L = min(left, start) and A = min(ahead, n - end) in a text of n characters, the cost of a reading
+        r (the span as written, or a candidate) is -sum log2(max(p, 1e-99)), in f64, over the predictions of r and of the A
+        characters after the span, made by a stateful window that starts from a ZERO state and has read the L characters in
+        front of the span: `corrections`' definition, and its fairness argument -- all readings of a span share the left
+        context and the continuation.  +inf where there is no such hypothesis: a span at a text's first character (no
+        prediction to be held against: all of it +inf, as a text's first character is never a suspect), a span and continuation
+        of no characters at all, a candidate equal to what is written (as ids: two different unmapped characters are equal)
+        or, with A == 0, the empty one.  `best` is the candidate of least cost (the first among equal ones), `gain` =
+        cost0 - cost[best] in bits -- kept only where gain >= min_gain, else -1 and 0.0.
+
+        On the HIP engine no first pass is run: ids, offsets, contexts, spans and the candidate pool are uploaded once; the
+        rows (one per span for the text as written, one per candidate) are taken in chunks of consecutive whole spans of at
+        most `streams` rows (a span with more rows is a chunk of its own): zero states, `span_windows` at
+        T = max(left + ahead + M - 1, 3) with M the longest span or candidate of the call, one `rate_window_bulk` ("bf16") or
+        `rate_window` ("split"), the rows' f64 bits into one device array; at the end one `span_pick`.  With want_costs=False
+        only 12 bytes per span leave the device (cost0 and cost are None).  ValueError for a stateless rater, left < 1,
+        ahead < 0, a text index out of range, a span outside its text or with end < start, a span or candidate longer than 64
+        characters, left + ahead + M - 1 > 1024.  No edits, or only spans that cannot hold a prediction, give their results
+        without a launch.  State and precision afterwards are as after `suspects`.'''
+        texts, contexts = self._rating_request("rescore", texts, contexts, precision)[:2]
+        if not self.stateful:
+            raise ValueError('rescore needs a stateful rater: it rates through stateful windows')
+        left, ahead, streams = int(left), int(ahead), max(1, int(streams))
+        if left < 1 or ahead < 0:
+            raise ValueError("left >= 1 and ahead >= 0 (got %d, %d)" % (left, ahead))
+        n = len(texts)
+        lm = self.model
+        texts = [windows.normalize(t) for t in texts]
+        sizes = np.asarray([len(t) for t in texts], dtype=np.int64)
+        edits = list(edits)
+        S = len(edits)
+        as_array = lambda k: np.asarray([int(e[k]) for e in edits], dtype=np.int64).reshape(S)
+        span_text, starts, ends = as_array(0), as_array(1), as_array(2)
+        count = [len(e[3]) for e in edits]
+        strings = [windows.normalize(c) for e in edits for c in e[3]]
+        lengths = np.asarray([len(c) for c in strings], dtype=np.int64)
+        C = len(strings)
+        if ((span_text < 0) | (span_text >= n)).any():
+            raise ValueError("rescore: text index %d out of range" % span_text[(span_text < 0) | (span_text >= n)][0])
+        bad = np.nonzero((starts < 0) | (ends < starts) | (ends > sizes[span_text]))[0]
+        if len(bad):
+            raise ValueError("rescore: span [%d, %d) outside text %d of %d characters"
+                             % (starts[bad[0]], ends[bad[0]], span_text[bad[0]], sizes[span_text[bad[0]]]))
+        span_text, span_len = span_text.astype(np.int32), (ends - starts).astype(np.int32)
+        M = int(max([1] + ([int(span_len.max())] if S else []) + ([int(lengths.max())] if C else [])))
+        if M > ratebulk.SPAN_LEN_MAX:
+            raise ValueError("rescore: a span or candidate longer than %d characters" % ratebulk.SPAN_LEN_MAX)
+        if left + ahead + M - 1 > 1024:
+            raise ValueError("left + ahead + %d - 1 <= 1024 (got %d, %d)" % (M, left, ahead))
+        T = max(left + ahead + M - 1, ratebulk.MIN_T)
+        span_first = np.concatenate([[0], np.cumsum(count)]).astype(np.int64)
+        if precision == "split":
+            self._ensure_precision()
+        cost = np.full(S + C, np.inf, dtype=np.float64) if want_costs else None
+        best = np.full(S, -1, dtype=np.int32)
+        gain = np.zeros(S, dtype=np.float64)
+        # (a span at a text's first character, and one in a text of a single character, holds no prediction)
+        if S and ((starts >= 1) & (sizes[span_text] >= 2)).any():
+            # (all texts, and all candidates, encoded in one go: many short strings cost a Python loop each)
+            offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+            joined = "".join(texts)
+            corpus = windows.encode(joined, self.mapping[0]).astype(np.int32)
+            for g in np.nonzero(corpus == 0)[0]:
+                if joined[int(g)] not in self.mapping[0]:
+                    self._unmapped_input(joined[int(g)], int(g - offsets[np.searchsorted(offsets, g, side="right") - 1]))
+            clamped = {}      # (one context list for all texts is one object n times)
+            for c in contexts:
+                if id(c) not in clamped:
+                    clamped[id(c)] = windows.clamp_context(c)
+            text_ctx = np.asarray([clamped[id(c)] for c in contexts], dtype=np.int32).reshape(n, -1)
+            span_start = starts + offsets[span_text]      # (corpus positions)
+            pool = windows.encode("".join(strings), self.mapping[0]).astype(np.int32)
+            cand_off = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+            chunks = ratebulk.span_chunks(span_first, streams)
+            if hasattr(lm, 'span_windows'):
+                torch = lm.torch
+                up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(lm.device)
+                where = [up(a) for a in (corpus, offsets)] + [up(text_ctx) if lm.n_ctx else None]
+                spans = [up(a) for a in (span_text, span_start, span_len, span_first, pool, cand_off)]
+                cost_d = torch.empty(S + C, dtype=torch.float64, device=lm.device)
+                valid_d = torch.empty(S + C, dtype=torch.int32, device=lm.device)
+                lm.rate_bits_read(reset=True)
+                for a, b in chunks:
+                    x, z, y, ok = lm.span_windows(*(where + spans), row0=a, rows=b - a, left=left, ahead=ahead, max_len=M, T=T)
+                    lm.reset_states(b - a)
+                    (lm.rate_window_bulk if precision == "bf16" else lm.rate_window)(x, z, y, want_probs=False)
+                    cost_d[a:b] = lm.rate_bits_take_all()      # (the rows' f64 bits are the costs)
+                    valid_d[a:b] = ok
+                best_d, gain_d, cost_d = lm.span_pick(cost_d, valid_d, spans[3], float(min_gain), want_costs=want_costs)
+                lm.rate_status_check()
+                best, gain = _np(best_d), _np(gain_d)
+                if want_costs:
+                    cost = _np(cost_d)
+            else:
+                # an engine without the device path (the tests' CPU double): the numpy statements of the windows and of the
+                # choice, the whole softmax of every window and the logs summed on the host
+                costs, valids = [], []
+                for a, b in chunks:
+                    x, z, y, ok = ratebulk.span_windows_host(corpus, offsets, text_ctx, span_text, span_start, span_len,
+                                                             span_first, pool, cand_off, a, b - a, left, ahead, M, T)
+                    lm.reset_states(b - a)
+                    full = _np(lm.forward_window(x, z, want_probs=True)).astype(np.float64)
+                    p = np.take_along_axis(full, np.maximum(y, 0)[:, :, None], axis=2)[:, :, 0]
+                    costs.append(-np.where(y >= 0, np.log2(np.maximum(p, 1e-99)), 0.0).sum(axis=1))
+                    valids.append(ok)
+                best, gain, all_costs = ratebulk.span_pick_host(np.concatenate(costs), np.concatenate(valids), span_first,
+                                                                float(min_gain))
+                if want_costs:
+                    cost = all_costs
+        lm.reset_states(1)
+        # per text: its spans in the order given -- everything gathered text by text once, then cut
+        order = np.argsort(span_text, kind="stable")
+        cut = np.searchsorted(span_text[order], np.arange(n + 1), side="left")
+        counts = (span_first[1:] - span_first[:-1])[order]
+        first = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        # the candidates of the spans in that order: candidate c of span s has row c + s + 1
+        cands = np.repeat(span_first[order] - first[:-1], counts) + np.arange(int(first[-1]), dtype=np.int64)
+        names = [strings[c] for c in cands]
+        starts, ends, best, gain = starts[order], starts[order] + span_len[order], best[order], gain[order]
+        cost0 = cost[span_first[order] + order] if want_costs else None
+        cost = cost[cands + np.repeat(order, counts) + 1] if want_costs else None
+        # (most texts of a large corpus hold no span at all: they share ONE empty result, so that the call costs per span)
+        found = [ratebatch.Rescored(starts[:0], ends[:0], first[:1] * 0, [], cost0[:0] if want_costs else None,
+                                    cost[:0] if want_costs else None, best[:0], gain[:0])] * n
+        for i in np.unique(span_text).tolist():
+            a, b = int(cut[i]), int(cut[i + 1])
+            ca, cb = int(first[a]), int(first[b])
+            found[i] = ratebatch.Rescored(starts[a:b], ends[a:b], first[a:b + 1] - ca, names[ca:cb],
+                                          cost0[a:b] if want_costs else None, cost[ca:cb] if want_costs else None,
+                                          best[a:b], gain[a:b])
+        return found
+
     def _contexts_per_text(self, contexts, n):
         '''None, one context list for all texts, or one per text -> one list per text (as `rate_batch` reads them)'''
         if contexts is None or len(contexts) == 0:

@@ -11,6 +11,9 @@ Additional command `suspects`: per DATA file the characters the model does not b
 Additional command `correct`: the suspects of every DATA file with their alternatives rescored against the text that follows,
 and what that proposes to write instead (Rater.corrections); --deletions also tries dropping the character, --insertions a
 lost character in front of it; --apply also gives the corrected text.
+Additional command `rescore`: replacements that come from outside the model -- per-file candidate lists (--candidates) or a
+table of known confusions (--confusions, gated by a `suspects` pass) -- rated against the text around their spans
+(Rater.rescore); --apply also gives the corrected text.
 Additional options on `train`: --streams (stateful streams per GPU, default 1 = the
 reference's batching) and --segment-streams (with fewer files than streams, cut the files
 into contiguous segments on window boundaries, one list of segments per stream).  Under `python -m torch.distributed.run` training is
@@ -27,7 +30,7 @@ import click
 
 from .. import lib
 
-COMMAND_ORDER = ['train', 'test', 'score', 'suspects', 'correct', 'apply', 'generate', 'print-history', 'print-charset', 'prune-charset',
+COMMAND_ORDER = ['train', 'test', 'score', 'suspects', 'correct', 'rescore', 'apply', 'generate', 'print-history', 'print-charset', 'prune-charset',
                  'plot-char-embeddings-similarity', 'plot-context-embeddings-similarity', 'plot-context-embeddings-projection']
 
 
@@ -293,6 +296,103 @@ def correct(model, streams, precision, k, max_prob, min_rank, left, ahead, delet
                 "corrections": proposals}
         if apply_:
             line["corrected"] = one.apply(text, rater.mapping)
+        click.echo(json.dumps(line, ensure_ascii=False))
+
+
+def _read_confusions(path):
+    """TSV lines `source<TAB>replacement[<TAB>replacement ...]` -> [(source, [replacements])]; an empty field drops the source"""
+    rules = []
+    with open(path, mode='r') as file:
+        for number, line in enumerate(file, 1):
+            line = line.rstrip('\n').rstrip('\r')
+            if not line:
+                continue
+            fields = line.split('\t')
+            if not fields[0] or len(fields) < 2:
+                raise click.UsageError("%s:%d: a source and at least one replacement, separated by tabs" % (path, number))
+            rules.append((fields[0], fields[1:]))
+    return rules
+
+
+def _read_candidates(path, names):
+    """JSON lines {"file", "start", "end", "candidates"} -> edits for Rater.rescore over the files `names`"""
+    index = dict((name, i) for i, name in enumerate(names))
+    edits = []
+    with open(path, mode='r') as file:
+        for number, line in enumerate(file, 1):
+            if not line.strip():
+                continue
+            try:
+                one = json.loads(line)
+                edits.append((index[one["file"]], int(one["start"]), int(one["end"]), [str(c) for c in one["candidates"]]))
+            except (ValueError, KeyError, TypeError) as err:
+                raise click.UsageError("%s:%d: %r (a JSON object with \"file\" -- one of DATA --, \"start\", \"end\", "
+                                       "\"candidates\")" % (path, number, err))
+    return edits
+
+
+@cli.command(short_help='rate replacements from outside the model for spans of every file')
+@click.option('-m', '--model', default="model.h5", show_default=True, help='model file', type=click.Path(dir_okay=False, exists=True))
+@click.option('-s', '--streams', default=1024, show_default=True, help='rows of a window call: hypotheses (files in the pass of --confusions)',
+              type=click.IntRange(min=1, max=4096))
+@click.option('--precision', default='bf16', show_default=True, type=click.Choice(['bf16', 'split']),
+              help='bf16: bulk rating on the training forward; split: the inference kernels, ~f32 accuracy')
+@click.option('--left', default=64, show_default=True, type=click.IntRange(min=1, max=1024),
+              help='characters in front of a span that a hypothesis is read from (from a zero state)')
+@click.option('--ahead', default=8, show_default=True, type=click.IntRange(min=0, max=1023),
+              help='characters after a span that a hypothesis is held against')
+@click.option('--min-gain', default=1.0, show_default=True, type=click.FLOAT,
+              help='a proposal must save at least this many bits against the text as written')
+@click.option('--apply', 'apply_', is_flag=True, default=False, help='also give the text with the proposals applied ("corrected")')
+@click.option('--candidates', default=None, type=click.Path(dir_okay=False, exists=True),
+              help='JSON lines {"file", "start", "end", "candidates"}: replacement strings for the span [start, end) of a DATA file')
+@click.option('--confusions', default=None, type=click.Path(dir_okay=False, exists=True),
+              help='TSV lines: a source string, then its replacements (an empty field drops the source); tried at the '
+                   'occurrences that hold a suspect character')
+@click.option('-k', 'k', default=3, show_default=True, type=click.IntRange(min=1, max=8),
+              help='(--confusions) alternatives of the suspects pass')
+@click.option('--max-prob', default=0.01, show_default=True, type=click.FLOAT,
+              help='(--confusions) a suspect has at most this probability')
+@click.option('--min-rank', default=1, show_default=True, type=click.IntRange(min=0),
+              help='(--confusions) ... and at least this rank; --max-prob 1 --min-rank 0 keeps every occurrence')
+@click.argument('data', nargs=-1, type=click.Path(exists=True, dir_okay=True, file_okay=True))
+def rescore(model, streams, precision, left, ahead, min_gain, apply_, candidates, confusions, k, max_prob, min_rank, data):
+    """Apply a language model to DATA files and print one JSON line per file: characters and
+       "rescored": one [start, end, written, proposed, gain] per span -- proposed is what replaces
+       text[start:end]: null for no proposal, "" for dropping it; gain the bits the proposal saves over the
+       span and the AHEAD characters after it, read after the LEFT characters in front.  The replacements
+       come from --candidates or from --confusions (exactly one of them).  With --apply the line also
+       holds the corrected text.
+    """
+    from ..lib import ratebatch, windows
+    if (candidates is None) == (confusions is None):
+        raise click.UsageError("exactly one of --candidates and --confusions")
+    rules = _read_confusions(confusions) if confusions is not None else None
+    rater = _load(model)
+    names, texts, contexts = [], [], []
+    for file in _open_all(data):
+        with file:
+            texts.append(windows.normalize(file.read()))
+        names.append(file.name)
+        contexts.append(windows.context_from_filename(file.name))
+    if not texts:
+        return
+    if rules is not None:
+        found, _ = rater.suspects(texts, contexts, k=k, streams=streams, max_prob=max_prob, min_rank=min_rank, precision=precision)
+        edits = ratebatch.confusion_edits(texts, rules, at=[one.positions for one in found])
+    else:
+        edits = _read_candidates(candidates, names)
+    try:
+        found = rater.rescore(texts, edits, contexts, streams=streams, left=left, ahead=ahead, min_gain=min_gain,
+                              precision=precision, want_costs=False)
+    except ValueError as err:
+        raise click.UsageError(str(err))
+    for name, text, one in zip(names, texts, found):
+        rows = [[int(a), int(b), text[int(a):int(b)], new, float(g)]
+                for a, b, new, g in zip(one.starts, one.ends, one.proposals(), one.gain)]
+        line = {"file": name, "chars": len(text), "rescored": rows}
+        if apply_:
+            line["corrected"] = one.apply(text)
         click.echo(json.dumps(line, ensure_ascii=False))
 
 
