@@ -336,6 +336,43 @@ int kl_span_windows(const int32_t* corpus, size_t n_corpus, const int64_t* offse
 int kl_span_pick(const double* cost, const int32_t* valid, const int64_t* span_first, int S, int64_t C, double min_gain,
                  int32_t* best, double* gain, double* cost_out, void* stream);
 
+/* Rating under candidate contexts: every text of a corpus rated under each of C context tuples in one bulk plan (the plan rows
+ * are pairs of a text and a candidate over the same ids, so kl_assemble_windows serves unchanged), the results read side by
+ * side.  No handle.
+ * kl_rate_scatter_planes: kl_rate_scatter with a destination plane per row.  tprob (device f32 [B][T]) and plan (device int64
+ *   [B][4 + n_ctx]) as there; plane (device int32 [B]) names the candidate every row was rated under; out is device f32
+ *   [C][ld] with n_out <= ld.  For 0 <= t < min(vlen, T) with 0 <= g = start + 1 + t < n_out and 0 <= plane[b] < C:
+ *   out[plane[b] * ld + g] = tprob[b][t].  A bit copy; nothing else is written: a row with vlen <= 0 or a plane outside
+ *   [0, C) writes nothing.  KL_ERR_ARG, before the launch, for null pointers, B, T or C < 1, C > KL_CTX_CAND_MAX, n_ctx outside
+ *   0 .. 8, ld < n_out, ld > 2^40, misaligned pointers (4 bytes; plan 8).  One launch on `stream`.
+ * kl_context_mix: planes (device f32 [C][ld]) as kl_rate_scatter_planes filled them; offsets (device int64 [n_texts + 1],
+ *   ascending, repeated values -- empty texts -- allowed) as in kl_rate_text_bits; log2prior (device f64 [C]; NULL: uniform,
+ *   every entry 0) holds finite entries or -inf (a candidate that is rated but takes no part).  For text i and its predicted
+ *   positions j = max(offsets[i] + 1, 1) .. min(offsets[i+1], ld) - 1 in ascending order (the first character has no
+ *   prediction; nothing outside the planes is read), all in f64:
+ *     q_c[j]  = fmax((double)planes[c * ld + j], 1e-99)             (C's fmax: a NaN counts as 1e-99)
+ *     lw_c(j) = log2prior[c] + sum over j' < j of log2 q_c[j']      (the candidate's weight in front of j, in bits)
+ *     w_c     = exp2(lw_c(j) - max_c lw_c(j)), 0 where lw_c(j) = -inf
+ *     r[j]    = sum_c w_c q_c[j] / sum_c w_c                        (the sequential Bayesian mixture of the candidates)
+ *   mix[j] = (float)r[j]  (device f32 [ld], may be NULL; first characters and everything outside the texts are not written);
+ *   cand_bits[i][c] = -sum_j log2 q_c[j]  (device f64 [n_texts][C]);  mix_bits[i] = -sum_j log2 r[j]  (device f64 [n_texts]);
+ *   and with the final lw_c (behind the text's last character; the prior itself for a text without predictions):
+ *   post[i][c] = w_c / sum_c w_c  (device f64 [n_texts][C]);  best[i] (device int32 [n_texts]) the smallest c of maximal lw_c;
+ *   margin[i] (device f64 [n_texts]) = lw_best minus the largest lw_c of the others, +inf where no other is finite (C == 1).
+ *   All outputs are OVERWRITTEN.  With C == 1, mix[j] is (float)q[j]: the plane bit for bit, but 0 for a NaN.  The caller
+ *   guarantees one finite entry of log2prior; without one, mix, mix_bits and post are NaN, best is 0, margin +inf and
+ *   cand_bits as always -- and nothing outside the outputs is touched.  One workgroup per text walks it in tiles of 64
+ *   positions; every sum is taken in an order that depends on indices only, no atomics, no workgroup waits for another: two
+ *   calls on the same input agree bit for bit.  Against a sequential evaluation the sums differ by rounding only.
+ *   KL_ERR_ARG, before the launch, for null pointers other than mix and log2prior, n_texts < 1, C outside
+ *   1 .. KL_CTX_CAND_MAX, ld < 1 or > 2^40, misaligned pointers (planes, mix and best 4 bytes, the others 8).  One launch on
+ *   `stream`. */
+#define KL_CTX_CAND_MAX 256
+int kl_rate_scatter_planes(const float* tprob, const int64_t* plan, const int32_t* plane, int B, int T, int n_ctx, int C, float* out,
+                           size_t ld, size_t n_out, void* stream);
+int kl_context_mix(const float* planes, size_t ld, const int64_t* offsets, int n_texts, int C, const double* log2prior, float* mix,
+                   double* cand_bits, double* mix_bits, double* post, int32_t* best, double* margin, void* stream);
+
 /* One training batch, forward + backward (rating.py:292-298 -> train_on_batch):
  * writes the gradient of (mean CE + embedding regularisers, rating.py:187-246)
  * into grads (param layout; overwritten), advances states, and accumulates

@@ -522,6 +522,52 @@ class HipLM:
                          "kl_rate_text_bits")
         return bits
 
+    def rate_scatter_planes(self, tprob, plan, plane, n_ctx, out):
+        """kl_rate_scatter_planes: `rate_scatter` with a destination plane per row -- out f32 DEVICE tensor [C, ld], plane int32
+        DEVICE tensor [B]: out[plane[b], start + 1 + t] = tprob[b][t] for t < min(vlen, T); a row whose plane is outside
+        [0, C) writes nothing.  In place, no synchronisation."""
+        torch = self.torch
+        B, T = int(tprob.shape[0]), int(tprob.shape[1])
+        tensors = (tprob, plan, plane, out)
+        if ([t.dtype for t in tensors] != [torch.float32, torch.int64, torch.int32, torch.float32] or plan.dim() != 2
+                or tuple(plan.shape) != (B, 4 + n_ctx) or tuple(plane.shape) != (B,) or out.dim() != 2
+                or not all(t.is_contiguous() and t.is_cuda for t in tensors)):
+            raise hipabi.KlError("rate_scatter_planes: tprob f32 [B, T], plan int64 [B, 4 + n_ctx], plane int32 [B], out f32 [C, ld], "
+                                 "contiguous, on the device")
+        C, ld = int(out.shape[0]), int(out.shape[1])
+        with self._launch():
+            hipabi.check(self.lib.kl_rate_scatter_planes(_ptr(tprob), _ptr(plan), _ptr(plane), B, T, int(n_ctx), C, _ptr(out), ld,
+                                                         ld, self._stream()), "kl_rate_scatter_planes")
+        return out
+
+    def context_mix(self, planes, offsets, log2prior=None, mix=None):
+        """kl_context_mix over planes (f32 DEVICE tensor [C, ld], what `rate_scatter_planes` filled), offsets (int64 DEVICE
+        tensor [n + 1]) and log2prior (f64 DEVICE tensor [C], or None: uniform): returns the DEVICE tensors (cand_bits f64
+        [n, C], mix_bits f64 [n], post f64 [n, C], best int32 [n], margin f64 [n]); mix (f32 DEVICE tensor [ld], or None)
+        takes the mixture's probability at every predicted position, in place.  The statement is ratebulk.context_mix_host.
+        No synchronisation."""
+        torch = self.torch
+        if (planes.dtype != torch.float32 or planes.dim() != 2 or offsets.dtype != torch.int64 or offsets.dim() != 1
+                or offsets.numel() < 2 or not (planes.is_contiguous() and offsets.is_contiguous())
+                or not (planes.is_cuda and offsets.is_cuda)):
+            raise hipabi.KlError("context_mix: planes f32 [C, ld], offsets int64 [n_texts + 1], contiguous, on the device")
+        C, ld = int(planes.shape[0]), int(planes.shape[1])
+        if log2prior is not None and (log2prior.dtype != torch.float64 or tuple(log2prior.shape) != (C,)
+                                      or not (log2prior.is_contiguous() and log2prior.is_cuda)):
+            raise hipabi.KlError("context_mix: log2prior f64 [C], contiguous, on the device")
+        if mix is not None and (mix.dtype != torch.float32 or tuple(mix.shape) != (ld,)
+                                or not (mix.is_contiguous() and mix.is_cuda)):
+            raise hipabi.KlError("context_mix: mix f32 [ld], contiguous, on the device")
+        n = offsets.numel() - 1
+        with self._launch():
+            f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=self.device)
+            cand_bits, mix_bits, post, margin = f64(n, C), f64(n), f64(n, C), f64(n)
+            best = torch.empty(n, dtype=torch.int32, device=self.device)
+            hipabi.check(self.lib.kl_context_mix(_ptr(planes), ld, _ptr(offsets), n, C, _ptr(log2prior), _ptr(mix),
+                                                 _ptr(cand_bits), _ptr(mix_bits), _ptr(post), _ptr(best), _ptr(margin),
+                                                 self._stream()), "kl_context_mix")
+        return cand_bits, mix_bits, post, best, margin
+
     def rate_scatter_alts(self, tprob, rank, alt_id, alt_p, plan, n_ctx, out_prob, out_rank, out_alt_id, out_alt_p):
         """kl_rate_scatter_alts: `rate_scatter` for all four results of a `rate_window_alts(_bulk)` call (DEVICE tensors tprob,
         rank [B,T], alt_id, alt_p [B,T,k]) into corpus-order DEVICE arrays out_prob f32 [n], out_rank i32 [n], out_alt_id i32

@@ -247,6 +247,25 @@ class Rescored(object):
         return "".join(chars)
 
 
+class ContextRating(object):
+    """One text of `Rater.rate_contexts`, n characters rated under C candidate contexts:
+
+    bits       [C] f64    bits of the text under every candidate, as `rate_batch(texts, contexts=candidates[c])` gives them
+    posterior  [C] f64    the prior times 2**-bits, normalised: how much of the belief every candidate holds after the text
+    best       int        the index into `candidates` of the most probable one (the smallest among equal ones)
+    margin     float      bits between the best and the next candidate with a positive prior (+inf: there is no other)
+    mix_bits   float      bits of the text under the sequential Bayesian mixture of the candidates
+    probs      [n] f32    probability of every character under that mixture (1.0 for the first); None without want_probs
+    """
+
+    def __init__(self, bits, posterior, best, margin, mix_bits, probs):
+        self.bits, self.posterior, self.best, self.margin = bits, posterior, int(best), float(margin)
+        self.mix_bits, self.probs = float(mix_bits), probs
+
+    def __len__(self):
+        return len(self.bits)
+
+
 def confusion_edits(texts, rules, at=None):
     """Edits for `Rater.rescore` from a table of known confusions: rules is a list of (source, [replacements]) with a non-empty
     source; one edit (i, start, end, replacements) per occurrence of a source in the NFC-normalised texts[i], overlapping

@@ -21,13 +21,17 @@ kl_rate_text_bits compute; `scatter_alts_host` and `select_host` what kl_rate_sc
 with alternatives (`Rater.rate_alternatives(precision="bf16")`, `Rater.suspects`); `variant_windows_host` what
 kl_variant_windows / kl_edit_windows make of the suspects for `Rater.corrections`, and `variant_pick_host` is the choice among a suspect's
 variants (numpy on every path: S * R doubles); `span_windows_host` and `span_pick_host` what kl_span_windows and kl_span_pick
-make of spans with caller-supplied replacements for `Rater.rescore`.  numpy only: the plan is built and tested without an
-engine.
+make of spans with caller-supplied replacements for `Rater.rescore`.  `plan_candidates` is the plan of `Rater.rate_contexts`
+-- every text under every one of C candidate contexts, the pairs as plan rows over the one corpus --, and
+`scatter_planes_host` and `context_mix_host` state what kl_rate_scatter_planes and kl_context_mix make of its calls.  numpy
+only: the plan is built and tested without an engine.
 """
 from __future__ import annotations
 
 import numpy as np
 
+CTX_CAND_MAX = 256          # candidate contexts of `plan_candidates` at most (KL_CTX_CAND_MAX of the C ABI)
+PLANE_BYTES = 1 << 30       # `Rater.rate_contexts`: device bytes of the [C][characters] f32 planes of one chunk of texts
 MIN_T = 3          # shorter windows fall off the persistent scans (engine.HipLM._padded_streams)
 ROUND_T = 32       # short-text groups: T is rounded up to a multiple of this
 
@@ -444,3 +448,122 @@ def span_chunks(span_first, streams):
         out.append((int(keys[a]), int(keys[b])))
         a = b
     return out
+
+
+def plan_candidates(sizes, candidates, length, streams):
+    """`plan` for every text under every one of C candidate contexts: its rules over the n * C virtual texts v = i * C + c, a
+    virtual text having the size and the corpus start of text i and the (clamped) context candidates[c].  The rows point into
+    the shared corpus of the n texts -- kl_assemble_windows serves unchanged --, so a row's start does not tell its candidate:
+    that is `plane`.  Returns (Plan, planes): the Plan has offsets and sizes of the n texts, and row, first and count per
+    virtual text [n * C]; planes[s] is int32 [B] for call s, the candidate of every row, -1 for a row with nothing to do.
+    With C = 1 the calls are `plan`'s, row for row."""
+    sizes = np.asarray(sizes, dtype=np.int64).reshape(-1)
+    n, C = len(sizes), len(candidates)
+    if not 1 <= C <= CTX_CAND_MAX:
+        raise ValueError("1 .. %d candidate contexts (got %d)" % (CTX_CAND_MAX, C))
+    cand = np.asarray(candidates, dtype=np.int64).reshape(C, -1)
+    virtual = plan(np.repeat(sizes, C), np.tile(cand, (n, 1)), length, streams)
+    offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    shift = np.repeat(offsets[:-1], C) - virtual.offsets[:-1]      # (from a virtual text's own start to its text's)
+    planes = [np.full(c.B, -1, dtype=np.int32) for c in virtual.calls]
+    # every window of every virtual text: (call, row), grouped by call
+    count = np.where(virtual.row >= 0, virtual.count, 0)
+    v = np.repeat(np.arange(n * C, dtype=np.int64), count)
+    w = np.arange(len(v), dtype=np.int64) - np.repeat(np.cumsum(count) - count, count)
+    call = virtual.first[v] + w
+    order = np.argsort(call, kind="stable")
+    cut = np.searchsorted(call[order], np.arange(len(virtual.calls) + 1), side="left")
+    for s, one in enumerate(virtual.calls):
+        mine = v[order[cut[s]:cut[s + 1]]]
+        rows = virtual.row[mine]
+        one.rows[rows, 0] += shift[mine]
+        planes[s][rows] = mine % C
+    return Plan(virtual.calls, offsets, sizes, virtual.n_ctx, virtual.row, virtual.first, virtual.count), planes
+
+
+def text_chunks(sizes, limit):
+    """texts in input order cut for `Rater.rate_contexts`: consecutive whole texts while the chunk has at most `limit`
+    characters, a single larger text a chunk of its own.  Returns [(first text, end)], covering every text; [] for no text."""
+    ends = np.cumsum(np.asarray(sizes, dtype=np.int64).reshape(-1))
+    limit = max(1, int(limit))
+    out = []
+    a = 0
+    while a < len(ends):
+        done = int(ends[a - 1]) if a else 0
+        b = max(a + 1, int(np.searchsorted(ends, done + limit, side="right")))
+        out.append((a, b))
+        a = b
+    return out
+
+
+def scatter_planes_host(tprob, rows, plane, out, n_out=None):
+    """what kl_rate_scatter_planes does: `scatter_host` with a destination plane per row -- out [C, ld]:
+    out[plane[b], start + 1 + t] = tprob[b][t] for t < min(vlen, T), inside [0, n_out) (n_out <= ld; None: ld); a row whose
+    plane is outside [0, C) writes nothing; in place, returns out"""
+    tprob = np.asarray(tprob)
+    B, T = tprob.shape
+    C, ld = out.shape
+    n = ld if n_out is None else int(n_out)
+    assert n <= ld
+    for b in range(B):
+        c = int(plane[b])
+        if not 0 <= c < C:
+            continue
+        start, vlen = int(rows[b, 0]), int(min(max(rows[b, 1], 0), T))
+        for t in range(vlen):
+            g = start + 1 + t
+            if 0 <= g < n:
+                out[c, g] = tprob[b, t]
+    return out
+
+
+def context_mix_host(planes, offsets, log2prior=None, mix=None):
+    """what kl_context_mix computes from planes [C, ld] f32 (candidate c's probabilities in corpus order), offsets [n + 1] and
+    log2prior [C] f64 (None: uniform, every entry 0; finite entries or -inf, one finite).  For text i and its predicted
+    positions j = max(offsets[i] + 1, 1) .. min(offsets[i + 1], ld) - 1, ascending, sequential f64:
+      q_c[j] = np.fmax(planes[c, j], 1e-99) (a NaN counts as 1e-99);  lw_c(j) = log2prior[c] + sum_{j' < j} log2 q_c[j'];
+      w_c = exp2(lw_c(j) - max_c lw_c(j)), 0 where lw_c(j) is -inf;  r[j] = sum_c w_c q_c[j] / sum_c w_c.
+    mix (f32 [ld] or None) takes float32(r[j]) at these positions, in place; nothing else of it is written.  Returns
+    (cand_bits [n, C] = -sum_j log2 q_c[j], mix_bits [n] = -sum_j log2 r[j], post [n, C], best [n] int32, margin [n]) -- with
+    the final lw_c (the prior for a text without predictions): post = w_c / sum w, best the smallest c of maximal lw_c, margin
+    lw_best minus the largest lw of the others, +inf where none of them is finite.  Without a finite prior entry: mix, mix_bits
+    and post are NaN, best 0, margin +inf."""
+    planes = np.asarray(planes)
+    C, ld = planes.shape
+    offsets = np.asarray(offsets, dtype=np.int64).reshape(-1)
+    n = len(offsets) - 1
+    prior = np.zeros(C, dtype=np.float64) if log2prior is None else np.asarray(log2prior, dtype=np.float64).reshape(C)
+    cand_bits = np.zeros((n, C), dtype=np.float64)
+    mix_bits = np.zeros(n, dtype=np.float64)
+    post = np.zeros((n, C), dtype=np.float64)
+    best = np.zeros(n, dtype=np.int32)
+    margin = np.zeros(n, dtype=np.float64)
+
+    def weights(lw):      # [C, m] -> the weights and their sequential sum over c
+        with np.errstate(invalid="ignore"):
+            w = np.where(np.isneginf(lw), 0.0, np.exp2(lw - lw.max(axis=0)))
+        return w, np.add.accumulate(w, axis=0)[-1]
+
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for i in range(n):
+            a, b = max(int(offsets[i]) + 1, 1), min(int(offsets[i + 1]), ld)
+            sums = np.zeros(C, dtype=np.float64)
+            if b > a:
+                q = np.fmax(planes[:, a:b].astype(np.float64), 1e-99)
+                run = np.add.accumulate(np.log2(q), axis=1)      # (sequential along the text)
+                sums = run[:, -1]
+                lw = prior[:, None] + np.concatenate([np.zeros((C, 1)), run[:, :-1]], axis=1)
+                w, total = weights(lw)
+                r = np.add.accumulate(w * q, axis=0)[-1] / total
+                if mix is not None:
+                    mix[a:b] = r.astype(np.float32)
+                mix_bits[i] = -np.add.accumulate(np.log2(r))[-1]
+            cand_bits[i] = 0.0 - sums
+            lw = prior + sums
+            w, total = weights(lw[:, None])
+            post[i] = w[:, 0] / total[0]
+            best[i] = int(np.argmax(lw))      # (the first of equal maxima)
+            rest = np.delete(lw, best[i])
+            second = rest.max() if len(rest) else -np.inf
+            margin[i] = np.inf if np.isneginf(second) else lw[best[i]] - second
+    return cand_bits, mix_bits, post, best, margin

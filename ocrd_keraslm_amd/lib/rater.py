@@ -991,7 +991,6 @@ class Rater(object):
             lm.reset_states(1)
             return plan, None, bits
         n_ctx = plan.n_ctx
-        bounds = np.concatenate([[0], np.cumsum([c.B for c in plan.calls])])
         corpus = torch.from_numpy(np.concatenate(ids).astype(np.int32)).to(lm.device)
         rows = torch.from_numpy(np.concatenate([c.rows for c in plan.calls])).to(lm.device)
         reset = torch.from_numpy(np.concatenate([c.reset for c in plan.calls])).to(lm.device)
@@ -1005,8 +1004,29 @@ class Rater(object):
                     torch.full((plan.total, k), -1, dtype=torch.int32, device=lm.device),
                     torch.zeros((plan.total, k), dtype=torch.float32, device=lm.device)]
         bulk = precision == "bf16"
+
+        def deliver(s, a, b, x, z, y):
+            if k:
+                p, ai, ap, rk = (lm.rate_window_alts_bulk if bulk else lm.rate_window_alts)(x, z, y, k)
+                lm.rate_scatter_alts(p, rk, ai, ap, rows[a:b], n_ctx, *out)
+            else:
+                p = (lm.rate_window_bulk if bulk else lm.rate_window)(x, z, y, want_probs=True)
+                lm.rate_scatter(p, rows[a:b], n_ctx, out[0])
+        self._corpus_calls(plan.calls, corpus, rows, reset, n_ctx, deliver)
+        bits[:] = _np(lm.rate_text_bits(out[0], offsets))
+        lm.rate_bits_read(reset=True)      # (the per-stream sums are not used here; also raises on a timed-out scan hand-off)
+        lm.reset_states(1)
+        return plan, tuple(out), bits
+
+    def _corpus_calls(self, calls, corpus, rows, reset, n_ctx, deliver):
+        '''The window calls of a bulk plan (ratebulk.Call) over an uploaded corpus, in order: rows and reset are the DEVICE
+        concatenations of the calls' plan rows and reset masks.  Before a call the rows that start a text are zeroed (all of
+        them where the number of rows changes), `assemble_windows` makes its batch, and deliver(s, a, b, x, z, y) rates it and
+        takes its results away -- rows[a:b] are the call's.'''
+        lm = self.model
+        bounds = np.concatenate([[0], np.cumsum([c.B for c in calls])])
         B = None
-        for s, call in enumerate(plan.calls):
+        for s, call in enumerate(calls):
             a, b = int(bounds[s]), int(bounds[s + 1])
             if call.B != B:
                 B = call.B
@@ -1014,16 +1034,106 @@ class Rater(object):
             elif call.reset.any():
                 lm.reset_states_where(reset[a:b])
             x, z, y = lm.assemble_windows(corpus, rows[a:b], call.T, n_ctx)
-            if k:
-                p, ai, ap, rk = (lm.rate_window_alts_bulk if bulk else lm.rate_window_alts)(x, z, y, k)
-                lm.rate_scatter_alts(p, rk, ai, ap, rows[a:b], n_ctx, *out)
-            else:
+            deliver(s, a, b, x, z, y)
+
+    def rate_contexts(self, texts, candidates, prior=None, streams=1024, precision="bf16", want_probs=True):
+        '''Which context does every text read like?  Rates all texts under each of C candidate contexts at once and returns
+        one ratebatch.ContextRating per text, in input order: `bits` [C] -- what `rate_batch(texts, contexts=candidates[c])`
+        gives for the text --, `posterior` [C] (the prior times 2**-bits, normalised), `best` (an index into `candidates`:
+        the most probable one, the smallest among equal ones), `margin` (bits between it and the next candidate of positive
+        prior, +inf if there is none), `mix_bits`, and `probs` [n] f32: per character the probability under the sequential
+        Bayesian mixture of the candidates -- at every character each candidate weighs as much as its prior times the
+        probability it gave to the text so far -- with 1.0 for the first; the rating of a text whose context is not known,
+        instead of context 0.  With want_probs=False `probs` is None and nothing per character leaves the device.
+
+        candidates: 1 .. 256 context lists of the model's arity (clamped as everywhere; duplicates are allowed and tie).
+        prior: None (uniform) or C non-negative weights with a positive sum; a candidate of weight 0 is rated -- its `bits`
+        are delivered -- but takes no part in posterior, best, margin or the mixture.
+
+        On the HIP engine the n * C pairs of a text and a candidate are the rows of ONE bulk plan over one upload of the ids
+        (ratebulk.plan_candidates: 64 documents under 20 candidates fill a launch as 1280 streams): per call
+        `assemble_windows`, `rate_window_bulk` ("bf16") or `rate_window` ("split"), `rate_scatter_planes` into a [C][characters]
+        array, then one `context_mix`.  Texts go in input order in chunks of whole texts of at most ratebulk.PLANE_BYTES of
+        that array (a single larger text is a chunk of its own).  An engine without these calls rates once per candidate
+        through `rate_batch` and mixes in numpy (ratebulk.context_mix_host).  ValueError for a bad precision, a stateless
+        rater with "bf16", no candidate or more than 256, a candidate of another arity, a prior of another length, with a
+        negative or non-finite weight or without a positive one.  State and precision afterwards are as after `rate_batch`.'''
+        texts = self._rating_request("rate_contexts", texts, None, precision)[0]
+        candidates = [list(c) for c in candidates]
+        C = len(candidates)
+        if not 1 <= C <= ratebulk.CTX_CAND_MAX:
+            raise ValueError("rate_contexts: 1 .. %d candidate contexts (got %d)" % (ratebulk.CTX_CAND_MAX, C))
+        for c in candidates:
+            if len(c) != self.n_ctx:
+                raise ValueError("rate_contexts: the model has %d context variables (got %r)" % (self.n_ctx, c))
+        candidates = [windows.clamp_context(c) for c in candidates]
+        log2prior = None
+        if prior is not None:
+            weights = np.asarray(prior, dtype=np.float64).reshape(-1)
+            if len(weights) != C or not np.isfinite(weights).all() or (weights < 0).any() or not weights.sum() > 0:
+                raise ValueError("rate_contexts: prior must be %d non-negative weights with a positive sum" % C)
+            with np.errstate(divide="ignore"):
+                log2prior = np.log2(weights / weights.sum())
+        n = len(texts)
+        lm = self.model
+        found = [None] * n
+        if not self.stateful or not (hasattr(lm, 'rate_scatter_planes') and hasattr(lm, 'context_mix')):
+            # a stateless rater (its windows are `rate`'s own), or an engine without the device path (the tests' CPU double):
+            # rate_batch per candidate, the numpy statement
+            per = [self.rate_batch(texts, candidates[c], streams=streams, precision=precision)[0] for c in range(C)]
+            offsets = np.concatenate([[0], np.cumsum([len(p) for p in per[0]])]).astype(np.int64)
+            planes = np.ones((C, max(int(offsets[-1]), 1)), dtype=np.float32)
+            for c in range(C):
+                planes[c, :int(offsets[-1])] = np.concatenate(per[c]) if n else []
+            mix = np.ones(planes.shape[1], dtype=np.float32)
+            results = ratebulk.context_mix_host(planes, offsets, log2prior, mix if want_probs else None)
+            self._context_ratings(found, 0, offsets, results, mix if want_probs else None)
+            return found
+        torch = lm.torch
+        texts = [windows.normalize(t) for t in texts]
+        ids = [windows.encode(t, self.mapping[0], self._unmapped_input) for t in texts]
+        sizes = np.asarray([len(a) for a in ids], dtype=np.int64)
+        if precision == "split":
+            self._ensure_precision()
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(lm.device)
+        prior_d = None if log2prior is None else up(log2prior)
+        bulk = precision == "bf16"
+        for t0, t1 in ratebulk.text_chunks(sizes, ratebulk.PLANE_BYTES // (4 * C)):
+            plan, plane = ratebulk.plan_candidates(sizes[t0:t1], candidates, self.length, streams)
+            total = max(plan.total, 1)
+            if not plan.calls:       # (nothing but empty texts and single characters: the prior)
+                planes = np.ones((C, total), dtype=np.float32)
+                mix = np.ones(total, dtype=np.float32) if want_probs else None
+                self._context_ratings(found, t0, plan.offsets, ratebulk.context_mix_host(planes, plan.offsets, log2prior, mix), mix)
+                continue
+            n_ctx = plan.n_ctx
+            corpus = up(np.concatenate(ids[t0:t1]).astype(np.int32))
+            rows = up(np.concatenate([c.rows for c in plan.calls]))
+            reset = up(np.concatenate([c.reset for c in plan.calls]))
+            plane = up(np.concatenate(plane))
+            offsets = up(plan.offsets)
+            planes = torch.ones((C, total), dtype=torch.float32, device=lm.device)
+            mix = torch.ones(total, dtype=torch.float32, device=lm.device) if want_probs else None      # (1.0: a first character)
+
+            def deliver(s, a, b, x, z, y):
                 p = (lm.rate_window_bulk if bulk else lm.rate_window)(x, z, y, want_probs=True)
-                lm.rate_scatter(p, rows[a:b], n_ctx, out[0])
-        bits[:] = _np(lm.rate_text_bits(out[0], offsets))
-        lm.rate_bits_read(reset=True)      # (the per-stream sums are not used here; also raises on a timed-out scan hand-off)
+                lm.rate_scatter_planes(p, rows[a:b], plane[a:b], n_ctx, planes)
+            self._corpus_calls(plan.calls, corpus, rows, reset, n_ctx, deliver)
+            results = [_np(t) for t in lm.context_mix(planes, offsets, prior_d, mix)]
+            lm.rate_bits_read(reset=True)      # (the per-stream sums are not used here; also raises on a timed-out scan hand-off)
+            self._context_ratings(found, t0, plan.offsets, results, None if mix is None else _np(mix))
+            del planes, mix
         lm.reset_states(1)
-        return plan, tuple(out), bits
+        return found
+
+    @staticmethod
+    def _context_ratings(found, t0, offsets, results, mix):
+        '''found[t0 + i] = the ContextRating of text i of a chunk: results as `context_mix` returns them (host arrays), mix the
+        chunk's mixture probabilities in corpus order or None'''
+        cand_bits, mix_bits, post, best, margin = results
+        for i in range(len(offsets) - 1):
+            probs = None if mix is None else np.array(mix[int(offsets[i]):int(offsets[i + 1])], dtype=np.float32)
+            found[t0 + i] = ratebatch.ContextRating(cand_bits[i].copy(), post[i].copy(), best[i], margin[i], mix_bits[i], probs)
 
     @staticmethod
     def _empty_selection(k):

@@ -14,6 +14,9 @@ lost character in front of it; --apply also gives the corrected text.
 Additional command `rescore`: replacements that come from outside the model -- per-file candidate lists (--candidates) or a
 table of known confusions (--confusions, gated by a `suspects` pass) -- rated against the text around their spans
 (Rater.rescore); --apply also gives the corrected text.
+Additional command `contexts`: per DATA file the context it reads like among the candidates given (--years or --candidates),
+the posterior over them, and its bits under the best one, under their sequential mixture and under context 0
+(Rater.rate_contexts: every file under every candidate in one bulk plan).
 Additional options on `train`: --streams (stateful streams per GPU, default 1 = the
 reference's batching) and --segment-streams (with fewer files than streams, cut the files
 into contiguous segments on window boundaries, one list of segments per stream).  Under `python -m torch.distributed.run` training is
@@ -30,7 +33,7 @@ import click
 
 from .. import lib
 
-COMMAND_ORDER = ['train', 'test', 'score', 'suspects', 'correct', 'rescore', 'apply', 'generate', 'print-history', 'print-charset', 'prune-charset',
+COMMAND_ORDER = ['train', 'test', 'score', 'suspects', 'correct', 'rescore', 'contexts', 'apply', 'generate', 'print-history', 'print-charset', 'prune-charset',
                  'plot-char-embeddings-similarity', 'plot-context-embeddings-similarity', 'plot-context-embeddings-projection']
 
 
@@ -393,6 +396,89 @@ def rescore(model, streams, precision, left, ahead, min_gain, apply_, candidates
         line = {"file": name, "chars": len(text), "rescored": rows}
         if apply_:
             line["corrected"] = one.apply(text)
+        click.echo(json.dumps(line, ensure_ascii=False))
+
+
+def _year_candidates(spec):
+    """'1700:1900:10' -> the distinct context ids of the years FROM, FROM + STEP, .. up to TO (STEP 10 if left out), as
+    `_contexts` maps them, in ascending order of the years"""
+    parts = spec.split(':')
+    if len(parts) not in (2, 3):
+        raise click.BadParameter('FROM:TO[:STEP]', param_hint='--years')
+    try:
+        first, last = int(parts[0]), int(parts[1])
+        step = int(parts[2]) if len(parts) == 3 else 10
+    except ValueError:
+        raise click.BadParameter('FROM:TO[:STEP] in whole years', param_hint='--years')
+    if step < 1 or last < first:
+        raise click.BadParameter('FROM <= TO and STEP >= 1', param_hint='--years')
+    out = []
+    for year in range(first, last + 1, step):
+        c = _contexts(str(year))
+        if c not in out:
+            out.append(c)
+    return out
+
+
+def _read_context_candidates(path):
+    """one blank-separated context tuple per line, in the notation `apply -c` takes (years); empty lines are skipped"""
+    with open(path, mode='r') as file:
+        return [_contexts(' '.join(line.split())) for line in file if line.strip()]
+
+
+@cli.command(short_help='find the context every file reads like, and rate it under the mixture of the candidates')
+@click.option('-m', '--model', default="model.h5", show_default=True, help='model file', type=click.Path(dir_okay=False, exists=True))
+@click.option('-s', '--streams', default=1024, show_default=True, help='rows of a window call: pairs of a file and a candidate',
+              type=click.IntRange(min=1, max=4096))
+@click.option('--precision', default='bf16', show_default=True, type=click.Choice(['bf16', 'split']),
+              help='bf16: bulk rating on the training forward; split: the inference kernels, ~f32 accuracy')
+@click.option('--years', default=None, help='FROM:TO[:STEP]: one candidate per decade of these years (models of one context variable)')
+@click.option('--candidates', default=None, type=click.Path(dir_okay=False, exists=True),
+              help='file with one candidate per line: blank-separated meta-data as `apply -c` takes it')
+@click.option('--top', default=3, show_default=True, type=click.IntRange(min=1, max=256), help='posteriors listed per file')
+@click.argument('data', nargs=-1, type=click.Path(exists=True, dir_okay=True, file_okay=True))
+def contexts(model, streams, precision, years, candidates, top, data):
+    """Apply a language model to DATA files under every candidate context and print one JSON line per file:
+       characters, the most probable candidate and its margin in bits, the --top candidates with their
+       posteriors (uniform prior), and bits per character under the best candidate, under the sequential
+       mixture of all of them and -- if it is not a candidate itself -- under context 0, the rating a
+       caller gets today who does not know the context.
+
+       Files are read as `score` reads them; their names are not asked for a context.
+    """
+    from ..lib import windows
+    if (years is None) == (candidates is None):
+        raise click.UsageError('give either --years or --candidates')
+    rater = _load(model)
+    if years is not None:
+        if rater.n_ctx != 1:
+            raise click.UsageError('--years is for models of one context variable (this one has %d)' % rater.n_ctx)
+        cands = _year_candidates(years)
+    else:
+        cands = _read_context_candidates(candidates)
+    cands = [windows.clamp_context(c) for c in cands]
+    names, texts = [], []
+    for file in _open_all(data):
+        with file:
+            texts.append(windows.normalize(file.read()))
+        names.append(file.name)
+    if not texts:
+        return
+    # context 0 is one more candidate of the same call, kept out of the posterior and the mixture by a zero prior
+    zero = [0] * rater.n_ctx
+    prior = None
+    if zero not in cands:
+        prior = [1.0] * len(cands) + [0.0]
+    found = rater.rate_contexts(texts, cands + ([zero] if prior else []), prior=prior, streams=streams, precision=precision,
+                                want_probs=False)
+    for name, text, one in zip(names, texts, found):
+        preds = max(len(text) - 1, 1)
+        order = sorted(range(len(cands)), key=lambda c: (-one.posterior[c], c))[:top]
+        line = {"file": name, "chars": len(text), "best": cands[one.best], "margin_bits": None if one.margin == float("inf") else one.margin,      # (None: no other candidate)
+                "top": [[cands[c], float(one.posterior[c])] for c in order],
+                "bits_per_char": float(one.bits[one.best]) / preds, "bits_per_char_mixture": one.mix_bits / preds}
+        if prior:
+            line["bits_per_char_context0"] = float(one.bits[-1]) / preds
         click.echo(json.dumps(line, ensure_ascii=False))
 
 
