@@ -19,6 +19,8 @@
  *   ... and the suspects' alternatives rescored against what follows  kl_variant_windows (rows for kl_rate_window(_bulk))
  *   ... with a lost character inserted in front of the suspect         kl_edit_windows
  *   ... for caller-supplied replacements of spans of the text          kl_span_windows, kl_span_pick
+ *   ... per word: the words found, rated and the suspect ones picked out  kl_word_bounds, kl_rate_segments, kl_segment_select
+ *       (the processor's mean probability per TextEquiv substring, wrapper/rate.py:308-317, for a whole corpus)
  *   model.predict_on_batch, stateful (1,1) step, :566        kl_forward_window with T = 1
  *   model.predict_on_batch, incremental + states, :631       kl_step_batch
  *   ... once per character of a lattice edge, :796-851       kl_walk_batch_host (all characters of all hypotheses, one call)
@@ -372,6 +374,71 @@ int kl_rate_scatter_planes(const float* tprob, const int64_t* plan, const int32_
                            size_t ld, size_t n_out, void* stream);
 int kl_context_mix(const float* planes, size_t ld, const int64_t* offsets, int n_texts, int C, const double* log2prior, float* mix,
                    double* cand_bits, double* mix_bits, double* post, int32_t* best, double* margin, void* stream);
+
+/* Word-level ratings over corpus-order results (what kl_rate_scatter(_alts) filled): the words of the texts, a rating of every
+ * segment, and the segments that look wrong picked out -- all on the device, in three calls.  No handle.  offsets (device int64
+ * [n_texts + 1], ascending, repeated values -- empty texts -- allowed) as in kl_rate_text_bits throughout.  The two compactions
+ * follow kl_rate_select: counts per KL_RATE_SELECT_BLOCK consecutive items, ONE workgroup of KL_RATE_SELECT_SCAN_THREADS threads
+ * for the offsets, a third launch that places the records (the counting call stops after the second); plain launches on
+ * `stream`, no atomics, no workgroup waits for another, and the output depends on indices only: two calls on the same input
+ * agree bit for bit.  KL_ERR_ARG and KL_ERR_WORKSPACE are returned before anything is launched.
+ *
+ * kl_word_bounds: the tokeniser.  corpus (device int32 [n_corpus]) the ids, delim (device uint8 [V]) nonzero for the ids that
+ *   separate words.  With lo = max(offsets[0], 0) and hi = min(n_corpus, offsets[n_texts]):
+ *     is_char(j)  iff  lo <= j < hi  and not (0 <= corpus[j] < V and delim[corpus[j]] != 0)   -- an id outside the table is a
+ *                                                                                                 character
+ *     first(j)    iff  j == offsets[i] for some i
+ *     a word starts at j      iff  is_char(j) and (first(j) or not is_char(j - 1))
+ *     a word ends behind j    iff  is_char(j) and (j + 1 >= hi or first(j + 1) or not is_char(j + 1))
+ *   Starts and ends alternate: the i-th start and the i-th end are one word, and a word never crosses a text boundary.
+ *   count (device int64 [1]) = the number of words, whatever `capacity` is; for i < min(count, capacity), seg_start[i] and
+ *   seg_end[i] (device int64 [capacity]) hold the i-th word in ascending order as [start, end).  Entries beyond are not written;
+ *   capacity == 0 allows null outputs: the counting call.  Nothing outside [0, n_corpus) is read.  ws: device scratch of
+ *   kl_word_bounds_workspace_bytes(n_corpus, n_texts) bytes (one int64 per block; 0 for n_corpus > 2^40 or n_texts < 1), 8-byte
+ *   aligned.  KL_ERR_ARG for null corpus, offsets, delim, count or ws, null outputs with capacity > 0, n_texts < 1, V < 1,
+ *   n_corpus or capacity > 2^40, misaligned pointers (corpus 4 bytes, the others but delim 8); KL_ERR_WORKSPACE if ws_bytes is too
+ *   small.  n_corpus == 0 is valid: count 0.
+ *
+ * kl_rate_segments: probs (device f32 [n]) and rank (device int32 [n], or NULL) in corpus order; seg_start, seg_end (device
+ *   int64 [S]) in any order, segments may overlap.  Segment s = [a, b) belongs to the text i with offsets[i] <= a < offsets[i+1]
+ *   (binary search; empty texts are skipped); its counted positions are the j in
+ *     [max(a, offsets[i] + 1), min(b, offsets[i+1], n))
+ *   -- a text's first character has no prediction and is left out, and a segment ends with its text.  There are none where
+ *   a < 0, b < a, a lies in no text, or a >= n.  Every output is OVERWRITTEN for every s < S:
+ *     seg_n     (int32)  the number of counted positions
+ *     seg_bits  (f64)    -sum log2(fmax((double)probs[j], 1e-99))            (C's fmax: a NaN counts as 1e-99)
+ *     seg_psum  (f64)    sum (double)probs[j], a NaN as it is; seg_psum / seg_n is the mean probability of wrapper/rate.py:308-317
+ *     seg_min   (f32)    a bit copy of the least probs[j] under `<`          (a NaN is never the minimum)
+ *     seg_worst (int64)  that j, the smallest among equal values
+ *     seg_bad   (int32)  how many counted j have rank[j] >= min_rank && probs[j] <= max_prob (kl_rate_select's rule, in f32);
+ *                        0 with rank == NULL
+ *   Where seg_n == 0, or no counted probability is below +inf (all NaN), seg_min is +inf and seg_worst -1.  A group of 16 lanes
+ *   serves a segment: lane l takes the positions first + l, first + l + 16, .. in ascending order, and the 16 partial results
+ *   are folded in a fixed butterfly -- the sums differ from a sequential sum by rounding only.  KL_ERR_ARG for null pointers
+ *   other than rank, S < 1 or > 2^32, n_texts < 1, n > 2^40, min_rank < 0, a NaN max_prob, misaligned pointers (probs, rank,
+ *   seg_n, seg_min and seg_bad 4 bytes, the others 8).  One launch.
+ *
+ * kl_segment_select: the records of S segments as kl_rate_segments wrote them, with seg_start and seg_end.  Segment s is
+ *   selected iff  seg_n[s] >= min_n && seg_bad[s] >= min_bad && seg_bits[s] >= min_bpc * (double)seg_n[s]  (the last in f64).
+ *   count (device int64 [1]) = the number selected, whatever `capacity` is; for i < min(count, capacity), in ascending s,
+ *   sel_index[i] = s (device int64 [capacity]) and sel_start, sel_end, sel_n, sel_bits, sel_psum, sel_min, sel_worst, sel_bad
+ *   (device [capacity], typed as the records) are bit copies of the record.  Entries beyond are not written; capacity == 0
+ *   allows null sel_* pointers: the counting call.  ws: device scratch of kl_segment_select_workspace_bytes(S) bytes (0 for
+ *   S < 1 or S > 2^40), 8-byte aligned.  KL_ERR_ARG for null records, count or ws, S < 1, S or capacity > 2^40, min_n < 1,
+ *   min_bad < 0, min_bpc negative or NaN, null sel_* with capacity > 0, misaligned pointers (seg_n, seg_min, seg_bad and their
+ *   sel_* 4 bytes, the others 8); KL_ERR_WORKSPACE if ws_bytes is too small. */
+size_t kl_word_bounds_workspace_bytes(size_t n_corpus, int n_texts);
+int kl_word_bounds(const int32_t* corpus, size_t n_corpus, const int64_t* offsets, int n_texts, const uint8_t* delim, int V,
+                   size_t capacity, int64_t* seg_start, int64_t* seg_end, int64_t* count, void* ws, size_t ws_bytes, void* stream);
+int kl_rate_segments(const float* probs, const int32_t* rank, size_t n, const int64_t* offsets, int n_texts,
+                     const int64_t* seg_start, const int64_t* seg_end, size_t S, float max_prob, int min_rank, int32_t* seg_n,
+                     double* seg_bits, double* seg_psum, float* seg_min, int64_t* seg_worst, int32_t* seg_bad, void* stream);
+size_t kl_segment_select_workspace_bytes(size_t S);
+int kl_segment_select(const int64_t* seg_start, const int64_t* seg_end, const int32_t* seg_n, const double* seg_bits,
+                      const double* seg_psum, const float* seg_min, const int64_t* seg_worst, const int32_t* seg_bad, size_t S,
+                      int min_n, int min_bad, double min_bpc, size_t capacity, int64_t* sel_index, int64_t* sel_start,
+                      int64_t* sel_end, int32_t* sel_n, double* sel_bits, double* sel_psum, float* sel_min, int64_t* sel_worst,
+                      int32_t* sel_bad, int64_t* count, void* ws, size_t ws_bytes, void* stream);
 
 /* One training batch, forward + backward (rating.py:292-298 -> train_on_batch):
  * writes the gradient of (mean CE + embedding regularisers, rating.py:187-246)

@@ -12,6 +12,7 @@
 // No atomics, no look-back, no spinning; 64-bit indices throughout.  No model: no handle.
 #include "keraslm_hip.h"
 #include "kl_common.h"
+#include "kl_compact.h"
 
 namespace {
 
@@ -19,17 +20,11 @@ constexpr int SEL_THREADS = 256;
 constexpr int SEL_WAVES = SEL_THREADS / KL_WAVE;
 constexpr int SEL_ROUNDS = KL_RATE_SELECT_BLOCK / SEL_THREADS;
 static_assert(SEL_ROUNDS * SEL_THREADS == KL_RATE_SELECT_BLOCK, "a block is a whole number of rounds");
-static_assert(KL_RATE_SELECT_SCAN_THREADS == 4 * KL_WAVE, "rate_select_offsets_kernel folds four waves");
 
 // the selection rule, in f32: a NaN probability compares false
 __device__ __forceinline__ bool selected(const float* __restrict__ probs, const int* __restrict__ rank, long long j, long long n,
                                          float max_prob, int min_rank) {
   return j < n && rank[j] >= min_rank && probs[j] <= max_prob;
-}
-
-// lanes below this one whose bit is set in a wave's ballot
-__device__ __forceinline__ int lanes_before(unsigned long long mask) {
-  return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
 }
 
 __global__ void __launch_bounds__(SEL_THREADS) rate_select_count_kernel(const float* __restrict__ probs,
@@ -57,32 +52,7 @@ __global__ void __launch_bounds__(SEL_THREADS) rate_select_count_kernel(const fl
 __global__ void __launch_bounds__(KL_RATE_SELECT_SCAN_THREADS) rate_select_offsets_kernel(long long* __restrict__ counts,
                                                                                           long long n_blocks,
                                                                                           long long* __restrict__ total) {
-  __shared__ long long wave_sum[4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  long long carry = 0;
-  for (long long b0 = 0; b0 < n_blocks; b0 += KL_RATE_SELECT_SCAN_THREADS) {
-    const long long i = b0 + threadIdx.x;
-    const long long v = i < n_blocks ? counts[i] : 0;
-    long long inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const long long u = __shfl_up(inc, off);
-      if (lane >= off) inc += u;
-    }
-    if (lane == 63) wave_sum[wave] = inc;
-    __syncthreads();
-    long long before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      const long long s = wave_sum[w];
-      before += w < wave ? s : 0;
-      all += s;
-    }
-    if (i < n_blocks) counts[i] = carry + before + inc - v;
-    carry += all;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) total[0] = carry;
+  kl_counts_to_offsets(counts, n_blocks, total);
 }
 
 __global__ void __launch_bounds__(SEL_THREADS) rate_select_place_kernel(
@@ -112,7 +82,7 @@ __global__ void __launch_bounds__(SEL_THREADS) rate_select_place_kernel(
       before += w < wave ? c : 0;
       all += c;
     }
-    const long long to = at + before + lanes_before(mask[r]);
+    const long long to = at + before + kl_lanes_before(mask[r]);
     if (flag[r] && to < capacity) {
       const long long j = base + r * SEL_THREADS + threadIdx.x;
       sel_pos[to] = j;

@@ -88,7 +88,9 @@ class HipLM:
         self.rate_bits = None       # [B] f64: bits per stream accumulated by rate_window
         self._rate_status = None
         self._rate_select_ws = None
-        self.states = None         # [B][2L][W] implicit state of the stateful streams
+        self._word_bounds_ws = None
+        self._segment_select_ws = None
+        self.states = None        # [B][2L][W] implicit state of the stateful streams
         self.pool = None            # [slots][2L][W] explicit states of hypotheses
         self.max_streams_per_launch = 0      # 0: what the kernels address (train_window splits larger batches into groups)
         self._part_grads = None
@@ -626,6 +628,107 @@ class HipLM:
                 _ptr(probs), _ptr(rank), _ptr(alt_id), _ptr(alt_p), n, k, max_prob, min_rank, m, _ptr(out[0]), _ptr(out[1]),
                 _ptr(out[2]), _ptr(out[3]), _ptr(out[4]), _ptr(count), _ptr(ws), ws.numel(), self._stream()), "kl_rate_select")
             call(0, (None,) * 5)
+            m = int(count.item())
+            out = empty(m)
+            if m:
+                call(m, out)
+        return out
+
+    def _scratch(self, slot, n_bytes):
+        """the device scratch kept on the engine under `slot`, grown to n_bytes"""
+        ws = getattr(self, slot)
+        if ws is None or ws.numel() < n_bytes:
+            setattr(self, slot, None)
+            ws = self.torch.empty(max(n_bytes, 8), dtype=self.torch.uint8, device=self.device)
+            setattr(self, slot, ws)
+        return ws
+
+    def word_bounds(self, corpus_d, offsets_d, delim_d):
+        """kl_word_bounds over corpus_d int32 [n] and offsets_d int64 [n_texts + 1] as bulk rating keeps them and delim_d uint8
+        [V] (nonzero: the id separates words) -- DEVICE tensors: the words of the texts as DEVICE tensors (start int64 [m], end
+        int64 [m]), ascending, [start, end) in corpus positions; the statement is ratebulk.word_bounds_host.  One counting call,
+        one read of the count -- the only wait --, buffers of exactly that size, one writing call; nothing more is launched
+        when the count is 0."""
+        torch = self.torch
+        tensors = (corpus_d, offsets_d, delim_d)
+        if ([t.dtype for t in tensors] != [torch.int32, torch.int64, torch.uint8] or any(t.dim() != 1 for t in tensors)
+                or offsets_d.numel() < 2 or delim_d.numel() < 1 or not all(t.is_contiguous() and t.is_cuda for t in tensors)):
+            raise hipabi.KlError("word_bounds: corpus int32 [n], offsets int64 [n_texts + 1], delim uint8 [V], contiguous, on the "
+                                 "device")
+        dev = self.device
+        n, n_texts, V = corpus_d.numel(), offsets_d.numel() - 1, delim_d.numel()
+        empty = lambda m: (torch.empty(m, dtype=torch.int64, device=dev), torch.empty(m, dtype=torch.int64, device=dev))
+        if n == 0:
+            return empty(0)
+        with self._launch():
+            ws = self._scratch("_word_bounds_ws", self.lib.kl_word_bounds_workspace_bytes(n, n_texts))
+            count = torch.zeros(1, dtype=torch.int64, device=dev)
+            call = lambda m, out: hipabi.check(self.lib.kl_word_bounds(
+                _ptr(corpus_d), n, _ptr(offsets_d), n_texts, _ptr(delim_d), V, m, _ptr(out[0]), _ptr(out[1]), _ptr(count),
+                _ptr(ws), ws.numel(), self._stream()), "kl_word_bounds")
+            call(0, (None, None))
+            m = int(count.item())
+            out = empty(m)
+            if m:
+                call(m, out)
+        return out
+
+    def rate_segments(self, probs, rank, offsets_d, seg_start, seg_end, max_prob=0.0, min_rank=0):
+        """kl_rate_segments over corpus-order DEVICE arrays probs f32 [n] and rank int32 [n] (None: no suspects are counted),
+        offsets_d int64 [n_texts + 1] and the segments seg_start, seg_end int64 [S] (any order, overlap allowed): the DEVICE
+        tensors (n int32, bits f64, psum f64, min f32, worst int64, bad int32), each [S]; the statement is
+        ratebulk.segments_host.  No synchronisation."""
+        torch = self.torch
+        tensors = [probs, offsets_d, seg_start, seg_end] + ([rank] if rank is not None else [])
+        kinds = [torch.float32, torch.int64, torch.int64, torch.int64] + ([torch.int32] if rank is not None else [])
+        n, S = probs.numel(), seg_start.numel()
+        if ([t.dtype for t in tensors] != kinds or any(t.dim() != 1 for t in tensors) or offsets_d.numel() < 2
+                or seg_end.numel() != S or (rank is not None and rank.numel() != n)
+                or not all(t.is_contiguous() and t.is_cuda for t in tensors)):
+            raise hipabi.KlError("rate_segments: probs f32 / rank int32 [n], offsets int64 [n_texts + 1], seg_start / seg_end int64 "
+                                 "[S], contiguous, on the device")
+        min_rank = int(min_rank)
+        max_prob = float(np.float32(max_prob))
+        if min_rank < 0 or max_prob != max_prob:
+            raise ValueError("rate_segments: min_rank >= 0 and max_prob not NaN")
+        dev = self.device
+        with self._launch():
+            out = tuple(torch.empty(S, dtype=kind, device=dev)
+                        for kind in (torch.int32, torch.float64, torch.float64, torch.float32, torch.int64, torch.int32))
+            if S:
+                hipabi.check(self.lib.kl_rate_segments(
+                    _ptr(probs), _ptr(rank), n, _ptr(offsets_d), offsets_d.numel() - 1, _ptr(seg_start), _ptr(seg_end), S, max_prob,
+                    min_rank, *([_ptr(t) for t in out] + [self._stream()])), "kl_rate_segments")
+        return out
+
+    def segment_select(self, seg_start, seg_end, records, min_n=1, min_bad=1, min_bpc=0.0):
+        """kl_segment_select over seg_start, seg_end int64 [S] and the records `rate_segments` returned (DEVICE tensors): the
+        segments with n >= min_n, bad >= min_bad and bits >= min_bpc * n, ascending, as DEVICE tensors (index int64 [m], start,
+        end, n, bits, psum, min, worst, bad -- bit copies of the records); the statement is ratebulk.segment_select_host.  One
+        counting call, one read of the count -- the only wait --, buffers of exactly that size, one writing call; nothing more
+        is launched when the count is 0."""
+        torch = self.torch
+        src = (seg_start, seg_end) + tuple(records)
+        kinds = [torch.int64, torch.int64, torch.int32, torch.float64, torch.float64, torch.float32, torch.int64, torch.int32]
+        S = seg_start.numel()
+        if (len(src) != 8 or [t.dtype for t in src] != kinds or any(tuple(t.shape) != (S,) for t in src)
+                or not all(t.is_contiguous() and t.is_cuda for t in src)):
+            raise hipabi.KlError("segment_select: seg_start / seg_end int64 and the six records of rate_segments, [S] each, "
+                                 "contiguous, on the device")
+        min_n, min_bad, min_bpc = int(min_n), int(min_bad), float(min_bpc)
+        if min_n < 1 or min_bad < 0 or not min_bpc >= 0.0:
+            raise ValueError("segment_select: min_n >= 1, min_bad >= 0 and min_bpc >= 0, not NaN")
+        dev = self.device
+        empty = lambda m: tuple(torch.empty(m, dtype=kind, device=dev) for kind in [torch.int64] + kinds)
+        if S == 0:
+            return empty(0)
+        with self._launch():
+            ws = self._scratch("_segment_select_ws", self.lib.kl_segment_select_workspace_bytes(S))
+            count = torch.zeros(1, dtype=torch.int64, device=dev)
+            call = lambda m, out: hipabi.check(self.lib.kl_segment_select(
+                *([_ptr(t) for t in src] + [S, min_n, min_bad, min_bpc, m] + [_ptr(t) for t in out]
+                  + [_ptr(count), _ptr(ws), ws.numel(), self._stream()])), "kl_segment_select")
+            call(0, (None,) * 9)
             m = int(count.item())
             out = empty(m)
             if m:

@@ -266,6 +266,76 @@ class ContextRating(object):
         return len(self.bits)
 
 
+class Words(object):
+    """One text's share of `Rater.suspect_words`, m words in ascending order:
+
+    start      [m] i64    position of the word in the normalised text
+    length     [m] i32    its number of characters
+    n          [m] i32    how many of them the model predicted (the text's first character has no prediction)
+    bits       [m] f64    bits of the word: -sum log2(max(p, 1e-99)) over its predicted characters
+    mean_prob  [m] f64    mean probability over the predicted characters (NaN where n is 0)
+    min_prob   [m] f32    the least probability (+inf where n is 0)
+    worst      [m] i64    position in the text of the least probable character, the first among equal ones (-1 where n is 0)
+    suspects   [m] i32    how many of its characters are suspects (`Rater.suspects`' rule)
+    """
+
+    def __init__(self, start, length, n, bits, mean_prob, min_prob, worst, suspects):
+        self.start, self.length, self.n, self.bits, self.mean_prob = start, length, n, bits, mean_prob
+        self.min_prob, self.worst, self.suspects = min_prob, worst, suspects
+
+    @classmethod
+    def from_records(cls, start, end, n, bits, psum, least, worst, bad, offset=0):
+        """from records in corpus positions (ratebulk.segments_host with their segments) of a text that begins at `offset` -- or
+        of many texts, with one offset per record"""
+        start, end, worst = (np.asarray(a, dtype=np.int64) for a in (start, end, worst))
+        n = np.asarray(n, dtype=np.int32)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            mean = np.where(n > 0, np.asarray(psum, dtype=np.float64) / np.maximum(n, 1), np.nan)
+        return cls(start - offset, (end - start).astype(np.int32), n, np.asarray(bits, dtype=np.float64), mean,
+                   np.asarray(least, dtype=np.float32), np.where(worst >= 0, worst - offset, -1), np.asarray(bad, dtype=np.int32))
+
+    def __len__(self):
+        return len(self.start)
+
+    def cut(self, a, b):
+        """the records a .. b - 1 as a result of their own"""
+        return type(self)(*(f[a:b] for f in (self.start, self.length, self.n, self.bits, self.mean_prob, self.min_prob,
+                                             self.worst, self.suspects)))
+
+    def spans(self):
+        """the words as [(start, end)] in the normalised text"""
+        return [(int(a), int(a) + int(m)) for a, m in zip(self.start, self.length)]
+
+    def strings(self, text):
+        """the words as strings; text is the normalised text"""
+        return [text[a:b] for a, b in self.spans()]
+
+
+class Segments(Words):
+    """One text's share of `Rater.rate_segments`: `Words`' fields for the caller's segments of that text, in the order given
+    (`suspects` are zeros: no ranks are computed)."""
+
+
+def word_edits(found, texts, candidates):
+    """Edits for `Rater.rescore` from the words `Rater.suspect_words` found: found is one `Words` per text, candidates a dict or
+    a callable word -> list of replacement strings (a lexicon look-up, a spell checker, a second engine's token).  One edit
+    (i, start, end, replacements) per word that yields replacements; a word that yields none is skipped, and so is a word at a
+    text's first character (no prediction to be held against).  Ordered by text and start.  Host only."""
+    if len(found) != len(texts):
+        raise ValueError("word_edits: one Words per text")
+    look_up = candidates if callable(candidates) else (lambda word: candidates.get(word, ()))
+    edits = []
+    for i, (words, text) in enumerate(zip(found, texts)):
+        text = windows.normalize(text)
+        for start, end in sorted(words.spans()):
+            if start < 1:
+                continue
+            replacements = list(look_up(text[start:end]) or ())
+            if replacements:
+                edits.append((i, start, end, replacements))
+    return edits
+
+
 def confusion_edits(texts, rules, at=None):
     """Edits for `Rater.rescore` from a table of known confusions: rules is a list of (source, [replacements]) with a non-empty
     source; one edit (i, start, end, replacements) per occurrence of a source in the NFC-normalised texts[i], overlapping

@@ -23,8 +23,10 @@ kl_variant_windows / kl_edit_windows make of the suspects for `Rater.corrections
 variants (numpy on every path: S * R doubles); `span_windows_host` and `span_pick_host` what kl_span_windows and kl_span_pick
 make of spans with caller-supplied replacements for `Rater.rescore`.  `plan_candidates` is the plan of `Rater.rate_contexts`
 -- every text under every one of C candidate contexts, the pairs as plan rows over the one corpus --, and
-`scatter_planes_host` and `context_mix_host` state what kl_rate_scatter_planes and kl_context_mix make of its calls.  numpy
-only: the plan is built and tested without an engine.
+`scatter_planes_host` and `context_mix_host` state what kl_rate_scatter_planes and kl_context_mix make of its calls.
+`word_bounds_host`, `segments_host` and `segment_select_host` state kl_word_bounds, kl_rate_segments and kl_segment_select: the
+words of the texts, a rating per segment and the ordered selection among them (`Rater.suspect_words`, `Rater.rate_segments`).
+numpy only: the plan is built and tested without an engine.
 """
 from __future__ import annotations
 
@@ -567,3 +569,98 @@ def context_mix_host(planes, offsets, log2prior=None, mix=None):
             second = rest.max() if len(rest) else -np.inf
             margin[i] = np.inf if np.isneginf(second) else lw[best[i]] - second
     return cand_bits, mix_bits, post, best, margin
+
+
+def word_bounds_host(corpus, offsets, delim):
+    """what kl_word_bounds computes: the words of the texts as (seg_start, seg_end) int64, ascending, [start, end) in corpus
+    positions.  corpus [n] ids, offsets [n_texts + 1] ascending (repeated values: empty texts), delim [V] nonzero for the ids that
+    separate words.  With lo = max(offsets[0], 0) and hi = min(n, offsets[n_texts]): position j is a character iff
+    lo <= j < hi and not (0 <= corpus[j] < V and delim[corpus[j]] != 0) -- an id outside the table is a character --, it is a
+    text's first iff j == offsets[i] for some i; a word starts at a character that is a first or follows no character, and ends
+    behind a character that is the last below hi, or is followed by a first or by no character.  A word never crosses a text
+    boundary."""
+    corpus = np.asarray(corpus).reshape(-1)
+    offsets = np.asarray(offsets, dtype=np.int64).reshape(-1)
+    delim = np.asarray(delim).reshape(-1)
+    n, V = len(corpus), len(delim)
+    if len(offsets) < 2 or V < 1:
+        raise ValueError("word_bounds_host: one text and one table entry at least")
+    lo, hi = max(int(offsets[0]), 0), min(n, int(offsets[-1]))
+    char = np.zeros(n + 2, dtype=bool)           # (char[j + 1] is position j: one position of no character on either side)
+    first = np.zeros(n + 2, dtype=bool)
+    if hi > lo:
+        ids = corpus[lo:hi].astype(np.int64)
+        known = (ids >= 0) & (ids < V)
+        char[lo + 1:hi + 1] = ~(known & (delim[np.where(known, ids, 0)] != 0))
+    inside = offsets[(offsets >= 0) & (offsets <= n)]
+    first[inside + 1] = True
+    here, before, after = char[1:n + 1], char[0:n], char[2:n + 2]
+    start = here & (first[1:n + 1] | ~before)
+    end = here & (first[2:n + 2] | ~after)        # (hi itself is no character: the last one below it ends a word)
+    return np.nonzero(start)[0].astype(np.int64), np.nonzero(end)[0].astype(np.int64) + 1
+
+
+def segments_host(probs, rank, offsets, seg_start, seg_end, max_prob=0.0, min_rank=0):
+    """what kl_rate_segments computes over probs [n] f32 and rank [n] int32 (or None) in corpus order: per segment s =
+    [seg_start[s], seg_end[s]) -- any order, overlap allowed -- of the text i with offsets[i] <= seg_start[s] < offsets[i + 1]
+    (empty texts are skipped), over its counted positions j in [max(a, offsets[i] + 1), min(b, offsets[i + 1], n)) (none where
+    a < 0, b < a, a lies in no text or a >= n), sequentially in f64:
+      seg_n int32, seg_bits = -sum log2(np.fmax(probs[j], 1e-99)) (a NaN counts as 1e-99), seg_psum = sum probs[j] (a NaN as it
+      is), seg_min f32 the least probs[j] under `<` (a bit copy; a NaN is never it) and seg_worst int64 its j, the smallest among
+      equal values -- +inf and -1 where nothing is counted or nothing counted lies below +inf --, seg_bad int32 the counted j
+      with rank[j] >= min_rank and probs[j] <= float32(max_prob) (0 without rank).
+    Returns (seg_n, seg_bits, seg_psum, seg_min, seg_worst, seg_bad)."""
+    min_rank = int(min_rank)
+    limit = np.float32(max_prob)
+    if min_rank < 0 or np.isnan(limit):
+        raise ValueError("min_rank >= 0 and max_prob not NaN")
+    probs = np.asarray(probs, dtype=np.float32).reshape(-1)
+    offsets = np.asarray(offsets, dtype=np.int64).reshape(-1)
+    seg_start = np.asarray(seg_start, dtype=np.int64).reshape(-1)
+    seg_end = np.asarray(seg_end, dtype=np.int64).reshape(-1)
+    n, n_texts, S = len(probs), len(offsets) - 1, len(seg_start)
+    if n_texts < 1 or len(seg_end) != S:
+        raise ValueError("segments_host: one text at least, and one end per start")
+    with np.errstate(invalid="ignore", divide="ignore"):
+        logs = -np.log2(np.fmax(probs.astype(np.float64), 1e-99))
+        bad = np.zeros(n, dtype=bool) if rank is None else (np.asarray(rank).reshape(-1) >= min_rank) & (probs <= limit)
+    text = np.searchsorted(offsets, seg_start, side="right") - 1      # (the largest i with offsets[i] <= a)
+    seg_n = np.zeros(S, dtype=np.int32)
+    seg_bits = np.zeros(S, dtype=np.float64)
+    seg_psum = np.zeros(S, dtype=np.float64)
+    seg_min = np.full(S, np.inf, dtype=np.float32)
+    seg_worst = np.full(S, -1, dtype=np.int64)
+    seg_bad = np.zeros(S, dtype=np.int32)
+    for s in range(S):
+        a, b, i = int(seg_start[s]), int(seg_end[s]), int(text[s])
+        if a < 0 or b < a or a >= n or not 0 <= i < n_texts:
+            continue
+        lo, hi = max(a, int(offsets[i]) + 1), min(b, int(offsets[i + 1]), n)
+        if hi <= lo:
+            continue
+        p = probs[lo:hi]
+        seg_n[s] = hi - lo
+        seg_bits[s] = np.add.accumulate(logs[lo:hi])[-1]
+        seg_psum[s] = np.add.accumulate(p.astype(np.float64))[-1]
+        seg_bad[s] = int(bad[lo:hi].sum())
+        least = np.fmin.reduce(p)                 # (np.fmin passes a NaN over)
+        if least < np.inf:
+            at = int(np.argmax(p == least))       # (the first of equal values)
+            seg_min[s], seg_worst[s] = p[at], lo + at
+    return seg_n, seg_bits, seg_psum, seg_min, seg_worst, seg_bad
+
+
+def segment_select_host(seg_start, seg_end, seg_n, seg_bits, seg_psum, seg_min, seg_worst, seg_bad, min_n=1, min_bad=1,
+                        min_bpc=0.0):
+    """what kl_segment_select computes: the segments s with seg_n[s] >= min_n, seg_bad[s] >= min_bad and
+    seg_bits[s] >= min_bpc * float64(seg_n[s]), ascending -- equality selects, NaN bits never do.  Returns (index int64 [m],
+    start, end, n, bits, psum, min, worst, bad): copies of the selected records."""
+    min_n, min_bad, min_bpc = int(min_n), int(min_bad), float(min_bpc)
+    if min_n < 1 or min_bad < 0 or not min_bpc >= 0.0:
+        raise ValueError("min_n >= 1, min_bad >= 0 and min_bpc >= 0, not NaN")
+    records = [np.asarray(a).reshape(-1) for a in (seg_start, seg_end, seg_n, seg_bits, seg_psum, seg_min, seg_worst, seg_bad)]
+    n, bits, bad = records[2], records[3], records[7]
+    with np.errstate(invalid="ignore"):
+        keep = (n >= min_n) & (bad >= min_bad) & (bits.astype(np.float64) >= min_bpc * n.astype(np.float64))
+    index = np.nonzero(keep)[0].astype(np.int64)
+    return (index,) + tuple(a[index] for a in records)

@@ -1179,6 +1179,143 @@ class Rater(object):
             sel = [_np(t) for t in lm.rate_select(*arrays, max_prob=float(limit), min_rank=min_rank)]
         return [ratebatch.Suspects(*one) for one in self._selection_per_text(sel, plan.offsets)], bits
 
+    def _delimiter_table(self, delimiters):
+        '''uint8 [voc_size]: 1 at the ids of the characters that separate words -- those of the (normalised) string, or every
+        mapped character with str.isspace(); characters outside the mapping have no id of their own and are left out'''
+        chars = [c for c in self.mapping[0] if c.isspace()] if delimiters is None else windows.normalize(delimiters)
+        table = np.zeros(self.voc_size, dtype=np.uint8)
+        for c in chars:
+            if 0 < self.mapping[0].get(c, 0) < self.voc_size:
+                table[self.mapping[0][c]] = 1
+        return table
+
+    def suspect_words(self, texts, contexts=None, delimiters=None, k=3, streams=1024, max_prob=0.01, min_rank=1, min_suspects=1,
+                      min_bits_per_char=0.0, min_chars=1, precision="bf16"):
+        '''Which WORDS does the model not believe?  `suspects` per word, for whoever looks words up -- a lexicon, a spell
+        checker, a second OCR engine's token (`ratebatch.word_edits` makes `rescore`'s edits of them).  Returns (found, bits),
+        both in input order: `bits` is as in `rate_batch`, `found[i]` a ratebatch.Words holding, in ascending order, the words
+        of the normalised texts[i] with at least `min_chars` predicted characters, at least `min_suspects` suspect characters
+        (rank >= min_rank and probability <= np.float32(max_prob), as in `suspects`) and at least `min_bits_per_char` bits per
+        predicted character -- with their bits, mean and least probability, the place of the least probable character and the
+        number of suspects.
+
+        A word is a maximal run of characters that are no delimiters, within one text.  delimiters is a string; the default is
+        every mapped character with str.isspace().  A whitespace character outside the mapping has id 0, as every unmapped
+        character has, and is part of a word; so is a character of `delimiters` that is not mapped.  A text's first character
+        has no prediction: it belongs to its word (`start`, `length`) but not to the word's ratings (`n`).
+
+        On the HIP engine everything stays on the device in corpus order, as in `suspects`: `word_bounds` finds the words,
+        `rate_segments` rates them, `segment_select` picks them out, and 52 bytes per selected word plus the bits leave the
+        device; the selection is cut per text on the host (`_words_per_text`: the texts without a word share one empty result).  An engine without `rate_segments` runs `rate_alternatives` and the numpy statements of ratebulk.py.  texts,
+        contexts, k, streams and precision are as in `suspects` (k only sizes the rating pass), and so are the state and the
+        precision afterwards.  ValueError for a stateless rater, min_suspects < 0, min_chars < 1, a negative or NaN
+        min_bits_per_char.'''
+        texts, contexts, k, limit, min_rank = self._rating_request("suspect_words", texts, contexts, precision, k, max_prob,
+                                                                   min_rank)
+        min_suspects, min_chars, min_bpc = int(min_suspects), int(min_chars), float(min_bits_per_char)
+        if min_suspects < 0 or min_chars < 1 or not min_bpc >= 0.0:
+            raise ValueError("min_suspects >= 0, min_chars >= 1 and min_bits_per_char >= 0 (got %d, %d, %r)"
+                             % (min_suspects, min_chars, min_bits_per_char))
+        delim = self._delimiter_table(delimiters)
+        rule = dict(min_n=min_chars, min_bad=min_suspects, min_bpc=min_bpc)
+        lm = self.model
+        if not hasattr(lm, 'rate_segments'):
+            # an engine without the device path (the tests' CPU double): rate_alternatives and the numpy statements, per text
+            rated, bits = self.rate_alternatives(texts, contexts, k=k, streams=streams, precision=precision)
+            found = []
+            for text, one in zip(texts, rated):
+                ids = windows.encode(windows.normalize(text), self.mapping[0])
+                offsets = np.asarray([0, len(ids)], dtype=np.int64)
+                start, end = ratebulk.word_bounds_host(ids, offsets, delim)
+                records = ratebulk.segments_host(one.probs, one.rank, offsets, start, end, limit, min_rank)
+                found.append(ratebatch.Words.from_records(*ratebulk.segment_select_host(start, end, *records, **rule)[1:]))
+            return found, bits
+        keep = {}
+        plan, arrays, bits = self._rate_in_corpus_order(texts, contexts, k, streams, precision, keep=keep)
+        sel = None
+        if arrays is not None:
+            start, end = lm.word_bounds(keep["corpus"], keep["offsets"], lm.torch.from_numpy(delim).to(lm.device))
+            if start.numel():
+                records = lm.rate_segments(arrays[0], arrays[1], keep["offsets"], start, end, float(limit), min_rank)
+                sel = [_np(t) for t in lm.segment_select(start, end, records, **rule)[1:]]      # (all but the index)
+        if sel is None:
+            sel = [np.zeros(0, dtype=kind) for kind in (np.int64, np.int64, np.int32, np.float64, np.float64, np.float32,
+                                                        np.int64, np.int32)]
+        return self._words_per_text(sel, plan.offsets), bits
+
+    @staticmethod
+    def _words_per_text(sel, offsets):
+        '''A corpus-ordered selection of words (the records of `segment_select` without the index: start, end, n, bits, psum,
+        min, worst, bad; starts ascending) cut per text as `_selection_per_text` cuts: one ratebatch.Words per text.  Positions
+        within the texts and the means are taken for the whole selection at once; a text's share is one slice of views, and the
+        texts without a word (many lines of a corpus of lines) share ONE empty result, as in `rescore`: the split costs per text
+        with a word.'''
+        base = offsets[np.searchsorted(offsets, sel[0], side="right") - 1]
+        whole = ratebatch.Words.from_records(*sel, offset=base)
+        lo = np.searchsorted(sel[0], offsets[:-1], side="left")
+        hi = np.searchsorted(sel[0], offsets[1:], side="left")
+        found = [whole.cut(0, 0)] * (len(offsets) - 1)
+        for i in np.nonzero(hi > lo)[0].tolist():
+            found[i] = whole.cut(int(lo[i]), int(hi[i]))
+        return found
+
+    def rate_segments(self, texts, segments, contexts=None, streams=1024, precision="bf16"):
+        '''How does the model rate these spans of the texts?  The bulk counterpart of the processor's score per TextEquiv
+        substring (a mean over the character probabilities of the substring).  segments is a sequence of (i, start, end):
+        [start, end) is a span of the NFC-normalised texts[i], as in `rescore`'s edits; spans may overlap.  Returns one
+        ratebatch.Segments per text holding that text's spans in the order given (the texts without a span share one empty
+        result): bits, mean and least probability and the
+        place of the least probable character, over the characters of the span that have a prediction (`n`: all but a text's
+        first character; an empty span, or the first character alone, has n 0, bits 0.0, mean NaN, least +inf, worst -1).
+        No ranks are computed: `suspects` are zeros.
+
+        On the HIP engine the texts are rated with probabilities only (the bulk plan of `rate_batch(precision="bf16")`, or the
+        same plan through `rate_window` for "split"), the probabilities stay on the device in corpus order, `rate_segments`
+        reduces them per span, and 36 bytes per span leave the device -- no per-character array does.  An engine without
+        `rate_segments` runs `rate_batch` and the numpy statement.  ValueError for a stateless rater, a text index out of
+        range, a span outside its text or with end < start.  State and precision afterwards are as after `suspects`.'''
+        texts, contexts = self._rating_request("rate_segments", texts, contexts, precision)[:2]
+        if not self.stateful:
+            raise ValueError('rate_segments needs a stateful rater: it rates through stateful windows')
+        n = len(texts)
+        sizes = np.asarray([len(windows.normalize(t)) for t in texts], dtype=np.int64)
+        segments = list(segments)
+        S = len(segments)
+        as_array = lambda k: np.asarray([int(e[k]) for e in segments], dtype=np.int64).reshape(S)
+        span_text, starts, ends = as_array(0), as_array(1), as_array(2)
+        if ((span_text < 0) | (span_text >= n)).any():
+            raise ValueError("rate_segments: text index %d out of range" % span_text[(span_text < 0) | (span_text >= n)][0])
+        bad = np.nonzero((starts < 0) | (ends < starts) | (ends > sizes[span_text]))[0]
+        if len(bad):
+            raise ValueError("rate_segments: span [%d, %d) outside text %d of %d characters"
+                             % (starts[bad[0]], ends[bad[0]], span_text[bad[0]], sizes[span_text[bad[0]]]))
+        offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        seg_start, seg_end = starts + offsets[span_text], ends + offsets[span_text]      # (corpus positions)
+        lm = self.model
+        if not hasattr(lm, 'rate_segments'):
+            # an engine without the device path (the tests' CPU double): rate_batch and the numpy statement
+            probs, _ = self.rate_batch(texts, contexts, streams=streams, precision=precision)
+            flat = np.concatenate([np.zeros(0, dtype=np.float32)] + [np.asarray(p, dtype=np.float32) for p in probs])
+            records = ratebulk.segments_host(flat, None, offsets, seg_start, seg_end)
+        else:
+            keep = {}
+            arrays = self._rate_in_corpus_order(texts, contexts, 0, streams, precision, keep=keep)[1] if S else None
+            if arrays is None:      # (no span, or no text with a prediction -- which the statement needs no engine for)
+                lm.reset_states(1)
+                records = ratebulk.segments_host(np.ones(int(offsets[-1]), dtype=np.float32), None, offsets, seg_start, seg_end)
+            else:
+                up = lambda a: lm.torch.from_numpy(np.ascontiguousarray(a)).to(lm.device)
+                records = [_np(t) for t in lm.rate_segments(arrays[0], None, keep["offsets"], up(seg_start), up(seg_end))]
+        order = np.argsort(span_text, kind="stable")
+        cut = np.searchsorted(span_text[order], np.arange(n + 1), side="left")
+        whole = ratebatch.Segments.from_records(seg_start[order], seg_end[order], *[r[order] for r in records],
+                                                offset=offsets[span_text[order]])
+        # (most texts of a large corpus may hold no span at all: they share ONE empty result, as in `rescore`)
+        found = [whole.cut(0, 0)] * n
+        for i in np.unique(span_text).tolist():
+            found[i] = whole.cut(int(cut[i]), int(cut[i + 1]))
+        return found
+
     def corrections(self, texts, contexts=None, k=3, streams=1024, max_prob=0.01, min_rank=1, left=64, ahead=8, deletions=False,
                     min_gain=1.0, precision="bf16", insertions=False):
         '''`suspects`, and for every suspect: does the text that FOLLOWS read better with one of the model's alternatives than

@@ -17,6 +17,9 @@ table of known confusions (--confusions, gated by a `suspects` pass) -- rated ag
 Additional command `contexts`: per DATA file the context it reads like among the candidates given (--years or --candidates),
 the posterior over them, and its bits under the best one, under their sequential mixture and under context 0
 (Rater.rate_contexts: every file under every candidate in one bulk plan).
+Additional command `words`: per DATA file the words the model does not believe -- at least --min-suspects suspect characters,
+--min-bits-per-char bits per predicted character and --min-chars predicted characters -- with their bits, mean and least
+probability (Rater.suspect_words: rated in bulk, the words found, rated and picked out on the device).
 Additional options on `train`: --streams (stateful streams per GPU, default 1 = the
 reference's batching) and --segment-streams (with fewer files than streams, cut the files
 into contiguous segments on window boundaries, one list of segments per stream).  Under `python -m torch.distributed.run` training is
@@ -33,7 +36,7 @@ import click
 
 from .. import lib
 
-COMMAND_ORDER = ['train', 'test', 'score', 'suspects', 'correct', 'rescore', 'contexts', 'apply', 'generate', 'print-history', 'print-charset', 'prune-charset',
+COMMAND_ORDER = ['train', 'test', 'score', 'suspects', 'correct', 'rescore', 'contexts', 'words', 'apply', 'generate', 'print-history', 'print-charset', 'prune-charset',
                  'plot-char-embeddings-similarity', 'plot-context-embeddings-similarity', 'plot-context-embeddings-projection']
 
 
@@ -480,6 +483,53 @@ def contexts(model, streams, precision, years, candidates, top, data):
         if prior:
             line["bits_per_char_context0"] = float(one.bits[-1]) / preds
         click.echo(json.dumps(line, ensure_ascii=False))
+
+
+@cli.command(short_help='list the words of every file that the model does not believe')
+@click.option('-m', '--model', default="model.h5", show_default=True, help='model file', type=click.Path(dir_okay=False, exists=True))
+@click.option('-s', '--streams', default=1024, show_default=True, help='files rated in lockstep, one per row of a window call',
+              type=click.IntRange(min=1, max=4096))
+@click.option('--precision', default='bf16', show_default=True, type=click.Choice(['bf16', 'split']),
+              help='bf16: bulk rating on the training forward; split: the inference kernels, ~f32 accuracy')
+@click.option('-k', 'k', default=3, show_default=True, type=click.IntRange(min=1, max=8),
+              help='alternatives ranked per character in the rating pass')
+@click.option('--max-prob', default=0.01, show_default=True, type=click.FLOAT,
+              help='a suspect character has at most this probability')
+@click.option('--min-rank', default=1, show_default=True, type=click.IntRange(min=0),
+              help='... and at least this rank among the characters the model could have written (0: its first choice)')
+@click.option('--min-suspects', default=1, show_default=True, type=click.IntRange(min=0),
+              help='a listed word has at least this many suspect characters')
+@click.option('--min-bits-per-char', default=0.0, show_default=True, type=click.FloatRange(min=0.0),
+              help='... at least this many bits per predicted character')
+@click.option('--min-chars', default=1, show_default=True, type=click.IntRange(min=1),
+              help='... and at least this many predicted characters')
+@click.option('--delimiters', default=None, help='the characters that separate words [default: the mapped whitespace characters]')
+@click.argument('data', nargs=-1, type=click.Path(exists=True, dir_okay=True, file_okay=True))
+def words(model, streams, precision, k, max_prob, min_rank, min_suspects, min_bits_per_char, min_chars, delimiters, data):
+    """Apply a language model to DATA files and print one JSON line per file: characters, bits per
+       character and the suspect words as [start, word, n, bits, mean_prob, min_prob, worst, suspects].
+
+       Files are read, and given their contexts, as `score` does.  Only the listed words leave the device.
+    """
+    from ..lib import windows
+    rater = _load(model)
+    names, texts, contexts = [], [], []
+    for file in _open_all(data):
+        with file:
+            texts.append(windows.normalize(file.read()))
+        names.append(file.name)
+        contexts.append(windows.context_from_filename(file.name))
+    if not texts:
+        return
+    found, bits = rater.suspect_words(texts, contexts, delimiters=delimiters, k=k, streams=streams, max_prob=max_prob,
+                                      min_rank=min_rank, min_suspects=min_suspects, min_bits_per_char=min_bits_per_char,
+                                      min_chars=min_chars, precision=precision)
+    for name, text, one, total in zip(names, texts, found, bits):
+        rows = [[int(a), word, int(n), float(b), float(mean), float(least), int(worst), int(bad)]
+                for a, word, n, b, mean, least, worst, bad in zip(one.start, one.strings(text), one.n, one.bits, one.mean_prob,
+                                                                  one.min_prob, one.worst, one.suspects)]
+        click.echo(json.dumps({"file": name, "chars": len(text), "bits_per_char": float(total) / max(len(text) - 1, 1),
+                               "words": rows}, ensure_ascii=False))
 
 
 @cli.command(short_help='sample characters from language model')
