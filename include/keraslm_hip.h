@@ -606,6 +606,52 @@ int kl_sample_pick_from(kl_handle* h, int rows, uint32_t row0, const float* prob
                         int top_k, float floor, uint64_t seed, uint32_t step, const float* cum_in, int32_t* idx_next,
                         float* cum_next, float* u_log, void* ws, size_t ws_bytes, void* stream);
 
+/* THE BEAM BOOKKEEPING OF MANY LATTICE EDGES ON THE DEVICE (rating.py:796-851, Rater.rate_best_batch): after one
+ * kl_walk_batch_host over the hypotheses of E edges, two launches turn its probabilities into every edge's new beam.  The
+ * statement both implement is lib/lattice_batch.py (edge_costs_host, edge_decode_host): results agree with it bit for bit.
+ * Both: caller's stream, no device memory owned, no host synchronisation, nothing launched when a code is returned; two calls
+ * on the same inputs are bit-identical.  All pointers are DEVICE pointers (probs may be device-visible host memory).
+ *
+ * kl_edge_costs: cost[s] = -(log(max((double)probs[s], 1e-99)) / log(2.0)) * lm_weight + alt_conf[pair_alt[s]] for the n_pairs
+ *   (track, step) pairs, every operation an IEEE f64 operation of its own (what the host computes with math.log(p, 2); the
+ *   device's log is within 1 ulp of the host's).  probs may be the walk's kl_host_alloc result buffer: launched on the walk's
+ *   stream it reads what the walk delivered, without a host wait in between.  KL_ERR_ARG: null or misaligned pointers, n_pairs
+ *   outside 1 .. 2^40, a NaN lm_weight.
+ *
+ * kl_edge_decode: E edges, one workgroup of one wave each.
+ *   desc [E][8] int32       n_in, n_alt, n_pre, in_off, alt_off, trk_off, pre_off, max_batches -- counts and offsets into:
+ *   cum_in f64              per incoming hypothesis: cumulative cost
+ *   alt_len, alt_class      per alternative: characters, text-class id (equal texts share one)
+ *   step_off, final_slot    per track (hypothesis-major, alternative-minor; track t of an edge = hypothesis t / n_alt,
+ *                           alternative t % n_alt): offset of its step costs in `cost`, slot of its state after the last step
+ *                           (a track of an empty alternative has no steps: final_slot holds its hypothesis' slot)
+ *   pre_cost f64, pre_class, pre_slot   per entry other in-edges already left at the destination, in beam order (may be
+ *                           null if no edge has any)
+ *   cost f64                per (track, step) pair (kl_edge_costs)
+ *   pool, depth_k, dist     history clustering: depth_k = 0 off; else two entries of one class are close when for each of
+ *                           the first depth_k state vectors the squared distance of their slots (kl_state_dist2's sum) is
+ *                           < dist * dist
+ *   batch_size, beam_width  as Rater.batch_size and rate_best's beam_width
+ *   cap_tracks              1 .. 1024: tracks per edge the launch reserves LDS for (46 bytes each + 768)
+ *   out                     one block of kl_edge_decode_out_bytes(E, beam_width, n_tracks, n_pairs) bytes, parts 8-byte aligned:
+ *                           cost f64 [E][beam_width] | count int32 [E] | status [E] | ref [E][beam_width] | consumed
+ *                           [n_tracks] | when [n_pairs].  Per edge: count = survivors (<= beam_width), ref = track number or
+ *                           -1 - j for the j-th pre-existing entry, cost = its cumulative cost (entries beyond count: 0);
+ *                           consumed = characters every track took; when[step_off + k] = batch number * 1024 + place in
+ *                           the batch at which a track took its k-th step (defined for the steps taken).
+ *   status 1: the edge was not decoded (n_in * n_alt > cap_tracks, n_pre > 64, an alternative above 65535 characters,
+ *   max_batches outside 1 .. 2^20, negative counts, a NaN cost); count is 0, its other outputs are undefined, other edges are
+ *   not affected.  KL_ERR_ARG: null or misaligned pointers, E, batch_size, beam_width < 1, cap_tracks outside 1 .. 1024,
+ *   depth_k outside 0 .. 2 * depth, depth_k > 0 without pool or with a NaN dist; KL_ERR_WORKSPACE: out_bytes too small. */
+int kl_edge_costs(long n_pairs, const float* probs, const int32_t* pair_alt, const double* alt_conf, double lm_weight,
+                  double* cost, void* stream);
+size_t kl_edge_decode_out_bytes(int n_edges, int beam_width, long n_tracks, long n_pairs);
+int kl_edge_decode(const kl_handle* h, int n_edges, const int32_t* desc, const double* cum_in, const int32_t* alt_len,
+                   const int32_t* alt_class, const int32_t* step_off, const int32_t* final_slot,
+                   const double* pre_cost, const int32_t* pre_class, const int32_t* pre_slot, const double* cost,
+                   const float* pool, int depth_k, double dist, int batch_size, int beam_width, int cap_tracks, long n_tracks,
+                   long n_pairs, void* out, size_t out_bytes, void* stream);
+
 /* Squared L2 distances between state vectors of pool slots, for beam history
  * clustering (rating.py:887-916): out[i] = || pool[a[i]][k] - pool[b[i]][k] ||^2
  * for state entry k (0 = h1, 1 = c1, ...). */

@@ -25,6 +25,7 @@
 
 #include "kl_common.h"
 #include "kl_kernels.h"
+#include "kl_state_dist.h"
 
 namespace {
 
@@ -1033,10 +1034,7 @@ __global__ void state_dist2_kernel(const float* __restrict__ pool, long slot_str
   if (i >= n) return;
   const float* pa = pool + (long)a[i] * slot_stride + (long)k * W;
   const float* pb = pool + (long)b[i] * slot_stride + (long)k * W;
-  float acc = 0.f;
-  for (int u = lane; u < W; u += 64) { const float q = pa[u] - pb[u]; acc += q * q; }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+  const float acc = kl_wave_dist2(pa, pb, W, lane);      // (kl_state_dist.h: shared with kl_edge_decode)
   if (lane == 0) out[i] = acc;
 }
 
@@ -2292,6 +2290,51 @@ int kl_state_dist2(const kl_handle* h, int n, const float* pool, const int32_t* 
   hipLaunchKernelGGL(state_dist2_kernel, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, pool,
                      (long)2 * h->cfg.depth * W, W, k, a, b, n, out);
   return hip_ok(hipGetLastError());
+}
+
+// ---- the beam bookkeeping of many lattice edges on the device (edge_decode.hip) ----------------------------------------
+int kl_edge_costs(long n_pairs, const float* probs, const int32_t* pair_alt, const double* alt_conf, double lm_weight,
+                  double* cost, void* stream) {
+  if (!probs || !pair_alt || !alt_conf || !cost || n_pairs < 1 || n_pairs > (1L << 40) || lm_weight != lm_weight) return KL_ERR_ARG;
+  if (((uintptr_t)probs | (uintptr_t)pair_alt) & 3 || ((uintptr_t)alt_conf | (uintptr_t)cost) & 7) return KL_ERR_ARG;
+  return kl_launch_edge_costs(n_pairs, probs, pair_alt, alt_conf, lm_weight, cost, (hipStream_t)stream);
+}
+
+static size_t edge_up8(size_t n) { return (n + 7) & ~(size_t)7; }
+
+size_t kl_edge_decode_out_bytes(int n_edges, int beam_width, long n_tracks, long n_pairs) {
+  if (n_edges < 1 || beam_width < 1 || n_tracks < 1 || n_pairs < 0 || n_tracks > (1L << 40) || n_pairs > (1L << 40)) return 0;
+  const size_t eb = (size_t)n_edges * beam_width;
+  return eb * 8 + edge_up8((size_t)n_edges * 4) * 2 + edge_up8(eb * 4) + edge_up8((size_t)n_tracks * 4) + edge_up8((size_t)n_pairs * 4);
+}
+
+int kl_edge_decode(const kl_handle* h, int n_edges, const int32_t* desc, const double* cum_in, const int32_t* alt_len,
+                   const int32_t* alt_class, const int32_t* step_off, const int32_t* final_slot,
+                   const double* pre_cost, const int32_t* pre_class, const int32_t* pre_slot, const double* cost,
+                   const float* pool, int depth_k, double dist, int batch_size, int beam_width, int cap_tracks, long n_tracks,
+                   long n_pairs, void* out, size_t out_bytes, void* stream) {
+  if (!h || !desc || !cum_in || !alt_len || !alt_class || !step_off || !final_slot || !cost || !out) return KL_ERR_ARG;
+  if (n_edges < 1 || batch_size < 1 || beam_width < 1 || cap_tracks < 1 || cap_tracks > KL_EDGE_MAX_TRACKS) return KL_ERR_ARG;
+  if (n_tracks < 1 || n_pairs < 0 || n_tracks > (1L << 40) || n_pairs > (1L << 40)) return KL_ERR_ARG;
+  if (depth_k < 0 || depth_k > 2 * h->cfg.depth || (depth_k > 0 && (!pool || !(dist == dist)))) return KL_ERR_ARG;
+  if (((uintptr_t)cum_in | (uintptr_t)cost | (uintptr_t)out | (uintptr_t)pre_cost) & 7) return KL_ERR_ARG;
+  if (out_bytes < kl_edge_decode_out_bytes(n_edges, beam_width, n_tracks, n_pairs)) return KL_ERR_WORKSPACE;
+  KlEdgeDecode a;
+  memset(&a, 0, sizeof(a));
+  a.n_edges = n_edges; a.batch_size = batch_size; a.beam_width = beam_width; a.cap_tracks = cap_tracks; a.depth_k = depth_k;
+  a.W = h->cfg.width; a.slot_stride = (long)2 * h->cfg.depth * h->cfg.width; a.dist2 = dist * dist;
+  a.desc = desc; a.cum_in = cum_in; a.alt_len = alt_len; a.alt_class = alt_class; a.step_off = step_off;
+  a.final_slot = final_slot; a.pre_cost = pre_cost; a.pre_class = pre_class; a.pre_slot = pre_slot; a.cost = cost; a.pool = pool;
+  // the output block: [cost f64 E x bw][count E][status E][ref E x bw][consumed tracks][when pairs], every part 8-byte aligned
+  char* o = (char*)out;
+  const size_t eb = (size_t)n_edges * beam_width;
+  a.out_cost = (double*)o; o += eb * 8;
+  a.out_count = (int*)o; o += edge_up8((size_t)n_edges * 4);
+  a.out_status = (int*)o; o += edge_up8((size_t)n_edges * 4);
+  a.out_ref = (int*)o; o += edge_up8(eb * 4);
+  a.out_consumed = (int*)o; o += edge_up8((size_t)n_tracks * 4);
+  a.out_when = (int*)o;
+  return kl_launch_edge_decode(a, (hipStream_t)stream);
 }
 
 size_t kl_beam_workspace_bytes(const kl_handle* h, int rows, int fan) {

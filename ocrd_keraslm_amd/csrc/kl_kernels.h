@@ -436,6 +436,27 @@ struct KlBeamExpand {
 size_t kl_beam_ws_bytes(int rows, int fan);
 int kl_launch_beam_expand(KlBeamExpand a, void* ws, hipStream_t stream);      // KL_ERR_ARG before anything is launched
 
+// ---- edge_decode.hip ----------------------------------------------------
+// the beam bookkeeping of E lattice edges in one launch (kl_edge_costs, kl_edge_decode), see edge_decode.hip; all pointers device
+#define KL_EDGE_MAX_TRACKS 1024
+#define KL_EDGE_MAX_PRE 64
+struct KlEdgeDecode {
+  int n_edges, batch_size, beam_width, cap_tracks, depth_k, W;
+  long slot_stride; double dist2;
+  const int* desc;                   // [n_edges][8]: n_in, n_alt, n_pre, in_off, alt_off, trk_off, pre_off, max_batches
+  const double* cum_in;                                              // per incoming hypothesis
+  const int* alt_len; const int* alt_class;                          // per alternative
+  const int* step_off; const int* final_slot;                        // per track (an empty alternative's: its hypothesis' slot)
+  const double* pre_cost; const int* pre_class; const int* pre_slot;  // per entry already at the destination
+  const double* cost;                // per (track, step) pair
+  const float* pool;                 // may be null with depth_k == 0
+  int* out_count; int* out_status; int* out_ref; double* out_cost; int* out_consumed; int* out_when;
+};
+size_t kl_edge_decode_lds_bytes(int cap_tracks);
+int kl_launch_edge_decode(const KlEdgeDecode& a, hipStream_t stream);      // KL_ERR_ARG before anything is launched
+int kl_launch_edge_costs(long n_pairs, const float* probs, const int* pair_alt, const double* alt_conf, double lm_weight,
+                         double* cost, hipStream_t stream);
+
 // ---- sample.hip ---------------------------------------------------------
 // one drawn character per row (kl_sample_pick), see sample.hip; all pointers device
 #define KL_SAMPLE_MAX_ROWS 1024

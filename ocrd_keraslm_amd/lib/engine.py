@@ -13,6 +13,7 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 import math
+import time
 
 import numpy as np
 
@@ -1272,7 +1273,7 @@ class HipLM:
         self._wstage = (ptr, cap)
         return ptr
 
-    def walk_host(self, lens, idx, target, ctx, slot_in, slot_step, head_k=0, timeout=20.0):
+    def walk_host(self, lens, idx, target, ctx, slot_in, slot_step, head_k=0, timeout=20.0, wait=True):
         """len(lens) rows walked through lens[i] chained LSTM steps each, HOST index arrays in, results on the HOST:
         idx / target / slot_step are ragged (row i at the prefix sum of lens), ctx [n][n_ctx], slot_in [n].  Step t of a row
         reads the state step t - 1 left (slot_in[i] for the first) and leaves its own in slot_step[off + t]; returns
@@ -1307,12 +1308,20 @@ class HipLM:
             self.handle, n, lens.ctypes.data, idx.ctypes.data, tg.ctypes.data, ctx.ctypes.data if ctx is not None else None,
             si.ctypes.data, so.ctypes.data, _ptr(self.pool), int(head_k), io["ptr"]["probs"], io["ptr"]["heads"], stage,
             io["ptr"]["done"], ticket, _ptr(self._walk_ws), self._walk_ws.numel(), stream), "kl_walk_batch_host")
+        if not wait:      # (edge_round: the caller enqueues more behind the walk and waits once, with `walk_wait`)
+            return io, ticket, total
         hipabi.check(self.lib.kl_step_wait(io["ptr"]["done"], ticket, float(timeout)), "kl_step_wait")
         tprob = io["np"]["probs"][:total].copy()
         heads = None
         if head_k:
             heads = io["np"]["heads"][:n * head_k * self.pwidth].reshape(n, head_k, self.pwidth)[:, :, :self.width].copy()
         return tprob, heads
+
+    # ---- the beam bookkeeping of many lattice edges (kl_edge_costs, kl_edge_decode): one round of Rater.rate_best_batch
+    def edge_round(self, arrays, lm_weight, batch_size, beam_width, depth_k=0, dist=0.0, timeout=20.0):
+        """One round of `lattice_batch.decode_lattices` on the device: uploads the edges' arrays (EdgeBatch.arrays()) in ONE
+        transfer and returns an EdgeRound -- `walk(args, pair_off, n_pairs)` per walk call of the round, then `finish()`."""
+        return EdgeRound(self, arrays, lm_weight, batch_size, beam_width, depth_k, dist, timeout)
 
     # ---- generate's beam search on the device (kl_beam_expand): expansion and pruning where the probabilities already are
     def beam_expand(self, probs, cum_in, slot_new, zero_slot, fan, floor, valid=None, out=None):
@@ -1505,3 +1514,130 @@ class HipLM:
             if self.padded and v.shape[-1] == self.width:
                 v = self.torch.nn.functional.pad(v, (0, self.pwidth - self.width))
             self.pool[self.torch.as_tensor(list(slots), device=self.device, dtype=self.torch.long)] = v
+
+
+
+class EdgeRound(object):
+    """The device side of one round of many lattices' decoding (lib/lattice_batch.py): the walk's probabilities become costs
+    (kl_edge_costs, reading the walk's host-visible result buffer on the walk's stream -- the host does not wait in between),
+    kl_edge_decode takes every edge's bookkeeping, ONE copy brings the outputs and the host waits ONCE, for at most
+    `timeout` seconds.  A round whose walk goes in several calls waits for each call but the last before it issues the next
+    (the staging buffers belong to a call until it has arrived).
+    For tests: `costs_from(probs)` computes the costs from given f32 probabilities instead of a walk, `set_costs(cost)`
+    uploads given f64 costs; `finish(want_costs=True)` also returns the device's cost array."""
+    F64 = ("cum_in", "alt_conf", "pre_cost")
+    I32 = ("desc", "slot_in", "alt_len", "alt_class", "step_off", "final_slot", "pre_class", "pre_slot", "pair_alt")
+
+    def __init__(self, lm, arrays, lm_weight, batch_size, beam_width, depth_k, dist, timeout):
+        torch = lm.torch
+        self.lm, self.timeout = lm, float(timeout)
+        self.lm_weight, self.batch_size, self.beam_width = float(lm_weight), int(batch_size), int(beam_width)
+        self.depth_k, self.dist = int(depth_k), float(dist)
+        desc = arrays["desc"]
+        self.n_edges = int(desc.shape[0])
+        self.n_tracks = int(arrays["step_off"].shape[0])
+        self.n_pairs = int(arrays["pair_alt"].shape[0])
+        tracks = desc[:, 0].astype(np.int64) * desc[:, 1]
+        fits = tracks[tracks <= 1024]
+        self.cap = int(fits.max()) if len(fits) else 1      # (an edge above the limit gets its status from the kernel)
+        # ---- one upload: the f64 arrays, then the int32 arrays, every part 8-byte aligned
+        parts, self.off, at = [], {}, 0
+        for name in self.F64 + self.I32:
+            a = np.ascontiguousarray(arrays[name], dtype=np.float64 if name in self.F64 else np.int32).reshape(-1)
+            raw = a.view(np.uint8)
+            pad = (-len(raw)) % 8
+            self.off[name] = at
+            parts.append(raw)
+            if pad:
+                parts.append(np.zeros(pad, dtype=np.uint8))
+            at += len(raw) + pad
+        host = np.concatenate(parts) if at else np.zeros(8, dtype=np.uint8)
+        self.stream = torch.cuda.current_stream(lm.device)
+        with torch.cuda.device(lm.device):
+            self.inp = torch.from_numpy(host).to(lm.device, non_blocking=True)
+            self.cost = torch.empty(max(1, self.n_pairs), dtype=torch.float64, device=lm.device)
+            self.out_bytes = int(lm.lib.kl_edge_decode_out_bytes(self.n_edges, self.beam_width, self.n_tracks, self.n_pairs))
+            if not self.out_bytes:
+                raise hipabi.KlError("edge_round: %d edges, %d tracks, %d pairs" % (self.n_edges, self.n_tracks, self.n_pairs))
+            self.out = torch.empty(self.out_bytes, dtype=torch.uint8, device=lm.device)
+        self.pending = None      # (io, ticket, pair_off, n_pairs) of the walk call that has not arrived yet
+        self.tprob = np.zeros(self.n_pairs, dtype=np.float32)
+        self.keep = []
+
+    def _in(self, name):
+        return self.inp.data_ptr() + self.off[name]
+
+    def _stream(self):
+        return C.c_void_p(self.stream.cuda_stream)
+
+    def _arrived(self):
+        if self.pending is not None:
+            io, ticket, p0, n = self.pending
+            hipabi.check(self.lm.lib.kl_step_wait(io["ptr"]["done"], ticket, self.timeout), "kl_step_wait")
+            self.tprob[p0:p0 + n] = io["np"]["probs"][:n]
+            self.pending = None
+
+    def walk(self, args, pair_off, n_pairs):
+        """one walk call (walk_host's arguments) whose rows are the pairs pair_off .. pair_off + n_pairs - 1 of the round"""
+        self._arrived()
+        io, ticket, total = self.lm.walk_host(*args, wait=False)
+        if total != n_pairs:
+            raise hipabi.KlError("edge_round: a walk of %d pairs where %d were announced" % (total, n_pairs))
+        hipabi.check(self.lm.lib.kl_edge_costs(n_pairs, io["ptr"]["probs"], self._in("pair_alt") + 4 * pair_off, self._in("alt_conf"),
+                                               self.lm_weight, self.cost.data_ptr() + 8 * pair_off, self._stream()), "kl_edge_costs")
+        self.pending = (io, ticket, pair_off, n_pairs)
+
+    def costs_from(self, probs):
+        probs = np.ascontiguousarray(probs, dtype=np.float32).reshape(-1)
+        assert len(probs) == self.n_pairs
+        with self.lm.torch.cuda.device(self.lm.device):
+            dev = self.lm.torch.from_numpy(probs).to(self.lm.device)
+        self.keep.append(dev)
+        hipabi.check(self.lm.lib.kl_edge_costs(self.n_pairs, dev.data_ptr(), self._in("pair_alt"), self._in("alt_conf"), self.lm_weight,
+                                               self.cost.data_ptr(), self._stream()), "kl_edge_costs")
+
+    def set_costs(self, cost):
+        cost = np.ascontiguousarray(cost, dtype=np.float64).reshape(-1)
+        assert len(cost) == self.n_pairs
+        self.cost[:self.n_pairs].copy_(self.lm.torch.from_numpy(cost))
+
+    def decode_args(self):
+        """the arguments of kl_edge_decode as this round passes them (tests vary them)"""
+        lm = self.lm
+        return [lm.handle, self.n_edges] + [self._in(k) for k in ("desc", "cum_in", "alt_len", "alt_class", "step_off",
+                                                                   "final_slot", "pre_cost", "pre_class", "pre_slot")] + [
+            self.cost.data_ptr(), _ptr(lm.pool) if self.depth_k else None, self.depth_k, self.dist, self.batch_size, self.beam_width,
+            self.cap, self.n_tracks, self.n_pairs, self.out.data_ptr(), self.out_bytes, self._stream()]
+
+    def finish(self, want_costs=False):
+        """the decode launch, the one copy and the one wait; {count, status, ref, cost, consumed, when, tprob}"""
+        lm, torch = self.lm, self.lm.torch
+        hipabi.check(lm.lib.kl_edge_decode(*self.decode_args()), "kl_edge_decode")
+        with torch.cuda.device(lm.device):
+            host = torch.empty(self.out_bytes, dtype=torch.uint8, pin_memory=True)
+            host.copy_(self.out, non_blocking=True)
+            cost_host = None
+            if want_costs:
+                cost_host = torch.empty(self.n_pairs, dtype=torch.float64, pin_memory=True)
+                cost_host.copy_(self.cost[:self.n_pairs], non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(self.stream)
+        t0 = time.monotonic()
+        while not done.query():
+            if time.monotonic() - t0 > self.timeout:
+                raise hipabi.KlError("edge_round: no result after %.0f s" % self.timeout)
+        self._arrived()      # (behind the event on the same stream: it has arrived)
+        raw = host.numpy()
+        e, bw = self.n_edges, self.beam_width
+        up8 = lambda n: (n + 7) & ~7
+        at = 0
+        out = {"cost": raw[at:at + e * bw * 8].view(np.float64).reshape(e, bw)}
+        at += e * bw * 8
+        for name, n in (("count", e), ("status", e), ("ref", e * bw), ("consumed", self.n_tracks), ("when", self.n_pairs)):
+            out[name] = raw[at:at + 4 * n].view(np.int32)
+            at += up8(4 * n)
+        out["ref"] = out["ref"].reshape(e, bw)
+        out["tprob"] = self.tprob
+        if want_costs:
+            out["step_cost"] = cost_host.numpy()
+        return out

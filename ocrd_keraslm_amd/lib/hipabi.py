@@ -167,6 +167,10 @@ SIGNATURES = {
     "kl_sample_pick_from": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_float,
                                       C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_size_t, C.c_void_p]),
+    "kl_edge_costs": (C.c_int, [C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
+    "kl_edge_decode_out_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_long, C.c_long]),
+    "kl_edge_decode": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 11 + [C.c_int, C.c_double, C.c_int, C.c_int, C.c_int,
+                                 C.c_long, C.c_long, C.c_void_p, C.c_size_t, C.c_void_p]),
     "kl_step_wait": (C.c_int, [C.c_void_p, C.c_uint32, C.c_double]),
     "kl_state_dist2": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                  C.c_void_p]),

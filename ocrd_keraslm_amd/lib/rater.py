@@ -151,6 +151,7 @@ class Rater(object):
     - `Rater.rate2` (alias `rate_once`) : character string, one by one
     - `Rater.rate` : character string, all at once
     - `Rater.rate_best` : lattice graph
+    - `Rater.rate_best_batch` : many independent lattice graphs at once
     - `Rater.generate` : alternative list of characters and states
     - `Rater.sample` : character strings drawn from the model's distribution
     '''
@@ -2009,6 +2010,24 @@ class Rater(object):
         assert 'traceback' in graph.nodes[reached], \
             "breadth-first search failed to reach end node with any result"
         return self.next_path(graph.nodes[reached]['traceback'], start_traceback)
+
+    def rate_best_batch(self, graphs, start_nodes, end_nodes, start_tracebacks=None, contexts=None, lm_weight=0.5,
+                        beam_width=10, beam_clustering_dist=0, slot_budget_bytes=None):
+        '''`rate_best(..., edge_walk=True)` for many independent lattices at once: returns [(path, entropy, traceback)] in
+        input order, entry i what the single call returns for graphs[i] alone (the same `Node` trees: `next_path` and a
+        carried traceback work unchanged; pass the returned tracebacks as `start_tracebacks` for every chain's next page).
+
+        The lattices advance in lockstep (lattice_batch.py): round r takes the r-th edge of every lattice that still has
+        one, all those edges' hypotheses are walked in ONE engine call and their beam bookkeeping runs in ONE more --
+        on the device (HipLM.edge_round: kl_edge_costs + kl_edge_decode, one host wait per round), or, on an engine
+        without it, as the plain function that defines the kernel (lattice_batch.edge_decode_host).
+        contexts: None, one list for all lattices, or one list per lattice.  slot_budget_bytes: HBM one round's walk may
+        take for the states between characters (None: lattice_batch.BATCH_SCRATCH_BYTES, 1 GiB -- 131072 states at
+        depth 2, width 512); a round that needs more is walked in several calls.
+        Unmapped characters are reported per edge in alternative order, the same set of messages as the single call.'''
+        from . import lattice_batch
+        return lattice_batch.decode_lattices(self, graphs, start_nodes, end_nodes, start_tracebacks, contexts, lm_weight,
+                                             beam_width, beam_clustering_dist, slot_budget_bytes)
 
     def next_path(self, beam, traceback):
         '''Advance from `traceback` to `beam` (rating.py:862-885): lock into the best
