@@ -18,6 +18,7 @@
  *   ... with alternatives, and the suspect positions picked out  kl_rate_window_alts_bulk, kl_rate_scatter_alts, kl_rate_select
  *   ... and the suspects' alternatives rescored against what follows  kl_variant_windows (rows for kl_rate_window(_bulk))
  *   ... with a lost character inserted in front of the suspect         kl_edit_windows
+ *   ... the suspect's left context read once for all its variants      kl_prefix_windows, kl_state_fanout
  *   ... for caller-supplied replacements of spans of the text          kl_span_windows, kl_span_pick
  *   ... per word: the words found, rated and the suspect ones picked out  kl_word_bounds, kl_rate_segments, kl_segment_select
  *       (the processor's mean probability per TextEquiv substring, wrapper/rate.py:308-317, for a whole corpus)
@@ -290,6 +291,36 @@ int kl_variant_windows(const int32_t* corpus, size_t n_corpus, const int64_t* of
 int kl_edit_windows(const int32_t* corpus, size_t n_corpus, const int64_t* offsets, int n_texts, const int32_t* text_ctx,
                     int n_ctx, const int64_t* sel_pos, const int32_t* sel_alt_id, int S, int K, int left, int ahead, int deletions,
                     int insertions, int T, int32_t* idx, int32_t* ctx, int32_t* tgt, int32_t* valid, void* stream);
+
+/* The left context of a suspect as a window of its own, read once for all its variants: one row per SUSPECT.  No handle.
+ * corpus, offsets, text_ctx and sel_pos as in kl_variant_windows.  For suspect s < S at g = sel_pos[s] in text i (binary search,
+ * as there) the row is valid iff g lies in a text, inside [0, min(n_corpus, offsets[n_texts])), and g - offsets[i] >= left: the
+ * suspects whose kl_edit_windows rows have L == left.  A valid row is
+ *   idx[s][t] = x[g - left + t] for t < left - 1, else 0;  ctx[s][t][c] = text_ctx[i][c] for t < left - 1, else 0;
+ *   tgt[s][t] = -1 everywhere;  valid[s] = 1
+ * -- a window from a zero state over it predicts nothing (it adds no bits) and leaves the state after x[g-left .. g-2].  The rows
+ * of kl_edit_windows(left = 1) for the same suspect feed x[g-1] first and target from there on: continued from that state (see
+ * kl_state_fanout) they compute what the rows of kl_edit_windows(left) compute from a zero state, the arithmetic cut in two.
+ * An invalid row is the dummy stream: idx 0, ctx 0, tgt -1, valid[s] = 0.  idx, tgt (device int32 [S][T]), ctx (device int32
+ * [S][T][n_ctx]) and valid (device int32 [S]) are written in every word, nothing outside them is touched; a corpus position
+ * outside [0, min(n_corpus, offsets[n_texts])) reads as 0 without touching memory.  One workgroup per row, one launch on
+ * `stream`, no atomics, no workgroup waits for another: the output does not depend on scheduling.
+ * KL_ERR_ARG, before any launch, for null pointers (ctx and text_ctx may be null only with n_ctx == 0), S or n_texts < 1,
+ * S > 2^22, left < 2, T < left - 1 or T > 1024, n_ctx outside 0 .. 8, n_corpus > 2^40, misaligned pointers (4 bytes; offsets
+ * and sel_pos 8). */
+int kl_prefix_windows(const int32_t* corpus, size_t n_corpus, const int64_t* offsets, int n_texts, const int32_t* text_ctx,
+                      int n_ctx, const int64_t* sel_pos, int S, int left, int T, int32_t* idx, int32_t* ctx, int32_t* tgt,
+                      int32_t* valid, void* stream);
+
+/* One state row handed to the rows that continue from it.  No handle.  src (device f32 [n_src][row_floats]) and dst (device
+ * f32 [rows][row_floats]) are state arrays, row_floats = 2 * depth * (padded) width; parent (device int32 [rows]) names the
+ * source row of every row of dst:
+ *   dst[b][0 .. row_floats) = src[parent[b]][..]  for 0 <= parent[b] < n_src,  a row of zeros for any other parent[b]
+ * -- a bit copy; any number of rows per parent, in any order (a fixed number R per suspect for kl_edit_windows' rows:
+ * parent[b] = b / R).  Every word of dst is written, nothing else is; 16-byte loads and stores, one launch on `stream`, no
+ * atomics.  KL_ERR_ARG, before the launch, for null pointers, rows or n_src < 1, row_floats not a positive multiple of 4,
+ * rows * row_floats / 4 > 2^31 - 1, src or dst not 16-byte aligned (parent: 4), or dst overlapping src. */
+int kl_state_fanout(const float* src, int n_src, const int32_t* parent, int rows, int row_floats, float* dst, void* stream);
 
 /* Hypothesis windows of spans with caller-supplied replacements: the general form of kl_edit_windows, for readings that come
  * from outside the model (a second OCR engine, a lexicon, a table of confusions).  No handle.  corpus, offsets and text_ctx as

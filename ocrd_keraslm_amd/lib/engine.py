@@ -97,6 +97,7 @@ class HipLM:
         self._part_grads = None
         self._part_loss = None
         self._pad_states = {}
+        self._fan_states = {}                # rows -> the state buffer `fan_states` fills for that many streams
         self.pad_streams = True              # pad a group of streams up to the next fast count (HipLM._padded_streams)
         self.plan_override = None            # width 512: a stream plan to use instead of _plan_512's (tests)
         self._step_ws = None
@@ -772,6 +773,66 @@ class HipLM:
                 _ptr(sel_pos_d), _ptr(sel_alt_id_d), S, K, left, ahead, deletions, insertions, T, _ptr(idx),
                 _ptr(ctx) if n_ctx else None, _ptr(tgt), _ptr(valid), self._stream()), "kl_edit_windows")
         return idx, ctx, tgt, valid
+
+    def prefix_windows(self, corpus_d, offsets_d, text_ctx_d, sel_pos_d, left, T):
+        """kl_prefix_windows: the left context of S suspects as rows of their own, one per suspect, built on the device in one
+        launch.  corpus_d int32 [n], offsets_d int64 [n_texts + 1], text_ctx_d int32 [n_texts, n_ctx] (None without contexts)
+        and sel_pos_d int64 [S] (or a slice) as in `variant_windows` -- all DEVICE tensors.  Returns the DEVICE tensors (idx
+        [S, T], ctx [S, T, n_ctx], tgt [S, T], valid [S]) int32: what `ratebulk.prefix_windows_host` states.  hipabi.KlError for
+        what the entry point rejects.  No synchronisation."""
+        torch = self.torch
+        n_ctx = 0 if text_ctx_d is None else int(text_ctx_d.shape[-1])
+        tensors = [corpus_d, offsets_d, sel_pos_d] + ([text_ctx_d] if n_ctx else [])
+        kinds = [torch.int32, torch.int64, torch.int64] + ([torch.int32] if n_ctx else [])
+        n_texts = offsets_d.numel() - 1
+        S = int(sel_pos_d.numel())
+        if ([t.dtype for t in tensors] != kinds or corpus_d.dim() != 1 or offsets_d.dim() != 1 or sel_pos_d.dim() != 1
+                or (n_ctx and tuple(text_ctx_d.shape) != (n_texts, n_ctx))
+                or not all(t.is_contiguous() and t.is_cuda for t in tensors)):
+            raise hipabi.KlError("prefix_windows: corpus int32 [n], offsets int64 [n_texts + 1], text_ctx int32 [n_texts, n_ctx], "
+                                 "sel_pos int64 [S], contiguous, on the device")
+        left, T = int(left), int(T)
+        if S < 1 or T < 1:
+            raise hipabi.KlError("prefix_windows: S >= 1, T >= 1 (got %d, %d)" % (S, T))
+        with self._launch():
+            idx = torch.empty((S, T), dtype=torch.int32, device=self.device)
+            tgt = torch.empty((S, T), dtype=torch.int32, device=self.device)
+            ctx = torch.empty((S, T, n_ctx), dtype=torch.int32, device=self.device)
+            valid = torch.empty(S, dtype=torch.int32, device=self.device)
+            hipabi.check(self.lib.kl_prefix_windows(
+                _ptr(corpus_d), corpus_d.numel(), _ptr(offsets_d), n_texts, _ptr(text_ctx_d) if n_ctx else None, n_ctx,
+                _ptr(sel_pos_d), S, left, T, _ptr(idx), _ptr(ctx) if n_ctx else None, _ptr(tgt), _ptr(valid), self._stream()),
+                "kl_prefix_windows")
+        return idx, ctx, tgt, valid
+
+    def fan_states(self, src_states, parent_d):
+        """kl_state_fanout: the states of the streams that continue from the rows of src_states (f32 DEVICE tensor [n, 2 depth,
+        pwidth], as `states` is after a window) -- stream b from row parent_d[b] (int32 DEVICE tensor [rows]), from a zero state
+        where that names no row: what `ratebulk.fan_states_host` states.  The result is installed as `states` and returned.  It
+        lives in a buffer the engine keeps per number of rows (a window's replayed launch sequence is keyed by the address of its
+        states), another one where src_states is that buffer itself.  hipabi.KlError for what the entry point rejects.  No
+        synchronisation."""
+        torch = self.torch
+        shape = (2 * self.depth, self.pwidth)
+        if (not isinstance(src_states, torch.Tensor) or not isinstance(parent_d, torch.Tensor) or src_states.dtype != torch.float32
+                or parent_d.dtype != torch.int32 or src_states.dim() != 3 or tuple(src_states.shape[1:]) != shape
+                or parent_d.dim() != 1 or src_states.shape[0] < 1 or parent_d.numel() < 1
+                or not all(t.is_contiguous() and t.is_cuda for t in (src_states, parent_d))):
+            raise hipabi.KlError("fan_states: states f32 [n, %d, %d] and parent int32 [rows], contiguous, on the device" % shape)
+        rows = int(parent_d.numel())
+        row_bytes = 4 * shape[0] * shape[1]
+        with self._launch():
+            dst = self._fan_states.get(rows)
+            if dst is not None:      # (disjoint from the source?  a slice of the buffer counts as the buffer)
+                a, b = dst.data_ptr(), src_states.data_ptr()
+                if a < b + src_states.shape[0] * row_bytes and b < a + rows * row_bytes:
+                    dst = None
+            if dst is None:
+                dst = self._fan_states[rows] = torch.empty((rows,) + shape, dtype=torch.float32, device=self.device)
+            hipabi.check(self.lib.kl_state_fanout(_ptr(src_states), int(src_states.shape[0]), _ptr(parent_d), rows,
+                                                  shape[0] * shape[1], _ptr(dst), self._stream()), "kl_state_fanout")
+        self.states = dst
+        return dst
 
     def span_windows(self, corpus_d, offsets_d, text_ctx_d, span_text_d, span_start_d, span_len_d, span_first_d, pool_d,
                      cand_off_d, row0, rows, left, ahead, max_len, T):

@@ -20,7 +20,9 @@ Rules of the plan:
 kl_rate_text_bits compute; `scatter_alts_host` and `select_host` what kl_rate_scatter_alts and kl_rate_select do for rating
 with alternatives (`Rater.rate_alternatives(precision="bf16")`, `Rater.suspects`); `variant_windows_host` what
 kl_variant_windows / kl_edit_windows make of the suspects for `Rater.corrections`, and `variant_pick_host` is the choice among a suspect's
-variants (numpy on every path: S * R doubles); `span_windows_host` and `span_pick_host` what kl_span_windows and kl_span_pick
+variants (numpy on every path: S * R doubles); `prefix_windows_host` and `fan_states_host` state kl_prefix_windows and
+kl_state_fanout, which read a suspect's left context once for all its variants (`Rater.corrections(share_left=True)`);
+`span_windows_host` and `span_pick_host` what kl_span_windows and kl_span_pick
 make of spans with caller-supplied replacements for `Rater.rescore`.  `plan_candidates` is the plan of `Rater.rate_contexts`
 -- every text under every one of C candidate contexts, the pairs as plan rows over the one corpus --, and
 `scatter_planes_host` and `context_mix_host` state what kl_rate_scatter_planes and kl_context_mix make of its calls.
@@ -276,6 +278,78 @@ def variant_windows_host(corpus, offsets, text_ctx, sel_pos, sel_alt_id, left, a
     ctx = (fed[:, :, :, None] * text_ctx[i][:, None, None, :]).astype(np.int32)
     return (idx.reshape(S * R, T), ctx.reshape(S * R, T, text_ctx.shape[1]), tgt.reshape(S * R, T),
             valid.reshape(S * R).astype(np.int32))
+
+
+def prefix_windows_host(corpus, offsets, text_ctx, sel_pos, left, T):
+    """what kl_prefix_windows makes of S suspects (sel_pos [S] corpus positions): the left context of each as a row of its own,
+    read once for all its variants.  For g = sel_pos[s] in text i (offsets[i] <= g < offsets[i + 1]) the row is valid iff g lies
+    in a text, inside [0, min(len(corpus), offsets[-1])), and g - offsets[i] >= left -- the suspects whose
+    `variant_windows_host` rows have L == left.  A valid row: idx[t] = x[g - left + t] for t < left - 1, else 0; ctx[t] =
+    text_ctx[i] for t < left - 1, else 0; tgt[t] = -1 everywhere -- a window from a zero state over it predicts nothing and
+    leaves the state after x[g-left .. g-2]; the rows of `variant_windows_host(left=1)`, which feed x[g-1] first, continue from
+    it (`fan_states_host`).  An invalid row is a dummy stream (idx 0, ctx 0, tgt -1).  text_ctx: [n_texts, n_ctx] (None: no
+    contexts).  left >= 2, left - 1 <= T <= 1024.
+    Returns (idx [S, T], ctx [S, T, n_ctx], tgt [S, T], valid [S]) int32."""
+    corpus = np.asarray(corpus, dtype=np.int32).reshape(-1)
+    offsets = np.asarray(offsets, dtype=np.int64).reshape(-1)
+    g = np.asarray(sel_pos, dtype=np.int64).reshape(-1)
+    S, left, T = len(g), int(left), int(T)
+    n_texts = len(offsets) - 1
+    if S < 1 or n_texts < 1 or left < 2 or not left - 1 <= T <= 1024:
+        raise ValueError("prefix_windows_host: S, n_texts >= 1, left >= 2, left - 1 <= T <= 1024")
+    text_ctx = np.zeros((n_texts, 0), dtype=np.int32) if text_ctx is None else np.asarray(text_ctx, dtype=np.int32)
+    text_ctx = text_ctx.reshape(n_texts, -1)
+    limit = min(len(corpus), int(offsets[-1]))
+    # the text of g: the last i with offsets[i] <= g (repeated offsets -- empty texts -- lie in front of it)
+    i = np.searchsorted(offsets, g, side="right") - 1
+    found = (g >= 0) & (g < limit) & (i >= 0)
+    i = np.clip(i, 0, n_texts - 1)
+    valid = found & (g - offsets[i] >= left)
+    t = np.arange(T, dtype=np.int64)[None, :]
+    fed = valid[:, None] & (t < left - 1)
+    at = g[:, None] - left + t      # (inside the text wherever the row is fed)
+    idx = np.where(fed, corpus[np.where(fed, at, 0)] if len(corpus) else 0, 0).astype(np.int32)
+    ctx = (fed[:, :, None] * text_ctx[i][:, None, :]).astype(np.int32)
+    return idx, ctx, np.full((S, T), -1, dtype=np.int32), valid.astype(np.int32)
+
+
+def fan_states_host(states, parent):
+    """what kl_state_fanout does: row b of the result is row parent[b] of `states`, a row of zeros where parent[b] is outside
+    [0, number of rows).  states: one array with the streams on axis 0 (the HIP engine's [B, 2 depth, width]), or a list of
+    such arrays (an engine that keeps h and c per layer apart: [B, width] each) -- the result has the same form, copies."""
+    parent = np.asarray(parent, dtype=np.int64).reshape(-1)
+
+    def fan(a):
+        a = np.asarray(a)
+        inside = (parent >= 0) & (parent < a.shape[0])
+        out = np.zeros((len(parent),) + a.shape[1:], dtype=a.dtype)
+        out[inside] = a[parent[inside]]
+        return out
+
+    return [fan(a) for a in states] if isinstance(states, (list, tuple)) else fan(states)
+
+
+def left_groups(sel_pos, offsets, left):
+    """the suspects of `Rater.corrections(share_left=True)` in two groups: (full, short), ascending int64 indices into sel_pos
+    [S] -- full where the whole of `left` characters stands in front of the suspect in its text (L == left: the rows
+    `prefix_windows_host` calls valid), short all the others (L < left, and what lies in no text)."""
+    offsets = np.asarray(offsets, dtype=np.int64).reshape(-1)
+    g = np.asarray(sel_pos, dtype=np.int64).reshape(-1)
+    i = np.searchsorted(offsets, g, side="right") - 1
+    inside = (g >= 0) & (g < offsets[-1]) & (i >= 0)
+    whole = inside & (g - offsets[np.clip(i, 0, len(offsets) - 2)] >= int(left))
+    return np.nonzero(whole)[0].astype(np.int64), np.nonzero(~whole)[0].astype(np.int64)
+
+
+def prefix_batches(n_full, streams, R):
+    """the full group of `left_groups` (n_full suspects of R variants each) cut for windows of at most `streams` rows: suffix
+    chunks of chunk = max(1, streams // R) suspects -- chunk * R hypothesis rows --, and prefix batches of
+    Pc = max(1, streams // chunk) * chunk suspects, one prefix row each, so that a batch is a whole number of chunks (but for
+    the last).  Returns [(a, b, [(c, d), ..])]: batch [a, b) and its chunks [c, d), a <= c < d <= b."""
+    chunk = max(1, int(streams) // int(R))
+    Pc = max(1, int(streams) // chunk) * chunk
+    return [(a, min(a + Pc, n_full), [(c, min(c + chunk, a + Pc, n_full)) for c in range(a, min(a + Pc, n_full), chunk)])
+            for a in range(0, int(n_full), Pc)]
 
 
 def variant_pick_host(cost, valid):

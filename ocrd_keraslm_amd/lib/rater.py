@@ -192,6 +192,7 @@ class Rater(object):
         self.edge_walk_slots = None          # ... slots one such call may be asked for (None: lattice_beam.walk_slot_budget of the pool's slot size)
         self.device_beam = os.environ.get('KERASLM_DEVICE_BEAM', '') == '1'      # generate: the beam's expansion and pruning on the device, the whole search enqueued without a wait (HipLM.beam_generate)
         self.sample_keep_probs = False      # sample: keep every step's probabilities in `sample_log` (tests look at what a pick saw)
+        self.shared_left = None              # corrections(share_left=True): how many suspects and windows took which route, of the last call
         self.segment_streams = False         # fewer files than streams: cut the files into segments, one list of segments per stream (segments.py)
         self._engine_factory = engine_factory
         self._pool = None
@@ -1318,7 +1319,7 @@ class Rater(object):
         return found
 
     def corrections(self, texts, contexts=None, k=3, streams=1024, max_prob=0.01, min_rank=1, left=64, ahead=8, deletions=False,
-                    min_gain=1.0, precision="bf16", insertions=False):
+                    min_gain=1.0, precision="bf16", insertions=False, share_left=False):
         '''`suspects`, and for every suspect: does the text that FOLLOWS read better with one of the model's alternatives than
         with the character that was written?  Returns (found, bits), both in input order; `bits` and texts, contexts, k,
         streams, max_prob, min_rank and precision are as in `suspects`, and `found[i]` is a ratebatch.Corrections: the five
@@ -1349,7 +1350,21 @@ class Rater(object):
         in chunks of max(1, streams // R): zero states, `variant_windows` at T = max(left + ahead + insertions, 3), one
         `rate_window_bulk` ("bf16") or `rate_window` ("split"), the rows' f64 bits are the costs.  Beyond the suspects' records
         (8k + 16 bytes each) 12 * R bytes per suspect leave the device.  ValueError for a stateless rater, left < 1, ahead < 0 or
-        left + ahead + insertions > 1024.  State and precision afterwards are as after `suspects`.'''
+        left + ahead + insertions > 1024.  State and precision afterwards are as after `suspects`.
+
+        share_left=True reads a suspect's left context once for all its R variants instead of once per variant.  The costs
+        follow the same definition -- a zero state, the L characters in front, the variant, A characters --, the arithmetic is
+        cut in two stateful windows: the suspects with L == left get one prefix row each (`prefix_windows` at T = left - 1, in
+        batches of (streams // chunk) * chunk suspects from zero states), and per chunk their variants' rows continue from the
+        states these left (`fan_states`, then `variant_windows(left=1)` at T = max(1 + ahead + insertions, 3)).  On the CPU
+        double the state only passes through an array, and the costs agree to rounding; on the device the two routes are
+        different launches over different numbers of rows and are not held to agree bit for bit -- each is held to the
+        definition in its precision.  Only L == left is shared: the suspects within the first `left` characters of their text
+        (L < left) run as without the flag, in chunks of their own -- on long texts nearly every suspect is shared, on short
+        lines with left = 64 almost none is: choose a smaller `left` there.
+        Below left = 4 the prefix window would be shorter than the persistent scans take, and share_left=True runs the
+        unshared route, bit for bit.  `shared_left` afterwards is None, or where suspects were shared a dict: suspects, shared
+        (those with L == left), prefix_windows, suffix_windows and unshared_windows (the window calls of each kind).'''
         texts, contexts, k, limit, min_rank = self._rating_request("corrections", texts, contexts, precision, k, max_prob,
                                                                     min_rank)
         left, ahead, deletions, insertions = int(left), int(ahead), int(bool(deletions)), int(bool(insertions))
@@ -1362,8 +1377,13 @@ class Rater(object):
         chunk = max(1, int(streams) // R)
         T = max(left + ahead + insertions, ratebulk.MIN_T)
         device = hasattr(lm, 'variant_windows')
-        # per path: the suspects (sel, in corpus order), then two callables for a chunk [a, b) of them -- `build` makes the
-        # variants' windows (idx, ctx, tgt, valid), `rate` runs them from zero states and returns their costs, one per row
+        share = bool(share_left) and left - 1 >= ratebulk.MIN_T      # (a shorter prefix window would fall off the persistent scans)
+        # per path: the suspects (sel, in corpus order; pos and alts where the windows are built), then callables -- `build`
+        # makes the variants' windows (idx, ctx, tgt, valid) of some suspects, `rate` runs a window from the states as they are
+        # and returns its rows' costs; for share_left also `prefix` (the left contexts' windows), `start` (zero states for n
+        # prefix rows), `fan` (the states of the rows [lo * R, hi * R) that continue from the prefix rows lo .. hi - 1 of `pre`),
+        # `take` (pos and alts of the suspects an index array names) and `place` (rows in the order they were rated, back to
+        # corpus order)
         if device:
             keep = {}
             plan, arrays, bits = self._rate_in_corpus_order(texts, contexts, k, streams, precision, keep=keep)
@@ -1373,14 +1393,37 @@ class Rater(object):
             S = int(sel_d[0].numel()) if sel_d is not None else 0
             sel = [_np(t) for t in sel_d] if S else self._empty_selection(k)
             cat = lm.torch.cat
+            pos, alts = (sel_d[0], sel_d[3]) if S else (None, None)
+            source = (keep.get("corpus"), keep.get("offsets"), keep.get("text_ctx") if lm.n_ctx else None)
 
-            def build(a, b):
-                return lm.variant_windows(keep["corpus"], keep["offsets"], keep["text_ctx"] if lm.n_ctx else None,
-                                          sel_d[0][a:b], sel_d[3][a:b], left, ahead, deletions, T, insertions=bool(insertions))
+            def build(pos, alts, left, T):
+                return lm.variant_windows(*source, pos, alts, left, ahead, deletions, T, insertions=bool(insertions))
 
             def rate(x, z, y):      # (the rows' f64 bits are the costs)
                 (lm.rate_window_bulk if precision == "bf16" else lm.rate_window)(x, z, y, want_probs=False)
                 return lm.rate_bits_take_all()
+
+            def prefix(pos):
+                return lm.prefix_windows(*source, pos, left, left - 1)
+
+            def start(n, pre):
+                # (the last batch's buffer again where it fits: a window's replayed launch sequence is keyed by the address of
+                # its states)
+                if pre is not None and pre.shape[0] == n:
+                    lm.states = pre
+                lm.reset_states(n)
+
+            def fan(pre, lo, hi):
+                lm.fan_states(pre, lm.torch.arange(lo * R, hi * R, dtype=lm.torch.int32, device=lm.device) // R)
+
+            def take(index):
+                index = lm.torch.from_numpy(index).to(lm.device)
+                return pos[index], alts[index]
+
+            def place(rows, order):
+                out = lm.torch.empty_like(rows)
+                out[lm.torch.from_numpy(order).to(lm.device)] = rows
+                return out
         else:
             # an engine without the device path (the tests' CPU double): `suspects`, the numpy statement of the windows, the
             # whole softmax of every window and the logs summed on the host
@@ -1393,26 +1436,74 @@ class Rater(object):
             sel[0] = sel[0] + np.repeat(offsets[:-1], [len(f) for f in found])
             S = len(sel[0])
             cat = np.concatenate
+            pos, alts = sel[0], sel[3]
             if S:
                 corpus = np.concatenate(ids).astype(np.int32)
                 text_ctx = np.asarray([windows.clamp_context(c) for c in contexts], dtype=np.int32).reshape(n, -1)
 
-            def build(a, b):
-                return ratebulk.variant_windows_host(corpus, offsets, text_ctx, sel[0][a:b], sel[3][a:b], left, ahead,
-                                                     deletions, T, insertions)
+            def build(pos, alts, left, T):
+                return ratebulk.variant_windows_host(corpus, offsets, text_ctx, pos, alts, left, ahead, deletions, T, insertions)
 
             def rate(x, z, y):
                 full = _np(lm.forward_window(x, z, want_probs=True)).astype(np.float64)
                 p = np.take_along_axis(full, np.maximum(y, 0)[:, :, None], axis=2)[:, :, 0]
                 return -np.where(y >= 0, np.log2(np.maximum(p, 1e-99)), 0.0).sum(axis=1)
+
+            def prefix(pos):
+                return ratebulk.prefix_windows_host(corpus, offsets, text_ctx, pos, left, left - 1)
+
+            def start(n, pre):
+                lm.reset_states(n)
+
+            def fan(pre, lo, hi):
+                lm.states = ratebulk.fan_states_host(pre, np.arange(lo * R, hi * R) // R)
+
+            def take(index):
+                return pos[index], alts[index]
+
+            def place(rows, order):
+                out = np.empty_like(rows)
+                out[order] = rows
+                return out
         costs, valids = [], []
-        for a in range(0, S, chunk):
-            x, z, y, ok = build(a, min(S, a + chunk))
-            lm.reset_states(int(x.shape[0]))
-            costs.append(rate(x, z, y))
-            valids.append(ok)
-        if S:
+
+        def unshared(pos, alts):      # suspects in chunks, every variant's window from a zero state
+            for a in range(0, len(pos), chunk):
+                x, z, y, ok = build(pos[a:a + chunk], alts[a:a + chunk], left, T)
+                lm.reset_states(int(x.shape[0]))
+                costs.append(rate(x, z, y))
+                valids.append(ok)
+        self.shared_left = None
+        if S and share:
+            # the suspects with the whole of `left` characters in front of them: one prefix row each, left - 1 characters from a
+            # zero state, then per chunk its variants' short rows (left = 1: x[g-1], the variant, `ahead` characters) from the
+            # states the prefix rows left; the others as without share_left
+            full, short = ratebulk.left_groups(sel[0], offsets, left)
+            batches = ratebulk.prefix_batches(len(full), streams, R)
+            self.shared_left = dict(suspects=S, shared=len(full), prefix_windows=len(batches),
+                                    suffix_windows=sum(len(chunks) for _, _, chunks in batches),
+                                    unshared_windows=-(-len(short) // chunk))
+            if len(short):
+                unshared(*take(short))
+            full_pos, full_alts = take(full) if len(full) else (None, None)
+            short_T = max(1 + ahead + insertions, ratebulk.MIN_T)
+            pre = None
+            for a, b, chunks in batches:
+                x, z, y, _ = prefix(full_pos[a:b])
+                start(b - a, pre)
+                rate(x, z, y)      # (no targets: the bits it adds are zeros)
+                pre = lm.states
+                for c, d in chunks:
+                    x, z, y, ok = build(full_pos[c:d], full_alts[c:d], 1, short_T)
+                    fan(pre, c - a, d - a)
+                    costs.append(rate(x, z, y))
+                    valids.append(ok)
+            order = np.concatenate([short, full])
+            cost, valid = (_np(place(cat(rows).reshape(S, R), order)) for rows in (costs, valids))
+        elif S:
+            unshared(pos, alts)
             cost, valid = _np(cat(costs)).reshape(S, R), _np(cat(valids)).reshape(S, R)
+        if S:
             if device:
                 lm.rate_status_check()
             lm.reset_states(1)

@@ -10,7 +10,8 @@ Additional command `suspects`: per DATA file the characters the model does not b
 (Rater.suspects: rated in bulk, picked out on the device).
 Additional command `correct`: the suspects of every DATA file with their alternatives rescored against the text that follows,
 and what that proposes to write instead (Rater.corrections); --deletions also tries dropping the character, --insertions a
-lost character in front of it; --apply also gives the corrected text.
+lost character in front of it, --share-left reads a suspect's left context once for all of these; --apply also gives the
+corrected text.
 Additional command `rescore`: replacements that come from outside the model -- per-file candidate lists (--candidates) or a
 table of known confusions (--confusions, gated by a `suspects` pass) -- rated against the text around their spans
 (Rater.rescore); --apply also gives the corrected text.
@@ -268,9 +269,13 @@ def suspects(model, streams, precision, k, max_prob, min_rank, data):
               help='also try each expected character in front of the suspect: a character the text has lost')
 @click.option('--min-gain', default=1.0, show_default=True, type=click.FLOAT,
               help='a proposal must save at least this many bits against the text as written')
+@click.option('--share-left', is_flag=True, default=False,
+              help='read the LEFT characters once per suspect instead of once per hypothesis (suspects with fewer than LEFT '
+                   'characters in front of them are not shared: on short lines choose a smaller --left)')
 @click.option('--apply', 'apply_', is_flag=True, default=False, help='also give the text with the proposals applied ("corrected")')
 @click.argument('data', nargs=-1, type=click.Path(exists=True, dir_okay=True, file_okay=True))
-def correct(model, streams, precision, k, max_prob, min_rank, left, ahead, deletions, insertions, min_gain, apply_, data):
+def correct(model, streams, precision, k, max_prob, min_rank, left, ahead, deletions, insertions, min_gain, share_left, apply_,
+            data):
     """Apply a language model to DATA files and print one JSON line per file, as `suspects` does, with
        "corrections": one [position, written, proposed, gain] per suspect -- proposed is what replaces the
        written character: null for no proposal, "" for dropping it, one character for another in its place
@@ -292,7 +297,7 @@ def correct(model, streams, precision, k, max_prob, min_rank, left, ahead, delet
         return
     found, bits = rater.corrections(texts, contexts, k=k, streams=streams, max_prob=max_prob, min_rank=min_rank, left=left,
                                     ahead=ahead, deletions=deletions, min_gain=min_gain, precision=precision,
-                                    insertions=insertions)
+                                    insertions=insertions, share_left=share_left)
     for name, text, one, total in zip(names, texts, found, bits):
         rows = [[int(j), text[int(j)], float(p), int(r), [[c, float(q)] for c, q in zip(chars, probs)]]
                 for j, p, r, chars, probs in zip(one.positions, one.probs, one.rank, one.chars(rater.mapping), one.alt_probs)]

@@ -5,6 +5,7 @@ numpy.
 
   python tools/bench_corrections.py [--out profiles/rate_corrections.json] [--repeats 5] [-k 3] [--suspect-share 0.02]
                                     [--min-rank 1] [--left 64] [--ahead 8] [--deletions] [--insertions] [--min-gain 1.0]
+                                    [--share-left]
 
 The corpus-sized inputs of bench_suspects.py, cfg2 size (depth 2, width 512, length 256): 1024 documents of 2048 characters
 and 20 000 lines of 30 to 90 characters, both at 1024 streams.  The benchmark's model is untrained, and at a fixed threshold
@@ -28,6 +29,14 @@ Also reported, from one run each outside the timings: that both legs give identi
 (`Rater.corrections(insertions=True)`, R = 2k + 1 + deletions rows per suspect; the parent leg builds the same rows with
 variant_windows_host(insertions=1)), adds a "first_pass" leg (Rater.suspects alone) so that the second pass of either can be
 told apart, and writes the result under the key "insertions" of --out, whose other content stays as it is.
+--share-left measures `Rater.corrections(share_left=True)` -- a suspect's left context read once for all its variants
+(kl_prefix_windows, kl_state_fanout) -- against the call without the flag, the two alternated in the same run, beside a
+"first_pass" leg (Rater.suspects alone), and nothing else: per set the key "share_left" of that set in --out, whose other
+content stays as it is, with both legs' seconds and spread, the share of the suspects that took the shared route (those with
+--left characters in front of them in their text), the window calls of each kind, the largest |cost_shared - cost_unshared|
+in bits (beside the file's |cost_bf16 - cost_split|) and whether the kept proposals are identical.  The lines are measured
+once more at --left 16, shared against unshared, under the key "share_left_left16": few suspects of a short line have 64
+characters in front of them.
 Host clock around work that ends in a device synchronise; every leg is warmed up once, then the legs are alternated in the
 same process; a leg is repeated inside one timing until it lasts at least --min-seconds; the median of --repeats (at least
 5) timings and the spread (max - min) / median.  One JSON line on stdout, also written to --out.
@@ -50,6 +59,84 @@ from tools.bench_rate_batch import ALPHABET, MODELS, emit, make_rater, timed    
 from tools.bench_suspects import corpus_sets      # noqa: E402
 
 
+def share_left_run(args, rater, context, repeats, sync):
+    """--share-left: the shared call against the unshared one per set, the lines once more at left = 16; written under keys
+    of their own of every set of --out"""
+    k, deletions, insertions = args.k, bool(args.deletions), bool(args.insertions)
+    whole = {}
+    if args.out and os.path.exists(args.out):
+        with open(args.out) as f:
+            whole = json.load(f)
+    for name, docs, streams in corpus_sets():
+        chars = sum(len(d) for d in docs)
+        probs, _ = rater.rate_batch(docs, context, streams=streams, precision="bf16")
+        max_prob = float(np.quantile(np.concatenate([p[1:] for p in probs]), args.suspect_share))
+        del probs
+        common = dict(k=k, streams=streams, max_prob=max_prob, min_rank=args.min_rank)
+        for key, left in [("share_left", args.left)] + ([("share_left_left16", 16)] if "lines" in name else []):
+            def corrections(share_left=False):
+                return rater.corrections(docs, context, left=left, ahead=args.ahead, deletions=deletions, min_gain=args.min_gain,
+                                         precision="bf16", insertions=insertions, share_left=share_left, **common)
+
+            # one run of each outside the timings: the costs side by side, the kept proposals
+            found, _ = corrections()
+            shared, _ = corrections(True)
+            stats = dict(rater.shared_left or {})
+            worst, same = 0.0, True
+            for a, b in zip(found, shared):
+                same &= bool(np.array_equal(a.positions, b.positions) and np.array_equal(np.isinf(a.cost), np.isinf(b.cost)))
+                both = np.isfinite(a.cost) & np.isfinite(b.cost) if a.cost.shape == b.cost.shape else np.zeros(0, dtype=bool)
+                if both.any():
+                    worst = max(worst, float(np.abs(a.cost[both] - b.cost[both]).max()))
+            kept = [np.concatenate([f.best_id for f in r]) for r in (found, shared)]
+            ops = [np.concatenate([f.best_op for f in r]) for r in (found, shared)]
+            legs = {"corrections": corrections, "share_left": lambda: corrections(True),
+                    "first_pass": lambda: rater.suspects(docs, context, precision="bf16", **common)}
+            inner = {}
+            for leg, fn in legs.items():
+                fn()
+                inner[leg] = max(1, int(np.ceil(args.min_seconds / max(timed(fn, sync, 1), 1e-6))))
+            times = dict((leg, []) for leg in legs)
+            for _ in range(repeats):
+                for leg, fn in legs.items():
+                    times[leg].append(timed(fn, sync, inner[leg]))
+            before = whole.get("sets", {}).get(name, {})
+            row = {"left": left, "ahead": args.ahead, "k": k, "deletions": deletions, "insertions": insertions,
+                   "variants_per_suspect": k + 1 + int(deletions) + k * int(insertions), "streams": streams, "max_prob": max_prob,
+                   "suspects_found": int(sum(len(f) for f in found)),
+                   "suspects_shared": int(stats.get("shared", 0)),
+                   "shared_share": stats.get("shared", 0) / max(1, stats.get("suspects", 0)),
+                   "prefix_windows": int(stats.get("prefix_windows", 0)), "suffix_windows": int(stats.get("suffix_windows", 0)),
+                   "unshared_windows": int(stats.get("unshared_windows", 0)),
+                   "same_suspects_and_inf_pattern": same,
+                   "max_abs_cost_shared_minus_unshared": worst,
+                   # (what the file's run without the flag measured, where it had the same hypotheses)
+                   "max_abs_cost_bf16_minus_split": before.get("max_abs_cost_bf16_minus_split") if (
+                       whole.get("left"), whole.get("ahead"), whole.get("deletions"), whole.get("k")) == (
+                       left, args.ahead, deletions, k) and not insertions else None,
+                   "proposals_kept": int((kept[0] != -1).sum()), "proposals_kept_shared": int((kept[1] != -1).sum()),
+                   "proposals_identical": bool(np.array_equal(kept[0], kept[1]) and np.array_equal(ops[0], ops[1])),
+                   "proposals_differing": int(((kept[0] != kept[1]) | (ops[0] != ops[1])).sum())}
+            for leg, ts in times.items():
+                med = statistics.median(ts)
+                row[leg] = {"chars_per_s": chars / med, "seconds": med, "spread": (max(ts) - min(ts)) / med,
+                            "runs_per_timing": inner[leg]}
+            row["speedup"] = row["corrections"]["seconds"] / row["share_left"]["seconds"]
+            row["second_pass_speedup"] = ((row["corrections"]["seconds"] - row["first_pass"]["seconds"])
+                                          / max(row["share_left"]["seconds"] - row["first_pass"]["seconds"], 1e-9))
+            # faster only if the medians differ by more than both legs' spreads
+            gap = (row["corrections"]["seconds"] - row["share_left"]["seconds"]) / row["corrections"]["seconds"]
+            row["faster_beyond_spread"] = bool(gap > max(row["corrections"]["spread"], row["share_left"]["spread"]))
+            whole.setdefault("sets", {}).setdefault(name, {})[key] = row
+            print("%-16s left %3d  corrections %.4f s (spread %.2f)  share_left %.4f s (spread %.2f): %.2fx, second pass %.2fx  "
+                  "%d of %d suspects shared, %d + %d + %d windows  |shared - unshared| <= %.3g bits  proposals identical %s (%d differ)"
+                  % (name, left, row["corrections"]["seconds"], row["corrections"]["spread"], row["share_left"]["seconds"],
+                     row["share_left"]["spread"], row["speedup"], row["second_pass_speedup"], row["suspects_shared"],
+                     row["suspects_found"], row["prefix_windows"], row["suffix_windows"], row["unshared_windows"], worst,
+                     row["proposals_identical"], row["proposals_differing"]), file=sys.stderr)
+    emit(whole, args.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rate_corrections.json"))
@@ -63,6 +150,7 @@ def main():
     ap.add_argument("--deletions", action="store_true")
     ap.add_argument("--insertions", action="store_true")
     ap.add_argument("--min-gain", type=float, default=1.0)
+    ap.add_argument("--share-left", action="store_true")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -75,6 +163,8 @@ def main():
     rater.model.init_weights(seed=3, emb_std=0.3)      # (as bench_rate_batch --bulk: peaked distributions)
     lm = rater.model
     context = [17]
+    if args.share_left:
+        return share_left_run(args, rater, context, repeats, sync)
     result = {"tool": "bench_corrections", "device": torch.cuda.get_device_name(0), "repeats": repeats, "k": k,
               "suspect_share": args.suspect_share, "min_rank": args.min_rank, "left": left, "ahead": ahead,
               "deletions": bool(deletions), "min_gain": args.min_gain,
