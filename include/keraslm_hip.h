@@ -22,6 +22,7 @@
  *   ... for caller-supplied replacements of spans of the text          kl_span_windows, kl_span_pick
  *   ... per word: the words found, rated and the suspect ones picked out  kl_word_bounds, kl_rate_segments, kl_segment_select
  *       (the processor's mean probability per TextEquiv substring, wrapper/rate.py:308-317, for a whole corpus)
+ *   ... and the suspect words' nearest entries of a lexicon, as replacements   kl_lexicon_neighbours
  *   model.predict_on_batch, stateful (1,1) step, :566        kl_forward_window with T = 1
  *   model.predict_on_batch, incremental + states, :631       kl_step_batch
  *   ... once per character of a lattice edge, :796-851       kl_walk_batch_host (all characters of all hypotheses, one call)
@@ -470,6 +471,53 @@ int kl_segment_select(const int64_t* seg_start, const int64_t* seg_end, const in
                       int min_n, int min_bad, double min_bpc, size_t capacity, int64_t* sel_index, int64_t* sel_start,
                       int64_t* sel_end, int32_t* sel_n, double* sel_bits, double* sel_psum, float* sel_min, int64_t* sel_worst,
                       int32_t* sel_bad, int64_t* count, void* ws, size_t ws_bytes, void* stream);
+
+/* Lexicon look-up: the entries of a lexicon within max_dist edits of every query word -- the step between the suspect words
+ * (kl_segment_select) and the replacements kl_span_windows rates.  No handle.  Words are sequences of int32 ids.
+ *
+ * Equality and distance.  Two ids are equal iff they are the same number AND that number lies in [0, V): an id outside the
+ * range equals nothing, itself included, and never indexes a table.  lev(q, e) is the Levenshtein distance with unit costs for
+ * insertion, deletion and substitution under that equality.
+ *
+ * The lexicon (what ratebulk.lexicon_layout_host builds): N' entries of 1 .. 64 ids, sorted by (length, original index).
+ *   class_first (HOST int64 [66])  the entries of length L are the sorted positions [class_first[L], class_first[L + 1]);
+ *                                  class_first[0] == class_first[1] == 0, non-decreasing, class_first[65] = N', 1 <= N' < 2^31.
+ *                                  Read on the host, so that every address the kernel forms is checked before the launch.
+ *   order (device int32 [N'])      the original index (>= 0) of every sorted position -- what the outputs name
+ *   chars (device int32 [n_chars]) column-major within a length class: with n_L entries in class L and base[L] = sum over
+ *                                  l < L of l * n_l, id j of sorted position p of class L is chars[base[L] + j * n_L +
+ *                                  (p - class_first[L])]; n_chars == sum over L of L * n_L.
+ * The queries: q_pool (device int32 [n_q]) and q_off (device int64 [Q + 1]); query q is q_pool[q_off[q] .. q_off[q + 1]).  A
+ * query of no ids or of more than 64, and one whose offsets do not lie ascending within [0, n_q], is a neighbour of nothing, and
+ * nothing of it is read.
+ *
+ * Every output is OVERWRITTEN for every q < Q (device int32; exact, found [Q]; cand, dist [Q][K]); nothing behind is written.
+ * Over the entries e with lev(q, e) <= max_dist:
+ *   exact[q]        the smallest original index with lev == 0, or -1
+ *   found[q]        the number of entries with lev >= 1, whatever K is
+ *   cand[q][0..K)   the original indices of the first K of these, ordered by (lev, original index); dist[q][.] their distances;
+ *                   unused places are -1 in both.
+ * A query that is a neighbour of nothing gets exact -1, found 0 and -1 in every place.  Duplicate entries are separate entries.
+ * The statement is ratebulk.lexicon_neighbours_host.
+ *
+ * One workgroup per query: the query is the pattern of Myers' bit-parallel edit distance (one 64-bit word: hence the limit of
+ * 64; a 32-bit word for a query of at most 32 ids unless KL_LEXICON_NARROW=0 is in the environment: same results), its match
+ * masks Peq[V] lie in LDS, every lane walks whole entries of the length classes max(1, m - max_dist) ..
+ * min(64, m + max_dist) and keeps its smallest keys (lev << 32 | original index) in registers; the workgroup takes the K
+ * smallest in a fixed order.  Two plain launches on `stream` (the class table into ws, then the look-up), no atomics, no workgroup
+ * waits for another, and the output depends on the inputs only: two calls agree bit for bit.  ws: device scratch of
+ * kl_lexicon_neighbours_workspace_bytes(Q, K) bytes (the class table: the same for every Q and K), 8-byte aligned, not to be
+ * shared by calls that may overlap.  KL_ERR_ARG, before any launch and with no output touched, for null pointers
+ * (q_pool may be null with n_q == 0), V outside 1 .. KL_LEXICON_V_MAX, max_dist outside 0 .. KL_LEXICON_DIST_MAX, K outside
+ * 1 .. KL_LEXICON_K_MAX, Q < 1 or >= 2^31, n_q or n_chars > 2^40, a class_first that breaks the rules above or disagrees with
+ * n_chars, misaligned pointers (q_off, class_first and ws 8 bytes, the others 4); KL_ERR_WORKSPACE if ws_bytes is too small. */
+#define KL_LEXICON_V_MAX 4096
+#define KL_LEXICON_DIST_MAX 8
+#define KL_LEXICON_K_MAX 16
+size_t kl_lexicon_neighbours_workspace_bytes(size_t Q, int K);
+int kl_lexicon_neighbours(const int32_t* chars, size_t n_chars, const int32_t* order, const int64_t* class_first, int V,
+                          const int32_t* q_pool, size_t n_q, const int64_t* q_off, size_t Q, int max_dist, int K, int32_t* exact,
+                          int32_t* found, int32_t* cand, int32_t* dist, void* ws, size_t ws_bytes, void* stream);
 
 /* One training batch, forward + backward (rating.py:292-298 -> train_on_batch):
  * writes the gradient of (mean CE + embedding regularisers, rating.py:187-246)

@@ -1,0 +1,287 @@
+// Lexicon look-up (kl_lexicon_neighbours): which entries of a lexicon lie within max_dist edits of each query word?
+//
+// The length classes of the lexicon are checked on the host and put into the workspace by a launch of one workgroup; then one
+// workgroup per query.  The query is the PATTERN of Myers' bit-parallel edit distance in Hyyro's form for the global
+// (Levenshtein) distance: bit i of Peq[id] says that pattern position i holds `id`, the vertical deltas of a DP column live in two
+// 64-bit words, and one lexicon character advances the column in about twenty 64-bit operations -- which is why a query holds at
+// most 64 ids; a query of at most 32 runs the same steps on 32-bit words (the VALU has no 64-bit add or shift: 10.7 against
+// 12.1 ms for 20 000 words against 228 576 entries; KL_LEXICON_NARROW=0 switches it off).  Peq[V] lies in LDS (V * 8 bytes,
+// only the query's own ids are non-zero); an id outside [0, V) on either side never reaches the table: it has no bit and
+// matches nothing.
+//
+// Every lane then walks whole entries of the length classes max(1, m - max_dist) .. min(64, m + max_dist) -- other lengths
+// cannot be within max_dist --, one character per step from the column-major layout (consecutive lanes read consecutive
+// addresses), and keeps its own KL_LEXICON_K_MAX smallest keys (distance << 32 | original index) sorted in registers.  The
+// workgroup then takes the K smallest heads one after the other: a minimum over the waves, the winner (the lowest thread among
+// equal keys) drops its head.  `found` is an integer sum and `exact` a minimum, both folded in a fixed order.  No atomics, no
+// workgroup waits for another, the output depends on the inputs only.  No model: no handle.
+#include "keraslm_hip.h"
+#include "kl_common.h"
+#include <stdlib.h>
+
+namespace {
+
+constexpr int LEX_THREADS = 256;
+constexpr int LEX_WAVES = LEX_THREADS / KL_WAVE;
+constexpr int LEX_LEN_MAX = 64;      // ids of a query and of an entry at most: one pattern word
+constexpr unsigned long long NO_KEY = ~0ull;
+constexpr size_t MAX_QUERIES = 0x7FFFFFFF;      // (one workgroup per query in one grid)
+constexpr size_t MAX_POOL = (size_t)1 << 40;
+static_assert(KL_LEXICON_V_MAX * 8 <= 32 * 1024, "Peq fits 32 KiB of LDS");
+static_assert(KL_LEXICON_K_MAX == 16, "the lanes' key lists are written out for 16 keys");
+
+constexpr int LEX_CLASSES = LEX_LEN_MAX + 2;
+// the length classes, checked on the host: entries of length L are the sorted positions [first[L], first[L + 1]) and their
+// characters begin at chars[base[L]]
+struct lex_classes {
+  long long first[LEX_CLASSES];
+  long long base[LEX_CLASSES];
+};
+
+// the class table from a launch's arguments to the workspace, every index into the arguments a constant (an index known at run
+// time only would send the table through scratch): table[L] = first[L], table[LEX_CLASSES + L] = base[L]
+__global__ void __launch_bounds__(2 * KL_WAVE) lexicon_classes_kernel(const lex_classes cls, long long* __restrict__ table) {
+#pragma unroll
+  for (int i = 0; i < LEX_CLASSES; ++i)
+    if ((int)threadIdx.x == i) {
+      table[i] = cls.first[i];
+      table[LEX_CLASSES + i] = cls.base[i];
+    }
+}
+
+// one text character against the pattern column (Pv, Mv: vertical deltas +1 / -1; score: the distance to the whole pattern); the
+// pattern word W is 64 bits, or 32 for a query of at most 32 ids (half the instructions: the VALU has no 64-bit add or shift)
+template <typename W>
+__device__ __forceinline__ void myers_step(W Eq, W top, W& Pv, W& Mv, int& score) {
+  const W Xv = Eq | Mv;
+  const W Xh = (((Eq & Pv) + Pv) ^ Pv) | Eq;
+  W Ph = Mv | ~(Xh | Pv);
+  W Mh = Pv & Xh;
+  score += (Ph & top) ? 1 : 0;
+  score -= (Mh & top) ? 1 : 0;
+  Ph = (Ph << 1) | (W)1;      // (row 0 of the global distance grows by one per text character)
+  Mh <<= 1;
+  Pv = Mh | ~(Xv | Ph);
+  Mv = Ph & Xv;
+}
+
+// the match mask of id c for the pattern word: the whole word of Peq, or its low half
+template <typename W>
+__device__ __forceinline__ W match_mask(const unsigned long long* peq, int c, int V);
+template <>
+__device__ __forceinline__ unsigned long long match_mask<unsigned long long>(const unsigned long long* peq, int c, int V) {
+  return (c >= 0 && c < V) ? peq[c] : 0ull;
+}
+template <>
+__device__ __forceinline__ unsigned int match_mask<unsigned int>(const unsigned long long* peq, int c, int V) {
+  return (c >= 0 && c < V) ? reinterpret_cast<const unsigned int*>(peq)[2 * c] : 0u;
+}
+
+__device__ __forceinline__ unsigned long long wave_min(unsigned long long v) {
+#pragma unroll
+  for (int off = KL_WAVE / 2; off > 0; off >>= 1) {
+    const unsigned long long o = __shfl_xor(v, off, KL_WAVE);
+    v = o < v ? o : v;
+  }
+  return v;
+}
+
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+  for (int off = KL_WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, KL_WAVE);
+  return v;
+}
+
+// a lane's walk over the entries e = tid, tid + LEX_THREADS, .. of every length class that can hold a neighbour of a query of m
+// ids: its KL_LEXICON_K_MAX smallest keys (sorted), the least index at distance 0 and the number within 1 .. max_dist
+template <typename W>
+__device__ __forceinline__ void walk_classes(const int* __restrict__ chars, const int* __restrict__ order,
+                                             const long long* __restrict__ table, const unsigned long long* peq, int V, int m,
+                                             int max_dist, int tid, unsigned long long (&best)[KL_LEXICON_K_MAX],
+                                             unsigned int& least_exact, int& n_found) {
+  const W top = (W)1 << (m - 1);
+  const int lo = m - max_dist > 1 ? m - max_dist : 1;
+  const int hi = m + max_dist < LEX_LEN_MAX ? m + max_dist : LEX_LEN_MAX;
+  for (int L = lo; L <= hi; ++L) {
+    const long long at = table[L], n_L = table[L + 1] - at, base = table[LEX_CLASSES + L];
+    for (long long e = tid; e < n_L; e += LEX_THREADS) {
+      const int* __restrict__ col = chars + base + e;      // character j of the entry: col[j * n_L]
+      W Pv = ~(W)0, Mv = 0;
+      int score = m;
+      int c = col[0];
+      for (int j = 0; j < L; ++j) {
+        const int next = j + 1 < L ? col[(long long)(j + 1) * n_L] : 0;      // (the next character is under way)
+        myers_step<W>(match_mask<W>(peq, c, V), top, Pv, Mv, score);
+        c = next;
+      }
+      if (score <= max_dist) {
+        const unsigned int index = (unsigned int)order[at + e];
+        if (score == 0) {
+          least_exact = index < least_exact ? index : least_exact;
+        } else {
+          ++n_found;
+          unsigned long long key = ((unsigned long long)score << 32) | index;
+          if (key < best[KL_LEXICON_K_MAX - 1]) {
+#pragma unroll
+            for (int i = 0; i < KL_LEXICON_K_MAX; ++i) {      // (sorted insertion, every index a constant: registers)
+              const unsigned long long b = best[i];
+              const bool less = key < b;
+              best[i] = less ? key : b;
+              key = less ? b : key;
+            }
+          }
+        }
+      }
+    }
+  }
+}
+
+__global__ void __launch_bounds__(LEX_THREADS) lexicon_neighbours_kernel(
+    const int* __restrict__ chars, const int* __restrict__ order, const long long* __restrict__ table, int V,
+    const int* __restrict__ q_pool, long long n_q, const long long* __restrict__ q_off, int max_dist, int K, int narrow,
+    int* __restrict__ exact, int* __restrict__ found, int* __restrict__ cand, int* __restrict__ dist) {
+  __shared__ unsigned long long peq[KL_LEXICON_V_MAX];
+  __shared__ int s_query[LEX_LEN_MAX];
+  __shared__ unsigned long long s_key[LEX_WAVES], s_mask[LEX_WAVES];
+  __shared__ unsigned int s_exact[LEX_WAVES];
+  __shared__ int s_found[LEX_WAVES];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long q = blockIdx.x;
+  const long long qa = q_off[q], qb = q_off[q + 1];
+  // a query outside the pool, of no ids or of more than 64 is a neighbour of nothing: nothing of it is read
+  const bool none = qa < 0 || qb <= qa || qb > n_q || qb - qa > LEX_LEN_MAX;
+  if (none) {      // (uniform: the whole workgroup leaves)
+    if (tid == 0) {
+      exact[q] = -1;
+      found[q] = 0;
+    }
+    if (tid < K) {
+      cand[q * K + tid] = -1;
+      dist[q * K + tid] = -1;
+    }
+    return;
+  }
+  const int m = (int)(qb - qa);
+  for (int v = tid; v < V; v += LEX_THREADS) peq[v] = 0ull;
+  if (tid < m) s_query[tid] = q_pool[qa + tid];
+  __syncthreads();
+  if (tid < m) {
+    // all positions that hold this id write the same word: no atomics
+    const int id = s_query[tid];
+    if (id >= 0 && id < V) {
+      unsigned long long bits = 0ull;
+      for (int j = 0; j < m; ++j) bits |= s_query[j] == id ? 1ull << j : 0ull;
+      peq[id] = bits;
+    }
+  }
+  __syncthreads();
+
+  unsigned long long best[KL_LEXICON_K_MAX];
+#pragma unroll
+  for (int i = 0; i < KL_LEXICON_K_MAX; ++i) best[i] = NO_KEY;
+  unsigned int least_exact = 0xFFFFFFFFu;
+  int n_found = 0;
+  if (narrow && m <= 32)      // (uniform: a workgroup is one query)
+    walk_classes<unsigned int>(chars, order, table, peq, V, m, max_dist, tid, best, least_exact, n_found);
+  else
+    walk_classes<unsigned long long>(chars, order, table, peq, V, m, max_dist, tid, best, least_exact, n_found);
+
+  // exact and found
+  {
+    unsigned int x = least_exact;
+#pragma unroll
+    for (int off = KL_WAVE / 2; off > 0; off >>= 1) {
+      const unsigned int o = __shfl_xor(x, off, KL_WAVE);
+      x = o < x ? o : x;
+    }
+    const int f = wave_sum(n_found);
+    if (lane == 0) {
+      s_exact[wave] = x;
+      s_found[wave] = f;
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    unsigned int x = s_exact[0];
+    int f = s_found[0];
+#pragma unroll
+    for (int w = 1; w < LEX_WAVES; ++w) {
+      x = s_exact[w] < x ? s_exact[w] : x;
+      f += s_found[w];
+    }
+    exact[q] = x == 0xFFFFFFFFu ? -1 : (int)x;
+    found[q] = f;
+  }
+  // the K smallest keys of the workgroup, one per round
+  for (int r = 0; r < K; ++r) {
+    const unsigned long long head = best[0];
+    const unsigned long long wmin = wave_min(head);
+    if (lane == 0) s_key[wave] = wmin;
+    __syncthreads();
+    unsigned long long gmin = s_key[0];
+#pragma unroll
+    for (int w = 1; w < LEX_WAVES; ++w) gmin = s_key[w] < gmin ? s_key[w] : gmin;
+    const unsigned long long mask = __ballot(head == gmin && gmin != NO_KEY);
+    if (lane == 0) s_mask[wave] = mask;
+    __syncthreads();
+    int w_first = LEX_WAVES;
+#pragma unroll
+    for (int w = LEX_WAVES - 1; w >= 0; --w) w_first = s_mask[w] != 0ull ? w : w_first;
+    if (wave == w_first && lane == __ffsll((long long)mask) - 1) {      // the lowest thread among equal keys drops its head
+#pragma unroll
+      for (int i = 0; i + 1 < KL_LEXICON_K_MAX; ++i) best[i] = best[i + 1];
+      best[KL_LEXICON_K_MAX - 1] = NO_KEY;
+    }
+    if (tid == 0) {
+      cand[q * K + r] = gmin == NO_KEY ? -1 : (int)(unsigned int)(gmin & 0xFFFFFFFFull);
+      dist[q * K + r] = gmin == NO_KEY ? -1 : (int)(gmin >> 32);
+    }
+  }
+}
+
+inline bool misaligned(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
+
+}  // namespace
+
+extern "C" size_t kl_lexicon_neighbours_workspace_bytes(size_t Q, int K) {
+  (void)Q;
+  (void)K;
+  return sizeof(lex_classes);      // (the class table, whatever Q and K are)
+}
+
+extern "C" int kl_lexicon_neighbours(const int32_t* chars, size_t n_chars, const int32_t* order, const int64_t* class_first, int V,
+                                     const int32_t* q_pool, size_t n_q, const int64_t* q_off, size_t Q, int max_dist, int K,
+                                     int32_t* exact, int32_t* found, int32_t* cand, int32_t* dist, void* ws, size_t ws_bytes,
+                                     void* stream) {
+  if (!chars || !order || !class_first || !q_off || !exact || !found || !cand || !dist || !ws) return KL_ERR_ARG;
+  if (n_q > 0 && !q_pool) return KL_ERR_ARG;
+  if (V < 1 || V > KL_LEXICON_V_MAX || max_dist < 0 || max_dist > KL_LEXICON_DIST_MAX || K < 1 || K > KL_LEXICON_K_MAX)
+    return KL_ERR_ARG;
+  if (Q < 1 || Q > MAX_QUERIES || n_q > MAX_POOL || n_chars > MAX_POOL) return KL_ERR_ARG;
+  const void* words[] = {chars, order, q_pool, exact, found, cand, dist};
+  for (const void* p : words)
+    if (misaligned(p, 3)) return KL_ERR_ARG;
+  if (misaligned(q_off, 7) || misaligned(class_first, 7) || misaligned(ws, 7)) return KL_ERR_ARG;
+  // the class table: every address the kernel forms is checked here
+  lex_classes cls;
+  if (class_first[0] != 0 || class_first[1] != 0) return KL_ERR_ARG;
+  for (int L = 1; L <= LEX_LEN_MAX + 1; ++L)
+    if (class_first[L] < class_first[L - 1] || class_first[L] > 0x7FFFFFFFll) return KL_ERR_ARG;
+  long long total = 0;      // (at most 64 * 2^31)
+  for (int L = 0; L <= LEX_LEN_MAX + 1; ++L) {
+    cls.first[L] = class_first[L];
+    cls.base[L] = total;
+    if (L <= LEX_LEN_MAX) total += (long long)L * (class_first[L + 1] - class_first[L]);
+  }
+  if (class_first[LEX_LEN_MAX + 1] < 1 || (unsigned long long)total != (unsigned long long)n_chars) return KL_ERR_ARG;
+  if (ws_bytes < kl_lexicon_neighbours_workspace_bytes(Q, K)) return KL_ERR_WORKSPACE;
+  // KL_LEXICON_NARROW=0: the 64-bit pattern word for every query (the A/B switch of tools/bench_lexicon.py)
+  const char* env = getenv("KL_LEXICON_NARROW");
+  const int narrow = !(env && env[0] == '0');
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  long long* table = reinterpret_cast<long long*>(ws);
+  hipLaunchKernelGGL(lexicon_classes_kernel, dim3(1), dim3(2 * KL_WAVE), 0, s, cls, table);
+  hipLaunchKernelGGL(lexicon_neighbours_kernel, dim3((unsigned)Q), dim3(LEX_THREADS), 0, s, chars, order, table, V, q_pool,
+                     (long long)n_q, reinterpret_cast<const long long*>(q_off), max_dist, K, narrow, exact, found, cand, dist);
+  return hipGetLastError() == hipSuccess ? KL_OK : KL_ERR_LAUNCH;
+}

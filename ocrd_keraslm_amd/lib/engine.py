@@ -91,7 +91,8 @@ class HipLM:
         self._rate_select_ws = None
         self._word_bounds_ws = None
         self._segment_select_ws = None
-        self.states = None        # [B][2L][W] implicit state of the stateful streams
+        self._lexicon_ws = None
+        self.states = None       # [B][2L][W] implicit state of the stateful streams
         self.pool = None            # [slots][2L][W] explicit states of hypotheses
         self.max_streams_per_launch = 0      # 0: what the kernels address (train_window splits larger batches into groups)
         self._part_grads = None
@@ -735,6 +736,34 @@ class HipLM:
             out = empty(m)
             if m:
                 call(m, out)
+        return out
+
+    def lexicon_neighbours(self, chars_d, order_d, class_first, V, q_pool_d, q_off_d, max_dist, K):
+        """kl_lexicon_neighbours: the entries of a lexicon within max_dist edits of Q query words.  chars_d int32 and order_d
+        int32 [N'] are DEVICE copies of what `ratebulk.lexicon_layout_host` built, class_first its int64 [66] on the HOST (every
+        bound is checked there before the launch); q_pool_d int32 and q_off_d int64 [Q + 1] the queries on the DEVICE; ids are
+        equal only within [0, V).  Returns the DEVICE tensors (exact int32 [Q], found int32 [Q], cand int32 [Q, K], dist int32
+        [Q, K]); the statement is ratebulk.lexicon_neighbours_host.  hipabi.KlError for what the entry point rejects.  No
+        synchronisation."""
+        torch = self.torch
+        tensors = (chars_d, order_d, q_pool_d, q_off_d)
+        if ([t.dtype for t in tensors] != [torch.int32, torch.int32, torch.int32, torch.int64] or any(t.dim() != 1 for t in tensors)
+                or q_off_d.numel() < 2 or not all(t.is_contiguous() and t.is_cuda for t in tensors)):
+            raise hipabi.KlError("lexicon_neighbours: chars, order and q_pool int32, q_off int64 [Q + 1], contiguous, on the device")
+        class_first = np.ascontiguousarray(class_first, dtype=np.int64).reshape(-1)
+        if len(class_first) != 66 or order_d.numel() != int(class_first[-1]):
+            raise hipabi.KlError("lexicon_neighbours: class_first int64 [66] on the host, its last value the size of order")
+        V, max_dist, K = int(V), int(max_dist), int(K)
+        Q = q_off_d.numel() - 1
+        dev = self.device
+        with self._launch():
+            ws = self._scratch("_lexicon_ws", self.lib.kl_lexicon_neighbours_workspace_bytes(Q, K))
+            out = (torch.empty(Q, dtype=torch.int32, device=dev), torch.empty(Q, dtype=torch.int32, device=dev),
+                   torch.empty((Q, max(K, 0)), dtype=torch.int32, device=dev), torch.empty((Q, max(K, 0)), dtype=torch.int32, device=dev))
+            hipabi.check(self.lib.kl_lexicon_neighbours(
+                _ptr(chars_d), chars_d.numel(), _ptr(order_d), class_first.ctypes.data, V, _ptr(q_pool_d), q_pool_d.numel(),
+                _ptr(q_off_d), Q, max_dist, K, *([_ptr(t) for t in out] + [_ptr(ws), ws.numel(), self._stream()])),
+                "kl_lexicon_neighbours")
         return out
 
     def variant_windows(self, corpus_d, offsets_d, text_ctx_d, sel_pos_d, sel_alt_id_d, left, ahead, deletions, T,

@@ -18,6 +18,7 @@ KL_PREC_SPLIT = 3
 KL_RATE_ALTS_MAX = 8     # alternatives per position kl_rate_window_alts delivers at most
 KL_SPAN_LEN_MAX = 64     # ids of a span and of a candidate of kl_span_windows at most
 KL_CTX_CAND_MAX = 256    # candidate contexts of kl_rate_scatter_planes / kl_context_mix at most
+KL_LEXICON_V_MAX, KL_LEXICON_DIST_MAX, KL_LEXICON_K_MAX = 4096, 8, 16      # kl_lexicon_neighbours: ids, max_dist and K at most
 KL_RATE_SELECT_BLOCK = 1024          # positions per workgroup of kl_rate_select
 KL_RATE_SELECT_SCAN_THREADS = 256    # ... and blocks per round of its one offsets workgroup
 KL_SAMPLE_MAX_ROWS = 1024  # chains per kl_sample_pick call
@@ -137,6 +138,10 @@ SIGNATURES = {
     "kl_segment_select_workspace_bytes": (C.c_size_t, [C.c_size_t]),
     "kl_segment_select": (C.c_int, [C.c_void_p] * 8 + [C.c_size_t, C.c_int, C.c_int, C.c_double, C.c_size_t] + [C.c_void_p] * 11
                           + [C.c_size_t, C.c_void_p]),
+    "kl_lexicon_neighbours_workspace_bytes": (C.c_size_t, [C.c_size_t, C.c_int]),
+    "kl_lexicon_neighbours": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                                        C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_size_t, C.c_void_p]),
     "kl_train_window": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "kl_assemble_windows": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,

@@ -18,7 +18,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import windows
+from . import ratebulk, windows
 
 
 class Plan(object):
@@ -334,6 +334,79 @@ def word_edits(found, texts, candidates):
             if replacements:
                 edits.append((i, start, end, replacements))
     return edits
+
+
+class Lexicon(object):
+    """A list of words to look suspect words up in (`Rater.lexicon` builds it, `Rater.lexicon_neighbours` and
+    `Rater.correct_words` read it).  `entries` is an iterable of strings in priority order, the most frequent first; they are
+    NFC-normalised and encoded with `mapping` (char -> id), ids below `voc_size`.  Dropped, and counted by reason in `dropped`
+    ("empty", "long": more than 64 characters, "unmapped": a character outside the mapping, "duplicate": the first is kept):
+
+    words        [N] str         the kept entries, in the order given -- what the neighbours' indices refer to
+    pool, off    int32, int64 [N + 1]   their ids end to end and where each begins
+    chars, order, class_first    the device layout of `ratebulk.lexicon_layout_host`
+    mapping, voc_size            what it was encoded with
+    dropped      dict            reason -> count
+    """
+
+    def __init__(self, entries, mapping, voc_size):
+        if int(voc_size) > ratebulk.LEXICON_V_MAX:
+            raise ValueError("a lexicon needs a mapping of at most %d characters (got %d)" % (ratebulk.LEXICON_V_MAX, voc_size))
+        self.mapping, self.voc_size = mapping, int(voc_size)
+        self._mapped = len(mapping)
+        self.dropped = dict(empty=0, long=0, unmapped=0, duplicate=0)
+        self.words = []
+        seen = set()
+        for entry in entries:
+            word = windows.normalize(entry)
+            reason = ("empty" if not word else "long" if len(word) > ratebulk.SPAN_LEN_MAX
+                      else "unmapped" if any(not 0 < mapping.get(c, 0) < self.voc_size for c in word)
+                      else "duplicate" if word in seen else None)
+            if reason:
+                self.dropped[reason] += 1
+            else:
+                seen.add(word)
+                self.words.append(word)
+        self.pool = windows.encode("".join(self.words), mapping).astype(np.int32)
+        self.off = np.concatenate([[0], np.cumsum([len(w) for w in self.words])]).astype(np.int64)
+        self.chars, self.order, self.class_first = ratebulk.lexicon_layout_host(self.pool, self.off)
+        self._device = {}      # id(engine) -> (engine, chars, order) on its device: uploaded once
+
+    def __len__(self):
+        return len(self.words)
+
+    def same_mapping(self, mapping):
+        """was the lexicon encoded with this very mapping (the same object, no character added since)?"""
+        return mapping is self.mapping and len(mapping) == self._mapped
+
+    def on_device(self, lm):
+        """(chars, order) as int32 tensors on the engine's device: uploaded at the first call, kept for the later ones"""
+        held = self._device.get(id(lm))
+        if held is None or held[0] is not lm:
+            up = lambda a: lm.torch.from_numpy(np.ascontiguousarray(a)).to(lm.device)
+            held = self._device[id(lm)] = (lm, up(self.chars), up(self.order))
+        return held[1], held[2]
+
+
+class Neighbours(object):
+    """What `Rater.lexicon_neighbours` returns for n words, in input order, K = per_word:
+
+    exact   [n] i32     the index into `lexicon.words` of the word itself, -1: it is not in the lexicon
+    found   [n] i32     how many entries lie within 1 .. max_dist edits of it, whatever K is
+    index   [n,K] i32   the first K of them, ordered by (distance, index) -- the nearest first, the more frequent among equally
+                        near ones --, -1 from the found-th on
+    dist    [n,K] i32   their distances, -1 where index is
+    """
+
+    def __init__(self, lexicon, exact, found, index, dist):
+        self.lexicon, self.exact, self.found, self.index, self.dist = lexicon, exact, found, index, dist
+
+    def __len__(self):
+        return len(self.exact)
+
+    def strings(self, i):
+        """the neighbours of word i as strings, the nearest first"""
+        return [self.lexicon.words[int(e)] for e in self.index[i] if e >= 0]
 
 
 def confusion_edits(texts, rules, at=None):

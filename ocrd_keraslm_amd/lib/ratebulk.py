@@ -28,6 +28,8 @@ make of spans with caller-supplied replacements for `Rater.rescore`.  `plan_cand
 `scatter_planes_host` and `context_mix_host` state what kl_rate_scatter_planes and kl_context_mix make of its calls.
 `word_bounds_host`, `segments_host` and `segment_select_host` state kl_word_bounds, kl_rate_segments and kl_segment_select: the
 words of the texts, a rating per segment and the ordered selection among them (`Rater.suspect_words`, `Rater.rate_segments`).
+`lexicon_layout_host` builds the device layout of a word list and `lexicon_neighbours_host` states kl_lexicon_neighbours: the
+entries within a few edits of every query word (`Rater.lexicon_neighbours`, `Rater.correct_words`).
 numpy only: the plan is built and tested without an engine.
 """
 from __future__ import annotations
@@ -738,3 +740,105 @@ def segment_select_host(seg_start, seg_end, seg_n, seg_bits, seg_psum, seg_min, 
         keep = (n >= min_n) & (bad >= min_bad) & (bits.astype(np.float64) >= min_bpc * n.astype(np.float64))
     index = np.nonzero(keep)[0].astype(np.int64)
     return (index,) + tuple(a[index] for a in records)
+
+
+LEXICON_V_MAX, LEXICON_DIST_MAX, LEXICON_K_MAX = 4096, 8, 16      # (KL_LEXICON_* of the C ABI)
+
+
+def lexicon_layout_host(pool, off):
+    """the device layout of a lexicon for kl_lexicon_neighbours: pool int32 ids and off int64 [N + 1] are the N entries in the
+    caller's order -- the priority order, the most frequent entry first.  Returns (chars, order, class_first):
+      order        int32 [N']  the original indices of the entries of 1 .. SPAN_LEN_MAX ids, sorted by (length, original
+                               index); entries of no ids or of more are left out -- they are neighbours of nothing;
+      class_first  int64 [66]  the entries of length L are the sorted positions [class_first[L], class_first[L + 1]);
+                               class_first[0] = class_first[1] = 0, class_first[65] = N';
+      chars        int32       column-major within a length class: with n_L entries in class L and base[L] = sum over l < L of
+                               l * n_l, id j of sorted position p of class L is chars[base[L] + j * n_L + (p - class_first[L])]
+                               -- consecutive lanes read consecutive addresses."""
+    pool = np.asarray(pool, dtype=np.int32).reshape(-1)
+    off = np.asarray(off, dtype=np.int64).reshape(-1)
+    if len(off) < 1 or off[0] < 0 or (np.diff(off) < 0).any() or off[-1] > len(pool):
+        raise ValueError("lexicon_layout_host: off [N + 1] ascending within the pool")
+    length = np.diff(off)
+    kept = np.nonzero((length >= 1) & (length <= SPAN_LEN_MAX))[0]
+    order = kept[np.argsort(length[kept], kind="stable")].astype(np.int32)      # (stable: ascending index within a class)
+    class_first = np.zeros(SPAN_LEN_MAX + 2, dtype=np.int64)
+    class_first[1:] = np.searchsorted(length[order], np.arange(1, SPAN_LEN_MAX + 2), side="left")
+    parts = []
+    for L in range(1, SPAN_LEN_MAX + 1):
+        a, b = int(class_first[L]), int(class_first[L + 1])
+        if b > a:
+            rows = pool[off[order[a:b]][:, None] + np.arange(L)[None, :]]      # [n_L, L]
+            parts.append(np.ascontiguousarray(rows.T).reshape(-1))
+    chars = np.concatenate(parts).astype(np.int32) if parts else np.zeros(0, dtype=np.int32)
+    return chars, order, class_first
+
+
+def lexicon_neighbours_host(q_pool, q_off, chars, order, class_first, V, max_dist, K):
+    """what kl_lexicon_neighbours computes: for the Q queries q_pool[q_off[q]:q_off[q + 1]] and the lexicon (chars, order,
+    class_first) of `lexicon_layout_host`, (exact int32 [Q], found int32 [Q], cand int32 [Q, K], dist int32 [Q, K]).  Two ids
+    are equal iff they are the same number AND that number lies in [0, V): an id outside the range equals nothing, itself
+    included.  lev is the Levenshtein distance with unit costs under that equality.  For a query of 1 .. 64 ids, over the
+    entries e of `order` with lev(q, e) <= max_dist: exact[q] the smallest original index with lev == 0, or -1; found[q] the
+    number with lev >= 1, whatever K is; cand[q] the original indices of the first K of these ordered by (lev, original index),
+    dist[q] their distances, unused places -1 in both.  A query of no ids or of more than 64 gets -1, 0 and -1 everywhere.
+    Duplicate entries are separate entries.  A plain DP, row by row of the query, over all entries of a length class at once
+    -- only the classes max(1, m - max_dist) .. min(64, m + max_dist) can hold a neighbour."""
+    q_pool = np.asarray(q_pool, dtype=np.int64).reshape(-1)
+    q_off = np.asarray(q_off, dtype=np.int64).reshape(-1)
+    chars = np.asarray(chars, dtype=np.int64).reshape(-1)
+    order = np.asarray(order, dtype=np.int64).reshape(-1)
+    class_first = np.asarray(class_first, dtype=np.int64).reshape(-1)
+    V, max_dist, K = int(V), int(max_dist), int(K)
+    if not (1 <= V <= LEXICON_V_MAX and 0 <= max_dist <= LEXICON_DIST_MAX and 1 <= K <= LEXICON_K_MAX):
+        raise ValueError("lexicon_neighbours_host: V in 1 .. %d, max_dist in 0 .. %d, K in 1 .. %d"
+                         % (LEXICON_V_MAX, LEXICON_DIST_MAX, LEXICON_K_MAX))
+    n_class = np.diff(class_first)
+    base = np.concatenate([[0], np.cumsum(np.arange(SPAN_LEN_MAX + 1) * n_class)])
+    if (len(class_first) != SPAN_LEN_MAX + 2 or class_first[0] != 0 or class_first[1] != 0 or (n_class < 0).any()
+            or class_first[-1] != len(order) or base[-1] != len(chars)):
+        raise ValueError("lexicon_neighbours_host: class_first [66] ascending from 0, 0 to len(order), chars of sum L * n_L ids")
+    if len(q_off) < 1 or q_off[0] < 0 or (np.diff(q_off) < 0).any() or q_off[-1] > len(q_pool):
+        raise ValueError("lexicon_neighbours_host: q_off [Q + 1] ascending within the pool")
+    Q = len(q_off) - 1
+    exact = np.full(Q, -1, dtype=np.int32)
+    found = np.zeros(Q, dtype=np.int32)
+    cand = np.full((Q, K), -1, dtype=np.int32)
+    dist = np.full((Q, K), -1, dtype=np.int32)
+    known = (chars >= 0) & (chars < V)
+    for q in range(Q):
+        word = q_pool[q_off[q]:q_off[q + 1]]
+        m = len(word)
+        if not 1 <= m <= SPAN_LEN_MAX:
+            continue
+        hits, levs = [], []
+        for L in range(max(1, m - max_dist), min(SPAN_LEN_MAX, m + max_dist) + 1):
+            n = int(n_class[L])
+            if n == 0:
+                continue
+            entry = chars[base[L]:base[L + 1]].reshape(L, n)             # [L, n]: id j of every entry of the class
+            valid = known[base[L]:base[L + 1]].reshape(L, n)
+            prev = np.repeat(np.arange(L + 1, dtype=np.int32)[:, None], n, axis=1)      # row 0: j edits
+            for i in range(1, m + 1):
+                differ = ~((entry == word[i - 1]) & valid)      # (a query id outside [0, V) is never among the valid ones)
+                cur = np.empty_like(prev)
+                cur[0] = i
+                for j in range(1, L + 1):
+                    cur[j] = np.minimum(np.minimum(prev[j] + 1, cur[j - 1] + 1), prev[j - 1] + differ[j - 1])
+                prev = cur
+            lev = prev[L]
+            near = np.nonzero(lev <= max_dist)[0]
+            hits.append(order[class_first[L] + near])
+            levs.append(lev[near].astype(np.int64))
+        if not hits:
+            continue
+        hits, levs = np.concatenate(hits), np.concatenate(levs)
+        same = hits[levs == 0]
+        if len(same):
+            exact[q] = same.min()
+        hits, levs = hits[levs > 0], levs[levs > 0]
+        found[q] = len(hits)
+        first = np.lexsort((hits, levs))[:K]
+        cand[q, :len(first)] = hits[first]
+        dist[q, :len(first)] = levs[first]
+    return exact, found, cand, dist

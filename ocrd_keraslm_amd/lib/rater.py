@@ -1671,6 +1671,95 @@ class Rater(object):
                                           best[a:b], gain[a:b])
         return found
 
+    def lexicon(self, words):
+        '''A ratebatch.Lexicon of `words` -- an iterable of strings in priority order, the most frequent first --, normalised
+        and encoded with this rater's mapping: what `lexicon_neighbours` and `correct_words` look suspect words up in.  Empty
+        entries, entries of more than 64 characters, entries with a character outside the mapping and duplicates (the first is
+        kept) are dropped and counted in `.dropped`.  Its device copy is made at the first look-up on an engine and kept.
+        ValueError for a mapping of more than 4096 characters.'''
+        assert self.status > 1
+        return ratebatch.Lexicon(words, self.mapping[0], self.voc_size)
+
+    def _lexicon_request(self, method, lexicon, max_dist, per_word):
+        max_dist, per_word = int(max_dist), int(per_word)
+        if not (0 <= max_dist <= ratebulk.LEXICON_DIST_MAX and 1 <= per_word <= ratebulk.LEXICON_K_MAX):
+            raise ValueError("%s: max_dist in 0 .. %d and per_word in 1 .. %d (got %d, %d)"
+                             % (method, ratebulk.LEXICON_DIST_MAX, ratebulk.LEXICON_K_MAX, max_dist, per_word))
+        if not isinstance(lexicon, ratebatch.Lexicon) or not lexicon.same_mapping(self.mapping[0]) or lexicon.voc_size != self.voc_size:
+            raise ValueError("%s: the lexicon was not built by this rater's `lexicon`, or the mapping has changed since" % method)
+        return max_dist, per_word
+
+    def lexicon_neighbours(self, words, lexicon, max_dist=2, per_word=8):
+        '''Which entries of the lexicon could these words have been?  Returns a ratebatch.Neighbours in input order: per word
+        `exact` (its own index in `lexicon.words`, -1: not an entry), `found` (how many entries lie within 1 .. max_dist
+        edits -- Levenshtein distance, unit costs) and the first `per_word` of them ordered by (distance, index), that is the
+        nearest first and the more frequent among equally near ones, with their distances; -1 fills the unused places.
+
+        The words are normalised, made unique on the host and encoded; there is one upload (offsets and ids in one buffer), one
+        kernel call (`HipLM.lexicon_neighbours`: every (word, entry) pair of the length classes within max_dist on the device)
+        and one download of 8 + 8 * per_word bytes per distinct word; the result is spread back over the duplicates.  A word of
+        more than 64 characters (or of none) is a neighbour of nothing.  A character outside the mapping keeps id 0 here, and id
+        0 is an ordinary id of the look-up: two different unmapped characters are equal, as in `rescore` -- but no entry holds
+        one, so such a position always costs an edit.  No words, or a lexicon without an entry, give their result without a
+        launch.  An engine without `lexicon_neighbours` (the tests' CPU double) runs ratebulk.lexicon_neighbours_host.
+        ValueError for max_dist outside 0 .. 8, per_word outside 1 .. 16, a lexicon of another mapping.'''
+        assert self.status > 1
+        max_dist, K = self._lexicon_request("lexicon_neighbours", lexicon, max_dist, per_word)
+        words = [windows.normalize(w) for w in words]
+        slot = {}
+        for w in words:
+            slot.setdefault(w, len(slot))
+        unique = list(slot)
+        Q = len(unique)
+        out = np.full((Q, 2 + 2 * K), -1, dtype=np.int32)      # (exact, found, index [K], dist [K] per distinct word)
+        out[:, 1] = 0
+        if Q and len(lexicon):
+            pool = windows.encode("".join(unique), self.mapping[0]).astype(np.int32)
+            q_off = np.concatenate([[0], np.cumsum([len(w) for w in unique])]).astype(np.int64)
+            lm = self.model
+            if hasattr(lm, 'lexicon_neighbours'):
+                torch = lm.torch
+                chars_d, order_d = lexicon.on_device(lm)
+                both = torch.from_numpy(np.concatenate([q_off.view(np.int32), pool])).to(lm.device)
+                res = lm.lexicon_neighbours(chars_d, order_d, lexicon.class_first, self.voc_size, both[2 * (Q + 1):],
+                                            both[:2 * (Q + 1)].view(torch.int64), max_dist, K)
+                out = _np(torch.cat([res[0][:, None], res[1][:, None], res[2], res[3]], dim=1))
+            else:
+                res = ratebulk.lexicon_neighbours_host(pool, q_off, lexicon.chars, lexicon.order, lexicon.class_first,
+                                                       self.voc_size, max_dist, K)
+                out = np.concatenate([res[0][:, None], res[1][:, None], res[2], res[3]], axis=1)
+        rows = np.asarray([slot[w] for w in words], dtype=np.int64)
+        out = out[rows] if len(rows) else out[:0]
+        return ratebatch.Neighbours(lexicon, out[:, 0].copy(), out[:, 1].copy(), out[:, 2:2 + K].copy(), out[:, 2 + K:].copy())
+
+    def correct_words(self, texts, lexicon, contexts=None, max_dist=2, per_word=8, known=False, delimiters=None, k=3,
+                      max_prob=0.01, min_rank=1, min_suspects=1, min_bits_per_char=0.0, min_chars=1, left=64, ahead=8,
+                      min_gain=1.0, streams=1024, precision="bf16"):
+        '''From texts to lexicon-backed corrections: `suspect_words` -> the suspect words' nearest lexicon entries ->
+        `rescore`.  Returns (found, rescored, bits): `found` and `bits` are `suspect_words(texts, contexts, delimiters=..,
+        k=.., max_prob=.., min_rank=.., min_suspects=.., min_bits_per_char=.., min_chars=.., streams=.., precision=..)`'s;
+        all selected words of all texts go through ONE `lexicon_neighbours(words, lexicon, max_dist, per_word)`; a word that is
+        an entry itself (`exact` >= 0) yields no candidates unless known=True -- a word of the lexicon is left alone by default
+        --, every other word its neighbours in order; `rescored` is `rescore(texts, ratebatch.word_edits(found, texts, table),
+        contexts, streams=.., left=.., ahead=.., min_gain=.., precision=..)` with `table` the dict word -> neighbour strings.
+        The edits are built on the host from the downloaded neighbours (8 bytes per candidate).  State and precision afterwards
+        are as after `rescore`.  ValueError for what these three raise.'''
+        self._lexicon_request("correct_words", lexicon, max_dist, per_word)
+        texts = list(texts)
+        found, bits = self.suspect_words(texts, contexts, delimiters=delimiters, k=k, streams=streams, max_prob=max_prob,
+                                         min_rank=min_rank, min_suspects=min_suspects, min_bits_per_char=min_bits_per_char,
+                                         min_chars=min_chars, precision=precision)
+        words = [w for one, text in zip(found, texts) for w in one.strings(windows.normalize(text))]
+        near = self.lexicon_neighbours(words, lexicon, max_dist=max_dist, per_word=per_word)
+        table = {}
+        for i, word in enumerate(words):
+            if word not in table:
+                table[word] = near.strings(i) if known or near.exact[i] < 0 else []
+        edits = ratebatch.word_edits(found, texts, table)
+        rescored = self.rescore(texts, edits, contexts, streams=streams, left=left, ahead=ahead, min_gain=min_gain,
+                                precision=precision)
+        return found, rescored, bits
+
     def _contexts_per_text(self, contexts, n):
         '''None, one context list for all texts, or one per text -> one list per text (as `rate_batch` reads them)'''
         if contexts is None or len(contexts) == 0:

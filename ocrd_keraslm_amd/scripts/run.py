@@ -21,6 +21,9 @@ the posterior over them, and its bits under the best one, under their sequential
 Additional command `words`: per DATA file the words the model does not believe -- at least --min-suspects suspect characters,
 --min-bits-per-char bits per predicted character and --min-chars predicted characters -- with their bits, mean and least
 probability (Rater.suspect_words: rated in bulk, the words found, rated and picked out on the device).
+Additional command `lexicon`: the suspect words of every DATA file looked up in a word list (--lexicon, the most frequent entry
+first) on the device, and their nearest entries rated against the text around them (Rater.correct_words: suspect_words ->
+lexicon_neighbours -> rescore); output as `rescore`'s, --apply also gives the corrected text.
 Additional options on `train`: --streams (stateful streams per GPU, default 1 = the
 reference's batching) and --segment-streams (with fewer files than streams, cut the files
 into contiguous segments on window boundaries, one list of segments per stream).  Under `python -m torch.distributed.run` training is
@@ -37,7 +40,7 @@ import click
 
 from .. import lib
 
-COMMAND_ORDER = ['train', 'test', 'score', 'suspects', 'correct', 'rescore', 'contexts', 'words', 'apply', 'generate', 'print-history', 'print-charset', 'prune-charset',
+COMMAND_ORDER = ['train', 'test', 'score', 'suspects', 'correct', 'rescore', 'contexts', 'words', 'lexicon', 'apply', 'generate', 'print-history', 'print-charset', 'prune-charset',
                  'plot-char-embeddings-similarity', 'plot-context-embeddings-similarity', 'plot-context-embeddings-projection']
 
 
@@ -535,6 +538,85 @@ def words(model, streams, precision, k, max_prob, min_rank, min_suspects, min_bi
                                                                   one.min_prob, one.worst, one.suspects)]
         click.echo(json.dumps({"file": name, "chars": len(text), "bits_per_char": float(total) / max(len(text) - 1, 1),
                                "words": rows}, ensure_ascii=False))
+
+
+def _read_lexicon(path):
+    """one entry per line, the most frequent first; anything after a tab (a count, say) is ignored"""
+    with open(path, mode='r') as file:
+        return [line.rstrip('\r\n').split('\t')[0] for line in file]
+
+
+@cli.command('lexicon', short_help='correct the words the model does not believe from a word list')
+@click.option('-m', '--model', default="model.h5", show_default=True, help='model file', type=click.Path(dir_okay=False, exists=True))
+@click.option('--lexicon', 'lexicon_file', required=True, type=click.Path(dir_okay=False, exists=True),
+              help='word list: one entry per line, the most frequent first; anything after a tab is ignored')
+@click.option('--max-dist', default=2, show_default=True, type=click.IntRange(min=0, max=8),
+              help='an entry is a candidate for a word within this many edits (insertions, deletions, substitutions)')
+@click.option('--per-word', default=8, show_default=True, type=click.IntRange(min=1, max=16),
+              help='candidates per word at most: the nearest, the more frequent among equally near ones')
+@click.option('--known', is_flag=True, default=False, help='also look up the words that are entries themselves')
+@click.option('-s', '--streams', default=1024, show_default=True, help='rows of a window call: files, then hypotheses',
+              type=click.IntRange(min=1, max=4096))
+@click.option('--precision', default='bf16', show_default=True, type=click.Choice(['bf16', 'split']),
+              help='bf16: bulk rating on the training forward; split: the inference kernels, ~f32 accuracy')
+@click.option('-k', 'k', default=3, show_default=True, type=click.IntRange(min=1, max=8),
+              help='alternatives ranked per character in the rating pass')
+@click.option('--max-prob', default=0.01, show_default=True, type=click.FLOAT,
+              help='a suspect character has at most this probability')
+@click.option('--min-rank', default=1, show_default=True, type=click.IntRange(min=0),
+              help='... and at least this rank among the characters the model could have written (0: its first choice)')
+@click.option('--min-suspects', default=1, show_default=True, type=click.IntRange(min=0),
+              help='a word is looked up with at least this many suspect characters')
+@click.option('--min-bits-per-char', default=0.0, show_default=True, type=click.FloatRange(min=0.0),
+              help='... at least this many bits per predicted character')
+@click.option('--min-chars', default=1, show_default=True, type=click.IntRange(min=1),
+              help='... and at least this many predicted characters')
+@click.option('--delimiters', default=None, help='the characters that separate words [default: the mapped whitespace characters]')
+@click.option('--left', default=64, show_default=True, type=click.IntRange(min=1, max=1024),
+              help='characters in front of a word that a hypothesis is read from (from a zero state)')
+@click.option('--ahead', default=8, show_default=True, type=click.IntRange(min=0, max=1023),
+              help='characters after a word that a hypothesis is held against')
+@click.option('--min-gain', default=1.0, show_default=True, type=click.FLOAT,
+              help='a proposal must save at least this many bits against the text as written')
+@click.option('--apply', 'apply_', is_flag=True, default=False, help='also give the text with the proposals applied ("corrected")')
+@click.argument('data', nargs=-1, type=click.Path(exists=True, dir_okay=True, file_okay=True))
+def lexicon_(model, lexicon_file, max_dist, per_word, known, streams, precision, k, max_prob, min_rank, min_suspects,
+             min_bits_per_char, min_chars, delimiters, left, ahead, min_gain, apply_, data):
+    """Apply a language model to DATA files, look the words it does not believe up in the word list and
+       print one JSON line per file, as `rescore` does: characters and "rescored": one [start, end, written,
+       proposed, gain] per word that has candidates -- proposed is the entry that replaces text[start:end],
+       null for no proposal.  With --apply the line also holds the corrected text.
+
+       Files are read, and given their contexts, as `score` does; the words are chosen as `words` chooses them.
+    """
+    from ..lib import windows
+    rater = _load(model)
+    try:
+        lexicon = rater.lexicon(_read_lexicon(lexicon_file))
+    except ValueError as err:
+        raise click.UsageError(str(err))
+    names, texts, contexts = [], [], []
+    for file in _open_all(data):
+        with file:
+            texts.append(windows.normalize(file.read()))
+        names.append(file.name)
+        contexts.append(windows.context_from_filename(file.name))
+    if not texts:
+        return
+    try:
+        _, found, _ = rater.correct_words(texts, lexicon, contexts, max_dist=max_dist, per_word=per_word, known=known,
+                                          delimiters=delimiters, k=k, max_prob=max_prob, min_rank=min_rank,
+                                          min_suspects=min_suspects, min_bits_per_char=min_bits_per_char, min_chars=min_chars,
+                                          left=left, ahead=ahead, min_gain=min_gain, streams=streams, precision=precision)
+    except ValueError as err:
+        raise click.UsageError(str(err))
+    for name, text, one in zip(names, texts, found):
+        rows = [[int(a), int(b), text[int(a):int(b)], new, float(g)]
+                for a, b, new, g in zip(one.starts, one.ends, one.proposals(), one.gain)]
+        line = {"file": name, "chars": len(text), "rescored": rows}
+        if apply_:
+            line["corrected"] = one.apply(text)
+        click.echo(json.dumps(line, ensure_ascii=False))
 
 
 @cli.command(short_help='sample characters from language model')
