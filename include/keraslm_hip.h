@@ -865,6 +865,42 @@ typedef struct kl_window_view {
 } kl_window_view;
 int kl_test_window_view(const kl_handle* h, int B, int T, const void* ws, kl_window_view* out);
 
+/* Test hook: which scan family ran the handle's most recent INFERENCE-layout window of B streams x T steps on workspace ws
+ * in the handle's current precision -- kl_forward_window on a workspace of kl_window_workspace_bytes(h, B, T, 0), or
+ * kl_rate_window / kl_rate_window_alts, which carve the same window at the start of theirs --, and where it left what it wrote.
+ * All arrays are time-major with the padded width W = `width`: row r = block * B + b.
+ *   off_H    f32  [(T+1)B][W]   outputs, block 0 = the carried-in h, block t + 1 = step t
+ *   off_C    f32  [(T+1)B][W]   cell states, block 0 = the carried-in c; block T = the carried-out c; the blocks between are
+ *                               written only with c_every_step (the persistent scans keep c in registers)
+ *   off_Xhi, off_Xlo  bf16 [(T+1)B][W]   the (hi, lo) planes the split-precision scans exchange: hi = RNE bf16 of h, lo = RNE
+ *                               bf16 of h - hi, every block 0 .. T.  0 where the finishing family leaves no planes (the launch
+ *                               per step wavefront reads the f32 rows; bf16 precision has none)
+ *   off_P1   f32  [TB][4W]      gate inputs x . K_l + b_l of layer p1_layer for all steps, gates i, f, c, o [4][W] per row: the
+ *                               one buffer every layer's input side passes through, so it holds the LAST layer that used it
+ *                               (0: the rows gathered from the look-up tables; the top layer where the layers run one after the
+ *                               other)
+ * Byte offsets into ws, per layer.  family = the KL_FWD_* family that finished the window; passed_mask = the families that issued
+ * launches for it and then handed it on (their arrays are overwritten by the finishing family).  ring_mask / thin_mask bit l:
+ * layer l's gate inputs came from the three products of the split (hi.hi + b, lo.hi, hi.lo) on the ring GEMM over the planes
+ * of the layer below / from the thin split-precision GEMM over its f32 rows (KL_FWD_SPLIT_LAYERS only; in every other family
+ * the scan contracts the inputs itself).  handoff = how the scan's workgroups hand rows over.  precision = KL_PREC_*.
+ * Each value is noted by the family itself while the window's launch sequence is built, so it also holds for a window that was
+ * a replayed graph; nothing is launched or allocated.  KL_ERR_STATE if no such window has run on ws. */
+#define KL_FWD_SPLIT_PAIRS 1     /* width 1024, up to 32 streams: two layers per launch, eight units per workgroup */
+#define KL_FWD_SPLIT_LAYERS 2    /* width 1024, up to 256 streams: one layer per launch, its input side from one product over all steps */
+#define KL_FWD_SPLIT_FUSED 4     /* all layers and steps in one persistent launch */
+#define KL_FWD_WAVEFRONT 8       /* a launch per step, layers as a wavefront */
+#define KL_FWD_HANDOFF_NONE 0
+#define KL_FWD_HANDOFF_SENTINELS 1   /* the published rows themselves, armed with a pattern no value takes */
+#define KL_FWD_HANDOFF_COUNTERS 2
+typedef struct kl_forward_view {
+  int32_t depth, width, B, T;
+  int32_t family, passed_mask, ring_mask, thin_mask, handoff, c_every_step, precision, p1_layer, reserved[4];
+  uint64_t off_H[16], off_C[16], off_Xhi[16], off_Xlo[16];
+  uint64_t off_P1;
+} kl_forward_view;
+int kl_test_forward_view(const kl_handle* h, int B, int T, const void* ws, kl_forward_view* out);
+
 /* Test hook: where kl_bind carved every operand array the kernels read instead of the parameter vector, and which of them
  * match the bound parameters now.  Byte offsets into the bound derived buffer; per-layer arrays have 16 entries, per-context
  * arrays 8.  W = width, V = voc_size, Vp = V padded to the table rows; bf16 unless stated; gate column order i, f, c, o.

@@ -202,6 +202,25 @@ struct kl_handle {
     view_notes.push_back(ViewNote{B, T, ws, 0, 0, 0, 0, 0u});
     return &view_notes.back();
   }
+  // what kl_test_forward_view reports: noted by the scan families of forward_impl per (B, T, workspace, precision) of an
+  // inference-layout window while they build its launch sequence (as ViewNote: a replayed graph does not run them again)
+  struct ForwardNote {
+    int B, T;
+    const void* ws;
+    int precision;
+    int family = 0, passed_mask = 0, handoff = 0, c_every_step = 0, planes = 0, p1_layer = -1;
+    unsigned ring_mask = 0, thin_mask = 0;
+  };
+  std::vector<ForwardNote> forward_notes;
+  // the note of (B, T, ws) in the handle's current precision; insert: a new one where there is none (the 64 most recent are kept), else null
+  ForwardNote* forward_note(int B, int T, const void* ws, bool insert) {
+    for (auto& n : forward_notes)
+      if (n.B == B && n.T == T && n.ws == ws && n.precision == precision) return &n;
+    if (!insert) return nullptr;
+    if (forward_notes.size() >= 64) forward_notes.erase(forward_notes.begin());
+    forward_notes.push_back(ForwardNote{B, T, ws, precision});
+    return &forward_notes.back();
+  }
   bool segsum = true;           // KL_SEGSUM = 0: layer 0's table gradients as one-hot products (default: sorted segment sums, segsum.hip -- read in
                                 // kl_create, it decides the window workspace's size)
   bool fuse_wg = true;          // KL_FUSE_WG = 0: one launch per weight-gradient product (else products over the same dZ share a pass)
@@ -568,7 +587,14 @@ int plan_scan2(const kl_handle* h, int B, int T, bool km_plan, bool need_bwd) {
 struct FwdCall {       // a forward pass over one window as its scan families see it
   kl_handle* h; int B, T; const int *idx, *ctx; float* states; const float* masks; int training, split; WindowWs& w; hipStream_t s;
   int W, L; size_t BW; int n_rb;      // n_rb: row blocks of 16 streams
+  kl_handle::ForwardNote* note;       // inference layout: what kl_test_forward_view will say about this window (training layout: null)
 };
+// a family of the inference layout hands the window on after it has issued launches / has finished it
+static void note_passed(const FwdCall& c, int family) { if (c.note) c.note->passed_mask |= family; }
+static void note_finished(const FwdCall& c, int family, int handoff, int planes, int c_every_step, int p1_layer) {
+  if (!c.note) return;
+  c.note->family = family; c.note->handoff = handoff; c.note->planes = planes; c.note->c_every_step = c_every_step; c.note->p1_layer = p1_layer;
+}
 // a scan family's "not mine" (no public return code -- those are 0 .. 5, keraslm_hip.h)
 constexpr int FWD_PASS = -1;
 static_assert(FWD_PASS < KL_OK, "FWD_PASS must not be a public return code");
@@ -863,7 +889,10 @@ static int fwd_split_pairs(const FwdCall& c) {
   if (!(split_w1024(c, 2) && c.h->split8)) return FWD_PASS;
   for (int l0 = 0; l0 < c.L; l0 += 2) {
     const int nl = c.L - l0 < 2 ? c.L - l0 : 2;
-    if (l0 + nl > KL_SCAN_MAXL) return FWD_PASS;
+    if (l0 + nl > KL_SCAN_MAXL) {
+      if (l0 > 0) note_passed(c, KL_FWD_SPLIT_PAIRS);      // (the pairs below l0 have gone out)
+      return FWD_PASS;
+    }
     KlScanFwdSplit a = scan_args<KlScanFwdSplit>(c, nl);
     a.l0 = l0; a.units8 = 1;
     for (int l = (l0 > 0 ? l0 - 1 : 0); l < l0 + nl; ++l) split_layer_args(c, a, l, l, true);
@@ -873,9 +902,13 @@ static int fwd_split_pairs(const FwdCall& c) {
       KL_TRY(arm_split(c, l));
     }
     const int e = kl_launch_scan_fwd_split(a, c.s);
-    if (e == KL_ERR_SHAPE && l0 == 0) return FWD_PASS;      // (fewer than 256 CUs: layer by layer)
+    if (e == KL_ERR_SHAPE && l0 == 0) {      // (fewer than 256 CUs: layer by layer)
+      note_passed(c, KL_FWD_SPLIT_PAIRS);      // (the planes of the first pair were split and armed)
+      return FWD_PASS;
+    }
     if (e != 0) return e;
   }
+  note_finished(c, KL_FWD_SPLIT_PAIRS, KL_FWD_HANDOFF_SENTINELS, 1, 0, 0);      // (P1: gather_layer0's rows)
   return 0;
 }
 
@@ -896,12 +929,14 @@ static int fwd_split_layers(const FwdCall& c) {
       KL_TRY(kl_launch_gemm_tn(xh, d.KT_hi[l], w.P1, bias, B * T, 4 * W, W, W, W, 4 * W, 0, 1, 1.f, s));
       KL_TRY(kl_launch_gemm_tn(xl, d.KT_hi[l], w.P1, nullptr, B * T, 4 * W, W, W, W, 4 * W, 2, 1, 1.f, s));
       KL_TRY(kl_launch_gemm_tn(xh, d.KT_lo[l], w.P1, nullptr, B * T, 4 * W, W, W, W, 4 * W, 2, 1, 1.f, s));
+      if (c.note) c.note->ring_mask |= 1u << l;
     } else if (l > 0) {
       KlOperand op;
       memset(&op, 0, sizeof(op));
       op.A = h_rows(c, l - 1, 1); op.lda = W; op.a_is_f32 = 1;
       op.WT_hi = d.KT_hi[l]; op.WT_lo = d.KT_lo[l]; op.ldw = W; op.K = W;
       KL_TRY(kl_launch_thin_gemm(&op, B * T, 4 * W, w.P1, 4 * W, bias, KL_PREC_SPLIT, s));
+      if (c.note) c.note->thin_mask |= 1u << l;
     }
     KlScanFwdSplit a = scan_args<KlScanFwdSplit>(c, 1);
     split_layer_args(c, a, l, 0, false);
@@ -910,6 +945,7 @@ static int fwd_split_layers(const FwdCall& c) {
     KL_TRY(arm_split(c, l));
     KL_TRY(kl_launch_scan_fwd_split(a, s));
   }
+  note_finished(c, KL_FWD_SPLIT_LAYERS, KL_FWD_HANDOFF_SENTINELS, 1, 0, c.L - 1);      // (P1: the top layer's gate inputs)
   return 0;
 }
 
@@ -926,6 +962,8 @@ static int fwd_split_fused(const FwdCall& c) {
   else
     KL_TRY(kl_zero_coherent_async(c.w.scan_cnt, (size_t)L * c.n_rb * c.T, c.s));      // (all layers' counters)
   const int e = kl_launch_scan_fwd_split(a, c.s);
+  if (e == KL_ERR_SHAPE) note_passed(c, KL_FWD_SPLIT_FUSED);      // (the planes were split and armed, or the counters zeroed)
+  if (e == 0) note_finished(c, KL_FWD_SPLIT_FUSED, a.sentinel ? KL_FWD_HANDOFF_SENTINELS : KL_FWD_HANDOFF_COUNTERS, 1, 0, 0);
   return e == KL_ERR_SHAPE ? FWD_PASS : e;
 }
 
@@ -995,6 +1033,7 @@ static int fwd_wavefront(const FwdCall& c) {
       if (steady && dgl % 8 == 7) h->trace_end(0, c.s);
     }
   }
+  note_finished(c, KL_FWD_WAVEFRONT, KL_FWD_HANDOFF_NONE, 0, 1, 0);      // (every step writes its C block; no planes; P1: gather_layer0's rows)
   return 0;
 }
 
@@ -1003,7 +1042,10 @@ static int fwd_wavefront(const FwdCall& c) {
 int forward_impl(kl_handle* h, int B, int T, const int* idx, const int* ctx, float* states, const float* masks,
                  int training, WindowWs& w, hipStream_t s) {
   const int W = h->cfg.width, L = h->cfg.depth;
-  const FwdCall c = {h, B, T, idx, ctx, states, masks, training, training ? 1 : h->precision, w, s, W, L, (size_t)B * W, (B + 15) / 16};
+  // (the inference layout's P1 is the first array carved: its address is the workspace's)
+  kl_handle::ForwardNote* note = training ? nullptr : h->forward_note(B, T, w.P1, true);
+  if (note) *note = kl_handle::ForwardNote{B, T, w.P1, h->precision};
+  const FwdCall c = {h, B, T, idx, ctx, states, masks, training, training ? 1 : h->precision, w, s, W, L, (size_t)B * W, (B + 15) / 16, note};
   for (int l = 0; l < L; ++l)
     KL_TRY(kl_launch_state_to_rows(states, B, W, L, l, training ? (bf16_t*)w.H[l] : nullptr, training ? nullptr : (float*)w.H[l], w.C[l], s));
   int e = fwd_wide(c);
@@ -2760,6 +2802,27 @@ extern "C" int kl_test_window_view(const kl_handle* h, int B, int T, const void*
     out->off_Hd[l] = ((note->hd_mask >> l) & 1u) ? off(w.Hd[l]) : 0;
   }
   out->off_dlogits = off(w.dlogits); out->ld_dlogits = (uint64_t)h->Vp;
+  return 0;
+}
+
+extern "C" int kl_test_forward_view(const kl_handle* h, int B, int T, const void* ws, kl_forward_view* out) {
+  if (!h || !ws || !out || B < 1 || T < 1) return KL_ERR_ARG;
+  const kl_handle::ForwardNote* note = const_cast<kl_handle*>(h)->forward_note(B, T, ws, false);
+  if (!note || !note->family) return KL_ERR_STATE;      // (no family finished: the window's launch sequence failed half built)
+  WindowWs w;
+  carve_window(h, const_cast<void*>(ws), B, T, 0, &w);
+  memset(out, 0, sizeof(*out));
+  out->depth = h->cfg.depth; out->width = h->cfg.width; out->B = B; out->T = T;
+  out->family = note->family; out->passed_mask = note->passed_mask;
+  out->ring_mask = (int32_t)note->ring_mask; out->thin_mask = (int32_t)note->thin_mask;
+  out->handoff = note->handoff; out->c_every_step = note->c_every_step; out->precision = note->precision; out->p1_layer = note->p1_layer;
+  const unsigned char* base = reinterpret_cast<const unsigned char*>(ws);
+  auto off = [&](const void* p) { return (uint64_t)(reinterpret_cast<const unsigned char*>(p) - base); };
+  for (int l = 0; l < h->cfg.depth; ++l) {      // (config_ok: at most 16 layers)
+    out->off_H[l] = off(w.H[l]); out->off_C[l] = off(w.C[l]);
+    out->off_Xhi[l] = note->planes ? off(w.Xhi[l]) : 0; out->off_Xlo[l] = note->planes ? off(w.Xlo[l]) : 0;
+  }
+  out->off_P1 = off(w.P1);
   return 0;
 }
 

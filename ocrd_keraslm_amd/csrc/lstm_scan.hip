@@ -262,6 +262,12 @@ __global__ __launch_bounds__(256, 2) void lstm_scan_fwd_kernel(const KlScanFwd a
 //  helpers -- the MFMA triple, the gate-input gather, the epilogue were tried --, changed the compiled schedule of the step
 //  loop every time: registers, the waits around the sentinel check, in two instantiations the occupancy; rating windows came
 //  out 1-3 % slower.  profiles/split_scan_refactor_ab.json has the measurements.)
+// a - b of the two f32 values as they are: never fused with the multiplication that produced one of them
+__device__ __forceinline__ float sub_uncontracted(float a, float b) {
+#pragma clang fp contract(off)
+  return a - b;
+}
+
 template <int KSTEPS, int MAXRB>
 __global__ __launch_bounds__(256, 1) void lstm_scan_fwd_split_kernel(const KlScanFwdSplit a) {
   // K is split over KW waves (four; fewer for widths below 128, where the other waves contribute zero tiles)
@@ -416,7 +422,10 @@ __global__ __launch_bounds__(256, 1) void lstm_scan_fwd_split_kernel(const KlSca
       const float h = go * fast_tanh(c);
       const bool row_ok = (r0 + er) < B;
       const unsigned hh = f2bf(h);
-      const unsigned hl = f2bf(h - bf2f((bf16_t)hh));
+      // (the remainder of the ROUNDED h, as Hf keeps it and as the sentinel kernels split it: left to itself the compiler contracts
+      //  the product go * tanh(c) into this subtraction -- one FMA on the unrounded product -- and the lo plane is then the split
+      //  of a number nobody stored, another bf16 in one element of a hundred)
+      const unsigned hl = f2bf(sub_uncontracted(h, bf2f((bf16_t)hh)));
       const unsigned hh_n = __shfl_xor(hh, 1), hl_n = __shfl_xor(hl, 1);
       const long orow = (long)t * B + r0 + er;
       if (row_ok && alive && (eu & 1) == 0) {

@@ -111,6 +111,7 @@ class HipLM:
         self._step_ws_bytes = {}
         self.last_only = False
         self._last_window = None    # (streams run, T, first real stream, real streams, groups) of the last train_window
+        self._last_forward = None   # (streams, T, workspace) of the last inference-layout window (forward_window, rate_window[_alts])
         self._rng = np.random.default_rng(0)
 
     def __del__(self):
@@ -373,6 +374,8 @@ class HipLM:
                 hipabi.check(self.lib.kl_forward_window(self.handle, B, T, _ptr(idx_d), _ptr(ctx_d), _ptr(tgt_d),
                                                         _ptr(self.states), _ptr(probs), _ptr(self.loss_acc), _ptr(ws),
                                                         ws.numel(), self._stream()), "kl_forward_window")
+                if not training_ws:
+                    self._last_forward = (B, T, ws)
             else:
                 # (more streams than one launch sequence addresses: groups of streams one after the other, as in train_window;
                 # the means over the batch are the size-weighted sums of the groups' means)
@@ -394,6 +397,8 @@ class HipLM:
                     finally:
                         if Bp != n:
                             hipabi.check(self.lib.kl_set_loss_rows(self.handle, 0), "kl_set_loss_rows")
+                    if not training_ws:
+                        self._last_forward = (Bp, T, ws)
                     self._unpad_states(b0, b1, st)
                     self.loss_acc[:2] += (n / B) * self._part_loss[:2]
                     self.loss_acc[3] = torch.maximum(self.loss_acc[3], self._part_loss[3])
@@ -452,6 +457,8 @@ class HipLM:
                 hipabi.check(fn(self.handle, Bp, T, *([k] if alts else []), _ptr(x), _ptr(c), _ptr(y), _ptr(st),
                                 *([_ptr(t) for t in out] or [_ptr(None)]), _ptr(bits), _ptr(self._rate_status), _ptr(ws), ws.numel(),
                                 self._stream()), name)
+                if not bulk:
+                    self._last_forward = (Bp, T, ws)
                 if Bp != n:
                     self._unpad_states(b0, b1, st)
                     self.rate_bits[b0:b1] += bits[:n]
@@ -1092,6 +1099,19 @@ class HipLM:
         self.torch.cuda.synchronize(self.device)
         hipabi.check(self.lib.kl_test_window_view(self.handle, B, T, _ptr(self._ws), C.byref(view)), "kl_test_window_view")
         return view, self._ws, dict(B=B, T=T, first=first, n=n, groups=groups)
+
+    def forward_view(self, B=None, T=None, ws=None):
+        """Test hook (kl_test_forward_view): which scan family ran the last inference-layout window -- `forward_window` in split
+        precision, `rate_window`, `rate_window_alts`; of a batch in several groups, the last group -- and where it left H, C, the
+        (hi, lo) planes and P1.  Returns (view, workspace): the kl_forward_view and the uint8 tensor its byte offsets point into.
+        B, T, ws: a window run through the library on a workspace of the caller's instead."""
+        if ws is None:
+            if self._last_forward is None:
+                raise hipabi.KlError("forward_view: no inference window has run")
+            B, T, ws = self._last_forward
+        view = hipabi.KlForwardView()
+        hipabi.check(self.lib.kl_test_forward_view(self.handle, int(B), int(T), _ptr(ws), C.byref(view)), "kl_test_forward_view")
+        return view, ws
 
     def derived_view(self):
         """Test hook (kl_test_derived_view): where every operand array derived from the parameters lies and which groups of

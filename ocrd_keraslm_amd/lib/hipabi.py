@@ -27,6 +27,9 @@ KL_SAMPLE_MAX_TOPK = 64
 KL_WG_KMAJOR, KL_WG_SCAN_T, KL_WG_TRANSPOSE, KL_WG_SEGSUM, KL_WG_PAIR_CTX = 1, 2, 4, 8, 16
 # kl_window_view.out_route
 KL_OUT_LOGITS_WS, KL_OUT_LOGITS_W128, KL_OUT_DH_WS, KL_OUT_DE_KMAJOR = 1, 2, 4, 8
+# kl_forward_view.family / .passed_mask; .handoff
+KL_FWD_SPLIT_PAIRS, KL_FWD_SPLIT_LAYERS, KL_FWD_SPLIT_FUSED, KL_FWD_WAVEFRONT = 1, 2, 4, 8
+KL_FWD_HANDOFF_NONE, KL_FWD_HANDOFF_SENTINELS, KL_FWD_HANDOFF_COUNTERS = 0, 1, 2
 # kl_derived_view.current; the first three bits of the mask of kl_test_prepare_lazy
 KL_DV_EAGER, KL_DV_LO, KL_DV_INTERLEAVED, KL_DV_INC, KL_DV_BIG, KL_DV_COMB = 1, 2, 4, 8, 16, 32
 KL_LAZY_INC, KL_LAZY_BIG, KL_LAZY_COMB = 1, 2, 4
@@ -50,6 +53,13 @@ class KlWindowView(C.Structure):
                 ("off_H", C.c_uint64 * 16), ("off_C", C.c_uint64 * 16), ("off_Cb", C.c_uint64 * 16),
                 ("off_G", C.c_uint64 * 16), ("off_dZ", C.c_uint64 * 16), ("off_Hd", C.c_uint64 * 16),
                 ("off_dlogits", C.c_uint64), ("ld_dlogits", C.c_uint64)]
+
+
+class KlForwardView(C.Structure):
+    """kl_forward_view of include/keraslm_hip.h (kl_test_forward_view)"""
+    _fields_ = ([(n, C.c_int32) for n in ("depth", "width", "B", "T", "family", "passed_mask", "ring_mask", "thin_mask", "handoff",
+                                          "c_every_step", "precision", "p1_layer")] + [("reserved", C.c_int32 * 4)] +
+                [("off_" + n, C.c_uint64 * 16) for n in ("H", "C", "Xhi", "Xlo")] + [("off_P1", C.c_uint64)])
 
 
 class KlDerivedView(C.Structure):
@@ -217,6 +227,7 @@ SIGNATURES = {
     "kl_test_rate_topk": (C.c_int, [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kl_test_window_view": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(KlWindowView)]),
+    "kl_test_forward_view": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(KlForwardView)]),
     "kl_test_derived_view": (C.c_int, [C.c_void_p, C.POINTER(KlDerivedView)]),
     "kl_test_prepare_lazy": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "kl_test_step_route": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(KlStepRoute)]),

@@ -48,4 +48,11 @@ def test_host_only_entry_points():
     assert lib.kl_window_workspace_bytes(h, 64, 256, 1) > lib.kl_window_workspace_bytes(h, 64, 256, 0) > 0
     assert lib.kl_prepare(h, 1, None) == 3                       # KL_ERR_STATE: nothing bound
     assert lib.kl_error_string(3).decode().startswith("call order")
+    # the inference-window view: no window has run on this handle (the workspace address is only compared, never read)
+    view = hipabi.KlForwardView()
+    spot = C.create_string_buffer(256)
+    assert lib.kl_test_forward_view(h, 4, 8, C.cast(spot, C.c_void_p), C.byref(view)) == 3      # KL_ERR_STATE
+    assert lib.kl_test_forward_view(h, 4, 8, None, C.byref(view)) == 5                           # KL_ERR_ARG
+    assert lib.kl_test_forward_view(h, 0, 8, C.cast(spot, C.c_void_p), C.byref(view)) == 5
+    assert C.sizeof(hipabi.KlForwardView) == 16 * 4 + 4 * 16 * 8 + 8      # kl_forward_view of the header
     lib.kl_destroy(h)

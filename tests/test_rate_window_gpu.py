@@ -104,7 +104,10 @@ class Abi(object):
 @pytest.mark.parametrize("depth,width,n_ctx,voc,B,T,precision", [
     (1, 64, 0, 11, 1, 1, 3), (2, 128, 1, 96, 1, 32, 3), (2, 512, 1, 256, 64, 256, 3), (3, 256, 2, 300, 5, 7, 3),
     (2, 1024, 1, 96, 5, 7, 3), (2, 128, 2, 11, 5, 7, 1), (2, 512, 1, 256, 1, 32, 1), (2, 128, 0, 300, 64, 256, 1),
-    (2, 512, 1, 230, 64, 32, 3)])
+    (2, 512, 1, 230, 64, 32, 3),
+    # width 1024: 2048 rows -- layer 1's gate inputs from the three ring products over the planes --, and five layers -- the
+    # two-layer launches hand the window on after layers 0..3 (the routes are asserted in tests/test_forward_view_gpu.py)
+    (2, 1024, 1, 40, 64, 32, 3), (5, 1024, 1, 30, 20, 3, 3)])
 def test_rate_window_is_forward_window_picked(depth, width, n_ctx, voc, B, T, precision):
     """tprob against kl_forward_window's probabilities gathered at tgt: <= 1e-6 (the same operations in the same order
     should make it 0; one f32 ulp below 1 is 1.2e-7, so 1e-6 is eight ulps of slack for a different contraction by the
