@@ -101,6 +101,7 @@ class HipLM:
         self._fan_states = {}                # rows -> the state buffer `fan_states` fills for that many streams
         self.pad_streams = True              # pad a group of streams up to the next fast count (HipLM._padded_streams)
         self.plan_override = None            # width 512: a stream plan to use instead of _plan_512's (tests)
+        self.group_hook = None               # tests: called per stream group of a grouped window (see window_view)
         self._step_ws = None
         self._step_host_ws = None
         self._walk_ws = None
@@ -382,7 +383,7 @@ class HipLM:
                 if self._part_loss is None:
                     self._part_loss = torch.zeros_like(self.loss_acc)
                 ws = self._workspace(max(padded), T, training_ws)
-                for (b0, b1), Bp in zip(parts, padded):
+                for i, ((b0, b1), Bp) in enumerate(zip(parts, padded)):
                     n = b1 - b0
                     self._part_loss.zero_()
                     # (-2, not the -1 of a padded tail: a dummy stream is no hit for the accuracy either)
@@ -400,6 +401,8 @@ class HipLM:
                     if not training_ws:
                         self._last_forward = (Bp, T, ws)
                     self._unpad_states(b0, b1, st)
+                    if self.group_hook is not None:
+                        self.group_hook(i, b0, b1, Bp)
                     self.loss_acc[:2] += (n / B) * self._part_loss[:2]
                     self.loss_acc[3] = torch.maximum(self.loss_acc[3], self._part_loss[3])
             if want_probs and float(self.loss_acc[3].item()) != 0.0:
@@ -1065,7 +1068,9 @@ class HipLM:
                     if m is not None:
                         # (the dummy streams' keep-masks repeat real streams': the register-tile backward scan keeps a mask as
                         #  one bit per cell plus ONE scale per thread and refuses a mask with a second non-zero value)
-                        m = torch.cat([m, m[:, :Bp - n]], dim=1)
+                        # (_padded_streams adds at most as many dummy streams as there are real ones; a plan handed in may
+                        #  add more, and a mask array short of Bp rows would be read beyond its end)
+                        m = torch.cat([m, m[:, :Bp - n]], dim=1) if Bp - n <= n else m.repeat(1, -(-Bp // n), 1)[:, :Bp]
                     hipabi.check(self.lib.kl_set_loss_rows(self.handle, n), "kl_set_loss_rows")
                 if m is not None:
                     m = m.contiguous()
@@ -1078,6 +1083,8 @@ class HipLM:
                         hipabi.check(self.lib.kl_set_loss_rows(self.handle, 0), "kl_set_loss_rows")
                 self._unpad_states(b0, b1, st)
                 self._last_window = (Bp, T, b0, n, len(parts))
+                if self.group_hook is not None:
+                    self.group_hook(i, b0, b1, Bp)
                 if i == 0:
                     torch.mul(self._part_grads, wgt, out=self.grads)
                     self.loss_acc[2] += self._part_loss[2]
@@ -1091,7 +1098,14 @@ class HipLM:
         workspace, info): the kl_window_view, the uint8 workspace tensor its byte offsets point into, and info = dict(B -- streams
         the kernels ran, dummy streams included --, T, first, n -- the real streams [first, first + n) of the batch that occupy
         rows [0, n) --, groups).  With several stream groups (groups > 1) the workspace holds the LAST group only.  Decoding:
-        tests/window_ref.py."""
+        tests/window_ref.py.
+
+        Every group of a grouped or padded window is reached through `group_hook` (default None: nothing is called, nothing
+        else changes): when set, `train_window` and `forward_window` call group_hook(i, b0, b1, Bp) in their group loops --
+        group i = streams [b0, b1) of the batch, run as Bp streams -- after the group's launch and `_unpad_states` and before
+        its results are folded into `grads` / `loss_acc`.  There `_part_loss` (and, in `train_window`, `_part_grads`) are that
+        group's own values, and in `train_window` this view describes group i.  The hook may synchronise; the engine does not
+        on its behalf.  A batch that runs in one piece without padding calls no hook."""
         if self._last_window is None:
             raise hipabi.KlError("window_view: no training window has run")
         B, T, first, n, groups = self._last_window
@@ -1210,7 +1224,9 @@ class HipLM:
         launch-per-step kernels --, or (b) it is none of the stream counts the fastest kernels of its width take and large
         enough (FAST_STREAMS): then the largest such counts are peeled off as long as 512 streams or more remain
         (width 512: 2560 -> 2048 + 512, 3584 -> 3072 + 512, 4096 -> 3072 + 1024) and only the rest runs on the slower path."""
-        limit = self.max_streams_per_launch or (0xfffffff0 // (T * 4 * self.pwidth * 2))
+        limit = 0xfffffff0 // (T * 4 * self.pwidth * 2)
+        if self.max_streams_per_launch:      # (never more than the offsets reach, whatever a caller asks for)
+            limit = min(limit, self.max_streams_per_launch)
         if self.pwidth == 512 and T >= 3 and not self.max_streams_per_launch:
             parts, b0 = [], 0
             for n, _run in self._plan_512(B, limit):

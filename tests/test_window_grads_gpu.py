@@ -5,7 +5,7 @@ per ROUTE of the stage, each at the smallest shape that takes the route, each as
 wg_route / wg_pair_mask / wg_db_scan_mask.  Inputs as in tests/test_window_intermediates_gpu.py: dropout masks, a padded
 tail, an all-dummy 16-row block and a half-dummy one.  Every product is checked in full (the f64 references take 0.1 - 0.9 s
 per case).  The gemm-level switches (KL_GEMM_WIDE, KL_GEMM_LONG, ...) are read once per process and not toggled here:
-tests/test_gemm_wide_gpu.py covers them.  Stream groups are not covered (the workspace holds the last group only).
+tests/test_gemm_wide_gpu.py covers them.  Stream groups (every group's own gradients): tests/test_train_groups_gpu.py.
 
 Layer 0's character rows (E_bf16^T . bf16(S)) are asserted by a test of their own, test_window_grads_characters, from the
 same run: their allowance for sums near a bf16 rounding boundary is half of what a sum that really rounds the other way

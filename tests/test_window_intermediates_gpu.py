@@ -6,7 +6,7 @@ without tolerance (no sentinel left, dummy streams' dZ exactly zero, blocks 0 an
 
 Each case forces one kernel family with the switches of tests/test_gpu_kernels.py and asserts both kernel names; each runs
 with dropout masks, a padded tail, an all-dummy 16-row block and a half-dummy one (kl_set_loss_rows), one case in the stateless
-window mode.  Stream groups are not covered (the workspace holds the last group only).
+window mode.  Stream groups and the engine's own dummy streams: tests/test_train_groups_gpu.py, group by group.
 
 Observed on an MI355X (largest ratio kernel tile error / the emulation's largest tile error over the family's cases and
 layers; the bound is 2.00).  The emulation's own largest tile error was 0.0046 .. 0.0070 (bound for it: 0.1), the floor was

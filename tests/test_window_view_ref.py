@@ -250,3 +250,38 @@ def test_floor_share_of_the_gpu_cases(case):
     share = R.floor_share(R.references(case, _weights(case), inp), n_real, B)
     print(case.name, "largest floor share %.4f" % max(share.values()))
     assert max(share.values()) <= R.FLOOR_SHARE_MAX, share
+
+
+def _group_cases():
+    from tests import train_groups
+    return train_groups.CASES
+
+
+@pytest.mark.parametrize("gc", _group_cases(), ids=lambda g: g.name)
+def test_floor_and_near_tie_share_of_the_group_cases(gc):
+    """the inputs of tests/test_train_groups_gpu.py, from the oracle alone: the plan cuts and pads each batch as the case says;
+    in the SECOND window (carried states: here the f64 oracle's) of every checked group at most 5 % of the non-dummy tiles are
+    measured against the floor, and at most 5 % of the real positions have their two largest probabilities within 1e-2 of
+    each other (the allowance of the accuracy check); at most 15 % of the targets had to be moved away from the loss clip"""
+    from ocrd_keraslm_amd.lib.engine import HipLM, physical_width
+    from tests import train_groups as G
+    c = gc.case
+    lm = HipLM.__new__(HipLM)
+    lm.pwidth, lm.pad_streams, lm.plan_override, lm.max_streams_per_launch = physical_width(c.width), True, gc.plan_override, gc.max_streams
+    parts = lm._stream_groups(c.B, c.T)
+    assert [(b0, b1, lm._padded_streams(b1 - b0, c.T)) for b0, b1 in parts] == [tuple(g) for g in gc.groups]
+    w = G.weights(gc)
+    first = G.batch_inputs(gc, seed=21)
+    inp = G.batch_inputs(gc, seed=22, states=G.carried_states(gc, w, first))
+    groups, replaced = G.settle_batch(gc, w, inp)
+    assert replaced <= 0.15 * c.B * c.T, replaced
+    for i in gc.checked:
+        g, case, ginp, fw = groups[i]
+        n = g.b1 - g.b0
+        assert (ginp["tgt"][n:] == -2).all() and not ginp["states"][n:].any() and np.array_equal(ginp["tgt"][:n], inp["tgt"][g.b0:g.b1])
+        ref = G.group_oracle(case, fw, ginp)
+        share = R.floor_share(ref["ref64"], n, g.Bp)
+        print(gc.name, tuple(g), "largest floor share %.4f, near ties %.4f, CE %.3f, accuracy %.4f, targets moved in the batch %d"
+              % (max(share.values()), ref["near_ties"], ref["ce"], ref["acc"], replaced))
+        assert max(share.values()) <= R.FLOOR_SHARE_MAX, share
+        assert ref["near_ties"] <= G.NEAR_TIE_MAX, ref["near_ties"]
