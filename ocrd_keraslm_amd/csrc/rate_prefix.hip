@@ -2,12 +2,12 @@
 // hypothesis window of kl_edit_windows into a window over the characters in front of the suspect -- one row per SUSPECT -- and a
 // short window per variant that continues from the state the first one left.
 //
-// kl_prefix_windows: one workgroup per suspect s, one launch.  With g = sel_pos[s] inside text i (the upper-bound binary search
-// of variant_windows_kernel, every thread with the same uniform addresses), the row is valid iff g - offsets[i] >= left; it
-// then feeds x[g-left .. g-2] -- all of them inside the text, so inside the corpus -- and predicts nothing.  The ids come in
-// as lane-consecutive dwords and are parked in LDS, the rows leave through emit_row (kl_emit_row.h): 16-byte stores between
-// the first and the last 16-byte boundary of a row.  Every word of the four outputs is written by exactly one thread of one
-// workgroup: no atomics, no workgroup waits for another, nothing depends on scheduling.  No model: no handle.
+// kl_prefix_windows: one workgroup per suspect s, one launch.  With g = sel_pos[s] inside text i (text_of), the row is valid
+// iff g - offsets[i] >= left; it then feeds x[g-left .. g-2] -- all of them inside the text, so inside the corpus, and the
+// only positions read -- and predicts nothing.  The ids come in as lane-consecutive dwords and are parked in LDS, the row
+// leaves through emit_hypothesis (kl_emit_row.h) with every fed id in q and no target behind the last.  Every output word
+// is written by exactly one thread (who writes what: see emit_hypothesis).  No atomics, no workgroup waits for another,
+// nothing depends on scheduling.  No model: no handle.
 //
 // kl_state_fanout: dst[b] = src[parent[b]], a row of zeros where parent[b] names no row of src.  One thread per 16 bytes of
 // dst over a flat index (a row of depth 2 / width 512 is 512 such words, a row of 4 floats is one): a 16-byte load and a
@@ -24,42 +24,15 @@ __global__ void __launch_bounds__(256) prefix_windows_kernel(
     int32_t* __restrict__ idx, int32_t* __restrict__ ctx, int32_t* __restrict__ tgt, int32_t* __restrict__ valid) {
   __shared__ int32_t s_q[KL_VAR_MAX_Q];
   __shared__ int32_t s_ctx[KL_VAR_MAX_CTX];
-  const int s = blockIdx.x;
-  const long long g = sel_pos[s];
-  // a position at or beyond min(n_corpus, offsets[n_texts]) is in no text, or has no id
-  const long long end = offsets[n_texts];
-  const long long n_read = end < n_corpus ? end : n_corpus;
-  bool ok = g >= 0 && g < n_read;
-  int text = 0;
-  if (ok) {
-    // the first j in [0, n_texts] with offsets[j] > g  (g < offsets[n_texts]: j <= n_texts); the text is j - 1
-    int lo = 0, hi = n_texts;
-    while (lo < hi) {
-      const int mid = lo + ((hi - lo) >> 1);
-      if (offsets[mid] > g) hi = mid; else lo = mid + 1;
-    }
-    ok = lo > 0;
-    if (ok) {
-      text = lo - 1;
-      ok = g - offsets[text] >= left;      // the whole of `left` characters stands in front of g: the shared route
-    }
-  }
+  const long long g = sel_pos[blockIdx.x];
+  const CorpusView x(corpus, n_corpus, offsets, n_texts);
+  const int text = (g >= 0 && g < x.n_read) ? text_of(offsets, n_texts, g) : -1;
+  // the whole of `left` characters stands in front of g: the shared route
+  const bool ok = text >= 0 && g - offsets[text] >= left;
   // x[g-left .. g-2] is fed (left - 1 <= T ids); x[g-1] is the first id of the rows that continue
   const int fed = ok ? left - 1 : 0;
-  for (int t = threadIdx.x; t < fed; t += blockDim.x) {
-    const long long p = g - left + t;
-    s_q[t] = (p >= 0 && p < n_read) ? corpus[p] : 0;
-  }
-  if ((int)threadIdx.x < n_ctx) s_ctx[threadIdx.x] = ok ? text_ctx[(long long)text * n_ctx + threadIdx.x] : 0;
-  __syncthreads();
-  const long long at = (long long)s * T;
-  emit_row(idx + at, T, [&](int t) { return t < fed ? s_q[t] : 0; });
-  emit_row(tgt + at, T, [&](int) { return -1; });
-  if (n_ctx > 0) {
-    const int live = fed * n_ctx;      // the fed positions come first in the row: [t][c]
-    emit_row(ctx + at * n_ctx, T * n_ctx, [&](int r) { return r < live ? s_ctx[r % n_ctx] : 0; });
-  }
-  if (threadIdx.x == 0) valid[s] = ok ? 1 : 0;
+  for (int t = threadIdx.x; t < fed; t += blockDim.x) s_q[t] = x.read(g - left + t);
+  emit_hypothesis(ok, text, fed, fed, s_q, s_ctx, text_ctx, n_ctx, T, idx, ctx, tgt, valid);
 }
 
 // word i of dst, 16 bytes each: row i / q, words i % q of it
@@ -82,21 +55,13 @@ extern "C" int kl_prefix_windows(const int32_t* corpus, size_t n_corpus, const i
                                  int32_t* ctx, int32_t* tgt, int32_t* valid, void* stream) {
   if (!corpus || !offsets || !sel_pos || !idx || !tgt || !valid) return KL_ERR_ARG;
   if (S < 1 || (long long)S > KL_VAR_MAX_ROWS || n_texts < 1) return KL_ERR_ARG;
-  // (T <= KL_VAR_MAX_T: the left - 1 <= T fed ids fit the staging array)
-  if (left < 2 || T > KL_VAR_MAX_T || T < left - 1) return KL_ERR_ARG;
-  if (n_ctx < 0 || n_ctx > KL_VAR_MAX_CTX || (n_ctx > 0 && (!text_ctx || !ctx))) return KL_ERR_ARG;
-  if (n_corpus > (size_t)1 << 40) return KL_ERR_ARG;
-  const void* words[] = {corpus, text_ctx, idx, ctx, tgt, valid};
-  for (const void* p : words)
-    if (reinterpret_cast<uintptr_t>(p) & 3) return KL_ERR_ARG;
-  if ((reinterpret_cast<uintptr_t>(offsets) & 7) || (reinterpret_cast<uintptr_t>(sel_pos) & 7)) return KL_ERR_ARG;
-  // a thread owns four positions: as many waves as the longest row (the contexts') needs, at most four
-  const int longest = T * (n_ctx > 1 ? n_ctx : 1);
-  int threads = ((longest + 3) / 4 + 63) / 64 * 64;
-  if (threads > 256) threads = 256;
-  hipLaunchKernelGGL(prefix_windows_kernel, dim3((unsigned)S), dim3(threads), 0, static_cast<hipStream_t>(stream), corpus,
-                     (long long)n_corpus, reinterpret_cast<const long long*>(offsets), n_texts, text_ctx, n_ctx,
-                     reinterpret_cast<const long long*>(sel_pos), left, T, idx, ctx, tgt, valid);
+  // (with T <= KL_VAR_MAX_T: the left - 1 <= T fed ids fit the staging array)
+  if (left < 2 || T < left - 1) return KL_ERR_ARG;
+  if (!hypothesis_args_ok(n_ctx, text_ctx, ctx, n_corpus, T, {corpus, text_ctx, idx, ctx, tgt, valid}, {offsets, sel_pos}))
+    return KL_ERR_ARG;
+  hipLaunchKernelGGL(prefix_windows_kernel, dim3((unsigned)S), dim3(hypothesis_threads(T, n_ctx)), 0,
+                     static_cast<hipStream_t>(stream), corpus, (long long)n_corpus, reinterpret_cast<const long long*>(offsets),
+                     n_texts, text_ctx, n_ctx, reinterpret_cast<const long long*>(sel_pos), left, T, idx, ctx, tgt, valid);
   return hipGetLastError() == hipSuccess ? KL_OK : KL_ERR_LAUNCH;
 }
 

@@ -7,16 +7,16 @@
 //
 // One workgroup per row, one launch.  The row's span is the last s with span_first[s] + s <= b (an upper-bound binary search
 // every thread walks with the same uniform addresses, log2(S) steps; a span without candidates has one row and is found like
-// any other).  With L = min(left, g - offsets[i]) and A = min(ahead, offsets[i+1] - g - D) the hypothesis q is L characters of
-// left context, the row's string r (the written characters, or the candidate's ids) and the A characters behind the span; the
-// row feeds q[0 .. len-2] and targets q[L .. len-1] (see keraslm_hip.h for the rule per word).  Whether a candidate holds a
-// negative id, and whether it differs from what is written, is decided by the first m <= 64 threads and a workgroup-wide OR.
-// q (at most left + M + ahead <= T + 1 ids) comes in as lane-consecutive dwords and is parked in LDS; every thread then owns
-// four consecutive output positions and stores them as one 16-byte word (emit_row of kl_emit_row.h).  An invalid row leaves as
-// a dummy stream (idx 0, ctx 0, tgt -1).  Every word of the four outputs is written by exactly one thread of one workgroup: no
-// atomics, no workgroup waits for another, nothing depends on scheduling.  Corpus addresses are 64-bit; a position outside
-// [0, min(n_corpus, offsets[n_texts])) reads as 0 without touching memory; a candidate whose pool range is not inside the pool,
-// and a row whose candidate index is not in [0, C), is invalid and reads nothing.  No model: no handle.
+// any other; the span names its text, so there is no search for it).  With L = min(left, g - offsets[i]) and
+// A = min(ahead, offsets[i+1] - g - D) the hypothesis q is L characters of left context, the row's string r (the written
+// characters, or the candidate's ids) and the A characters behind the span; the row feeds q[0 .. len-2] and targets
+// q[L .. len-1] (see keraslm_hip.h for the rule per word).  Whether a candidate holds a negative id, and whether it differs
+// from what is written, is decided by the first m <= 64 threads and a workgroup-wide OR.  q (at most left + M + ahead <= T + 1
+// ids) comes in as lane-consecutive dwords and is parked in LDS; the row leaves through emit_hypothesis (kl_emit_row.h, where
+// the corpus view and the cut of L and A live too), an invalid one as a dummy stream.  Only the positions g - L .. g + D + A
+// of the corpus are read, through the view; a candidate whose pool range is not inside the pool, and a row whose candidate
+// index is not in [0, C), is invalid and reads nothing.  No atomics, no workgroup waits for another, nothing depends on
+// scheduling.  No model: no handle.
 //
 // kl_span_pick: one wave per span.  Lane l walks candidates l, l + 64, .. in ascending order and keeps the least cost (the
 // first among equal ones); a butterfly over the wave then takes the minimum under the total order (cost, index) -- the result
@@ -49,21 +49,17 @@ __global__ void __launch_bounds__(256) span_windows_kernel(
   const int s = ok ? lo - 1 : 0;
   const long long v = b - (span_first[s] + s);      // 0: the text as written, else candidate v - 1 of the span
   const bool written = v == 0;
-  const long long end = offsets[n_texts];
-  const long long n_read = end < n_corpus ? end : n_corpus;
-  auto read = [&](long long p) -> int32_t { return (p >= 0 && p < n_read) ? corpus[p] : 0; };
+  const CorpusView x(corpus, n_corpus, offsets, n_texts);
   const int text = span_text[s], D = span_len[s];
   const long long g = span_start[s];
   int L = 0, A = 0;
   ok = ok && text >= 0 && text < n_texts && D >= 0 && D <= M;
   if (ok) {
     const long long o0 = offsets[text], o1 = offsets[text + 1];
-    const long long lim = o1 < n_read ? o1 : n_read;
+    const long long lim = o1 < x.n_read ? o1 : x.n_read;
     ok = o0 <= g && g <= lim && (long long)D <= lim - g;
     if (ok) {
-      const long long before = g - o0, after = o1 - g - D;      // (after >= 0: g + D <= lim <= o1)
-      L = before < left ? (int)before : left;
-      A = after < ahead ? (int)after : ahead;
+      cut_contexts(g - o0, o1 - g - D, left, ahead, L, A);      // (after >= 0: g + D <= lim <= o1)
       ok = L >= 1 && D + A >= 1;
     }
   }
@@ -88,7 +84,7 @@ __global__ void __launch_bounds__(256) span_windows_kernel(
     if (ok && (int)threadIdx.x < m) {
       const int32_t id = pool[r0 + threadIdx.x];
       negative = id < 0;
-      differs = (int)threadIdx.x >= D || id != read(g + threadIdx.x);
+      differs = (int)threadIdx.x >= D || id != x.read(g + threadIdx.x);
     }
     negative = __syncthreads_or(negative);
     differs = __syncthreads_or(differs);
@@ -98,22 +94,13 @@ __global__ void __launch_bounds__(256) span_windows_kernel(
   const int len = ok ? L + m + A : 0;
   for (int t = threadIdx.x; t < len; t += blockDim.x) {
     int32_t id;
-    if (t < L) id = read(g - L + t);
-    else if (t < L + m) id = written ? read(g + (t - L)) : pool[r0 + (t - L)];
-    else id = read(g + D + (t - L - m));
+    if (t < L) id = x.read(g - L + t);
+    else if (t < L + m) id = written ? x.read(g + (t - L)) : pool[r0 + (t - L)];
+    else id = x.read(g + D + (t - L - m));
     s_q[t] = id;
   }
-  if ((int)threadIdx.x < n_ctx) s_ctx[threadIdx.x] = ok ? text_ctx[(long long)text * n_ctx + threadIdx.x] : 0;
-  __syncthreads();
-  const int fed = len > 0 ? len - 1 : 0;      // q[0 .. len-2] is fed, q[L .. len-1] is predicted
-  const long long at = (long long)blockIdx.x * T;
-  emit_row(idx + at, T, [&](int t) { return t < fed ? s_q[t] : 0; });
-  emit_row(tgt + at, T, [&](int t) { return (t < fed && t >= L - 1) ? s_q[t + 1] : -1; });
-  if (n_ctx > 0) {
-    const int live = fed * n_ctx;      // the fed positions come first in the row: [t][c]
-    emit_row(ctx + at * n_ctx, T * n_ctx, [&](int r) { return r < live ? s_ctx[r % n_ctx] : 0; });
-  }
-  if (threadIdx.x == 0) valid[blockIdx.x] = ok ? 1 : 0;
+  // q[0 .. len-2] is fed, q[L .. len-1] is predicted
+  emit_hypothesis(ok, text, len > 0 ? len - 1 : 0, L - 1, s_q, s_ctx, text_ctx, n_ctx, T, idx, ctx, tgt, valid);
 }
 
 __global__ void __launch_bounds__(KL_WAVE) span_pick_kernel(
@@ -169,25 +156,17 @@ extern "C" int kl_span_windows(const int32_t* corpus, size_t n_corpus, const int
   if (S < 1 || n_texts < 1 || rows < 1 || (long long)rows > KL_VAR_MAX_ROWS) return KL_ERR_ARG;
   if (C < 0 || C > ((int64_t)1 << 40) || row0 < 0 || row0 + (int64_t)rows > (int64_t)S + C) return KL_ERR_ARG;
   if (left < 1 || ahead < 0 || max_len < 1 || max_len > KL_SPAN_LEN_MAX) return KL_ERR_ARG;
-  // (T <= KL_VAR_MAX_T: q, at most left + max_len + ahead <= T + 1 ids, fits the staging array)
-  if (T > KL_VAR_MAX_T || (long long)T < (long long)left + ahead + max_len - 1) return KL_ERR_ARG;
-  if (n_ctx < 0 || n_ctx > KL_VAR_MAX_CTX || (n_ctx > 0 && (!text_ctx || !ctx))) return KL_ERR_ARG;
-  if (n_corpus > (size_t)1 << 40 || n_pool > (size_t)1 << 40) return KL_ERR_ARG;
-  const void* words[] = {corpus, text_ctx, span_text, span_len, pool, idx, ctx, tgt, valid};
-  for (const void* p : words)
-    if (reinterpret_cast<uintptr_t>(p) & 3) return KL_ERR_ARG;
-  const void* longs[] = {offsets, span_start, span_first, cand_off};
-  for (const void* p : longs)
-    if (reinterpret_cast<uintptr_t>(p) & 7) return KL_ERR_ARG;
-  // a thread owns four positions: as many waves as the longest row (the contexts') needs, at most four
-  const int longest = T * (n_ctx > 1 ? n_ctx : 1);
-  int threads = ((longest + 3) / 4 + 63) / 64 * 64;
-  if (threads > 256) threads = 256;
-  hipLaunchKernelGGL(span_windows_kernel, dim3((unsigned)rows), dim3(threads), 0, static_cast<hipStream_t>(stream), corpus,
-                     (long long)n_corpus, reinterpret_cast<const long long*>(offsets), n_texts, text_ctx, n_ctx, span_text,
-                     reinterpret_cast<const long long*>(span_start), span_len, reinterpret_cast<const long long*>(span_first), S,
-                     pool, (long long)n_pool, reinterpret_cast<const long long*>(cand_off), (long long)C, (long long)row0, left,
-                     ahead, max_len, T, idx, ctx, tgt, valid);
+  // (with T <= KL_VAR_MAX_T: q, at most left + max_len + ahead <= T + 1 ids, fits the staging array)
+  if ((long long)T < (long long)left + ahead + max_len - 1 || n_pool > (size_t)1 << 40) return KL_ERR_ARG;
+  if (!hypothesis_args_ok(n_ctx, text_ctx, ctx, n_corpus, T, {corpus, text_ctx, span_text, span_len, pool, idx, ctx, tgt, valid},
+                          {offsets, span_start, span_first, cand_off}))
+    return KL_ERR_ARG;
+  hipLaunchKernelGGL(span_windows_kernel, dim3((unsigned)rows), dim3(hypothesis_threads(T, n_ctx)), 0,
+                     static_cast<hipStream_t>(stream), corpus, (long long)n_corpus, reinterpret_cast<const long long*>(offsets),
+                     n_texts, text_ctx, n_ctx, span_text, reinterpret_cast<const long long*>(span_start), span_len,
+                     reinterpret_cast<const long long*>(span_first), S, pool, (long long)n_pool,
+                     reinterpret_cast<const long long*>(cand_off), (long long)C, (long long)row0, left, ahead, max_len, T, idx, ctx,
+                     tgt, valid);
   return hipGetLastError() == hipSuccess ? KL_OK : KL_ERR_LAUNCH;
 }
 

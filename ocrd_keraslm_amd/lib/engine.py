@@ -31,6 +31,11 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
+# what the builders of hypothesis rows say of their tensors (the call's name, its own tensors)
+_HYPOTHESIS_TENSORS = ("%s: corpus int32 [n], offsets int64 [n_texts + 1], text_ctx int32 [n_texts, n_ctx], %s, contiguous, "
+                       "on the device")
+
+
 def physical_width(width):
     """The width the kernels run at: the next one the persistent scans serve (else the next multiple of 32).
     The extra hidden units are zero-padding -- all their weights and biases are zero, so their cell and
@@ -776,6 +781,40 @@ class HipLM:
                 "kl_lexicon_neighbours")
         return out
 
+    def _hypothesis_fits(self, source, own):
+        """Whether the tensors of `variant_windows`, `prefix_windows` or `span_windows` are as the call's message says:
+        source (corpus_d int32 [n], offsets_d int64 [n_texts + 1], text_ctx_d int32 [n_texts, n_ctx] or None) and own, the
+        call's further tensors as (tensor, dtype, dims), every one contiguous and on the device.  The sizes of `own` against
+        each other are the call's to compare."""
+        torch = self.torch
+        corpus_d, offsets_d, text_ctx_d = source
+        told = [(corpus_d, torch.int32, 1), (offsets_d, torch.int64, 1)] + own
+        contexts = text_ctx_d is not None and text_ctx_d.shape[-1] > 0
+        if contexts:
+            told.append((text_ctx_d, torch.int32, 2))
+        return (all(t is not None and t.dtype == kind and t.dim() == dims and t.is_contiguous() and t.is_cuda
+                    for t, kind, dims in told)
+                and (not contexts or text_ctx_d.shape[0] == offsets_d.numel() - 1))
+
+    def _hypothesis_rows(self, entry, source, rows, T, middle):
+        """The launch of `variant_windows`, `prefix_windows` and `span_windows`: allocates the four outputs and calls `entry`
+        with the six arguments of source (corpus_d, offsets_d, text_ctx_d), then middle (the entry point's own), then T, the
+        outputs and the stream.  Returns the DEVICE tensors (idx [rows, T], ctx [rows, T, n_ctx], tgt [rows, T], valid [rows])
+        int32."""
+        torch = self.torch
+        corpus_d, offsets_d, text_ctx_d = source
+        n_ctx = 0 if text_ctx_d is None else int(text_ctx_d.shape[-1])
+        with self._launch():
+            idx = torch.empty((rows, T), dtype=torch.int32, device=self.device)
+            tgt = torch.empty((rows, T), dtype=torch.int32, device=self.device)
+            ctx = torch.empty((rows, T, n_ctx), dtype=torch.int32, device=self.device)
+            valid = torch.empty(rows, dtype=torch.int32, device=self.device)
+            hipabi.check(entry(
+                _ptr(corpus_d), corpus_d.numel(), _ptr(offsets_d), offsets_d.numel() - 1, _ptr(text_ctx_d) if n_ctx else None,
+                n_ctx, *middle, T, _ptr(idx), _ptr(ctx) if n_ctx else None, _ptr(tgt), _ptr(valid), self._stream()),
+                entry.__name__)
+        return idx, ctx, tgt, valid
+
     def variant_windows(self, corpus_d, offsets_d, text_ctx_d, sel_pos_d, sel_alt_id_d, left, ahead, deletions, T,
                         insertions=False):
         """kl_edit_windows (kl_variant_windows with insertion rows): the hypothesis rows of S suspects, built on the device in one launch.  corpus_d int32 [n] and
@@ -785,33 +824,16 @@ class HipLM:
         R = K + 1 + deletions + K * insertions, row s * R + v: what `ratebulk.variant_windows_host` states (insertions: every
         alternative once more, in front of the written character; T >= left + ahead + 1 then).  hipabi.KlError for what the
         entry point rejects.  No synchronisation."""
-        torch = self.torch
-        n_ctx = 0 if text_ctx_d is None else int(text_ctx_d.shape[-1])
-        tensors = [corpus_d, offsets_d, sel_pos_d, sel_alt_id_d] + ([text_ctx_d] if n_ctx else [])
-        kinds = [torch.int32, torch.int64, torch.int64, torch.int32] + ([torch.int32] if n_ctx else [])
-        n_texts = offsets_d.numel() - 1
-        S = int(sel_pos_d.numel())
-        if ([t.dtype for t in tensors] != kinds or corpus_d.dim() != 1 or offsets_d.dim() != 1 or sel_pos_d.dim() != 1
-                or sel_alt_id_d.dim() != 2 or sel_alt_id_d.shape[0] != S
-                or (n_ctx and tuple(text_ctx_d.shape) != (n_texts, n_ctx))
-                or not all(t.is_contiguous() and t.is_cuda for t in tensors)):
-            raise hipabi.KlError("variant_windows: corpus int32 [n], offsets int64 [n_texts + 1], text_ctx int32 [n_texts, n_ctx], "
-                                 "sel_pos int64 [S], sel_alt_id int32 [S, K], contiguous, on the device")
-        K = int(sel_alt_id_d.shape[1])
+        source, torch = (corpus_d, offsets_d, text_ctx_d), self.torch
+        if (not self._hypothesis_fits(source, [(sel_pos_d, torch.int64, 1), (sel_alt_id_d, torch.int32, 2)])
+                or sel_alt_id_d.shape[0] != sel_pos_d.numel()):
+            raise hipabi.KlError(_HYPOTHESIS_TENSORS % ("variant_windows", "sel_pos int64 [S], sel_alt_id int32 [S, K]"))
+        S, K = sel_alt_id_d.shape
         left, ahead, deletions, T, insertions = int(left), int(ahead), int(bool(deletions)), int(T), int(insertions)
         if insertions not in (0, 1):
             raise hipabi.KlError("variant_windows: insertions is a flag (got %d)" % insertions)
-        rows = S * (K + 1 + deletions + K * insertions)
-        with self._launch():
-            idx = torch.empty((rows, T), dtype=torch.int32, device=self.device)
-            tgt = torch.empty((rows, T), dtype=torch.int32, device=self.device)
-            ctx = torch.empty((rows, T, n_ctx), dtype=torch.int32, device=self.device)
-            valid = torch.empty(rows, dtype=torch.int32, device=self.device)
-            hipabi.check(self.lib.kl_edit_windows(
-                _ptr(corpus_d), corpus_d.numel(), _ptr(offsets_d), n_texts, _ptr(text_ctx_d) if n_ctx else None, n_ctx,
-                _ptr(sel_pos_d), _ptr(sel_alt_id_d), S, K, left, ahead, deletions, insertions, T, _ptr(idx),
-                _ptr(ctx) if n_ctx else None, _ptr(tgt), _ptr(valid), self._stream()), "kl_edit_windows")
-        return idx, ctx, tgt, valid
+        return self._hypothesis_rows(self.lib.kl_edit_windows, source, S * (K + 1 + deletions + K * insertions), T,
+                                     (_ptr(sel_pos_d), _ptr(sel_alt_id_d), S, K, left, ahead, deletions, insertions))
 
     def prefix_windows(self, corpus_d, offsets_d, text_ctx_d, sel_pos_d, left, T):
         """kl_prefix_windows: the left context of S suspects as rows of their own, one per suspect, built on the device in one
@@ -819,30 +841,13 @@ class HipLM:
         and sel_pos_d int64 [S] (or a slice) as in `variant_windows` -- all DEVICE tensors.  Returns the DEVICE tensors (idx
         [S, T], ctx [S, T, n_ctx], tgt [S, T], valid [S]) int32: what `ratebulk.prefix_windows_host` states.  hipabi.KlError for
         what the entry point rejects.  No synchronisation."""
-        torch = self.torch
-        n_ctx = 0 if text_ctx_d is None else int(text_ctx_d.shape[-1])
-        tensors = [corpus_d, offsets_d, sel_pos_d] + ([text_ctx_d] if n_ctx else [])
-        kinds = [torch.int32, torch.int64, torch.int64] + ([torch.int32] if n_ctx else [])
-        n_texts = offsets_d.numel() - 1
-        S = int(sel_pos_d.numel())
-        if ([t.dtype for t in tensors] != kinds or corpus_d.dim() != 1 or offsets_d.dim() != 1 or sel_pos_d.dim() != 1
-                or (n_ctx and tuple(text_ctx_d.shape) != (n_texts, n_ctx))
-                or not all(t.is_contiguous() and t.is_cuda for t in tensors)):
-            raise hipabi.KlError("prefix_windows: corpus int32 [n], offsets int64 [n_texts + 1], text_ctx int32 [n_texts, n_ctx], "
-                                 "sel_pos int64 [S], contiguous, on the device")
-        left, T = int(left), int(T)
+        source = (corpus_d, offsets_d, text_ctx_d)
+        if not self._hypothesis_fits(source, [(sel_pos_d, self.torch.int64, 1)]):
+            raise hipabi.KlError(_HYPOTHESIS_TENSORS % ("prefix_windows", "sel_pos int64 [S]"))
+        S, left, T = int(sel_pos_d.numel()), int(left), int(T)
         if S < 1 or T < 1:
             raise hipabi.KlError("prefix_windows: S >= 1, T >= 1 (got %d, %d)" % (S, T))
-        with self._launch():
-            idx = torch.empty((S, T), dtype=torch.int32, device=self.device)
-            tgt = torch.empty((S, T), dtype=torch.int32, device=self.device)
-            ctx = torch.empty((S, T, n_ctx), dtype=torch.int32, device=self.device)
-            valid = torch.empty(S, dtype=torch.int32, device=self.device)
-            hipabi.check(self.lib.kl_prefix_windows(
-                _ptr(corpus_d), corpus_d.numel(), _ptr(offsets_d), n_texts, _ptr(text_ctx_d) if n_ctx else None, n_ctx,
-                _ptr(sel_pos_d), S, left, T, _ptr(idx), _ptr(ctx) if n_ctx else None, _ptr(tgt), _ptr(valid), self._stream()),
-                "kl_prefix_windows")
-        return idx, ctx, tgt, valid
+        return self._hypothesis_rows(self.lib.kl_prefix_windows, source, S, T, (_ptr(sel_pos_d), S, left))
 
     def fan_states(self, src_states, parent_d):
         """kl_state_fanout: the states of the streams that continue from the rows of src_states (f32 DEVICE tensor [n, 2 depth,
@@ -882,37 +887,22 @@ class HipLM:
         number of rows there are.  Returns the DEVICE tensors (idx [rows, T], ctx [rows, T, n_ctx], tgt [rows, T], valid
         [rows]) int32: what `ratebulk.span_windows_host` states.  hipabi.KlError for what the entry point rejects.  No
         synchronisation (span_first_d[S] == C is the caller's word)."""
-        torch = self.torch
-        n_ctx = 0 if text_ctx_d is None else int(text_ctx_d.shape[-1])
-        tensors = [corpus_d, offsets_d, span_text_d, span_start_d, span_len_d, span_first_d, pool_d, cand_off_d]
-        kinds = [torch.int32, torch.int64, torch.int32, torch.int64, torch.int32, torch.int64, torch.int32, torch.int64]
-        if n_ctx:
-            tensors.append(text_ctx_d)
-            kinds.append(torch.int32)
-        if (any(t is None for t in tensors) or [t.dtype for t in tensors] != kinds or any(t.dim() != 1 for t in tensors[:8])
+        source, i32, i64 = (corpus_d, offsets_d, text_ctx_d), self.torch.int32, self.torch.int64
+        if (not self._hypothesis_fits(source, [(span_text_d, i32, 1), (span_start_d, i64, 1), (span_len_d, i32, 1),
+                                               (span_first_d, i64, 1), (pool_d, i32, 1), (cand_off_d, i64, 1)])
                 or span_first_d.numel() < 2 or cand_off_d.numel() < 1 or offsets_d.numel() < 2
-                or not span_text_d.numel() == span_start_d.numel() == span_len_d.numel() == span_first_d.numel() - 1
-                or (n_ctx and tuple(text_ctx_d.shape) != (offsets_d.numel() - 1, n_ctx))
-                or not all(t.is_contiguous() and t.is_cuda for t in tensors)):
-            raise hipabi.KlError("span_windows: corpus int32 [n], offsets int64 [n_texts + 1], text_ctx int32 [n_texts, n_ctx], "
-                                 "span_text int32 [S], span_start int64 [S], span_len int32 [S], span_first int64 [S + 1], "
-                                 "pool int32 [n_pool], cand_off int64 [C + 1], contiguous, on the device")
-        n_texts = offsets_d.numel() - 1
+                or not span_text_d.numel() == span_start_d.numel() == span_len_d.numel() == span_first_d.numel() - 1):
+            raise hipabi.KlError(_HYPOTHESIS_TENSORS % (
+                "span_windows", "span_text int32 [S], span_start int64 [S], span_len int32 [S], span_first int64 [S + 1], "
+                "pool int32 [n_pool], cand_off int64 [C + 1]"))
         S, C = int(span_text_d.numel()), int(cand_off_d.numel()) - 1
         row0, rows, left, ahead, max_len, T = int(row0), int(rows), int(left), int(ahead), int(max_len), int(T)
         if rows < 1 or T < 1 or not -2 ** 63 <= row0 < 2 ** 63:
             raise hipabi.KlError("span_windows: rows >= 1, T >= 1 (got %d, %d)" % (rows, T))
-        with self._launch():
-            idx = torch.empty((rows, T), dtype=torch.int32, device=self.device)
-            tgt = torch.empty((rows, T), dtype=torch.int32, device=self.device)
-            ctx = torch.empty((rows, T, n_ctx), dtype=torch.int32, device=self.device)
-            valid = torch.empty(rows, dtype=torch.int32, device=self.device)
-            hipabi.check(self.lib.kl_span_windows(
-                _ptr(corpus_d), corpus_d.numel(), _ptr(offsets_d), n_texts, _ptr(text_ctx_d) if n_ctx else None, n_ctx,
-                _ptr(span_text_d), _ptr(span_start_d), _ptr(span_len_d), _ptr(span_first_d), S,
-                _ptr(pool_d) if pool_d.numel() else None, pool_d.numel(), _ptr(cand_off_d), C, row0, rows, left, ahead, max_len,
-                T, _ptr(idx), _ptr(ctx) if n_ctx else None, _ptr(tgt), _ptr(valid), self._stream()), "kl_span_windows")
-        return idx, ctx, tgt, valid
+        return self._hypothesis_rows(
+            self.lib.kl_span_windows, source, rows, T,
+            (_ptr(span_text_d), _ptr(span_start_d), _ptr(span_len_d), _ptr(span_first_d), S,
+             _ptr(pool_d) if pool_d.numel() else None, pool_d.numel(), _ptr(cand_off_d), C, row0, rows, left, ahead, max_len))
 
     def span_pick(self, cost_d, valid_d, span_first_d, min_gain, want_costs=True):
         """kl_span_pick: the choice among every span's candidates, on the device.  cost_d f64 [S + C] and valid_d int32 [S + C]

@@ -53,6 +53,12 @@ def _np(x):
     return np.asarray(x)
 
 
+def _target_probs(full, y):
+    """the probability of the target y [B, T] in the distributions full [B, T, V]; 0.0 where there is no target (y < 0)"""
+    p = np.take_along_axis(full, np.maximum(y, 0)[:, :, None], axis=2)[:, :, 0]
+    return np.where(y >= 0, p, 0.0)
+
+
 class StateRef(object):
     """Handle of one hypothesis state in the engine's device pool.  Quacks like
     the reference's state list [h1,c1,...,hL,cL] of (1,W) arrays when indexed."""
@@ -908,10 +914,7 @@ class Rater(object):
         else:
             def rate(s, x, z, y):
                 full = _np(lm.forward_window(x, z, want_probs=True))
-                if k:
-                    return ratebatch.alternatives_of(full, y, k)
-                p = np.take_along_axis(full, np.maximum(y, 0)[:, :, None], axis=2)[:, :, 0]
-                return (np.where(y >= 0, p, 0.0),)
+                return ratebatch.alternatives_of(full, y, k) if k else (_target_probs(full, y),)
         steps = []
         for s in range(plan.n_calls):
             x, z, y = plan.call(s)
@@ -930,6 +933,45 @@ class Rater(object):
             cols[2] = cols[2].astype(np.float32)
         bits[:] = [ratebatch.bits_of(plan.text_probs(i, cols[0])) for i in range(len(bits))]
         return cols
+
+    def _row_costs(self, precision):
+        '''How `corrections` and `rescore` rate hypothesis rows: returns rate(x, z, y) -> costs [rows], which runs one window
+        from the states as they are.  A row's cost is -sum log2(max(p, 1e-99)), in f64, over its targets.  On the HIP engine
+        that is one `rate_window_bulk` ("bf16") or `rate_window` ("split") without probabilities, and the rows' f64 bits are
+        the costs (a DEVICE tensor; the caller has cleared the sums before its first window); an engine without these sums
+        (the tests' CPU double) delivers the whole softmax of `forward_window`, and the logs are summed on the host.  Which
+        form rates is decided here alone, whoever built the windows: `corrections` and `rescore` pick their builders by
+        `variant_windows` and `span_windows`, and an engine with the sums rates host-built windows through them too.'''
+        lm = self.model
+        if hasattr(lm, 'rate_bits_take_all'):
+            window = lm.rate_window_bulk if precision == "bf16" else lm.rate_window
+
+            def rate(x, z, y):
+                window(x, z, y, want_probs=False)
+                return lm.rate_bits_take_all()
+        else:
+            def rate(x, z, y):
+                p = _target_probs(_np(lm.forward_window(x, z, want_probs=True)).astype(np.float64), y)
+                return -np.where(y >= 0, np.log2(np.maximum(p, 1e-99)), 0.0).sum(axis=1)
+        return rate
+
+    def _spans_request(self, method, texts, items):
+        '''What `rate_segments` and `rescore` (`method`) check of their spans: items is a sequence whose entries start with
+        (i, start, end), [start, end) a span of the NFC-normalised texts[i].  Returns (the normalised texts, offsets [n + 1] of
+        their sizes, span_text [S], starts [S], ends [S]), the arrays int64.  ValueError for a text index out of range, a span
+        outside its text or with end < start.'''
+        texts = [windows.normalize(t) for t in texts]
+        n, S = len(texts), len(items)
+        sizes = np.asarray([len(t) for t in texts], dtype=np.int64)
+        span_text, starts, ends = (np.asarray([int(e[k]) for e in items], dtype=np.int64).reshape(S) for k in range(3))
+        outside = (span_text < 0) | (span_text >= n)
+        if outside.any():
+            raise ValueError("%s: text index %d out of range" % (method, span_text[outside][0]))
+        bad = np.nonzero((starts < 0) | (ends < starts) | (ends > sizes[span_text]))[0]
+        if len(bad):
+            raise ValueError("%s: span [%d, %d) outside text %d of %d characters"
+                             % (method, starts[bad[0]], ends[bad[0]], span_text[bad[0]], sizes[span_text[bad[0]]]))
+        return texts, np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64), span_text, starts, ends
 
     def rate_alternatives(self, texts, contexts=None, k=3, streams=64, precision="split"):
         '''`rate_batch` answering also what the model expected instead: returns (rated, bits), both in input order.
@@ -1280,18 +1322,9 @@ class Rater(object):
         if not self.stateful:
             raise ValueError('rate_segments needs a stateful rater: it rates through stateful windows')
         n = len(texts)
-        sizes = np.asarray([len(windows.normalize(t)) for t in texts], dtype=np.int64)
         segments = list(segments)
         S = len(segments)
-        as_array = lambda k: np.asarray([int(e[k]) for e in segments], dtype=np.int64).reshape(S)
-        span_text, starts, ends = as_array(0), as_array(1), as_array(2)
-        if ((span_text < 0) | (span_text >= n)).any():
-            raise ValueError("rate_segments: text index %d out of range" % span_text[(span_text < 0) | (span_text >= n)][0])
-        bad = np.nonzero((starts < 0) | (ends < starts) | (ends > sizes[span_text]))[0]
-        if len(bad):
-            raise ValueError("rate_segments: span [%d, %d) outside text %d of %d characters"
-                             % (starts[bad[0]], ends[bad[0]], span_text[bad[0]], sizes[span_text[bad[0]]]))
-        offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        _, offsets, span_text, starts, ends = self._spans_request("rate_segments", texts, segments)
         seg_start, seg_end = starts + offsets[span_text], ends + offsets[span_text]      # (corpus positions)
         lm = self.model
         if not hasattr(lm, 'rate_segments'):
@@ -1378,10 +1411,11 @@ class Rater(object):
         T = max(left + ahead + insertions, ratebulk.MIN_T)
         device = hasattr(lm, 'variant_windows')
         share = bool(share_left) and left - 1 >= ratebulk.MIN_T      # (a shorter prefix window would fall off the persistent scans)
+        rate = self._row_costs(precision)
         # per path: the suspects (sel, in corpus order; pos and alts where the windows are built), then callables -- `build`
-        # makes the variants' windows (idx, ctx, tgt, valid) of some suspects, `rate` runs a window from the states as they are
-        # and returns its rows' costs; for share_left also `prefix` (the left contexts' windows), `start` (zero states for n
-        # prefix rows), `fan` (the states of the rows [lo * R, hi * R) that continue from the prefix rows lo .. hi - 1 of `pre`),
+        # makes the variants' windows (idx, ctx, tgt, valid) of some suspects (`rate` runs one from the states as they are and
+        # returns its rows' costs); for share_left also `prefix` (the left contexts' windows), `start` (zero states for n prefix
+        # rows), `fan` (the states of the rows [lo * R, hi * R) that continue from the prefix rows lo .. hi - 1 of `pre`),
         # `take` (pos and alts of the suspects an index array names) and `place` (rows in the order they were rated, back to
         # corpus order)
         if device:
@@ -1398,10 +1432,6 @@ class Rater(object):
 
             def build(pos, alts, left, T):
                 return lm.variant_windows(*source, pos, alts, left, ahead, deletions, T, insertions=bool(insertions))
-
-            def rate(x, z, y):      # (the rows' f64 bits are the costs)
-                (lm.rate_window_bulk if precision == "bf16" else lm.rate_window)(x, z, y, want_probs=False)
-                return lm.rate_bits_take_all()
 
             def prefix(pos):
                 return lm.prefix_windows(*source, pos, left, left - 1)
@@ -1443,11 +1473,6 @@ class Rater(object):
 
             def build(pos, alts, left, T):
                 return ratebulk.variant_windows_host(corpus, offsets, text_ctx, pos, alts, left, ahead, deletions, T, insertions)
-
-            def rate(x, z, y):
-                full = _np(lm.forward_window(x, z, want_probs=True)).astype(np.float64)
-                p = np.take_along_axis(full, np.maximum(y, 0)[:, :, None], axis=2)[:, :, 0]
-                return -np.where(y >= 0, np.log2(np.maximum(p, 1e-99)), 0.0).sum(axis=1)
 
             def prefix(pos):
                 return ratebulk.prefix_windows_host(corpus, offsets, text_ctx, pos, left, left - 1)
@@ -1566,22 +1591,14 @@ class Rater(object):
             raise ValueError("left >= 1 and ahead >= 0 (got %d, %d)" % (left, ahead))
         n = len(texts)
         lm = self.model
-        texts = [windows.normalize(t) for t in texts]
-        sizes = np.asarray([len(t) for t in texts], dtype=np.int64)
         edits = list(edits)
         S = len(edits)
-        as_array = lambda k: np.asarray([int(e[k]) for e in edits], dtype=np.int64).reshape(S)
-        span_text, starts, ends = as_array(0), as_array(1), as_array(2)
-        count = [len(e[3]) for e in edits]
+        count = [len(e[3]) for e in edits]      # (the candidates are read before a span is refused)
         strings = [windows.normalize(c) for e in edits for c in e[3]]
         lengths = np.asarray([len(c) for c in strings], dtype=np.int64)
         C = len(strings)
-        if ((span_text < 0) | (span_text >= n)).any():
-            raise ValueError("rescore: text index %d out of range" % span_text[(span_text < 0) | (span_text >= n)][0])
-        bad = np.nonzero((starts < 0) | (ends < starts) | (ends > sizes[span_text]))[0]
-        if len(bad):
-            raise ValueError("rescore: span [%d, %d) outside text %d of %d characters"
-                             % (starts[bad[0]], ends[bad[0]], span_text[bad[0]], sizes[span_text[bad[0]]]))
+        texts, offsets, span_text, starts, ends = self._spans_request("rescore", texts, edits)
+        sizes = offsets[1:] - offsets[:-1]
         span_text, span_len = span_text.astype(np.int32), (ends - starts).astype(np.int32)
         M = int(max([1] + ([int(span_len.max())] if S else []) + ([int(lengths.max())] if C else [])))
         if M > ratebulk.SPAN_LEN_MAX:
@@ -1598,7 +1615,6 @@ class Rater(object):
         # (a span at a text's first character, and one in a text of a single character, holds no prediction)
         if S and ((starts >= 1) & (sizes[span_text] >= 2)).any():
             # (all texts, and all candidates, encoded in one go: many short strings cost a Python loop each)
-            offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
             joined = "".join(texts)
             corpus = windows.encode(joined, self.mapping[0]).astype(np.int32)
             for g in np.nonzero(corpus == 0)[0]:
@@ -1613,6 +1629,7 @@ class Rater(object):
             pool = windows.encode("".join(strings), self.mapping[0]).astype(np.int32)
             cand_off = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
             chunks = ratebulk.span_chunks(span_first, streams)
+            rate = self._row_costs(precision)
             if hasattr(lm, 'span_windows'):
                 torch = lm.torch
                 up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(lm.device)
@@ -1624,8 +1641,7 @@ class Rater(object):
                 for a, b in chunks:
                     x, z, y, ok = lm.span_windows(*(where + spans), row0=a, rows=b - a, left=left, ahead=ahead, max_len=M, T=T)
                     lm.reset_states(b - a)
-                    (lm.rate_window_bulk if precision == "bf16" else lm.rate_window)(x, z, y, want_probs=False)
-                    cost_d[a:b] = lm.rate_bits_take_all()      # (the rows' f64 bits are the costs)
+                    cost_d[a:b] = rate(x, z, y)
                     valid_d[a:b] = ok
                 best_d, gain_d, cost_d = lm.span_pick(cost_d, valid_d, spans[3], float(min_gain), want_costs=want_costs)
                 lm.rate_status_check()
@@ -1640,9 +1656,7 @@ class Rater(object):
                     x, z, y, ok = ratebulk.span_windows_host(corpus, offsets, text_ctx, span_text, span_start, span_len,
                                                              span_first, pool, cand_off, a, b - a, left, ahead, M, T)
                     lm.reset_states(b - a)
-                    full = _np(lm.forward_window(x, z, want_probs=True)).astype(np.float64)
-                    p = np.take_along_axis(full, np.maximum(y, 0)[:, :, None], axis=2)[:, :, 0]
-                    costs.append(-np.where(y >= 0, np.log2(np.maximum(p, 1e-99)), 0.0).sum(axis=1))
+                    costs.append(rate(x, z, y))
                     valids.append(ok)
                 best, gain, all_costs = ratebulk.span_pick_host(np.concatenate(costs), np.concatenate(valids), span_first,
                                                                 float(min_gain))

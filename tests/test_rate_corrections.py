@@ -97,7 +97,7 @@ def brute_row(corpus, offsets, text_ctx, g, alts, v, left, ahead, T):
 
 
 # ---------------------------------------------------------------------------------------------- the numpy statements
-@pytest.mark.parametrize("n_ctx", [0, 2])
+@pytest.mark.parametrize("n_ctx", [0, 2, 3])
 @pytest.mark.parametrize("deletions", [0, 1])
 def test_variant_windows_host_against_brute_force(deletions, n_ctx):
     corpus, offsets, text_ctx = variant_corpus(n_ctx)

@@ -64,7 +64,7 @@ def twice_equal_to(v, want, *args):
 
 
 # ---------------------------------------------------------------------------------------------- kl_edit_windows
-@pytest.mark.parametrize("n_ctx", [0, 2])
+@pytest.mark.parametrize("n_ctx", [0, 2, 3])
 @pytest.mark.parametrize("deletions", [0, 1])
 @pytest.mark.parametrize("S,K,left,ahead,T", SHAPES)
 def test_edit_windows_is_variant_windows_host(S, K, left, ahead, T, deletions, n_ctx):

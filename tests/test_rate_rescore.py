@@ -127,7 +127,7 @@ def rows_of(spans):
 
 
 # ---------------------------------------------------------------------------------------------- the numpy statements
-@pytest.mark.parametrize("n_ctx", [0, 2])
+@pytest.mark.parametrize("n_ctx", [0, 2, 3])
 def test_span_windows_host_against_brute_force(n_ctx):
     corpus, offsets, text_ctx = span_corpus(n_ctx)
     short = corpus[:int(offsets[-1]) - 2]      # n_read = len(corpus) < offsets[-1]: the last text's end has no ids

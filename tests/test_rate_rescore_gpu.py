@@ -93,7 +93,7 @@ def twice_equal_to(v, want, *args, **kw):
 
 
 # ---------------------------------------------------------------------------------------------- kl_span_windows
-@pytest.mark.parametrize("n_ctx", [0, 2])
+@pytest.mark.parametrize("n_ctx", [0, 2, 3])
 @pytest.mark.parametrize("S,most,left,ahead,M,T", SHAPES)
 def test_span_windows_is_span_windows_host(S, most, left, ahead, M, T, n_ctx):
     corpus, offsets, text_ctx = span_corpus(n_ctx)

@@ -94,7 +94,7 @@ class Prefix(object):
 
 
 # ---------------------------------------------------------------------------------------------- kl_prefix_windows
-@pytest.mark.parametrize("n_ctx", [0, 2])
+@pytest.mark.parametrize("n_ctx", [0, 2, 3])
 @pytest.mark.parametrize("S", [1, 37])
 @pytest.mark.parametrize("extra", [-1, 2])
 @pytest.mark.parametrize("left", [2, 4, 7, 64])
