@@ -23,6 +23,7 @@
  *   ... per word: the words found, rated and the suspect ones picked out  kl_word_bounds, kl_rate_segments, kl_segment_select
  *       (the processor's mean probability per TextEquiv substring, wrapper/rate.py:308-317, for a whole corpus)
  *   ... and the suspect words' nearest entries of a lexicon, as replacements   kl_lexicon_neighbours
+ *   ... and the spans where a second reading of the text (another OCR engine) differs   kl_align_pairs
  *   model.predict_on_batch, stateful (1,1) step, :566        kl_forward_window with T = 1
  *   model.predict_on_batch, incremental + states, :631       kl_step_batch
  *   ... once per character of a lattice edge, :796-851       kl_walk_batch_host (all characters of all hypotheses, one call)
@@ -518,6 +519,55 @@ size_t kl_lexicon_neighbours_workspace_bytes(size_t Q, int K);
 int kl_lexicon_neighbours(const int32_t* chars, size_t n_chars, const int32_t* order, const int64_t* class_first, int V,
                           const int32_t* q_pool, size_t n_q, const int64_t* q_off, size_t Q, int max_dist, int K, int32_t* exact,
                           int32_t* found, int32_t* cand, int32_t* dist, void* ws, size_t ws_bytes, void* stream);
+
+/* Alignment of two readings: where do the texts of P pairs differ?  The step in front of kl_span_windows for a second witness of
+ * the same line or page (another OCR engine): the differing spans become the spans and replacements it rates.  No handle.
+ *
+ * Text p of side a is a_pool[a_off[p] .. a_off[p + 1]) -- device int32 symbols [n_a] and device int64 offsets [P + 1] --, side b
+ * the same.  Two symbols are equal iff they are the same number (the callers pass Unicode code points: no mapping is involved).
+ *
+ * Distance matrix.  With n, m the lengths of a pair: D[i][0] = i, D[0][j] = j, otherwise
+ *   D[i][j] = min(D[i-1][j-1] + (a[i-1] != b[j-1]), D[i-1][j] + 1, D[i][j-1] + 1);   d = D[n][m].
+ * Status in dist[p] (device int32 [P]): d if d <= max_dist; -1 if d > max_dist -- the two are not readings of the same text;
+ * |n - m| > max_dist decides that without any DP --; -2 if n > max_len or m > max_len, or if the pair's offsets are descending
+ * or reach outside [0, n_a] / [0, n_b]: nothing of such a pair is read, and no address beyond max_len symbols of a pair is ever
+ * formed.  For -1 and -2, n_spans[p] = 0.
+ *
+ * Canonical alignment.  Walk back from (n, m) and take the first of these that applies at (i, j):
+ *   1. i, j > 0, a[i-1] == b[j-1] and D[i-1][j-1] == D[i][j]:  match
+ *   2. i, j > 0 and D[i-1][j-1] + 1 == D[i][j]:                substitution
+ *   3. i > 0 and D[i-1][j] + 1 == D[i][j]:                     deletion of a[i-1]
+ *   4. otherwise:                                              insertion of b[j-1]
+ *
+ * Spans.  Read the operations forwards: a maximal run of non-matches is a difference; two successive differences with at most
+ * `join` matches between them become one, and the matches between them belong to both sides of it.  Span s of pair p is
+ * spans[(p * max_dist + s) * 4 ..] = (a_start, a_end, b_start, b_end) (device int32 [P][max_dist][4]), relative to the texts'
+ * beginnings, ascending: a[a_start:a_end] reads b[b_start:b_end] in the witness.  n_spans[p] (device int32 [P]) <= d <= max_dist;
+ * every place from n_spans[p] on holds -1 in all four fields, for rejected pairs too.  Two empty texts give d = 0 and no span,
+ * one empty text one span.  Every output is OVERWRITTEN for every p < P; nothing behind is written.  The statement is
+ * ratebulk.align_pairs_host.
+ *
+ * The band.  The DP runs over |i - j| <= max_dist only, which leaves all of the above unchanged for pairs with d <= max_dist: a
+ * cell whose true value is at most max_dist is exact under the band, every other cell can only come out larger, and every cell
+ * on an optimal path is worth at most d -- so no wrong predecessor can qualify in the walk, and D[n][m] <= max_dist under the
+ * band iff it is so without.
+ *
+ * One workgroup of 2 * max_dist + 1 lanes (in whole waves) per pair, a grid-stride loop when P exceeds the grid of 512; the
+ * anti-diagonals in turn, one barrier each, the last values in LDS; per cell the two bits of the rule that applies, in LDS while
+ * (n / 16 + 1) * (2 * max_dist + 1) words fit 24 KiB, else in the workgroup's slice of ws; the walk back on one lane.  One plain
+ * launch on `stream`, no atomics, no workgroup waits for another, and the output depends on the inputs only: two calls agree bit
+ * for bit.  ws: device scratch of kl_align_pairs_workspace_bytes(P, max_len, max_dist) bytes (0 for arguments out of range) --
+ * a slice per workgroup of the grid, not per pair, and 8 bytes where every text of max_len symbols fits LDS --, 8-byte aligned,
+ * not to be shared by calls that may overlap.  KL_ERR_ARG, before any launch and with no output touched, for null pointers (a
+ * pool may be null when its n_* is 0), P < 1 or >= 2^31, max_len outside 0 .. KL_ALIGN_LEN_MAX, max_dist outside
+ * 1 .. KL_ALIGN_DIST_MAX, join < 0, n_a or n_b > 2^40, misaligned pointers (the offsets 8 bytes, the others 4);
+ * KL_ERR_WORKSPACE if ws_bytes is too small or ws is not 8-byte aligned. */
+#define KL_ALIGN_DIST_MAX 255
+#define KL_ALIGN_LEN_MAX 4096
+size_t kl_align_pairs_workspace_bytes(size_t P, int max_len, int max_dist);
+int kl_align_pairs(const int32_t* a_pool, size_t n_a, const int64_t* a_off, const int32_t* b_pool, size_t n_b, const int64_t* b_off,
+                   size_t P, int max_len, int max_dist, int join, int32_t* dist, int32_t* n_spans, int32_t* spans, void* ws,
+                   size_t ws_bytes, void* stream);
 
 /* One training batch, forward + backward (rating.py:292-298 -> train_on_batch):
  * writes the gradient of (mean CE + embedding regularisers, rating.py:187-246)

@@ -97,6 +97,7 @@ class HipLM:
         self._word_bounds_ws = None
         self._segment_select_ws = None
         self._lexicon_ws = None
+        self._align_ws = None
         self.states = None       # [B][2L][W] implicit state of the stateful streams
         self.pool = None            # [slots][2L][W] explicit states of hypotheses
         self.max_streams_per_launch = 0      # 0: what the kernels address (train_window splits larger batches into groups)
@@ -814,6 +815,29 @@ class HipLM:
                 n_ctx, *middle, T, _ptr(idx), _ptr(ctx) if n_ctx else None, _ptr(tgt), _ptr(valid), self._stream()),
                 entry.__name__)
         return idx, ctx, tgt, valid
+
+    def align_pairs(self, a_pool_d, a_off_d, b_pool_d, b_off_d, max_len, max_dist, join):
+        """kl_align_pairs: where the texts of P pairs differ, within a band of max_dist edits.  a_pool_d, b_pool_d int32 symbols
+        and a_off_d, b_off_d int64 [P + 1] on the DEVICE: text p of a side is pool[off[p]:off[p + 1]].  Returns the DEVICE tensors
+        (dist int32 [P], n_spans int32 [P], spans int32 [P, max_dist, 4]); the statement is ratebulk.align_pairs_host.
+        hipabi.KlError for what the entry point rejects.  No synchronisation."""
+        torch = self.torch
+        tensors = (a_pool_d, a_off_d, b_pool_d, b_off_d)
+        if ([t.dtype for t in tensors] != [torch.int32, torch.int64, torch.int32, torch.int64] or any(t.dim() != 1 for t in tensors)
+                or a_off_d.numel() < 2 or a_off_d.numel() != b_off_d.numel()
+                or not all(t.is_contiguous() and t.is_cuda for t in tensors)):
+            raise hipabi.KlError("align_pairs: pools int32, offsets int64 [P + 1] of one size, contiguous, on the device")
+        max_len, max_dist, join = int(max_len), int(max_dist), int(join)
+        P = a_off_d.numel() - 1
+        dev = self.device
+        with self._launch():
+            ws = self._scratch("_align_ws", self.lib.kl_align_pairs_workspace_bytes(P, max_len, max_dist))
+            out = (torch.empty(P, dtype=torch.int32, device=dev), torch.empty(P, dtype=torch.int32, device=dev),
+                   torch.empty((P, max(max_dist, 0), 4), dtype=torch.int32, device=dev))
+            hipabi.check(self.lib.kl_align_pairs(
+                _ptr(a_pool_d), a_pool_d.numel(), _ptr(a_off_d), _ptr(b_pool_d), b_pool_d.numel(), _ptr(b_off_d), P, max_len,
+                max_dist, join, *([_ptr(t) for t in out] + [_ptr(ws), ws.numel(), self._stream()])), "kl_align_pairs")
+        return out
 
     def variant_windows(self, corpus_d, offsets_d, text_ctx_d, sel_pos_d, sel_alt_id_d, left, ahead, deletions, T,
                         insertions=False):

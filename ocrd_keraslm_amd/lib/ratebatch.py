@@ -409,6 +409,63 @@ class Neighbours(object):
         return [self.lexicon.words[int(e)] for e in self.index[i] if e >= 0]
 
 
+class Alignment(object):
+    """One pair of `Rater.align`, a text `a` against a witness `b` (both NFC-normalised):
+
+    dist    int          the Levenshtein distance (unit costs) if it is at most max_dist; -1: more than max_dist edits apart --
+                         not two readings of the same text; -2: a text longer than the call could take
+    spans   [m, 4] i32   where they differ, ascending: a[a_start:a_end] reads b[b_start:b_end] in the witness (one side may be
+                         empty: an insertion or a deletion); none for dist <= 0
+    """
+
+    def __init__(self, dist, spans):
+        self.dist, self.spans = int(dist), spans
+
+    def __len__(self):
+        return len(self.spans)
+
+    def strings(self, a, b):
+        """the differences as [(written, witness_reading)]"""
+        return [(a[a0:a1], b[b0:b1]) for a0, a1, b0, b1 in self.spans.tolist()]
+
+    def apply(self, a, b):
+        """a with every span replaced by the witness' reading, from right to left: the witness itself (where dist >= 0)"""
+        chars = list(a)
+        for a0, a1, b0, b1 in reversed(self.spans.tolist()):
+            chars[a0:a1] = list(b[b0:b1])
+        return "".join(chars)
+
+
+def witness_edits(alignments, pairs, texts, witnesses, max_len=ratebulk.SPAN_LEN_MAX):
+    """Edits for `Rater.rescore` from second readings of the texts: witnesses[i] is a sequence of strings (possibly none) that
+    read the same line or page as texts[i], pairs[q] = (i, w) says that alignments[q] (`Rater.align`'s `Alignment`) is texts[i]
+    against witnesses[i][w].  Returns (edits, skipped): one edit (i, start, end, readings) per differing span of a text, ordered
+    by text and start; spans of one text with the same (start, end) from several witnesses pool their readings -- first seen
+    first, duplicates dropped --, spans that merely overlap stay separate (`Rescored.apply` resolves overlaps by gain).
+    `skipped` counts what yields no edit, by reason: "different" -- pairs with dist < 0 --, "first" -- spans with start == 0:
+    no prediction to be held against, as `word_edits` skips them --, "long" -- spans with more than max_len characters on a
+    side.  Host only."""
+    if len(alignments) != len(pairs) or len(texts) != len(witnesses):
+        raise ValueError("witness_edits: one alignment per pair, one sequence of witnesses per text")
+    skipped = dict(different=0, first=0, long=0)
+    pooled = {}
+    for one, (i, w) in zip(alignments, pairs):
+        if one.dist < 0:
+            skipped["different"] += 1
+            continue
+        reading = windows.normalize(witnesses[i][w])
+        for a0, a1, b0, b1 in one.spans.tolist():
+            if a0 == 0:
+                skipped["first"] += 1
+            elif a1 - a0 > max_len or b1 - b0 > max_len:
+                skipped["long"] += 1
+            else:
+                readings = pooled.setdefault((i, a0, a1), [])
+                if reading[b0:b1] not in readings:
+                    readings.append(reading[b0:b1])
+    return [(i, a0, a1, pooled[i, a0, a1]) for i, a0, a1 in sorted(pooled)], skipped
+
+
 def confusion_edits(texts, rules, at=None):
     """Edits for `Rater.rescore` from a table of known confusions: rules is a list of (source, [replacements]) with a non-empty
     source; one edit (i, start, end, replacements) per occurrence of a source in the NFC-normalised texts[i], overlapping

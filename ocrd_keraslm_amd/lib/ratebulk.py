@@ -842,3 +842,101 @@ def lexicon_neighbours_host(q_pool, q_off, chars, order, class_first, V, max_dis
         cand[q, :len(first)] = hits[first]
         dist[q, :len(first)] = levs[first]
     return exact, found, cand, dist
+
+
+ALIGN_DIST_MAX, ALIGN_LEN_MAX = 255, 4096      # (KL_ALIGN_* of the C ABI)
+_BEYOND = 1 << 20                              # a value outside the band
+
+
+def align_pairs_host(a_pool, a_off, b_pool, b_off, max_len, max_dist, join):
+    """what kl_align_pairs computes: for the P pairs a = a_pool[a_off[p]:a_off[p + 1]], b = b_pool[b_off[p]:b_off[p + 1]] of
+    int32 symbols (equal iff the same number), (dist int32 [P], n_spans int32 [P], spans int32 [P, max_dist, 4]).
+
+    With n, m the lengths: D[i][0] = i, D[0][j] = j, D[i][j] = min(D[i-1][j-1] + (a[i-1] != b[j-1]), D[i-1][j] + 1,
+    D[i][j-1] + 1), d = D[n][m].  dist[p] is d if d <= max_dist, -1 if d > max_dist, -2 if n > max_len or m > max_len or the
+    offsets are descending or reach outside their pool; n_spans is 0 for -1 and -2.  The walk back from (n, m) takes the first
+    that applies at (i, j): a match (i, j > 0, a[i-1] == b[j-1], D[i-1][j-1] == D[i][j]), a substitution (i, j > 0,
+    D[i-1][j-1] + 1 == D[i][j]), a deletion of a[i-1] (i > 0, D[i-1][j] + 1 == D[i][j]), else an insertion of b[j-1].  Read
+    forwards, a maximal run of non-matches is a difference; two with at most `join` matches between them become one, the
+    matches included.  spans[p, s] = (a_start, a_end, b_start, b_end), ascending, -1 in every place from n_spans[p] on.
+
+    A plain DP, row by row, over the band |i - j| <= max_dist (row i holds j = i - max_dist .. i + max_dist at index
+    j - i + max_dist, `_BEYOND` outside the matrix): a cell worth at most max_dist is exact under the band and every other only
+    larger, so nothing above changes for d <= max_dist, and d > max_dist is seen as such."""
+    a_pool = np.asarray(a_pool, dtype=np.int32).reshape(-1)
+    b_pool = np.asarray(b_pool, dtype=np.int32).reshape(-1)
+    a_off = np.asarray(a_off, dtype=np.int64).reshape(-1)
+    b_off = np.asarray(b_off, dtype=np.int64).reshape(-1)
+    max_len, K, join = int(max_len), int(max_dist), int(join)
+    if not (0 <= max_len <= ALIGN_LEN_MAX and 1 <= K <= ALIGN_DIST_MAX and join >= 0):
+        raise ValueError("align_pairs_host: max_len in 0 .. %d, max_dist in 1 .. %d, join >= 0" % (ALIGN_LEN_MAX, ALIGN_DIST_MAX))
+    if len(a_off) < 2 or len(a_off) != len(b_off):
+        raise ValueError("align_pairs_host: a_off and b_off [P + 1], P >= 1")
+    P = len(a_off) - 1
+    dist = np.zeros(P, dtype=np.int32)
+    n_spans = np.zeros(P, dtype=np.int32)
+    spans = np.full((P, K, 4), -1, dtype=np.int32)
+    L = 2 * K + 1
+    lane = np.arange(L)
+    for p in range(P):
+        a0, a1, b0, b1 = int(a_off[p]), int(a_off[p + 1]), int(b_off[p]), int(b_off[p + 1])
+        n, m = a1 - a0, b1 - b0
+        if a0 < 0 or n < 0 or a1 > len(a_pool) or b0 < 0 or m < 0 or b1 > len(b_pool) or n > max_len or m > max_len:
+            dist[p] = -2
+            continue
+        if abs(n - m) > K:
+            dist[p] = -1
+            continue
+        a, b = a_pool[a0:a1], b_pool[b0:b1]
+        padded = np.concatenate([np.zeros(K + 1, dtype=np.int32), b, np.zeros(2 * K, dtype=np.int32)])      # b[j - 1] at [j + K]
+        D = np.full((n + 1, L + 1), _BEYOND, dtype=np.int64)      # (one column more: D[i - 1][j] of the last diagonal)
+        j = lane - K
+        D[0, :L][(j >= 0) & (j <= m)] = j[(j >= 0) & (j <= m)]
+        for i in range(1, n + 1):
+            j = i + lane - K
+            inside = (j >= 0) & (j <= m)
+            differ = (padded[i:i + L] != a[i - 1]).astype(np.int64)
+            cell = np.minimum(D[i - 1, :L] + differ, D[i - 1, 1:] + 1)      # from (i - 1, j - 1) and from (i - 1, j)
+            cell[j == 0] = i
+            cell[~inside] = _BEYOND
+            cell = np.minimum.accumulate(cell - lane) + lane                 # from (i, j - 1), all the way along the row
+            cell[~inside] = _BEYOND
+            D[i, :L] = np.minimum(cell, _BEYOND)
+        d = int(D[n, m - n + K])
+        if d > K:
+            dist[p] = -1
+            continue
+        dist[p] = d
+        at = lambda i, j: int(D[i, j - i + K]) if i >= 0 and 0 <= j <= m and abs(i - j) <= K else _BEYOND
+        ops = []                                  # backwards: (is a match, i, j) with (i, j) the cell the operation ends in
+        i, j = n, m
+        while i > 0 or j > 0:
+            here = at(i, j)
+            if i > 0 and j > 0 and a[i - 1] == b[j - 1] and at(i - 1, j - 1) == here:
+                ops.append((True, i, j))
+                i, j = i - 1, j - 1
+            elif i > 0 and j > 0 and at(i - 1, j - 1) + 1 == here:
+                ops.append((False, i, j))
+                i, j = i - 1, j - 1
+            elif i > 0 and at(i - 1, j) + 1 == here:
+                ops.append((False, i, j))
+                i = i - 1
+            else:
+                ops.append((False, i, j))
+                j = j - 1
+        found = []                                # [a_start, a_end, b_start, b_end], ascending
+        i = j = matches = 0
+        for match, i_next, j_next in reversed(ops):
+            if match:
+                matches += 1
+            else:
+                if found and matches <= join:
+                    found[-1][1], found[-1][3] = i_next, j_next
+                else:
+                    found.append([i, i_next, j, j_next])
+                matches = 0
+            i, j = i_next, j_next
+        n_spans[p] = len(found)
+        if found:
+            spans[p, :len(found)] = found
+    return dist, n_spans, spans

@@ -1774,6 +1774,84 @@ class Rater(object):
                                 precision=precision)
         return found, rescored, bits
 
+    def align(self, texts, others, max_dist=32, join=0):
+        '''Where does each of `texts` differ from its second reading in `others` (one string per side and pair)?  Returns one
+        ratebatch.Alignment per pair: `dist`, the Levenshtein distance (unit costs) if it is at most max_dist, -1 if the two are
+        further apart -- not readings of the same text --, and `spans`, the differences as (a_start, a_end, b_start, b_end):
+        maximal runs of substitutions, insertions and deletions of the canonical alignment (a diagonal step before a deletion
+        before an insertion, walking back from the ends), two of them with at most `join` equal characters between them made
+        one.  join=0 reports what is there.
+
+        Both sides are NFC-normalised and positions are those of the normalised strings, as everywhere in `rescore`; the texts
+        are compared as code points, so the result does not depend on the model's mapping.  On the HIP engine there is one
+        upload per side (offsets and code points in one buffer), one kernel call (`HipLM.align_pairs`, max_len the longest text
+        of the call), the used spans are compacted on the device, and dist, the span counts and the spans come back in one
+        download.  No pairs give their result without a launch.  An engine without `align_pairs` (the tests' CPU double) runs
+        ratebulk.align_pairs_host.  Needs a loaded engine, not a stateful rater.  ValueError for unequal numbers of texts, a
+        text of more than 4096 characters, max_dist outside 1 .. 255, join < 0.'''
+        assert self.status > 1
+        texts, others = [windows.normalize(t) for t in texts], [windows.normalize(t) for t in others]
+        max_dist, join = int(max_dist), int(join)
+        if len(texts) != len(others):
+            raise ValueError("align: one witness per text (got %d and %d)" % (len(texts), len(others)))
+        if not 1 <= max_dist <= ratebulk.ALIGN_DIST_MAX or join < 0:
+            raise ValueError("align: max_dist in 1 .. %d and join >= 0 (got %d, %d)" % (ratebulk.ALIGN_DIST_MAX, max_dist, join))
+        P = len(texts)
+        max_len = max([len(t) for t in texts + others] or [0])
+        if max_len > ratebulk.ALIGN_LEN_MAX:
+            raise ValueError("align: a text of %d characters; at most %d -- cut pages into lines or paragraphs"
+                             % (max_len, ratebulk.ALIGN_LEN_MAX))
+        if P == 0:
+            return []
+        sides = []
+        for strings in (texts, others):
+            off = np.concatenate([[0], np.cumsum([len(t) for t in strings])]).astype(np.int64)
+            sides.append((np.frombuffer("".join(strings).encode("utf-32-le", "surrogatepass"), dtype=np.int32), off))
+        lm = self.model
+        if hasattr(lm, 'align_pairs'):
+            torch = lm.torch
+            args = []
+            for pool, off in sides:
+                both = torch.from_numpy(np.concatenate([off.view(np.int32), pool])).to(lm.device)
+                args += [both[2 * (P + 1):], both[:2 * (P + 1)].view(torch.int64)]
+            dist, n_spans, spans = lm.align_pairs(*args, max_len, max_dist, join)
+            used = torch.arange(max_dist, device=lm.device)[None, :] < n_spans[:, None]
+            out = _np(torch.cat([dist, n_spans, spans[used].reshape(-1)]))
+            dist, n_spans, spans = out[:P], out[P:2 * P], out[2 * P:].reshape(-1, 4)
+        else:
+            dist, n_spans, spans = ratebulk.align_pairs_host(sides[0][0], sides[0][1], sides[1][0], sides[1][1], max_len, max_dist, join)
+            spans = spans[np.arange(max_dist)[None, :] < n_spans[:, None]]
+        first = np.concatenate([[0], np.cumsum(n_spans)])
+        return [ratebatch.Alignment(dist[p], spans[first[p]:first[p + 1]].copy()) for p in range(P)]
+
+    def merge_witnesses(self, texts, witnesses, contexts=None, max_dist=32, join=1, left=64, ahead=8, min_gain=1.0, streams=1024,
+                        precision="bf16"):
+        '''From a text and other readings of it to the readings the model prefers: `align` -> `ratebatch.witness_edits` ->
+        `rescore`.  witnesses is one sequence of strings per text, possibly empty: what a second OCR engine (or several) read
+        in the same line or page.  All pairs of all texts go through ONE `align(.., max_dist, join)`; the differing spans become
+        `rescore`'s edits, the witnesses' readings of a span its candidates (`witness_edits`: spans at a text's first character,
+        spans of more than 64 characters on a side and witnesses further than max_dist edits away yield none and are counted);
+        `rescore(texts, edits, contexts, streams=.., left=.., ahead=.., min_gain=.., precision=..)` rates them.  Returns
+        (alignments, rescored, skipped): per text the list of its witnesses' `Alignment`s, `rescore`'s result, and
+        `witness_edits`' counts by reason.
+
+        join defaults to 1 here and to 0 in `align`: two differences one character apart are ONE hypothesis to a model that
+        reads `ahead` = 8 characters on -- rated apart, each would be held against a continuation that holds the other's
+        error --, while `align` reports what is there.  State and precision afterwards are as after `rescore`.  ValueError for
+        what `align` and `rescore` raise, and for a number of witness lists other than the number of texts.'''
+        texts = list(texts)
+        witnesses = [list(w) for w in witnesses]
+        if len(witnesses) != len(texts):
+            raise ValueError("merge_witnesses: one sequence of witnesses per text (got %d for %d texts)" % (len(witnesses), len(texts)))
+        pairs = [(i, w) for i, readings in enumerate(witnesses) for w in range(len(readings))]
+        flat = self.align([texts[i] for i, _ in pairs], [witnesses[i][w] for i, w in pairs], max_dist=max_dist, join=join)
+        edits, skipped = ratebatch.witness_edits(flat, pairs, texts, witnesses)
+        rescored = self.rescore(texts, edits, contexts, streams=streams, left=left, ahead=ahead, min_gain=min_gain, precision=precision)
+        alignments = [[] for _ in texts]
+        for one, (i, _) in zip(flat, pairs):
+            alignments[i].append(one)
+        return alignments, rescored, skipped
+
     def _contexts_per_text(self, contexts, n):
         '''None, one context list for all texts, or one per text -> one list per text (as `rate_batch` reads them)'''
         if contexts is None or len(contexts) == 0:

@@ -24,6 +24,9 @@ probability (Rater.suspect_words: rated in bulk, the words found, rated and pick
 Additional command `lexicon`: the suspect words of every DATA file looked up in a word list (--lexicon, the most frequent entry
 first) on the device, and their nearest entries rated against the text around them (Rater.correct_words: suspect_words ->
 lexicon_neighbours -> rescore); output as `rescore`'s, --apply also gives the corrected text.
+Additional command `witnesses`: every DATA file aligned with other readings of it (--witness DIR: the file of the same base
+name) on the device, and the readings of the spans where they differ rated against the text around them
+(Rater.merge_witnesses: align -> witness_edits -> rescore); --apply also gives the corrected text.
 Additional options on `train`: --streams (stateful streams per GPU, default 1 = the
 reference's batching) and --segment-streams (with fewer files than streams, cut the files
 into contiguous segments on window boundaries, one list of segments per stream).  Under `python -m torch.distributed.run` training is
@@ -40,7 +43,7 @@ import click
 
 from .. import lib
 
-COMMAND_ORDER = ['train', 'test', 'score', 'suspects', 'correct', 'rescore', 'contexts', 'words', 'lexicon', 'apply', 'generate', 'print-history', 'print-charset', 'prune-charset',
+COMMAND_ORDER = ['train', 'test', 'score', 'suspects', 'correct', 'rescore', 'contexts', 'words', 'lexicon', 'witnesses', 'apply', 'generate', 'print-history', 'print-charset', 'prune-charset',
                  'plot-char-embeddings-similarity', 'plot-context-embeddings-similarity', 'plot-context-embeddings-projection']
 
 
@@ -614,6 +617,69 @@ def lexicon_(model, lexicon_file, max_dist, per_word, known, streams, precision,
         rows = [[int(a), int(b), text[int(a):int(b)], new, float(g)]
                 for a, b, new, g in zip(one.starts, one.ends, one.proposals(), one.gain)]
         line = {"file": name, "chars": len(text), "rescored": rows}
+        if apply_:
+            line["corrected"] = one.apply(text)
+        click.echo(json.dumps(line, ensure_ascii=False))
+
+
+@cli.command('witnesses', short_help='let the model choose between every file and other readings of it')
+@click.option('-m', '--model', default="model.h5", show_default=True, help='model file', type=click.Path(dir_okay=False, exists=True))
+@click.option('--witness', 'witness_dirs', multiple=True, required=True, type=click.Path(file_okay=False, exists=True),
+              help='directory of second readings: the witness of a DATA file is the file of the same base name (may be missing); '
+                   'repeat for further witnesses')
+@click.option('--max-dist', default=32, show_default=True, type=click.IntRange(min=1, max=255),
+              help='a witness further than this many edits from its file is not a reading of the same text')
+@click.option('--join', default=1, show_default=True, type=click.IntRange(min=0),
+              help='differences with at most this many equal characters between them are one span')
+@click.option('-s', '--streams', default=1024, show_default=True, help='rows of a window call: hypotheses',
+              type=click.IntRange(min=1, max=4096))
+@click.option('--precision', default='bf16', show_default=True, type=click.Choice(['bf16', 'split']),
+              help='bf16: bulk rating on the training forward; split: the inference kernels, ~f32 accuracy')
+@click.option('--left', default=64, show_default=True, type=click.IntRange(min=1, max=1024),
+              help='characters in front of a span that a hypothesis is read from (from a zero state)')
+@click.option('--ahead', default=8, show_default=True, type=click.IntRange(min=0, max=1023),
+              help='characters after a span that a hypothesis is held against')
+@click.option('--min-gain', default=1.0, show_default=True, type=click.FLOAT,
+              help='a proposal must save at least this many bits against the text as written')
+@click.option('--apply', 'apply_', is_flag=True, default=False, help='also give the text with the proposals applied ("corrected")')
+@click.argument('data', nargs=-1, type=click.Path(exists=True, dir_okay=True, file_okay=True))
+def witnesses_(model, witness_dirs, max_dist, join, streams, precision, left, ahead, min_gain, apply_, data):
+    """Align every DATA file with its witnesses -- the files of the same base name in the --witness
+       directories --, rate the witnesses' readings of the spans where they differ against the text
+       around them, and print one JSON line per file: characters, "witnesses": one {"file", "dist"} per
+       witness found (dist -1: more than --max-dist edits apart, not used), "rescored" as `rescore` prints
+       it, and "skipped": what yielded no hypothesis, by reason.  With --apply the line also holds the
+       corrected text.  A file or witness of more than 4096 characters is an error: cut pages into lines.
+    """
+    from ..lib import ratebatch, windows
+    rater = _load(model)
+    names, texts, contexts, readings, sources = [], [], [], [], []
+    for file in _open_all(data):
+        with file:
+            texts.append(windows.normalize(file.read()))
+        names.append(file.name)
+        contexts.append(windows.context_from_filename(file.name))
+        paths = [os.path.join(d, os.path.basename(file.name)) for d in witness_dirs]
+        sources.append([p for p in paths if os.path.isfile(p)])
+        readings.append([])
+        for path in sources[-1]:
+            with open(path, mode='r') as other:
+                readings[-1].append(windows.normalize(other.read()))
+    if not texts:
+        return
+    try:
+        alignments, found, _ = rater.merge_witnesses(texts, readings, contexts, max_dist=max_dist, join=join, left=left,
+                                                     ahead=ahead, min_gain=min_gain, streams=streams, precision=precision)
+    except ValueError as err:
+        raise click.UsageError(str(err))
+    for i, (name, text, one) in enumerate(zip(names, texts, found)):
+        rows = [[int(a), int(b), text[int(a):int(b)], new, float(g)]
+                for a, b, new, g in zip(one.starts, one.ends, one.proposals(), one.gain)]
+        # (the counts of this file alone: witness_edits on its own alignments)
+        _, skipped = ratebatch.witness_edits(alignments[i], [(0, w) for w in range(len(readings[i]))], [text], [readings[i]])
+        line = {"file": name, "chars": len(text),
+                "witnesses": [{"file": path, "dist": al.dist} for path, al in zip(sources[i], alignments[i])],
+                "rescored": rows, "skipped": skipped}
         if apply_:
             line["corrected"] = one.apply(text)
         click.echo(json.dumps(line, ensure_ascii=False))
