@@ -24,6 +24,7 @@
  *       (the processor's mean probability per TextEquiv substring, wrapper/rate.py:308-317, for a whole corpus)
  *   ... and the suspect words' nearest entries of a lexicon, as replacements   kl_lexicon_neighbours
  *   ... and the spans where a second reading of the text (another OCR engine) differs   kl_align_pairs
+ *   ... and, against ground truth, the table of confusions these spans amount to   kl_confusion_counts
  *   model.predict_on_batch, stateful (1,1) step, :566        kl_forward_window with T = 1
  *   model.predict_on_batch, incremental + states, :631       kl_step_batch
  *   ... once per character of a lattice edge, :796-851       kl_walk_batch_host (all characters of all hypotheses, one call)
@@ -568,6 +569,54 @@ size_t kl_align_pairs_workspace_bytes(size_t P, int max_len, int max_dist);
 int kl_align_pairs(const int32_t* a_pool, size_t n_a, const int64_t* a_off, const int32_t* b_pool, size_t n_b, const int64_t* b_off,
                    size_t P, int max_len, int max_dist, int join, int32_t* dist, int32_t* n_spans, int32_t* spans, void* ws,
                    size_t ws_bytes, void* stream);
+
+/* Confusion counts: which strings of an OCR text were read as which strings of its ground truth, how often, and how often each
+ * such source string stands in the OCR texts at all.  The step behind kl_align_pairs for pairs (a = OCR, b = truth); what it
+ * counts is the table `keraslm-rate rescore --confusions` takes.  No handle.
+ *
+ * Inputs: the texts as kl_align_pairs read them (a_pool, n_a, a_off, b_pool, n_b, b_off, P, max_dist) and what it left on the
+ * device (dist [P], n_spans [P], spans [P][max_dist][4]).  A pair is ACCEPTED if dist[p] >= 0 and its offsets ascend and lie
+ * inside [0, n_a] / [0, n_b]; nothing of any other pair is read.  The span slots s < n_spans[p] of an accepted pair are its spans.
+ *
+ * Record of a span (a0, a1, b0, b1), a and b the pair's texts of n and m symbols:
+ *   fields outside the texts (not 0 <= a0 <= a1 <= n and 0 <= b0 <= b1 <= m)            no record, counted as `long`
+ *   a1 > a0:                          source a[a0:a1], target b[b0:b1] (an empty target: a deletion)
+ *   a1 == a0 > 0:                     the OCR lost characters and a rule needs a source -- anchored on the character in front:
+ *                                     source a[a0-1:a0], target b[b0-1:b1] (the run is maximal: the step before it is a match
+ *                                     and both begin with the same symbol; b0 == 0, which no alignment gives, is `long`)
+ *   a1 == a0 == 0, n > 0:             anchored behind: source a[0:1], target b[0:b1+1] (b1 == m is `long`)
+ *   a1 == a0 == 0, n == 0:            no record, counted as `empty`
+ *   more than max_chars symbols on either side after anchoring: no record, counted as `long`.
+ * Symbols are equal iff they are the same number.
+ *
+ * Table.  The distinct records (src_len, tgt_len, src[4], tgt[4]; unused places 0) in order of first occurrence -- by pair, then
+ * by span --, each with count, the number of spans that gave it, and occ, the number of positions i of the a-texts of all accepted
+ * pairs with a[i:i+src_len] == source: overlapping occurrences count ("aa" stands three times in "aaaa"), none reaches across the
+ * end of its text.  Records with the same source have the same occ, and count <= occ for spans of a true alignment.
+ *
+ * Outputs (device): rules int32 [room][10], count int64 [room], occ int64 [room] hold the first min(R, room) records, every
+ * place behind them -1 in rules and 0 in count and occ; stats int64 [4] = (R: the distinct records however large room is; the
+ * spans that gave a record; `long`; `empty`).  Every output is OVERWRITTEN over its whole room, nothing behind any output or
+ * the workspace is written, and the outputs depend on the inputs only: two calls give the same bytes.  The statement is
+ * ratebulk.confusion_counts_host.
+ *
+ * Eight plain launches on `stream` (confusions.hip): the records of all span slots; an open-addressing table of at least twice
+ * as many slots whose entries are the least span id of a record (atomicCAS to claim, atomicMin and an integer add otherwise); the
+ * ordered compaction of kl_compact.h over the spans that are their record's first; a second table of the distinct sources; a
+ * walk of the accepted a-texts, one lane per position with the lengths 1 .. max_chars, that adds to the source's count; a last
+ * launch that hands the counts to the records.  Integer atomics on global memory only: no sum or minimum depends on the order
+ * of arrival, no lane waits for another.  ws: device scratch of kl_confusion_counts_workspace_bytes(P, max_dist, n_a) bytes (0
+ * for arguments out of range), 8-byte aligned, not to be shared by calls that may overlap.  KL_ERR_ARG, before any launch and
+ * with nothing touched, for null pointers (a pool may be null when its n_* is 0), P < 1 or >= 2^31, max_dist outside
+ * 1 .. KL_ALIGN_DIST_MAX, max_chars outside 1 .. KL_CONFUSION_CHARS_MAX, room < 1 or > 2^40, n_a or n_b > 2^40, misaligned
+ * pointers (offsets, count, occ and stats 8 bytes, the others 4); KL_ERR_WORKSPACE if ws_bytes is too small or ws is not
+ * 8-byte aligned. */
+#define KL_CONFUSION_CHARS_MAX 4
+size_t kl_confusion_counts_workspace_bytes(size_t P, int max_dist, size_t n_a);
+int kl_confusion_counts(const int32_t* a_pool, size_t n_a, const int64_t* a_off, const int32_t* b_pool, size_t n_b,
+                        const int64_t* b_off, size_t P, int max_dist, const int32_t* dist, const int32_t* n_spans,
+                        const int32_t* spans, int max_chars, size_t room, int32_t* rules, int64_t* count, int64_t* occ,
+                        int64_t* stats, void* ws, size_t ws_bytes, void* stream);
 
 /* One training batch, forward + backward (rating.py:292-298 -> train_on_batch):
  * writes the gradient of (mean CE + embedding regularisers, rating.py:187-246)

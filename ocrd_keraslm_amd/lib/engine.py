@@ -98,6 +98,7 @@ class HipLM:
         self._segment_select_ws = None
         self._lexicon_ws = None
         self._align_ws = None
+        self._confusion_ws = None
         self.states = None       # [B][2L][W] implicit state of the stateful streams
         self.pool = None            # [slots][2L][W] explicit states of hypotheses
         self.max_streams_per_launch = 0      # 0: what the kernels address (train_window splits larger batches into groups)
@@ -837,6 +838,33 @@ class HipLM:
             hipabi.check(self.lib.kl_align_pairs(
                 _ptr(a_pool_d), a_pool_d.numel(), _ptr(a_off_d), _ptr(b_pool_d), b_pool_d.numel(), _ptr(b_off_d), P, max_len,
                 max_dist, join, *([_ptr(t) for t in out] + [_ptr(ws), ws.numel(), self._stream()])), "kl_align_pairs")
+        return out
+
+    def confusion_counts(self, a_pool_d, a_off_d, b_pool_d, b_off_d, dist_d, n_spans_d, spans_d, max_chars, room):
+        """kl_confusion_counts: the table of confusions the spans of `align_pairs` amount to (a the OCR, b the truth).  The
+        texts as `align_pairs` took them and the three tensors it returned, all on the DEVICE.  Returns the DEVICE tensors
+        (rules int32 [room, 10], count int64 [room], occ int64 [room], stats int64 [4]); the statement is
+        ratebulk.confusion_counts_host.  hipabi.KlError for what the entry point rejects.  No synchronisation."""
+        torch = self.torch
+        tensors = (a_pool_d, a_off_d, b_pool_d, b_off_d, dist_d, n_spans_d, spans_d)
+        P = a_off_d.numel() - 1
+        if ([t.dtype for t in tensors] != [torch.int32, torch.int64, torch.int32, torch.int64] + [torch.int32] * 3
+                or any(t.dim() != 1 for t in tensors[:6]) or P < 1 or b_off_d.numel() != P + 1 or dist_d.numel() != P
+                or n_spans_d.numel() != P or spans_d.dim() != 3 or spans_d.shape[0] != P or spans_d.shape[2] != 4
+                or not all(t.is_contiguous() and t.is_cuda for t in tensors)):
+            raise hipabi.KlError("confusion_counts: pools int32, offsets int64 [P + 1], dist and n_spans int32 [P], spans int32 "
+                                 "[P, max_dist, 4], contiguous, on the device")
+        max_chars, room, max_dist = int(max_chars), int(room), int(spans_d.shape[1])
+        dev = self.device
+        with self._launch():
+            ws = self._scratch("_confusion_ws", self.lib.kl_confusion_counts_workspace_bytes(P, max_dist, a_pool_d.numel()))
+            rows = max(room, 0)
+            out = (torch.empty((rows, 10), dtype=torch.int32, device=dev), torch.empty(rows, dtype=torch.int64, device=dev),
+                   torch.empty(rows, dtype=torch.int64, device=dev), torch.empty(4, dtype=torch.int64, device=dev))
+            hipabi.check(self.lib.kl_confusion_counts(
+                _ptr(a_pool_d), a_pool_d.numel(), _ptr(a_off_d), _ptr(b_pool_d), b_pool_d.numel(), _ptr(b_off_d), P, max_dist,
+                _ptr(dist_d), _ptr(n_spans_d), _ptr(spans_d), max_chars, rows,
+                *([_ptr(t) for t in out] + [_ptr(ws), ws.numel(), self._stream()])), "kl_confusion_counts")
         return out
 
     def variant_windows(self, corpus_d, offsets_d, text_ctx_d, sel_pos_d, sel_alt_id_d, left, ahead, deletions, T,

@@ -466,6 +466,77 @@ def witness_edits(alignments, pairs, texts, witnesses, max_len=ratebulk.SPAN_LEN
     return [(i, a0, a1, pooled[i, a0, a1]) for i, a0, a1 in sorted(pooled)], skipped
 
 
+class Confusions(object):
+    """What `Rater.confusions` returns: the table of confusions of OCR texts held against their ground truth.
+
+    sources, targets   [R] str   record i: `sources[i]` in the OCR stands for `targets[i]` in the truth ("" for characters the
+                                 OCR added; never an empty source: lost characters are anchored on a neighbour), in order of
+                                 first occurrence
+    count     [R] i64            the spans that gave the record
+    occ       [R] i64            how often its source stands in the OCR texts of the accepted pairs, overlaps included
+    dist      [P] i32            per pair, as `Alignment.dist`
+    chars, edits, cer            truth characters of the accepted pairs (dist >= 0), the sum of their dist, and edits / chars
+                                 (0.0 for no characters): the character error rate
+    skipped   dict               what gave no record: "different" -- pairs with dist < 0 --, "long" -- spans with more than
+                                 max_chars characters on a side --, "empty" -- spans of an empty OCR text
+    spans     int                the spans that gave a record (the sum of count)
+    """
+
+    def __init__(self, rules, count, occ, stats, dist, truth_sizes):
+        rules = np.asarray(rules, dtype=np.int32).reshape(-1, 2 + 2 * ratebulk.CONFUSION_CHARS_MAX)
+        word = lambda symbols: "".join(chr(int(c)) for c in symbols)
+        self.sources = [word(r[2:2 + r[0]]) for r in rules]
+        self.targets = [word(r[2 + ratebulk.CONFUSION_CHARS_MAX:2 + ratebulk.CONFUSION_CHARS_MAX + r[1]]) for r in rules]
+        self.count, self.occ = np.asarray(count, dtype=np.int64), np.asarray(occ, dtype=np.int64)
+        self.dist = np.asarray(dist, dtype=np.int32)
+        accepted = self.dist >= 0
+        self.chars = int(np.asarray(truth_sizes, dtype=np.int64)[accepted].sum())
+        self.edits = int(self.dist[accepted].sum())
+        self.cer = self.edits / self.chars if self.chars else 0.0
+        self.spans = int(stats[1])
+        self.skipped = dict(different=int((~accepted).sum()), long=int(stats[2]), empty=int(stats[3]))
+
+    def __len__(self):
+        return len(self.sources)
+
+    def rate(self, i):
+        """the share of its source's occurrences at which record i was read"""
+        return float(self.count[i]) / float(self.occ[i]) if self.occ[i] else 0.0
+
+    def kept(self, min_count=2, min_rate=0.0, per_source=3):
+        """the records `rules` keeps, as [[indices of one source]]: records below min_count or min_rate dropped, those of a
+        source ordered by (-count, first occurrence) and cut to per_source, the sources by their best record likewise"""
+        by_source = {}
+        for i in range(len(self)):
+            if self.count[i] >= min_count and self.rate(i) >= min_rate:
+                by_source.setdefault(self.sources[i], []).append(i)
+        order = lambda i: (-int(self.count[i]), i)
+        groups = [sorted(rows, key=order)[:max(int(per_source), 0)] for rows in by_source.values()]
+        return sorted([rows for rows in groups if rows], key=lambda rows: order(rows[0]))
+
+    def rules(self, min_count=2, min_rate=0.0, per_source=3):
+        """[(source, [replacements])] as `confusion_edits` and `keraslm-rate rescore --confusions` take them ("" drops the
+        source): see `kept`"""
+        return [(self.sources[rows[0]], [self.targets[i] for i in rows]) for rows in self.kept(min_count, min_rate, per_source)]
+
+    def write(self, file, **same):
+        """`rules(**same)` as the TSV that `keraslm-rate rescore --confusions` reads -- a source, then its replacements, separated
+        by tabs -- to a path or an open text file.  A tab or a line break cannot be written: replacements that hold one are left
+        out, and so is a source that holds one or keeps no replacement.  Returns the number of lines."""
+        unwritable = lambda word: any(c in word for c in "\t\n\r")
+        lines = []
+        for source, replacements in self.rules(**same):
+            replacements = [r for r in replacements if not unwritable(r)]
+            if replacements and not unwritable(source):
+                lines.append("\t".join([source] + replacements) + "\n")
+        if hasattr(file, "write"):
+            file.write("".join(lines))
+        else:
+            with open(file, mode="w") as out:
+                out.write("".join(lines))
+        return len(lines)
+
+
 def confusion_edits(texts, rules, at=None):
     """Edits for `Rater.rescore` from a table of known confusions: rules is a list of (source, [replacements]) with a non-empty
     source; one edit (i, start, end, replacements) per occurrence of a source in the NFC-normalised texts[i], overlapping

@@ -940,3 +940,98 @@ def align_pairs_host(a_pool, a_off, b_pool, b_off, max_len, max_dist, join):
         if found:
             spans[p, :len(found)] = found
     return dist, n_spans, spans
+
+
+CONFUSION_CHARS_MAX = 4      # (KL_CONFUSION_CHARS_MAX of the C ABI)
+
+
+def confusion_counts_host(a_pool, a_off, b_pool, b_off, dist, n_spans, spans, max_chars, room):
+    """what kl_confusion_counts computes: from the pairs of `align_pairs_host` (a the OCR, b the truth) and what it returned --
+    dist [P], n_spans [P], spans [P, max_dist, 4] --, (rules int32 [room, 10], count int64 [room], occ int64 [room], stats
+    int64 [4]).
+
+    A pair is accepted if dist[p] >= 0 and its offsets ascend and lie inside their pools; nothing of another pair is read.  The
+    record of a span (a0, a1, b0, b1) -- the slots s < n_spans[p] -- of an accepted pair with the texts a, b of n, m symbols:
+    fields outside the texts (not 0 <= a0 <= a1 <= n and 0 <= b0 <= b1 <= m) give none and count as `long`; for a1 > a0 source
+    a[a0:a1] and target b[b0:b1]; for a1 == a0 > 0 (the OCR lost characters, a rule needs a source: anchored in front) source
+    a[a0-1:a0] and target b[b0-1:b1], `long` for b0 == 0; for a1 == a0 == 0 and n > 0 (anchored behind) source a[0:1] and target
+    b[0:b1+1], `long` for b1 == m; for a1 == a0 == 0 and n == 0 none, counted as `empty`; more than max_chars symbols on either
+    side after anchoring give none and count as `long`.
+
+    The table holds the distinct records (src_len, tgt_len, src[4], tgt[4]; unused places 0) in order of first occurrence, by
+    pair and then by span, with count -- the spans that gave the record -- and occ -- the positions i of the a-texts of all
+    accepted pairs with a[i:i+src_len] == source, overlapping ones included, none across a text's end.  The outputs hold the
+    first min(R, room) records, behind them -1 in rules and 0 in count and occ; stats = (R, spans that gave a record, long,
+    empty).  Plain Python over the spans and a dictionary: the reference, not fast."""
+    a_pool = np.asarray(a_pool, dtype=np.int32).reshape(-1)
+    b_pool = np.asarray(b_pool, dtype=np.int32).reshape(-1)
+    a_off = np.asarray(a_off, dtype=np.int64).reshape(-1)
+    b_off = np.asarray(b_off, dtype=np.int64).reshape(-1)
+    dist = np.asarray(dist, dtype=np.int32).reshape(-1)
+    n_spans = np.asarray(n_spans, dtype=np.int32).reshape(-1)
+    spans = np.asarray(spans, dtype=np.int32)
+    max_chars, room = int(max_chars), int(room)
+    P = len(a_off) - 1
+    if P < 1 or len(b_off) != P + 1 or len(dist) != P or len(n_spans) != P or spans.ndim != 3 or spans.shape[0] != P or spans.shape[2] != 4:
+        raise ValueError("confusion_counts_host: a_off and b_off [P + 1], dist and n_spans [P], spans [P, max_dist, 4], P >= 1")
+    if not (1 <= spans.shape[1] <= ALIGN_DIST_MAX and 1 <= max_chars <= CONFUSION_CHARS_MAX and room >= 1):
+        raise ValueError("confusion_counts_host: max_dist in 1 .. %d, max_chars in 1 .. %d, room >= 1" % (ALIGN_DIST_MAX, CONFUSION_CHARS_MAX))
+    table = {}            # record -> its row: insertion order is the order of first occurrence
+    counts = []
+    counted = too_long = empty = 0
+    texts = []            # the a-texts of the accepted pairs
+    for p in range(P):
+        a0, a1, b0, b1 = int(a_off[p]), int(a_off[p + 1]), int(b_off[p]), int(b_off[p + 1])
+        if dist[p] < 0 or a0 < 0 or a1 < a0 or a1 > len(a_pool) or b0 < 0 or b1 < b0 or b1 > len(b_pool):
+            continue
+        a, b = a_pool[a0:a1].tolist(), b_pool[b0:b1].tolist()
+        n, m = len(a), len(b)
+        texts.append(a)
+        for a0, a1, b0, b1 in spans[p, :max(int(n_spans[p]), 0)].tolist():
+            if not (0 <= a0 <= a1 <= n and 0 <= b0 <= b1 <= m):
+                too_long += 1
+                continue
+            if a1 > a0:
+                source, target = a[a0:a1], b[b0:b1]
+            elif a0 > 0:
+                if b0 == 0:
+                    too_long += 1
+                    continue
+                source, target = a[a0 - 1:a0], b[b0 - 1:b1]
+            elif n > 0:
+                if b1 == m:
+                    too_long += 1
+                    continue
+                source, target = a[0:1], b[0:b1 + 1]
+            else:
+                empty += 1
+                continue
+            if len(source) > max_chars or len(target) > max_chars:
+                too_long += 1
+                continue
+            counted += 1
+            pad = lambda word: word + [0] * (CONFUSION_CHARS_MAX - len(word))
+            record = tuple([len(source), len(target)] + pad(source) + pad(target))
+            if record not in table:
+                table[record] = len(counts)
+                counts.append(0)
+            counts[table[record]] += 1
+    stands = {}           # (length, symbols) -> occurrences, for the sources of the table only
+    for record in table:
+        stands[record[0], record[2:2 + record[0]]] = 0
+    for a in texts:
+        for i in range(len(a)):
+            for size in range(1, min(max_chars, len(a) - i) + 1):
+                key = (size, tuple(a[i:i + size]))
+                if key in stands:
+                    stands[key] += 1
+    R = len(counts)
+    rules = np.full((room, 2 + 2 * CONFUSION_CHARS_MAX), -1, dtype=np.int32)
+    count = np.zeros(room, dtype=np.int64)
+    occ = np.zeros(room, dtype=np.int64)
+    for record, row in table.items():
+        if row < room:
+            rules[row] = record
+            count[row] = counts[row]
+            occ[row] = stands[record[0], record[2:2 + record[0]]]
+    return rules, count, occ, np.array([R, counted, too_long, empty], dtype=np.int64)

@@ -1852,6 +1852,74 @@ class Rater(object):
             alignments[i].append(one)
         return alignments, rescored, skipped
 
+    _CONFUSION_ROOM = 65536      # rows of the first `confusion_counts` call of `confusions`
+
+    def confusions(self, texts, truths, max_dist=32, join=0, max_chars=4):
+        '''The table of OCR confusions that `texts` (OCR output) amount to when held against `truths` (ground truth of the
+        same lines or pages, one string per side and pair): which strings were read as which, how often, and how often each
+        source stands in the OCR texts at all.  Returns a ratebatch.Confusions; its `rules()` is what `confusion_edits` and
+        `keraslm-rate rescore --confusions` take.
+
+        A record is a differing span of `align(texts, truths, max_dist, join)` -- the OCR's side the source, the truth's the
+        target, "" for characters the OCR added --; where the OCR LOST characters the span is anchored on the character in
+        front (at a text's beginning: behind), so that every rule has a source.  Spans with more than max_chars characters on
+        a side after anchoring, spans of an empty text and pairs further than max_dist edits apart are counted in `skipped`.
+
+        Both sides are normalised and encoded as in `align`: one upload per side.  On the HIP engine `align_pairs` and
+        `confusion_counts` are chained with no download between them, with room for 65536 records -- once more with room for
+        all if there are more: the number of records is read first, eight bytes and the only wait --, and dist, the counts and
+        the R records come back in one transfer.  No pairs give an empty
+        table without a launch.  An engine without `confusion_counts` (the tests' CPU double) runs the numpy statements.
+        ValueError for what `align` raises and for max_chars outside 1 .. 4.'''
+        assert self.status > 1
+        texts, truths = [windows.normalize(t) for t in texts], [windows.normalize(t) for t in truths]
+        max_dist, join, max_chars = int(max_dist), int(join), int(max_chars)
+        if len(texts) != len(truths):
+            raise ValueError("confusions: one truth per text (got %d and %d)" % (len(texts), len(truths)))
+        if not 1 <= max_dist <= ratebulk.ALIGN_DIST_MAX or join < 0:
+            raise ValueError("confusions: max_dist in 1 .. %d and join >= 0 (got %d, %d)" % (ratebulk.ALIGN_DIST_MAX, max_dist, join))
+        if not 1 <= max_chars <= ratebulk.CONFUSION_CHARS_MAX:
+            raise ValueError("confusions: max_chars in 1 .. %d (got %d)" % (ratebulk.CONFUSION_CHARS_MAX, max_chars))
+        P = len(texts)
+        max_len = max([len(t) for t in texts + truths] or [0])
+        if max_len > ratebulk.ALIGN_LEN_MAX:
+            raise ValueError("confusions: a text of %d characters; at most %d -- cut pages into lines or paragraphs"
+                             % (max_len, ratebulk.ALIGN_LEN_MAX))
+        if P == 0:
+            return ratebatch.Confusions(np.full((0, 10), -1, dtype=np.int32), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64),
+                                        np.zeros(4, dtype=np.int64), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int64))
+        sides = []
+        for strings in (texts, truths):
+            off = np.concatenate([[0], np.cumsum([len(t) for t in strings])]).astype(np.int64)
+            sides.append((np.frombuffer("".join(strings).encode("utf-32-le", "surrogatepass"), dtype=np.int32), off))
+        lm = self.model
+        if hasattr(lm, 'confusion_counts'):
+            torch = lm.torch
+            args = []
+            for pool, off in sides:
+                both = torch.from_numpy(np.concatenate([off.view(np.int32), pool])).to(lm.device)
+                args += [both[2 * (P + 1):], both[:2 * (P + 1)].view(torch.int64)]
+            aligned = lm.align_pairs(*args, max_len, max_dist, join)
+            room = self._CONFUSION_ROOM
+            rules, count, occ, stats = lm.confusion_counts(*args, *aligned, max_chars, room)
+            R = int(stats[0].item())
+            if R > room:
+                rules, count, occ, stats = lm.confusion_counts(*args, *aligned, max_chars, R)
+            out = _np(torch.cat([aligned[0].to(torch.int64), stats, count[:R], occ[:R], rules[:R].reshape(-1).to(torch.int64)]))
+            dist, stats, count, occ = out[:P].astype(np.int32), out[P:P + 4], out[P + 4:P + 4 + R], out[P + 4 + R:P + 4 + 2 * R]
+            rules = out[P + 4 + 2 * R:].astype(np.int32).reshape(R, 10)
+        else:
+            aligned = ratebulk.align_pairs_host(sides[0][0], sides[0][1], sides[1][0], sides[1][1], max_len, max_dist, join)
+            dist = aligned[0]
+            rules, count, occ, stats = ratebulk.confusion_counts_host(sides[0][0], sides[0][1], sides[1][0], sides[1][1], *aligned,
+                                                                      max_chars, self._CONFUSION_ROOM)
+            if stats[0] > self._CONFUSION_ROOM:
+                rules, count, occ, stats = ratebulk.confusion_counts_host(sides[0][0], sides[0][1], sides[1][0], sides[1][1], *aligned,
+                                                                          max_chars, int(stats[0]))
+            R = int(stats[0])
+            rules, count, occ = rules[:R], count[:R], occ[:R]
+        return ratebatch.Confusions(rules, count, occ, stats, dist, np.array([len(t) for t in truths], dtype=np.int64))
+
     def _contexts_per_text(self, contexts, n):
         '''None, one context list for all texts, or one per text -> one list per text (as `rate_batch` reads them)'''
         if contexts is None or len(contexts) == 0:

@@ -27,6 +27,11 @@ lexicon_neighbours -> rescore); output as `rescore`'s, --apply also gives the co
 Additional command `witnesses`: every DATA file aligned with other readings of it (--witness DIR: the file of the same base
 name) on the device, and the readings of the spans where they differ rated against the text around them
 (Rater.merge_witnesses: align -> witness_edits -> rescore); --apply also gives the corrected text.
+Additional command `confusions`: every DATA file (OCR output) aligned with its ground truth (--truth DIR: the file of the same
+base name) on the device, and the differences counted there into a table of confusions -- which strings were read as which, how
+often, and how often the source stands in the OCR at all (Rater.confusions: align_pairs -> confusion_counts); the table goes to
+stdout as the TSV that `rescore --confusions` reads, or with --counts as one JSON line per record; pairs, skipped spans and the
+character error rate go to stderr.
 Additional options on `train`: --streams (stateful streams per GPU, default 1 = the
 reference's batching) and --segment-streams (with fewer files than streams, cut the files
 into contiguous segments on window boundaries, one list of segments per stream).  Under `python -m torch.distributed.run` training is
@@ -43,7 +48,7 @@ import click
 
 from .. import lib
 
-COMMAND_ORDER = ['train', 'test', 'score', 'suspects', 'correct', 'rescore', 'contexts', 'words', 'lexicon', 'witnesses', 'apply', 'generate', 'print-history', 'print-charset', 'prune-charset',
+COMMAND_ORDER = ['train', 'test', 'score', 'suspects', 'correct', 'rescore', 'contexts', 'words', 'lexicon', 'witnesses', 'confusions', 'apply', 'generate', 'print-history', 'print-charset', 'prune-charset',
                  'plot-char-embeddings-similarity', 'plot-context-embeddings-similarity', 'plot-context-embeddings-projection']
 
 
@@ -683,6 +688,59 @@ def witnesses_(model, witness_dirs, max_dist, join, streams, precision, left, ah
         if apply_:
             line["corrected"] = one.apply(text)
         click.echo(json.dumps(line, ensure_ascii=False))
+
+
+@cli.command('confusions', short_help='count the confusions of OCR files against their ground truth')
+@click.option('-m', '--model', default="model.h5", show_default=True, help='model file', type=click.Path(dir_okay=False, exists=True))
+@click.option('--truth', 'truth_dir', required=True, type=click.Path(file_okay=False, exists=True),
+              help='directory of ground truth: the truth of a DATA file is the file of the same base name (a file without one is left out)')
+@click.option('--max-dist', default=32, show_default=True, type=click.IntRange(min=1, max=255),
+              help='a file further than this many edits from its truth is not a reading of it')
+@click.option('--join', default=0, show_default=True, type=click.IntRange(min=0),
+              help='differences with at most this many equal characters between them are one span')
+@click.option('--max-chars', default=4, show_default=True, type=click.IntRange(min=1, max=4),
+              help='characters of a source and of a replacement at most')
+@click.option('--min-count', default=2, show_default=True, type=click.IntRange(min=0), help='a rule was seen at least this often')
+@click.option('--min-rate', default=0.0, show_default=True, type=click.FLOAT,
+              help='... and at no less than this share of the occurrences of its source')
+@click.option('--per-source', default=3, show_default=True, type=click.IntRange(min=1), help='replacements of a source at most')
+@click.option('--counts', is_flag=True, default=False,
+              help='one JSON line per kept record (source, target, count, occ, rate) instead of the TSV')
+@click.argument('data', nargs=-1, type=click.Path(exists=True, dir_okay=True, file_okay=True))
+def confusions_(model, truth_dir, max_dist, join, max_chars, min_count, min_rate, per_source, counts, data):
+    """Align every DATA file -- OCR output -- with its ground truth, the file of the same base name in
+       --truth, count the differences and print the table of confusions: TSV lines of a source and its
+       replacements, the most frequent first, as `rescore --confusions` reads them (an empty field drops the
+       source).  With --counts one JSON line per kept record instead.  A last line on stderr gives the
+       pairs, what was skipped (files further than --max-dist from their truth: "different"; spans of more
+       than --max-chars characters: "long"; spans of an empty file: "empty"), the truth's characters, the
+       edits and the character error rate.  A file of more than 4096 characters is an error: cut pages
+       into lines.
+    """
+    from ..lib import windows
+    rater = _load(model)
+    texts, truths = [], []
+    for file in _open_all(data):
+        with file:
+            text = windows.normalize(file.read())
+        path = os.path.join(truth_dir, os.path.basename(file.name))
+        if os.path.isfile(path):
+            with open(path, mode='r') as other:
+                truths.append(windows.normalize(other.read()))
+            texts.append(text)
+    try:
+        found = rater.confusions(texts, truths, max_dist=max_dist, join=join, max_chars=max_chars)
+    except ValueError as err:
+        raise click.UsageError(str(err))
+    same = dict(min_count=min_count, min_rate=min_rate, per_source=per_source)
+    if counts:
+        for rows in found.kept(**same):
+            for i in rows:
+                click.echo(json.dumps({"source": found.sources[i], "target": found.targets[i], "count": int(found.count[i]),
+                                       "occ": int(found.occ[i]), "rate": found.rate(i)}, ensure_ascii=False))
+    else:
+        found.write(click.get_text_stream('stdout'), **same)
+    click.echo(json.dumps(dict(found.skipped, pairs=len(texts), chars=found.chars, edits=found.edits, cer=found.cer)), err=True)
 
 
 @cli.command(short_help='sample characters from language model')
