@@ -25,6 +25,7 @@
  *   ... and the suspect words' nearest entries of a lexicon, as replacements   kl_lexicon_neighbours
  *   ... and the spans where a second reading of the text (another OCR engine) differs   kl_align_pairs
  *   ... and, against ground truth, the table of confusions these spans amount to   kl_confusion_counts
+ *   ... and, with several such readings, their spans clustered and the readings counted   kl_witness_clusters, kl_witness_pool
  *   model.predict_on_batch, stateful (1,1) step, :566        kl_forward_window with T = 1
  *   model.predict_on_batch, incremental + states, :631       kl_step_batch
  *   ... once per character of a lattice edge, :796-851       kl_walk_batch_host (all characters of all hypotheses, one call)
@@ -617,6 +618,72 @@ int kl_confusion_counts(const int32_t* a_pool, size_t n_a, const int64_t* a_off,
                         const int64_t* b_off, size_t P, int max_dist, const int32_t* dist, const int32_t* n_spans,
                         const int32_t* spans, int max_chars, size_t room, int32_t* rules, int64_t* count, int64_t* occ,
                         int64_t* stats, void* ws, size_t ws_bytes, void* stream);
+
+/* Witness consensus: the differing spans of ALL witnesses of a text clustered, every witness read over a whole cluster, equal
+ * readings made one and counted -- the step between kl_align_pairs and kl_span_windows, whose span and candidate arrays it leaves
+ * on the device.  No handle.
+ *
+ * Inputs: side b as kl_align_pairs read it (b_pool, n_b, b_off, P, max_dist) and what it left on the device (dist [P], n_spans
+ * [P], spans [P][max_dist][4]); pair_first (device int64 [n_texts + 1], ascending from 0 to P): text i owns the pairs
+ * pair_first[i] .. pair_first[i+1]-1, its witnesses w = 0, 1, .. in that order, all aligned with that text as side a (a text
+ * may own none); text_off (device int64 [n_texts + 1]): the texts' offsets in kl_span_windows' corpus, n_i = text_off[i+1] -
+ * text_off[i]; join as kl_align_pairs took it.
+ *
+ * A text whose pair range does not lie in [0, P] in ascending order, or holds more than KL_WITNESS_MAX pairs, is counted in
+ * stats[7] and nothing of it is read: pair_first lies on the device, so the entry point cannot refuse it -- a caller that wants
+ * the error compares stats[7] with 0.  A pair q of any other text is ACCEPTED if dist[q] >= 0, b_off[q] <= b_off[q+1] lie inside
+ * [0, n_b] (m_q their difference), 0 <= n_spans[q] <= max_dist, and every slot s < n_spans[q] has 0 <= a0 <= a1 <= n_i,
+ * 0 <= b0 <= b1 <= m_q, a0 >= the previous slot's a1 and b0 >= its b1.  Every other pair is counted as `different`, and nothing
+ * more of it is read.  kl_align_pairs never leaves a pair with dist >= 0 that fails the rest.
+ *
+ * Clusters of text i.  Take the spans (a0, a1) of its accepted pairs in order of (a0, a1, witness, slot) and sweep with a running
+ * end E: a span opens a cluster iff a0 > E + join, else it joins the current one and E = max(E, a1).  The cluster is [u0, u1) =
+ * [least a0, greatest a1): two differences with at most `join` equal characters between them are one -- kl_align_pairs' rule,
+ * across witnesses --, spans that touch and insertions at the same place chain.
+ * Reading.  The spans of witness w in a cluster are a run f .. l of its slots; without one it agrees with the text as written.
+ * Else it reads b[bs:be) for text[u0:u1], bs = b0_f - (a0_f - u0), be = b1_l + (u1 - a1_l): outside its spans an alignment is
+ * matches.
+ * Candidates and votes.  The candidates of a cluster are its distinct readings, compared as symbols of b_pool, in order of the
+ * first witness that gives one; a candidate's votes are the accepted witnesses that read it, the votes of the text as written 1
+ * plus the accepted witnesses without a span in the cluster: a cluster's votes sum to 1 plus the text's accepted witnesses.
+ * Dropped, and counted: `first`, a cluster with u0 == 0 (no prediction to be held against); else `long`, one with u1 - u0 >
+ * KL_SPAN_LEN_MAX, a reading longer than that, or a reading range outside [0, m_q] (which no true alignment gives).
+ *
+ * Outputs (device), with R = P * max_dist the room -- clusters and candidates are each at most the spans there are --: the S
+ * kept clusters ordered by text and u0 as kl_span_windows' spans, span_text int32 [R], span_start int64 [R] (text_off[i] + u0),
+ * span_len int32 [R], span_first int64 [R + 1]; their C candidates, cand_src int64 [R] (the first position of the reading of
+ * the first witness in b_pool) and cand_off int64 [R + 1] (the offsets of kl_witness_pool's pool); votes int32 [2 R] in
+ * kl_span_windows' ROW numbering (row span_first[s] + s the text as written, then the span's candidates); stats int64 [8] = (S,
+ * C, n_pool = cand_off[C], M: the longest kept span or reading, `different`, `first`, `long`, texts with a bad pair range).
+ * Every output is OVERWRITTEN over its whole room: behind the used places -1, in votes and behind span_first[S] and cand_off[C]
+ * 0.  Nothing behind an output or the workspace is written, and the outputs depend on the inputs only: two calls give the same
+ * bytes.  The statement is ratebulk.witness_clusters_host.
+ *
+ * Four plain launches on `stream` (witnesses.hip): the fills; one WAVE per text, a lane per witness, that merges the lanes' span
+ * slots by minima and maxima over the wave and settles equal readings by ballots, counting per text; kl_compact.h's one
+ * workgroup that turns the counts into offsets and writes stats; the same sweep again, placing.  Integer atomics only, one per
+ * wave and reason for the sums and the maximum of stats; no address outside the arrays is formed whatever bytes dist, n_spans,
+ * spans or the offsets hold.  ws: device scratch of kl_witness_clusters_workspace_bytes(P, max_dist, n_texts) bytes (0 for
+ * arguments out of range), 8-byte aligned, not to be shared by calls that may overlap.  KL_ERR_ARG, before any launch and with
+ * nothing touched, for null pointers (b_pool may be null when n_b is 0), P or n_texts < 1 or >= 2^31, max_dist outside
+ * 1 .. KL_ALIGN_DIST_MAX, join < 0, n_b > 2^40, misaligned pointers (the offsets, span_start, span_first, cand_src, cand_off
+ * and stats 8 bytes, the others 4); KL_ERR_WORKSPACE if ws_bytes is too small or ws is not 8-byte aligned.
+ *
+ * kl_witness_pool: the candidates as ids.  pool[cand_off[c] + k] = b_ids[cand_src[c] + k] for c < C (device int32 [n_pool]; b_ids
+ * device int32 [n_b], the witnesses encoded with the caller's mapping, parallel to b_pool; cand_off [C + 1] ascending from 0 to
+ * n_pool, else which candidate a place is read from is undefined -- but every place of pool is written and no other).  A
+ * position outside [0, n_b) reads as 0 without touching memory.  One launch, a lane per place; n_pool == 0 launches nothing.
+ * KL_ERR_ARG for null pointers (b_ids with n_b == 0 and pool with n_pool == 0 may be null), C < 1, C, n_b or n_pool > 2^40,
+ * misaligned pointers. */
+#define KL_WITNESS_MAX 64
+size_t kl_witness_clusters_workspace_bytes(size_t P, int max_dist, size_t n_texts);
+int kl_witness_clusters(const int32_t* b_pool, size_t n_b, const int64_t* b_off, size_t P, int max_dist, const int32_t* dist,
+                        const int32_t* n_spans, const int32_t* spans, const int64_t* pair_first, const int64_t* text_off,
+                        size_t n_texts, int join, int32_t* span_text, int64_t* span_start, int32_t* span_len, int64_t* span_first,
+                        int64_t* cand_src, int64_t* cand_off, int32_t* votes, int64_t* stats, void* ws, size_t ws_bytes,
+                        void* stream);
+int kl_witness_pool(const int32_t* b_ids, size_t n_b, const int64_t* cand_src, const int64_t* cand_off, size_t C, int32_t* pool,
+                    size_t n_pool, void* stream);
 
 /* One training batch, forward + backward (rating.py:292-298 -> train_on_batch):
  * writes the gradient of (mean CE + embedding regularisers, rating.py:187-246)

@@ -99,6 +99,7 @@ class HipLM:
         self._lexicon_ws = None
         self._align_ws = None
         self._confusion_ws = None
+        self._witness_ws = None
         self.states = None       # [B][2L][W] implicit state of the stateful streams
         self.pool = None            # [slots][2L][W] explicit states of hypotheses
         self.max_streams_per_launch = 0      # 0: what the kernels address (train_window splits larger batches into groups)
@@ -866,6 +867,55 @@ class HipLM:
                 _ptr(dist_d), _ptr(n_spans_d), _ptr(spans_d), max_chars, rows,
                 *([_ptr(t) for t in out] + [_ptr(ws), ws.numel(), self._stream()])), "kl_confusion_counts")
         return out
+
+    def witness_clusters(self, b_pool_d, b_off_d, dist_d, n_spans_d, spans_d, pair_first_d, text_off_d, join):
+        """kl_witness_clusters: the differing spans of all witnesses of a text clustered, the witnesses' readings of every
+        cluster made distinct and counted.  Side b as `align_pairs` took it and the three tensors it returned, pair_first_d and
+        text_off_d int64 [n_texts + 1] (the pairs of every text; the texts' offsets in `span_windows`' corpus), all on the
+        DEVICE.  With R = P * max_dist returns the DEVICE tensors (span_text int32 [R], span_start int64 [R], span_len int32
+        [R], span_first int64 [R + 1], cand_src int64 [R], cand_off int64 [R + 1], votes int32 [2 R], stats int64 [8]); the
+        statement is ratebulk.witness_clusters_host.  hipabi.KlError for what the entry point rejects.  No synchronisation."""
+        torch = self.torch
+        tensors = (b_pool_d, b_off_d, dist_d, n_spans_d, spans_d, pair_first_d, text_off_d)
+        P = b_off_d.numel() - 1
+        if ([t.dtype for t in tensors] != [torch.int32, torch.int64] + [torch.int32] * 3 + [torch.int64] * 2
+                or any(t.dim() != 1 for t in tensors[:4] + tensors[5:]) or P < 1 or dist_d.numel() != P or n_spans_d.numel() != P
+                or spans_d.dim() != 3 or spans_d.shape[0] != P or spans_d.shape[2] != 4 or pair_first_d.numel() < 2
+                or text_off_d.numel() != pair_first_d.numel() or not all(t.is_contiguous() and t.is_cuda for t in tensors)):
+            raise hipabi.KlError("witness_clusters: b_pool int32, b_off int64 [P + 1], dist and n_spans int32 [P], spans int32 "
+                                 "[P, max_dist, 4], pair_first and text_off int64 [n_texts + 1], contiguous, on the device")
+        max_dist, join, n_texts = int(spans_d.shape[1]), int(join), pair_first_d.numel() - 1
+        R = P * max_dist
+        dev, i32, i64 = self.device, torch.int32, torch.int64
+        with self._launch():
+            ws = self._scratch("_witness_ws", self.lib.kl_witness_clusters_workspace_bytes(P, max_dist, n_texts))
+            out = tuple(torch.empty(n, dtype=kind, device=dev)
+                        for n, kind in ((R, i32), (R, i64), (R, i32), (R + 1, i64), (R, i64), (R + 1, i64), (2 * R, i32), (8, i64)))
+            hipabi.check(self.lib.kl_witness_clusters(
+                _ptr(b_pool_d), b_pool_d.numel(), _ptr(b_off_d), P, max_dist, _ptr(dist_d), _ptr(n_spans_d), _ptr(spans_d),
+                _ptr(pair_first_d), _ptr(text_off_d), n_texts, join,
+                *([_ptr(t) for t in out] + [_ptr(ws), ws.numel(), self._stream()])), "kl_witness_clusters")
+        return out
+
+    def witness_pool(self, b_ids_d, cand_src_d, cand_off_d, C, n_pool):
+        """kl_witness_pool: the C candidates of `witness_clusters` as ids -- pool[cand_off[c] + k] = b_ids[cand_src[c] + k].
+        b_ids_d int32 [n_b] (the witnesses encoded with the rater's mapping, parallel to b_pool), cand_src_d int64 (at least C)
+        and cand_off_d int64 (at least C + 1) on the DEVICE; C and n_pool as `witness_clusters`' stats gave them.  Returns the
+        DEVICE tensor pool int32 [n_pool]: what ratebulk.witness_pool_host states.  No synchronisation."""
+        torch = self.torch
+        tensors = (b_ids_d, cand_src_d, cand_off_d)
+        C, n_pool = int(C), int(n_pool)
+        if ([t.dtype for t in tensors] != [torch.int32, torch.int64, torch.int64] or any(t.dim() != 1 for t in tensors)
+                or not all(t.is_contiguous() and t.is_cuda for t in tensors) or C < 1 or n_pool < 0
+                or cand_src_d.numel() < C or cand_off_d.numel() < C + 1):
+            raise hipabi.KlError("witness_pool: b_ids int32, cand_src int64 [C ..], cand_off int64 [C + 1 ..], contiguous, on the "
+                                 "device, C >= 1, n_pool >= 0")
+        with self._launch():
+            pool = torch.empty(n_pool, dtype=torch.int32, device=self.device)
+            hipabi.check(self.lib.kl_witness_pool(_ptr(b_ids_d) if b_ids_d.numel() else None, b_ids_d.numel(), _ptr(cand_src_d),
+                                                  _ptr(cand_off_d), C, _ptr(pool) if n_pool else None, n_pool, self._stream()),
+                         "kl_witness_pool")
+        return pool
 
     def variant_windows(self, corpus_d, offsets_d, text_ctx_d, sel_pos_d, sel_alt_id_d, left, ahead, deletions, T,
                         insertions=False):

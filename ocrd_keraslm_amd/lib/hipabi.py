@@ -21,6 +21,7 @@ KL_CTX_CAND_MAX = 256    # candidate contexts of kl_rate_scatter_planes / kl_con
 KL_LEXICON_V_MAX, KL_LEXICON_DIST_MAX, KL_LEXICON_K_MAX = 4096, 8, 16      # kl_lexicon_neighbours: ids, max_dist and K at most
 KL_ALIGN_DIST_MAX, KL_ALIGN_LEN_MAX = 255, 4096      # kl_align_pairs: max_dist and symbols of a text at most
 KL_CONFUSION_CHARS_MAX = 4      # kl_confusion_counts: symbols of a source and of a target at most
+KL_WITNESS_MAX = 64      # kl_witness_clusters: witnesses (pairs) of a text at most
 KL_RATE_SELECT_BLOCK = 1024          # positions per workgroup of kl_rate_select
 KL_RATE_SELECT_SCAN_THREADS = 256    # ... and blocks per round of its one offsets workgroup
 KL_SAMPLE_MAX_ROWS = 1024  # chains per kl_sample_pick call
@@ -161,6 +162,10 @@ SIGNATURES = {
     "kl_confusion_counts": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "kl_witness_clusters_workspace_bytes": (C.c_size_t, [C.c_size_t, C.c_int, C.c_size_t]),
+    "kl_witness_clusters": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_size_t, C.c_int] + [C.c_void_p] * 9 + [C.c_size_t, C.c_void_p]),
+    "kl_witness_pool": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "kl_train_window": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "kl_assemble_windows": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,

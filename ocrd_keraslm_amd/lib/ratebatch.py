@@ -466,6 +466,22 @@ def witness_edits(alignments, pairs, texts, witnesses, max_len=ratebulk.SPAN_LEN
     return [(i, a0, a1, pooled[i, a0, a1]) for i, a0, a1 in sorted(pooled)], skipped
 
 
+class Consensus(Rescored):
+    """One text's share of `Rater.consensus`: a `Rescored` whose m spans are the clusters of its witnesses' differences, ascending,
+    and whose candidates are the witnesses' distinct readings of a whole cluster, in order of the first witness that gives one.
+    cost0 and cost are SCORES: the reading's bits minus vote_bits per vote (with vote_bits = 0.0 the model's bits alone); `gain`
+    is the score of the text as written minus the best score.  In addition:
+
+    votes0   [m] i32          1 (the text itself) plus the accepted witnesses that agree with the text over the span
+    votes    [first[m]] i32   the accepted witnesses that read the candidate; a span's votes sum to 1 plus the text's accepted
+                              witnesses
+    """
+
+    def __init__(self, starts, ends, first, candidates, cost0, cost, best, gain, votes0, votes):
+        Rescored.__init__(self, starts, ends, first, candidates, cost0, cost, best, gain)
+        self.votes0, self.votes = votes0, votes
+
+
 class Confusions(object):
     """What `Rater.confusions` returns: the table of confusions of OCR texts held against their ground truth.
 

@@ -1035,3 +1035,135 @@ def confusion_counts_host(a_pool, a_off, b_pool, b_off, dist, n_spans, spans, ma
             count[row] = counts[row]
             occ[row] = stands[record[0], record[2:2 + record[0]]]
     return rules, count, occ, np.array([R, counted, too_long, empty], dtype=np.int64)
+
+
+WITNESS_MAX = 64      # witnesses of a text at most (KL_WITNESS_MAX of the C ABI)
+
+
+def witness_clusters_host(b_pool, b_off, dist, n_spans, spans, pair_first, text_off, join):
+    """what kl_witness_clusters computes: the differing spans of ALL witnesses of a text clustered, every witness read over a
+    whole cluster, equal readings made one and counted.  b_pool [n_b] int32 and b_off [P + 1] are the witnesses as
+    `align_pairs_host` read them (side b), dist [P], n_spans [P], spans [P, max_dist, 4] what it returned; pair_first
+    [n_texts + 1] (ascending from 0 to P) gives text i the pairs pair_first[i] .. pair_first[i+1]-1, its witnesses w = 0, 1, ..
+    in order, all with that text as side a; text_off [n_texts + 1] are the texts' offsets in `span_windows_host`'s corpus,
+    n_i = text_off[i+1] - text_off[i].  With R = P * max_dist returns (span_text int32 [R], span_start int64 [R], span_len
+    int32 [R], span_first int64 [R + 1], cand_src int64 [R], cand_off int64 [R + 1], votes int32 [2 R], stats int64 [8]).
+
+    A text whose pair range does not lie in [0, P] in ascending order, or holds more than WITNESS_MAX pairs, is counted in
+    stats[7] and nothing of it is read.  A pair q of any other text is ACCEPTED if dist[q] >= 0, b_off[q] <= b_off[q+1] lie in
+    [0, n_b] (m_q their difference), 0 <= n_spans[q] <= max_dist, and every slot s < n_spans[q] has 0 <= a0 <= a1 <= n_i,
+    0 <= b0 <= b1 <= m_q, a0 >= the previous slot's a1 and b0 >= its b1; every other pair counts as `different` and nothing
+    more of it is read.
+
+    Clusters of text i: the spans (a0, a1) of its accepted pairs in order of (a0, a1, witness, slot), swept with a running end
+    E: a span opens a cluster iff a0 > E + join, else it joins the current one and E = max(E, a1); the cluster is [u0, u1) =
+    [least a0, greatest a1).  The spans of witness w in a cluster are a run f .. l of its slots -- none: it agrees with the text
+    as written --, and its reading of text[u0:u1] is b[bs:be) with bs = b0_f - (a0_f - u0), be = b1_l + (u1 - a1_l).  The
+    candidates of a cluster are the distinct readings, compared as code points, in order of the first witness that gives one;
+    the votes of a candidate are the accepted witnesses that read it, those of the text as written 1 plus the accepted
+    witnesses without a span in the cluster.  A cluster with u0 == 0 is dropped and counted as `first`; otherwise one with
+    u1 - u0 > SPAN_LEN_MAX, a reading longer than that or a reading range outside [0, m_q] as `long`.
+
+    The S kept clusters, ordered by text and u0, are `span_windows_host`'s spans: span_text, span_start = text_off[i] + u0,
+    span_len, span_first [S + 1]; candidate c is b_pool[cand_src[c] : cand_src[c] + cand_off[c+1] - cand_off[c]] (cand_src
+    the first witness' position in the pool, cand_off [C + 1] the offsets `witness_pool_host` fills); votes in ROW numbering --
+    row span_first[s] + s the text as written, then the span's candidates.  Behind the used places -1, in votes and the two
+    offset arrays 0.  stats = (S, C, n_pool = cand_off[C], the longest kept span or reading, different, first, long, texts
+    with a bad pair range).  Plain Python over the spans: the reference, not fast."""
+    b_pool = np.asarray(b_pool, dtype=np.int32).reshape(-1)
+    b_off = np.asarray(b_off, dtype=np.int64).reshape(-1)
+    dist = np.asarray(dist, dtype=np.int32).reshape(-1)
+    n_spans = np.asarray(n_spans, dtype=np.int32).reshape(-1)
+    spans = np.asarray(spans, dtype=np.int32)
+    pair_first = np.asarray(pair_first, dtype=np.int64).reshape(-1)
+    text_off = np.asarray(text_off, dtype=np.int64).reshape(-1)
+    join = int(join)
+    P, n_texts = len(b_off) - 1, len(pair_first) - 1
+    if P < 1 or len(dist) != P or len(n_spans) != P or spans.ndim != 3 or spans.shape[0] != P or spans.shape[2] != 4:
+        raise ValueError("witness_clusters_host: b_off [P + 1], dist and n_spans [P], spans [P, max_dist, 4], P >= 1")
+    if n_texts < 1 or len(text_off) != n_texts + 1 or not 1 <= spans.shape[1] <= ALIGN_DIST_MAX or join < 0:
+        raise ValueError("witness_clusters_host: pair_first and text_off [n_texts + 1], n_texts >= 1, max_dist in 1 .. %d, join >= 0"
+                         % ALIGN_DIST_MAX)
+    K, n_b = spans.shape[1], len(b_pool)
+    R = P * K
+    span_text, span_len = np.full(R, -1, dtype=np.int32), np.full(R, -1, dtype=np.int32)
+    span_start, cand_src = np.full(R, -1, dtype=np.int64), np.full(R, -1, dtype=np.int64)
+    span_first, cand_off = np.zeros(R + 1, dtype=np.int64), np.zeros(R + 1, dtype=np.int64)
+    votes = np.zeros(2 * R, dtype=np.int32)
+    S = C = n_pool = longest = different = first = too_long = bad = 0
+    for i in range(n_texts):
+        q0, q1 = int(pair_first[i]), int(pair_first[i + 1])
+        if q0 < 0 or q1 < q0 or q1 > P or q1 - q0 > WITNESS_MAX:
+            bad += 1
+            continue
+        n_i = int(text_off[i + 1]) - int(text_off[i])
+        accepted, items = {}, []      # witness -> (where its text begins in the pool, m_q, its slots)
+        for w, q in enumerate(range(q0, q1)):
+            lo, hi = int(b_off[q]), int(b_off[q + 1])
+            m = hi - lo
+            slots = spans[q, :max(int(n_spans[q]), 0)].tolist() if 0 <= n_spans[q] <= K else None
+            ok = dist[q] >= 0 and 0 <= lo <= hi <= n_b and slots is not None
+            end_a = end_b = 0
+            for a0, a1, b0, b1 in slots or []:
+                ok = ok and end_a <= a0 <= a1 <= n_i and end_b <= b0 <= b1 <= m
+                end_a, end_b = a1, b1
+            if not ok:
+                different += 1
+                continue
+            accepted[w] = (lo, m, slots)
+            items += [(a0, a1, w, s) for s, (a0, a1, _, _) in enumerate(slots)]
+        clusters = []      # [u0, u1, {witness: [f, l]}]
+        for a0, a1, w, s in sorted(items):
+            if not clusters or a0 > clusters[-1][1] + join:
+                clusters.append([a0, a1, {}])
+            one = clusters[-1]
+            one[1] = max(one[1], a1)
+            one[2].setdefault(w, [s, s])[1] = s
+        for u0, u1, runs in clusters:
+            if u0 == 0:
+                first += 1
+                continue
+            readings = []      # (position in the pool, length, witness) of every witness with a run
+            fits = u1 - u0 <= SPAN_LEN_MAX
+            for w in sorted(runs):
+                lo, m, slots = accepted[w]
+                f, l = runs[w]
+                bs, be = slots[f][2] - (slots[f][0] - u0), slots[l][3] + (u1 - slots[l][1])
+                fits = fits and 0 <= bs and be <= m and be - bs <= SPAN_LEN_MAX
+                readings.append((lo + bs, be - bs))
+            if not fits:
+                too_long += 1
+                continue
+            distinct = {}      # code points -> [position of the first, length, votes]: insertion order is the order of first witnesses
+            for at, size in readings:
+                distinct.setdefault(tuple(b_pool[at:at + size].tolist()), [at, size, 0])[2] += 1
+            span_text[S], span_start[S], span_len[S], span_first[S] = i, int(text_off[i]) + u0, u1 - u0, C
+            votes[C + S] = 1 + len(accepted) - len(runs)
+            longest = max(longest, u1 - u0)
+            for at, size, count in distinct.values():
+                cand_src[C], cand_off[C] = at, n_pool
+                votes[C + S + 1] = count
+                n_pool += size
+                longest = max(longest, size)
+                C += 1
+            S += 1
+    span_first[S], cand_off[C] = C, n_pool
+    return (span_text, span_start, span_len, span_first, cand_src, cand_off, votes,
+            np.array([S, C, n_pool, longest, different, first, too_long, bad], dtype=np.int64))
+
+
+def witness_pool_host(b_ids, cand_src, cand_off, C, n_pool):
+    """what kl_witness_pool computes: pool int32 [n_pool] with pool[cand_off[c] + k] = b_ids[cand_src[c] + k] for the candidates
+    c < C of `witness_clusters_host` (cand_off [C + 1] ascending from 0 to n_pool): the readings as ids of the rater's mapping,
+    b_ids [n_b] parallel to the code points the readings were compared by.  A position outside [0, n_b) reads as 0."""
+    b_ids = np.asarray(b_ids, dtype=np.int32).reshape(-1)
+    cand_src = np.asarray(cand_src, dtype=np.int64).reshape(-1)
+    cand_off = np.asarray(cand_off, dtype=np.int64).reshape(-1)
+    C, n_pool = int(C), int(n_pool)
+    if C < 1 or n_pool < 0 or len(cand_src) < C or len(cand_off) < C + 1:
+        raise ValueError("witness_pool_host: C >= 1, n_pool >= 0, cand_src [C], cand_off [C + 1]")
+    g = np.arange(n_pool, dtype=np.int64)
+    c = np.clip(np.searchsorted(cand_off[:C + 1], g, side="right") - 1, 0, C - 1)      # the last c with cand_off[c] <= g
+    at = cand_src[c] + g - cand_off[c]
+    inside = (at >= 0) & (at < len(b_ids))
+    return np.where(inside, b_ids[np.where(inside, at, 0)] if len(b_ids) else 0, 0).astype(np.int32)

@@ -955,6 +955,35 @@ class Rater(object):
                 return -np.where(y >= 0, np.log2(np.maximum(p, 1e-99)), 0.0).sum(axis=1)
         return rate
 
+    def _span_row_costs(self, source, spans, chunks, precision, left, ahead, M, T):
+        '''The chunk loop of `rescore` and `consensus`: the hypothesis rows of `chunks` (`ratebulk.span_chunks`: all S + C rows
+        of the spans, in order) built, rated from zero states and their costs gathered.  source = [corpus, offsets, text_ctx or
+        None] and spans = [span_text, span_start, span_len, span_first, pool, cand_off] are DEVICE tensors on the HIP engine --
+        one `span_windows`, one `reset_states` and one window of `_row_costs` per chunk, the rows' f64 bits into one device
+        array, no synchronisation -- and host arrays on an engine without `span_windows` (the tests' CPU double), which runs
+        `ratebulk.span_windows_host`.  Returns (cost f64 [S + C], valid int32 [S + C]), device tensors or arrays alike.'''
+        lm = self.model
+        rate = self._row_costs(precision)
+        if hasattr(lm, 'span_windows'):
+            torch = lm.torch
+            rows = chunks[-1][1]
+            cost_d = torch.empty(rows, dtype=torch.float64, device=lm.device)
+            valid_d = torch.empty(rows, dtype=torch.int32, device=lm.device)
+            lm.rate_bits_read(reset=True)
+            for a, b in chunks:
+                x, z, y, ok = lm.span_windows(*(list(source) + list(spans)), row0=a, rows=b - a, left=left, ahead=ahead, max_len=M, T=T)
+                lm.reset_states(b - a)
+                cost_d[a:b] = rate(x, z, y)
+                valid_d[a:b] = ok
+            return cost_d, valid_d
+        costs, valids = [], []
+        for a, b in chunks:
+            x, z, y, ok = ratebulk.span_windows_host(*(list(source) + list(spans)), a, b - a, left, ahead, M, T)
+            lm.reset_states(b - a)
+            costs.append(rate(x, z, y))
+            valids.append(ok)
+        return np.concatenate(costs), np.concatenate(valids)
+
     def _spans_request(self, method, texts, items):
         '''What `rate_segments` and `rescore` (`method`) check of their spans: items is a sequence whose entries start with
         (i, start, end), [start, end) a span of the NFC-normalised texts[i].  Returns (the normalised texts, offsets [n + 1] of
@@ -1616,10 +1645,7 @@ class Rater(object):
         if S and ((starts >= 1) & (sizes[span_text] >= 2)).any():
             # (all texts, and all candidates, encoded in one go: many short strings cost a Python loop each)
             joined = "".join(texts)
-            corpus = windows.encode(joined, self.mapping[0]).astype(np.int32)
-            for g in np.nonzero(corpus == 0)[0]:
-                if joined[int(g)] not in self.mapping[0]:
-                    self._unmapped_input(joined[int(g)], int(g - offsets[np.searchsorted(offsets, g, side="right") - 1]))
+            corpus = self._corpus_ids(joined, offsets)
             clamped = {}      # (one context list for all texts is one object n times)
             for c in contexts:
                 if id(c) not in clamped:
@@ -1629,20 +1655,12 @@ class Rater(object):
             pool = windows.encode("".join(strings), self.mapping[0]).astype(np.int32)
             cand_off = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
             chunks = ratebulk.span_chunks(span_first, streams)
-            rate = self._row_costs(precision)
             if hasattr(lm, 'span_windows'):
                 torch = lm.torch
                 up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(lm.device)
                 where = [up(a) for a in (corpus, offsets)] + [up(text_ctx) if lm.n_ctx else None]
                 spans = [up(a) for a in (span_text, span_start, span_len, span_first, pool, cand_off)]
-                cost_d = torch.empty(S + C, dtype=torch.float64, device=lm.device)
-                valid_d = torch.empty(S + C, dtype=torch.int32, device=lm.device)
-                lm.rate_bits_read(reset=True)
-                for a, b in chunks:
-                    x, z, y, ok = lm.span_windows(*(where + spans), row0=a, rows=b - a, left=left, ahead=ahead, max_len=M, T=T)
-                    lm.reset_states(b - a)
-                    cost_d[a:b] = rate(x, z, y)
-                    valid_d[a:b] = ok
+                cost_d, valid_d = self._span_row_costs(where, spans, chunks, precision, left, ahead, M, T)
                 best_d, gain_d, cost_d = lm.span_pick(cost_d, valid_d, spans[3], float(min_gain), want_costs=want_costs)
                 lm.rate_status_check()
                 best, gain = _np(best_d), _np(gain_d)
@@ -1651,15 +1669,9 @@ class Rater(object):
             else:
                 # an engine without the device path (the tests' CPU double): the numpy statements of the windows and of the
                 # choice, the whole softmax of every window and the logs summed on the host
-                costs, valids = [], []
-                for a, b in chunks:
-                    x, z, y, ok = ratebulk.span_windows_host(corpus, offsets, text_ctx, span_text, span_start, span_len,
-                                                             span_first, pool, cand_off, a, b - a, left, ahead, M, T)
-                    lm.reset_states(b - a)
-                    costs.append(rate(x, z, y))
-                    valids.append(ok)
-                best, gain, all_costs = ratebulk.span_pick_host(np.concatenate(costs), np.concatenate(valids), span_first,
-                                                                float(min_gain))
+                costs, valids = self._span_row_costs([corpus, offsets, text_ctx], [span_text, span_start, span_len, span_first, pool,
+                                                                                   cand_off], chunks, precision, left, ahead, M, T)
+                best, gain, all_costs = ratebulk.span_pick_host(costs, valids, span_first, float(min_gain))
                 if want_costs:
                     cost = all_costs
         lm.reset_states(1)
@@ -1851,6 +1863,161 @@ class Rater(object):
         for one, (i, _) in zip(flat, pairs):
             alignments[i].append(one)
         return alignments, rescored, skipped
+
+    def consensus(self, texts, witnesses, contexts=None, max_dist=32, join=1, vote_bits=0.0, left=64, ahead=8, min_gain=1.0,
+                  streams=1024, precision="bf16", want_costs=True):
+        '''`merge_witnesses` for texts with SEVERAL witnesses: the witnesses' differences are clustered across witnesses, so
+        that differences which overlap -- or lie at most `join` equal characters apart -- are ONE hypothesis however many
+        engines take part in it; every witness is read over the whole cluster, equal readings are one candidate, and how many
+        witnesses give a reading counts.  witnesses is one sequence of strings per text, possibly empty, at most 64.  Returns
+        (found, dists, skipped): `found` one ratebatch.Consensus per text (a `Rescored` with votes; the texts without a
+        cluster share one empty result), dists[i] int32, the distance of every witness of text i as `align` gives it, and
+        `skipped`, what yielded no hypothesis, by reason: "different" -- witnesses further than max_dist edits away --,
+        "first" -- clusters at a text's first character --, "long" -- clusters with more than 64 characters as written or in a
+        reading.  The definitions are ratebulk.witness_clusters_host's.
+
+        A reading's score is its cost in bits as `rescore` defines it, minus vote_bits per vote -- the text as written has its
+        own vote and that of every witness that agrees with it over the cluster --; `best`, `gain` and min_gain are
+        `rescore`'s over the scores, and cost0 and cost hold the scores.  vote_bits = 0.0 is the model alone: with one witness
+        per text the result is `merge_witnesses`' `rescored`.
+
+        On the HIP engine: one upload per side as in `align`, the corpus as in `rescore`, the witnesses' ids; `align_pairs`
+        and `witness_clusters` are chained with nothing read between them, then the 64 bytes of the clusters' counts are read
+        -- the only wait before rating -- and the S + 1 candidate offsets for the chunks; `witness_pool`, `rescore`'s chunk
+        loop on the arrays as they lie on the device, the votes subtracted there, one `span_pick`; one download of what the
+        results hold.  No `Alignment` is made and no span passes through Python.  No pairs or no clusters give their result
+        without a rating launch.  An engine without `witness_clusters` (the tests' CPU double) runs the numpy statements.
+        State and precision afterwards are as after `rescore`.  ValueError for what `align` and `rescore` raise, vote_bits
+        < 0, a number of witness lists other than the number of texts, more than 64 witnesses of a text.'''
+        texts, contexts = self._rating_request("consensus", texts, contexts, precision)[:2]
+        if not self.stateful:
+            raise ValueError('consensus needs a stateful rater: it rates through stateful windows')
+        texts = [windows.normalize(t) for t in texts]
+        witnesses = [[windows.normalize(w) for w in readings] for readings in witnesses]
+        n = len(texts)
+        if len(witnesses) != n:
+            raise ValueError("consensus: one sequence of witnesses per text (got %d for %d texts)" % (len(witnesses), n))
+        max_dist, join, vote_bits = int(max_dist), int(join), float(vote_bits)
+        left, ahead, streams = int(left), int(ahead), max(1, int(streams))
+        if not 1 <= max_dist <= ratebulk.ALIGN_DIST_MAX or join < 0:
+            raise ValueError("consensus: max_dist in 1 .. %d and join >= 0 (got %d, %d)" % (ratebulk.ALIGN_DIST_MAX, max_dist, join))
+        if not vote_bits >= 0.0:
+            raise ValueError("consensus: vote_bits >= 0 (got %r)" % vote_bits)
+        if left < 1 or ahead < 0:
+            raise ValueError("left >= 1 and ahead >= 0 (got %d, %d)" % (left, ahead))
+        if left + ahead > 1024:
+            raise ValueError("left + ahead <= 1024 (got %d, %d)" % (left, ahead))
+        count = np.asarray([len(readings) for readings in witnesses], dtype=np.int64).reshape(n)
+        if n and count.max() > ratebulk.WITNESS_MAX:
+            raise ValueError("consensus: %d witnesses of a text; at most %d" % (count.max(), ratebulk.WITNESS_MAX))
+        others = [w for readings in witnesses for w in readings]
+        max_len = max([len(t) for t in texts + others] or [0])
+        if max_len > ratebulk.ALIGN_LEN_MAX:
+            raise ValueError("consensus: a text of %d characters; at most %d -- cut pages into lines or paragraphs"
+                             % (max_len, ratebulk.ALIGN_LEN_MAX))
+        P = len(others)
+        pair_first = np.concatenate([[0], np.cumsum(count)]).astype(np.int64)
+        offsets = np.concatenate([[0], np.cumsum([len(t) for t in texts])]).astype(np.int64)
+        real = lambda m: np.zeros(m, dtype=np.float64) if want_costs else None
+        none = ratebatch.Consensus(np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64), np.zeros(1, dtype=np.int64), [], real(0),
+                                   real(0), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.float64), np.zeros(0, dtype=np.int32),
+                                   np.zeros(0, dtype=np.int32))
+        found = [none] * n
+        if P == 0:
+            return found, [np.zeros(0, dtype=np.int32)] * n, dict(different=0, first=0, long=0)
+        lm = self.model
+        if precision == "split":
+            self._ensure_precision()
+        sides = []
+        for strings in ([t for t, c in zip(texts, count.tolist()) for _ in range(c)], others):
+            off = np.concatenate([[0], np.cumsum([len(t) for t in strings])]).astype(np.int64)
+            sides.append((np.frombuffer("".join(strings).encode("utf-32-le", "surrogatepass"), dtype=np.int32), off))
+        joined = "".join(others)
+        corpus = self._corpus_ids("".join(texts), offsets)
+        b_ids = windows.encode(joined, self.mapping[0]).astype(np.int32)
+        clamped = {}      # (one context list for all texts is one object n times)
+        for c in contexts:
+            if id(c) not in clamped:
+                clamped[id(c)] = windows.clamp_context(c)
+        text_ctx = np.asarray([clamped[id(c)] for c in contexts], dtype=np.int32).reshape(n, -1)
+        device = hasattr(lm, 'witness_clusters')
+        if device:
+            torch = lm.torch
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(lm.device)
+            args = []
+            for pool, off in sides:
+                both = torch.from_numpy(np.concatenate([off.view(np.int32), pool])).to(lm.device)
+                args += [both[2 * (P + 1):], both[:2 * (P + 1)].view(torch.int64)]
+            both = up(np.concatenate([pair_first, offsets]))
+            source = [up(corpus), both[n + 1:], up(text_ctx) if lm.n_ctx else None]
+            b_ids_d = up(b_ids)
+            aligned = lm.align_pairs(*args, max_len, max_dist, join)
+            out = lm.witness_clusters(args[2], args[3], *aligned, both[:n + 1], both[n + 1:], join)
+            stats = _np(out[7])      # (64 bytes: the only wait before rating)
+        else:
+            source = [corpus, offsets, text_ctx]
+            aligned = ratebulk.align_pairs_host(sides[0][0], sides[0][1], sides[1][0], sides[1][1], max_len, max_dist, join)
+            out = ratebulk.witness_clusters_host(sides[1][0], sides[1][1], *aligned, pair_first, offsets, join)
+            stats = out[7]
+        S, C, n_pool, M = (int(v) for v in stats[:4])
+        assert stats[7] == 0
+        skipped = dict(different=int(stats[4]), first=int(stats[5]), long=int(stats[6]))
+        cut_dists = lambda dist: [dist[a:b] for a, b in zip(pair_first[:-1].tolist(), pair_first[1:].tolist())]
+        if S == 0:
+            return found, cut_dists(_np(aligned[0]).astype(np.int32)), skipped
+        M = max(M, 1)
+        if left + ahead + M - 1 > 1024:
+            raise ValueError("left + ahead + %d - 1 <= 1024 (got %d, %d)" % (M, left, ahead))
+        T = max(left + ahead + M - 1, ratebulk.MIN_T)
+        span_first = _np(out[3][:S + 1])
+        chunks = ratebulk.span_chunks(span_first, streams)
+        pool = (lm.witness_pool if device else ratebulk.witness_pool_host)(b_ids_d if device else b_ids, out[4], out[5], C, n_pool)
+        spans = [out[0][:S], out[1][:S], out[2][:S], out[3][:S + 1], pool, out[5][:C + 1]]
+        cost, valid = self._span_row_costs(source, spans, chunks, precision, left, ahead, M, T)
+        votes = out[6][:S + C]
+        if device:
+            if vote_bits:
+                cost = cost - votes.to(torch.float64) * vote_bits
+            best, gain, cost = lm.span_pick(cost, valid, spans[3], float(min_gain), want_costs=want_costs)
+            lm.rate_status_check()
+            whole = _np(torch.cat([aligned[0].to(torch.int64), spans[0].to(torch.int64), spans[1], spans[2].to(torch.int64),
+                                   out[4][:C], spans[5], votes.to(torch.int64), best.to(torch.int64)]))
+            parts = np.split(whole, np.cumsum([P, S, S, S, C, C + 1, S + C]))
+            dist, span_text, span_start, span_len, cand_src, cand_off, votes, best = parts
+            best, gain, cost = best.astype(np.int32), _np(gain), _np(cost) if want_costs else None
+        else:
+            if vote_bits:
+                cost = cost - votes.astype(np.float64) * vote_bits
+            best, gain, cost = ratebulk.span_pick_host(cost, valid, span_first, float(min_gain))
+            cost = cost if want_costs else None
+            dist, span_text, span_start, span_len, cand_src, cand_off = aligned[0], out[0][:S], out[1][:S], out[2][:S], out[4][:C], spans[5]
+        lm.reset_states(1)
+        # per text: its clusters lie together and ascend -- everything gathered once, then cut
+        span_text = span_text.astype(np.int64)
+        starts = span_start.astype(np.int64) - offsets[span_text]
+        ends = starts + span_len
+        sizes = cand_off[1:] - cand_off[:-1]
+        names = [joined[a:a + m] for a, m in zip(cand_src.tolist(), sizes.tolist())]
+        written = span_first[:S] + np.arange(S, dtype=np.int64)
+        rows = np.arange(C, dtype=np.int64) + np.repeat(np.arange(S, dtype=np.int64), span_first[1:] - span_first[:-1]) + 1
+        votes = votes.astype(np.int32)
+        cut = np.searchsorted(span_text, np.arange(n + 1), side="left")
+        for i in np.unique(span_text).tolist():
+            a, b = int(cut[i]), int(cut[i + 1])
+            ca, cb = int(span_first[a]), int(span_first[b])
+            found[i] = ratebatch.Consensus(starts[a:b], ends[a:b], span_first[a:b + 1] - ca, names[ca:cb],
+                                           cost[written[a:b]] if want_costs else None, cost[rows[ca:cb]] if want_costs else None,
+                                           best[a:b], gain[a:b], votes[written[a:b]], votes[rows[ca:cb]])
+        return found, cut_dists(dist.astype(np.int32)), skipped
+
+    def _corpus_ids(self, joined, offsets):
+        '''the ids of all texts of a call, encoded in one go (`joined` their concatenation, offsets [n + 1]); a character
+        outside the mapping is reported with its position in its text, as `rate` does, and keeps id 0'''
+        corpus = windows.encode(joined, self.mapping[0]).astype(np.int32)
+        for g in np.nonzero(corpus == 0)[0]:
+            if joined[int(g)] not in self.mapping[0]:
+                self._unmapped_input(joined[int(g)], int(g - offsets[np.searchsorted(offsets, g, side="right") - 1]))
+        return corpus
 
     _CONFUSION_ROOM = 65536      # rows of the first `confusion_counts` call of `confusions`
 

@@ -32,6 +32,10 @@ base name) on the device, and the differences counted there into a table of conf
 often, and how often the source stands in the OCR at all (Rater.confusions: align_pairs -> confusion_counts); the table goes to
 stdout as the TSV that `rescore --confusions` reads, or with --counts as one JSON line per record; pairs, skipped spans and the
 character error rate go to stderr.
+Additional command `consensus`: `witnesses` for files with several witnesses -- the witnesses' differences clustered across
+witnesses on the device, so that overlapping differences are one hypothesis, every witness read over a whole cluster, equal
+readings counted (Rater.consensus: align_pairs -> witness_clusters -> the rating of `rescore`); --vote-bits weighs a witness'
+vote against the model's bits; the votes stand beside every rescored span, --apply also gives the corrected text.
 Additional options on `train`: --streams (stateful streams per GPU, default 1 = the
 reference's batching) and --segment-streams (with fewer files than streams, cut the files
 into contiguous segments on window boundaries, one list of segments per stream).  Under `python -m torch.distributed.run` training is
@@ -48,7 +52,7 @@ import click
 
 from .. import lib
 
-COMMAND_ORDER = ['train', 'test', 'score', 'suspects', 'correct', 'rescore', 'contexts', 'words', 'lexicon', 'witnesses', 'confusions', 'apply', 'generate', 'print-history', 'print-charset', 'prune-charset',
+COMMAND_ORDER = ['train', 'test', 'score', 'suspects', 'correct', 'rescore', 'contexts', 'words', 'lexicon', 'witnesses', 'confusions', 'consensus', 'apply', 'generate', 'print-history', 'print-charset', 'prune-charset',
                  'plot-char-embeddings-similarity', 'plot-context-embeddings-similarity', 'plot-context-embeddings-projection']
 
 
@@ -741,6 +745,75 @@ def confusions_(model, truth_dir, max_dist, join, max_chars, min_count, min_rate
     else:
         found.write(click.get_text_stream('stdout'), **same)
     click.echo(json.dumps(dict(found.skipped, pairs=len(texts), chars=found.chars, edits=found.edits, cer=found.cer)), err=True)
+
+
+@cli.command('consensus', short_help='let the model and the votes choose among several readings of every file')
+@click.option('-m', '--model', default="model.h5", show_default=True, help='model file', type=click.Path(dir_okay=False, exists=True))
+@click.option('--witness', 'witness_dirs', multiple=True, required=True, type=click.Path(file_okay=False, exists=True),
+              help='directory of second readings: the witness of a DATA file is the file of the same base name (may be missing); '
+                   'repeat for further witnesses, at most 64')
+@click.option('--max-dist', default=32, show_default=True, type=click.IntRange(min=1, max=255),
+              help='a witness further than this many edits from its file is not a reading of the same text')
+@click.option('--join', default=1, show_default=True, type=click.IntRange(min=0),
+              help='differences of any witnesses with at most this many equal characters between them are one span')
+@click.option('--vote-bits', default=0.0, show_default=True, type=click.FloatRange(min=0.0),
+              help='bits a reading is credited per witness that gives it (the text as written: itself and every witness that agrees); '
+                   '0: the model alone')
+@click.option('-s', '--streams', default=1024, show_default=True, help='rows of a window call: hypotheses',
+              type=click.IntRange(min=1, max=4096))
+@click.option('--precision', default='bf16', show_default=True, type=click.Choice(['bf16', 'split']),
+              help='bf16: bulk rating on the training forward; split: the inference kernels, ~f32 accuracy')
+@click.option('--left', default=64, show_default=True, type=click.IntRange(min=1, max=1024),
+              help='characters in front of a span that a hypothesis is read from (from a zero state)')
+@click.option('--ahead', default=8, show_default=True, type=click.IntRange(min=0, max=1023),
+              help='characters after a span that a hypothesis is held against')
+@click.option('--min-gain', default=1.0, show_default=True, type=click.FLOAT,
+              help='a proposal must score at least this many bits better than the text as written')
+@click.option('--apply', 'apply_', is_flag=True, default=False, help='also give the text with the proposals applied ("corrected")')
+@click.argument('data', nargs=-1, type=click.Path(exists=True, dir_okay=True, file_okay=True))
+def consensus_(model, witness_dirs, max_dist, join, vote_bits, streams, precision, left, ahead, min_gain, apply_, data):
+    """Align every DATA file with its witnesses -- the files of the same base name in the --witness
+       directories --, cluster the differences of all witnesses of a file, rate every distinct reading
+       of a cluster against the text around it, and print one JSON line per file as `witnesses` does:
+       characters, "witnesses": one {"file", "dist"} per witness found, and "rescored": per cluster
+       [start, end, written, proposal, gain, votes of the text as written, [[reading, votes], ...]].
+       With --apply the line also holds the corrected text.  A last line on stderr gives what yielded no
+       hypothesis, by reason.  A file or witness of more than 4096 characters is an error: cut pages
+       into lines.
+    """
+    from ..lib import windows
+    rater = _load(model)
+    names, texts, contexts, readings, sources = [], [], [], [], []
+    for file in _open_all(data):
+        with file:
+            texts.append(windows.normalize(file.read()))
+        names.append(file.name)
+        contexts.append(windows.context_from_filename(file.name))
+        paths = [os.path.join(d, os.path.basename(file.name)) for d in witness_dirs]
+        sources.append([p for p in paths if os.path.isfile(p)])
+        readings.append([])
+        for path in sources[-1]:
+            with open(path, mode='r') as other:
+                readings[-1].append(windows.normalize(other.read()))
+    if not texts:
+        return
+    try:
+        found, dists, skipped = rater.consensus(texts, readings, contexts, max_dist=max_dist, join=join, vote_bits=vote_bits,
+                                                left=left, ahead=ahead, min_gain=min_gain, streams=streams, precision=precision,
+                                                want_costs=False)
+    except ValueError as err:
+        raise click.UsageError(str(err))
+    for i, (name, text, one) in enumerate(zip(names, texts, found)):
+        first = one.first.tolist()
+        rows = [[int(a), int(b), text[int(a):int(b)], new, float(g), int(v0),
+                 [[c, int(v)] for c, v in zip(one.candidates[first[j]:first[j + 1]], one.votes[first[j]:first[j + 1]])]]
+                for j, (a, b, new, g, v0) in enumerate(zip(one.starts, one.ends, one.proposals(), one.gain, one.votes0))]
+        line = {"file": name, "chars": len(text),
+                "witnesses": [{"file": path, "dist": int(d)} for path, d in zip(sources[i], dists[i])], "rescored": rows}
+        if apply_:
+            line["corrected"] = one.apply(text)
+        click.echo(json.dumps(line, ensure_ascii=False))
+    click.echo(json.dumps(skipped), err=True)
 
 
 @cli.command(short_help='sample characters from language model')
