@@ -23,6 +23,7 @@
  *   ... per word: the words found, rated and the suspect ones picked out  kl_word_bounds, kl_rate_segments, kl_segment_select
  *       (the processor's mean probability per TextEquiv substring, wrapper/rate.py:308-317, for a whole corpus)
  *   ... and the suspect words' nearest entries of a lexicon, as replacements   kl_lexicon_neighbours
+ *   ... or, under a table of learned confusions, its cheapest entries in a weighted distance   kl_lexicon_channel
  *   ... and the spans where a second reading of the text (another OCR engine) differs   kl_align_pairs
  *   ... and, against ground truth, the table of confusions these spans amount to   kl_confusion_counts
  *   ... and, with several such readings, their spans clustered and the readings counted   kl_witness_clusters, kl_witness_pool
@@ -521,6 +522,52 @@ size_t kl_lexicon_neighbours_workspace_bytes(size_t Q, int K);
 int kl_lexicon_neighbours(const int32_t* chars, size_t n_chars, const int32_t* order, const int64_t* class_first, int V,
                           const int32_t* q_pool, size_t n_q, const int64_t* q_off, size_t Q, int max_dist, int K, int32_t* exact,
                           int32_t* found, int32_t* cand, int32_t* dist, void* ws, size_t ws_bytes, void* stream);
+
+/* Lexicon look-up under learned confusions: the entries of a lexicon that are cheap to reach from every query word in a
+ * weighted edit distance whose steps are the plain edits and the rules of a confusion table -- the noisy-channel form of
+ * kl_lexicon_neighbours.  No handle.  The lexicon (chars, n_chars, order, class_first), the queries (q_pool, n_q, q_off, Q), V
+ * and the id equality are kl_lexicon_neighbours': an id outside [0, V) equals nothing, itself included.
+ *
+ * The channel.  rules (device int32 [R][10]) holds records in the layout kl_confusion_counts writes: src_len, tgt_len, src[4],
+ * tgt[4]; rule_cost (device int32 [R]) their costs; 0 <= R <= KL_CHANNEL_RULES_MAX, both may be null with R == 0.  The SOURCE
+ * is what stands in the query (the OCR word), the TARGET what stands in the entry (the truth).  unit, 1 ..
+ * KL_CHANNEL_COST_MAX, is the cost of a plain insertion, deletion or substitution; max_cost, 0 .. KL_CHANNEL_COST_MAX, the
+ * budget.  A rule is IGNORED, and nothing behind its used fields is read, if src_len is outside 1 .. 4, tgt_len outside
+ * 0 .. 4, a used id outside [0, V) or its cost outside 0 .. KL_CHANNEL_COST_MAX (the rules lie on the device: the entry point
+ * cannot refuse them).  Zero-cost rules are legal.
+ *
+ * Distance of a query q of m ids and an entry e of n ids: W[0][0] = 0, otherwise W[i][j] is the least of
+ *   W[i-1][j-1] + (q[i-1] == e[j-1] ? 0 : unit)   (i, j > 0),     W[i-1][j] + unit   (i > 0),     W[i][j-1] + unit   (j > 0),
+ *   W[i-s][j-t] + cost_r   for every rule r that is not ignored, s = src_len, t = tgt_len, i >= s, j >= t,
+ *                          q[i-s:i] == src and e[j-t:j] == tgt under the id equality;
+ * w(q, e) = W[m][n].
+ *
+ * Outputs (device int32, OVERWRITTEN for every q < Q, nothing behind them written), for a query of 1 .. 64 ids:
+ *   exact[q]        the smallest original index of an entry IDENTICAL to the query (same length, all ids equal), or -1;
+ *   found[q]        the number of entries that are not identical and have w <= max_cost, whatever K is;
+ *   cand[q][0..K)   the original indices of the first K of these, ordered by (w, original index); cost[q][.] their w; unused
+ *                   places are -1 in both.  A non-identical entry at w == 0 (zero-cost rules) is a candidate and comes first.
+ * A query of no ids, of more than 64 or with bad offsets gets -1, 0 and -1 everywhere, and nothing of it is read.  With
+ * R == 0 and unit == 1 the outputs are kl_lexicon_neighbours' at max_dist = max_cost.  The statement is
+ * ratebulk.lexicon_channel_host.
+ *
+ * A preparing launch of one workgroup (the class table, the rules checked and packed, the cheapest price per id of lengthening
+ * and of shortening, which bound the length classes a query can reach), then one workgroup per query: where each rule's source
+ * stands in the query is settled once and kept in LDS, every lane walks whole entries with a ring of five DP columns of 16-bit
+ * saturated cells in LDS (a value above max_cost is max_cost + 1), and keeps its smallest keys (w << 32 | original index); the
+ * workgroup takes the K smallest in a fixed order.  Two plain launches on `stream`, no atomics on global memory, no workgroup
+ * waits for another, the output depends on the inputs only: two calls agree bit for bit, and so does any order of the rules.
+ * ws: device scratch of kl_lexicon_channel_workspace_bytes(Q, K, R) bytes, 8-byte aligned, not to be shared by calls that may
+ * overlap.  KL_ERR_ARG, before any launch and with nothing touched, for what kl_lexicon_neighbours rejects (max_dist aside), R,
+ * unit or max_cost out of range, a null rule pointer with R > 0, a misaligned rule pointer (4 bytes); KL_ERR_WORKSPACE if
+ * ws_bytes is too small. */
+#define KL_CHANNEL_RULES_MAX 1024
+#define KL_CHANNEL_COST_MAX 4095
+size_t kl_lexicon_channel_workspace_bytes(size_t Q, int K, int R);
+int kl_lexicon_channel(const int32_t* chars, size_t n_chars, const int32_t* order, const int64_t* class_first, int V,
+                       const int32_t* q_pool, size_t n_q, const int64_t* q_off, size_t Q, const int32_t* rules,
+                       const int32_t* rule_cost, int R, int unit, int max_cost, int K, int32_t* exact, int32_t* found,
+                       int32_t* cand, int32_t* cost, void* ws, size_t ws_bytes, void* stream);
 
 /* Alignment of two readings: where do the texts of P pairs differ?  The step in front of kl_span_windows for a second witness of
  * the same line or page (another OCR engine): the differing spans become the spans and replacements it rates.  No handle.

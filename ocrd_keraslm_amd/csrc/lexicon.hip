@@ -13,10 +13,12 @@
 // cannot be within max_dist --, one character per step from the column-major layout (consecutive lanes read consecutive
 // addresses), and keeps its own KL_LEXICON_K_MAX smallest keys (distance << 32 | original index) sorted in registers.  The
 // workgroup then takes the K smallest heads one after the other: a minimum over the waves, the winner (the lowest thread among
-// equal keys) drops its head.  `found` is an integer sum and `exact` a minimum, both folded in a fixed order.  No atomics, no
+// equal keys) drops its head.  `found` is an integer sum and `exact` a minimum, both folded in a fixed order (the lists and the
+// fold are kl_lexicon_topk.h's, shared with kl_lexicon_channel).  No atomics, no
 // workgroup waits for another, the output depends on the inputs only.  No model: no handle.
 #include "keraslm_hip.h"
 #include "kl_common.h"
+#include "kl_lexicon_topk.h"
 #include <stdlib.h>
 
 namespace {
@@ -24,11 +26,9 @@ namespace {
 constexpr int LEX_THREADS = 256;
 constexpr int LEX_WAVES = LEX_THREADS / KL_WAVE;
 constexpr int LEX_LEN_MAX = 64;      // ids of a query and of an entry at most: one pattern word
-constexpr unsigned long long NO_KEY = ~0ull;
 constexpr size_t MAX_QUERIES = 0x7FFFFFFF;      // (one workgroup per query in one grid)
 constexpr size_t MAX_POOL = (size_t)1 << 40;
 static_assert(KL_LEXICON_V_MAX * 8 <= 32 * 1024, "Peq fits 32 KiB of LDS");
-static_assert(KL_LEXICON_K_MAX == 16, "the lanes' key lists are written out for 16 keys");
 
 constexpr int LEX_CLASSES = LEX_LEN_MAX + 2;
 // the length classes, checked on the host: entries of length L are the sorted positions [first[L], first[L + 1]) and their
@@ -77,21 +77,6 @@ __device__ __forceinline__ unsigned int match_mask<unsigned int>(const unsigned 
   return (c >= 0 && c < V) ? reinterpret_cast<const unsigned int*>(peq)[2 * c] : 0u;
 }
 
-__device__ __forceinline__ unsigned long long wave_min(unsigned long long v) {
-#pragma unroll
-  for (int off = KL_WAVE / 2; off > 0; off >>= 1) {
-    const unsigned long long o = __shfl_xor(v, off, KL_WAVE);
-    v = o < v ? o : v;
-  }
-  return v;
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-  for (int off = KL_WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, KL_WAVE);
-  return v;
-}
-
 // a lane's walk over the entries e = tid, tid + LEX_THREADS, .. of every length class that can hold a neighbour of a query of m
 // ids: its KL_LEXICON_K_MAX smallest keys (sorted), the least index at distance 0 and the number within 1 .. max_dist
 template <typename W>
@@ -120,16 +105,7 @@ __device__ __forceinline__ void walk_classes(const int* __restrict__ chars, cons
           least_exact = index < least_exact ? index : least_exact;
         } else {
           ++n_found;
-          unsigned long long key = ((unsigned long long)score << 32) | index;
-          if (key < best[KL_LEXICON_K_MAX - 1]) {
-#pragma unroll
-            for (int i = 0; i < KL_LEXICON_K_MAX; ++i) {      // (sorted insertion, every index a constant: registers)
-              const unsigned long long b = best[i];
-              const bool less = key < b;
-              best[i] = less ? key : b;
-              key = less ? b : key;
-            }
-          }
+          kl_lex_keep(((unsigned long long)score << 32) | index, best);
         }
       }
     }
@@ -142,10 +118,8 @@ __global__ void __launch_bounds__(LEX_THREADS) lexicon_neighbours_kernel(
     int* __restrict__ exact, int* __restrict__ found, int* __restrict__ cand, int* __restrict__ dist) {
   __shared__ unsigned long long peq[KL_LEXICON_V_MAX];
   __shared__ int s_query[LEX_LEN_MAX];
-  __shared__ unsigned long long s_key[LEX_WAVES], s_mask[LEX_WAVES];
-  __shared__ unsigned int s_exact[LEX_WAVES];
-  __shared__ int s_found[LEX_WAVES];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ kl_lex_fold<LEX_WAVES> s_fold;
+  const int tid = threadIdx.x;
   const long long q = blockIdx.x;
   const long long qa = q_off[q], qb = q_off[q + 1];
   // a query outside the pool, of no ids or of more than 64 is a neighbour of nothing: nothing of it is read
@@ -178,65 +152,15 @@ __global__ void __launch_bounds__(LEX_THREADS) lexicon_neighbours_kernel(
 
   unsigned long long best[KL_LEXICON_K_MAX];
 #pragma unroll
-  for (int i = 0; i < KL_LEXICON_K_MAX; ++i) best[i] = NO_KEY;
-  unsigned int least_exact = 0xFFFFFFFFu;
+  for (int i = 0; i < KL_LEXICON_K_MAX; ++i) best[i] = KL_LEX_NO_KEY;
+  unsigned int least_exact = KL_LEX_NO_EXACT;
   int n_found = 0;
   if (narrow && m <= 32)      // (uniform: a workgroup is one query)
     walk_classes<unsigned int>(chars, order, table, peq, V, m, max_dist, tid, best, least_exact, n_found);
   else
     walk_classes<unsigned long long>(chars, order, table, peq, V, m, max_dist, tid, best, least_exact, n_found);
 
-  // exact and found
-  {
-    unsigned int x = least_exact;
-#pragma unroll
-    for (int off = KL_WAVE / 2; off > 0; off >>= 1) {
-      const unsigned int o = __shfl_xor(x, off, KL_WAVE);
-      x = o < x ? o : x;
-    }
-    const int f = wave_sum(n_found);
-    if (lane == 0) {
-      s_exact[wave] = x;
-      s_found[wave] = f;
-    }
-  }
-  __syncthreads();
-  if (tid == 0) {
-    unsigned int x = s_exact[0];
-    int f = s_found[0];
-#pragma unroll
-    for (int w = 1; w < LEX_WAVES; ++w) {
-      x = s_exact[w] < x ? s_exact[w] : x;
-      f += s_found[w];
-    }
-    exact[q] = x == 0xFFFFFFFFu ? -1 : (int)x;
-    found[q] = f;
-  }
-  // the K smallest keys of the workgroup, one per round
-  for (int r = 0; r < K; ++r) {
-    const unsigned long long head = best[0];
-    const unsigned long long wmin = wave_min(head);
-    if (lane == 0) s_key[wave] = wmin;
-    __syncthreads();
-    unsigned long long gmin = s_key[0];
-#pragma unroll
-    for (int w = 1; w < LEX_WAVES; ++w) gmin = s_key[w] < gmin ? s_key[w] : gmin;
-    const unsigned long long mask = __ballot(head == gmin && gmin != NO_KEY);
-    if (lane == 0) s_mask[wave] = mask;
-    __syncthreads();
-    int w_first = LEX_WAVES;
-#pragma unroll
-    for (int w = LEX_WAVES - 1; w >= 0; --w) w_first = s_mask[w] != 0ull ? w : w_first;
-    if (wave == w_first && lane == __ffsll((long long)mask) - 1) {      // the lowest thread among equal keys drops its head
-#pragma unroll
-      for (int i = 0; i + 1 < KL_LEXICON_K_MAX; ++i) best[i] = best[i + 1];
-      best[KL_LEXICON_K_MAX - 1] = NO_KEY;
-    }
-    if (tid == 0) {
-      cand[q * K + r] = gmin == NO_KEY ? -1 : (int)(unsigned int)(gmin & 0xFFFFFFFFull);
-      dist[q * K + r] = gmin == NO_KEY ? -1 : (int)(gmin >> 32);
-    }
-  }
+  kl_lex_fold_out<LEX_WAVES>(s_fold, best, least_exact, n_found, K, q, exact, found, cand, dist);
 }
 
 inline bool misaligned(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }

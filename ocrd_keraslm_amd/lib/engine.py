@@ -97,6 +97,7 @@ class HipLM:
         self._word_bounds_ws = None
         self._segment_select_ws = None
         self._lexicon_ws = None
+        self._lexicon_channel_ws = None
         self._align_ws = None
         self._confusion_ws = None
         self._witness_ws = None
@@ -782,6 +783,42 @@ class HipLM:
                 _ptr(chars_d), chars_d.numel(), _ptr(order_d), class_first.ctypes.data, V, _ptr(q_pool_d), q_pool_d.numel(),
                 _ptr(q_off_d), Q, max_dist, K, *([_ptr(t) for t in out] + [_ptr(ws), ws.numel(), self._stream()])),
                 "kl_lexicon_neighbours")
+        return out
+
+    def lexicon_channel(self, chars_d, order_d, class_first, V, q_pool_d, q_off_d, rules_d, rule_cost_d, unit, max_cost, K):
+        """kl_lexicon_channel: the entries of a lexicon within max_cost of Q query words in the weighted distance of a
+        confusion table.  The lexicon, V and the queries as in `lexicon_neighbours`; rules_d int32 [R, 10] (src_len, tgt_len,
+        src[4], tgt[4]: the source stands in the query) and rule_cost_d int32 [R] on the DEVICE, both None for no rules;
+        unit the cost of a plain edit.  Returns the DEVICE tensors (exact int32 [Q], found int32 [Q], cand int32 [Q, K], cost
+        int32 [Q, K]); the statement is ratebulk.lexicon_channel_host.  hipabi.KlError for what the entry point rejects.  No
+        synchronisation."""
+        torch = self.torch
+        tensors = (chars_d, order_d, q_pool_d, q_off_d)
+        if ([t.dtype for t in tensors] != [torch.int32, torch.int32, torch.int32, torch.int64] or any(t.dim() != 1 for t in tensors)
+                or q_off_d.numel() < 2 or not all(t.is_contiguous() and t.is_cuda for t in tensors)):
+            raise hipabi.KlError("lexicon_channel: chars, order and q_pool int32, q_off int64 [Q + 1], contiguous, on the device")
+        class_first = np.ascontiguousarray(class_first, dtype=np.int64).reshape(-1)
+        if len(class_first) != 66 or order_d.numel() != int(class_first[-1]):
+            raise hipabi.KlError("lexicon_channel: class_first int64 [66] on the host, its last value the size of order")
+        R = 0
+        if rules_d is not None or rule_cost_d is not None:
+            both = (rules_d, rule_cost_d)
+            if (any(t is None or t.dtype != torch.int32 or not (t.is_contiguous() and t.is_cuda) for t in both)
+                    or rules_d.dim() != 2 or rules_d.shape[1] != 10 or rule_cost_d.dim() != 1
+                    or rule_cost_d.numel() != rules_d.shape[0]):
+                raise hipabi.KlError("lexicon_channel: rules int32 [R, 10] and rule_cost int32 [R], contiguous, on the device")
+            R = int(rule_cost_d.numel())
+        V, unit, max_cost, K = int(V), int(unit), int(max_cost), int(K)
+        Q = q_off_d.numel() - 1
+        dev = self.device
+        with self._launch():
+            ws = self._scratch("_lexicon_channel_ws", self.lib.kl_lexicon_channel_workspace_bytes(Q, K, R))
+            out = (torch.empty(Q, dtype=torch.int32, device=dev), torch.empty(Q, dtype=torch.int32, device=dev),
+                   torch.empty((Q, max(K, 0)), dtype=torch.int32, device=dev), torch.empty((Q, max(K, 0)), dtype=torch.int32, device=dev))
+            hipabi.check(self.lib.kl_lexicon_channel(
+                _ptr(chars_d), chars_d.numel(), _ptr(order_d), class_first.ctypes.data, V, _ptr(q_pool_d), q_pool_d.numel(),
+                _ptr(q_off_d), Q, _ptr(rules_d) if R else None, _ptr(rule_cost_d) if R else None, R, unit, max_cost, K,
+                *([_ptr(t) for t in out] + [_ptr(ws), ws.numel(), self._stream()])), "kl_lexicon_channel")
         return out
 
     def _hypothesis_fits(self, source, own):

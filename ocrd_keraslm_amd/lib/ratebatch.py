@@ -316,15 +316,20 @@ class Segments(Words):
     (`suspects` are zeros: no ranks are computed)."""
 
 
-def word_edits(found, texts, candidates):
+def word_edits(found, texts, candidates, priors=None):
     """Edits for `Rater.rescore` from the words `Rater.suspect_words` found: found is one `Words` per text, candidates a dict or
     a callable word -> list of replacement strings (a lexicon look-up, a spell checker, a second engine's token).  One edit
     (i, start, end, replacements) per word that yields replacements; a word that yields none is skipped, and so is a word at a
-    text's first character (no prediction to be held against).  Ordered by text and start.  Host only."""
+    text's first character (no prediction to be held against).  Ordered by text and start.  Host only.
+
+    With priors -- a dict or a callable word -> one number per replacement of that word, e.g. a channel's bits -- returns
+    (edits, prior): prior[e] is the list of numbers of edit e, parallel to its replacements: what `Rater.rescore(prior=..)`
+    takes.  ValueError for a word whose numbers are not as many as its replacements."""
     if len(found) != len(texts):
         raise ValueError("word_edits: one Words per text")
     look_up = candidates if callable(candidates) else (lambda word: candidates.get(word, ()))
-    edits = []
+    weigh = None if priors is None else priors if callable(priors) else (lambda word: priors.get(word, ()))
+    edits, prior = [], []
     for i, (words, text) in enumerate(zip(found, texts)):
         text = windows.normalize(text)
         for start, end in sorted(words.spans()):
@@ -333,7 +338,11 @@ def word_edits(found, texts, candidates):
             replacements = list(look_up(text[start:end]) or ())
             if replacements:
                 edits.append((i, start, end, replacements))
-    return edits
+                if weigh is not None:
+                    prior.append([float(b) for b in weigh(text[start:end]) or ()])
+                    if len(prior[-1]) != len(replacements):
+                        raise ValueError("word_edits: one prior per replacement of %r" % text[start:end])
+    return edits if weigh is None else (edits, prior)
 
 
 class Lexicon(object):
@@ -396,10 +405,12 @@ class Neighbours(object):
     index   [n,K] i32   the first K of them, ordered by (distance, index) -- the nearest first, the more frequent among equally
                         near ones --, -1 from the found-th on
     dist    [n,K] i32   their distances, -1 where index is
+    bits    None, or with a channel [n,K] f64: dist then holds sixteenths of a bit under the channel -- `found` counts the entries
+                        within max_bits --, bits their float value, NaN where index is -1
     """
 
-    def __init__(self, lexicon, exact, found, index, dist):
-        self.lexicon, self.exact, self.found, self.index, self.dist = lexicon, exact, found, index, dist
+    def __init__(self, lexicon, exact, found, index, dist, bits=None):
+        self.lexicon, self.exact, self.found, self.index, self.dist, self.bits = lexicon, exact, found, index, dist, bits
 
     def __len__(self):
         return len(self.exact)
@@ -407,6 +418,91 @@ class Neighbours(object):
     def strings(self, i):
         """the neighbours of word i as strings, the nearest first"""
         return [self.lexicon.words[int(e)] for e in self.index[i] if e >= 0]
+
+
+class Channel(object):
+    """A table of confusions as the weighted look-up takes it (`Rater.channel` builds it, `Rater.lexicon_neighbours` and
+    `Rater.correct_words` read it).  `records` is a `Confusions` or an iterable of (source, target, count, occ): `source` in
+    the OCR stands for `target` in the truth, `count` times at `occ` occurrences of the source.  The strings are NFC-normalised
+    and encoded with `mapping` (char -> id), ids below `voc_size`.  Costs are sixteenths of a bit: a record costs
+    round(16 * min(-log2(count / occ), 255)), a plain edit `unit` = round(16 * unit_bits).  Dropped, and counted by reason in
+    `dropped`: "count" and "rate" -- below min_count, below min_rate --, "empty" -- no source --, "same" -- the source is the
+    target --, "unmapped" -- a character outside the mapping --, "long" -- a side of more than 4 characters --, "duplicate" -- the
+    least cost of a (source, target) is kept --, "cut" -- beyond 1024 rules those of largest count are kept, the first among
+    equal ones.
+
+    sources, targets, count   [R]   the kept rules, in the order given
+    rules    [R, 10] i32      src_len, tgt_len, src[4], tgt[4]: the records of kl_confusion_counts, as ids
+    cost     [R] i32          sixteenths of a bit
+    unit     int              the cost of a plain insertion, deletion or substitution
+    mapping, voc_size         what it was encoded with
+    dropped  dict             reason -> count
+    """
+
+    def __init__(self, records, mapping, voc_size, unit_bits=8.0, min_count=2, min_rate=0.0):
+        if int(voc_size) > ratebulk.LEXICON_V_MAX:
+            raise ValueError("a channel needs a mapping of at most %d characters (got %d)" % (ratebulk.LEXICON_V_MAX, voc_size))
+        unit = int(round(ratebulk.CHANNEL_SCALE * float(unit_bits)))
+        if not 1 <= unit <= ratebulk.CHANNEL_COST_MAX:
+            raise ValueError("a channel's unit_bits lies in 1/16 .. 255.9 (got %r)" % (unit_bits,))
+        self.mapping, self.voc_size, self.unit = mapping, int(voc_size), unit
+        self._mapped = len(mapping)
+        self.dropped = dict(count=0, rate=0, empty=0, same=0, unmapped=0, long=0, duplicate=0, cut=0)
+        if isinstance(records, Confusions):
+            records = zip(records.sources, records.targets, records.count.tolist(), records.occ.tolist())
+        chars_max = ratebulk.CONFUSION_CHARS_MAX
+        kept, place = [], {}
+        for source, target, count, occ in records:
+            source, target = windows.normalize(source), windows.normalize(target)
+            count, occ = int(count), int(occ)
+            rate = count / occ if occ > 0 else 0.0
+            reason = ("count" if count < min_count else "rate" if rate < min_rate else "empty" if not source
+                      else "same" if source == target else "long" if max(len(source), len(target)) > chars_max
+                      else "unmapped" if any(not 0 < mapping.get(c, 0) < self.voc_size for c in source + target) else None)
+            if reason:
+                self.dropped[reason] += 1
+                continue
+            bits = 255.0 if rate <= 0.0 else min(max(-np.log2(rate), 0.0), 255.0)
+            cost = int(round(ratebulk.CHANNEL_SCALE * bits))
+            if (source, target) in place:
+                self.dropped["duplicate"] += 1
+                at = place[source, target]
+                if cost < kept[at][3]:
+                    kept[at] = (source, target, count, cost)
+            else:
+                place[source, target] = len(kept)
+                kept.append((source, target, count, cost))
+        if len(kept) > ratebulk.CHANNEL_RULES_MAX:
+            first = sorted(range(len(kept)), key=lambda i: (-kept[i][2], i))[:ratebulk.CHANNEL_RULES_MAX]
+            self.dropped["cut"] = len(kept) - len(first)
+            kept = [kept[i] for i in sorted(first)]
+        self.sources, self.targets = [r[0] for r in kept], [r[1] for r in kept]
+        self.count = np.asarray([r[2] for r in kept], dtype=np.int64)
+        self.cost = np.asarray([r[3] for r in kept], dtype=np.int32)
+        self.rules = np.zeros((len(kept), 2 + 2 * chars_max), dtype=np.int32)
+        for r, (source, target, _, _) in enumerate(kept):
+            self.rules[r, 0], self.rules[r, 1] = len(source), len(target)
+            self.rules[r, 2:2 + len(source)] = [mapping[c] for c in source]
+            self.rules[r, 2 + chars_max:2 + chars_max + len(target)] = [mapping[c] for c in target]
+        self._device = {}      # id(engine) -> (engine, rules, cost) on its device: uploaded once
+
+    def __len__(self):
+        return len(self.sources)
+
+    def same_mapping(self, mapping):
+        """was the channel encoded with this very mapping (the same object, no character added since)?"""
+        return mapping is self.mapping and len(mapping) == self._mapped
+
+    def on_device(self, lm):
+        """(rules, cost) as int32 tensors on the engine's device, (None, None) for no rules: uploaded at the first call, kept
+        for the later ones"""
+        if not len(self):
+            return None, None
+        held = self._device.get(id(lm))
+        if held is None or held[0] is not lm:
+            up = lambda a: lm.torch.from_numpy(np.ascontiguousarray(a)).to(lm.device)
+            held = self._device[id(lm)] = (lm, up(self.rules), up(self.cost))
+        return held[1], held[2]
 
 
 class Alignment(object):

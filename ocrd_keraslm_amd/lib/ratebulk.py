@@ -844,6 +844,149 @@ def lexicon_neighbours_host(q_pool, q_off, chars, order, class_first, V, max_dis
     return exact, found, cand, dist
 
 
+CHANNEL_RULES_MAX, CHANNEL_COST_MAX = 1024, 4095      # (KL_CHANNEL_* of the C ABI)
+CHANNEL_SCALE = 16                                    # the Python layer counts in sixteenths of a bit
+
+
+def channel_rules_kept(rules, rule_cost, V):
+    """the rules kl_lexicon_channel does not ignore, as [(src tuple, tgt tuple, cost)] in the order given: src_len in 1 .. 4,
+    tgt_len in 0 .. 4, every used id in [0, V), the cost in 0 .. CHANNEL_COST_MAX.  rules is int32 [R, 10] in the record
+    layout of `confusion_counts_host` (src_len, tgt_len, src[4], tgt[4]), rule_cost int32 [R]."""
+    rules = np.asarray(rules, dtype=np.int64).reshape(-1, 2 + 2 * CONFUSION_CHARS_MAX)
+    rule_cost = np.asarray(rule_cost, dtype=np.int64).reshape(-1)
+    if len(rules) != len(rule_cost):
+        raise ValueError("channel_rules_kept: one cost per rule")
+    kept = []
+    for rec, cost in zip(rules.tolist(), rule_cost.tolist()):
+        s, t = rec[0], rec[1]
+        if not (1 <= s <= CONFUSION_CHARS_MAX and 0 <= t <= CONFUSION_CHARS_MAX and 0 <= cost <= CHANNEL_COST_MAX):
+            continue
+        src, tgt = tuple(rec[2:2 + s]), tuple(rec[2 + CONFUSION_CHARS_MAX:2 + CONFUSION_CHARS_MAX + t])
+        if all(0 <= c < V for c in src + tgt):
+            kept.append((src, tgt, cost))
+    return kept
+
+
+def lexicon_channel_host(q_pool, q_off, chars, order, class_first, V, rules, rule_cost, unit, max_cost, K):
+    """what kl_lexicon_channel computes: `lexicon_neighbours_host` under a weighted distance.  The lexicon, the queries, the
+    id equality (an id outside [0, V) equals nothing, itself included) and the outputs' conventions are the same; rules and
+    rule_cost are those of `channel_rules_kept` (None or empty: no rules), the SOURCE of a rule is what stands in the query,
+    the TARGET what stands in the entry.  With m, n the lengths of query q and entry e: W[0][0] = 0 and otherwise W[i][j] is
+    the least of W[i-1][j-1] + (q[i-1] == e[j-1] ? 0 : unit), W[i-1][j] + unit, W[i][j-1] + unit and W[i-s][j-t] + cost for
+    every kept rule (src, tgt, cost) with s = len(src) <= i, t = len(tgt) <= j, q[i-s:i] == src, e[j-t:j] == tgt;
+    w(q, e) = W[m][n].  Returns (exact int32 [Q], found int32 [Q], cand int32 [Q, K], cost int32 [Q, K]): exact[q] the smallest
+    original index of an entry IDENTICAL to the query, or -1; found[q] the number of entries that are not identical with
+    w <= max_cost; cand[q] the first K of these ordered by (w, original index), cost[q] their w, unused places -1.  A query of
+    no ids or of more than 64 gets -1, 0 and -1 everywhere.
+
+    A plain DP over all entries of a length class at once.  Only the classes m + d with |d| * price <= max_cost can hold
+    such an entry, price being the least cost per id of lengthening (unit, or cost / (t - s) over the rules with t > s) for
+    d > 0 and of shortening (s > t) for d < 0 -- compared as exact fractions."""
+    q_pool = np.asarray(q_pool, dtype=np.int64).reshape(-1)
+    q_off = np.asarray(q_off, dtype=np.int64).reshape(-1)
+    chars = np.asarray(chars, dtype=np.int64).reshape(-1)
+    order = np.asarray(order, dtype=np.int64).reshape(-1)
+    class_first = np.asarray(class_first, dtype=np.int64).reshape(-1)
+    V, unit, max_cost, K = int(V), int(unit), int(max_cost), int(K)
+    if not (1 <= V <= LEXICON_V_MAX and 1 <= unit <= CHANNEL_COST_MAX and 0 <= max_cost <= CHANNEL_COST_MAX
+            and 1 <= K <= LEXICON_K_MAX):
+        raise ValueError("lexicon_channel_host: V in 1 .. %d, unit in 1 .. %d, max_cost in 0 .. %d, K in 1 .. %d"
+                         % (LEXICON_V_MAX, CHANNEL_COST_MAX, CHANNEL_COST_MAX, LEXICON_K_MAX))
+    if rules is None or len(rules) == 0:
+        rules, rule_cost = np.zeros((0, 2 + 2 * CONFUSION_CHARS_MAX), dtype=np.int32), np.zeros(0, dtype=np.int32)
+    if len(rule_cost) > CHANNEL_RULES_MAX:
+        raise ValueError("lexicon_channel_host: at most %d rules" % CHANNEL_RULES_MAX)
+    kept = channel_rules_kept(rules, rule_cost, V)
+    n_class = np.diff(class_first)
+    base = np.concatenate([[0], np.cumsum(np.arange(SPAN_LEN_MAX + 1) * n_class)])
+    if (len(class_first) != SPAN_LEN_MAX + 2 or class_first[0] != 0 or class_first[1] != 0 or (n_class < 0).any()
+            or class_first[-1] != len(order) or base[-1] != len(chars)):
+        raise ValueError("lexicon_channel_host: class_first [66] ascending from 0, 0 to len(order), chars of sum L * n_L ids")
+    if len(q_off) < 1 or q_off[0] < 0 or (np.diff(q_off) < 0).any() or q_off[-1] > len(q_pool):
+        raise ValueError("lexicon_channel_host: q_off [Q + 1] ascending within the pool")
+    # how far a length may lie from the query's: d * (num / den) <= max_cost
+    reach = []
+    for longer in (True, False):
+        num, den = unit, 1
+        for src, tgt, cost in kept:
+            by = len(tgt) - len(src) if longer else len(src) - len(tgt)
+            if by > 0 and cost * den < num * by:
+                num, den = cost, by
+        reach.append(SPAN_LEN_MAX if num == 0 else min(SPAN_LEN_MAX, max_cost * den // num))
+    Q = len(q_off) - 1
+    exact = np.full(Q, -1, dtype=np.int32)
+    found = np.zeros(Q, dtype=np.int32)
+    cand = np.full((Q, K), -1, dtype=np.int32)
+    cost_out = np.full((Q, K), -1, dtype=np.int32)
+    known = (chars >= 0) & (chars < V)
+    beyond = max_cost + 1      # (every larger value is as good as this one)
+    tables = {}                # (class, rules of one shape) -> [L + 1, n]: the least cost of those whose target ends at column j
+    for q in range(Q):
+        word = q_pool[q_off[q]:q_off[q + 1]]
+        m = len(word)
+        if not 1 <= m <= SPAN_LEN_MAX:
+            continue
+        word = np.where((word >= 0) & (word < V), word, -1)
+        # the rules whose source stands in front of row i, by shape (s, t)
+        active = [{} for _ in range(m + 1)]
+        for r, (src, tgt, cost) in enumerate(kept):
+            s = len(src)
+            for i in range(s, m + 1):
+                if tuple(word[i - s:i].tolist()) == src:
+                    active[i].setdefault((s, len(tgt)), []).append(r)
+        active = [[(s, t, tuple(rows)) for (s, t), rows in sorted(one.items())] for one in active]
+        hits, costs, sames = [], [], []
+        for L in range(max(1, m - reach[1]), min(SPAN_LEN_MAX, m + reach[0]) + 1):
+            n = int(n_class[L])
+            if n == 0:
+                continue
+            entry = np.where(known[base[L]:base[L + 1]], chars[base[L]:base[L + 1]], -2).reshape(L, n)
+            W = np.full((m + 1, L + 1, n), beyond, dtype=np.int64)
+            W[0, 0] = 0
+            for j in range(L + 1):
+                for i in range(m + 1):
+                    v = W[i, j]
+                    if i > 0:
+                        v = np.minimum(v, W[i - 1, j] + unit)
+                    if j > 0:
+                        v = np.minimum(v, W[i, j - 1] + unit)
+                    if i > 0 and j > 0:
+                        v = np.minimum(v, W[i - 1, j - 1] + np.where(entry[j - 1] == word[i - 1], 0, unit))
+                    for s, t, rows in active[i]:
+                        if j < t:
+                            continue
+                        if (L, rows) not in tables:
+                            least = np.full((L + 1, n), beyond, dtype=np.int64)
+                            for r in rows:
+                                tgt, cost = kept[r][1], kept[r][2]
+                                if t <= L:
+                                    ends = np.ones((L - t + 1, n), dtype=bool)
+                                    for k in range(t):
+                                        ends &= entry[k:L - t + 1 + k] == tgt[k]
+                                    least[t:] = np.where(ends, np.minimum(least[t:], cost), least[t:])
+                            tables[L, rows] = least
+                        v = np.minimum(v, W[i - s, j - t] + tables[L, rows][j])
+                    W[i, j] = np.minimum(v, beyond)
+            w = W[m, L]
+            near = np.nonzero(w <= max_cost)[0]
+            hits.append(order[class_first[L] + near])
+            costs.append(w[near])
+            sames.append((entry[:, near] == word[:, None]).all(axis=0) if L == m else np.zeros(len(near), dtype=bool))
+        if len(tables) > 1024:      # (the tables of one call, bounded)
+            tables.clear()
+        if not hits:
+            continue
+        hits, costs, sames = np.concatenate(hits), np.concatenate(costs), np.concatenate(sames)
+        if sames.any():
+            exact[q] = hits[sames].min()
+        hits, costs = hits[~sames], costs[~sames]
+        found[q] = len(hits)
+        first = np.lexsort((hits, costs))[:K]
+        cand[q, :len(first)] = hits[first]
+        cost_out[q, :len(first)] = costs[first]
+    return exact, found, cand, cost_out
+
+
 ALIGN_DIST_MAX, ALIGN_LEN_MAX = 255, 4096      # (KL_ALIGN_* of the C ABI)
 _BEYOND = 1 << 20                              # a value outside the band
 

@@ -1585,7 +1585,8 @@ class Rater(object):
         return [ratebatch.Corrections(*one)
                 for one in self._selection_per_text(list(sel) + [cost, best_id, gain, best_op], offsets)], bits
 
-    def rescore(self, texts, edits, contexts=None, streams=1024, left=64, ahead=8, min_gain=1.0, precision="bf16", want_costs=True):
+    def rescore(self, texts, edits, contexts=None, streams=1024, left=64, ahead=8, min_gain=1.0, precision="bf16", want_costs=True,
+                prior=None):
         '''Does a text read better with one of the caller's replacements for a span of it?  `corrections` for readings that come
         from outside the model -- a second OCR engine, a lexicon, a table of confusions (`ratebatch.confusion_edits`) --, many
         characters for many.  edits is a sequence of (i, start, end, candidates): [start, end) is a span of the NFC-normalised
@@ -1611,7 +1612,13 @@ class Rater(object):
         only 12 bytes per span leave the device (cost0 and cost are None).  ValueError for a stateless rater, left < 1,
         ahead < 0, a text index out of range, a span outside its text or with end < start, a span or candidate longer than 64
         characters, left + ahead + M - 1 > 1024.  No edits, or only spans that cannot hold a prediction, give their results
-        without a launch.  State and precision afterwards are as after `suspects`.'''
+        without a launch.  State and precision afterwards are as after `suspects`.
+
+        prior (None: the model's bits alone, the path above with nothing added) is a sequence parallel to `edits` of
+        per-candidate bits >= 0 from outside the model -- what a candidate costs under a channel (`correct_words(channel=..)`).
+        They are added in f64 to the candidates' rows before the pick, the text as written gets nothing: `cost` then holds
+        the sums, `best` and `gain` are taken over them.  On the device that is one add of an uploaded array.  ValueError for
+        a prior of another shape than the edits' candidates, or a negative or non-finite value.'''
         texts, contexts = self._rating_request("rescore", texts, contexts, precision)[:2]
         if not self.stateful:
             raise ValueError('rescore needs a stateful rater: it rates through stateful windows')
@@ -1636,6 +1643,16 @@ class Rater(object):
             raise ValueError("left + ahead + %d - 1 <= 1024 (got %d, %d)" % (M, left, ahead))
         T = max(left + ahead + M - 1, ratebulk.MIN_T)
         span_first = np.concatenate([[0], np.cumsum(count)]).astype(np.int64)
+        prior_rows = None
+        if prior is not None:
+            prior = [np.asarray(one, dtype=np.float64).reshape(-1) for one in prior]
+            if len(prior) != S or any(len(one) != c for one, c in zip(prior, count)):
+                raise ValueError("rescore: prior holds one value per candidate of every edit")
+            flat = np.concatenate(prior) if prior else np.zeros(0, dtype=np.float64)
+            if not (np.isfinite(flat).all() and (flat >= 0.0).all()):
+                raise ValueError("rescore: prior values are bits >= 0, finite")
+            prior_rows = np.zeros(S + C, dtype=np.float64)      # (candidate c of span s has row c + s + 1)
+            prior_rows[np.arange(C, dtype=np.int64) + np.repeat(np.arange(S, dtype=np.int64), count) + 1] = flat
         if precision == "split":
             self._ensure_precision()
         cost = np.full(S + C, np.inf, dtype=np.float64) if want_costs else None
@@ -1661,6 +1678,8 @@ class Rater(object):
                 where = [up(a) for a in (corpus, offsets)] + [up(text_ctx) if lm.n_ctx else None]
                 spans = [up(a) for a in (span_text, span_start, span_len, span_first, pool, cand_off)]
                 cost_d, valid_d = self._span_row_costs(where, spans, chunks, precision, left, ahead, M, T)
+                if prior_rows is not None:
+                    cost_d = cost_d + up(prior_rows)
                 best_d, gain_d, cost_d = lm.span_pick(cost_d, valid_d, spans[3], float(min_gain), want_costs=want_costs)
                 lm.rate_status_check()
                 best, gain = _np(best_d), _np(gain_d)
@@ -1671,6 +1690,8 @@ class Rater(object):
                 # choice, the whole softmax of every window and the logs summed on the host
                 costs, valids = self._span_row_costs([corpus, offsets, text_ctx], [span_text, span_start, span_len, span_first, pool,
                                                                                    cand_off], chunks, precision, left, ahead, M, T)
+                if prior_rows is not None:
+                    costs = costs + prior_rows
                 best, gain, all_costs = ratebulk.span_pick_host(costs, valids, span_first, float(min_gain))
                 if want_costs:
                     cost = all_costs
@@ -1706,6 +1727,27 @@ class Rater(object):
         assert self.status > 1
         return ratebatch.Lexicon(words, self.mapping[0], self.voc_size)
 
+    def channel(self, records, unit_bits=8.0, min_count=2, min_rate=0.0):
+        '''A ratebatch.Channel from a table of confusions: what `lexicon_neighbours` and `correct_words` weigh the way from a
+        word to a lexicon entry with.  records is `confusions`' result or an iterable of (source, target, count, occ) -- what
+        `keraslm-rate confusions --counts` prints --, the source being what the OCR reads for the target; the strings are
+        normalised and encoded with this rater's mapping.  A record costs round(16 * min(-log2(count / occ), 255))
+        sixteenths of a bit, a plain edit round(16 * unit_bits).  Dropped and counted in `.dropped`: records below min_count
+        or min_rate, with an empty source, a source equal to the target, a character outside the mapping, a side of more than
+        4 characters; duplicates (the least cost is kept) and, beyond 1024 rules, those of least count.  Its device copy is
+        made at the first look-up on an engine and kept.  ValueError for unit_bits outside 1/16 .. 255.9.'''
+        assert self.status > 1
+        return ratebatch.Channel(records, self.mapping[0], self.voc_size, unit_bits=unit_bits, min_count=min_count,
+                                 min_rate=min_rate)
+
+    def _channel_request(self, method, channel, max_bits):
+        max_bits = float(max_bits)
+        if not 0.0 <= max_bits <= 255.9:
+            raise ValueError("%s: max_bits in 0 .. 255.9 (got %r)" % (method, max_bits))
+        if not isinstance(channel, ratebatch.Channel) or not channel.same_mapping(self.mapping[0]) or channel.voc_size != self.voc_size:
+            raise ValueError("%s: the channel was not built by this rater's `channel`, or the mapping has changed since" % method)
+        return int(round(ratebulk.CHANNEL_SCALE * max_bits))
+
     def _lexicon_request(self, method, lexicon, max_dist, per_word):
         max_dist, per_word = int(max_dist), int(per_word)
         if not (0 <= max_dist <= ratebulk.LEXICON_DIST_MAX and 1 <= per_word <= ratebulk.LEXICON_K_MAX):
@@ -1715,7 +1757,7 @@ class Rater(object):
             raise ValueError("%s: the lexicon was not built by this rater's `lexicon`, or the mapping has changed since" % method)
         return max_dist, per_word
 
-    def lexicon_neighbours(self, words, lexicon, max_dist=2, per_word=8):
+    def lexicon_neighbours(self, words, lexicon, max_dist=2, per_word=8, channel=None, max_bits=12.0):
         '''Which entries of the lexicon could these words have been?  Returns a ratebatch.Neighbours in input order: per word
         `exact` (its own index in `lexicon.words`, -1: not an entry), `found` (how many entries lie within 1 .. max_dist
         edits -- Levenshtein distance, unit costs) and the first `per_word` of them ordered by (distance, index), that is the
@@ -1728,9 +1770,16 @@ class Rater(object):
         0 is an ordinary id of the look-up: two different unmapped characters are equal, as in `rescore` -- but no entry holds
         one, so such a position always costs an edit.  No words, or a lexicon without an entry, give their result without a
         launch.  An engine without `lexicon_neighbours` (the tests' CPU double) runs ratebulk.lexicon_neighbours_host.
-        ValueError for max_dist outside 0 .. 8, per_word outside 1 .. 16, a lexicon of another mapping.'''
+        ValueError for max_dist outside 0 .. 8, per_word outside 1 .. 16, a lexicon of another mapping.
+
+        With a channel (`channel`) the search is the weighted one (`HipLM.lexicon_channel`, the statement
+        ratebulk.lexicon_channel_host): the entries within max_cost = round(16 * max_bits) sixteenths of a bit, a plain edit
+        at the channel's unit and every rule at its cost; max_dist is not used, `exact` is the entry identical to the word,
+        `dist` holds sixteenths of a bit and `bits` their float value (None without a channel).  The rules are uploaded once
+        per channel and engine.  ValueError for a channel of another mapping, or max_bits outside 0 .. 255.9.'''
         assert self.status > 1
         max_dist, K = self._lexicon_request("lexicon_neighbours", lexicon, max_dist, per_word)
+        max_cost = None if channel is None else self._channel_request("lexicon_neighbours", channel, max_bits)
         words = [windows.normalize(w) for w in words]
         slot = {}
         for w in words:
@@ -1743,24 +1792,34 @@ class Rater(object):
             pool = windows.encode("".join(unique), self.mapping[0]).astype(np.int32)
             q_off = np.concatenate([[0], np.cumsum([len(w) for w in unique])]).astype(np.int64)
             lm = self.model
-            if hasattr(lm, 'lexicon_neighbours'):
+            if hasattr(lm, 'lexicon_channel' if channel is not None else 'lexicon_neighbours'):
                 torch = lm.torch
                 chars_d, order_d = lexicon.on_device(lm)
                 both = torch.from_numpy(np.concatenate([q_off.view(np.int32), pool])).to(lm.device)
-                res = lm.lexicon_neighbours(chars_d, order_d, lexicon.class_first, self.voc_size, both[2 * (Q + 1):],
-                                            both[:2 * (Q + 1)].view(torch.int64), max_dist, K)
+                if channel is not None:
+                    res = lm.lexicon_channel(chars_d, order_d, lexicon.class_first, self.voc_size, both[2 * (Q + 1):],
+                                             both[:2 * (Q + 1)].view(torch.int64), *channel.on_device(lm), channel.unit, max_cost, K)
+                else:
+                    res = lm.lexicon_neighbours(chars_d, order_d, lexicon.class_first, self.voc_size, both[2 * (Q + 1):],
+                                                both[:2 * (Q + 1)].view(torch.int64), max_dist, K)
                 out = _np(torch.cat([res[0][:, None], res[1][:, None], res[2], res[3]], dim=1))
+            elif channel is not None:
+                res = ratebulk.lexicon_channel_host(pool, q_off, lexicon.chars, lexicon.order, lexicon.class_first, self.voc_size,
+                                                    channel.rules, channel.cost, channel.unit, max_cost, K)
+                out = np.concatenate([res[0][:, None], res[1][:, None], res[2], res[3]], axis=1)
             else:
                 res = ratebulk.lexicon_neighbours_host(pool, q_off, lexicon.chars, lexicon.order, lexicon.class_first,
                                                        self.voc_size, max_dist, K)
                 out = np.concatenate([res[0][:, None], res[1][:, None], res[2], res[3]], axis=1)
         rows = np.asarray([slot[w] for w in words], dtype=np.int64)
         out = out[rows] if len(rows) else out[:0]
-        return ratebatch.Neighbours(lexicon, out[:, 0].copy(), out[:, 1].copy(), out[:, 2:2 + K].copy(), out[:, 2 + K:].copy())
+        dist = out[:, 2 + K:].copy()
+        bits = None if channel is None else np.where(dist >= 0, dist / float(ratebulk.CHANNEL_SCALE), np.nan)
+        return ratebatch.Neighbours(lexicon, out[:, 0].copy(), out[:, 1].copy(), out[:, 2:2 + K].copy(), dist, bits)
 
     def correct_words(self, texts, lexicon, contexts=None, max_dist=2, per_word=8, known=False, delimiters=None, k=3,
                       max_prob=0.01, min_rank=1, min_suspects=1, min_bits_per_char=0.0, min_chars=1, left=64, ahead=8,
-                      min_gain=1.0, streams=1024, precision="bf16"):
+                      min_gain=1.0, streams=1024, precision="bf16", channel=None, max_bits=12.0, channel_weight=1.0):
         '''From texts to lexicon-backed corrections: `suspect_words` -> the suspect words' nearest lexicon entries ->
         `rescore`.  Returns (found, rescored, bits): `found` and `bits` are `suspect_words(texts, contexts, delimiters=..,
         k=.., max_prob=.., min_rank=.., min_suspects=.., min_bits_per_char=.., min_chars=.., streams=.., precision=..)`'s;
@@ -1769,21 +1828,37 @@ class Rater(object):
         --, every other word its neighbours in order; `rescored` is `rescore(texts, ratebatch.word_edits(found, texts, table),
         contexts, streams=.., left=.., ahead=.., min_gain=.., precision=..)` with `table` the dict word -> neighbour strings.
         The edits are built on the host from the downloaded neighbours (8 bytes per candidate).  State and precision afterwards
-        are as after `rescore`.  ValueError for what these three raise.'''
+        are as after `rescore`.  ValueError for what these three raise.
+
+        With a channel (`channel`) the candidates are `lexicon_neighbours(words, lexicon, per_word=.., channel=..,
+        max_bits=..)`'s -- the entries that are cheap under the learned confusions, max_dist is not used -- and the channel's
+        bits enter the choice beside the model's: `rescore(.., prior=..)` with channel_weight * bits per candidate
+        (`ratebatch.word_edits` returns them beside the edits).  channel_weight = 0.0 lets the model alone choose among the
+        channel's candidates.  ValueError also for channel_weight < 0 or not finite.'''
         self._lexicon_request("correct_words", lexicon, max_dist, per_word)
+        channel_weight = float(channel_weight)
+        if channel is not None:
+            self._channel_request("correct_words", channel, max_bits)
+            if not (np.isfinite(channel_weight) and channel_weight >= 0.0):
+                raise ValueError("correct_words: channel_weight >= 0, finite (got %r)" % channel_weight)
         texts = list(texts)
         found, bits = self.suspect_words(texts, contexts, delimiters=delimiters, k=k, streams=streams, max_prob=max_prob,
                                          min_rank=min_rank, min_suspects=min_suspects, min_bits_per_char=min_bits_per_char,
                                          min_chars=min_chars, precision=precision)
         words = [w for one, text in zip(found, texts) for w in one.strings(windows.normalize(text))]
-        near = self.lexicon_neighbours(words, lexicon, max_dist=max_dist, per_word=per_word)
-        table = {}
+        near = self.lexicon_neighbours(words, lexicon, max_dist=max_dist, per_word=per_word, channel=channel, max_bits=max_bits)
+        table, weights = {}, {}
         for i, word in enumerate(words):
             if word not in table:
                 table[word] = near.strings(i) if known or near.exact[i] < 0 else []
-        edits = ratebatch.word_edits(found, texts, table)
+                if channel is not None:
+                    weights[word] = [channel_weight * float(b) for b in near.bits[i][:len(table[word])]]
+        if channel is None:
+            edits, prior = ratebatch.word_edits(found, texts, table), None
+        else:
+            edits, prior = ratebatch.word_edits(found, texts, table, priors=weights)
         rescored = self.rescore(texts, edits, contexts, streams=streams, left=left, ahead=ahead, min_gain=min_gain,
-                                precision=precision)
+                                precision=precision, prior=prior)
         return found, rescored, bits
 
     def align(self, texts, others, max_dist=32, join=0):

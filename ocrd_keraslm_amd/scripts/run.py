@@ -23,7 +23,8 @@ Additional command `words`: per DATA file the words the model does not believe -
 probability (Rater.suspect_words: rated in bulk, the words found, rated and picked out on the device).
 Additional command `lexicon`: the suspect words of every DATA file looked up in a word list (--lexicon, the most frequent entry
 first) on the device, and their nearest entries rated against the text around them (Rater.correct_words: suspect_words ->
-lexicon_neighbours -> rescore); output as `rescore`'s, --apply also gives the corrected text.
+lexicon_neighbours -> rescore); output as `rescore`'s, --apply also gives the corrected text.  With --channel FILE (the JSON
+lines of `confusions --counts`) the look-up weighs the learned confusions and their bits enter the choice (Rater.channel).
 Additional command `witnesses`: every DATA file aligned with other readings of it (--witness DIR: the file of the same base
 name) on the device, and the readings of the spans where they differ rated against the text around them
 (Rater.merge_witnesses: align -> witness_edits -> rescore); --apply also gives the corrected text.
@@ -558,6 +559,13 @@ def _read_lexicon(path):
         return [line.rstrip('\r\n').split('\t')[0] for line in file]
 
 
+def _read_channel(path):
+    """the JSON lines of `confusions --counts` as (source, target, count, occ); empty lines are skipped"""
+    with open(path, mode='r') as file:
+        records = [json.loads(line) for line in file if line.strip()]
+    return [(r["source"], r["target"], r["count"], r["occ"]) for r in records]
+
+
 @cli.command('lexicon', short_help='correct the words the model does not believe from a word list')
 @click.option('-m', '--model', default="model.h5", show_default=True, help='model file', type=click.Path(dir_okay=False, exists=True))
 @click.option('--lexicon', 'lexicon_file', required=True, type=click.Path(dir_okay=False, exists=True),
@@ -591,21 +599,44 @@ def _read_lexicon(path):
 @click.option('--min-gain', default=1.0, show_default=True, type=click.FLOAT,
               help='a proposal must save at least this many bits against the text as written')
 @click.option('--apply', 'apply_', is_flag=True, default=False, help='also give the text with the proposals applied ("corrected")')
+@click.option('--channel', 'channel_file', default=None, type=click.Path(dir_okay=False, exists=True),
+              help='table of confusions, the JSON lines of `confusions --counts`: the candidates of a word are the entries that are '
+                   'cheap under these confusions (--max-dist is not used), and what they cost enters the choice')
+@click.option('--unit-bits', default=8.0, show_default=True, type=click.FloatRange(min=0.0625, max=255.9),
+              help='with --channel: bits of an insertion, deletion or substitution that no confusion explains')
+@click.option('--max-bits', default=12.0, show_default=True, type=click.FloatRange(min=0.0, max=255.9),
+              help='with --channel: an entry is a candidate for a word within this many bits')
+@click.option('--channel-weight', default=1.0, show_default=True, type=click.FloatRange(min=0.0),
+              help="with --channel: a candidate's bits under the channel count this much beside the model's (0: the model alone chooses)")
+@click.option('--min-count', default=2, show_default=True, type=click.IntRange(min=0),
+              help='with --channel: a confusion was seen at least this often')
+@click.option('--min-rate', default=0.0, show_default=True, type=click.FLOAT,
+              help='with --channel: ... and at no less than this share of the occurrences of its source')
 @click.argument('data', nargs=-1, type=click.Path(exists=True, dir_okay=True, file_okay=True))
 def lexicon_(model, lexicon_file, max_dist, per_word, known, streams, precision, k, max_prob, min_rank, min_suspects,
-             min_bits_per_char, min_chars, delimiters, left, ahead, min_gain, apply_, data):
+             min_bits_per_char, min_chars, delimiters, left, ahead, min_gain, apply_, channel_file, unit_bits, max_bits,
+             channel_weight, min_count, min_rate, data):
     """Apply a language model to DATA files, look the words it does not believe up in the word list and
        print one JSON line per file, as `rescore` does: characters and "rescored": one [start, end, written,
        proposed, gain] per word that has candidates -- proposed is the entry that replaces text[start:end],
        null for no proposal.  With --apply the line also holds the corrected text.
 
        Files are read, and given their contexts, as `score` does; the words are chosen as `words` chooses them.
+
+       With --channel (what `confusions --counts` printed for OCR of the same kind) the look-up is the
+       noisy-channel one: an entry costs what the learned confusions and --unit-bits per unexplained edit make
+       of the way from it to the word, the candidates are the cheapest entries within --max-bits, and
+       --channel-weight times these bits are added to the model's before the choice.
     """
     from ..lib import windows
     rater = _load(model)
+    channel = {}
     try:
         lexicon = rater.lexicon(_read_lexicon(lexicon_file))
-    except ValueError as err:
+        if channel_file is not None:
+            channel = dict(channel=rater.channel(_read_channel(channel_file), unit_bits=unit_bits, min_count=min_count,
+                                                 min_rate=min_rate), max_bits=max_bits, channel_weight=channel_weight)
+    except (ValueError, KeyError, TypeError) as err:
         raise click.UsageError(str(err))
     names, texts, contexts = [], [], []
     for file in _open_all(data):
@@ -619,7 +650,8 @@ def lexicon_(model, lexicon_file, max_dist, per_word, known, streams, precision,
         _, found, _ = rater.correct_words(texts, lexicon, contexts, max_dist=max_dist, per_word=per_word, known=known,
                                           delimiters=delimiters, k=k, max_prob=max_prob, min_rank=min_rank,
                                           min_suspects=min_suspects, min_bits_per_char=min_bits_per_char, min_chars=min_chars,
-                                          left=left, ahead=ahead, min_gain=min_gain, streams=streams, precision=precision)
+                                          left=left, ahead=ahead, min_gain=min_gain, streams=streams, precision=precision,
+                                          **channel)
     except ValueError as err:
         raise click.UsageError(str(err))
     for name, text, one in zip(names, texts, found):
