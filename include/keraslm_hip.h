@@ -24,6 +24,7 @@
  *       (the processor's mean probability per TextEquiv substring, wrapper/rate.py:308-317, for a whole corpus)
  *   ... and the suspect words' nearest entries of a lexicon, as replacements   kl_lexicon_neighbours
  *   ... or, under a table of learned confusions, its cheapest entries in a weighted distance   kl_lexicon_channel
+ *   ... or, where a space was lost, the pairs of entries a run-together word falls into   kl_lexicon_splits
  *   ... and the spans where a second reading of the text (another OCR engine) differs   kl_align_pairs
  *   ... and, against ground truth, the table of confusions these spans amount to   kl_confusion_counts
  *   ... and, with several such readings, their spans clustered and the readings counted   kl_witness_clusters, kl_witness_pool
@@ -568,6 +569,44 @@ int kl_lexicon_channel(const int32_t* chars, size_t n_chars, const int32_t* orde
                        const int32_t* q_pool, size_t n_q, const int64_t* q_off, size_t Q, const int32_t* rules,
                        const int32_t* rule_cost, int R, int unit, int max_cost, int K, int32_t* exact, int32_t* found,
                        int32_t* cand, int32_t* cost, void* ws, size_t ws_bytes, void* stream);
+
+/* Lexicon look-up across a lost space: at which places does a query word fall into two entries of the lexicon?  The run-together
+ * word (`ofthe`) beside kl_lexicon_neighbours' single entries; a spurious space (`to gether`) needs no call of its own -- the
+ * joined string is an ordinary query of kl_lexicon_neighbours.  No handle.  The lexicon (chars, n_chars, order, class_first), the
+ * queries (q_pool, n_q, q_off, Q), V and the id equality are kl_lexicon_neighbours': an id outside [0, V) equals nothing, itself
+ * included.
+ *
+ * max_dist, 1 .. KL_LEXICON_DIST_MAX, is the budget of the whole split; the missing delimiter itself costs one edit, so the two
+ * halves share d = max_dist - 1.  min_part, 1 .. 32, is the least number of ids of a half.  For a query q of m ids, 1 <= m <= 64,
+ * and every split point s with min_part <= s <= m - min_part:
+ *   best(h)   for a half h the entry minimising (lev(h, e), original index) among the entries with lev(h, e) <= d; entries at
+ *             distance 0 count, duplicate entries are separate entries;
+ *   s is VALID iff best(q[:s]) and best(q[s:]) both exist and total = 1 + lev_left + lev_right <= max_dist.
+ * Outputs (device int32; found [Q]; split, left, right, dist [Q][K]; OVERWRITTEN for every q < Q, nothing behind them written):
+ *   found[q]                       the number of valid split points, whatever K is;
+ *   split, left, right, dist[q][0..K)   s, the original indices of best(q[:s]) and best(q[s:]), and total, of the first K valid
+ *                                  split points ordered by (total, max(left index, right index), s) -- the nearest pair first,
+ *                                  among equally near pairs the one whose rarer half is more frequent; unused places are -1 in
+ *                                  all four.
+ * A query with no split point (m < 2 * min_part), of no ids, of more than 64 or with bad offsets gets found 0 and -1 everywhere,
+ * and nothing of the lexicon is read for it.  The statement is ratebulk.lexicon_splits_host.
+ *
+ * One workgroup of 256 threads per query.  Pairs of entries are never formed: after Myers' column has consumed an entry of L ids,
+ * its vertical deltas hold lev(q[:i], e) for every prefix length i at once (D[i] = L + popc(Pv & low(i)) - popc(Mv & low(i))), and
+ * the same walk with the reversed query over the entry read back to front holds every suffix.  Two passes over the length
+ * classes max(1, min_part - d) .. min(64, m - min_part + d) (Peq[V] in LDS; the 32-bit pattern word for m <= 32 unless
+ * KL_LEXICON_NARROW=0, same results) lower one key (lev << 32 | original index) per split point and side with a 64-bit unsigned
+ * minimum in LDS; then thread s ranks total << 37 | max index << 6 | s among the at most 63 keys.  Two plain launches on `stream`
+ * (the class table into ws, then the look-up), no atomics on global memory, no workgroup waits for another, and a minimum does
+ * not depend on the order of arrival: two calls agree bit for bit.  ws: device scratch of
+ * kl_lexicon_splits_workspace_bytes(Q, K) bytes (the class table), 8-byte aligned, not to be shared by calls that may overlap.
+ * KL_ERR_ARG, before any launch and with nothing touched, for what kl_lexicon_neighbours rejects (max_dist 0 too) and for
+ * min_part outside 1 .. 32; KL_ERR_WORKSPACE if ws_bytes is too small. */
+size_t kl_lexicon_splits_workspace_bytes(size_t Q, int K);
+int kl_lexicon_splits(const int32_t* chars, size_t n_chars, const int32_t* order, const int64_t* class_first, int V,
+                      const int32_t* q_pool, size_t n_q, const int64_t* q_off, size_t Q, int max_dist, int min_part, int K,
+                      int32_t* found, int32_t* split, int32_t* left, int32_t* right, int32_t* dist, void* ws, size_t ws_bytes,
+                      void* stream);
 
 /* Alignment of two readings: where do the texts of P pairs differ?  The step in front of kl_span_windows for a second witness of
  * the same line or page (another OCR engine): the differing spans become the spans and replacements it rates.  No handle.

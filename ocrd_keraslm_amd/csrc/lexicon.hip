@@ -7,7 +7,7 @@
 // most 64 ids; a query of at most 32 runs the same steps on 32-bit words (the VALU has no 64-bit add or shift: 10.7 against
 // 12.1 ms for 20 000 words against 228 576 entries; KL_LEXICON_NARROW=0 switches it off).  Peq[V] lies in LDS (V * 8 bytes,
 // only the query's own ids are non-zero); an id outside [0, V) on either side never reaches the table: it has no bit and
-// matches nothing.
+// matches nothing.  (The step and the class table are kl_lexicon_myers.h's, shared with kl_lexicon_splits.)
 //
 // Every lane then walks whole entries of the length classes max(1, m - max_dist) .. min(64, m + max_dist) -- other lengths
 // cannot be within max_dist --, one character per step from the column-major layout (consecutive lanes read consecutive
@@ -18,64 +18,11 @@
 // workgroup waits for another, the output depends on the inputs only.  No model: no handle.
 #include "keraslm_hip.h"
 #include "kl_common.h"
+#include "kl_lexicon_myers.h"
 #include "kl_lexicon_topk.h"
 #include <stdlib.h>
 
 namespace {
-
-constexpr int LEX_THREADS = 256;
-constexpr int LEX_WAVES = LEX_THREADS / KL_WAVE;
-constexpr int LEX_LEN_MAX = 64;      // ids of a query and of an entry at most: one pattern word
-constexpr size_t MAX_QUERIES = 0x7FFFFFFF;      // (one workgroup per query in one grid)
-constexpr size_t MAX_POOL = (size_t)1 << 40;
-static_assert(KL_LEXICON_V_MAX * 8 <= 32 * 1024, "Peq fits 32 KiB of LDS");
-
-constexpr int LEX_CLASSES = LEX_LEN_MAX + 2;
-// the length classes, checked on the host: entries of length L are the sorted positions [first[L], first[L + 1]) and their
-// characters begin at chars[base[L]]
-struct lex_classes {
-  long long first[LEX_CLASSES];
-  long long base[LEX_CLASSES];
-};
-
-// the class table from a launch's arguments to the workspace, every index into the arguments a constant (an index known at run
-// time only would send the table through scratch): table[L] = first[L], table[LEX_CLASSES + L] = base[L]
-__global__ void __launch_bounds__(2 * KL_WAVE) lexicon_classes_kernel(const lex_classes cls, long long* __restrict__ table) {
-#pragma unroll
-  for (int i = 0; i < LEX_CLASSES; ++i)
-    if ((int)threadIdx.x == i) {
-      table[i] = cls.first[i];
-      table[LEX_CLASSES + i] = cls.base[i];
-    }
-}
-
-// one text character against the pattern column (Pv, Mv: vertical deltas +1 / -1; score: the distance to the whole pattern); the
-// pattern word W is 64 bits, or 32 for a query of at most 32 ids (half the instructions: the VALU has no 64-bit add or shift)
-template <typename W>
-__device__ __forceinline__ void myers_step(W Eq, W top, W& Pv, W& Mv, int& score) {
-  const W Xv = Eq | Mv;
-  const W Xh = (((Eq & Pv) + Pv) ^ Pv) | Eq;
-  W Ph = Mv | ~(Xh | Pv);
-  W Mh = Pv & Xh;
-  score += (Ph & top) ? 1 : 0;
-  score -= (Mh & top) ? 1 : 0;
-  Ph = (Ph << 1) | (W)1;      // (row 0 of the global distance grows by one per text character)
-  Mh <<= 1;
-  Pv = Mh | ~(Xv | Ph);
-  Mv = Ph & Xv;
-}
-
-// the match mask of id c for the pattern word: the whole word of Peq, or its low half
-template <typename W>
-__device__ __forceinline__ W match_mask(const unsigned long long* peq, int c, int V);
-template <>
-__device__ __forceinline__ unsigned long long match_mask<unsigned long long>(const unsigned long long* peq, int c, int V) {
-  return (c >= 0 && c < V) ? peq[c] : 0ull;
-}
-template <>
-__device__ __forceinline__ unsigned int match_mask<unsigned int>(const unsigned long long* peq, int c, int V) {
-  return (c >= 0 && c < V) ? reinterpret_cast<const unsigned int*>(peq)[2 * c] : 0u;
-}
 
 // a lane's walk over the entries e = tid, tid + LEX_THREADS, .. of every length class that can hold a neighbour of a query of m
 // ids: its KL_LEXICON_K_MAX smallest keys (sorted), the least index at distance 0 and the number within 1 .. max_dist
@@ -163,8 +110,6 @@ __global__ void __launch_bounds__(LEX_THREADS) lexicon_neighbours_kernel(
   kl_lex_fold_out<LEX_WAVES>(s_fold, best, least_exact, n_found, K, q, exact, found, cand, dist);
 }
 
-inline bool misaligned(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
-
 }  // namespace
 
 extern "C" size_t kl_lexicon_neighbours_workspace_bytes(size_t Q, int K) {
@@ -181,23 +126,14 @@ extern "C" int kl_lexicon_neighbours(const int32_t* chars, size_t n_chars, const
   if (n_q > 0 && !q_pool) return KL_ERR_ARG;
   if (V < 1 || V > KL_LEXICON_V_MAX || max_dist < 0 || max_dist > KL_LEXICON_DIST_MAX || K < 1 || K > KL_LEXICON_K_MAX)
     return KL_ERR_ARG;
-  if (Q < 1 || Q > MAX_QUERIES || n_q > MAX_POOL || n_chars > MAX_POOL) return KL_ERR_ARG;
+  if (Q < 1 || Q > LEX_MAX_QUERIES || n_q > LEX_MAX_POOL || n_chars > LEX_MAX_POOL) return KL_ERR_ARG;
   const void* words[] = {chars, order, q_pool, exact, found, cand, dist};
   for (const void* p : words)
-    if (misaligned(p, 3)) return KL_ERR_ARG;
-  if (misaligned(q_off, 7) || misaligned(class_first, 7) || misaligned(ws, 7)) return KL_ERR_ARG;
+    if (lex_misaligned(p, 3)) return KL_ERR_ARG;
+  if (lex_misaligned(q_off, 7) || lex_misaligned(class_first, 7) || lex_misaligned(ws, 7)) return KL_ERR_ARG;
   // the class table: every address the kernel forms is checked here
   lex_classes cls;
-  if (class_first[0] != 0 || class_first[1] != 0) return KL_ERR_ARG;
-  for (int L = 1; L <= LEX_LEN_MAX + 1; ++L)
-    if (class_first[L] < class_first[L - 1] || class_first[L] > 0x7FFFFFFFll) return KL_ERR_ARG;
-  long long total = 0;      // (at most 64 * 2^31)
-  for (int L = 0; L <= LEX_LEN_MAX + 1; ++L) {
-    cls.first[L] = class_first[L];
-    cls.base[L] = total;
-    if (L <= LEX_LEN_MAX) total += (long long)L * (class_first[L + 1] - class_first[L]);
-  }
-  if (class_first[LEX_LEN_MAX + 1] < 1 || (unsigned long long)total != (unsigned long long)n_chars) return KL_ERR_ARG;
+  if (!lex_classes_checked(class_first, n_chars, cls)) return KL_ERR_ARG;
   if (ws_bytes < kl_lexicon_neighbours_workspace_bytes(Q, K)) return KL_ERR_WORKSPACE;
   // KL_LEXICON_NARROW=0: the 64-bit pattern word for every query (the A/B switch of tools/bench_lexicon.py)
   const char* env = getenv("KL_LEXICON_NARROW");

@@ -98,6 +98,7 @@ class HipLM:
         self._segment_select_ws = None
         self._lexicon_ws = None
         self._lexicon_channel_ws = None
+        self._lexicon_splits_ws = None
         self._align_ws = None
         self._confusion_ws = None
         self._witness_ws = None
@@ -783,6 +784,32 @@ class HipLM:
                 _ptr(chars_d), chars_d.numel(), _ptr(order_d), class_first.ctypes.data, V, _ptr(q_pool_d), q_pool_d.numel(),
                 _ptr(q_off_d), Q, max_dist, K, *([_ptr(t) for t in out] + [_ptr(ws), ws.numel(), self._stream()])),
                 "kl_lexicon_neighbours")
+        return out
+
+    def lexicon_splits(self, chars_d, order_d, class_first, V, q_pool_d, q_off_d, max_dist, min_part, K):
+        """kl_lexicon_splits: the places at which Q query words fall into two entries of a lexicon, a lost delimiter counted as
+        one of max_dist edits and every half of at least min_part ids.  The lexicon, V and the queries as in
+        `lexicon_neighbours`.  Returns the DEVICE tensors (found int32 [Q], split, left, right, dist int32 [Q, K]); the statement
+        is ratebulk.lexicon_splits_host.  hipabi.KlError for what the entry point rejects.  No synchronisation."""
+        torch = self.torch
+        tensors = (chars_d, order_d, q_pool_d, q_off_d)
+        if ([t.dtype for t in tensors] != [torch.int32, torch.int32, torch.int32, torch.int64] or any(t.dim() != 1 for t in tensors)
+                or q_off_d.numel() < 2 or not all(t.is_contiguous() and t.is_cuda for t in tensors)):
+            raise hipabi.KlError("lexicon_splits: chars, order and q_pool int32, q_off int64 [Q + 1], contiguous, on the device")
+        class_first = np.ascontiguousarray(class_first, dtype=np.int64).reshape(-1)
+        if len(class_first) != 66 or order_d.numel() != int(class_first[-1]):
+            raise hipabi.KlError("lexicon_splits: class_first int64 [66] on the host, its last value the size of order")
+        V, max_dist, min_part, K = int(V), int(max_dist), int(min_part), int(K)
+        Q = q_off_d.numel() - 1
+        dev = self.device
+        with self._launch():
+            ws = self._scratch("_lexicon_splits_ws", self.lib.kl_lexicon_splits_workspace_bytes(Q, K))
+            out = (torch.empty(Q, dtype=torch.int32, device=dev),) + tuple(
+                torch.empty((Q, max(K, 0)), dtype=torch.int32, device=dev) for _ in range(4))
+            hipabi.check(self.lib.kl_lexicon_splits(
+                _ptr(chars_d), chars_d.numel(), _ptr(order_d), class_first.ctypes.data, V, _ptr(q_pool_d), q_pool_d.numel(),
+                _ptr(q_off_d), Q, max_dist, min_part, K, *([_ptr(t) for t in out] + [_ptr(ws), ws.numel(), self._stream()])),
+                "kl_lexicon_splits")
         return out
 
     def lexicon_channel(self, chars_d, order_d, class_first, V, q_pool_d, q_off_d, rules_d, rule_cost_d, unit, max_cost, K):

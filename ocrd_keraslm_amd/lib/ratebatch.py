@@ -345,6 +345,37 @@ def word_edits(found, texts, candidates, priors=None):
     return edits if weigh is None else (edits, prior)
 
 
+def join_edits(found, texts, delimiter_of, joiner=" ", only=None):
+    """Spans for `Rater.rescore` over PAIRS of words that a spurious `joiner` may have parted (`to gether`): found is one
+    `Words` per text -- the selected words --, delimiter_of a callable character -> bool, the rater's delimiter table.  Per
+    selected word (with `only`, a callable word -> bool: per selected word it accepts) the word before and the word after are
+    looked at, if exactly one character separates them and that character is `joiner`; the neighbour's extent is found from the
+    text, since `found` holds only selected words.  Returns [(i, start, end, joined)]: the span over the two words and the
+    joiner in the normalised texts[i], and the two words run together -- what a look-up takes.  A pair is listed once, also
+    where both of its words are selected; a span at a text's first character is skipped (no prediction to be held against),
+    and so is a span of more than 64 characters (`rescore` takes no longer one).  Ordered by text, start and end.  Host only."""
+    if len(found) != len(texts):
+        raise ValueError("join_edits: one Words per text")
+    joins = set()
+    for i, (words, text) in enumerate(zip(found, texts)):
+        text = windows.normalize(text)
+        n = len(text)
+        for a, b in words.spans():
+            if only is not None and not only(text[a:b]):
+                continue
+            if a >= 2 and text[a - 1] == joiner and not delimiter_of(text[a - 2]):
+                p = a - 2
+                while p > 0 and not delimiter_of(text[p - 1]):
+                    p -= 1
+                joins.add((i, p, b, text[p:a - 1] + text[a:b]))
+            if b + 1 < n and text[b] == joiner and not delimiter_of(text[b + 1]):
+                e = b + 2
+                while e < n and not delimiter_of(text[e]):
+                    e += 1
+                joins.add((i, a, e, text[a:b] + text[b + 1:e]))
+    return sorted(j for j in joins if j[1] >= 1 and j[2] - j[1] <= ratebulk.SPAN_LEN_MAX)
+
+
 class Lexicon(object):
     """A list of words to look suspect words up in (`Rater.lexicon` builds it, `Rater.lexicon_neighbours` and
     `Rater.correct_words` read it).  `entries` is an iterable of strings in priority order, the most frequent first; they are
@@ -418,6 +449,31 @@ class Neighbours(object):
     def strings(self, i):
         """the neighbours of word i as strings, the nearest first"""
         return [self.lexicon.words[int(e)] for e in self.index[i] if e >= 0]
+
+
+class Splits(object):
+    """What `Rater.lexicon_splits` returns for n words, in input order, K = per_word:
+
+    found   [n] i32     at how many places the word falls into two entries within max_dist edits, the lost delimiter being one
+                        of them, whatever K is
+    at      [n,K] i32   the first K of these places s -- word[:s] and word[s:] are the halves --, ordered by (dist, the larger of
+                        the two indices, s): the nearest pair first, among equally near pairs the one whose rarer half is more
+                        frequent; -1 from the found-th on
+    left    [n,K] i32   the index into `lexicon.words` of the entry nearest to word[:s] (the more frequent among equally near ones)
+    right   [n,K] i32   the same for word[s:]
+    dist    [n,K] i32   1 + the two halves' distances; -1 where `at` is
+    """
+
+    def __init__(self, lexicon, found, at, left, right, dist):
+        self.lexicon, self.found, self.at, self.left, self.right, self.dist = lexicon, found, at, left, right, dist
+
+    def __len__(self):
+        return len(self.found)
+
+    def strings(self, i, joiner=" "):
+        """the splits of word i as strings `left + joiner + right`, the nearest first"""
+        words = self.lexicon.words
+        return [words[int(a)] + joiner + words[int(b)] for a, b in zip(self.left[i], self.right[i]) if a >= 0]
 
 
 class Channel(object):

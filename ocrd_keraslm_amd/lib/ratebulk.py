@@ -29,7 +29,8 @@ make of spans with caller-supplied replacements for `Rater.rescore`.  `plan_cand
 `word_bounds_host`, `segments_host` and `segment_select_host` state kl_word_bounds, kl_rate_segments and kl_segment_select: the
 words of the texts, a rating per segment and the ordered selection among them (`Rater.suspect_words`, `Rater.rate_segments`).
 `lexicon_layout_host` builds the device layout of a word list and `lexicon_neighbours_host` states kl_lexicon_neighbours: the
-entries within a few edits of every query word (`Rater.lexicon_neighbours`, `Rater.correct_words`).
+entries within a few edits of every query word (`Rater.lexicon_neighbours`, `Rater.correct_words`); `lexicon_splits_host` states
+kl_lexicon_splits: the places at which a query word falls into two entries (`Rater.lexicon_splits`).
 numpy only: the plan is built and tested without an engine.
 """
 from __future__ import annotations
@@ -842,6 +843,89 @@ def lexicon_neighbours_host(q_pool, q_off, chars, order, class_first, V, max_dis
         cand[q, :len(first)] = hits[first]
         dist[q, :len(first)] = levs[first]
     return exact, found, cand, dist
+
+
+LEXICON_MIN_PART_MAX = 32      # (kl_lexicon_splits: min_part at most)
+
+
+def lexicon_splits_host(q_pool, q_off, chars, order, class_first, V, max_dist, min_part, K):
+    """what kl_lexicon_splits computes: for the Q queries and the lexicon of `lexicon_neighbours_host`, under its id equality,
+    (found int32 [Q], split, left, right, dist int32 [Q, K]).  The missing delimiter costs one edit, so the halves share
+    d = max_dist - 1.  For a query q of m ids, 1 <= m <= 64, and every split point s with min_part <= s <= m - min_part:
+    best(h) of a half h is the entry minimising (lev(h, e), original index) among the entries with lev(h, e) <= d -- entries
+    at distance 0 count, duplicate entries are separate entries --, and s is valid iff best(q[:s]) and best(q[s:]) both exist
+    and total = 1 + lev_left + lev_right <= max_dist.  found[q] is the number of valid split points, whatever K is;
+    split, left, right, dist[q] hold s, the two original indices and total of the first K valid split points ordered by
+    (total, max(left index, right index), s), unused places -1 in all four.  A query with no split point, of no ids or of
+    more than 64 gets 0 and -1 everywhere.  A plain DP per half and length class, row by row of the half, over all entries of
+    the class at once -- only the classes within d of the half's length can hold its entry."""
+    q_pool = np.asarray(q_pool, dtype=np.int64).reshape(-1)
+    q_off = np.asarray(q_off, dtype=np.int64).reshape(-1)
+    chars = np.asarray(chars, dtype=np.int64).reshape(-1)
+    order = np.asarray(order, dtype=np.int64).reshape(-1)
+    class_first = np.asarray(class_first, dtype=np.int64).reshape(-1)
+    V, max_dist, min_part, K = int(V), int(max_dist), int(min_part), int(K)
+    if not (1 <= V <= LEXICON_V_MAX and 1 <= max_dist <= LEXICON_DIST_MAX and 1 <= min_part <= LEXICON_MIN_PART_MAX
+            and 1 <= K <= LEXICON_K_MAX):
+        raise ValueError("lexicon_splits_host: V in 1 .. %d, max_dist in 1 .. %d, min_part in 1 .. %d, K in 1 .. %d"
+                         % (LEXICON_V_MAX, LEXICON_DIST_MAX, LEXICON_MIN_PART_MAX, LEXICON_K_MAX))
+    n_class = np.diff(class_first)
+    base = np.concatenate([[0], np.cumsum(np.arange(SPAN_LEN_MAX + 1) * n_class)])
+    if (len(class_first) != SPAN_LEN_MAX + 2 or class_first[0] != 0 or class_first[1] != 0 or (n_class < 0).any()
+            or class_first[-1] != len(order) or base[-1] != len(chars)):
+        raise ValueError("lexicon_splits_host: class_first [66] ascending from 0, 0 to len(order), chars of sum L * n_L ids")
+    if len(q_off) < 1 or q_off[0] < 0 or (np.diff(q_off) < 0).any() or q_off[-1] > len(q_pool):
+        raise ValueError("lexicon_splits_host: q_off [Q + 1] ascending within the pool")
+    d = max_dist - 1
+    known = (chars >= 0) & (chars < V)
+    seen = {}      # (halves recur within a call: a half is looked up once)
+
+    def best(half):
+        """(lev, original index) of the half's nearest entry within d, None: there is none"""
+        if half.tobytes() in seen:
+            return seen[half.tobytes()]
+        n_half, least = len(half), None
+        for L in range(max(1, n_half - d), min(SPAN_LEN_MAX, n_half + d) + 1):
+            n = int(n_class[L])
+            if n == 0:
+                continue
+            entry = chars[base[L]:base[L + 1]].reshape(L, n)
+            valid = known[base[L]:base[L + 1]].reshape(L, n)
+            along = np.arange(L + 1, dtype=np.int32)[:, None]
+            prev = np.repeat(along, n, axis=1)                         # row 0: j edits
+            for i in range(1, n_half + 1):
+                differ = ~((entry == half[i - 1]) & valid)
+                # cur[j] = min(prev[j] + 1, prev[j - 1] + differ, cur[j - 1] + 1), cur[0] = i: the third term is a running
+                # minimum along j of the first two, each j behind costing one more
+                cur = np.full_like(prev, i)
+                cur[1:] = np.minimum(prev[1:] + 1, prev[:-1] + differ)
+                prev = np.minimum.accumulate(cur - along, axis=0) + along
+            lev = prev[L]
+            near = np.nonzero(lev <= d)[0]
+            if len(near):
+                one = min(zip(lev[near].tolist(), order[class_first[L] + near].tolist()))
+                least = one if least is None or one < least else least
+        seen[half.tobytes()] = least
+        return least
+
+    Q = len(q_off) - 1
+    found = np.zeros(Q, dtype=np.int32)
+    out = np.full((4, Q, K), -1, dtype=np.int32)
+    for q in range(Q):
+        word = q_pool[q_off[q]:q_off[q + 1]]
+        m = len(word)
+        if not 1 <= m <= SPAN_LEN_MAX:
+            continue
+        valid = []
+        for s in range(min_part, m - min_part + 1):
+            a = best(word[:s])
+            b = best(word[s:]) if a is not None else None
+            if a is not None and b is not None and 1 + a[0] + b[0] <= max_dist:
+                valid.append((1 + a[0] + b[0], max(a[1], b[1]), s, a[1], b[1]))
+        found[q] = len(valid)
+        for place, (total, _, s, a, b) in enumerate(sorted(valid)[:K]):
+            out[:, q, place] = s, a, b, total
+    return found, out[0], out[1], out[2], out[3]
 
 
 CHANNEL_RULES_MAX, CHANNEL_COST_MAX = 1024, 4095      # (KL_CHANNEL_* of the C ABI)

@@ -1817,9 +1817,58 @@ class Rater(object):
         bits = None if channel is None else np.where(dist >= 0, dist / float(ratebulk.CHANNEL_SCALE), np.nan)
         return ratebatch.Neighbours(lexicon, out[:, 0].copy(), out[:, 1].copy(), out[:, 2:2 + K].copy(), dist, bits)
 
+    def lexicon_splits(self, words, lexicon, max_dist=1, min_part=2, per_word=4):
+        '''Where could these words be TWO entries of the lexicon run together (`ofthe`)?  Returns a ratebatch.Splits in input
+        order: per word `found` (at how many places it falls into two entries, each half of at least `min_part` characters,
+        within max_dist edits in all -- the lost delimiter is one of them, so max_dist=1 asks for two exact halves) and the
+        first `per_word` places ordered by (distance, the larger of the two entries' indices, place), with the entries and the
+        distance; -1 fills the unused places.  Per place and side only the nearest entry counts, the more frequent among
+        equally near ones.
+
+        As in `lexicon_neighbours` the words are normalised, made unique on the host and encoded; one upload, one kernel call
+        (`HipLM.lexicon_splits`: no pairs of entries are formed, two walks over the shorter length classes give every place's
+        nearest entry on either side), one download of 4 + 16 * per_word bytes per distinct word, spread back over the
+        duplicates.  A word of more than 64 characters, or of fewer than 2 * min_part, has no such place.  No words, or a lexicon
+        without an entry, give their result without a launch.  An engine without `lexicon_splits` (the tests' CPU double) runs
+        ratebulk.lexicon_splits_host.  ValueError for max_dist outside 1 .. 8, min_part outside 1 .. 32, per_word outside
+        1 .. 16, a lexicon of another mapping.'''
+        assert self.status > 1
+        max_dist, K = self._lexicon_request("lexicon_splits", lexicon, max_dist, per_word)
+        min_part = int(min_part)
+        if max_dist < 1 or not 1 <= min_part <= ratebulk.LEXICON_MIN_PART_MAX:
+            raise ValueError("lexicon_splits: max_dist in 1 .. %d and min_part in 1 .. %d (got %d, %d)"
+                             % (ratebulk.LEXICON_DIST_MAX, ratebulk.LEXICON_MIN_PART_MAX, max_dist, min_part))
+        words = [windows.normalize(w) for w in words]
+        slot = {}
+        for w in words:
+            slot.setdefault(w, len(slot))
+        unique = list(slot)
+        Q = len(unique)
+        out = np.full((Q, 1 + 4 * K), -1, dtype=np.int32)      # (found, at [K], left [K], right [K], dist [K] per distinct word)
+        out[:, 0] = 0
+        if Q and len(lexicon):
+            pool = windows.encode("".join(unique), self.mapping[0]).astype(np.int32)
+            q_off = np.concatenate([[0], np.cumsum([len(w) for w in unique])]).astype(np.int64)
+            lm = self.model
+            if hasattr(lm, 'lexicon_splits'):
+                torch = lm.torch
+                chars_d, order_d = lexicon.on_device(lm)
+                both = torch.from_numpy(np.concatenate([q_off.view(np.int32), pool])).to(lm.device)
+                res = lm.lexicon_splits(chars_d, order_d, lexicon.class_first, self.voc_size, both[2 * (Q + 1):],
+                                        both[:2 * (Q + 1)].view(torch.int64), max_dist, min_part, K)
+                out = _np(torch.cat([res[0][:, None]] + list(res[1:]), dim=1))
+            else:
+                res = ratebulk.lexicon_splits_host(pool, q_off, lexicon.chars, lexicon.order, lexicon.class_first, self.voc_size,
+                                                   max_dist, min_part, K)
+                out = np.concatenate([res[0][:, None]] + list(res[1:]), axis=1)
+        rows = np.asarray([slot[w] for w in words], dtype=np.int64)
+        out = out[rows] if len(rows) else out[:0]
+        return ratebatch.Splits(lexicon, out[:, 0].copy(), *(out[:, 1 + f * K:1 + (f + 1) * K].copy() for f in range(4)))
+
     def correct_words(self, texts, lexicon, contexts=None, max_dist=2, per_word=8, known=False, delimiters=None, k=3,
                       max_prob=0.01, min_rank=1, min_suspects=1, min_bits_per_char=0.0, min_chars=1, left=64, ahead=8,
-                      min_gain=1.0, streams=1024, precision="bf16", channel=None, max_bits=12.0, channel_weight=1.0):
+                      min_gain=1.0, streams=1024, precision="bf16", channel=None, max_bits=12.0, channel_weight=1.0,
+                      boundaries=False, min_part=2, joiner=" "):
         '''From texts to lexicon-backed corrections: `suspect_words` -> the suspect words' nearest lexicon entries ->
         `rescore`.  Returns (found, rescored, bits): `found` and `bits` are `suspect_words(texts, contexts, delimiters=..,
         k=.., max_prob=.., min_rank=.., min_suspects=.., min_bits_per_char=.., min_chars=.., streams=.., precision=..)`'s;
@@ -1834,8 +1883,29 @@ class Rater(object):
         max_bits=..)`'s -- the entries that are cheap under the learned confusions, max_dist is not used -- and the channel's
         bits enter the choice beside the model's: `rescore(.., prior=..)` with channel_weight * bits per candidate
         (`ratebatch.word_edits` returns them beside the edits).  channel_weight = 0.0 lets the model alone choose among the
-        channel's candidates.  ValueError also for channel_weight < 0 or not finite.'''
-        self._lexicon_request("correct_words", lexicon, max_dist, per_word)
+        channel's candidates.  ValueError also for channel_weight < 0 or not finite.
+
+        With boundaries=True (and max_dist >= 1) lost and spurious delimiters are hypotheses too.  SPLITS: every looked-up word
+        (one that is no entry, or any word with known=True) of fewer than 64 characters also goes through ONE
+        `lexicon_splits(words, lexicon, max_dist, min_part, per_word)`, and its strings `left + joiner + right` follow the
+        word's neighbours among its candidates (a string equal to an earlier candidate, or of more than 64 characters, is
+        dropped).  MERGES: the `ratebatch.join_edits(found, texts, .., joiner)` of the pairs with at least one looked-up word go
+        through ONE `lexicon_neighbours(joined, lexicon, max_dist - 1, per_word)`; here `exact` is a candidate and comes first,
+        and every pair with candidates is an edit of its own over the two words and the joiner.  All edits go to the one
+        `rescore`, ordered by text and start; overlapping spans are `Rescored.apply`'s business.  With a channel the merges are
+        looked up through it at max_bits - unit_bits (none if that is negative) and cost their bits plus unit_bits for the
+        joiner, a split costs unit_bits * dist, both times channel_weight.  ValueError also for min_part outside 1 .. 32 and for
+        a joiner that is not one mapped character which the delimiter table holds.'''
+        max_dist, per_word = self._lexicon_request("correct_words", lexicon, max_dist, per_word)
+        boundaries = bool(boundaries) and max_dist >= 1
+        if boundaries:
+            min_part, joiner = int(min_part), windows.normalize(joiner)
+            if not 1 <= min_part <= ratebulk.LEXICON_MIN_PART_MAX:
+                raise ValueError("correct_words: min_part in 1 .. %d (got %d)" % (ratebulk.LEXICON_MIN_PART_MAX, min_part))
+            delim = self._delimiter_table(delimiters)
+            is_delimiter = lambda c: bool(0 < self.mapping[0].get(c, 0) < self.voc_size and delim[self.mapping[0][c]])
+            if len(joiner) != 1 or not is_delimiter(joiner):
+                raise ValueError("correct_words: joiner is one mapped character among the delimiters (got %r)" % (joiner,))
         channel_weight = float(channel_weight)
         if channel is not None:
             self._channel_request("correct_words", channel, max_bits)
@@ -1853,10 +1923,40 @@ class Rater(object):
                 table[word] = near.strings(i) if known or near.exact[i] < 0 else []
                 if channel is not None:
                     weights[word] = [channel_weight * float(b) for b in near.bits[i][:len(table[word])]]
+        unit_bits = None if channel is None else channel.unit / float(ratebulk.CHANNEL_SCALE)
+        if boundaries:
+            looked = dict((word, bool(known or near.exact[i] < 0)) for i, word in enumerate(words))
+            apart = [word for word in table if looked[word] and len(word) < ratebulk.SPAN_LEN_MAX]
+            splits = self.lexicon_splits(apart, lexicon, max_dist=max_dist, min_part=min_part, per_word=per_word)
+            for i, word in enumerate(apart):
+                for string, dist in zip(splits.strings(i, joiner), splits.dist[i]):
+                    if string not in table[word] and len(string) <= ratebulk.SPAN_LEN_MAX:
+                        table[word].append(string)
+                        if channel is not None:
+                            weights[word].append(channel_weight * unit_bits * int(dist))
         if channel is None:
             edits, prior = ratebatch.word_edits(found, texts, table), None
         else:
             edits, prior = ratebatch.word_edits(found, texts, table, priors=weights)
+        merge_bits = max_bits if channel is None else float(max_bits) - unit_bits
+        if boundaries and merge_bits >= 0.0:
+            joins = ratebatch.join_edits(found, texts, is_delimiter, joiner, only=looked.get)
+            whole = self.lexicon_neighbours([j[3] for j in joins], lexicon, max_dist=max_dist - 1, per_word=per_word,
+                                            channel=channel, max_bits=merge_bits)
+            merges, merge_prior = [], []
+            for j, (i, start, end, _) in enumerate(joins):
+                strings = ([lexicon.words[int(whole.exact[j])]] if whole.exact[j] >= 0 else []) + whole.strings(j)
+                if strings:
+                    merges.append((i, start, end, strings))
+                    if channel is not None:
+                        cost = ([0.0] if whole.exact[j] >= 0 else []) + [float(b) for b in whole.bits[j][:len(strings)]]
+                        merge_prior.append([channel_weight * (b + unit_bits) for b in cost[:len(strings)]])
+            # one list ordered by text and start (a word's own edit in front of the pair that begins with it)
+            edits = edits + merges
+            both = sorted(range(len(edits)), key=lambda e: edits[e][:3] + (e,))
+            if channel is not None:
+                prior = [(prior + merge_prior)[e] for e in both]
+            edits = [edits[e] for e in both]
         rescored = self.rescore(texts, edits, contexts, streams=streams, left=left, ahead=ahead, min_gain=min_gain,
                                 precision=precision, prior=prior)
         return found, rescored, bits

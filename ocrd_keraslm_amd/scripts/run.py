@@ -25,6 +25,7 @@ Additional command `lexicon`: the suspect words of every DATA file looked up in 
 first) on the device, and their nearest entries rated against the text around them (Rater.correct_words: suspect_words ->
 lexicon_neighbours -> rescore); output as `rescore`'s, --apply also gives the corrected text.  With --channel FILE (the JSON
 lines of `confusions --counts`) the look-up weighs the learned confusions and their bits enter the choice (Rater.channel).
+With --boundaries lost and spurious spaces are hypotheses too: a word as two entries (Rater.lexicon_splits), two words as one.
 Additional command `witnesses`: every DATA file aligned with other readings of it (--witness DIR: the file of the same base
 name) on the device, and the readings of the spans where they differ rated against the text around them
 (Rater.merge_witnesses: align -> witness_edits -> rescore); --apply also gives the corrected text.
@@ -612,10 +613,15 @@ def _read_channel(path):
               help='with --channel: a confusion was seen at least this often')
 @click.option('--min-rate', default=0.0, show_default=True, type=click.FLOAT,
               help='with --channel: ... and at no less than this share of the occurrences of its source')
+@click.option('--boundaries', is_flag=True, default=False,
+              help='also try word boundaries: a looked-up word as two entries with a space between them ("split"), and a '
+                   'looked-up word run together with the word before or after it ("merge"); every record then ends with its kind')
+@click.option('--min-part', default=2, show_default=True, type=click.IntRange(min=1, max=32),
+              help='with --boundaries: each half of a split has at least this many characters')
 @click.argument('data', nargs=-1, type=click.Path(exists=True, dir_okay=True, file_okay=True))
 def lexicon_(model, lexicon_file, max_dist, per_word, known, streams, precision, k, max_prob, min_rank, min_suspects,
              min_bits_per_char, min_chars, delimiters, left, ahead, min_gain, apply_, channel_file, unit_bits, max_bits,
-             channel_weight, min_count, min_rate, data):
+             channel_weight, min_count, min_rate, boundaries, min_part, data):
     """Apply a language model to DATA files, look the words it does not believe up in the word list and
        print one JSON line per file, as `rescore` does: characters and "rescored": one [start, end, written,
        proposed, gain] per word that has candidates -- proposed is the entry that replaces text[start:end],
@@ -627,14 +633,20 @@ def lexicon_(model, lexicon_file, max_dist, per_word, known, streams, precision,
        noisy-channel one: an entry costs what the learned confusions and --unit-bits per unexplained edit make
        of the way from it to the word, the candidates are the cheapest entries within --max-bits, and
        --channel-weight times these bits are added to the model's before the choice.
+
+       With --boundaries a lost or spurious space is a hypothesis too (--max-dist counts it as one edit), and
+       every record has a sixth field: "merge" for a span over two words and the space between them, "split"
+       where the proposal puts a space into the word, "word" otherwise.
     """
     from ..lib import windows
     rater = _load(model)
-    channel = {}
+    more = {}
+    if boundaries:
+        more.update(boundaries=True, min_part=min_part)
     try:
         lexicon = rater.lexicon(_read_lexicon(lexicon_file))
         if channel_file is not None:
-            channel = dict(channel=rater.channel(_read_channel(channel_file), unit_bits=unit_bits, min_count=min_count,
+            more.update(channel=rater.channel(_read_channel(channel_file), unit_bits=unit_bits, min_count=min_count,
                                                  min_rate=min_rate), max_bits=max_bits, channel_weight=channel_weight)
     except (ValueError, KeyError, TypeError) as err:
         raise click.UsageError(str(err))
@@ -651,12 +663,14 @@ def lexicon_(model, lexicon_file, max_dist, per_word, known, streams, precision,
                                           delimiters=delimiters, k=k, max_prob=max_prob, min_rank=min_rank,
                                           min_suspects=min_suspects, min_bits_per_char=min_bits_per_char, min_chars=min_chars,
                                           left=left, ahead=ahead, min_gain=min_gain, streams=streams, precision=precision,
-                                          **channel)
+                                          **more)
     except ValueError as err:
         raise click.UsageError(str(err))
     for name, text, one in zip(names, texts, found):
         rows = [[int(a), int(b), text[int(a):int(b)], new, float(g)]
                 for a, b, new, g in zip(one.starts, one.ends, one.proposals(), one.gain)]
+        if boundaries:      # (a word holds no delimiter: a span with a space is a pair, a space in the proposal a split)
+            rows = [row + ["merge" if " " in row[2] else "split" if row[3] is not None and " " in row[3] else "word"] for row in rows]
         line = {"file": name, "chars": len(text), "rescored": rows}
         if apply_:
             line["corrected"] = one.apply(text)
