@@ -25,6 +25,7 @@
  *   ... and the suspect words' nearest entries of a lexicon, as replacements   kl_lexicon_neighbours
  *   ... or, under a table of learned confusions, its cheapest entries in a weighted distance   kl_lexicon_channel
  *   ... or, where a space was lost, the pairs of entries a run-together word falls into   kl_lexicon_splits
+ *   ... or a word as a chain of up to 8 entries: compounds, more than one lost space   kl_lexicon_chains
  *   ... and the spans where a second reading of the text (another OCR engine) differs   kl_align_pairs
  *   ... and, against ground truth, the table of confusions these spans amount to   kl_confusion_counts
  *   ... and, with several such readings, their spans clustered and the readings counted   kl_witness_clusters, kl_witness_pool
@@ -607,6 +608,53 @@ int kl_lexicon_splits(const int32_t* chars, size_t n_chars, const int32_t* order
                       const int32_t* q_pool, size_t n_q, const int64_t* q_off, size_t Q, int max_dist, int min_part, int K,
                       int32_t* found, int32_t* split, int32_t* left, int32_t* right, int32_t* dist, void* ws, size_t ws_bytes,
                       void* stream);
+
+/* Lexicon chains: is a query word a concatenation of up to P exact entries of the lexicon, and of which?  The compound
+ * (`arbeit|s|amt`: three entries and a linking element between two of them) and the word that lost more than one space
+ * (`inthehouse`) beside kl_lexicon_splits' pairs.  No handle.  The lexicon (chars, n_chars, order, class_first), the queries
+ * (q_pool, n_q, q_off, Q), V and the id equality are kl_lexicon_neighbours': an id outside [0, V) equals nothing, itself
+ * included.  Duplicate entries are separate entries.
+ *
+ * links (HOST int32 [n_links][4]: len, ids[3]; 0 <= n_links <= KL_LEXICON_LINKS_MAX, may be null with n_links == 0) are the
+ * linking elements, 1 .. KL_LEXICON_LINK_LEN_MAX ids each, every used id in [0, V); they are read on the host, as class_first
+ * is.  max_parts = P, 2 .. KL_LEXICON_PARTS_MAX; min_part, 1 .. 32, the least number of ids of a piece (links do not count).
+ *
+ * For a query q of m ids, 1 <= m <= 64: piece(a, b), 0 <= a < b <= m and b - a >= min_part, is the smallest original index of an
+ * entry identical to q[a:b], or none.  A chain of p parts is a sequence of pieces (a_1, b_1) .. (a_p, b_p) with a_1 = 0,
+ * b_p = m and, between neighbours, either a_{k+1} = b_k or q[b_k:a_{k+1}] identical to one of the links; a link never stands
+ * in front of the first piece or behind the last.  The key of a chain is its bottleneck, the largest piece index -- the rarest
+ * part.  Per p in 1 .. P one chain of exactly p parts with the least bottleneck is reported; ties are settled by the DP, which
+ * is the definition: E[1][b] = piece(0, b); for p >= 2, E[p][b] is the least of max(E[p-1][b'], piece(a, b)), the candidates
+ * visited with a ascending and, per a, first b' = a (no link), then the links in index order that are identical to
+ * q[a-len:a], b' = a - len >= 1; the first candidate of least key is kept (a strict <); the chain of p parts is the walk back
+ * from E[p][m] through the kept predecessors.
+ * Outputs (device int32; found [Q]; worst [Q][P]; entry, start, link [Q][P][P]; OVERWRITTEN for every q < Q, nothing behind
+ * them written):
+ *   found[q]               bit p-1 is set iff a chain of p parts exists;
+ *   worst[q][p-1]          its bottleneck, or -1;
+ *   entry[q][p-1][0..p)    the pieces' original indices; start[q][p-1][0..p) their a_k;
+ *   link[q][p-1][0..p-1)   the index of the link between piece k and k + 1, -1 for none; unused places are -1 in all three.
+ * A query of no ids, of more than 64, with bad offsets or with m < min_part gets 0 and -1 everywhere, and nothing of the lexicon
+ * is read for it.  The statement is ratebulk.lexicon_chains_host.
+ *
+ * One workgroup of 256 threads per query.  Peq[V] of the query in LDS; a lane walks whole entries of the length classes
+ * min_part .. m with a word R whose bit a says "the entry could start at a": R = low(m - L + 1), R &= Peq[c_j] >> j per entry
+ * character (the 32-bit word for m <= 32 unless KL_LEXICON_NARROW=0, same results), and every bit left lowers the piece table
+ * (64 x 64 words of LDS) with a 32-bit unsigned minimum.  Then thread b owns column b of the DP, one barrier per p, and thread
+ * p - 1 walks back.  Two plain launches on `stream` (the class table into ws, then the look-up), no atomics on global memory,
+ * no workgroup waits for another, and a minimum does not depend on the order of arrival: two calls agree bit for bit.  ws:
+ * device scratch of kl_lexicon_chains_workspace_bytes(Q, P) bytes (the class table), 8-byte aligned, not to be shared by calls
+ * that may overlap.  KL_ERR_ARG, before any launch and with nothing touched, for what kl_lexicon_neighbours rejects (max_dist
+ * and K aside), max_parts outside 2 .. 8, min_part outside 1 .. 32, n_links outside 0 .. 8, null links with n_links > 0, a
+ * link length outside 1 .. 3, a used link id outside [0, V); KL_ERR_WORKSPACE if ws_bytes is too small. */
+#define KL_LEXICON_PARTS_MAX 8
+#define KL_LEXICON_LINKS_MAX 8
+#define KL_LEXICON_LINK_LEN_MAX 3
+size_t kl_lexicon_chains_workspace_bytes(size_t Q, int P);
+int kl_lexicon_chains(const int32_t* chars, size_t n_chars, const int32_t* order, const int64_t* class_first, int V,
+                      const int32_t* q_pool, size_t n_q, const int64_t* q_off, size_t Q, const int32_t* links, int n_links,
+                      int max_parts, int min_part, int32_t* found, int32_t* worst, int32_t* entry, int32_t* start,
+                      int32_t* link, void* ws, size_t ws_bytes, void* stream);
 
 /* Alignment of two readings: where do the texts of P pairs differ?  The step in front of kl_span_windows for a second witness of
  * the same line or page (another OCR engine): the differing spans become the spans and replacements it rates.  No handle.

@@ -17,7 +17,7 @@ import time
 
 import numpy as np
 
-from . import hipabi
+from . import hipabi, ratebulk
 
 CTX_VOCAB = 200   # rating.py:111
 CTX_DIM = 10
@@ -99,6 +99,7 @@ class HipLM:
         self._lexicon_ws = None
         self._lexicon_channel_ws = None
         self._lexicon_splits_ws = None
+        self._lexicon_chains_ws = None
         self._align_ws = None
         self._confusion_ws = None
         self._witness_ws = None
@@ -810,6 +811,39 @@ class HipLM:
                 _ptr(chars_d), chars_d.numel(), _ptr(order_d), class_first.ctypes.data, V, _ptr(q_pool_d), q_pool_d.numel(),
                 _ptr(q_off_d), Q, max_dist, min_part, K, *([_ptr(t) for t in out] + [_ptr(ws), ws.numel(), self._stream()])),
                 "kl_lexicon_splits")
+        return out
+
+    def lexicon_chains(self, chars_d, order_d, class_first, V, q_pool_d, q_off_d, links, max_parts, min_part):
+        """kl_lexicon_chains: Q query words as chains of up to P = max_parts exact entries of a lexicon, every piece of at
+        least min_part ids, with the linking elements `links` allowed between pieces -- a sequence of id sequences (1 .. 3 ids
+        each, at most 8) or the int32 [n, 4] of `ratebulk.lexicon_links_host`, read on the HOST.  The lexicon, V and the
+        queries as in `lexicon_neighbours`.  Returns the DEVICE tensors (found int32 [Q], worst int32 [Q, P], entry, start,
+        link int32 [Q, P, P]); the statement is ratebulk.lexicon_chains_host.  hipabi.KlError for what the entry point
+        rejects.  No synchronisation."""
+        torch = self.torch
+        tensors = (chars_d, order_d, q_pool_d, q_off_d)
+        if ([t.dtype for t in tensors] != [torch.int32, torch.int32, torch.int32, torch.int64] or any(t.dim() != 1 for t in tensors)
+                or q_off_d.numel() < 2 or not all(t.is_contiguous() and t.is_cuda for t in tensors)):
+            raise hipabi.KlError("lexicon_chains: chars, order and q_pool int32, q_off int64 [Q + 1], contiguous, on the device")
+        class_first = np.ascontiguousarray(class_first, dtype=np.int64).reshape(-1)
+        if len(class_first) != 66 or order_d.numel() != int(class_first[-1]):
+            raise hipabi.KlError("lexicon_chains: class_first int64 [66] on the host, its last value the size of order")
+        V, P, min_part = int(V), int(max_parts), int(min_part)
+        try:
+            links = np.ascontiguousarray(ratebulk.lexicon_links_host(links, V), dtype=np.int32)
+        except ValueError as err:
+            raise hipabi.KlError(str(err))
+        Q = q_off_d.numel() - 1
+        dev = self.device
+        room = min(max(P, 0), hipabi.KL_LEXICON_PARTS_MAX)      # (an out-of-range P is the entry point's to refuse)
+        with self._launch():
+            ws = self._scratch("_lexicon_chains_ws", self.lib.kl_lexicon_chains_workspace_bytes(Q, P))
+            out = (torch.empty(Q, dtype=torch.int32, device=dev), torch.empty((Q, room), dtype=torch.int32, device=dev)) + tuple(
+                torch.empty((Q, room, room), dtype=torch.int32, device=dev) for _ in range(3))
+            hipabi.check(self.lib.kl_lexicon_chains(
+                _ptr(chars_d), chars_d.numel(), _ptr(order_d), class_first.ctypes.data, V, _ptr(q_pool_d), q_pool_d.numel(),
+                _ptr(q_off_d), Q, links.ctypes.data if len(links) else None, len(links), P, min_part,
+                *([_ptr(t) for t in out] + [_ptr(ws), ws.numel(), self._stream()])), "kl_lexicon_chains")
         return out
 
     def lexicon_channel(self, chars_d, order_d, class_first, V, q_pool_d, q_off_d, rules_d, rule_cost_d, unit, max_cost, K):

@@ -20,7 +20,8 @@ KL_SPAN_LEN_MAX = 64     # ids of a span and of a candidate of kl_span_windows a
 KL_CTX_CAND_MAX = 256    # candidate contexts of kl_rate_scatter_planes / kl_context_mix at most
 KL_LEXICON_V_MAX, KL_LEXICON_DIST_MAX, KL_LEXICON_K_MAX = 4096, 8, 16      # kl_lexicon_neighbours: ids, max_dist and K at most
 KL_LEXICON_MIN_PART_MAX = 32      # kl_lexicon_splits: min_part at most
-KL_CHANNEL_RULES_MAX, KL_CHANNEL_COST_MAX = 1024, 4095      # kl_lexicon_channel: rules, and unit, max_cost and a rule's cost at most
+KL_LEXICON_PARTS_MAX, KL_LEXICON_LINKS_MAX, KL_LEXICON_LINK_LEN_MAX = 8, 8, 3      # kl_lexicon_chains: parts, links, ids of a link
+KL_CHANNEL_RULES_MAX, KL_CHANNEL_COST_MAX = 1024, 4095     # kl_lexicon_channel: rules, and unit, max_cost and a rule's cost at most
 KL_ALIGN_DIST_MAX, KL_ALIGN_LEN_MAX = 255, 4096      # kl_align_pairs: max_dist and symbols of a text at most
 KL_CONFUSION_CHARS_MAX = 4      # kl_confusion_counts: symbols of a source and of a target at most
 KL_WITNESS_MAX = 64      # kl_witness_clusters: witnesses (pairs) of a text at most
@@ -165,6 +166,10 @@ SIGNATURES = {
     "kl_lexicon_splits": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
                                     C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_size_t, C.c_void_p]),
+    "kl_lexicon_chains_workspace_bytes": (C.c_size_t, [C.c_size_t, C.c_int]),
+    "kl_lexicon_chains": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                                    C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "kl_align_pairs_workspace_bytes": (C.c_size_t, [C.c_size_t, C.c_int, C.c_int]),
     "kl_align_pairs": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int,
                                  C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

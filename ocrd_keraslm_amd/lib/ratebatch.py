@@ -476,6 +476,49 @@ class Splits(object):
         return [words[int(a)] + joiner + words[int(b)] for a, b in zip(self.left[i], self.right[i]) if a >= 0]
 
 
+class Chains(object):
+    """What `Rater.lexicon_chains` returns for n words, in input order, P = max_parts:
+
+    found   [n] i32       bit p-1 is set iff the word is a chain of exactly p entries (p = 1: the word is an entry itself), every
+                          piece of at least min_part characters, a link allowed between neighbours
+    worst   [n,P] i32     per p the chain's bottleneck: the largest index into `lexicon.words` among its pieces -- the rarest
+                          part; the chain reported for a p is one of least bottleneck; -1 where there is none
+    entry   [n,P,P] i32   entry[i, p-1, :p] the pieces of the chain of p parts, -1 behind them
+    start   [n,P,P] i32   where each piece begins in the word
+    link    [n,P,P] i32   link[i, p-1, k] the index into `links` of the link between piece k and k + 1, -1 for none
+    links   [str]         the linking elements the call allowed, normalised
+    """
+
+    def __init__(self, lexicon, found, worst, entry, start, link, links=()):
+        self.lexicon, self.found, self.worst, self.entry, self.start, self.link = lexicon, found, worst, entry, start, link
+        self.links = list(links)
+
+    def __len__(self):
+        return len(self.found)
+
+    def parts(self, i):
+        """the least p for which word i is a chain of p entries, 0: it is none"""
+        bits = int(self.found[i])
+        return (bits & -bits).bit_length()
+
+    def pieces(self, i, p):
+        """the entries of word i's chain of p parts as strings, [] if there is none"""
+        if not 1 <= p <= self.worst.shape[1] or not (int(self.found[i]) >> (p - 1)) & 1:
+            return []
+        return [self.lexicon.words[int(e)] for e in self.entry[i, p - 1, :p]]
+
+    def strings(self, i, joiner=" ", min_parts=2):
+        """one string per existing p >= min_parts, ascending: the pieces joined by `joiner`, a link attached to the piece
+        in front of it"""
+        out = []
+        for p in range(max(1, int(min_parts)), self.worst.shape[1] + 1):
+            pieces = self.pieces(i, p)
+            if pieces:
+                tails = [self.links[int(l)] if l >= 0 else "" for l in self.link[i, p - 1, :p - 1]] + [""]
+                out.append(joiner.join(piece + tail for piece, tail in zip(pieces, tails)))
+        return out
+
+
 class Channel(object):
     """A table of confusions as the weighted look-up takes it (`Rater.channel` builds it, `Rater.lexicon_neighbours` and
     `Rater.correct_words` read it).  `records` is a `Confusions` or an iterable of (source, target, count, occ): `source` in

@@ -30,7 +30,8 @@ make of spans with caller-supplied replacements for `Rater.rescore`.  `plan_cand
 words of the texts, a rating per segment and the ordered selection among them (`Rater.suspect_words`, `Rater.rate_segments`).
 `lexicon_layout_host` builds the device layout of a word list and `lexicon_neighbours_host` states kl_lexicon_neighbours: the
 entries within a few edits of every query word (`Rater.lexicon_neighbours`, `Rater.correct_words`); `lexicon_splits_host` states
-kl_lexicon_splits: the places at which a query word falls into two entries (`Rater.lexicon_splits`).
+kl_lexicon_splits: the places at which a query word falls into two entries (`Rater.lexicon_splits`); `lexicon_chains_host` states
+kl_lexicon_chains: a query word as a chain of up to 8 exact entries, links between them allowed (`Rater.lexicon_chains`).
 numpy only: the plan is built and tested without an engine.
 """
 from __future__ import annotations
@@ -926,6 +927,131 @@ def lexicon_splits_host(q_pool, q_off, chars, order, class_first, V, max_dist, m
         for place, (total, _, s, a, b) in enumerate(sorted(valid)[:K]):
             out[:, q, place] = s, a, b, total
     return found, out[0], out[1], out[2], out[3]
+
+
+LEXICON_PARTS_MAX, LEXICON_LINKS_MAX, LEXICON_LINK_LEN_MAX = 8, 8, 3      # (kl_lexicon_chains: parts, links, ids of a link)
+
+
+def lexicon_links_host(links, V):
+    """the links of `lexicon_chains_host` as kl_lexicon_chains takes them: int32 [n_links, 4] -- len, ids[3], unused ids 0 --
+    from a sequence of id sequences (or from such an array).  ValueError for more than 8 links, a link of no ids or of more
+    than 3, an id outside [0, V)."""
+    if isinstance(links, np.ndarray) and links.ndim == 2 and links.shape[1] == 1 + LEXICON_LINK_LEN_MAX:
+        rows = np.asarray(links, dtype=np.int64)
+        if ((rows[:, 0] < 1) | (rows[:, 0] > LEXICON_LINK_LEN_MAX)).any():
+            raise ValueError("lexicon_chains: a link has 1 .. %d ids" % LEXICON_LINK_LEN_MAX)
+        links = [row[1:1 + row[0]].tolist() for row in rows]
+    links = [[int(c) for c in one] for one in links]
+    if len(links) > LEXICON_LINKS_MAX:
+        raise ValueError("lexicon_chains: at most %d links (got %d)" % (LEXICON_LINKS_MAX, len(links)))
+    out = np.zeros((len(links), 1 + LEXICON_LINK_LEN_MAX), dtype=np.int32)
+    for l, one in enumerate(links):
+        if not 1 <= len(one) <= LEXICON_LINK_LEN_MAX or any(not 0 <= c < V for c in one):
+            raise ValueError("lexicon_chains: a link has 1 .. %d ids, each in [0, V)" % LEXICON_LINK_LEN_MAX)
+        out[l, 0] = len(one)
+        out[l, 1:1 + len(one)] = one
+    return out
+
+
+def lexicon_chains_host(q_pool, q_off, chars, order, class_first, V, links, max_parts, min_part):
+    """what kl_lexicon_chains computes: for the Q queries and the lexicon of `lexicon_neighbours_host`, under its id equality,
+    (found int32 [Q], worst int32 [Q, P], entry, start, link int32 [Q, P, P]) with P = max_parts.  links is a sequence of id
+    sequences (1 .. 3 ids in [0, V) each, at most 8), or the int32 [n, 4] of `lexicon_links_host`.  For a query q of m ids,
+    1 <= m <= 64: piece(a, b), b - a >= min_part, is the smallest original index of an entry identical to q[a:b] (duplicate
+    entries are separate entries), or none.  A chain of p parts is a sequence of pieces from 0 to m, neighbours adjacent or
+    with one of the links between them; its key is the largest piece index.  E[1][b] = piece(0, b); for p >= 2, E[p][b] is
+    the least of max(E[p-1][b'], piece(a, b)), the candidates visited with a ascending and per a first b' = a, then the links
+    in index order that are identical to q[a-len:a] with b' = a - len >= 1; the first candidate of least key is kept.  The
+    chain of p parts is the walk back from E[p][m].  found[q] has bit p-1 set iff a chain of p parts exists, worst[q, p-1]
+    is its key, entry[q, p-1, :p] the pieces' indices, start[q, p-1, :p] where they begin, link[q, p-1, :p-1] the link
+    between piece k and k + 1 (-1: none); -1 in every unused place.  A query of no ids, of more than 64 or shorter than
+    min_part gets 0 and -1 everywhere."""
+    q_pool = np.asarray(q_pool, dtype=np.int64).reshape(-1)
+    q_off = np.asarray(q_off, dtype=np.int64).reshape(-1)
+    chars = np.asarray(chars, dtype=np.int64).reshape(-1)
+    order = np.asarray(order, dtype=np.int64).reshape(-1)
+    class_first = np.asarray(class_first, dtype=np.int64).reshape(-1)
+    V, P, min_part = int(V), int(max_parts), int(min_part)
+    if not (1 <= V <= LEXICON_V_MAX and 2 <= P <= LEXICON_PARTS_MAX and 1 <= min_part <= LEXICON_MIN_PART_MAX):
+        raise ValueError("lexicon_chains_host: V in 1 .. %d, max_parts in 2 .. %d, min_part in 1 .. %d"
+                         % (LEXICON_V_MAX, LEXICON_PARTS_MAX, LEXICON_MIN_PART_MAX))
+    links = lexicon_links_host(links, V)
+    links = [tuple(row[1:1 + row[0]].tolist()) for row in links]
+    n_class = np.diff(class_first)
+    base = np.concatenate([[0], np.cumsum(np.arange(SPAN_LEN_MAX + 1) * n_class)])
+    if (len(class_first) != SPAN_LEN_MAX + 2 or class_first[0] != 0 or class_first[1] != 0 or (n_class < 0).any()
+            or class_first[-1] != len(order) or base[-1] != len(chars)):
+        raise ValueError("lexicon_chains_host: class_first [66] ascending from 0, 0 to len(order), chars of sum L * n_L ids")
+    if len(q_off) < 1 or q_off[0] < 0 or (np.diff(q_off) < 0).any() or q_off[-1] > len(q_pool):
+        raise ValueError("lexicon_chains_host: q_off [Q + 1] ascending within the pool")
+    by_class = {}      # L -> {the entry's ids: its smallest original index}, made when a query first asks for the class
+
+    def entries_of(L):
+        if L not in by_class:
+            n = int(n_class[L])
+            rows = np.ascontiguousarray(chars[base[L]:base[L + 1]].reshape(L, n).T)      # [n, L]
+            usable = ((rows >= 0) & (rows < V)).all(axis=1)
+            index = order[class_first[L]:class_first[L + 1]]
+            table = {}
+            for e in np.nonzero(usable)[0].tolist():
+                key = rows[e].tobytes()
+                if key not in table or index[e] < table[key]:
+                    table[key] = int(index[e])
+            by_class[L] = table
+        return by_class[L]
+
+    Q = len(q_off) - 1
+    found = np.zeros(Q, dtype=np.int32)
+    worst = np.full((Q, P), -1, dtype=np.int32)
+    entry = np.full((Q, P, P), -1, dtype=np.int32)
+    start = np.full((Q, P, P), -1, dtype=np.int32)
+    link = np.full((Q, P, P), -1, dtype=np.int32)
+    for q in range(Q):
+        word = np.ascontiguousarray(q_pool[q_off[q]:q_off[q + 1]])
+        m = len(word)
+        if not max(1, min_part) <= m <= SPAN_LEN_MAX:
+            continue
+        usable = (word >= 0) & (word < V)
+        bad_before = np.concatenate([[0], np.cumsum(~usable)])
+        piece = {}
+        for a in range(m):
+            for b in range(a + min_part, m + 1):
+                if bad_before[b] == bad_before[a]:
+                    index = entries_of(b - a).get(word[a:b].tobytes())
+                    if index is not None:
+                        piece[a, b] = index
+        ids = word.tolist()
+        ends = [[l for l, one in enumerate(links) if a - len(one) >= 1 and tuple(ids[a - len(one):a]) == one] for a in range(m + 1)]
+        E = [None, dict((b, (piece[0, b], 0, -1)) for b in range(1, m + 1) if (0, b) in piece)]      # b -> (key, a, link)
+        for p in range(2, P + 1):
+            row = {}
+            for b in range(1, m + 1):
+                best = None
+                for a in range(1, b - min_part + 1):
+                    if (a, b) not in piece:
+                        continue
+                    for l, before in [(-1, a)] + [(l, a - len(links[l])) for l in ends[a]]:
+                        if before in E[p - 1]:
+                            key = max(E[p - 1][before][0], piece[a, b])
+                            if best is None or key < best[0]:
+                                best = (key, a, l)
+                if best is not None:
+                    row[b] = best
+            E.append(row)
+        for p in range(1, P + 1):
+            if m not in E[p]:
+                continue
+            found[q] |= 1 << (p - 1)
+            worst[q, p - 1] = E[p][m][0]
+            b = m
+            for k in range(p, 0, -1):
+                _, a, l = E[k][b]
+                entry[q, p - 1, k - 1] = piece[a, b]
+                start[q, p - 1, k - 1] = a
+                if k >= 2:
+                    link[q, p - 1, k - 2] = l
+                b = a - len(links[l]) if l >= 0 else a
+    return found, worst, entry, start, link
 
 
 CHANNEL_RULES_MAX, CHANNEL_COST_MAX = 1024, 4095      # (KL_CHANNEL_* of the C ABI)

@@ -1865,10 +1865,71 @@ class Rater(object):
         out = out[rows] if len(rows) else out[:0]
         return ratebatch.Splits(lexicon, out[:, 0].copy(), *(out[:, 1 + f * K:1 + (f + 1) * K].copy() for f in range(4)))
 
+    def _chain_links(self, method, links):
+        """the linking elements of `lexicon_chains`, normalised, and their ids as int32 [n, 4] (len, ids[3])"""
+        links = [windows.normalize(one) for one in ([links] if isinstance(links, str) else links)]
+        if len(links) > ratebulk.LEXICON_LINKS_MAX:
+            raise ValueError("%s: at most %d links (got %d)" % (method, ratebulk.LEXICON_LINKS_MAX, len(links)))
+        for one in links:
+            if not 1 <= len(one) <= ratebulk.LEXICON_LINK_LEN_MAX or any(not 0 < self.mapping[0].get(c, 0) < self.voc_size for c in one):
+                raise ValueError("%s: a link is 1 .. %d mapped characters (got %r)" % (method, ratebulk.LEXICON_LINK_LEN_MAX, one))
+        return links, ratebulk.lexicon_links_host([[self.mapping[0][c] for c in one] for one in links], self.voc_size)
+
+    def lexicon_chains(self, words, lexicon, max_parts=4, min_part=2, links=(), per_word=None):
+        '''Are these words CHAINS of entries of the lexicon -- compounds (`dampf|schiff|fahrt`), or words that lost more than
+        one space (`inthehouse`)?  Returns a ratebatch.Chains in input order: per word and per number of parts p in
+        1 .. max_parts whether it is p exact entries end to end, each of at least `min_part` characters, and one such chain --
+        the one whose rarest piece is most frequent, ties as ratebulk.lexicon_chains_host settles them.  `links` are linking
+        elements (`s`, `es`, `n`: strings of 1 .. 3 mapped characters, at most 8) that may stand between two pieces; they
+        belong to no piece, do not count towards min_part and never stand at the word's ends.  per_word is not used (every p
+        has its one row); it is there for the family's signature.
+
+        As in `lexicon_neighbours` the words are normalised, made unique on the host and encoded; one upload, one kernel call
+        (`HipLM.lexicon_chains`: one walk over the length classes min_part .. m matches every substring of the word, a small
+        DP follows it), one download of 4 + 4 * P + 12 * P * P bytes per distinct word, spread back over the duplicates.  A
+        word of more than 64 characters, or of fewer than min_part, is no chain.  No words, or a lexicon without an entry,
+        give their result without a launch.  An engine without `lexicon_chains` (the tests' CPU double) runs
+        ratebulk.lexicon_chains_host.  ValueError for max_parts outside 2 .. 8, min_part outside 1 .. 32, more than 8 links,
+        a link of no or of more than 3 characters or with a character outside the mapping, a lexicon of another mapping.'''
+        assert self.status > 1
+        self._lexicon_request("lexicon_chains", lexicon, 0, 1)
+        P, min_part = int(max_parts), int(min_part)
+        if not (2 <= P <= ratebulk.LEXICON_PARTS_MAX and 1 <= min_part <= ratebulk.LEXICON_MIN_PART_MAX):
+            raise ValueError("lexicon_chains: max_parts in 2 .. %d and min_part in 1 .. %d (got %d, %d)"
+                             % (ratebulk.LEXICON_PARTS_MAX, ratebulk.LEXICON_MIN_PART_MAX, P, min_part))
+        links, link_ids = self._chain_links("lexicon_chains", links)
+        words = [windows.normalize(w) for w in words]
+        slot = {}
+        for w in words:
+            slot.setdefault(w, len(slot))
+        unique = list(slot)
+        Q = len(unique)
+        out = np.full((Q, 1 + P + 3 * P * P), -1, dtype=np.int32)      # (found, worst [P], entry, start, link [P, P] per distinct word)
+        out[:, 0] = 0
+        if Q and len(lexicon):
+            pool = windows.encode("".join(unique), self.mapping[0]).astype(np.int32)
+            q_off = np.concatenate([[0], np.cumsum([len(w) for w in unique])]).astype(np.int64)
+            lm = self.model
+            if hasattr(lm, 'lexicon_chains'):
+                torch = lm.torch
+                chars_d, order_d = lexicon.on_device(lm)
+                both = torch.from_numpy(np.concatenate([q_off.view(np.int32), pool])).to(lm.device)
+                res = lm.lexicon_chains(chars_d, order_d, lexicon.class_first, self.voc_size, both[2 * (Q + 1):],
+                                        both[:2 * (Q + 1)].view(torch.int64), link_ids, P, min_part)
+                out = _np(torch.cat([res[0][:, None]] + [t.reshape(Q, -1) for t in res[1:]], dim=1))
+            else:
+                res = ratebulk.lexicon_chains_host(pool, q_off, lexicon.chars, lexicon.order, lexicon.class_first, self.voc_size,
+                                                   link_ids, P, min_part)
+                out = np.concatenate([res[0][:, None]] + [a.reshape(Q, -1) for a in res[1:]], axis=1)
+        rows = np.asarray([slot[w] for w in words], dtype=np.int64)
+        out = out[rows] if len(rows) else out[:0]
+        cube = lambda f: out[:, 1 + P + f * P * P:1 + P + (f + 1) * P * P].reshape(-1, P, P).copy()
+        return ratebatch.Chains(lexicon, out[:, 0].copy(), out[:, 1:1 + P].copy(), cube(0), cube(1), cube(2), links)
+
     def correct_words(self, texts, lexicon, contexts=None, max_dist=2, per_word=8, known=False, delimiters=None, k=3,
                       max_prob=0.01, min_rank=1, min_suspects=1, min_bits_per_char=0.0, min_chars=1, left=64, ahead=8,
                       min_gain=1.0, streams=1024, precision="bf16", channel=None, max_bits=12.0, channel_weight=1.0,
-                      boundaries=False, min_part=2, joiner=" "):
+                      boundaries=False, min_part=2, joiner=" ", compounds=0, links=(), max_parts=2):
         '''From texts to lexicon-backed corrections: `suspect_words` -> the suspect words' nearest lexicon entries ->
         `rescore`.  Returns (found, rescored, bits): `found` and `bits` are `suspect_words(texts, contexts, delimiters=..,
         k=.., max_prob=.., min_rank=.., min_suspects=.., min_bits_per_char=.., min_chars=.., streams=.., precision=..)`'s;
@@ -1895,7 +1956,18 @@ class Rater(object):
         `rescore`, ordered by text and start; overlapping spans are `Rescored.apply`'s business.  With a channel the merges are
         looked up through it at max_bits - unit_bits (none if that is negative) and cost their bits plus unit_bits for the
         joiner, a split costs unit_bits * dist, both times channel_weight.  ValueError also for min_part outside 1 .. 32 and for
-        a joiner that is not one mapped character which the delimiter table holds.'''
+        a joiner that is not one mapped character which the delimiter table holds.
+
+        With compounds=P (2 .. 8) a word that is no entry but a CHAIN of 2 .. P entries, each of at least min_part characters
+        and `links` allowed between them (`lexicon_chains`), counts as an entry: every looked-up word that is no entry goes
+        through ONE `lexicon_chains(words, lexicon, P, min_part, links)`, and a chain yields no candidates unless known=True
+        and is "not looked up" for the boundary hypotheses.  With boundaries=True and max_parts >= 3 (at most 8) more than one
+        lost delimiter is a hypothesis: the words that go to `lexicon_splits` also go through ONE `lexicon_chains(words,
+        lexicon, max_parts, min_part, links=())`, and its strings of 3 .. max_parts exact entries follow the splits' among the
+        word's candidates (duplicates and strings of more than 64 characters dropped); with a channel each costs
+        channel_weight * unit_bits * (p - 1).  At compounds=0 and max_parts=2, the defaults, `lexicon_chains` is not called.
+        ValueError also for compounds other than 0 or 2 .. 8, max_parts outside 2 .. 8 and what `lexicon_chains` raises for
+        the links.'''
         max_dist, per_word = self._lexicon_request("correct_words", lexicon, max_dist, per_word)
         boundaries = bool(boundaries) and max_dist >= 1
         if boundaries:
@@ -1906,6 +1978,16 @@ class Rater(object):
             is_delimiter = lambda c: bool(0 < self.mapping[0].get(c, 0) < self.voc_size and delim[self.mapping[0][c]])
             if len(joiner) != 1 or not is_delimiter(joiner):
                 raise ValueError("correct_words: joiner is one mapped character among the delimiters (got %r)" % (joiner,))
+            max_parts = int(max_parts)
+            if not 2 <= max_parts <= ratebulk.LEXICON_PARTS_MAX:
+                raise ValueError("correct_words: max_parts in 2 .. %d (got %d)" % (ratebulk.LEXICON_PARTS_MAX, max_parts))
+        compounds = int(compounds)
+        if compounds:
+            min_part = int(min_part)
+            if not (2 <= compounds <= ratebulk.LEXICON_PARTS_MAX and 1 <= min_part <= ratebulk.LEXICON_MIN_PART_MAX):
+                raise ValueError("correct_words: compounds 0 or in 2 .. %d, min_part in 1 .. %d (got %d, %d)"
+                                 % (ratebulk.LEXICON_PARTS_MAX, ratebulk.LEXICON_MIN_PART_MAX, compounds, min_part))
+            self._chain_links("correct_words", links)      # (their ValueErrors before any rating)
         channel_weight = float(channel_weight)
         if channel is not None:
             self._channel_request("correct_words", channel, max_bits)
@@ -1917,15 +1999,24 @@ class Rater(object):
                                          min_chars=min_chars, precision=precision)
         words = [w for one, text in zip(found, texts) for w in one.strings(windows.normalize(text))]
         near = self.lexicon_neighbours(words, lexicon, max_dist=max_dist, per_word=per_word, channel=channel, max_bits=max_bits)
-        table, weights = {}, {}
+        first = {}
         for i, word in enumerate(words):
-            if word not in table:
-                table[word] = near.strings(i) if known or near.exact[i] < 0 else []
-                if channel is not None:
-                    weights[word] = [channel_weight * float(b) for b in near.bits[i][:len(table[word])]]
+            first.setdefault(word, i)
+        # a word that is an entry is left alone -- and so is, with compounds, one that is a chain of 2 .. compounds entries
+        as_entry = dict((word, bool(near.exact[i] >= 0)) for word, i in first.items())
+        if compounds:
+            unknown = [word for word in first if not as_entry[word]]
+            chains = self.lexicon_chains(unknown, lexicon, compounds, min_part, links)
+            for j, word in enumerate(unknown):
+                as_entry[word] = bool(int(chains.found[j]) & ~1)
+        table, weights = {}, {}
+        for word, i in first.items():
+            table[word] = near.strings(i) if known or not as_entry[word] else []
+            if channel is not None:
+                weights[word] = [channel_weight * float(b) for b in near.bits[i][:len(table[word])]]
         unit_bits = None if channel is None else channel.unit / float(ratebulk.CHANNEL_SCALE)
         if boundaries:
-            looked = dict((word, bool(known or near.exact[i] < 0)) for i, word in enumerate(words))
+            looked = dict((word, bool(known or not as_entry[word])) for word in first)
             apart = [word for word in table if looked[word] and len(word) < ratebulk.SPAN_LEN_MAX]
             splits = self.lexicon_splits(apart, lexicon, max_dist=max_dist, min_part=min_part, per_word=per_word)
             for i, word in enumerate(apart):
@@ -1934,6 +2025,16 @@ class Rater(object):
                         table[word].append(string)
                         if channel is not None:
                             weights[word].append(channel_weight * unit_bits * int(dist))
+            if max_parts >= 3:
+                # more than one lost delimiter: the word as 3 .. max_parts exact entries, behind the pairs
+                longer = self.lexicon_chains(apart, lexicon, max_parts, min_part, links=())
+                for i, word in enumerate(apart):
+                    parts = [p for p in range(3, max_parts + 1) if (int(longer.found[i]) >> (p - 1)) & 1]
+                    for string, p in zip(longer.strings(i, joiner, min_parts=3), parts):
+                        if string not in table[word] and len(string) <= ratebulk.SPAN_LEN_MAX:
+                            table[word].append(string)
+                            if channel is not None:
+                                weights[word].append(channel_weight * unit_bits * (p - 1))
         if channel is None:
             edits, prior = ratebatch.word_edits(found, texts, table), None
         else:

@@ -25,7 +25,8 @@ Additional command `lexicon`: the suspect words of every DATA file looked up in 
 first) on the device, and their nearest entries rated against the text around them (Rater.correct_words: suspect_words ->
 lexicon_neighbours -> rescore); output as `rescore`'s, --apply also gives the corrected text.  With --channel FILE (the JSON
 lines of `confusions --counts`) the look-up weighs the learned confusions and their bits enter the choice (Rater.channel).
-With --boundaries lost and spurious spaces are hypotheses too: a word as two entries (Rater.lexicon_splits), two words as one.
+With --boundaries lost and spurious spaces are hypotheses too: a word as two entries (Rater.lexicon_splits), two words as one;
+with --max-parts N a word as up to N entries, and with --compounds N a chain of 2 .. N entries is left alone (Rater.lexicon_chains).
 Additional command `witnesses`: every DATA file aligned with other readings of it (--witness DIR: the file of the same base
 name) on the device, and the readings of the spans where they differ rated against the text around them
 (Rater.merge_witnesses: align -> witness_edits -> rescore); --apply also gives the corrected text.
@@ -617,11 +618,18 @@ def _read_channel(path):
               help='also try word boundaries: a looked-up word as two entries with a space between them ("split"), and a '
                    'looked-up word run together with the word before or after it ("merge"); every record then ends with its kind')
 @click.option('--min-part', default=2, show_default=True, type=click.IntRange(min=1, max=32),
-              help='with --boundaries: each half of a split has at least this many characters')
+              help='with --boundaries or --compounds: each part of a word has at least this many characters')
+@click.option('--compounds', default=0, show_default=True, type=click.IntRange(min=0, max=8),
+              help='a word that is a chain of 2 .. N entries (a compound) counts as an entry and is left alone [0: off]')
+@click.option('--links', default=None,
+              help='with --compounds: linking elements that may stand between two parts, separated by commas (s,es,n); '
+                   'at most 8, of 1 .. 3 characters')
+@click.option('--max-parts', default=2, show_default=True, type=click.IntRange(min=2, max=8),
+              help='with --boundaries: also try a looked-up word as 3 .. N entries with spaces between them ("split")')
 @click.argument('data', nargs=-1, type=click.Path(exists=True, dir_okay=True, file_okay=True))
 def lexicon_(model, lexicon_file, max_dist, per_word, known, streams, precision, k, max_prob, min_rank, min_suspects,
              min_bits_per_char, min_chars, delimiters, left, ahead, min_gain, apply_, channel_file, unit_bits, max_bits,
-             channel_weight, min_count, min_rate, boundaries, min_part, data):
+             channel_weight, min_count, min_rate, boundaries, min_part, compounds, links, max_parts, data):
     """Apply a language model to DATA files, look the words it does not believe up in the word list and
        print one JSON line per file, as `rescore` does: characters and "rescored": one [start, end, written,
        proposed, gain] per word that has candidates -- proposed is the entry that replaces text[start:end],
@@ -636,13 +644,19 @@ def lexicon_(model, lexicon_file, max_dist, per_word, known, streams, precision,
 
        With --boundaries a lost or spurious space is a hypothesis too (--max-dist counts it as one edit), and
        every record has a sixth field: "merge" for a span over two words and the space between them, "split"
-       where the proposal puts a space into the word, "word" otherwise.
+       where the proposal puts a space into the word, "word" otherwise.  With --max-parts N a word may fall
+       into up to N entries ("split" too).  With --compounds N a word that is no entry but a chain of 2 .. N
+       entries, --links between them allowed, is left alone as an entry is.
     """
     from ..lib import windows
     rater = _load(model)
     more = {}
     if boundaries:
-        more.update(boundaries=True, min_part=min_part)
+        more.update(boundaries=True, min_part=min_part, max_parts=max_parts)
+    if compounds:
+        if compounds < 2:
+            raise click.UsageError("--compounds is 0 or 2 .. 8")
+        more.update(compounds=compounds, min_part=min_part, links=tuple(s for s in (links or "").split(",") if s))
     try:
         lexicon = rater.lexicon(_read_lexicon(lexicon_file))
         if channel_file is not None:
