@@ -7,7 +7,8 @@
 // most 64 ids; a query of at most 32 runs the same steps on 32-bit words (the VALU has no 64-bit add or shift: 10.7 against
 // 12.1 ms for 20 000 words against 228 576 entries; KL_LEXICON_NARROW=0 switches it off).  Peq[V] lies in LDS (V * 8 bytes,
 // only the query's own ids are non-zero); an id outside [0, V) on either side never reaches the table: it has no bit and
-// matches nothing.  (The step and the class table are kl_lexicon_myers.h's, shared with kl_lexicon_splits.)
+// matches nothing.  (The step is kl_lexicon_myers.h's; the class table, the query's bounds and Peq are the frame's,
+// kl_lexicon_frame.h, which all four look-ups share.)
 //
 // Every lane then walks whole entries of the length classes max(1, m - max_dist) .. min(64, m + max_dist) -- other lengths
 // cannot be within max_dist --, one character per step from the column-major layout (consecutive lanes read consecutive
@@ -20,7 +21,6 @@
 #include "kl_common.h"
 #include "kl_lexicon_myers.h"
 #include "kl_lexicon_topk.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -68,10 +68,9 @@ __global__ void __launch_bounds__(LEX_THREADS) lexicon_neighbours_kernel(
   __shared__ kl_lex_fold<LEX_WAVES> s_fold;
   const int tid = threadIdx.x;
   const long long q = blockIdx.x;
-  const long long qa = q_off[q], qb = q_off[q + 1];
-  // a query outside the pool, of no ids or of more than 64 is a neighbour of nothing: nothing of it is read
-  const bool none = qa < 0 || qb <= qa || qb > n_q || qb - qa > LEX_LEN_MAX;
-  if (none) {      // (uniform: the whole workgroup leaves)
+  long long qa;
+  int m;
+  if (lex_query_bounds(q_off, q, n_q, 1, qa, m)) {      // a neighbour of nothing (uniform: the whole workgroup leaves)
     if (tid == 0) {
       exact[q] = -1;
       found[q] = 0;
@@ -82,19 +81,7 @@ __global__ void __launch_bounds__(LEX_THREADS) lexicon_neighbours_kernel(
     }
     return;
   }
-  const int m = (int)(qb - qa);
-  for (int v = tid; v < V; v += LEX_THREADS) peq[v] = 0ull;
-  if (tid < m) s_query[tid] = q_pool[qa + tid];
-  __syncthreads();
-  if (tid < m) {
-    // all positions that hold this id write the same word: no atomics
-    const int id = s_query[tid];
-    if (id >= 0 && id < V) {
-      unsigned long long bits = 0ull;
-      for (int j = 0; j < m; ++j) bits |= s_query[j] == id ? 1ull << j : 0ull;
-      peq[id] = bits;
-    }
-  }
+  lex_query_peq<false>(peq, s_query, q_pool, qa, m, V, tid);
   __syncthreads();
 
   unsigned long long best[KL_LEXICON_K_MAX];
@@ -122,26 +109,18 @@ extern "C" int kl_lexicon_neighbours(const int32_t* chars, size_t n_chars, const
                                      const int32_t* q_pool, size_t n_q, const int64_t* q_off, size_t Q, int max_dist, int K,
                                      int32_t* exact, int32_t* found, int32_t* cand, int32_t* dist, void* ws, size_t ws_bytes,
                                      void* stream) {
-  if (!chars || !order || !class_first || !q_off || !exact || !found || !cand || !dist || !ws) return KL_ERR_ARG;
-  if (n_q > 0 && !q_pool) return KL_ERR_ARG;
-  if (V < 1 || V > KL_LEXICON_V_MAX || max_dist < 0 || max_dist > KL_LEXICON_DIST_MAX || K < 1 || K > KL_LEXICON_K_MAX)
-    return KL_ERR_ARG;
-  if (Q < 1 || Q > LEX_MAX_QUERIES || n_q > LEX_MAX_POOL || n_chars > LEX_MAX_POOL) return KL_ERR_ARG;
+  if (!exact || !found || !cand || !dist) return KL_ERR_ARG;
+  if (max_dist < 0 || max_dist > KL_LEXICON_DIST_MAX || K < 1 || K > KL_LEXICON_K_MAX) return KL_ERR_ARG;
   const void* words[] = {chars, order, q_pool, exact, found, cand, dist};
   for (const void* p : words)
     if (lex_misaligned(p, 3)) return KL_ERR_ARG;
-  if (lex_misaligned(q_off, 7) || lex_misaligned(class_first, 7) || lex_misaligned(ws, 7)) return KL_ERR_ARG;
-  // the class table: every address the kernel forms is checked here
   lex_classes cls;
-  if (!lex_classes_checked(class_first, n_chars, cls)) return KL_ERR_ARG;
+  if (lex_arguments_checked(chars, n_chars, order, class_first, V, q_pool, n_q, q_off, Q, ws, cls) != KL_OK) return KL_ERR_ARG;
   if (ws_bytes < kl_lexicon_neighbours_workspace_bytes(Q, K)) return KL_ERR_WORKSPACE;
-  // KL_LEXICON_NARROW=0: the 64-bit pattern word for every query (the A/B switch of tools/bench_lexicon.py)
-  const char* env = getenv("KL_LEXICON_NARROW");
-  const int narrow = !(env && env[0] == '0');
   hipStream_t s = static_cast<hipStream_t>(stream);
   long long* table = reinterpret_cast<long long*>(ws);
   hipLaunchKernelGGL(lexicon_classes_kernel, dim3(1), dim3(2 * KL_WAVE), 0, s, cls, table);
   hipLaunchKernelGGL(lexicon_neighbours_kernel, dim3((unsigned)Q), dim3(LEX_THREADS), 0, s, chars, order, table, V, q_pool,
-                     (long long)n_q, reinterpret_cast<const long long*>(q_off), max_dist, K, narrow, exact, found, cand, dist);
+                     (long long)n_q, reinterpret_cast<const long long*>(q_off), max_dist, K, lex_narrow(), exact, found, cand, dist);
   return hipGetLastError() == hipSuccess ? KL_OK : KL_ERR_LAUNCH;
 }

@@ -5,8 +5,9 @@
 // min_part .. m gives it: with the query's match masks Peq in LDS (kl_lexicon_myers.h), a lane that walks an entry of L ids
 // keeps a word R whose bit a says "the entry could start at a" -- R = low(m - L + 1) at first, R &= Peq[c_j] >> j per entry
 // character, an exact bit-parallel match in place of Myers' column -- and every bit left lowers s_piece[a][L] to the entry's
-// original index with a 32-bit unsigned minimum in LDS.  One workgroup per query, the class table through the workspace as in
-// kl_lexicon_neighbours.  Then a small DP in LDS over the piece table:
+// original index with a 32-bit unsigned minimum in LDS.  One workgroup per query in the frame all four look-ups share
+// (kl_lexicon_frame.h: the class table through the workspace, the query's bounds, Peq, the minimum in LDS).  Then a small DP
+// in LDS over the piece table:
 //
 //   links     where each link stands in the query is one 64-bit mask per link (bit a: the link ends in front of a);
 //   DP        thread b owns column b: E[1][b] = piece(0, b), E[p][b] = the least of max(E[p-1][b'], piece(a, b)) over a
@@ -19,7 +20,6 @@
 #include "keraslm_hip.h"
 #include "kl_common.h"
 #include "kl_lexicon_myers.h"
-#include <stdlib.h>
 #include <string.h>
 
 namespace {
@@ -36,16 +36,6 @@ struct chain_links {
   int len[LINKS_MAX];
   int ids[LINKS_MAX][LINK_LEN_MAX];
 };
-
-__device__ __forceinline__ int lowest(unsigned int w) { return __ffs(w) - 1; }
-__device__ __forceinline__ int lowest(unsigned long long w) { return __ffsll(w) - 1; }
-
-// the least original index of a piece so far, lowered (relaxed, workgroup scope: the barrier behind the pass orders it); an
-// index that is not below what the place already shows is dropped without the atomic -- what it shows can only have gone down
-__device__ __forceinline__ void lower(unsigned int* place, unsigned int index) {
-  if (index < __hip_atomic_load(place, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))
-    __hip_atomic_fetch_min(place, index, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
 
 // a lane's walk over the entries e = tid, tid + LEX_THREADS, .. of the length classes min_part .. m: where an entry of L
 // ids is identical to q[a : a + L], its original index lowers s_piece[a * LEX_LEN_MAX + L - 1]
@@ -73,7 +63,7 @@ __device__ __forceinline__ void walk_pieces(const int* __restrict__ chars, const
         while (R != 0) {
           const int a = lowest(R);      // (a < places <= m - L + 1: inside the table)
           R &= R - 1;
-          lower(&s_piece[a * LEX_LEN_MAX + L - 1], index);
+          lex_lower(&s_piece[a * LEX_LEN_MAX + L - 1], index);
         }
       }
     }
@@ -94,11 +84,10 @@ __global__ void __launch_bounds__(LEX_THREADS) lexicon_chains_kernel(
   __shared__ unsigned int s_from[PARTS_MAX + 1][LEX_LEN_MAX + 1];   // its predecessor: a | (link + 1) << 8
   const int tid = threadIdx.x;
   const long long q = blockIdx.x;
-  const long long qa = q_off[q], qb = q_off[q + 1];
-  // a query outside the pool, of no ids, of more than 64 or shorter than one piece is no chain: nothing of the lexicon is
-  // read for it
-  const bool none = qa < 0 || qb <= qa || qb > n_q || qb - qa > LEX_LEN_MAX || qb - qa < (long long)min_part;
-  if (none) {      // (uniform: the whole workgroup leaves)
+  long long qa;
+  int m;
+  // a query that is none, or shorter than one piece, is no chain: nothing of the lexicon is read for it
+  if (lex_query_bounds(q_off, q, n_q, min_part, qa, m)) {      // (uniform: the whole workgroup leaves)
     if (tid == 0) found[q] = 0;
     if (tid < P) worst[q * P + tid] = -1;
     if (tid < P * P) {
@@ -108,20 +97,8 @@ __global__ void __launch_bounds__(LEX_THREADS) lexicon_chains_kernel(
     }
     return;
   }
-  const int m = (int)(qb - qa);
-  for (int v = tid; v < V; v += LEX_THREADS) peq[v] = 0ull;
   for (int i = tid; i < LEX_LEN_MAX * LEX_LEN_MAX; i += LEX_THREADS) s_piece[i] = NO_PIECE;
-  if (tid < m) s_query[tid] = q_pool[qa + tid];
-  __syncthreads();
-  if (tid < m) {
-    // all positions that hold this id write the same word: no atomics
-    const int id = s_query[tid];
-    if (id >= 0 && id < V) {
-      unsigned long long bits = 0ull;
-      for (int j = 0; j < m; ++j) bits |= s_query[j] == id ? 1ull << j : 0ull;
-      peq[id] = bits;
-    }
-  }
+  lex_query_peq<false>(peq, s_query, q_pool, qa, m, V, tid);
   if (tid < KL_WAVE) {
     // where the links stand, by the first wave: lane a asks whether link l ends in front of a.  (Every index into the
     // argument is a constant: one known at run time only would send it through scratch.)  The links' ids lie in [0, V), so
@@ -229,16 +206,14 @@ extern "C" int kl_lexicon_chains(const int32_t* chars, size_t n_chars, const int
                                  const int32_t* q_pool, size_t n_q, const int64_t* q_off, size_t Q, const int32_t* links,
                                  int n_links, int max_parts, int min_part, int32_t* found, int32_t* worst, int32_t* entry,
                                  int32_t* start, int32_t* link, void* ws, size_t ws_bytes, void* stream) {
-  if (!chars || !order || !class_first || !q_off || !found || !worst || !entry || !start || !link || !ws) return KL_ERR_ARG;
-  if (n_q > 0 && !q_pool) return KL_ERR_ARG;
-  if (V < 1 || V > KL_LEXICON_V_MAX || max_parts < 2 || max_parts > PARTS_MAX || min_part < 1 || min_part > MIN_PART_MAX)
-    return KL_ERR_ARG;
+  if (!found || !worst || !entry || !start || !link) return KL_ERR_ARG;
+  if (max_parts < 2 || max_parts > PARTS_MAX || min_part < 1 || min_part > MIN_PART_MAX) return KL_ERR_ARG;
   if (n_links < 0 || n_links > LINKS_MAX || (n_links > 0 && !links)) return KL_ERR_ARG;
-  if (Q < 1 || Q > LEX_MAX_QUERIES || n_q > LEX_MAX_POOL || n_chars > LEX_MAX_POOL) return KL_ERR_ARG;
   const void* words[] = {chars, order, q_pool, found, worst, entry, start, link, links};
   for (const void* p : words)
     if (lex_misaligned(p, 3)) return KL_ERR_ARG;
-  if (lex_misaligned(q_off, 7) || lex_misaligned(class_first, 7) || lex_misaligned(ws, 7)) return KL_ERR_ARG;
+  lex_classes cls;
+  if (lex_arguments_checked(chars, n_chars, order, class_first, V, q_pool, n_q, q_off, Q, ws, cls) != KL_OK) return KL_ERR_ARG;
   chain_links by_value;
   memset(&by_value, 0, sizeof(by_value));
   by_value.n = n_links;
@@ -252,18 +227,12 @@ extern "C" int kl_lexicon_chains(const int32_t* chars, size_t n_chars, const int
       by_value.ids[l][j] = id;
     }
   }
-  // the class table: every address the kernel forms is checked here
-  lex_classes cls;
-  if (!lex_classes_checked(class_first, n_chars, cls)) return KL_ERR_ARG;
   if (ws_bytes < kl_lexicon_chains_workspace_bytes(Q, max_parts)) return KL_ERR_WORKSPACE;
-  // KL_LEXICON_NARROW=0: the 64-bit pattern word for every query, as in kl_lexicon_neighbours
-  const char* env = getenv("KL_LEXICON_NARROW");
-  const int narrow = !(env && env[0] == '0');
   hipStream_t s = static_cast<hipStream_t>(stream);
   long long* table = reinterpret_cast<long long*>(ws);
   hipLaunchKernelGGL(lexicon_classes_kernel, dim3(1), dim3(2 * KL_WAVE), 0, s, cls, table);
   hipLaunchKernelGGL(lexicon_chains_kernel, dim3((unsigned)Q), dim3(LEX_THREADS), 0, s, chars, order, table, V, q_pool,
-                     (long long)n_q, reinterpret_cast<const long long*>(q_off), by_value, max_parts, min_part, narrow, found,
-                     worst, entry, start, link);
+                     (long long)n_q, reinterpret_cast<const long long*>(q_off), by_value, max_parts, min_part, lex_narrow(),
+                     found, worst, entry, start, link);
   return hipGetLastError() == hipSuccess ? KL_OK : KL_ERR_LAUNCH;
 }

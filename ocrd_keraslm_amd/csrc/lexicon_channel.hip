@@ -6,10 +6,12 @@
 // W[i-s][j-t] + cost_r for every rule r with q[i-s:i] == src_r and e[j-t:j] == tgt_r); the distance is W[m][n].  Myers' bit
 // vectors carry neither weights nor rules, so this is the plain DP over every (query, entry) pair of the reachable classes.
 //
-// Frame as lexicon.hip's: a preparing launch of one workgroup puts the class table into the workspace, then one workgroup per
-// query, every lane walks whole entries of a length class from the column-major layout, the lanes' key lists and the fold are
-// kl_lexicon_topk.h's.  The preparing launch also checks the rules (they lie on the device: the entry point cannot), packs
-// the kept ones into 5 words each -- ids in 16 bits, V <= 4096 --, and reduces them to two prices.
+// The frame all four look-ups share (kl_lexicon_frame.h: the arguments and the class table checked on the host, the query's
+// bounds): a preparing launch of one workgroup puts the class table into the workspace, then one workgroup per query, every
+// lane walks whole entries of a length class from the column-major layout, the lanes' key lists and the fold are
+// kl_lexicon_topk.h's.  No Peq: ids are compared, and the query's ids outside [0, V) are -1 in LDS.  The preparing launch
+// also checks the rules (they lie on the device: the entry point cannot), packs the kept ones into 5 words each -- ids in 16
+// bits, V <= 4096 --, and reduces them to two prices.
 //
 // Which classes.  An entry of m + d ids costs at least |d| times the cheapest price per id of lengthening (d > 0: unit, or
 // cost / (t - s) of a rule with t > s) or of shortening (d < 0, s > t).  |t - s| is 1 .. 4, so 12 * cost / |t - s| is an
@@ -38,33 +40,26 @@
 // from an id, a length or a rule field that has not been range-checked: ids are only ever compared.  No model: no handle.
 #include "keraslm_hip.h"
 #include "kl_common.h"
+#include "kl_lexicon_frame.h"
 #include "kl_lexicon_topk.h"
 
 namespace {
 
 constexpr int CH_THREADS = 256;
 constexpr int CH_WAVES = CH_THREADS / KL_WAVE;
-constexpr int CH_LEN_MAX = 64;
+constexpr int CH_LEN_MAX = LEX_LEN_MAX;
 constexpr int CH_RING_COLS = 5;                  // a rule reaches back four columns
 constexpr int CH_RING = CH_RING_COLS * 33 * 128;      // cells: 128 lanes at m = 32, 64 at m = 64
 constexpr int CH_ACTIVE = 512;                   // (rule, row) pairs of the active list
 constexpr int CH_RULE_WORDS = 5;                 // a packed rule: src (2 words), tgt (2 words), meta
 constexpr int CH_RULES_PER_THREAD = KL_CHANNEL_RULES_MAX / CH_THREADS;
-constexpr size_t MAX_QUERIES = 0x7FFFFFFF;
-constexpr size_t MAX_POOL = (size_t)1 << 40;
 static_assert(CH_RING >= CH_RING_COLS * (CH_LEN_MAX + 1) * KL_WAVE, "one wave walks a query of 64 ids");
 static_assert(KL_CHANNEL_RULES_MAX % CH_THREADS == 0, "every thread settles the same number of rules");
 static_assert(KL_CHANNEL_COST_MAX < (1 << 12), "a cost is 12 bits of a rule's meta word");
 static_assert(KL_LEXICON_V_MAX <= 0xFFF0, "an id is 16 bits of a packed rule, 0xFFFE and 0xFFFF are no ids");
 
-constexpr int CH_CLASSES = CH_LEN_MAX + 2;
-struct ch_classes {
-  long long first[CH_CLASSES];
-  long long base[CH_CLASSES];
-};
-
 // the workspace: the class table, the two prices, the packed rules
-constexpr size_t WS_PRICES = 2 * CH_CLASSES * sizeof(long long);
+constexpr size_t WS_PRICES = 2 * LEX_CLASSES * sizeof(long long);
 constexpr size_t WS_RULES = WS_PRICES + 16;
 
 __device__ __forceinline__ unsigned int meta_s(unsigned int meta) { return (meta >> 12) & 7u; }
@@ -74,17 +69,17 @@ __device__ __forceinline__ int meta_cost(unsigned int meta) { return (int)(meta 
 // One workgroup: the class table (every index into the arguments a constant, as in lexicon.hip), every rule checked and packed
 // -- an ignored rule has meta 0, that is src_len 0 --, and the cheapest price per id of lengthening and of shortening in
 // twelfths of a cost unit.
-__global__ void __launch_bounds__(CH_THREADS) channel_prepare_kernel(const ch_classes cls, const int* __restrict__ rules,
+__global__ void __launch_bounds__(CH_THREADS) channel_prepare_kernel(const lex_classes cls, const int* __restrict__ rules,
                                                                      const int* __restrict__ rule_cost, int R, int V, int unit,
                                                                      long long* __restrict__ table, int* __restrict__ prices,
                                                                      unsigned int* __restrict__ packed) {
   __shared__ int s_up[CH_WAVES], s_down[CH_WAVES];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 #pragma unroll
-  for (int i = 0; i < CH_CLASSES; ++i)
+  for (int i = 0; i < LEX_CLASSES; ++i)
     if (tid == i) {
       table[i] = cls.first[i];
-      table[CH_CLASSES + i] = cls.base[i];
+      table[LEX_CLASSES + i] = cls.base[i];
     }
   int up = 12 * unit, down = 12 * unit;
   for (int r = tid; r < R; r += CH_THREADS) {
@@ -191,10 +186,9 @@ __global__ void __launch_bounds__(CH_THREADS) lexicon_channel_kernel(
   __shared__ kl_lex_fold<CH_WAVES> s_fold;
   const int tid = threadIdx.x;
   const long long q = blockIdx.x;
-  const long long qa = q_off[q], qb = q_off[q + 1];
-  // a query outside the pool, of no ids or of more than 64 is a neighbour of nothing: nothing of it is read
-  const bool none = qa < 0 || qb <= qa || qb > n_q || qb - qa > CH_LEN_MAX;
-  if (none) {      // (uniform: the whole workgroup leaves)
+  long long qa;
+  int m;
+  if (lex_query_bounds(q_off, q, n_q, 1, qa, m)) {      // a neighbour of nothing (uniform: the whole workgroup leaves)
     if (tid == 0) {
       exact[q] = -1;
       found[q] = 0;
@@ -205,7 +199,6 @@ __global__ void __launch_bounds__(CH_THREADS) lexicon_channel_kernel(
     }
     return;
   }
-  const int m = (int)(qb - qa);
   if (tid < m) {
     const int id = q_pool[qa + tid];
     s_query[tid] = id >= 0 && id < V ? id : -1;      // (equals nothing)
@@ -285,7 +278,7 @@ __global__ void __launch_bounds__(CH_THREADS) lexicon_channel_kernel(
     const unsigned short* ring_r = s_ring + tid;
     unsigned short* ring_w = s_ring + tid;
     for (int L = lo; L <= hi; ++L) {
-      const long long at = table[L], n_L = table[L + 1] - at, base = table[CH_CLASSES + L];
+      const long long at = table[L], n_L = table[L + 1] - at, base = table[LEX_CLASSES + L];
       for (long long e = tid; e < n_L; e += lanes) {
         const int* __restrict__ col = chars + base + e;      // id j of the entry: col[j * n_L]
         unsigned int e_lo = 0xFFFEFFFEu, e_hi = 0xFFFEFFFEu;
@@ -354,8 +347,6 @@ __global__ void __launch_bounds__(CH_THREADS) lexicon_channel_kernel(
   kl_lex_fold_out<CH_WAVES>(s_fold, best, least_exact, n_found, K, q, exact, found, cand, cost_out);
 }
 
-inline bool misaligned(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
-
 }  // namespace
 
 extern "C" size_t kl_lexicon_channel_workspace_bytes(size_t Q, int K, int R) {
@@ -369,29 +360,16 @@ extern "C" int kl_lexicon_channel(const int32_t* chars, size_t n_chars, const in
                                   const int32_t* q_pool, size_t n_q, const int64_t* q_off, size_t Q, const int32_t* rules,
                                   const int32_t* rule_cost, int R, int unit, int max_cost, int K, int32_t* exact, int32_t* found,
                                   int32_t* cand, int32_t* cost, void* ws, size_t ws_bytes, void* stream) {
-  if (!chars || !order || !class_first || !q_off || !exact || !found || !cand || !cost || !ws) return KL_ERR_ARG;
-  if (n_q > 0 && !q_pool) return KL_ERR_ARG;
-  if (V < 1 || V > KL_LEXICON_V_MAX || K < 1 || K > KL_LEXICON_K_MAX) return KL_ERR_ARG;
+  if (!exact || !found || !cand || !cost) return KL_ERR_ARG;
+  if (K < 1 || K > KL_LEXICON_K_MAX) return KL_ERR_ARG;
   if (R < 0 || R > KL_CHANNEL_RULES_MAX || unit < 1 || unit > KL_CHANNEL_COST_MAX || max_cost < 0 || max_cost > KL_CHANNEL_COST_MAX)
     return KL_ERR_ARG;
   if (R > 0 && (!rules || !rule_cost)) return KL_ERR_ARG;
-  if (Q < 1 || Q > MAX_QUERIES || n_q > MAX_POOL || n_chars > MAX_POOL) return KL_ERR_ARG;
   const void* words[] = {chars, order, q_pool, exact, found, cand, cost, rules, rule_cost};
   for (const void* p : words)
-    if (misaligned(p, 3)) return KL_ERR_ARG;
-  if (misaligned(q_off, 7) || misaligned(class_first, 7) || misaligned(ws, 7)) return KL_ERR_ARG;
-  // the class table: every address the kernel forms is checked here
-  ch_classes cls;
-  if (class_first[0] != 0 || class_first[1] != 0) return KL_ERR_ARG;
-  for (int L = 1; L <= CH_LEN_MAX + 1; ++L)
-    if (class_first[L] < class_first[L - 1] || class_first[L] > 0x7FFFFFFFll) return KL_ERR_ARG;
-  long long total = 0;      // (at most 64 * 2^31)
-  for (int L = 0; L <= CH_LEN_MAX + 1; ++L) {
-    cls.first[L] = class_first[L];
-    cls.base[L] = total;
-    if (L <= CH_LEN_MAX) total += (long long)L * (class_first[L + 1] - class_first[L]);
-  }
-  if (class_first[CH_LEN_MAX + 1] < 1 || (unsigned long long)total != (unsigned long long)n_chars) return KL_ERR_ARG;
+    if (lex_misaligned(p, 3)) return KL_ERR_ARG;
+  lex_classes cls;
+  if (lex_arguments_checked(chars, n_chars, order, class_first, V, q_pool, n_q, q_off, Q, ws, cls) != KL_OK) return KL_ERR_ARG;
   if (ws_bytes < kl_lexicon_channel_workspace_bytes(Q, K, R)) return KL_ERR_WORKSPACE;
   hipStream_t s = static_cast<hipStream_t>(stream);
   char* bytes = reinterpret_cast<char*>(ws);

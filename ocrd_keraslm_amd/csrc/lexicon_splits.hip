@@ -3,8 +3,9 @@
 // The missing delimiter costs one edit, so each half may lie d = max_dist - 1 edits from its entry.  Pairs of entries are never
 // formed: after Myers' column (kl_lexicon_myers.h) has consumed an entry e of L ids, its vertical deltas hold lev(q[:i], e) for
 // EVERY prefix length i -- D[i] = L + popc(Pv & low(i)) - popc(Mv & low(i)) --, and the same walk with the reversed query over the
-// entry read back to front holds every suffix.  So one workgroup per query, the class table through the workspace as in
-// kl_lexicon_neighbours, and two passes over the length classes max(1, min_part - d) .. min(64, m - min_part + d):
+// entry read back to front holds every suffix.  So one workgroup per query in the frame all four look-ups share
+// (kl_lexicon_frame.h: the class table through the workspace, the query's bounds, Peq, the minimum in LDS), and two passes
+// over the length classes max(1, min_part - d) .. min(64, m - min_part + d):
 //
 //   forward   Peq of the query in LDS; every lane walks whole entries and, after an entry's last character, reads D[i] for the
 //             split points i in [max(min_part, L - d), min(m - min_part, L + d)] -- at most 2d + 1 pairs of popcounts; where
@@ -19,22 +20,11 @@
 #include "keraslm_hip.h"
 #include "kl_common.h"
 #include "kl_lexicon_myers.h"
-#include <stdlib.h>
 
 namespace {
 
 constexpr unsigned long long NO_KEY = ~0ull;
 constexpr int MIN_PART_MAX = LEX_LEN_MAX / 2;      // a larger one leaves no query a split point
-
-__device__ __forceinline__ int ones(unsigned int w) { return __popc(w); }
-__device__ __forceinline__ int ones(unsigned long long w) { return __popcll(w); }
-
-// the least key of a split point so far, lowered (relaxed, workgroup scope: the barrier behind a pass orders it); a key that is
-// not below what the place already shows is dropped without the atomic -- what it shows can only have gone down since
-__device__ __forceinline__ void lower(unsigned long long* place, unsigned long long key) {
-  if (key < __hip_atomic_load(place, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))
-    __hip_atomic_fetch_min(place, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
 
 // a lane's walk over the entries e = tid, tid + LEX_THREADS, .. of every length class that can hold a half of a query of m
 // ids: where the first i ids of the pattern (the query, or with BACK the reversed query against the entry read back to
@@ -70,7 +60,7 @@ __device__ __forceinline__ void walk_halves(const int* __restrict__ chars, const
             index = (unsigned int)order[at + e];
             have = true;
           }
-          lower(&s_best[BACK ? m - i : i], ((unsigned long long)D << 32) | index);
+          lex_lower(&s_best[BACK ? m - i : i], ((unsigned long long)D << 32) | index);
         }
       }
     }
@@ -87,11 +77,10 @@ __global__ void __launch_bounds__(LEX_THREADS) lexicon_splits_kernel(
   __shared__ unsigned long long s_left[LEX_LEN_MAX], s_right[LEX_LEN_MAX];      // by split point s (1 .. 63)
   const int tid = threadIdx.x;
   const long long q = blockIdx.x;
-  const long long qa = q_off[q], qb = q_off[q + 1];
-  // a query outside the pool, of no ids, of more than 64 or too short for two halves has no split point: nothing of the
-  // lexicon is read for it
-  const bool none = qa < 0 || qb <= qa || qb > n_q || qb - qa > LEX_LEN_MAX || qb - qa < 2 * (long long)min_part;
-  if (none) {      // (uniform: the whole workgroup leaves)
+  long long qa;
+  int m;
+  // a query that is none, or too short for two halves, has no split point: nothing of the lexicon is read for it
+  if (lex_query_bounds(q_off, q, n_q, 2 * min_part, qa, m)) {      // (uniform: the whole workgroup leaves)
     if (tid == 0) found[q] = 0;
     if (tid < K) {
       split[q * K + tid] = -1;
@@ -101,24 +90,12 @@ __global__ void __launch_bounds__(LEX_THREADS) lexicon_splits_kernel(
     }
     return;
   }
-  const int m = (int)(qb - qa);
   const int d = max_dist - 1;
-  for (int v = tid; v < V; v += LEX_THREADS) peq[v] = 0ull;
-  if (tid < m) s_query[tid] = q_pool[qa + tid];
   if (tid < LEX_LEN_MAX) {
     s_left[tid] = NO_KEY;
     s_right[tid] = NO_KEY;
   }
-  __syncthreads();
-  if (tid < m) {
-    // all positions that hold this id write the same word: no atomics
-    const int id = s_query[tid];
-    if (id >= 0 && id < V) {
-      unsigned long long bits = 0ull;
-      for (int j = 0; j < m; ++j) bits |= s_query[j] == id ? 1ull << j : 0ull;
-      peq[id] = bits;
-    }
-  }
+  lex_query_peq<false>(peq, s_query, q_pool, qa, m, V, tid);
   __syncthreads();
   const bool w32 = narrow && m <= 32;      // (uniform: a workgroup is one query)
   if (w32)
@@ -126,15 +103,7 @@ __global__ void __launch_bounds__(LEX_THREADS) lexicon_splits_kernel(
   else
     walk_halves<unsigned long long, false>(chars, order, table, peq, V, m, d, min_part, tid, s_left);
   __syncthreads();
-  if (tid < m) {
-    // the reversed query: the same ids hold bits, every one of their words is rewritten
-    const int id = s_query[tid];
-    if (id >= 0 && id < V) {
-      unsigned long long bits = 0ull;
-      for (int j = 0; j < m; ++j) bits |= s_query[m - 1 - j] == id ? 1ull << j : 0ull;
-      peq[id] = bits;
-    }
-  }
+  lex_query_peq<true>(peq, s_query, q_pool, qa, m, V, tid);      // the reversed query: the same ids hold bits
   __syncthreads();
   if (w32)
     walk_halves<unsigned int, true>(chars, order, table, peq, V, m, d, min_part, tid, s_right);
@@ -192,28 +161,20 @@ extern "C" int kl_lexicon_splits(const int32_t* chars, size_t n_chars, const int
                                  const int32_t* q_pool, size_t n_q, const int64_t* q_off, size_t Q, int max_dist, int min_part,
                                  int K, int32_t* found, int32_t* split, int32_t* left, int32_t* right, int32_t* dist, void* ws,
                                  size_t ws_bytes, void* stream) {
-  if (!chars || !order || !class_first || !q_off || !found || !split || !left || !right || !dist || !ws) return KL_ERR_ARG;
-  if (n_q > 0 && !q_pool) return KL_ERR_ARG;
-  if (V < 1 || V > KL_LEXICON_V_MAX || max_dist < 1 || max_dist > KL_LEXICON_DIST_MAX || K < 1 || K > KL_LEXICON_K_MAX)
-    return KL_ERR_ARG;
+  if (!found || !split || !left || !right || !dist) return KL_ERR_ARG;
+  if (max_dist < 1 || max_dist > KL_LEXICON_DIST_MAX || K < 1 || K > KL_LEXICON_K_MAX) return KL_ERR_ARG;
   if (min_part < 1 || min_part > MIN_PART_MAX) return KL_ERR_ARG;
-  if (Q < 1 || Q > LEX_MAX_QUERIES || n_q > LEX_MAX_POOL || n_chars > LEX_MAX_POOL) return KL_ERR_ARG;
   const void* words[] = {chars, order, q_pool, found, split, left, right, dist};
   for (const void* p : words)
     if (lex_misaligned(p, 3)) return KL_ERR_ARG;
-  if (lex_misaligned(q_off, 7) || lex_misaligned(class_first, 7) || lex_misaligned(ws, 7)) return KL_ERR_ARG;
-  // the class table: every address the kernel forms is checked here
   lex_classes cls;
-  if (!lex_classes_checked(class_first, n_chars, cls)) return KL_ERR_ARG;
+  if (lex_arguments_checked(chars, n_chars, order, class_first, V, q_pool, n_q, q_off, Q, ws, cls) != KL_OK) return KL_ERR_ARG;
   if (ws_bytes < kl_lexicon_splits_workspace_bytes(Q, K)) return KL_ERR_WORKSPACE;
-  // KL_LEXICON_NARROW=0: the 64-bit pattern word for every query, as in kl_lexicon_neighbours
-  const char* env = getenv("KL_LEXICON_NARROW");
-  const int narrow = !(env && env[0] == '0');
   hipStream_t s = static_cast<hipStream_t>(stream);
   long long* table = reinterpret_cast<long long*>(ws);
   hipLaunchKernelGGL(lexicon_classes_kernel, dim3(1), dim3(2 * KL_WAVE), 0, s, cls, table);
   hipLaunchKernelGGL(lexicon_splits_kernel, dim3((unsigned)Q), dim3(LEX_THREADS), 0, s, chars, order, table, V, q_pool,
-                     (long long)n_q, reinterpret_cast<const long long*>(q_off), max_dist, min_part, K, narrow, found, split, left,
-                     right, dist);
+                     (long long)n_q, reinterpret_cast<const long long*>(q_off), max_dist, min_part, K, lex_narrow(), found, split,
+                     left, right, dist);
   return hipGetLastError() == hipSuccess ? KL_OK : KL_ERR_LAUNCH;
 }

@@ -759,6 +759,37 @@ class HipLM:
                 call(m, out)
         return out
 
+    def _lexicon_fits(self, method, chars_d, order_d, class_first, q_pool_d, q_off_d):
+        """What `lexicon_neighbours`, `lexicon_splits`, `lexicon_chains` and `lexicon_channel` ask of the lexicon and the queries
+        before anything else, hipabi.KlError with `method` in front otherwise: chars_d, order_d, q_pool_d int32 and q_off_d int64
+        [Q + 1], of one dimension, contiguous, on the device; class_first int64 [66] on the host.  Returns class_first as a
+        contiguous array and Q."""
+        torch = self.torch
+        tensors = (chars_d, order_d, q_pool_d, q_off_d)
+        if ([t.dtype for t in tensors] != [torch.int32, torch.int32, torch.int32, torch.int64] or any(t.dim() != 1 for t in tensors)
+                or q_off_d.numel() < 2 or not all(t.is_contiguous() and t.is_cuda for t in tensors)):
+            raise hipabi.KlError("%s: chars, order and q_pool int32, q_off int64 [Q + 1], contiguous, on the device" % method)
+        class_first = np.ascontiguousarray(class_first, dtype=np.int64).reshape(-1)
+        if len(class_first) != 66 or order_d.numel() != int(class_first[-1]):
+            raise hipabi.KlError("%s: class_first int64 [66] on the host, its last value the size of order" % method)
+        return class_first, q_off_d.numel() - 1
+
+    def _lexicon_call(self, entry, ws_name, ws_bytes, lexicon_args, middle, shapes):
+        """The launch of the four lexicon look-ups: allocates int32 outputs of `shapes`, takes the scratch kept under ws_name at
+        ws_bytes, and calls `entry` with the nine arguments lexicon_args stands for (chars_d, order_d, class_first, V, q_pool_d,
+        q_off_d and the sizes), then middle (the entry point's own), then the outputs, the workspace and the stream.  Returns
+        the DEVICE tensors."""
+        torch = self.torch
+        chars_d, order_d, class_first, V, q_pool_d, q_off_d = lexicon_args
+        with self._launch():
+            ws = self._scratch(ws_name, ws_bytes)
+            out = tuple(torch.empty(shape, dtype=torch.int32, device=self.device) for shape in shapes)
+            hipabi.check(entry(
+                _ptr(chars_d), chars_d.numel(), _ptr(order_d), class_first.ctypes.data, V, _ptr(q_pool_d), q_pool_d.numel(),
+                _ptr(q_off_d), q_off_d.numel() - 1, *middle, *([_ptr(t) for t in out] + [_ptr(ws), ws.numel(), self._stream()])),
+                entry.__name__)
+        return out
+
     def lexicon_neighbours(self, chars_d, order_d, class_first, V, q_pool_d, q_off_d, max_dist, K):
         """kl_lexicon_neighbours: the entries of a lexicon within max_dist edits of Q query words.  chars_d int32 and order_d
         int32 [N'] are DEVICE copies of what `ratebulk.lexicon_layout_host` built, class_first its int64 [66] on the HOST (every
@@ -766,52 +797,24 @@ class HipLM:
         equal only within [0, V).  Returns the DEVICE tensors (exact int32 [Q], found int32 [Q], cand int32 [Q, K], dist int32
         [Q, K]); the statement is ratebulk.lexicon_neighbours_host.  hipabi.KlError for what the entry point rejects.  No
         synchronisation."""
-        torch = self.torch
-        tensors = (chars_d, order_d, q_pool_d, q_off_d)
-        if ([t.dtype for t in tensors] != [torch.int32, torch.int32, torch.int32, torch.int64] or any(t.dim() != 1 for t in tensors)
-                or q_off_d.numel() < 2 or not all(t.is_contiguous() and t.is_cuda for t in tensors)):
-            raise hipabi.KlError("lexicon_neighbours: chars, order and q_pool int32, q_off int64 [Q + 1], contiguous, on the device")
-        class_first = np.ascontiguousarray(class_first, dtype=np.int64).reshape(-1)
-        if len(class_first) != 66 or order_d.numel() != int(class_first[-1]):
-            raise hipabi.KlError("lexicon_neighbours: class_first int64 [66] on the host, its last value the size of order")
+        class_first, Q = self._lexicon_fits("lexicon_neighbours", chars_d, order_d, class_first, q_pool_d, q_off_d)
         V, max_dist, K = int(V), int(max_dist), int(K)
-        Q = q_off_d.numel() - 1
-        dev = self.device
-        with self._launch():
-            ws = self._scratch("_lexicon_ws", self.lib.kl_lexicon_neighbours_workspace_bytes(Q, K))
-            out = (torch.empty(Q, dtype=torch.int32, device=dev), torch.empty(Q, dtype=torch.int32, device=dev),
-                   torch.empty((Q, max(K, 0)), dtype=torch.int32, device=dev), torch.empty((Q, max(K, 0)), dtype=torch.int32, device=dev))
-            hipabi.check(self.lib.kl_lexicon_neighbours(
-                _ptr(chars_d), chars_d.numel(), _ptr(order_d), class_first.ctypes.data, V, _ptr(q_pool_d), q_pool_d.numel(),
-                _ptr(q_off_d), Q, max_dist, K, *([_ptr(t) for t in out] + [_ptr(ws), ws.numel(), self._stream()])),
-                "kl_lexicon_neighbours")
-        return out
+        return self._lexicon_call(self.lib.kl_lexicon_neighbours, "_lexicon_ws",
+                                  self.lib.kl_lexicon_neighbours_workspace_bytes(Q, K),
+                                  (chars_d, order_d, class_first, V, q_pool_d, q_off_d), (max_dist, K),
+                                  [Q, Q, (Q, max(K, 0)), (Q, max(K, 0))])
 
     def lexicon_splits(self, chars_d, order_d, class_first, V, q_pool_d, q_off_d, max_dist, min_part, K):
         """kl_lexicon_splits: the places at which Q query words fall into two entries of a lexicon, a lost delimiter counted as
         one of max_dist edits and every half of at least min_part ids.  The lexicon, V and the queries as in
         `lexicon_neighbours`.  Returns the DEVICE tensors (found int32 [Q], split, left, right, dist int32 [Q, K]); the statement
         is ratebulk.lexicon_splits_host.  hipabi.KlError for what the entry point rejects.  No synchronisation."""
-        torch = self.torch
-        tensors = (chars_d, order_d, q_pool_d, q_off_d)
-        if ([t.dtype for t in tensors] != [torch.int32, torch.int32, torch.int32, torch.int64] or any(t.dim() != 1 for t in tensors)
-                or q_off_d.numel() < 2 or not all(t.is_contiguous() and t.is_cuda for t in tensors)):
-            raise hipabi.KlError("lexicon_splits: chars, order and q_pool int32, q_off int64 [Q + 1], contiguous, on the device")
-        class_first = np.ascontiguousarray(class_first, dtype=np.int64).reshape(-1)
-        if len(class_first) != 66 or order_d.numel() != int(class_first[-1]):
-            raise hipabi.KlError("lexicon_splits: class_first int64 [66] on the host, its last value the size of order")
+        class_first, Q = self._lexicon_fits("lexicon_splits", chars_d, order_d, class_first, q_pool_d, q_off_d)
         V, max_dist, min_part, K = int(V), int(max_dist), int(min_part), int(K)
-        Q = q_off_d.numel() - 1
-        dev = self.device
-        with self._launch():
-            ws = self._scratch("_lexicon_splits_ws", self.lib.kl_lexicon_splits_workspace_bytes(Q, K))
-            out = (torch.empty(Q, dtype=torch.int32, device=dev),) + tuple(
-                torch.empty((Q, max(K, 0)), dtype=torch.int32, device=dev) for _ in range(4))
-            hipabi.check(self.lib.kl_lexicon_splits(
-                _ptr(chars_d), chars_d.numel(), _ptr(order_d), class_first.ctypes.data, V, _ptr(q_pool_d), q_pool_d.numel(),
-                _ptr(q_off_d), Q, max_dist, min_part, K, *([_ptr(t) for t in out] + [_ptr(ws), ws.numel(), self._stream()])),
-                "kl_lexicon_splits")
-        return out
+        return self._lexicon_call(self.lib.kl_lexicon_splits, "_lexicon_splits_ws",
+                                  self.lib.kl_lexicon_splits_workspace_bytes(Q, K),
+                                  (chars_d, order_d, class_first, V, q_pool_d, q_off_d), (max_dist, min_part, K),
+                                  [Q] + [(Q, max(K, 0))] * 4)
 
     def lexicon_chains(self, chars_d, order_d, class_first, V, q_pool_d, q_off_d, links, max_parts, min_part):
         """kl_lexicon_chains: Q query words as chains of up to P = max_parts exact entries of a lexicon, every piece of at
@@ -820,31 +823,18 @@ class HipLM:
         queries as in `lexicon_neighbours`.  Returns the DEVICE tensors (found int32 [Q], worst int32 [Q, P], entry, start,
         link int32 [Q, P, P]); the statement is ratebulk.lexicon_chains_host.  hipabi.KlError for what the entry point
         rejects.  No synchronisation."""
-        torch = self.torch
-        tensors = (chars_d, order_d, q_pool_d, q_off_d)
-        if ([t.dtype for t in tensors] != [torch.int32, torch.int32, torch.int32, torch.int64] or any(t.dim() != 1 for t in tensors)
-                or q_off_d.numel() < 2 or not all(t.is_contiguous() and t.is_cuda for t in tensors)):
-            raise hipabi.KlError("lexicon_chains: chars, order and q_pool int32, q_off int64 [Q + 1], contiguous, on the device")
-        class_first = np.ascontiguousarray(class_first, dtype=np.int64).reshape(-1)
-        if len(class_first) != 66 or order_d.numel() != int(class_first[-1]):
-            raise hipabi.KlError("lexicon_chains: class_first int64 [66] on the host, its last value the size of order")
+        class_first, Q = self._lexicon_fits("lexicon_chains", chars_d, order_d, class_first, q_pool_d, q_off_d)
         V, P, min_part = int(V), int(max_parts), int(min_part)
         try:
             links = np.ascontiguousarray(ratebulk.lexicon_links_host(links, V), dtype=np.int32)
         except ValueError as err:
             raise hipabi.KlError(str(err))
-        Q = q_off_d.numel() - 1
-        dev = self.device
         room = min(max(P, 0), hipabi.KL_LEXICON_PARTS_MAX)      # (an out-of-range P is the entry point's to refuse)
-        with self._launch():
-            ws = self._scratch("_lexicon_chains_ws", self.lib.kl_lexicon_chains_workspace_bytes(Q, P))
-            out = (torch.empty(Q, dtype=torch.int32, device=dev), torch.empty((Q, room), dtype=torch.int32, device=dev)) + tuple(
-                torch.empty((Q, room, room), dtype=torch.int32, device=dev) for _ in range(3))
-            hipabi.check(self.lib.kl_lexicon_chains(
-                _ptr(chars_d), chars_d.numel(), _ptr(order_d), class_first.ctypes.data, V, _ptr(q_pool_d), q_pool_d.numel(),
-                _ptr(q_off_d), Q, links.ctypes.data if len(links) else None, len(links), P, min_part,
-                *([_ptr(t) for t in out] + [_ptr(ws), ws.numel(), self._stream()])), "kl_lexicon_chains")
-        return out
+        return self._lexicon_call(self.lib.kl_lexicon_chains, "_lexicon_chains_ws",
+                                  self.lib.kl_lexicon_chains_workspace_bytes(Q, P),
+                                  (chars_d, order_d, class_first, V, q_pool_d, q_off_d),
+                                  (links.ctypes.data if len(links) else None, len(links), P, min_part),
+                                  [Q, (Q, room)] + [(Q, room, room)] * 3)
 
     def lexicon_channel(self, chars_d, order_d, class_first, V, q_pool_d, q_off_d, rules_d, rule_cost_d, unit, max_cost, K):
         """kl_lexicon_channel: the entries of a lexicon within max_cost of Q query words in the weighted distance of a
@@ -854,13 +844,7 @@ class HipLM:
         int32 [Q, K]); the statement is ratebulk.lexicon_channel_host.  hipabi.KlError for what the entry point rejects.  No
         synchronisation."""
         torch = self.torch
-        tensors = (chars_d, order_d, q_pool_d, q_off_d)
-        if ([t.dtype for t in tensors] != [torch.int32, torch.int32, torch.int32, torch.int64] or any(t.dim() != 1 for t in tensors)
-                or q_off_d.numel() < 2 or not all(t.is_contiguous() and t.is_cuda for t in tensors)):
-            raise hipabi.KlError("lexicon_channel: chars, order and q_pool int32, q_off int64 [Q + 1], contiguous, on the device")
-        class_first = np.ascontiguousarray(class_first, dtype=np.int64).reshape(-1)
-        if len(class_first) != 66 or order_d.numel() != int(class_first[-1]):
-            raise hipabi.KlError("lexicon_channel: class_first int64 [66] on the host, its last value the size of order")
+        class_first, Q = self._lexicon_fits("lexicon_channel", chars_d, order_d, class_first, q_pool_d, q_off_d)
         R = 0
         if rules_d is not None or rule_cost_d is not None:
             both = (rules_d, rule_cost_d)
@@ -870,17 +854,11 @@ class HipLM:
                 raise hipabi.KlError("lexicon_channel: rules int32 [R, 10] and rule_cost int32 [R], contiguous, on the device")
             R = int(rule_cost_d.numel())
         V, unit, max_cost, K = int(V), int(unit), int(max_cost), int(K)
-        Q = q_off_d.numel() - 1
-        dev = self.device
-        with self._launch():
-            ws = self._scratch("_lexicon_channel_ws", self.lib.kl_lexicon_channel_workspace_bytes(Q, K, R))
-            out = (torch.empty(Q, dtype=torch.int32, device=dev), torch.empty(Q, dtype=torch.int32, device=dev),
-                   torch.empty((Q, max(K, 0)), dtype=torch.int32, device=dev), torch.empty((Q, max(K, 0)), dtype=torch.int32, device=dev))
-            hipabi.check(self.lib.kl_lexicon_channel(
-                _ptr(chars_d), chars_d.numel(), _ptr(order_d), class_first.ctypes.data, V, _ptr(q_pool_d), q_pool_d.numel(),
-                _ptr(q_off_d), Q, _ptr(rules_d) if R else None, _ptr(rule_cost_d) if R else None, R, unit, max_cost, K,
-                *([_ptr(t) for t in out] + [_ptr(ws), ws.numel(), self._stream()])), "kl_lexicon_channel")
-        return out
+        return self._lexicon_call(self.lib.kl_lexicon_channel, "_lexicon_channel_ws",
+                                  self.lib.kl_lexicon_channel_workspace_bytes(Q, K, R),
+                                  (chars_d, order_d, class_first, V, q_pool_d, q_off_d),
+                                  (_ptr(rules_d) if R else None, _ptr(rule_cost_d) if R else None, R, unit, max_cost, K),
+                                  [Q, Q, (Q, max(K, 0)), (Q, max(K, 0))])
 
     def _hypothesis_fits(self, source, own):
         """Whether the tensors of `variant_windows`, `prefix_windows` or `span_windows` are as the call's message says:

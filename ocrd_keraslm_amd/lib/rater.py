@@ -1757,6 +1757,35 @@ class Rater(object):
             raise ValueError("%s: the lexicon was not built by this rater's `lexicon`, or the mapping has changed since" % method)
         return max_dist, per_word
 
+    def _lexicon_lookup(self, words, lexicon, blank, method, on_device, on_host):
+        """The sequence `lexicon_neighbours`, `lexicon_splits` and `lexicon_chains` share: the words normalised, made unique
+        and encoded, offsets and ids uploaded in ONE buffer, on_device(lm, chars_d, order_d, q_pool_d, q_off_d) called for
+        the DEVICE tensors of the look-up ([Q] or [Q, ..] int32 each) -- on an engine without `method` (the tests' CPU double)
+        on_host(pool, q_off) for the arrays of its statement --, these laid side by side as one int32 [Q, width] table,
+        downloaded ONCE and spread back over the duplicates.  No words, or a lexicon without an entry: every row is `blank`
+        and nothing is launched.  Returns the table in input order."""
+        words = [windows.normalize(w) for w in words]
+        slot = {}
+        for w in words:
+            slot.setdefault(w, len(slot))
+        unique = list(slot)
+        Q = len(unique)
+        out = np.tile(np.asarray(blank, dtype=np.int32), (Q, 1))
+        if Q and len(lexicon):
+            pool = windows.encode("".join(unique), self.mapping[0]).astype(np.int32)
+            q_off = np.concatenate([[0], np.cumsum([len(w) for w in unique])]).astype(np.int64)
+            lm = self.model
+            if hasattr(lm, method):
+                torch = lm.torch
+                chars_d, order_d = lexicon.on_device(lm)
+                both = torch.from_numpy(np.concatenate([q_off.view(np.int32), pool])).to(lm.device)
+                res = on_device(lm, chars_d, order_d, both[2 * (Q + 1):], both[:2 * (Q + 1)].view(torch.int64))
+                out = _np(torch.cat([t.reshape(Q, -1) for t in res], dim=1))
+            else:
+                out = np.concatenate([a.reshape(Q, -1) for a in on_host(pool, q_off)], axis=1)
+        rows = np.asarray([slot[w] for w in words], dtype=np.int64)
+        return out[rows] if len(rows) else out[:0]
+
     def lexicon_neighbours(self, words, lexicon, max_dist=2, per_word=8, channel=None, max_bits=12.0):
         '''Which entries of the lexicon could these words have been?  Returns a ratebatch.Neighbours in input order: per word
         `exact` (its own index in `lexicon.words`, -1: not an entry), `found` (how many entries lie within 1 .. max_dist
@@ -1780,39 +1809,19 @@ class Rater(object):
         assert self.status > 1
         max_dist, K = self._lexicon_request("lexicon_neighbours", lexicon, max_dist, per_word)
         max_cost = None if channel is None else self._channel_request("lexicon_neighbours", channel, max_bits)
-        words = [windows.normalize(w) for w in words]
-        slot = {}
-        for w in words:
-            slot.setdefault(w, len(slot))
-        unique = list(slot)
-        Q = len(unique)
-        out = np.full((Q, 2 + 2 * K), -1, dtype=np.int32)      # (exact, found, index [K], dist [K] per distinct word)
-        out[:, 1] = 0
-        if Q and len(lexicon):
-            pool = windows.encode("".join(unique), self.mapping[0]).astype(np.int32)
-            q_off = np.concatenate([[0], np.cumsum([len(w) for w in unique])]).astype(np.int64)
-            lm = self.model
-            if hasattr(lm, 'lexicon_channel' if channel is not None else 'lexicon_neighbours'):
-                torch = lm.torch
-                chars_d, order_d = lexicon.on_device(lm)
-                both = torch.from_numpy(np.concatenate([q_off.view(np.int32), pool])).to(lm.device)
-                if channel is not None:
-                    res = lm.lexicon_channel(chars_d, order_d, lexicon.class_first, self.voc_size, both[2 * (Q + 1):],
-                                             both[:2 * (Q + 1)].view(torch.int64), *channel.on_device(lm), channel.unit, max_cost, K)
-                else:
-                    res = lm.lexicon_neighbours(chars_d, order_d, lexicon.class_first, self.voc_size, both[2 * (Q + 1):],
-                                                both[:2 * (Q + 1)].view(torch.int64), max_dist, K)
-                out = _np(torch.cat([res[0][:, None], res[1][:, None], res[2], res[3]], dim=1))
-            elif channel is not None:
-                res = ratebulk.lexicon_channel_host(pool, q_off, lexicon.chars, lexicon.order, lexicon.class_first, self.voc_size,
-                                                    channel.rules, channel.cost, channel.unit, max_cost, K)
-                out = np.concatenate([res[0][:, None], res[1][:, None], res[2], res[3]], axis=1)
-            else:
-                res = ratebulk.lexicon_neighbours_host(pool, q_off, lexicon.chars, lexicon.order, lexicon.class_first,
-                                                       self.voc_size, max_dist, K)
-                out = np.concatenate([res[0][:, None], res[1][:, None], res[2], res[3]], axis=1)
-        rows = np.asarray([slot[w] for w in words], dtype=np.int64)
-        out = out[rows] if len(rows) else out[:0]
+        V, lex = self.voc_size, (lexicon.chars, lexicon.order, lexicon.class_first)
+        if channel is None:
+            on_device = lambda lm, chars_d, order_d, q_pool_d, q_off_d: lm.lexicon_neighbours(
+                chars_d, order_d, lexicon.class_first, V, q_pool_d, q_off_d, max_dist, K)
+            on_host = lambda pool, q_off: ratebulk.lexicon_neighbours_host(pool, q_off, *lex, V, max_dist, K)
+        else:
+            on_device = lambda lm, chars_d, order_d, q_pool_d, q_off_d: lm.lexicon_channel(
+                chars_d, order_d, lexicon.class_first, V, q_pool_d, q_off_d, *channel.on_device(lm), channel.unit, max_cost, K)
+            on_host = lambda pool, q_off: ratebulk.lexicon_channel_host(pool, q_off, *lex, V, channel.rules, channel.cost,
+                                                                        channel.unit, max_cost, K)
+        # (exact, found, index [K], dist [K] per distinct word)
+        out = self._lexicon_lookup(words, lexicon, [-1, 0] + [-1] * (2 * K), 'lexicon_neighbours' if channel is None else
+                                   'lexicon_channel', on_device, on_host)
         dist = out[:, 2 + K:].copy()
         bits = None if channel is None else np.where(dist >= 0, dist / float(ratebulk.CHANNEL_SCALE), np.nan)
         return ratebatch.Neighbours(lexicon, out[:, 0].copy(), out[:, 1].copy(), out[:, 2:2 + K].copy(), dist, bits)
@@ -1838,31 +1847,13 @@ class Rater(object):
         if max_dist < 1 or not 1 <= min_part <= ratebulk.LEXICON_MIN_PART_MAX:
             raise ValueError("lexicon_splits: max_dist in 1 .. %d and min_part in 1 .. %d (got %d, %d)"
                              % (ratebulk.LEXICON_DIST_MAX, ratebulk.LEXICON_MIN_PART_MAX, max_dist, min_part))
-        words = [windows.normalize(w) for w in words]
-        slot = {}
-        for w in words:
-            slot.setdefault(w, len(slot))
-        unique = list(slot)
-        Q = len(unique)
-        out = np.full((Q, 1 + 4 * K), -1, dtype=np.int32)      # (found, at [K], left [K], right [K], dist [K] per distinct word)
-        out[:, 0] = 0
-        if Q and len(lexicon):
-            pool = windows.encode("".join(unique), self.mapping[0]).astype(np.int32)
-            q_off = np.concatenate([[0], np.cumsum([len(w) for w in unique])]).astype(np.int64)
-            lm = self.model
-            if hasattr(lm, 'lexicon_splits'):
-                torch = lm.torch
-                chars_d, order_d = lexicon.on_device(lm)
-                both = torch.from_numpy(np.concatenate([q_off.view(np.int32), pool])).to(lm.device)
-                res = lm.lexicon_splits(chars_d, order_d, lexicon.class_first, self.voc_size, both[2 * (Q + 1):],
-                                        both[:2 * (Q + 1)].view(torch.int64), max_dist, min_part, K)
-                out = _np(torch.cat([res[0][:, None]] + list(res[1:]), dim=1))
-            else:
-                res = ratebulk.lexicon_splits_host(pool, q_off, lexicon.chars, lexicon.order, lexicon.class_first, self.voc_size,
-                                                   max_dist, min_part, K)
-                out = np.concatenate([res[0][:, None]] + list(res[1:]), axis=1)
-        rows = np.asarray([slot[w] for w in words], dtype=np.int64)
-        out = out[rows] if len(rows) else out[:0]
+        V, lex = self.voc_size, (lexicon.chars, lexicon.order, lexicon.class_first)
+        # (found, at [K], left [K], right [K], dist [K] per distinct word)
+        out = self._lexicon_lookup(
+            words, lexicon, [0] + [-1] * (4 * K), 'lexicon_splits',
+            lambda lm, chars_d, order_d, q_pool_d, q_off_d: lm.lexicon_splits(chars_d, order_d, lexicon.class_first, V, q_pool_d,
+                                                                              q_off_d, max_dist, min_part, K),
+            lambda pool, q_off: ratebulk.lexicon_splits_host(pool, q_off, *lex, V, max_dist, min_part, K))
         return ratebatch.Splits(lexicon, out[:, 0].copy(), *(out[:, 1 + f * K:1 + (f + 1) * K].copy() for f in range(4)))
 
     def _chain_links(self, method, links):
@@ -1898,31 +1889,13 @@ class Rater(object):
             raise ValueError("lexicon_chains: max_parts in 2 .. %d and min_part in 1 .. %d (got %d, %d)"
                              % (ratebulk.LEXICON_PARTS_MAX, ratebulk.LEXICON_MIN_PART_MAX, P, min_part))
         links, link_ids = self._chain_links("lexicon_chains", links)
-        words = [windows.normalize(w) for w in words]
-        slot = {}
-        for w in words:
-            slot.setdefault(w, len(slot))
-        unique = list(slot)
-        Q = len(unique)
-        out = np.full((Q, 1 + P + 3 * P * P), -1, dtype=np.int32)      # (found, worst [P], entry, start, link [P, P] per distinct word)
-        out[:, 0] = 0
-        if Q and len(lexicon):
-            pool = windows.encode("".join(unique), self.mapping[0]).astype(np.int32)
-            q_off = np.concatenate([[0], np.cumsum([len(w) for w in unique])]).astype(np.int64)
-            lm = self.model
-            if hasattr(lm, 'lexicon_chains'):
-                torch = lm.torch
-                chars_d, order_d = lexicon.on_device(lm)
-                both = torch.from_numpy(np.concatenate([q_off.view(np.int32), pool])).to(lm.device)
-                res = lm.lexicon_chains(chars_d, order_d, lexicon.class_first, self.voc_size, both[2 * (Q + 1):],
-                                        both[:2 * (Q + 1)].view(torch.int64), link_ids, P, min_part)
-                out = _np(torch.cat([res[0][:, None]] + [t.reshape(Q, -1) for t in res[1:]], dim=1))
-            else:
-                res = ratebulk.lexicon_chains_host(pool, q_off, lexicon.chars, lexicon.order, lexicon.class_first, self.voc_size,
-                                                   link_ids, P, min_part)
-                out = np.concatenate([res[0][:, None]] + [a.reshape(Q, -1) for a in res[1:]], axis=1)
-        rows = np.asarray([slot[w] for w in words], dtype=np.int64)
-        out = out[rows] if len(rows) else out[:0]
+        V, lex = self.voc_size, (lexicon.chars, lexicon.order, lexicon.class_first)
+        # (found, worst [P], entry, start, link [P, P] per distinct word)
+        out = self._lexicon_lookup(
+            words, lexicon, [0] + [-1] * (P + 3 * P * P), 'lexicon_chains',
+            lambda lm, chars_d, order_d, q_pool_d, q_off_d: lm.lexicon_chains(chars_d, order_d, lexicon.class_first, V, q_pool_d,
+                                                                              q_off_d, link_ids, P, min_part),
+            lambda pool, q_off: ratebulk.lexicon_chains_host(pool, q_off, *lex, V, link_ids, P, min_part))
         cube = lambda f: out[:, 1 + P + f * P * P:1 + P + (f + 1) * P * P].reshape(-1, P, P).copy()
         return ratebatch.Chains(lexicon, out[:, 0].copy(), out[:, 1:1 + P].copy(), cube(0), cube(1), cube(2), links)
 
